@@ -19,12 +19,17 @@ DESIGN section 6).
 No torch anywhere: ranks / addresses come from the environment `python -m torch.distributed.run` exports, the RCCL
 unique id travels over a small TCP side channel (pyhybridcontrol_amd.batch.TcpRendezvous).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel k_solve) and
-`cpu_baseline` (the C oracle and scipy's HiGHS on a bounded sample: one thread and every core this container may use) added, plus the
-exact-gap (1e-6) leg -- with sub-tree hand-off and, for continuity, in one pass -- checked against the committed HiGHS optima, and the
-same hand-off at the bench's own contract.  Order of the run: CPU leg (before the first HIP call: its HiGHS pool forks), exact leg,
-hand-off leg, staging, warm-up + timed steps, reference steps, queue-order check, closed loop (24 steps, MIP start from the shifted plan),
-condensing.  Progress lines go to stderr.
+Prints ONE JSON line on rank 0: `metric`, `value` (agent-solves/s over the K timed steps), `unit`, `higher_is_better`, `dtype`, `ms_per_step`
+(milliseconds of one timed step) and a `config` that describes the workload and the timed region.  A plain run does nothing else: set-up,
+staging, warm-up + timed steps, the result line.  `--dump-outputs DIR` writes what the last timed step computed (dump_outputs) after the
+timed region.
+
+`--full` adds every other leg: `roofline` (dominant kernel k_solve) and `cpu_baseline` (the C oracle and scipy's HiGHS on a bounded sample:
+one thread and every core this container may use), the exact-gap (1e-6) leg -- with sub-tree hand-off and, for continuity, in one pass --
+checked against the committed HiGHS optima, and the same hand-off at the bench's own contract.  Order of a --full run: CPU leg (before the
+first HIP call: its HiGHS pool forks), exact leg, hand-off leg, staging, warm-up + timed steps, fixed-cost steps, reference steps,
+queue-order check, closed loop (24 steps, MIP start from the shifted plan), single-instance / MIQP / cfg5 legs, condensing.  Progress lines
+go to stderr.
 """
 import argparse
 import json
@@ -74,7 +79,7 @@ def parse_kwargs(text):
     return out
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
@@ -85,6 +90,11 @@ def parse():
                     "(micro_grid_control_simulation.py:232 MIPGap=1e-2)")
     ap.add_argument("--node-limit", type=int, default=800, help="per-instance node limit (stands in for the reference's TimeLimit)")
     ap.add_argument("--pivot-limit", type=int, default=40000, help="per-instance simplex iteration limit")
+    ap.add_argument("--full", action="store_true", help="every leg besides the timed steps (CPU baseline, exact-gap and hand-off legs, fixed-cost and "
+                    "reference steps, roofline, queue-order check, closed loop, single-instance / MIQP / cfg5 legs, condensing roofline); the "
+                    "options below that name a leg act only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float64; "
+                    "rank 0's shard, v for a seeded sample of instances)")
     ap.add_argument("--cpu-sample", type=int, default=1024, help="instances timed with the CPU oracle on all cores (0 = skip)")
     ap.add_argument("--exact-sample", type=int, default=-1, help="instances of the exact-gap leg (-1 = the whole shard, 0 = skip)")
     ap.add_argument("--closed-loop-steps", type=int, default=24, help="steps of the closed-loop leg after the timed region (0 = skip)")
@@ -98,7 +108,10 @@ def parse():
     ap.add_argument("--fixed-cost", action="store_true", help="keep one cost for every timed step (round 3) instead of new prices per step (mld_problem_set_cost inside the timed region)")
     ap.add_argument("--no-extra-legs", action="store_true", help="skip the cfg5 / MIQP / single-instance legs after the timed region")
     ap.add_argument("--rehearse", action="store_true", help="multi-rank rehearsal on ONE GPU: every rank on device 0, gather over the TCP side channel")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def make_shard(n_agents, n_scen, scen_offset):
@@ -549,6 +562,68 @@ def run_pipelined(probs, count, state, n_sets, gatherer, costs=None):
     return res
 
 
+DUMP_V_ROWS = 4096                  # rows of v in a dump: 4096 x 575 fp64 = 18.8 MB
+DUMP_INSTANCE_BYTES = 40 << 20      # per-instance arrays of a dump; with the v rows the files stay under 64 MB
+
+
+def _dump_sample(b, k, seed):
+    """sorted, seeded choice of k of b instances (all of them when b <= k)"""
+    if b <= k:
+        return np.arange(b)
+    return np.sort(np.random.Generator(np.random.PCG64(seed)).choice(b, k, replace=False))
+
+
+def dump_outputs(path, prob):
+    """What a caller of the timed path receives for the handle's last solve (GpuProblem.download), as float64 DIR/<name>.npy:
+    obj, lower_bound, status, nodes, pivots and u0 (the step-0 slice of v: what the controller applies) for the instances in `index`
+    (every instance of the shard unless that exceeds DUMP_INSTANCE_BYTES), and v itself for the seeded sample of instances in `v_index`."""
+    out = prob.download()
+    b = out["v"].shape[0]
+    nv = prob.model.nv
+    idx = _dump_sample(b, DUMP_INSTANCE_BYTES // (8 * (6 + nv)), 1)
+    vidx = _dump_sample(b, DUMP_V_ROWS, 2)
+    arrays = {"index": idx, "u0": out["v"][idx, :nv], "v_index": vidx, "v": out["v"][vidx]}
+    for k in ("obj", "lower_bound", "status", "nodes", "pivots"):
+        arrays[k] = out[k][idx]
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(arrays)
+
+
+def headline(args, world, n_local, elapsed, stats_timed, H, cost_update, gatherer):
+    """the result line of every run: the rate of the K timed steps and what they were"""
+    hist = lambda s: {"optimal": int(s["n_optimal"]), "node_limit": int(s["n_node_limit"]), "infeasible": int(s["n_infeasible"]), "other": int(s["n_numerical"])}
+    return {
+        "metric": "MPC steps/sec (whole node) + p50 solve latency, 64-agent microgrid N=24",
+        "value": round(world * n_local * args.steps / elapsed, 2),
+        "unit": "agent-solves/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 2),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "BASELINE cfg4 shard: %d agents x %d scenarios per GPU (n_h=7, N_p=24: n=575, 200 binaries, m=500), "
+                               "full branch-and-cut MILP (library defaults: per-model big-M tightening, per-instance presolve, Gomory + c-MIR cuts), MIPGap=%g, NodeLimit=%d, IterationLimit=%d; every step solves a fresh, independently seeded "
+                               "scenario set of the same distribution" % (args.agents, args.scenarios, args.mip_gap, args.node_limit, args.pivot_limit),
+                   "timed_region": "K x (%smld_select_inputs [D2D copy of the next staged scenario set] + mld_solve_launch / mld_solve_finish [K3 + K5/K6] (+ RCCL gather of "
+                                   "(obj, status, step-0 inputs) from device buffers when N > 1)), the steps alternating over %d problem handles on their own HIP "
+                                   "streams: step k+1 is queued while step k runs, so its workgroups take the CUs the stragglers of step k leave idle (results are "
+                                   "bit-identical to one-at-a-time solves); all inputs were staged in HBM before the region, results stay in HBM; the host "
+                                   "download of the full results is outside (download_ms)" % ("mld_problem_set_cost [this step's tariff: new q_z / q_mu weights to the device] + " if cost_update else "", H),
+                   "instances_per_gpu": n_local, "microgrid_steps_per_s": round(world * n_local * args.steps / elapsed / args.agents, 3),
+                   "status_per_step": [hist(s) for s in stats_timed],
+                   "proven_fraction": round(float(np.mean([s["n_optimal"] for s in stats_timed]) / n_local), 5),
+                   "result_gather": (None if gatherer is None else type(gatherer).__name__),
+                   "cost_update_per_step": cost_update},
+    }
+
+
+def latency_ms(tel):
+    """p50 / p99 of the in-kernel per-instance solve latency of a handle's last solve"""
+    lat = np.sort(tel["latency_ns"]) * 1e-6
+    return {"p50_solve_latency_ms": round(float(lat[len(lat) // 2]), 3), "p99_solve_latency_ms": round(float(lat[int(len(lat) * 0.99)]), 3)}
+
+
 def main():
     args = parse()
     rank = int(os.environ.get("RANK", "0"))
@@ -559,7 +634,7 @@ def main():
     rd = TcpRendezvous() if world > 1 else None
     agents, N_p, N_t, x0, om, midx = make_shard(args.agents, args.scenarios, rank * args.scenarios)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and args.cpu_sample > 0:
         # CPU leg: rank 0 at N=1 only, and BEFORE the first HIP call of this process -- its HiGHS pool forks workers
         cpu = cpu_baseline(agents, N_p, N_t, x0, om, midx, args.cpu_sample, args.mip_gap, args.node_limit, args.pivot_limit)
     _lib.check(_lib.load().mld_set_device(0 if args.rehearse else local_rank))
@@ -569,18 +644,21 @@ def main():
     prob = gpu.GpuProblem(model, N_p, N_t, cost, gap_rel=args.mip_gap, max_nodes=args.node_limit, max_pivots=args.pivot_limit, reserved=args.reserved, **parse_kwargs(args.solver_opts))
     n_local = x0.shape[0]
     exact = None
-    if world == 1 and args.exact_sample != 0:
+    if args.full and world == 1 and args.exact_sample != 0:
         progress("exact-gap leg (1e-6) on the shard")
         exact = exact_leg(prob, x0, om, midx, args.exact_sample, args)
     hand1 = None
-    if world == 1 and args.exact_sample != 0:
+    if args.full and world == 1 and args.exact_sample != 0:
         progress("hand-off leg at the bench's own contract")
         hand1 = handoff_leg(prob, x0, om, midx, args)
-    progress("staging %d scenario sets" % (args.warmup + args.steps + max(1, args.reference_steps) + 5))
+    # fresh scenario sets for every step (set 0 = the shard's own scenarios), all resident in HBM before the timed region; step k solves set k
+    # in both kinds of run, so a plain run and a --full run time the same inputs
+    n_sets = args.warmup + args.steps
+    if args.full:
+        n_sets += max(1, args.reference_steps) + 5      # (+ 3 for the fixed-cost continuity steps, + 2 spare)
+    progress("staging %d scenario sets" % n_sets)
     prob.upload(x0, om, midx)                       # inputs resident in HBM before the timed region
-    # fresh scenario sets for every step (set 0 = the shard's own scenarios), all resident in HBM before the timed region
     from pyhybridcontrol_amd import synthetic as syn
-    n_sets = args.warmup + args.steps + max(1, args.reference_steps) + 5      # (+ 3 for the fixed-cost continuity steps, + 2 spare)
     x0_sets = np.empty((n_sets,) + x0.shape)
     om_sets = np.empty((n_sets,) + om.shape)
     x0_sets[0], om_sets[0] = x0, om
@@ -660,6 +738,18 @@ def main():
     elapsed = time.perf_counter() - t0
     if rd is not None:
         elapsed = rd.all_max(elapsed)
+    result = headline(args, world, n_local, elapsed, stats_timed, H, cost_sets is not None, gatherer)
+    last = probs[(args.steps - 1) % H]      # the handle of the last timed step: its results and telemetry are still on the device
+    if args.dump_outputs and rank == 0:
+        progress("outputs of the last timed step to %s" % args.dump_outputs)
+        dump_outputs(args.dump_outputs, last)
+    if not args.full:
+        result["config"].update(latency_ms(last.telemetry()), latency_measured_on="last timed step")
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if rd is not None:
+            rd.close()
+        return
     # continuity with rounds 1-3, whose timed steps all ran under the 05:00 tariff: two more pipelined steps with that one cost (outside `value`)
     value_fixed = None
     if cost_sets is not None and world == 1:
@@ -714,44 +804,24 @@ def main():
     ticks = np.array(list(prof)[:7], dtype=np.float64)
     share = float(ticks[0] / ticks.sum()) if ticks.sum() > 0 else None
     phase_names = ("rank1_update", "pivot_selection", "cut_separation", "leaf_checks", "bound_changes", "verification_refactor", "setup")
-    lat = np.sort(tel["latency_ns"]) * 1e-6
     status = out["status"]
     fin = np.isfinite(out["obj"])
     with np.errstate(invalid="ignore"):
         gap = np.where(fin, (out["obj"] - out["lower_bound"]) / np.maximum(1e-9, np.abs(out["obj"])), np.nan)
     lim = status == 2
     PATTERN = pattern_ceiling()
-    hist = lambda s: {"optimal": int(s["n_optimal"]), "node_limit": int(s["n_node_limit"]), "infeasible": int(s["n_infeasible"]), "other": int(s["n_numerical"])}
-    result = {
-        "metric": "MPC steps/sec (whole node) + p50 solve latency, 64-agent microgrid N=24",
-        "value": round(world * n_local * args.steps / elapsed, 2),
-        "unit": "agent-solves/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 2),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "BASELINE cfg4 shard: %d agents x %d scenarios per GPU (n_h=7, N_p=24: n=575, 200 binaries, m=500), "
-                               "full branch-and-cut MILP (library defaults: per-model big-M tightening, per-instance presolve, Gomory + c-MIR cuts), MIPGap=%g, NodeLimit=%d, IterationLimit=%d; every step solves a fresh, independently seeded "
-                               "scenario set of the same distribution" % (args.agents, args.scenarios, args.mip_gap, args.node_limit, args.pivot_limit),
-                   "timed_region": "K x (%smld_select_inputs [D2D copy of the next staged scenario set] + mld_solve_launch / mld_solve_finish [K3 + K5/K6] (+ RCCL gather of "
-                                   "(obj, status, step-0 inputs) from device buffers when N > 1)), the steps alternating over %d problem handles on their own HIP "
-                                   "streams: step k+1 is queued while step k runs, so its workgroups take the CUs the stragglers of step k leave idle (results are "
-                                   "bit-identical to one-at-a-time solves); all inputs were staged in HBM before the region, results stay in HBM; the host "
-                                   "download of the full results is outside (download_ms)" % ("" if cost_sets is None else "mld_problem_set_cost [this step's tariff: new q_z / q_mu weights to the device] + ", H),
-                   "instances_per_gpu": n_local, "microgrid_steps_per_s": round(world * n_local * args.steps / elapsed / args.agents, 3),
-                   "p50_solve_latency_ms": round(float(lat[len(lat) // 2]), 3), "p99_solve_latency_ms": round(float(lat[int(len(lat) * 0.99)]), 3),
+    result["config"].update(latency_ms(tel), latency_measured_on="last reference step")
+    result["config"].update({
                    "status_last_step": {"optimal": int((status == 0).sum()), "infeasible": int((status == 1).sum()), "node_limit": int(lim.sum()),
                                         "numerical": int((status == 3).sum()), "unbounded": int((status == 4).sum())},
-                   "status_per_step": [hist(s) for s in stats_timed],
-                   "proven_fraction": round(float(np.mean([s["n_optimal"] for s in stats_timed]) / n_local), 5),
                    "no_incumbent": int((~fin).sum()),
                    "gap_of_limited": ({"median": round(float(np.nanmedian(gap[lim])), 5), "p90": round(float(np.nanpercentile(gap[lim], 90)), 5),
                                        "max": round(float(np.nanmax(gap[lim])), 5)} if lim.any() else None),
                    "nodes_per_instance": round(float(out["nodes"].mean()), 1), "pivots_per_instance": round(pivots / n_local, 1),
                    "pivots_per_s": round(pivots / (kernel_ms * 1e-3)), "rhs_ms": round(float(np.mean([s["rhs_ms"] for s in stats])), 3),
                    "kernel_ms_per_step_reference": [round(float(s["solve_ms"]), 1) for s in stats],
-                   "download_ms": round(download_ms, 2),
-                   "result_gather": (None if gatherer is None else type(gatherer).__name__)},
+                   "download_ms": round(download_ms, 2)})
+    result.update({
         "roofline": {"kernel": "k_solve", "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_src,
                      "algorithmic_bytes_per_launch": int(upd_bytes), "bytes_per_instance": int(upd_bytes / n_local),
@@ -787,7 +857,7 @@ def main():
                              "the following steps with mld_solve_resident on one handle -- the difference is the ragged end of a step (0.5-1.2 s node-limited "
                              "instances at random positions of the work queue) that the next step's workgroups fill; value_no_idle_bound: instances / (sum of the "
                              "in-kernel latencies of the last reference step / CUs), the rate of a device that never waits for a straggler"},
-    }
+    })
     # K3 on the matrix cores: one [m0 x (nx + N nw)] . [(nx + N nw) x instances-of-the-model] GEMM per model
     rhs_ms = float(np.mean([s["rhs_ms"] for s in stats]))
     flops = 2.0 * prob.m * (d["nx"] + prob.nW) * n_local
@@ -884,7 +954,6 @@ def main():
     for leg in ("single_instance", "miqp", "cfg5"):
         if result.get(leg) is not None:
             cfgd[leg] = result[leg]
-    cfgd["cost_update_per_step"] = cost_sets is not None
     if value_fixed is not None:
         cfgd["value_fixed_cost"] = value_fixed
         cfgd["value_fixed_cost_note"] = ("two pipelined steps under the 05:00 tariff of every earlier round's timed region (same scenario distribution): with the clock moving, "

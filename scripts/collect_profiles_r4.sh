@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R"
 mkdir -p gpurun_out
-CMD="bench.py --steps 2 --warmup 1 --no-cpu --exact-sample 0 --handles 1 --closed-loop-steps 0 --no-extra-legs"
+CMD="bench.py --full --steps 2 --warmup 1 --no-cpu --exact-sample 0 --handles 1 --closed-loop-steps 0 --no-extra-legs"
 rm -rf gpurun_out/r4_prof_stats gpurun_out/r4_pmc_fetch gpurun_out/r4_pmc_write gpurun_out/r4_pmc_sqa gpurun_out/r4_pmc_sqb
 rocprofv3 -L > gpurun_out/r4_counters.txt 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/gpurun_out/r4_prof_stats" -- python3 $CMD > gpurun_out/r4_prof_stats.log 2>&1 && echo stats ok

@@ -20,7 +20,7 @@ if g("SQ_LDS_IDX_ACTIVE"):
     der["lds_bank_conflict_share (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE)"] = g("SQ_LDS_BANK_CONFLICT") / g("SQ_LDS_IDX_ACTIVE")
 if g("SQ_INSTS_FLAT"):
     der["flat_share_of_memory_instructions"] = g("SQ_INSTS_FLAT") / max(1.0, g("SQ_INSTS_FLAT") + g("SQ_INSTS_LDS"))
-json.dump({"kernel": "k_solve", "command": "rocprofv3 --pmc <8 SQ counters per pass> -- python3 bench.py --steps 2 --warmup 1 --no-cpu --exact-sample 0 --handles 1 --closed-loop-steps 0 --no-extra-legs",
+json.dump({"kernel": "k_solve", "command": "rocprofv3 --pmc <8 SQ counters per pass> -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu --exact-sample 0 --handles 1 --closed-loop-steps 0 --no-extra-legs",
            "counters_per_launch": doc, "derived": der,
            "units": "SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_* count quad-cycles summed over waves (MI355X_MICROARCH.md); instruction counters count wave instructions"}, open(sys.argv[1], "w"), indent=1)
 print(json.dumps(der, indent=1))
