@@ -287,7 +287,9 @@ int mld_download_open_nodes(mld_problem_t *, int32_t *depth_out, int16_t *var_ou
  * objective, on ties the node that comes first in the tree -- so mld_download_results returns per instance what an unlimited search of that
  * instance would have returned; the set of items and every item's arithmetic do not depend on which workgroup ran what, so results are
  * reproducible.  room_factor: items the queue has room for, as a multiple of the batch (at least 4096; <= 0 keeps the current value, default 2).
- * Takes effect with the next mld_upload_batch.  Not with a quadratic cost and not on the LDS-resident LP path (those solves run as before).
+ * Takes effect with the next mld_upload_batch.  Not on the LDS-resident LP path (those solves run as before).  Under a quadratic cost the
+ * search's closing sweep also tries the QP relaxation (its simplicial-decomposition bound) on every open sibling the LP(q) value leaves open,
+ * and an item's root stops at its cutoff on the QP bound as well; a node is closed only on a proven lower bound.
  * A tree for which more than max_tree items (default 160) of ONE generation have been published keeps growing and is GIVEN UP: its remaining items are skipped and the instance
  * keeps what its own search returned (MLD_STATUS_NODE_LIMIT, incumbent, bound) -- whether that happens does not depend on the queue order.
  * mld_handoff_stats: out[0] items published by the last solve, out[1] trees given up for their size, out[2] instances that were split and are

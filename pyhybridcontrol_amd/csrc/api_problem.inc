@@ -1269,7 +1269,7 @@ static int solve_impl(mld_problem_t *p, mld_stats *st, int mode)
     B.counter = p->d_counter;
     B.order = (p->order_batch == batch && !(p->opts.reserved & 8)) ? p->d_order : nullptr;
     P.binpos = p->d_binpos;
-    const bool ho = p->ho_enable && p->d_tail && !lp_path && !p->has_quad && p->nb > 0;
+    const bool ho = p->ho_enable && p->d_tail && !lp_path && p->nb > 0;      /* (a quadratic cost included: items index d_qs_inst / d_rconst by their source instance, < batch) */
     B.ho = 0; B.cap = p->batch_cap; B.tail = p->d_tail; B.finished = p->d_finished;
     B.ho_sub_nodes = p->ho_sub_nodes > 0 ? p->ho_sub_nodes : p->opts.max_nodes; B.ho_max_gen = p->ho_max_gen; B.ho_max_children = p->ho_max_children;
     B.item_src = p->d_item_src; B.item_root = p->d_item_root; B.item_gen = p->d_item_gen; B.item_label = p->d_item_label; B.item_ready = p->d_item_ready;

@@ -1845,6 +1845,17 @@ __device__ int s_sd_relax(const Ws &w, Shared &sh, double cutoff, int max_pivots
     return rc;
 }
 
+// Closing sweep of the in-kernel hand-off under a quadratic cost: an open sibling whose LP(q) value did not pass the cutoff gets its QP relaxation.
+// Closed only on a proven lower bound -- the simplicial-decomposition bound passed the cutoff (rc 1, or a finished bound above it); -1 (limit)
+// leaves the node open, -2 (QP relaxation not finished) leaves the verdict to LP(q), which did not close it.  s_sd_relax returns with the
+// dictionary's cost row at q and LP(q)-optimal for the node, as the node loop relies on.  Not inlined: the pivot loop's live ranges stay as they are.
+__device__ __noinline__ bool s_sweep_close_qp(const Ws &w, Shared &sh, double sweep_cut, int max_pivots)
+{
+    double lbq, fvq;
+    const int rc = s_sd_relax(w, sh, sweep_cut, max_pivots, &lbq, &fvq);
+    return rc == 1 || (rc == 0 && lbq > sweep_cut);
+}
+
 // one round of Gomory mixed-integer cuts; returns the number added (same value on all threads)
 __device__ __forceinline__ double wave_all_sum(double v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64); return v; }
 __device__ __forceinline__ double wave_all_max(double v) { for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64)); return v; }
@@ -3135,9 +3146,12 @@ __global__ void __launch_bounds__(SOL_NT, SOL_WPE) k_solve(SolverShape S, Proble
             }
         }
         if (root_ok && w.P) {   // root bound of the QP relaxation
+            // (an item of the in-kernel hand-off stops as soon as the bound passes its cutoff, as its root LP does: "nothing better in this node")
+            const double qcut = (is_item && ext_cut) ? best - s_gtol(S, best) + 1e-12 : S_INF;
             double lbq, fvq;
-            const int rcq = s_sd_relax(w, sh, S_INF, S.max_pivots, &lbq, &fvq);
-            if (rcq == -1) { root_ok = false; status = MLD_STATUS_NUMERICAL; }
+            const int rcq = s_sd_relax(w, sh, qcut, S.max_pivots, &lbq, &fvq);
+            if (rcq == 1) { root_ok = false; status = MLD_STATUS_INFEASIBLE; lb_proven = qcut; }
+            else if (rcq == -1) { root_ok = false; status = MLD_STATUS_NUMERICAL; }
             else root_bound = rcq == -2 ? s_objective(w, sh) : lbq;      // (-2: the QP relaxation could not be finished -- the LP(q) value is a bound too)
         }
         if (root_ok) {
@@ -3237,6 +3251,7 @@ __global__ void __launch_bounds__(SOL_NT, SOL_WPE) k_solve(SolverShape S, Proble
                     nodes++;
                     int branch_j = -1; double branch_x = 0.0;
                     int force_first = -1; bool second_done = false, pen_pruned = false;   // penalty branching: preferred side, other side closed
+                    bool qp_open = false;      // (quadratic cost: the node's QP relaxation hit the limit -- the node is unsolved, still open)
                     // RINS is a heuristic on a sub-problem: it keeps ANY improvement (round 4; oracle: same rule).  With the proof's cutoff -- "better by more than the
                     // gap" -- it threw away exactly the points that matter at the cfg5 size: the dive's leaf is 0.5-1 % above the best point, the root bound within 1 % of THAT one
                     const double inc_cut = (have || ext_cut) ? ((phase == PH_RINS && have) ? best - 1e-6 * fmax(1.0, fabs(best)) : best - s_gtol(S, best)) : S_INF;
@@ -3254,7 +3269,7 @@ __global__ void __launch_bounds__(SOL_NT, SOL_WPE) k_solve(SolverShape S, Proble
                         if (!pruned && w.P) {
                             double lbq, fvq;
                             const int rc = s_sd_relax(w, sh, cut, S.max_pivots, &lbq, &fvq);
-                            if (rc == -1) { limit = true; pruned = true; obj = S_INF; }
+                            if (rc == -1) { limit = true; pruned = true; obj = S_INF; qp_open = true; }
                             else if (rc == -2) qp_lp = true;      // the QP relaxation could not be finished: this node goes on with its LP(q) bound and LP point
                             else { obj = lbq; pruned = (rc == 1 || obj > cut); }
                         }
@@ -3344,7 +3359,7 @@ __global__ void __launch_bounds__(SOL_NT, SOL_WPE) k_solve(SolverShape S, Proble
                     if (have && (rescue || unbounded || best <= lbg + s_gtol(S, best))) finished = true;
                     if (nodes >= ((phase == PH_IDS && !have && !rescue) ? ids_cap : node_budget)) {
                         limit = true;
-                        if (B.ho && B.ho_donate > 0 && donations < B.ho_rounds && !finished && !rescue && !w.P && lp != LP_ITERLIMIT && (phase == PH_FINAL || (phase == PH_IDS && T == S_INF))) {
+                        if (B.ho && B.ho_donate > 0 && donations < B.ho_rounds && !finished && !rescue && lp != LP_ITERLIMIT && !qp_open && (phase == PH_FINAL || (phase == PH_IDS && T == S_INF))) {
                             // Node limit inside a complete search with the in-kernel hand-off on: give the LARGEST open subtrees away -- the shallowest
                             // open siblings of the stack become items for idle workgroups -- and go on below them with a new budget.  What stays here are
                             // the deep open nodes, which this dictionary closes in a few pivots each; an item pays a root LP and a cut loop of its own.
@@ -3403,7 +3418,7 @@ __global__ void __launch_bounds__(SOL_NT, SOL_WPE) k_solve(SolverShape S, Proble
                             // sub-tree hand-off (mld_download_open_nodes): when a COMPLETE search (plain depth-first search below the incumbent: FINAL, or
                             // the deepening passes once T is infinite) stops at a limit, the stack describes everything that is still open -- for every
                             // level whose sibling has not been visited the node (path above it, variable flipped), plus the current path itself
-                            const bool complete = limit && !finished && !rescue && !w.P && (phase == PH_FINAL || (phase == PH_IDS && T == S_INF));
+                            const bool complete = limit && !finished && !rescue && (phase == PH_FINAL || (phase == PH_IDS && T == S_INF));
                             if (complete) {
                                 for (int k = tid; k < depth; k += SOL_NT) {
                                     const int j = w.stk_j[k];
@@ -3415,7 +3430,7 @@ __global__ void __launch_bounds__(SOL_NT, SOL_WPE) k_solve(SolverShape S, Proble
                             if (tid == 0) B.open_depth[inst] = complete ? depth : -1;
                             __syncthreads();
                         }
-                        if (B.ho && limit && !finished && !rescue && !w.P && (phase == PH_FINAL || (phase == PH_IDS && T == S_INF))) {
+                        if (B.ho && limit && !finished && !rescue && (phase == PH_FINAL || (phase == PH_IDS && T == S_INF))) {
                             // In-kernel hand-off: this COMPLETE search stopped at its node limit.  Everything it leaves open -- for every level whose sibling has not
                             // been visited the node {path above it, that level flipped}, plus the current path itself -- is published as entries of the work
                             // queue; whichever workgroup runs out of instances solves them (root LP and cut loop of their own, this search's incumbent as cutoff).
@@ -3426,7 +3441,7 @@ __global__ void __launch_bounds__(SOL_NT, SOL_WPE) k_solve(SolverShape S, Proble
                             // visited gets that sibling's LP under the incumbent's cutoff: closed -> accounted for, still open -> it becomes an item.
                             for (int k = tid; k < depth; k += SOL_NT) w.stk_val[k] = (unsigned char)(w.lo[w.stk_j[k]] > 0.5 ? 1 : 0);
                             __syncthreads();
-                            const bool cur_open = branch_j >= 0 || lp == LP_ITERLIMIT;      // (a node whose LP hit the pivot limit is unsolved: still open)
+                            const bool cur_open = branch_j >= 0 || lp == LP_ITERLIMIT || qp_open;      // (a node whose LP -- or QP relaxation -- hit the pivot limit is unsolved: still open)
                             const double sweep_cut = (have || ext_cut) ? best - s_gtol(S, best) : S_INF;
                             const int depth_pub = depth;
                             if (!(S.debug & 524288))
@@ -3439,6 +3454,7 @@ __global__ void __launch_bounds__(SOL_NT, SOL_WPE) k_solve(SolverShape S, Proble
                                     nodes++;
                                     bool closed = l2 == LP_CUTOFF || l2 == LP_INFEASIBLE;
                                     if (l2 == LP_OPTIMAL) closed = s_objective(w, sh) > sweep_cut;
+                                    if (l2 == LP_OPTIMAL && !closed && w.P && sweep_cut < S_INF) closed = s_sweep_close_qp(w, sh, sweep_cut, S.max_pivots);
                                     __syncthreads();
                                     if (closed && tid == 0) w.stk_second[k] = 1;
                                     __syncthreads();
@@ -3523,7 +3539,7 @@ __global__ void __launch_bounds__(SOL_NT, SOL_WPE) k_solve(SolverShape S, Proble
             }
             // every way of ending OPTIMAL has closed all nodes below best - gtol; otherwise the bound is what exhaustive passes proved
             lb_proven = status == MLD_STATUS_OPTIMAL ? fmin(best, fmax(lbg, best - s_gtol(S, best))) : lbg;
-            if (B.ho && !expanded && !stopped_complete && status == MLD_STATUS_NODE_LIMIT && have && !w.P) {
+            if (B.ho && !expanded && !stopped_complete && status == MLD_STATUS_NODE_LIMIT && have) {
                 // The search stopped at a limit BEFORE it became a plain depth-first search below an incumbent (deepening passes, dive, RINS): no stack
                 // describes what is left, so its one open node is its own root -- published once more, now under the incumbent's value as cutoff (the
                 // item starts as a complete search and can be split).  Without an incumbent there is nothing to gain from running the same search again.

@@ -182,7 +182,6 @@ class GpuProblem(object):
             keep.append(a)
             setattr(c, k, _lib.dptr(a))
         self._keep_cost = keep
-        self._last_cost = dict(quad=tuple(cost.get(k) for k in ("quad_v", "quad_x", "quad_y")))
         return c, keep
 
     def set_cost(self, cost):
@@ -421,13 +420,12 @@ class GpuProblem(object):
         """The batch solved with sub-tree hand-off: a first pass over all instances (node limit `first_nodes`, default the problem's), then up to
         `rounds` passes in which the OPEN NODES of the instances that stopped at the limit -- read off their depth-first stacks -- are solved as
         instances of their own (node limit `sub_nodes` each, the parent's incumbent value as cutoff), so the whole device works on the few large
-        trees instead of one workgroup per tree.  An instance is proven once every one of its nodes has been closed; one whose open nodes
+        trees instead of one workgroup per tree (a quadratic cost included: the open nodes and cutoffs carry the instance's quadratic constant
+        through its objective).  An instance is proven once every one of its nodes has been closed; one whose open nodes
         outnumber `max_open` after a pass is given up (NODE_LIMIT with its incumbent and bound).  Returns the dict of
         download() (v, obj, status, lower_bound; nodes / pivots summed over all passes) plus `handoff` statistics; the resident batch afterwards
         is the last pass's sub-batch (upload again before advance() / warm starts)."""
         d = self.model.dims
-        if getattr(self, "_keep_cost", None) and any(k is not None for k in (self._last_cost or {}).get("quad", ())):
-            raise MldGpuError("solve_handoff: not with a quadratic cost (a stopped search records its stack only under a linear cost)")
         x0 = _lib.as_f64(x0).reshape(-1, d["nx"]) if d["nx"] else np.zeros((np.shape(omega)[0], 0))
         B = x0.shape[0] if d["nx"] else int(np.asarray(omega).reshape(-1, max(self.nW, 1)).shape[0])
         omega = _lib.as_f64(omega).reshape(B, self.nW) if self.nW else np.zeros((B, 0))
