@@ -6,6 +6,7 @@
 #include "lp_lds.inc"
 
 #include <limits>
+#include <memory>
 
 // ------------------------------------------------------------------------------------------------
 // probing-based coefficient tightening of one step's MLD rows (Savelsbergh 1994, sections 1.1, 3.2-3.3).
@@ -290,76 +291,74 @@ __global__ void __launch_bounds__(256) k_warm_from_plan(int batch, int nb, int n
 }
 
 // ------------------------------------------------------------------------------------------------
+/* buffers of the uploaded batch (ensure_batch, mld_upload_batch, mld_upload_constraint_blocks, mld_stage_inputs): released together when the
+ * batch is laid out anew.  Inputs have one entry per instance, results one per queue entry (instances, then the items of the in-kernel hand-off). */
+struct BatchBufs {
+    DevBuf<int> model_idx; DevBuf<double> x0, omega, hs, qs_inst, rconst;
+    DevBuf<double> x0b, omegab; DevBuf<int> skipped;     /* spare input buffers and device counter of mld_advance_batch (the counter: also the hand-off merge's) */
+    DevBuf<unsigned char> warm; DevBuf<int> order;       /* MIP start (mld_set_warm_start); longest-first work-queue order learnt from the previous solve */
+    DevBuf<unsigned char> fixed; DevBuf<double> cutoff, v, obj, lbnd;
+    DevBuf<int> status, nodes, pivots, cuts, refac; DevBuf<long long> ticks, rows, prof;
+    DevBuf<int> open_depth; DevBuf<short> open_var; DevBuf<unsigned char> open_val, open_flag;   /* open-node stacks (mld_download_open_nodes) */
+    DevBuf<double> stage_x0, stage_om;                   /* resident input sets (mld_stage_inputs) */
+    DevBuf<int> perm; DevBuf<RhsGroup> groups;           /* instances grouped by model for the MFMA right-hand sides (K3) */
+    DevBuf<double> xcols, xcols_x; DevBuf<int> xrows;    /* extra constraint blocks; the state every extra column was generated with (explicit x_k) */
+    struct Handoff {      /* in-kernel sub-tree hand-off queue: allocated only while mld_set_handoff has it on */
+        DevBuf<int> tail, finished, item_src, item_root, item_gen, item_ready, item_children; DevBuf<long long> item_label;
+        DevBuf<unsigned long long> mg_best, mg_lbopen, mg_label; DevBuf<int> mg_open;   /* merge accumulators per root */
+        DevBuf<int> tree_count, tree_dead;                /* items published per tree / tree given up */
+    } ho;
+};
+
+/* what mld_solve_finish has to do: nothing launched; a dense solve queued on the stream; or an LDS-path solve that ran to completion in the
+ * launch (the fall-back needs its statuses on the host), whose finish only reports */
+enum class Flight : unsigned char { idle, queued, lds_done };
+
 struct mld_problem {
-    mld_model *model;           // caller's (original) model: used by mld_rhs_batch
-    mld_model *tight;           // internal copy with tightened rows, condensed on device
-    mld_opts opts;
-    int N_p, N, n, m0, nb, nx, nW, nv, n_models;
-    void *h_trace; int *d_trace; size_t trace_bytes;   /* mld_debug_trace: file-backed host buffer the kernel writes its stage markers into */
-    int mir_cap;                /* integer entries of the widest scaled original row over all models, rounded up to 8 (k_solve's compact c-MIR lines) */
-    SolverShape S;
+    mld_model *model = nullptr;                 // caller's (original) model: used by mld_rhs_batch
+    std::unique_ptr<mld_model> tight;           // internal copy with tightened rows, condensed on device
+    mld_opts opts{};
+    int N_p = 0, N = 0, n = 0, m0 = 0, nb = 0, nx = 0, nW = 0, nv = 0, n_models = 0;
+    void *h_trace = nullptr; int *d_trace = nullptr; size_t trace_bytes = 0;   /* mld_debug_trace: file-backed host buffer the kernel writes its stage markers into */
+    int mir_cap = 0;            /* integer entries of the widest scaled original row over all models, rounded up to 8 (k_solve's compact c-MIR lines) */
+    SolverShape S{};
     // per-model device arrays
-    double *d_Gp;   /* d_Gs with columns in dictionary (position-major) order: coalesced dictionary reset */
-    double *d_actmax;   /* n_models x m0: largest row activity under the model's bounds (s_mark_dead) */
+    DevBuf<double> d_Gp;        /* d_Gs with columns in dictionary (position-major) order: coalesced dictionary reset */
+    DevBuf<double> d_actmax;    /* n_models x m0: largest row activity under the model's bounds (s_mark_dead) */
     /* sparse copies of the scaled rows for the per-instance presolve (s_presolve): by row and by column, nnz_cap entries per model */
-    int *d_csr_ptr, *d_csc_ptr; unsigned short *d_csr_col, *d_csc_row; double *d_csr_val, *d_csc_val; int nnz_cap;
-    double *d_Gs, *d_rs, *d_cs, *d_qs, *d_lb, *d_ub, *d_cx, *d_cw, *d_c0, *d_q0;
-    unsigned char *d_is_int;
-    int *d_bins, *d_colperm;
-    std::vector<double> h_cs;
+    DevBuf<int> d_csr_ptr, d_csc_ptr; DevBuf<unsigned short> d_csr_col, d_csc_row; DevBuf<double> d_csr_val, d_csc_val; int nnz_cap = 0;
+    DevBuf<double> d_Gs, d_rs, d_cs, d_qs, d_lb, d_ub, d_cx, d_cw, d_c0, d_q0;
+    DevBuf<unsigned char> d_is_int;
+    DevBuf<int> d_bins, d_colperm, d_binpos;   /* d_binpos: position of a structural among the binaries, -1 for continuous entries (in-kernel hand-off) */
     // quadratic cost (K4)
-    double *d_P, *d_Qx, *d_Qw, *d_Ps, *d_Wx, *d_Wy;
-    bool has_quad;
-    double *d_qs_inst, *d_rconst;
+    DevBuf<double> d_P, d_Qx, d_Qw, d_Ps, d_Wx, d_Wy;
+    bool has_quad = false;
     // workspace
-    unsigned char *d_ws;
-    int n_slots;
-    size_t lds_bytes;
-    // batch buffers
-    int batch, batch_cap;
-    int *d_model_idx; double *d_x0, *d_omega; unsigned char *d_fixed; bool has_fixed, has_midx;
-    double *d_x0b, *d_omegab;   /* spare input buffers of mld_advance_batch */
-    unsigned char *d_warm; bool has_warm;   /* MIP start of the resident batch (mld_set_warm_start / mld_warm_start_from_previous) */
-    bool solved;                /* the resident batch has a finished solve (mld_advance_batch / mld_warm_start_from_previous need one) */
-    bool advanced;              /* mld_advance_batch has applied that solve's plan: the next advance needs the next solve */
-    int *d_skipped;             /* device counter of mld_advance_batch2 */
-    double *d_gather; size_t gather_cap;   /* send + receive buffers of mld_gather_results */
-    double *d_cutoff; bool has_cutoff;     /* objective cutoffs of the resident batch (mld_set_cutoffs) */
-    int *d_open_depth; short *d_open_var; unsigned char *d_open_val, *d_open_flag; bool want_open;   /* open-node stacks (mld_download_open_nodes) */
-    double *d_stage_x0, *d_stage_om; int n_staged, staged_batch;   /* resident input sets (mld_stage_inputs) */
+    DevBuf<unsigned char> d_ws; DevBuf<int> d_counter;
+    int n_slots = 0;
+    size_t lds_bytes = 0;
+    // batch buffers, and what they hold: every per-entry result array has batch_cap entries, the inputs in_cap
+    BatchBufs bat;
+    int batch = 0, batch_cap = 0, in_cap = 0;
+    bool has_fixed = false, has_midx = false, has_warm = false;
+    bool solved = false;        /* the resident batch has a finished solve (mld_advance_batch / mld_warm_start_from_previous need one) */
+    bool advanced = false;      /* mld_advance_batch has applied that solve's plan: the next advance needs the next solve */
+    bool has_cutoff = false, want_open = false;    /* objective cutoffs (mld_set_cutoffs); record the open-node stacks (mld_record_open_nodes) */
+    int n_staged = 0, staged_batch = 0, n_groups = 0, n_xcols = 0, order_batch = 0; size_t xcols_cap = 0; bool has_xcols_x = false;
+    DevBuf<double> d_gather; size_t gather_cap = 0;   /* send + receive buffers of mld_gather_results */
     /* LDS-resident LP path (k_lp_lds): Toeplitz-compatible scaling of the tightened model */
-    bool lp_ok, all_fixed; LpShape LS; size_t lp_lds_bytes; int lp_slots;
-    double *d_blk_t, *d_rs_t, *d_cs_t, *d_lb_t, *d_ub_t, *d_qs_t; unsigned char *d_lpws; int *d_lp_list;
-    std::vector<double> h_cs_t; std::vector<int> lp_redo;
-    hipEvent_t ev[3]; bool ev_ok; long long *d_statbuf;
-    hipStream_t stream; bool own_stream, in_flight, flight_lp, lds_done;   /* stream of the solve path (0 = the legacy stream); a launched, not yet finished solve */
-    int *d_perm; RhsGroup *d_groups; int n_groups;   /* instances grouped by model for the MFMA right-hand sides (K3) */
-    double *d_xcols; int *d_xrows; int n_xcols; size_t xcols_cap;   /* extra constraint blocks of the uploaded batch */
-    double *d_xcols_x; bool has_xcols_x;   /* the state every extra column was generated with (explicit x_k), batch x n_cols x nx */
-    int *d_order; int order_batch;   /* longest-first work-queue order learnt from the previous solve of the same batch size */
-    /* in-kernel sub-tree hand-off (mld_set_handoff): queue state and per-entry item data; every per-entry result array has batch_cap entries, the inputs in_cap */
-    bool std_block;             /* the standard constraint block (right-hand side from the batch's own omega) is part of the problem (mld_set_std_block) */
-    int ho_enable, ho_sub_nodes, ho_max_gen, ho_max_children; double ho_factor; int in_cap; bool ho_ran;
-    int *d_binpos, *d_tail, *d_finished, *d_item_src, *d_item_root, *d_item_gen, *d_item_ready, *d_item_children; long long *d_item_label;
-    unsigned long long *d_mg_best, *d_mg_lbopen, *d_mg_label; int *d_mg_open;   /* merge accumulators per root */
-    int *d_tree_count, *d_tree_dead; int ho_max_tree, ho_donate, ho_rounds;   /* items published per tree / tree given up; shallow open nodes handed off per node-limit, times */
-    long long ho_stats[4];      /* last solve: items published, trees split, trees left unfinished, entries the queue had no room for (always 0: such trees stay unfinished) */
-    double *d_hs, *d_v, *d_obj, *d_lbnd;
-    int *d_status, *d_nodes, *d_pivots, *d_cuts, *d_refac, *d_counter;
-    long long *d_ticks, *d_rows, *d_prof;
+    bool lp_ok = false, all_fixed = false; LpShape LS{}; size_t lp_lds_bytes = 0; int lp_slots = 0;
+    DevBuf<double> d_blk_t, d_rs_t, d_cs_t, d_lb_t, d_ub_t, d_qs_t;
+    hipEvent_t ev[3] = {}; bool ev_ok = false; DevBuf<long long> d_statbuf;
+    hipStream_t stream = 0; bool own_stream = false; Flight flight = Flight::idle;   /* stream of the solve path (0 = the legacy stream); a launched, not yet finished solve */
+    bool std_block = true;      /* the standard constraint block (right-hand side from the batch's own omega) is part of the problem (mld_set_std_block) */
+    /* in-kernel sub-tree hand-off (mld_set_handoff) */
+    int ho_enable = 0, ho_sub_nodes = 0, ho_max_gen = 0, ho_max_children = 0; double ho_factor = 2.0; bool ho_ran = false;
+    int ho_max_tree = 160, ho_donate = 0, ho_rounds = 0;   /* items per tree; shallow open nodes handed off per node-limit, times */
+    long long ho_stats[4] = {};  /* last solve: items published, trees split, trees left unfinished, entries the queue had no room for (always 0: such trees stay unfinished) */
 };
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-/* device temporary of one API call: freed when the call returns, whichever way (the HIP_TRY early returns used to leak them) */
-template <typename T> struct DevBuf {
-    T *p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t count) { return hipMalloc(&p, sizeof(T) * std::max<size_t>(1, count)); }
-};
 
 /* mld_opts.time_limit (seconds) in ticks of the device's constant wall clock (wall_clock64: 100 MHz on gfx950) */
 static long long time_limit_ticks(double seconds)
@@ -436,42 +435,24 @@ static void build_shape(mld_problem *p)
     p->lds_bytes = loff;
 }
 
-static int upload(double **dst, const std::vector<double> &src)
+/* a host array to a buffer of its own size (an empty array leaves the buffer empty) */
+template <typename T> static int upload(DevBuf<T> &dst, const std::vector<T> &src)
 {
-    if (src.empty()) { *dst = nullptr; return MLD_OK; }
-    HIP_TRY(hipMalloc(dst, sizeof(double) * src.size()));
-    HIP_TRY(hipMemcpy(*dst, src.data(), sizeof(double) * src.size(), hipMemcpyHostToDevice));
+    if (src.empty()) { dst.reset(); return MLD_OK; }
+    HIP_TRY(dst.alloc(src.size()));
+    HIP_TRY(hipMemcpy(dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice));
     return MLD_OK;
 }
 
 /* a launched solve (mld_solve_launch) owns the problem's buffers until mld_solve_finish */
-#define MLD_NOT_IN_FLIGHT(p, who) do { if ((p) && (p)->in_flight) { mld_set_error("%s: a launched solve has not been finished (mld_solve_finish)", who); return MLD_ERR_INVALID; } } while (0)
+#define MLD_NOT_IN_FLIGHT(p, who) do { if ((p) && (p)->flight != Flight::idle) { mld_set_error("%s: a launched solve has not been finished (mld_solve_finish)", who); return MLD_ERR_INVALID; } } while (0)
 
 static void free_batch(mld_problem *p)
 {
-    void *ptrs[] = {p->d_cutoff, p->d_open_depth, p->d_open_var, p->d_open_val, p->d_open_flag, p->d_warm, p->d_skipped, p->d_stage_x0, p->d_stage_om, p->d_perm, p->d_groups, p->d_x0b, p->d_omegab, p->d_model_idx, p->d_x0, p->d_omega, p->d_fixed, p->d_hs, p->d_v, p->d_obj, p->d_lbnd,
-                    p->d_status, p->d_nodes, p->d_pivots, p->d_cuts, p->d_refac, p->d_ticks, p->d_rows, p->d_prof, p->d_qs_inst, p->d_rconst};
-    for (void *q : ptrs) if (q) (void)hipFree(q);
-    if (p->d_xcols) (void)hipFree(p->d_xcols);
-    if (p->d_xrows) (void)hipFree(p->d_xrows);
-    if (p->d_xcols_x) (void)hipFree(p->d_xcols_x);
-    if (p->d_order) (void)hipFree(p->d_order);
-    {
-        void *hp[] = {p->d_tree_count, p->d_tree_dead, p->d_tail, p->d_finished, p->d_item_src, p->d_item_root, p->d_item_gen, p->d_item_ready, p->d_item_children, p->d_item_label, p->d_mg_best, p->d_mg_lbopen, p->d_mg_label, p->d_mg_open};
-        for (void *q : hp) if (q) (void)hipFree(q);
-        p->d_tail = p->d_finished = p->d_item_src = p->d_item_root = p->d_item_gen = p->d_item_ready = p->d_item_children = nullptr; p->d_item_label = nullptr;
-        p->d_mg_best = p->d_mg_lbopen = p->d_mg_label = nullptr; p->d_mg_open = nullptr; p->in_cap = 0; p->d_tree_count = p->d_tree_dead = nullptr;
-    }
-    p->d_ticks = p->d_rows = p->d_prof = nullptr; p->d_qs_inst = p->d_rconst = nullptr;
-    p->d_model_idx = nullptr; p->d_x0 = p->d_omega = nullptr; p->d_fixed = nullptr; p->d_hs = p->d_v = p->d_obj = p->d_lbnd = nullptr;
-    p->d_x0b = p->d_omegab = nullptr; p->d_perm = nullptr; p->d_groups = nullptr; p->n_groups = 0;
-    p->d_warm = nullptr; p->has_warm = false; p->solved = false; p->advanced = false; p->d_skipped = nullptr;
-    p->d_cutoff = nullptr; p->has_cutoff = false; p->d_open_depth = nullptr; p->d_open_var = nullptr; p->d_open_val = p->d_open_flag = nullptr;
-    p->d_stage_x0 = p->d_stage_om = nullptr; p->n_staged = 0; p->staged_batch = 0;
-    p->d_xcols = nullptr; p->d_xrows = nullptr; p->n_xcols = 0; p->xcols_cap = 0; p->d_xcols_x = nullptr; p->has_xcols_x = false;
-    p->d_order = nullptr; p->order_batch = 0;
-    p->d_status = p->d_nodes = p->d_pivots = p->d_cuts = p->d_refac = nullptr;
-    p->batch_cap = 0;
+    p->bat = BatchBufs();
+    p->n_groups = 0; p->has_warm = false; p->solved = false; p->advanced = false; p->has_cutoff = false;
+    p->n_staged = 0; p->staged_batch = 0; p->n_xcols = 0; p->xcols_cap = 0; p->has_xcols_x = false;
+    p->order_batch = 0; p->in_cap = 0; p->batch_cap = 0;
 }
 
 // out[k] = a[k] * b[k]
@@ -485,7 +466,7 @@ static int set_cost_impl(mld_problem *p, const mld_cost *cost)
 {
     const int n = p->n, M = p->n_models, nx = p->nx, nW = p->nW;
     const int NX = p->N * p->model->dims.nx, NY = p->N * p->model->dims.ny;
-    mld_model *t = p->tight;
+    const mld_model *t = p->tight.get();
     /* Everything runs on the problem's own stream and ends with a wait on THAT stream: a caller that updates the cost of one problem every step
      * (the reference rebuilds its objective with the new prices before every solve, micro_grid_control_simulation.py:197-198,229) must not stall
      * the solve another problem has in flight.  A purely linear cost on v (lin_v only: the bench's q_z / q_mu atoms) needs no temporary and no
@@ -499,9 +480,8 @@ static int set_cost_impl(mld_problem *p, const mld_cost *cost)
     if (cost && cost->lin_v) HIP_TRY(hipMemcpyAsync(p->d_q0, cost->lin_v, sizeof(double) * n * M, hipMemcpyHostToDevice, sq));
     auto pull = [&](const double *hw, int len, int oV, int oX, int oW, int o5) -> int {
         if (!hw || len == 0) return MLD_OK;
-        DevBuf<double> wbuf;      /* (released on every return path) */
-        HIP_TRY(wbuf.alloc((size_t)len * M));
-        double *d_w = wbuf.p;
+        DevBuf<double> d_w;      /* (released on every return path) */
+        HIP_TRY(d_w.alloc((size_t)len * M));
         HIP_TRY(hipMemcpyAsync(d_w, hw, sizeof(double) * len * M, hipMemcpyHostToDevice, sq));
         const dim3 blk(256);
         if (t->d_out[oV]) hipLaunchKernelGGL(k_pullback, dim3((n + 255) / 256, M), blk, 0, sq, len, n, t->d_out[oV], t->lay.out_size[oV], d_w, (size_t)len, p->d_q0, (size_t)n, 1);
@@ -518,34 +498,27 @@ static int set_cost_impl(mld_problem *p, const mld_cost *cost)
     }
     // quadratic part (assembled for mld_cost_assemble; the MILP solver rejects it)
     p->has_quad = cost && (cost->quad_v || cost->quad_x || cost->quad_y);
-    if (p->d_P) { (void)hipFree(p->d_P); p->d_P = nullptr; }
-    if (p->d_Qx) { (void)hipFree(p->d_Qx); p->d_Qx = nullptr; }
-    if (p->d_Qw) { (void)hipFree(p->d_Qw); p->d_Qw = nullptr; }
-    if (p->d_Ps) { (void)hipFree(p->d_Ps); p->d_Ps = nullptr; }
-    if (p->d_Wx) { (void)hipFree(p->d_Wx); p->d_Wx = nullptr; }
-    if (p->d_Wy) { (void)hipFree(p->d_Wy); p->d_Wy = nullptr; }
+    p->d_P.reset(); p->d_Qx.reset(); p->d_Qw.reset(); p->d_Ps.reset(); p->d_Wx.reset(); p->d_Wy.reset();
     if (p->has_quad) {
-        HIP_TRY(hipMalloc(&p->d_P, sizeof(double) * (size_t)n * n * M));
+        HIP_TRY(p->d_P.alloc((size_t)n * n * M));
         HIP_TRY(hipMemset(p->d_P, 0, sizeof(double) * (size_t)n * n * M));
-        if (nx) { HIP_TRY(hipMalloc(&p->d_Qx, sizeof(double) * (size_t)n * nx * M)); HIP_TRY(hipMemset(p->d_Qx, 0, sizeof(double) * (size_t)n * nx * M)); }
-        if (nW) { HIP_TRY(hipMalloc(&p->d_Qw, sizeof(double) * (size_t)n * nW * M)); HIP_TRY(hipMemset(p->d_Qw, 0, sizeof(double) * (size_t)n * nW * M)); }
+        if (nx) { HIP_TRY(p->d_Qx.alloc((size_t)n * nx * M)); HIP_TRY(hipMemset(p->d_Qx, 0, sizeof(double) * (size_t)n * nx * M)); }
+        if (nW) { HIP_TRY(p->d_Qw.alloc((size_t)n * nW * M)); HIP_TRY(hipMemset(p->d_Qw, 0, sizeof(double) * (size_t)n * nW * M)); }
         if (cost->quad_v) {
-            DevBuf<double> bW, bWs;
-            HIP_TRY(bW.alloc((size_t)n * n * M)); HIP_TRY(bWs.alloc((size_t)n * n * M));
-            double *d_W = bW.p, *d_Ws = bWs.p;
+            DevBuf<double> d_W, d_Ws;
+            HIP_TRY(d_W.alloc((size_t)n * n * M)); HIP_TRY(d_Ws.alloc((size_t)n * n * M));
             HIP_TRY(hipMemcpyAsync(d_W, cost->quad_v, sizeof(double) * (size_t)n * n * M, hipMemcpyHostToDevice, sq));
             hipLaunchKernelGGL(k_symmetrize, dim3(((size_t)n * n + 255) / 256, M), dim3(256), 0, sq, n, d_W, d_Ws, (size_t)n * n);
             HIP_TRY(hipMemcpyAsync(p->d_P, d_Ws, sizeof(double) * (size_t)n * n * M, hipMemcpyDeviceToDevice, sq));
             HIP_TRY(hipStreamSynchronize(sq));
         }
-        auto quad = [&](const double *hW, int len, int oV, int oX, int oW, int o5, double **keepW) -> int {
+        auto quad = [&](const double *hW, int len, int oV, int oX, int oW, int o5, DevBuf<double> &keepW) -> int {
             if (!hW || len == 0) return MLD_OK;
             const size_t ll = (size_t)len * len;
-            DevBuf<double> bW, bWs, bT;
-            HIP_TRY(bW.alloc(ll * M)); HIP_TRY(bWs.alloc(ll * M));
+            DevBuf<double> d_W, d_Ws, d_T;
+            HIP_TRY(d_W.alloc(ll * M)); HIP_TRY(d_Ws.alloc(ll * M));
             const size_t tcols = (size_t)std::max(std::max(n, nx), std::max(nW, 1));     /* d_T also holds the len x nx and len x nW products */
-            HIP_TRY(bT.alloc((size_t)len * tcols * M));
-            double *d_W = bW.p, *d_Ws = bWs.p, *d_T = bT.p;
+            HIP_TRY(d_T.alloc((size_t)len * tcols * M));
             HIP_TRY(hipMemcpyAsync(d_W, hW, sizeof(double) * ll * M, hipMemcpyHostToDevice, sq));
             hipLaunchKernelGGL(k_symmetrize, dim3((ll + 255) / 256, M), dim3(256), 0, sq, len, d_W, d_Ws, ll);
             // T = Ws * Mv (len x n) ; P += Mv' T ; Qx += (Ws Mx)' ... computed as Mv' (Ws Mx)
@@ -572,13 +545,12 @@ static int set_cost_impl(mld_problem *p, const mld_cost *cost)
                 }
             }
             HIP_TRY(hipStreamSynchronize(sq));
-            *keepW = d_W;      // un-symmetrised weight, kept for the objective constant e'We
-            bW.p = nullptr;    // (ownership moves to the problem)
+            keepW = std::move(d_W);      // un-symmetrised weight, kept for the objective constant e'We
             return MLD_OK;
         };
-        if ((rc = quad(cost->quad_x, NX, O_GamV, O_PhiX, O_GamW, O_Gam5, &p->d_Wx))) return rc;
-        if ((rc = quad(cost->quad_y, NY, O_LV, O_LX, O_LW, O_L5, &p->d_Wy))) return rc;
-        HIP_TRY(hipMalloc(&p->d_Ps, sizeof(double) * (size_t)n * n * M));
+        if ((rc = quad(cost->quad_x, NX, O_GamV, O_PhiX, O_GamW, O_Gam5, p->d_Wx))) return rc;
+        if ((rc = quad(cost->quad_y, NY, O_LV, O_LX, O_LW, O_L5, p->d_Wy))) return rc;
+        HIP_TRY(p->d_Ps.alloc((size_t)n * n * M));
         hipLaunchKernelGGL(k_scale_P, dim3(((size_t)n * n + 255) / 256, M), dim3(256), 0, sq, n, p->d_P, p->d_cs, p->d_Ps);
     }
     // scaled cost for the solver: qs = q0 .* cs (and with the Toeplitz-compatible column scales for the LDS-resident LP path)
@@ -605,17 +577,14 @@ int mld_opts_default(mld_opts *o)
     return MLD_OK;
 }
 
+/* the device buffers release themselves with the handle; the solve path's stream is drained first (a queued kernel may still use them and the trace) */
 int mld_problem_destroy(mld_problem_t *p)
 {
     if (!p) return MLD_OK;
-    free_batch(p);
-    if (p->own_stream) { (void)hipStreamSynchronize(p->stream); (void)hipStreamDestroy(p->stream); }
+    (void)hipStreamSynchronize(p->stream);
     if (p->ev_ok) { (void)hipEventDestroy(p->ev[0]); (void)hipEventDestroy(p->ev[1]); (void)hipEventDestroy(p->ev[2]); }
-    void *ptrs[] = {p->d_gather, p->d_statbuf, p->d_blk_t, p->d_rs_t, p->d_cs_t, p->d_lb_t, p->d_ub_t, p->d_qs_t, p->d_lpws, p->d_lp_list, p->d_Gp, p->d_actmax, p->d_csr_ptr, p->d_csc_ptr, p->d_csr_col, p->d_csc_row, p->d_csr_val, p->d_csc_val, p->d_Gs, p->d_rs, p->d_cs, p->d_qs, p->d_lb, p->d_ub, p->d_cx, p->d_cw, p->d_c0, p->d_q0, p->d_is_int,
-                    p->d_bins, p->d_binpos, p->d_colperm, p->d_P, p->d_Qx, p->d_Qw, p->d_Ps, p->d_Wx, p->d_Wy, p->d_ws, p->d_counter};
-    for (void *q : ptrs) if (q) (void)hipFree(q);
+    if (p->own_stream) (void)hipStreamDestroy(p->stream);
     if (p->h_trace) { (void)hipHostUnregister(p->h_trace); munmap(p->h_trace, p->trace_bytes); }
-    if (p->tight) mld_model_destroy(p->tight);
     delete p;
     return MLD_OK;
 }
@@ -624,9 +593,8 @@ int mld_problem_create(mld_problem_t **out, mld_model_t *model, int N_p, int N_t
                        const mld_opts *opts)
 {
     if (!out || !model || N_tilde < 1) { mld_set_error("mld_problem_create: bad arguments"); return MLD_ERR_INVALID; }
-    mld_problem *p = new mld_problem();
-    memset((void *)&p->S, 0, sizeof(p->S));
-    p->model = model; p->tight = nullptr;
+    std::unique_ptr<mld_problem, int (*)(mld_problem_t *)> p(new mld_problem(), mld_problem_destroy);      /* (every error return releases it) */
+    p->model = model;
     if (opts) p->opts = *opts; else mld_opts_default(&p->opts);
     const mld_dims &d = model->dims;
     p->N_p = N_p; p->N = N_tilde; p->nv = model->nv; p->n = N_tilde * model->nv; p->m0 = N_tilde * d.nc;
@@ -645,22 +613,6 @@ int mld_problem_create(mld_problem_t **out, mld_model_t *model, int N_p, int N_t
     }
     if (p->opts.cut_rounds <= 0 || p->opts.max_cuts == 0) { p->opts.cut_rounds = 0; }
     p->nx = d.nx; p->nW = N_tilde * d.nomega; p->n_models = model->n_models;
-    p->d_Gp = nullptr; p->d_actmax = nullptr; p->d_csr_ptr = p->d_csc_ptr = nullptr; p->d_csr_col = p->d_csc_row = nullptr; p->d_csr_val = p->d_csc_val = nullptr; p->nnz_cap = 0; p->h_trace = nullptr; p->d_trace = nullptr; p->trace_bytes = 0;
-    p->d_Gs = p->d_rs = p->d_cs = p->d_qs = p->d_lb = p->d_ub = p->d_cx = p->d_cw = p->d_c0 = p->d_q0 = nullptr;
-    p->d_is_int = nullptr; p->d_bins = nullptr; p->d_colperm = nullptr; p->d_P = p->d_Qx = p->d_Qw = nullptr; p->d_Ps = p->d_Wx = p->d_Wy = nullptr; p->d_qs_inst = p->d_rconst = nullptr; p->d_ws = nullptr; p->d_counter = nullptr;
-    p->has_quad = false; p->batch = 0; p->batch_cap = 0;
-    p->lp_ok = false; p->all_fixed = false; p->d_blk_t = p->d_rs_t = p->d_cs_t = p->d_lb_t = p->d_ub_t = p->d_qs_t = nullptr; p->d_lpws = nullptr; p->d_lp_list = nullptr; p->ev_ok = false; p->d_statbuf = nullptr; p->stream = 0; p->own_stream = false; p->in_flight = false; p->flight_lp = false; p->lds_done = false; p->d_warm = nullptr; p->has_warm = false; p->solved = false; p->advanced = false; p->d_skipped = nullptr; p->d_gather = nullptr; p->gather_cap = 0; p->d_cutoff = nullptr; p->has_cutoff = false; p->d_open_depth = nullptr; p->d_open_var = nullptr; p->d_open_val = p->d_open_flag = nullptr; p->want_open = false;
-    p->d_model_idx = nullptr; p->d_x0 = p->d_omega = nullptr; p->d_fixed = nullptr; p->d_hs = p->d_v = p->d_obj = p->d_lbnd = nullptr;
-    p->d_x0b = p->d_omegab = nullptr; p->d_perm = nullptr; p->d_groups = nullptr; p->n_groups = 0;
-    p->d_stage_x0 = p->d_stage_om = nullptr; p->n_staged = 0; p->staged_batch = 0;
-    p->d_xcols = nullptr; p->d_xrows = nullptr; p->n_xcols = 0; p->xcols_cap = 0; p->d_xcols_x = nullptr; p->has_xcols_x = false;
-    p->d_order = nullptr; p->order_batch = 0;
-    p->d_status = p->d_nodes = p->d_pivots = p->d_cuts = p->d_refac = nullptr;
-    p->d_ticks = p->d_rows = p->d_prof = nullptr;
-    p->std_block = true; p->ho_ran = false; p->ho_enable = 0; p->ho_sub_nodes = 0; p->ho_max_gen = 0; p->ho_max_children = 0; p->ho_factor = 2.0; p->in_cap = 0; p->d_binpos = nullptr;
-    p->d_tail = p->d_finished = p->d_item_src = p->d_item_root = p->d_item_gen = p->d_item_ready = p->d_item_children = nullptr; p->d_item_label = nullptr;
-    p->d_mg_best = p->d_mg_lbopen = p->d_mg_label = nullptr; p->d_mg_open = nullptr; memset(p->ho_stats, 0, sizeof(p->ho_stats));
-    p->d_tree_count = p->d_tree_dead = nullptr; p->ho_max_tree = 160; p->ho_donate = 0; p->ho_rounds = 0;
     const int n = p->n, m0 = p->m0, M = p->n_models;
     int rc = MLD_OK;
     // 1. tightened copy of the model, condensed on device (K1+K2)
@@ -670,8 +622,10 @@ int mld_problem_create(mld_problem_t **out, mld_model_t *model, int N_p, int N_t
         if (p->opts.presolve & 2) for (int k = 0; k < M * steps; ++k) tighten::run(d, hm, (size_t)k);
         const double *ptrs[20];
         for (int k = 0; k < 20; ++k) ptrs[k] = hm[k].empty() ? nullptr : hm[k].data();
-        if ((rc = model_create_impl(&p->tight, &d, M, model->tv_N, ptrs))) { delete p; return rc; }
-        if ((rc = condense_model_device(p->tight, N_tilde, nullptr, 0))) { mld_problem_destroy(p); return rc; }
+        mld_model *t = nullptr;
+        if ((rc = model_create_impl(&t, &d, M, model->tv_N, ptrs))) return rc;
+        p->tight.reset(t);
+        if ((rc = condense_model_device(t, N_tilde, nullptr, 0))) return rc;
     }
     // 2. variable layout: bounds + binaries  (variables.py:189-243 ; mld_model.py:294-345)
     std::vector<double> lb((size_t)n, -std::numeric_limits<double>::infinity()), ub((size_t)n, std::numeric_limits<double>::infinity());
@@ -691,7 +645,7 @@ int mld_problem_create(mld_problem_t **out, mld_model_t *model, int N_p, int N_t
     std::vector<double> G((size_t)m0 * n * M), rs((size_t)m0 * M, 1.0), cs((size_t)n * M, 1.0);
     if (m0 && n) {
         hipError_t e = hipMemcpy(G.data(), p->tight->d_out[O_HV], sizeof(double) * G.size(), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { mld_set_error("D2H H_v: %s", hipGetErrorString(e)); mld_problem_destroy(p); return MLD_ERR_HIP; }
+        if (e != hipSuccess) { mld_set_error("D2H H_v: %s", hipGetErrorString(e)); return MLD_ERR_HIP; }
     }
     for (int k = 0; k < M; ++k) {
         double *g = G.data() + (size_t)k * m0 * n, *r = rs.data() + (size_t)k * m0, *c = cs.data() + (size_t)k * n;
@@ -712,12 +666,11 @@ int mld_problem_create(mld_problem_t **out, mld_model_t *model, int N_p, int N_t
         for (int i = 0; i < m0; ++i)
             for (int j = 0; j < n; ++j) g[(size_t)i * n + j] *= r[i] * c[j];
     }
-    p->h_cs = cs;
     std::vector<double> lbs((size_t)n * M), ubs((size_t)n * M);
     for (int k = 0; k < M; ++k)
         for (int j = 0; j < n; ++j) { lbs[(size_t)k * n + j] = lb[j] / cs[(size_t)k * n + j]; ubs[(size_t)k * n + j] = ub[j] / cs[(size_t)k * n + j]; }
-    if ((rc = upload(&p->d_Gs, G)) || (rc = upload(&p->d_rs, rs)) || (rc = upload(&p->d_cs, cs)) || (rc = upload(&p->d_lb, lbs)) ||
-        (rc = upload(&p->d_ub, ubs))) { mld_problem_destroy(p); return rc; }
+    if ((rc = upload(p->d_Gs, G)) || (rc = upload(p->d_rs, rs)) || (rc = upload(p->d_cs, cs)) || (rc = upload(p->d_lb, lbs)) ||
+        (rc = upload(p->d_ub, ubs))) return rc;
     {
         int cap = 0;
         for (size_t r = 0; r < (size_t)M * m0; ++r) {
@@ -740,7 +693,7 @@ int mld_problem_create(mld_problem_t **out, mld_model_t *model, int N_p, int N_t
                 }
                 am[(size_t)k * m0 + i] = inf ? (double)INFINITY : act;
             }
-        if ((rc = upload(&p->d_actmax, am))) { mld_problem_destroy(p); return rc; }
+        if ((rc = upload(p->d_actmax, am))) return rc;
     }
     if (m0 && n && (p->opts.presolve & 4) && m0 < 65536 && n < 65536) {
         /* the scaled rows once more, sparse (by row and by column): the per-instance presolve walks the non-zeros only (cfg4: 5 450 of 287 500) */
@@ -767,51 +720,28 @@ int mld_problem_create(mld_problem_t **out, mld_model_t *model, int N_p, int N_t
             cp[n] = (int)e;
         }
         p->nnz_cap = (int)cap;
-        hipError_t e = hipMalloc(&p->d_csr_ptr, sizeof(int) * rptr.size());
-        if (e == hipSuccess) e = hipMemcpy(p->d_csr_ptr, rptr.data(), sizeof(int) * rptr.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMalloc(&p->d_csc_ptr, sizeof(int) * cptr.size());
-        if (e == hipSuccess) e = hipMemcpy(p->d_csc_ptr, cptr.data(), sizeof(int) * cptr.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMalloc(&p->d_csr_col, sizeof(unsigned short) * rcol.size());
-        if (e == hipSuccess) e = hipMemcpy(p->d_csr_col, rcol.data(), sizeof(unsigned short) * rcol.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMalloc(&p->d_csc_row, sizeof(unsigned short) * crow.size());
-        if (e == hipSuccess) e = hipMemcpy(p->d_csc_row, crow.data(), sizeof(unsigned short) * crow.size(), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { mld_set_error("sparse rows: %s", hipGetErrorString(e)); mld_problem_destroy(p); return MLD_ERR_HIP; }
-        if ((rc = upload(&p->d_csr_val, rval)) || (rc = upload(&p->d_csc_val, cval))) { mld_problem_destroy(p); return rc; }
+        if ((rc = upload(p->d_csr_ptr, rptr)) || (rc = upload(p->d_csc_ptr, cptr)) || (rc = upload(p->d_csr_col, rcol)) || (rc = upload(p->d_csc_row, crow)) ||
+            (rc = upload(p->d_csr_val, rval)) || (rc = upload(p->d_csc_val, cval))) return rc;
     }
     {
-        hipError_t e = hipMalloc(&p->d_is_int, std::max(1, n));
-        if (e == hipSuccess && n) e = hipMemcpy(p->d_is_int, is_int.data(), n, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMalloc(&p->d_bins, sizeof(int) * std::max(1, p->nb));
-        if (e == hipSuccess && p->nb) e = hipMemcpy(p->d_bins, bins.data(), sizeof(int) * p->nb, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMalloc(&p->d_binpos, sizeof(int) * std::max(1, n));
-        if (e == hipSuccess && n) {
-            std::vector<int> pos(n, -1);
-            for (int k = 0; k < p->nb; ++k) pos[bins[k]] = k;
-            e = hipMemcpy(p->d_binpos, pos.data(), sizeof(int) * n, hipMemcpyHostToDevice);
-        }
-        if (e == hipSuccess) e = hipMalloc(&p->d_colperm, sizeof(int) * std::max(1, n));
-        if (e == hipSuccess && n) {
-            // dictionary column order: position-major (all horizon steps of one per-step variable adjacent), so that the
-            // non-zeros of a pivot row -- which follow the per-step coupling pattern -- fall into few 64-byte sectors
-            std::vector<int> perm(n);
-            int c = 0;
-            for (int pos = 0; pos < p->nv; ++pos) for (int k = 0; k < N_tilde; ++k) perm[c++] = k * p->nv + pos;
-            e = hipMemcpy(p->d_colperm, perm.data(), sizeof(int) * n, hipMemcpyHostToDevice);
-            if (e == hipSuccess && m0) {
-                std::vector<double> Gp((size_t)M * m0 * n);
-                for (size_t r = 0; r < (size_t)M * m0; ++r)
-                    for (int k = 0; k < n; ++k) Gp[r * n + k] = G[r * n + perm[k]];
-                e = hipMalloc(&p->d_Gp, sizeof(double) * Gp.size());
-                if (e == hipSuccess) e = hipMemcpy(p->d_Gp, Gp.data(), sizeof(double) * Gp.size(), hipMemcpyHostToDevice);
-            }
-        }
-        if (e == hipSuccess) e = hipMalloc(&p->d_qs, sizeof(double) * std::max(1, n) * M);
-        if (e == hipSuccess) e = hipMalloc(&p->d_q0, sizeof(double) * std::max(1, n) * M);
-        if (e == hipSuccess) e = hipMalloc(&p->d_cx, sizeof(double) * std::max(1, p->nx) * M);
-        if (e == hipSuccess) e = hipMalloc(&p->d_cw, sizeof(double) * std::max(1, p->nW) * M);
-        if (e == hipSuccess) e = hipMalloc(&p->d_c0, sizeof(double) * M);
-        if (e == hipSuccess) e = hipMalloc(&p->d_counter, sizeof(int));
-        if (e != hipSuccess) { mld_set_error("problem alloc: %s", hipGetErrorString(e)); mld_problem_destroy(p); return MLD_ERR_HIP; }
+        std::vector<int> pos(n, -1), perm(n);
+        for (int k = 0; k < p->nb; ++k) pos[bins[k]] = k;
+        // dictionary column order: position-major (all horizon steps of one per-step variable adjacent), so that the
+        // non-zeros of a pivot row -- which follow the per-step coupling pattern -- fall into few 64-byte sectors
+        int c = 0;
+        for (int q = 0; q < p->nv; ++q) for (int k = 0; k < N_tilde; ++k) perm[c++] = k * p->nv + q;
+        std::vector<double> Gp((size_t)M * m0 * n);
+        for (size_t r = 0; r < (size_t)M * m0; ++r)
+            for (int k = 0; k < n; ++k) Gp[r * n + k] = G[r * n + perm[k]];
+        if ((rc = upload(p->d_is_int, is_int)) || (rc = upload(p->d_bins, bins)) || (rc = upload(p->d_binpos, pos)) || (rc = upload(p->d_colperm, perm)) ||
+            (rc = upload(p->d_Gp, Gp))) return rc;
+        hipError_t e = p->d_qs.alloc((size_t)std::max(1, n) * M);
+        if (e == hipSuccess) e = p->d_q0.alloc((size_t)std::max(1, n) * M);
+        if (e == hipSuccess) e = p->d_cx.alloc((size_t)std::max(1, p->nx) * M);
+        if (e == hipSuccess) e = p->d_cw.alloc((size_t)std::max(1, p->nW) * M);
+        if (e == hipSuccess) e = p->d_c0.alloc(M);
+        if (e == hipSuccess) e = p->d_counter.alloc(1);
+        if (e != hipSuccess) { mld_set_error("problem alloc: %s", hipGetErrorString(e)); return MLD_ERR_HIP; }
     }
     // 3b. LDS-resident LP path: Toeplitz-compatible equilibration (one factor per row-in-step and per variable-in-step, so that the
     //     scaled H_v is still block Toeplitz) of the tightened model's lag blocks; only time-invariant models
@@ -842,7 +772,6 @@ int mld_problem_create(mld_problem_t **out, mld_model_t *model, int N_p, int N_t
                 for (int i = 0; i < m0; ++i) rst[(size_t)k * m0 + i] = r[i % nc];
                 for (int j = 0; j < n; ++j) { const double cj = c[j % nv]; cst[(size_t)k * n + j] = cj; lbt[(size_t)k * n + j] = lb[j] / cj; ubt[(size_t)k * n + j] = ub[j] / cj; }
             }
-            p->h_cs_t = cst;
             LpShape &LS = p->LS;
             LS.n = n; LS.m = m0; LS.N = N; LS.nc = nc; LS.nv = nv; LS.nx = p->nx; LS.nW = p->nW; LS.max_pivots = p->opts.max_pivots;
             int dev = 0; hipDeviceProp_t prop;
@@ -856,18 +785,17 @@ int mld_problem_create(mld_problem_t **out, mld_model_t *model, int N_p, int N_t
             if (kc >= 8 && n < 32767 && m0 < 32767) {
                 LS.kcap = kc; LS.ldw = kc + 1; LS.f32_off = (int)dbl_for(kc); p->lp_lds_bytes = lds_for(kc);
                 p->lp_slots = prop.multiProcessorCount;
-                hipError_t e = hipSuccess;
-                if ((rc = upload(&p->d_blk_t, blk)) || (rc = upload(&p->d_rs_t, rst)) || (rc = upload(&p->d_cs_t, cst)) || (rc = upload(&p->d_lb_t, lbt)) || (rc = upload(&p->d_ub_t, ubt))) { mld_problem_destroy(p); return rc; }
-                e = hipMalloc(&p->d_qs_t, sizeof(double) * (size_t)n * M);
-                if (e != hipSuccess) { mld_set_error("lp path alloc: %s", hipGetErrorString(e)); mld_problem_destroy(p); return MLD_ERR_HIP; }
+                if ((rc = upload(p->d_blk_t, blk)) || (rc = upload(p->d_rs_t, rst)) || (rc = upload(p->d_cs_t, cst)) || (rc = upload(p->d_lb_t, lbt)) || (rc = upload(p->d_ub_t, ubt))) return rc;
+                const hipError_t e = p->d_qs_t.alloc((size_t)n * M);
+                if (e != hipSuccess) { mld_set_error("lp path alloc: %s", hipGetErrorString(e)); return MLD_ERR_HIP; }
                 p->lp_ok = true;
             }
         }
     }
     // 4. cost (K4)
-    if ((rc = set_cost_impl(p, cost))) { mld_problem_destroy(p); return rc; }
+    if ((rc = set_cost_impl(p.get(), cost))) return rc;
     // 5. workspace: one dictionary per resident workgroup
-    build_shape(p);
+    build_shape(p.get());
     {
         int dev = 0; hipDeviceProp_t prop;
         (void)hipGetDevice(&dev); (void)hipGetDeviceProperties(&prop, dev);
@@ -879,13 +807,13 @@ int mld_problem_create(mld_problem_t **out, mld_model_t *model, int N_p, int N_t
         size_t free_b = 0, total_b = 0;
         (void)hipMemGetInfo(&free_b, &total_b);
         while (p->n_slots > 1 && (size_t)p->n_slots * p->S.ws_stride > free_b / 2) p->n_slots /= 2;
-        if (p->lds_bytes > 150 * 1024) { mld_set_error("problem too large for LDS staging (%zu bytes)", p->lds_bytes); mld_problem_destroy(p); return MLD_ERR_UNSUPPORTED; }
-        hipError_t e = hipMalloc(&p->d_ws, (size_t)p->n_slots * p->S.ws_stride);
-        if (e != hipSuccess) { mld_set_error("workspace alloc (%zu MB): %s", (size_t)p->n_slots * p->S.ws_stride >> 20, hipGetErrorString(e)); mld_problem_destroy(p); return MLD_ERR_HIP; }
+        if (p->lds_bytes > 150 * 1024) { mld_set_error("problem too large for LDS staging (%zu bytes)", p->lds_bytes); return MLD_ERR_UNSUPPORTED; }
+        hipError_t e = p->d_ws.alloc((size_t)p->n_slots * p->S.ws_stride);
+        if (e != hipSuccess) { mld_set_error("workspace alloc (%zu MB): %s", (size_t)p->n_slots * p->S.ws_stride >> 20, hipGetErrorString(e)); return MLD_ERR_HIP; }
         if (p->lds_bytes > 48 * 1024)
             (void)hipFuncSetAttribute((const void *)k_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_bytes);
     }
-    *out = p;
+    *out = p.release();
     return MLD_OK;
 }
 
@@ -951,41 +879,41 @@ static int ensure_batch(mld_problem *p, int batch)
     free_batch(p);
     const size_t b = batch;
     /* inputs: one per instance */
-    HIP_TRY(hipMalloc(&p->d_model_idx, sizeof(int) * b));
-    HIP_TRY(hipMalloc(&p->d_x0, sizeof(double) * b * std::max(1, p->nx)));
-    HIP_TRY(hipMalloc(&p->d_omega, sizeof(double) * b * std::max(1, p->nW)));
-    HIP_TRY(hipMalloc(&p->d_x0b, sizeof(double) * b * std::max(1, p->nx)));
-    HIP_TRY(hipMalloc(&p->d_omegab, sizeof(double) * b * std::max(1, p->nW)));
-    HIP_TRY(hipMalloc(&p->d_warm, b * std::max(1, p->nb)));
-    HIP_TRY(hipMalloc(&p->d_skipped, sizeof(int)));
-    HIP_TRY(hipMalloc(&p->d_hs, sizeof(double) * b * std::max(1, p->m0)));
-    HIP_TRY(hipMalloc(&p->d_qs_inst, sizeof(double) * b * std::max(1, p->n)));
-    HIP_TRY(hipMalloc(&p->d_rconst, sizeof(double) * b));
-    HIP_TRY(hipMalloc(&p->d_order, sizeof(int) * b));
+    HIP_TRY(p->bat.model_idx.alloc(b));
+    HIP_TRY(p->bat.x0.alloc(b * std::max(1, p->nx)));
+    HIP_TRY(p->bat.omega.alloc(b * std::max(1, p->nW)));
+    HIP_TRY(p->bat.x0b.alloc(b * std::max(1, p->nx)));
+    HIP_TRY(p->bat.omegab.alloc(b * std::max(1, p->nW)));
+    HIP_TRY(p->bat.warm.alloc(b * std::max(1, p->nb)));
+    HIP_TRY(p->bat.skipped.alloc(1));
+    HIP_TRY(p->bat.hs.alloc(b * std::max(1, p->m0)));
+    HIP_TRY(p->bat.qs_inst.alloc(b * std::max(1, p->n)));
+    HIP_TRY(p->bat.rconst.alloc(b));
+    HIP_TRY(p->bat.order.alloc(b));
     /* per entry (instances, then the items of the in-kernel hand-off) */
-    HIP_TRY(hipMalloc(&p->d_fixed, cap * std::max(1, p->nb)));
-    HIP_TRY(hipMalloc(&p->d_cutoff, sizeof(double) * cap));
-    HIP_TRY(hipMalloc(&p->d_open_depth, sizeof(int) * cap));
-    HIP_TRY(hipMalloc(&p->d_open_var, sizeof(short) * cap * std::max(1, p->nb)));
-    HIP_TRY(hipMalloc(&p->d_open_val, cap * std::max(1, p->nb)));
-    HIP_TRY(hipMalloc(&p->d_open_flag, cap * std::max(1, p->nb)));
-    HIP_TRY(hipMalloc(&p->d_v, sizeof(double) * cap * std::max(1, p->n)));
-    HIP_TRY(hipMalloc(&p->d_obj, sizeof(double) * cap));
-    HIP_TRY(hipMalloc(&p->d_lbnd, sizeof(double) * cap));
-    HIP_TRY(hipMalloc(&p->d_status, sizeof(int) * cap)); HIP_TRY(hipMalloc(&p->d_nodes, sizeof(int) * cap));
-    HIP_TRY(hipMalloc(&p->d_pivots, sizeof(int) * cap)); HIP_TRY(hipMalloc(&p->d_cuts, sizeof(int) * cap));
-    HIP_TRY(hipMalloc(&p->d_refac, sizeof(int) * cap));
-    HIP_TRY(hipMemset(p->d_status, 0, sizeof(int) * cap));      /* (ADVICE r3: a reallocation must not leave stale statuses for mld_warm_start_from_previous) */
-    HIP_TRY(hipMalloc(&p->d_ticks, sizeof(long long) * cap)); HIP_TRY(hipMalloc(&p->d_rows, sizeof(long long) * cap));
-    HIP_TRY(hipMalloc(&p->d_prof, sizeof(long long) * cap * 8));
+    HIP_TRY(p->bat.fixed.alloc(cap * std::max(1, p->nb)));
+    HIP_TRY(p->bat.cutoff.alloc(cap));
+    HIP_TRY(p->bat.open_depth.alloc(cap));
+    HIP_TRY(p->bat.open_var.alloc(cap * std::max(1, p->nb)));
+    HIP_TRY(p->bat.open_val.alloc(cap * std::max(1, p->nb)));
+    HIP_TRY(p->bat.open_flag.alloc(cap * std::max(1, p->nb)));
+    HIP_TRY(p->bat.v.alloc(cap * std::max(1, p->n)));
+    HIP_TRY(p->bat.obj.alloc(cap));
+    HIP_TRY(p->bat.lbnd.alloc(cap));
+    HIP_TRY(p->bat.status.alloc(cap)); HIP_TRY(p->bat.nodes.alloc(cap));
+    HIP_TRY(p->bat.pivots.alloc(cap)); HIP_TRY(p->bat.cuts.alloc(cap));
+    HIP_TRY(p->bat.refac.alloc(cap));
+    HIP_TRY(hipMemset(p->bat.status, 0, sizeof(int) * cap));      /* (ADVICE r3: a reallocation must not leave stale statuses for mld_warm_start_from_previous) */
+    HIP_TRY(p->bat.ticks.alloc(cap)); HIP_TRY(p->bat.rows.alloc(cap));
+    HIP_TRY(p->bat.prof.alloc(cap * 8));
     if (p->ho_enable) {
-        HIP_TRY(hipMalloc(&p->d_tail, sizeof(int))); HIP_TRY(hipMalloc(&p->d_finished, sizeof(int)));
-        HIP_TRY(hipMalloc(&p->d_item_src, sizeof(int) * cap)); HIP_TRY(hipMalloc(&p->d_item_root, sizeof(int) * cap));
-        HIP_TRY(hipMalloc(&p->d_item_gen, sizeof(int) * cap)); HIP_TRY(hipMalloc(&p->d_item_ready, sizeof(int) * cap));
-        HIP_TRY(hipMalloc(&p->d_item_children, sizeof(int) * cap)); HIP_TRY(hipMalloc(&p->d_item_label, sizeof(long long) * cap));
-        HIP_TRY(hipMalloc(&p->d_mg_best, sizeof(unsigned long long) * b)); HIP_TRY(hipMalloc(&p->d_mg_lbopen, sizeof(unsigned long long) * b));
-        HIP_TRY(hipMalloc(&p->d_mg_label, sizeof(unsigned long long) * b)); HIP_TRY(hipMalloc(&p->d_mg_open, sizeof(int) * b));
-        HIP_TRY(hipMalloc(&p->d_tree_count, sizeof(int) * b * 9)); HIP_TRY(hipMalloc(&p->d_tree_dead, sizeof(int) * b));
+        HIP_TRY(p->bat.ho.tail.alloc(1)); HIP_TRY(p->bat.ho.finished.alloc(1));
+        HIP_TRY(p->bat.ho.item_src.alloc(cap)); HIP_TRY(p->bat.ho.item_root.alloc(cap));
+        HIP_TRY(p->bat.ho.item_gen.alloc(cap)); HIP_TRY(p->bat.ho.item_ready.alloc(cap));
+        HIP_TRY(p->bat.ho.item_children.alloc(cap)); HIP_TRY(p->bat.ho.item_label.alloc(cap));
+        HIP_TRY(p->bat.ho.mg_best.alloc(b)); HIP_TRY(p->bat.ho.mg_lbopen.alloc(b));
+        HIP_TRY(p->bat.ho.mg_label.alloc(b)); HIP_TRY(p->bat.ho.mg_open.alloc(b));
+        HIP_TRY(p->bat.ho.tree_count.alloc(b * 9)); HIP_TRY(p->bat.ho.tree_dead.alloc(b));
     }
     p->order_batch = 0;
     p->in_cap = batch;
@@ -1011,17 +939,14 @@ int mld_upload_batch(mld_problem_t *p, int batch, const int32_t *model_idx, cons
     {
         std::vector<int> perm; std::vector<RhsGroup> groups;
         build_rhs_groups(model_idx, batch, p->n_models, perm, groups);
-        if (p->d_perm) { (void)hipFree(p->d_perm); p->d_perm = nullptr; }
-        if (p->d_groups) { (void)hipFree(p->d_groups); p->d_groups = nullptr; }
+        p->bat.perm.reset(); p->bat.groups.reset();
         p->n_groups = (int)groups.size();
-        if (!perm.empty()) { HIP_TRY(hipMalloc(&p->d_perm, sizeof(int) * perm.size())); HIP_TRY(hipMemcpy(p->d_perm, perm.data(), sizeof(int) * perm.size(), hipMemcpyHostToDevice)); }
-        HIP_TRY(hipMalloc(&p->d_groups, sizeof(RhsGroup) * groups.size()));
-        HIP_TRY(hipMemcpy(p->d_groups, groups.data(), sizeof(RhsGroup) * groups.size(), hipMemcpyHostToDevice));
+        if ((rc = upload(p->bat.perm, perm)) || (rc = upload(p->bat.groups, groups))) return rc;
     }
-    if (model_idx) HIP_TRY(hipMemcpy(p->d_model_idx, model_idx, sizeof(int) * batch, hipMemcpyHostToDevice));
-    if (p->nx) HIP_TRY(hipMemcpy(p->d_x0, x0, sizeof(double) * (size_t)batch * p->nx, hipMemcpyHostToDevice));
-    if (p->nW) HIP_TRY(hipMemcpy(p->d_omega, omega, sizeof(double) * (size_t)batch * p->nW, hipMemcpyHostToDevice));
-    if (fixed_bin && p->nb) HIP_TRY(hipMemcpy(p->d_fixed, fixed_bin, (size_t)batch * p->nb, hipMemcpyHostToDevice));
+    if (model_idx) HIP_TRY(hipMemcpy(p->bat.model_idx, model_idx, sizeof(int) * batch, hipMemcpyHostToDevice));
+    if (p->nx) HIP_TRY(hipMemcpy(p->bat.x0, x0, sizeof(double) * (size_t)batch * p->nx, hipMemcpyHostToDevice));
+    if (p->nW) HIP_TRY(hipMemcpy(p->bat.omega, omega, sizeof(double) * (size_t)batch * p->nW, hipMemcpyHostToDevice));
+    if (fixed_bin && p->nb) HIP_TRY(hipMemcpy(p->bat.fixed, fixed_bin, (size_t)batch * p->nb, hipMemcpyHostToDevice));
     return MLD_OK;
 }
 
@@ -1041,23 +966,21 @@ int mld_upload_constraint_blocks_x(mld_problem_t *p, int n_cols, const double *o
     if (n_cols == 0 || !p->nW) return MLD_OK;
     const size_t need = (size_t)p->batch * n_cols * p->nW;
     if (need > p->xcols_cap) {
-        if (p->d_xcols) (void)hipFree(p->d_xcols);
-        p->d_xcols = nullptr; p->xcols_cap = 0;
-        HIP_TRY(hipMalloc(&p->d_xcols, sizeof(double) * need));
+        p->xcols_cap = 0;
+        HIP_TRY(p->bat.xcols.alloc(need));
         p->xcols_cap = need;
     }
-    if (p->d_xrows) { (void)hipFree(p->d_xrows); p->d_xrows = nullptr; }
-    HIP_TRY(hipMemcpy(p->d_xcols, omega_cols, sizeof(double) * need, hipMemcpyHostToDevice));
+    p->bat.xrows.reset();
+    HIP_TRY(hipMemcpy(p->bat.xcols, omega_cols, sizeof(double) * need, hipMemcpyHostToDevice));
     if (col_rows) {
-        HIP_TRY(hipMalloc(&p->d_xrows, sizeof(int) * n_cols));
-        HIP_TRY(hipMemcpy(p->d_xrows, col_rows, sizeof(int) * n_cols, hipMemcpyHostToDevice));
+        HIP_TRY(p->bat.xrows.alloc(n_cols));
+        HIP_TRY(hipMemcpy(p->bat.xrows, col_rows, sizeof(int) * n_cols, hipMemcpyHostToDevice));
     }
     p->has_xcols_x = false;
     if (x_cols && p->nx) {
-        if (p->d_xcols_x) { (void)hipFree(p->d_xcols_x); p->d_xcols_x = nullptr; }
         const size_t nxs = (size_t)p->batch * n_cols * p->nx;
-        HIP_TRY(hipMalloc(&p->d_xcols_x, sizeof(double) * nxs));
-        HIP_TRY(hipMemcpy(p->d_xcols_x, x_cols, sizeof(double) * nxs, hipMemcpyHostToDevice));
+        HIP_TRY(p->bat.xcols_x.alloc(nxs));
+        HIP_TRY(hipMemcpy(p->bat.xcols_x, x_cols, sizeof(double) * nxs, hipMemcpyHostToDevice));
         p->has_xcols_x = true;
     }
     p->n_xcols = n_cols;
@@ -1172,209 +1095,265 @@ __global__ void __launch_bounds__(256) k_batch_stats(int batch, const int *statu
     if (threadIdx.x < 8) out[threadIdx.x] = acc[threadIdx.x];
 }
 
-/* mode 0: launch and finish (mld_solve_resident); 1: launch only -- returns once the kernels are queued on the problem's stream (the LDS
- * paths, which need their results on the host for the fall-back, run to completion here); 2: finish a launched solve */
-static int solve_impl(mld_problem_t *p, mld_stats *st, int mode)
+/* LDS-resident LP path -- relaxation-only mode: every binary fixed -> one LP per instance, solved in LDS (k_lp_lds); right-hand sides with the
+ * Toeplitz row scales.  Runs to completion: redo lists the instances whose working basis outgrew LDS (status -1), for the dense kernel. */
+static int launch_lds_lp(mld_problem *p, std::vector<int> &redo)
+{
+    const hipStream_t sq = p->stream;
+    const int batch = p->batch;
+    const mld_model *t = p->tight.get();
+    launch_rhs_mfma((p->opts.flags & MLD_F32) != 0, p->n_groups, p->m0, p->nx, p->nW, t->d_out[O_HX], t->d_out[O_HW], t->d_out[O_H5], p->d_rs_t,
+                    p->bat.groups, p->bat.perm, p->bat.x0, p->bat.omega, p->bat.hs, sq);
+    if (p->n_xcols > 0)
+        hipLaunchKernelGGL(k_rhs_extra, dim3(batch), dim3(256), 0, sq, p->m0, p->nx, p->nW, t->d_out[O_HX], t->d_out[O_HW], t->d_out[O_H5],
+                           p->d_rs_t, p->has_midx ? p->bat.model_idx.get() : nullptr, p->bat.x0, p->bat.xcols, p->n_xcols, p->bat.xrows, p->bat.hs, p->has_xcols_x ? p->bat.xcols_x.get() : nullptr);
+    HIP_TRY(hipEventRecord(p->ev[1], sq));
+    LpModelDev LM; LM.blk = p->d_blk_t; LM.qs = p->d_qs_t; LM.lb = p->d_lb_t; LM.ub = p->d_ub_t; LM.cs = p->d_cs_t;
+    LM.cx = p->nx ? p->d_cx.get() : nullptr; LM.cw = p->nW ? p->d_cw.get() : nullptr; LM.c0 = p->d_c0; LM.bins = p->d_bins; LM.nb = p->nb; LM.is_int = p->d_is_int;
+    LpBatchDev LB; LB.batch = batch; LB.model_idx = p->has_midx ? p->bat.model_idx.get() : nullptr; LB.x0 = p->bat.x0; LB.omega = p->bat.omega; LB.hs = p->bat.hs;
+    LB.fixed = p->bat.fixed; LB.v_out = p->bat.v; LB.obj_out = p->bat.obj; LB.lb_out = p->bat.lbnd; LB.status_out = p->bat.status; LB.nodes_out = p->bat.nodes;
+    LB.pivots_out = p->bat.pivots; LB.ticks_out = p->bat.ticks; LB.prof_out = p->bat.prof; LB.counter = p->d_counter; LB.cuts_out = p->bat.cuts;
+    p->LS.max_pivots = p->opts.max_pivots;
+    HIP_TRY(hipMemsetAsync(p->bat.cuts, 0, sizeof(int) * batch, sq));
+    HIP_TRY(hipFuncSetAttribute((const void *)k_lp_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lp_lds_bytes));
+    hipLaunchKernelGGL(k_lp_lds, dim3(std::min(batch, p->lp_slots)), dim3(LP_NT), p->lp_lds_bytes, sq, p->LS, LM, LB, (unsigned char *)nullptr);
+    HIP_TRY(hipMemsetAsync(p->bat.refac, 0, sizeof(int) * batch, sq));
+    HIP_TRY(hipMemsetAsync(p->bat.rows, 0, sizeof(long long) * batch, sq));
+    HIP_TRY(hipStreamSynchronize(sq));
+    HIP_TRY(hipGetLastError());
+    std::vector<int> stat(batch);
+    HIP_TRY(hipMemcpy(stat.data(), p->bat.status, sizeof(int) * batch, hipMemcpyDeviceToHost));
+    redo.clear();
+    if (!(p->opts.reserved & 2048))      /* diagnostics: bit 11 leaves status -1 visible instead of re-solving */
+        for (int i = 0; i < batch; ++i) if (stat[i] == -1) redo.push_back(i);
+    return MLD_OK;
+}
+
+/* right-hand sides of the dense path (K3) with the extra constraint blocks, and the per-instance part of a quadratic cost */
+static int launch_rhs_cost(mld_problem *p)
+{
+    const hipStream_t sq = p->stream;
+    const int batch = p->batch;
+    const mld_model *t = p->tight.get();
+    const int *midx = p->has_midx ? p->bat.model_idx.get() : nullptr;
+    if (p->m0 && !p->std_block)        /* no standard block: every row starts without a right-hand side; the extra blocks' row-wise minimum follows */
+        hipLaunchKernelGGL(k_fill_f64, dim3((unsigned)(((size_t)batch * p->m0 + 255) / 256)), dim3(256), 0, sq, (size_t)batch * p->m0, 1.0e30, p->bat.hs);
+    else if (p->m0 && rhs_mfma_fits(p->nx, p->nW) && !(p->opts.reserved & 128))     /* K3 as one GEMM per model on the matrix cores */
+        launch_rhs_mfma((p->opts.flags & MLD_F32) != 0, p->n_groups, p->m0, p->nx, p->nW, t->d_out[O_HX], t->d_out[O_HW], t->d_out[O_H5], p->d_rs,
+                        p->bat.groups, p->bat.perm, p->bat.x0, p->bat.omega, p->bat.hs, sq);
+    else if (p->m0)
+        hipLaunchKernelGGL(k_rhs, dim3(batch), dim3(256), 0, sq, p->m0, p->nx, p->nW, t->d_out[O_HX], t->d_out[O_HW], t->d_out[O_H5],
+                           p->d_rs, midx, p->bat.x0, p->bat.omega, p->bat.hs, 1);
+    if (p->m0 && p->n_xcols > 0)
+        hipLaunchKernelGGL(k_rhs_extra, dim3(batch), dim3(256), 0, sq, p->m0, p->nx, p->nW, t->d_out[O_HX], t->d_out[O_HW], t->d_out[O_H5],
+                           p->d_rs, midx, p->bat.x0, p->bat.xcols, p->n_xcols, p->bat.xrows, p->bat.hs, p->has_xcols_x ? p->bat.xcols_x.get() : nullptr);
+    if (p->has_quad) {
+        const int NX = p->N * p->model->dims.nx, NY = p->N * p->model->dims.ny;
+        hipLaunchKernelGGL(k_qinst, dim3(batch), dim3(256), 0, sq, p->n, p->nx, p->nW, p->d_q0, p->d_Qx, p->d_Qw, p->d_cs, midx, p->bat.x0, p->bat.omega, p->bat.qs_inst);
+        HIP_TRY(hipMemsetAsync(p->bat.rconst, 0, sizeof(double) * batch, sq));
+        if (p->d_Wx && NX) hipLaunchKernelGGL(k_quad_const, dim3(batch), dim3(256), sizeof(double) * NX, sq, NX, p->nx, p->nW, t->d_out[O_PhiX], t->lay.out_size[O_PhiX],
+                                              t->d_out[O_GamW], t->lay.out_size[O_GamW], t->d_out[O_Gam5], t->lay.out_size[O_Gam5], p->d_Wx, midx, p->bat.x0, p->bat.omega, p->bat.rconst);
+        if (p->d_Wy && NY) hipLaunchKernelGGL(k_quad_const, dim3(batch), dim3(256), sizeof(double) * NY, sq, NY, p->nx, p->nW, t->d_out[O_LX], t->lay.out_size[O_LX],
+                                              t->d_out[O_LW], t->lay.out_size[O_LW], t->d_out[O_L5], t->lay.out_size[O_L5], p->d_Wy, midx, p->bat.x0, p->bat.omega, p->bat.rconst);
+    }
+    return MLD_OK;
+}
+
+static ProblemDev problem_dev(const mld_problem *p)
+{
+    const mld_model *t = p->tight.get();
+    ProblemDev P;
+    P.Gp = p->d_Gp; P.Gs = p->d_Gs; P.rs = p->d_rs; P.cs = p->d_cs; P.qs = p->d_qs; P.lb = p->d_lb; P.ub = p->d_ub; P.is_int = p->d_is_int;
+    P.bins = p->d_bins; P.colperm = p->d_colperm; P.Hx = t->d_out[O_HX]; P.Hw = t->d_out[O_HW]; P.H5 = t->d_out[O_H5];
+    P.cx = p->nx ? p->d_cx.get() : nullptr; P.cw = p->nW ? p->d_cw.get() : nullptr; P.c0 = p->d_c0;
+    P.Ps = p->has_quad ? p->d_Ps.get() : nullptr;
+    P.act_max = p->d_actmax;
+    P.csr_ptr = p->d_csr_ptr; P.csr_col = p->d_csr_col; P.csr_val = p->d_csr_val; P.csc_ptr = p->d_csc_ptr; P.csc_row = p->d_csc_row; P.csc_val = p->d_csc_val; P.nnz_cap = p->nnz_cap;
+    P.binpos = p->d_binpos;
+    return P;
+}
+
+/* the resident batch as k_solve sees it; with the in-kernel hand-off (ho) the fixings and cutoffs become per-entry arrays the items write */
+static BatchDev batch_dev(const mld_problem *p, bool ho)
+{
+    const BatchBufs &b = p->bat;
+    BatchDev B;
+    B.batch = p->batch; B.model_idx = p->has_midx ? b.model_idx.get() : nullptr; B.x0 = b.x0; B.omega = b.omega;
+    B.fixed = p->has_fixed || ho ? b.fixed.get() : nullptr; B.hs = b.hs;
+    B.warm = p->has_warm ? b.warm.get() : nullptr;
+    B.cutoff = p->has_cutoff || ho ? b.cutoff.get() : nullptr;
+    B.open_depth = p->want_open ? b.open_depth.get() : nullptr; B.open_var = b.open_var; B.open_val = b.open_val; B.open_flag = b.open_flag;
+    B.qs_inst = p->has_quad ? b.qs_inst.get() : nullptr; B.rconst = p->has_quad ? b.rconst.get() : nullptr; B.v_out = b.v; B.obj_out = b.obj; B.lb_out = b.lbnd;
+    B.status_out = b.status; B.nodes_out = b.nodes; B.pivots_out = b.pivots; B.cuts_out = b.cuts; B.refac_out = b.refac;
+    B.ticks_out = b.ticks; B.rows_out = b.rows; B.prof_out = b.prof; B.trace = p->d_trace;
+    B.counter = p->d_counter;
+    B.order = (p->order_batch == p->batch && !(p->opts.reserved & 8)) ? b.order.get() : nullptr;
+    B.ho = ho ? 1 | (p->has_fixed ? 0 : 2) : 0; B.cap = p->batch_cap; B.tail = b.ho.tail; B.finished = b.ho.finished;
+    B.ho_sub_nodes = p->ho_sub_nodes > 0 ? p->ho_sub_nodes : p->opts.max_nodes; B.ho_max_gen = p->ho_max_gen; B.ho_max_children = p->ho_max_children;
+    B.item_src = b.ho.item_src; B.item_root = b.ho.item_root; B.item_gen = b.ho.item_gen; B.item_label = b.ho.item_label; B.item_ready = b.ho.item_ready;
+    B.item_children = b.ho.item_children;
+    B.tree_count = b.ho.tree_count; B.tree_dead = b.ho.tree_dead; B.ho_max_tree = p->ho_max_tree; B.ho_donate = p->ho_donate; B.ho_rounds = p->ho_rounds;
+    return B;
+}
+
+/* an empty hand-off queue behind the batch's instances (before k_solve) */
+static int handoff_reset(mld_problem *p)
+{
+    const hipStream_t sq = p->stream;
+    const int batch = p->batch;
+    const BatchBufs::Handoff &q = p->bat.ho;
+    HIP_TRY(hipMemsetAsync(q.tree_count, 0, sizeof(int) * (size_t)batch * 9, sq));
+    HIP_TRY(hipMemsetAsync(q.tree_dead, 0, sizeof(int) * (size_t)batch, sq));
+    hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, sq, q.tail, batch);
+    HIP_TRY(hipMemsetAsync(q.finished, 0, sizeof(int), sq));
+    HIP_TRY(hipMemsetAsync(q.item_ready, 0, sizeof(int) * (size_t)p->batch_cap, sq));
+    HIP_TRY(hipMemsetAsync(q.item_children, 0, sizeof(int) * (size_t)p->batch_cap, sq));
+    if (!p->has_cutoff) hipLaunchKernelGGL(k_fill_f64, dim3((batch + 255) / 256), dim3(256), 0, sq, (size_t)batch, (double)INFINITY, p->bat.cutoff);
+    return MLD_OK;
+}
+
+/* merge the items into their roots after k_solve (deterministic: best objective, smallest tree label on ties) */
+static int handoff_merge(mld_problem *p)
+{
+    const hipStream_t sq = p->stream;
+    const int batch = p->batch;
+    const BatchBufs &b = p->bat;
+    const BatchBufs::Handoff &q = b.ho;
+    const int items = p->batch_cap - batch;
+    const dim3 gi((items + 255) / 256), gb((batch + 255) / 256), blk(256);
+    HIP_TRY(hipMemsetAsync(b.skipped, 0, sizeof(int), sq));
+    hipLaunchKernelGGL(k_merge_init, gb, blk, 0, sq, batch, b.obj, q.mg_best, q.mg_lbopen, q.mg_label, q.mg_open);
+    hipLaunchKernelGGL(k_merge_a, gi, blk, 0, sq, batch, q.tail, q.item_root, b.obj, b.lbnd, b.status, b.nodes, b.pivots, b.cuts, b.refac, b.rows,
+                       q.mg_best, q.mg_lbopen, q.mg_open, q.tree_dead);
+    hipLaunchKernelGGL(k_merge_b, gi, blk, 0, sq, batch, q.tail, q.item_root, b.obj, q.item_label, q.mg_best, q.mg_label, q.tree_dead);
+    hipLaunchKernelGGL(k_merge_c, dim3(items), blk, 0, sq, batch, q.tail, p->n, q.item_root, b.obj, q.item_label, q.mg_best, q.mg_label, b.v, q.tree_dead);
+    hipLaunchKernelGGL(k_merge_d, gb, blk, 0, sq, batch, p->opts.gap_abs, p->opts.gap_rel, b.obj, b.lbnd, b.status, q.mg_best, q.mg_lbopen, q.mg_open, b.skipped, q.tree_dead, q.finished);      /* (finished: the queue is drained, the counter is free) */
+    return MLD_OK;
+}
+
+/* wait for the launched solve; the handle is unlocked whatever the outcome (every entry point refuses a problem that is in flight) */
+static int wait_solve(mld_problem *p)
+{
+    const hipError_t ew = hipEventSynchronize(p->ev[2]);
+    p->flight = Flight::idle;
+    if (ew != hipSuccess) { mld_set_error("mld_solve: %s", hipGetErrorString(ew)); return MLD_ERR_HIP; }
+    HIP_TRY(hipGetLastError());
+    p->solved = true; p->advanced = false;
+    return MLD_OK;
+}
+
+/* queue a solve of the resident batch on the problem's stream.  The dense path returns with k_solve queued (Flight::queued); the LDS path,
+ * whose fall-back needs the statuses on the host, returns complete (Flight::lds_done) */
+static int launch(mld_problem *p)
 {
     if (!p || p->batch < 1) { mld_set_error("mld_solve_resident: nothing uploaded"); return MLD_ERR_INVALID; }
     const hipStream_t sq = p->stream;
     const int batch = p->batch;
     if (!p->ev_ok) {      /* the three timing events and the statistics buffer live as long as the problem */
         HIP_TRY(hipEventCreate(&p->ev[0])); HIP_TRY(hipEventCreate(&p->ev[1])); HIP_TRY(hipEventCreate(&p->ev[2]));
-        HIP_TRY(hipMalloc(&p->d_statbuf, sizeof(long long) * 8));
+        HIP_TRY(p->d_statbuf.alloc(8));
         p->ev_ok = true;
     }
-    const hipEvent_t e0 = p->ev[0], e1 = p->ev[1], e2 = p->ev[2];
-    if (mode == 2 && !p->in_flight) { mld_set_error("mld_solve_finish: no launched solve"); return MLD_ERR_INVALID; }
-    if (mode != 2 && p->in_flight) { mld_set_error("mld_solve_launch: the previous launch has not been finished"); return MLD_ERR_INVALID; }
-    mld_model *t = p->tight;
-    bool lp_path = p->flight_lp;
-    if (mode != 2) {
+    if (p->flight != Flight::idle) { mld_set_error("mld_solve_launch: the previous launch has not been finished"); return MLD_ERR_INVALID; }
     HIP_TRY(hipMemsetAsync(p->d_counter, 0, sizeof(int), sq));
-    HIP_TRY(hipEventRecord(e0, sq));
-    const bool lds_lp = p->lp_ok && p->all_fixed && !(p->opts.reserved & 256) && p->std_block;
-    lp_path = lds_lp && !p->has_quad && rhs_mfma_fits(p->nx, p->nW);
-    if (lp_path) {
-        /* relaxation-only mode: every binary fixed -> one LP per instance, solved in LDS (k_lp_lds); right-hand sides with the Toeplitz row scales */
-        launch_rhs_mfma((p->opts.flags & MLD_F32) != 0, p->n_groups, p->m0, p->nx, p->nW, t->d_out[O_HX], t->d_out[O_HW], t->d_out[O_H5], p->d_rs_t,
-                        p->d_groups, p->d_perm, p->d_x0, p->d_omega, p->d_hs, sq);
-        if (p->n_xcols > 0)
-            hipLaunchKernelGGL(k_rhs_extra, dim3(batch), dim3(256), 0, sq, p->m0, p->nx, p->nW, t->d_out[O_HX], t->d_out[O_HW], t->d_out[O_H5],
-                               p->d_rs_t, p->has_midx ? p->d_model_idx : nullptr, p->d_x0, p->d_xcols, p->n_xcols, p->d_xrows, p->d_hs, p->has_xcols_x ? p->d_xcols_x : nullptr);
-        HIP_TRY(hipEventRecord(e1, sq));
-        LpModelDev LM; LM.blk = p->d_blk_t; LM.qs = p->d_qs_t; LM.lb = p->d_lb_t; LM.ub = p->d_ub_t; LM.cs = p->d_cs_t;
-        LM.cx = p->nx ? p->d_cx : nullptr; LM.cw = p->nW ? p->d_cw : nullptr; LM.c0 = p->d_c0; LM.bins = p->d_bins; LM.nb = p->nb; LM.is_int = p->d_is_int;
-        LpBatchDev LB; LB.batch = batch; LB.model_idx = p->has_midx ? p->d_model_idx : nullptr; LB.x0 = p->d_x0; LB.omega = p->d_omega; LB.hs = p->d_hs;
-        LB.fixed = p->d_fixed; LB.v_out = p->d_v; LB.obj_out = p->d_obj; LB.lb_out = p->d_lbnd; LB.status_out = p->d_status; LB.nodes_out = p->d_nodes;
-        LB.pivots_out = p->d_pivots; LB.ticks_out = p->d_ticks; LB.prof_out = p->d_prof; LB.counter = p->d_counter; LB.cuts_out = p->d_cuts;
-        p->LS.max_pivots = p->opts.max_pivots;
-        HIP_TRY(hipMemsetAsync(p->d_cuts, 0, sizeof(int) * batch, sq));
-        HIP_TRY(hipFuncSetAttribute((const void *)k_lp_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lp_lds_bytes));
-        hipLaunchKernelGGL(k_lp_lds, dim3(std::min(batch, p->lp_slots)), dim3(LP_NT), p->lp_lds_bytes, sq, p->LS, LM, LB, p->d_lpws);
-        HIP_TRY(hipMemsetAsync(p->d_refac, 0, sizeof(int) * batch, sq));
-        HIP_TRY(hipMemsetAsync(p->d_rows, 0, sizeof(long long) * batch, sq));
-        HIP_TRY(hipStreamSynchronize(sq));
-        HIP_TRY(hipGetLastError());
-        /* instances whose working basis outgrew LDS (status -1) go to the dense kernel below */
-        std::vector<int> stat(batch), redo;
-        HIP_TRY(hipMemcpy(stat.data(), p->d_status, sizeof(int) * batch, hipMemcpyDeviceToHost));
-        if (!(p->opts.reserved & 2048))      /* diagnostics: bit 11 leaves status -1 visible instead of re-solving */
-            for (int i = 0; i < batch; ++i) if (stat[i] == -1) redo.push_back(i);
-        p->lp_redo = redo;
-    }
-    if (lp_path && p->lp_redo.empty()) {
-        HIP_TRY(hipEventRecord(e2, sq));
-        HIP_TRY(hipEventSynchronize(e2));
+    HIP_TRY(hipEventRecord(p->ev[0], sq));
+    const bool lp_path = p->lp_ok && p->all_fixed && !(p->opts.reserved & 256) && p->std_block && !p->has_quad && rhs_mfma_fits(p->nx, p->nW);
+    std::vector<int> redo;      /* LP path: the overflow instances, re-solved by k_solve */
+    int rc;
+    if (lp_path && (rc = launch_lds_lp(p, redo))) return rc;
+    if (lp_path && redo.empty()) {
+        HIP_TRY(hipEventRecord(p->ev[2], sq));
     } else {
-    if (lp_path) HIP_TRY(hipMemsetAsync(p->d_counter, 0, sizeof(int), sq));
-    if (p->m0 && !p->std_block)        /* no standard block: every row starts without a right-hand side; the extra blocks' row-wise minimum follows */
-        hipLaunchKernelGGL(k_fill_f64, dim3((unsigned)(((size_t)batch * p->m0 + 255) / 256)), dim3(256), 0, sq, (size_t)batch * p->m0, 1.0e30, p->d_hs);
-    else if (p->m0 && rhs_mfma_fits(p->nx, p->nW) && !(p->opts.reserved & 128))     /* K3 as one GEMM per model on the matrix cores */
-        launch_rhs_mfma((p->opts.flags & MLD_F32) != 0, p->n_groups, p->m0, p->nx, p->nW, t->d_out[O_HX], t->d_out[O_HW], t->d_out[O_H5], p->d_rs,
-                        p->d_groups, p->d_perm, p->d_x0, p->d_omega, p->d_hs, sq);
-    else if (p->m0)
-        hipLaunchKernelGGL(k_rhs, dim3(batch), dim3(256), 0, sq, p->m0, p->nx, p->nW, t->d_out[O_HX], t->d_out[O_HW], t->d_out[O_H5],
-                           p->d_rs, p->has_midx ? p->d_model_idx : nullptr, p->d_x0, p->d_omega, p->d_hs, 1);
-    if (p->m0 && p->n_xcols > 0)
-        hipLaunchKernelGGL(k_rhs_extra, dim3(batch), dim3(256), 0, sq, p->m0, p->nx, p->nW, t->d_out[O_HX], t->d_out[O_HW], t->d_out[O_H5],
-                           p->d_rs, p->has_midx ? p->d_model_idx : nullptr, p->d_x0, p->d_xcols, p->n_xcols, p->d_xrows, p->d_hs, p->has_xcols_x ? p->d_xcols_x : nullptr);
-    if (p->has_quad) {
-        const int NX = p->N * p->model->dims.nx, NY = p->N * p->model->dims.ny;
-        const int *midx = p->has_midx ? p->d_model_idx : nullptr;
-        hipLaunchKernelGGL(k_qinst, dim3(batch), dim3(256), 0, sq, p->n, p->nx, p->nW, p->d_q0, p->d_Qx, p->d_Qw, p->d_cs, midx, p->d_x0, p->d_omega, p->d_qs_inst);
-        HIP_TRY(hipMemsetAsync(p->d_rconst, 0, sizeof(double) * batch, sq));
-        if (p->d_Wx && NX) hipLaunchKernelGGL(k_quad_const, dim3(batch), dim3(256), sizeof(double) * NX, sq, NX, p->nx, p->nW, t->d_out[O_PhiX], t->lay.out_size[O_PhiX],
-                                              t->d_out[O_GamW], t->lay.out_size[O_GamW], t->d_out[O_Gam5], t->lay.out_size[O_Gam5], p->d_Wx, midx, p->d_x0, p->d_omega, p->d_rconst);
-        if (p->d_Wy && NY) hipLaunchKernelGGL(k_quad_const, dim3(batch), dim3(256), sizeof(double) * NY, sq, NY, p->nx, p->nW, t->d_out[O_LX], t->lay.out_size[O_LX],
-                                              t->d_out[O_LW], t->lay.out_size[O_LW], t->d_out[O_L5], t->lay.out_size[O_L5], p->d_Wy, midx, p->d_x0, p->d_omega, p->d_rconst);
+        if (lp_path) HIP_TRY(hipMemsetAsync(p->d_counter, 0, sizeof(int), sq));
+        if ((rc = launch_rhs_cost(p))) return rc;
+        if (!lp_path) HIP_TRY(hipEventRecord(p->ev[1], sq));
+        p->S.qp = p->has_quad ? 1 : 0;
+        const bool ho = p->ho_enable && p->bat.ho.tail && !lp_path && p->nb > 0;      /* (a quadratic cost included: items index qs_inst / rconst by their source instance, < batch) */
+        const ProblemDev P = problem_dev(p);
+        BatchDev B = batch_dev(p, ho);
+        if (ho && (rc = handoff_reset(p))) return rc;
+        if (lp_path) {      /* only the overflow instances of the LP path */
+            HIP_TRY(hipMemcpy(p->bat.order, redo.data(), sizeof(int) * redo.size(), hipMemcpyHostToDevice));
+            p->order_batch = 0;
+            B.order = p->bat.order; B.batch = (int)redo.size();
+        }
+        const int grid = ho ? p->n_slots : std::min(B.batch, p->n_slots);      /* (hand-off: the workgroups without an instance wait for items) */
+        if (p->lds_bytes > 48 * 1024)   /* per-function limit: set for THIS problem (several problems of different size may be alive) */
+            HIP_TRY(hipFuncSetAttribute((const void *)k_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_bytes));
+        hipLaunchKernelGGL(k_solve, dim3(grid), dim3(SOL_NT), p->lds_bytes, sq, p->S, P, B, p->d_ws.get());
+        if (ho && (rc = handoff_merge(p))) return rc;
+        p->ho_ran = ho;
+        HIP_TRY(hipEventRecord(p->ev[2], sq));
     }
-    if (!lp_path) HIP_TRY(hipEventRecord(e1, sq));
-    ProblemDev P;
-    P.Gp = p->d_Gp; P.Gs = p->d_Gs; P.rs = p->d_rs; P.cs = p->d_cs; P.qs = p->d_qs; P.lb = p->d_lb; P.ub = p->d_ub; P.is_int = p->d_is_int;
-    P.bins = p->d_bins; P.colperm = p->d_colperm; P.Hx = t->d_out[O_HX]; P.Hw = t->d_out[O_HW]; P.H5 = t->d_out[O_H5];
-    P.cx = p->nx ? p->d_cx : nullptr; P.cw = p->nW ? p->d_cw : nullptr; P.c0 = p->d_c0;
-    P.Ps = p->has_quad ? p->d_Ps : nullptr;
-    P.act_max = p->d_actmax;
-    P.csr_ptr = p->d_csr_ptr; P.csr_col = p->d_csr_col; P.csr_val = p->d_csr_val; P.csc_ptr = p->d_csc_ptr; P.csc_row = p->d_csc_row; P.csc_val = p->d_csc_val; P.nnz_cap = p->nnz_cap;
-    p->S.qp = p->has_quad ? 1 : 0;
-    BatchDev B;
-    B.batch = batch; B.model_idx = p->has_midx ? p->d_model_idx : nullptr; B.x0 = p->d_x0; B.omega = p->d_omega;
-    B.fixed = p->has_fixed ? p->d_fixed : nullptr; B.hs = p->d_hs;
-    B.warm = p->has_warm ? p->d_warm : nullptr;
-    B.cutoff = p->has_cutoff ? p->d_cutoff : nullptr;
-    B.open_depth = p->want_open ? p->d_open_depth : nullptr; B.open_var = p->d_open_var; B.open_val = p->d_open_val; B.open_flag = p->d_open_flag;
-    B.qs_inst = p->has_quad ? p->d_qs_inst : nullptr; B.rconst = p->has_quad ? p->d_rconst : nullptr; B.v_out = p->d_v; B.obj_out = p->d_obj; B.lb_out = p->d_lbnd;
-    B.status_out = p->d_status; B.nodes_out = p->d_nodes; B.pivots_out = p->d_pivots; B.cuts_out = p->d_cuts; B.refac_out = p->d_refac;
-    B.ticks_out = p->d_ticks; B.rows_out = p->d_rows; B.prof_out = p->d_prof; B.trace = p->d_trace;
-    B.counter = p->d_counter;
-    B.order = (p->order_batch == batch && !(p->opts.reserved & 8)) ? p->d_order : nullptr;
-    P.binpos = p->d_binpos;
-    const bool ho = p->ho_enable && p->d_tail && !lp_path && p->nb > 0;      /* (a quadratic cost included: items index d_qs_inst / d_rconst by their source instance, < batch) */
-    B.ho = 0; B.cap = p->batch_cap; B.tail = p->d_tail; B.finished = p->d_finished;
-    B.ho_sub_nodes = p->ho_sub_nodes > 0 ? p->ho_sub_nodes : p->opts.max_nodes; B.ho_max_gen = p->ho_max_gen; B.ho_max_children = p->ho_max_children;
-    B.item_src = p->d_item_src; B.item_root = p->d_item_root; B.item_gen = p->d_item_gen; B.item_label = p->d_item_label; B.item_ready = p->d_item_ready;
-    B.item_children = p->d_item_children;
-    B.tree_count = p->d_tree_count; B.tree_dead = p->d_tree_dead; B.ho_max_tree = p->ho_max_tree; B.ho_donate = p->ho_donate; B.ho_rounds = p->ho_rounds;
-    if (ho) {
-        HIP_TRY(hipMemsetAsync(p->d_tree_count, 0, sizeof(int) * (size_t)batch * 9, sq));
-        HIP_TRY(hipMemsetAsync(p->d_tree_dead, 0, sizeof(int) * (size_t)batch, sq));
-        B.ho = 1 | (p->has_fixed ? 0 : 2);
-        B.fixed = p->d_fixed; B.cutoff = p->d_cutoff;
-        hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, sq, p->d_tail, batch);
-        HIP_TRY(hipMemsetAsync(p->d_finished, 0, sizeof(int), sq));
-        HIP_TRY(hipMemsetAsync(p->d_item_ready, 0, sizeof(int) * (size_t)p->batch_cap, sq));
-        HIP_TRY(hipMemsetAsync(p->d_item_children, 0, sizeof(int) * (size_t)p->batch_cap, sq));
-        if (!p->has_cutoff) hipLaunchKernelGGL(k_fill_f64, dim3((batch + 255) / 256), dim3(256), 0, sq, (size_t)batch, (double)INFINITY, p->d_cutoff);
-    }
-    if (lp_path) {      /* only the overflow instances of the LP path */
-        HIP_TRY(hipMemcpy(p->d_order, p->lp_redo.data(), sizeof(int) * p->lp_redo.size(), hipMemcpyHostToDevice));
-        p->order_batch = 0;
-        B.order = p->d_order; B.batch = (int)p->lp_redo.size();
-    }
-    const int grid = ho ? p->n_slots : std::min(B.batch, p->n_slots);      /* (hand-off: the workgroups without an instance wait for items) */
-    if (p->lds_bytes > 48 * 1024)   /* per-function limit: set for THIS problem (several problems of different size may be alive) */
-        HIP_TRY(hipFuncSetAttribute((const void *)k_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_bytes));
-    hipLaunchKernelGGL(k_solve, dim3(grid), dim3(SOL_NT), p->lds_bytes, sq, p->S, P, B, p->d_ws);
-    if (ho) {      /* merge the items into their roots (deterministic: best objective, smallest tree label on ties) */
-        const int items = p->batch_cap - batch;
-        const dim3 gi((items + 255) / 256), gb((batch + 255) / 256), blk(256);
-        HIP_TRY(hipMemsetAsync(p->d_skipped, 0, sizeof(int), sq));
-        hipLaunchKernelGGL(k_merge_init, gb, blk, 0, sq, batch, p->d_obj, p->d_mg_best, p->d_mg_lbopen, p->d_mg_label, p->d_mg_open);
-        hipLaunchKernelGGL(k_merge_a, gi, blk, 0, sq, batch, p->d_tail, p->d_item_root, p->d_obj, p->d_lbnd, p->d_status, p->d_nodes, p->d_pivots, p->d_cuts, p->d_refac, p->d_rows,
-                           p->d_mg_best, p->d_mg_lbopen, p->d_mg_open, p->d_tree_dead);
-        hipLaunchKernelGGL(k_merge_b, gi, blk, 0, sq, batch, p->d_tail, p->d_item_root, p->d_obj, p->d_item_label, p->d_mg_best, p->d_mg_label, p->d_tree_dead);
-        hipLaunchKernelGGL(k_merge_c, dim3(items), blk, 0, sq, batch, p->d_tail, p->n, p->d_item_root, p->d_obj, p->d_item_label, p->d_mg_best, p->d_mg_label, p->d_v, p->d_tree_dead);
-        hipLaunchKernelGGL(k_merge_d, gb, blk, 0, sq, batch, p->opts.gap_abs, p->opts.gap_rel, p->d_obj, p->d_lbnd, p->d_status, p->d_mg_best, p->d_mg_lbopen, p->d_mg_open, p->d_skipped, p->d_tree_dead, p->d_finished);      /* (d_finished: the queue is drained, the counter is free) */
-    }
-    p->ho_ran = ho;
-    HIP_TRY(hipEventRecord(e2, sq));
-    }
-    p->flight_lp = lp_path; p->in_flight = true;
-    if (mode == 1 && !lp_path) return MLD_OK;       /* queued; mld_solve_finish waits for it */
-    }
-    {   /* (a failed wait must not leave the handle locked: every entry point refuses a problem that is in flight) */
-        const hipError_t ew = hipEventSynchronize(e2);
-        p->in_flight = false;
-        if (ew != hipSuccess) { p->lds_done = false; mld_set_error("mld_solve: %s", hipGetErrorString(ew)); return MLD_ERR_HIP; }
-    }
-    HIP_TRY(hipGetLastError());
-    p->solved = true; p->advanced = false;
-    if (p->ho_ran && !lp_path) {      /* queue statistics of the launch that just ended */
+    if (!lp_path) { p->flight = Flight::queued; return MLD_OK; }
+    if ((rc = wait_solve(p))) return rc;
+    p->flight = Flight::lds_done;      /* (mld_solve_finish only reports -- the handle stays in flight until then, like a queued dense solve) */
+    return MLD_OK;
+}
+
+/* wait for the launched solve and report: queue statistics, mld_stats, and the longest-first order for the next solve of this batch size */
+static int finish(mld_problem *p, mld_stats *st)
+{
+    if (!p || p->batch < 1) { mld_set_error("mld_solve_resident: nothing uploaded"); return MLD_ERR_INVALID; }
+    if (p->flight == Flight::idle) { mld_set_error("mld_solve_finish: no launched solve"); return MLD_ERR_INVALID; }
+    const hipStream_t sq = p->stream;
+    const int batch = p->batch;
+    const bool dense = p->flight == Flight::queued;
+    int rc;
+    if ((rc = wait_solve(p))) return rc;
+    if (dense && p->ho_ran) {      /* queue statistics of the launch that just ended */
         int tl = 0, unf = 0, fin = 0;
-        HIP_TRY(hipMemcpyAsync(&tl, p->d_tail, sizeof(int), hipMemcpyDeviceToHost, sq));
-        HIP_TRY(hipMemcpyAsync(&unf, p->d_skipped, sizeof(int), hipMemcpyDeviceToHost, sq));
-        HIP_TRY(hipMemcpyAsync(&fin, p->d_finished, sizeof(int), hipMemcpyDeviceToHost, sq));
+        HIP_TRY(hipMemcpyAsync(&tl, p->bat.ho.tail, sizeof(int), hipMemcpyDeviceToHost, sq));
+        HIP_TRY(hipMemcpyAsync(&unf, p->bat.skipped, sizeof(int), hipMemcpyDeviceToHost, sq));
+        HIP_TRY(hipMemcpyAsync(&fin, p->bat.ho.finished, sizeof(int), hipMemcpyDeviceToHost, sq));
         HIP_TRY(hipStreamSynchronize(sq));
-        /* d_finished ended at tail and then took: + 1 per tree given up for its size, + 65536 per tree given up because the queue was full */
+        /* finished ended at tail and then took: + 1 per tree given up for its size, + 65536 per tree given up because the queue was full */
         const int extra = fin - tl;
         p->ho_stats[0] = tl - batch; p->ho_stats[1] = extra % 65536; p->ho_stats[2] = unf; p->ho_stats[3] = extra / 65536;
     }
-    if (mode == 1) { p->lds_done = true; p->in_flight = true; return MLD_OK; }      /* (LDS paths: complete already; mld_solve_finish only reports -- the handle stays in flight until then, like a queued dense solve) */
     if (st) {
         memset(st, 0, sizeof(*st));
         float a = 0, b = 0;
-        HIP_TRY(hipEventElapsedTime(&a, e0, e1)); HIP_TRY(hipEventElapsedTime(&b, e1, e2));
+        HIP_TRY(hipEventElapsedTime(&a, p->ev[0], p->ev[1])); HIP_TRY(hipEventElapsedTime(&b, p->ev[1], p->ev[2]));
         st->rhs_ms = a; st->solve_ms = b;
         long long h[8];
-        hipLaunchKernelGGL(k_batch_stats, dim3(1), dim3(256), 0, sq, batch, p->d_status, p->d_nodes, p->d_pivots, p->d_cuts, p->d_refac, p->d_statbuf);
+        hipLaunchKernelGGL(k_batch_stats, dim3(1), dim3(256), 0, sq, batch, p->bat.status, p->bat.nodes, p->bat.pivots, p->bat.cuts, p->bat.refac, p->d_statbuf);
         HIP_TRY(hipMemcpyAsync(h, p->d_statbuf, sizeof(h), hipMemcpyDeviceToHost, sq));
         HIP_TRY(hipStreamSynchronize(sq));
         st->nodes = h[0]; st->pivots = h[1]; st->cuts = h[2]; st->refactors = h[3];
         st->n_optimal = (int)h[4]; st->n_infeasible = (int)h[5]; st->n_node_limit = (int)h[6]; st->n_numerical = (int)h[7];
     }
-    if (!lp_path && batch > p->n_slots && !(p->opts.reserved & 8)) {
+    if (dense && batch > p->n_slots && !(p->opts.reserved & 8)) {
         /* Work-queue order for the next solve of this batch size: longest first (LPT).  Consecutive MPC steps solve
          * nearly the same instances, so the previous in-kernel time predicts the next one; starting the long
          * branch-and-bound runs first removes the partially idle tail of the persistent grid.  Results do not depend
          * on the order (every instance is solved by one workgroup, bit-reproducibly). */
         std::vector<long long> ticks(batch);
-        HIP_TRY(hipMemcpy(ticks.data(), p->d_ticks, sizeof(long long) * batch, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ticks.data(), p->bat.ticks, sizeof(long long) * batch, hipMemcpyDeviceToHost));
         std::vector<int> ord(batch);
         for (int i = 0; i < batch; ++i) ord[i] = i;
         std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return ticks[a] > ticks[b]; });
-        HIP_TRY(hipMemcpy(p->d_order, ord.data(), sizeof(int) * batch, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(p->bat.order, ord.data(), sizeof(int) * batch, hipMemcpyHostToDevice));
         p->order_batch = batch;
     }
     return MLD_OK;
 }
 
-int mld_solve_resident(mld_problem_t *p, mld_stats *st) { return solve_impl(p, st, 0); }
+int mld_solve_resident(mld_problem_t *p, mld_stats *st)
+{
+    const int rc = launch(p);
+    return rc ? rc : finish(p, st);
+}
 
 /* The same solve in two halves, for callers that keep several problems busy: with mld_problem_use_stream every problem owns a HIP stream, a
  * launched solve of one problem runs while another is being prepared or finished, and the workgroups of the next launch move onto the
  * CUs as the stragglers of the previous one retire (bench.py: consecutive, independent scenario sets on two problems). */
-int mld_solve_launch(mld_problem_t *p) { return solve_impl(p, nullptr, 1); }
-int mld_solve_finish(mld_problem_t *p, mld_stats *st)
-{
-    if (p && p->lds_done) {      /* an LDS-path launch ran to completion: statistics only */
-        p->lds_done = false; p->in_flight = true; p->flight_lp = true;
-    }
-    return solve_impl(p, st, 2);
-}
+int mld_solve_launch(mld_problem_t *p) { return launch(p); }
+int mld_solve_finish(mld_problem_t *p, mld_stats *st) { return finish(p, st); }
 int mld_problem_use_stream(mld_problem_t *p)
 {
     if (!p) { mld_set_error("mld_problem_use_stream: bad handle"); return MLD_ERR_INVALID; }
-    if (p->in_flight) { mld_set_error("mld_problem_use_stream: a solve is in flight"); return MLD_ERR_INVALID; }
+    if (p->flight != Flight::idle) { mld_set_error("mld_problem_use_stream: a solve is in flight"); return MLD_ERR_INVALID; }
     if (!p->own_stream) { HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking)); p->own_stream = true; }
     return MLD_OK;
 }
@@ -1385,12 +1364,12 @@ int mld_download_results(mld_problem_t *p, double *v_out, double *obj_out, int32
     MLD_NOT_IN_FLIGHT(p, "mld_download_results");
     if (!p || p->batch < 1) { mld_set_error("mld_download_results: nothing solved"); return MLD_ERR_INVALID; }
     const size_t b = p->batch;
-    if (v_out && p->n) HIP_TRY(hipMemcpy(v_out, p->d_v, sizeof(double) * b * p->n, hipMemcpyDeviceToHost));
-    if (obj_out) HIP_TRY(hipMemcpy(obj_out, p->d_obj, sizeof(double) * b, hipMemcpyDeviceToHost));
-    if (status_out) HIP_TRY(hipMemcpy(status_out, p->d_status, sizeof(int) * b, hipMemcpyDeviceToHost));
-    if (lower_bound_out) HIP_TRY(hipMemcpy(lower_bound_out, p->d_lbnd, sizeof(double) * b, hipMemcpyDeviceToHost));
-    if (nodes_out) HIP_TRY(hipMemcpy(nodes_out, p->d_nodes, sizeof(int) * b, hipMemcpyDeviceToHost));
-    if (pivots_out) HIP_TRY(hipMemcpy(pivots_out, p->d_pivots, sizeof(int) * b, hipMemcpyDeviceToHost));
+    if (v_out && p->n) HIP_TRY(hipMemcpy(v_out, p->bat.v, sizeof(double) * b * p->n, hipMemcpyDeviceToHost));
+    if (obj_out) HIP_TRY(hipMemcpy(obj_out, p->bat.obj, sizeof(double) * b, hipMemcpyDeviceToHost));
+    if (status_out) HIP_TRY(hipMemcpy(status_out, p->bat.status, sizeof(int) * b, hipMemcpyDeviceToHost));
+    if (lower_bound_out) HIP_TRY(hipMemcpy(lower_bound_out, p->bat.lbnd, sizeof(double) * b, hipMemcpyDeviceToHost));
+    if (nodes_out) HIP_TRY(hipMemcpy(nodes_out, p->bat.nodes, sizeof(int) * b, hipMemcpyDeviceToHost));
+    if (pivots_out) HIP_TRY(hipMemcpy(pivots_out, p->bat.pivots, sizeof(int) * b, hipMemcpyDeviceToHost));
     return MLD_OK;
 }
 
@@ -1401,13 +1380,13 @@ int mld_download_telemetry(mld_problem_t *p, int64_t *latency_ns, int64_t *rows_
     const size_t b = p->batch;
     if (latency_ns) {
         std::vector<long long> t(b);
-        HIP_TRY(hipMemcpy(t.data(), p->d_ticks, sizeof(long long) * b, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(t.data(), p->bat.ticks, sizeof(long long) * b, hipMemcpyDeviceToHost));
         int dev = 0, khz = 100000;
         (void)hipGetDevice(&dev);
         if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0) khz = 100000;
         for (size_t i = 0; i < b; ++i) latency_ns[i] = (int64_t)((double)t[i] * 1.0e6 / (double)khz);
     }
-    if (rows_updated) HIP_TRY(hipMemcpy(rows_updated, p->d_rows, sizeof(long long) * b, hipMemcpyDeviceToHost));
+    if (rows_updated) HIP_TRY(hipMemcpy(rows_updated, p->bat.rows, sizeof(long long) * b, hipMemcpyDeviceToHost));
     if (row_bytes) *row_bytes = 8 * SOL_SEC;   /* rows_updated counts update sectors (SOL_SEC doubles) */
     return MLD_OK;
 }
@@ -1441,7 +1420,7 @@ int mld_debug_profile(mld_problem_t *p, int64_t out[8])
 {
     if (!p || p->batch < 1) return MLD_ERR_INVALID;
     std::vector<long long> t((size_t)p->batch * 8);
-    HIP_TRY(hipMemcpy(t.data(), p->d_prof, sizeof(long long) * t.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(t.data(), p->bat.prof, sizeof(long long) * t.size(), hipMemcpyDeviceToHost));
     for (int k = 0; k < 8; ++k) out[k] = 0;
     for (size_t i = 0; i < (size_t)p->batch; ++i) for (int k = 0; k < 8; ++k) out[k] += t[i * 8 + k];
     return MLD_OK;
@@ -1464,16 +1443,16 @@ int mld_advance_batch2(mld_problem_t *p, int32_t *n_skipped_out)
     for (int k = 0; k < 7; ++k) oBv += m->mat_size[skip[k]];
     const size_t bx = ((size_t)p->batch * std::max(1, p->nx) + 255) / 256, bw = ((size_t)p->batch * std::max(1, p->nW) + 255) / 256;
     const int grid = (int)std::max<size_t>(bx, std::min<size_t>(bw, (size_t)1 << 20));   /* the state part is one thread per element, the shift strides */
-    HIP_TRY(hipMemsetAsync(p->d_skipped, 0, sizeof(int), p->stream));
+    HIP_TRY(hipMemsetAsync(p->bat.skipped, 0, sizeof(int), p->stream));
     hipLaunchKernelGGL(k_advance, dim3(grid), dim3(256), 0, p->stream, p->batch, p->nx, p->nv, d.nomega, p->N,
                        m->d_pack, m->pack_len, 1, oA, oB4, ob5, oBv,
-                       p->has_midx ? p->d_model_idx : nullptr, p->d_x0, p->d_omega, p->d_v, (size_t)p->n, p->d_x0b, p->d_omegab,
-                       p->d_status, p->d_obj, p->d_skipped);
+                       p->has_midx ? p->bat.model_idx : nullptr, p->bat.x0, p->bat.omega, p->bat.v, (size_t)p->n, p->bat.x0b, p->bat.omegab,
+                       p->bat.status, p->bat.obj, p->bat.skipped);
     HIP_TRY(hipGetLastError());
     int skipped = 0;
-    HIP_TRY(hipMemcpyAsync(&skipped, p->d_skipped, sizeof(int), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipMemcpyAsync(&skipped, p->bat.skipped, sizeof(int), hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
-    std::swap(p->d_x0, p->d_x0b); std::swap(p->d_omega, p->d_omegab);
+    std::swap(p->bat.x0, p->bat.x0b); std::swap(p->bat.omega, p->bat.omegab);
     p->n_xcols = 0;      /* extra constraint blocks belonged to the previous step's data */
     p->has_warm = false; /* a start belongs to one set of inputs (mld_warm_start_from_previous builds the next one from the plan) */
     p->has_cutoff = false;
@@ -1491,7 +1470,7 @@ int mld_set_warm_start(mld_problem_t *p, const uint8_t *bin_start)
     if (!bin_start || p->nb == 0) { p->has_warm = false; return MLD_OK; }
     const size_t tot = (size_t)p->batch * p->nb;
     for (size_t k = 0; k < tot; ++k) if (bin_start[k] > 1 && bin_start[k] != 255) { mld_set_error("mld_set_warm_start: entry %zu is %d (0, 1, or 255 = no start)", k, (int)bin_start[k]); return MLD_ERR_INVALID; }
-    HIP_TRY(hipMemcpy(p->d_warm, bin_start, tot, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(p->bat.warm, bin_start, tot, hipMemcpyHostToDevice));
     p->has_warm = true;
     return MLD_OK;
 }
@@ -1504,7 +1483,7 @@ int mld_warm_start_from_previous(mld_problem_t *p, int shift)
     if (p->nb == 0) { p->has_warm = false; return MLD_OK; }
     const size_t tot = (size_t)p->batch * p->nb;
     hipLaunchKernelGGL(k_warm_from_plan, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, p->stream, p->batch, p->nb, p->nv, p->N, shift, p->d_bins,
-                       p->d_v, (size_t)p->n, p->d_status, p->d_obj, p->d_warm);
+                       p->bat.v, (size_t)p->n, p->bat.status, p->bat.obj, p->bat.warm);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(p->stream));
     p->has_warm = true;
@@ -1516,7 +1495,7 @@ int mld_set_cutoffs(mld_problem_t *p, const double *cutoff)
     MLD_NOT_IN_FLIGHT(p, "mld_set_cutoffs");
     if (!p || p->batch < 1) { mld_set_error("mld_set_cutoffs: upload a batch first"); return MLD_ERR_INVALID; }
     if (!cutoff) { p->has_cutoff = false; return MLD_OK; }
-    HIP_TRY(hipMemcpy(p->d_cutoff, cutoff, sizeof(double) * (size_t)p->batch, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(p->bat.cutoff, cutoff, sizeof(double) * (size_t)p->batch, hipMemcpyHostToDevice));
     p->has_cutoff = true;
     return MLD_OK;
 }
@@ -1564,15 +1543,15 @@ int mld_set_handoff(mld_problem_t *p, int enable, int sub_nodes, int max_gen, in
 /* diagnostics (internal, not in the public header): per queue entry of the last hand-off solve -- in-kernel ticks, generation, status, root; returns the number of entries */
 int mld_debug_entries(mld_problem_t *p, int cap, int64_t *ticks, int32_t *gen, int32_t *status, int32_t *root)
 {
-    if (!p || !p->ho_ran || !p->d_tail) return -1;
+    if (!p || !p->ho_ran || !p->bat.ho.tail) return -1;
     int tl = 0;
-    if (hipMemcpy(&tl, p->d_tail, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (hipMemcpy(&tl, p->bat.ho.tail, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     const int k = std::min(tl, cap);
-    (void)hipMemcpy(ticks, p->d_ticks, sizeof(long long) * k, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(status, p->d_status, sizeof(int) * k, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(ticks, p->bat.ticks, sizeof(long long) * k, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(status, p->bat.status, sizeof(int) * k, hipMemcpyDeviceToHost);
     if (k > p->batch) {
-        (void)hipMemcpy(gen + p->batch, p->d_item_gen + p->batch, sizeof(int) * (k - p->batch), hipMemcpyDeviceToHost);
-        (void)hipMemcpy(root + p->batch, p->d_item_root + p->batch, sizeof(int) * (k - p->batch), hipMemcpyDeviceToHost);
+        (void)hipMemcpy(gen + p->batch, p->bat.ho.item_gen + p->batch, sizeof(int) * (k - p->batch), hipMemcpyDeviceToHost);
+        (void)hipMemcpy(root + p->batch, p->bat.ho.item_root + p->batch, sizeof(int) * (k - p->batch), hipMemcpyDeviceToHost);
     }
     for (int i = 0; i < std::min(k, p->batch); ++i) { gen[i] = 0; root[i] = i; }
     return k;
@@ -1600,10 +1579,10 @@ int mld_download_open_nodes(mld_problem_t *p, int32_t *depth_out, int16_t *var_o
     MLD_NOT_IN_FLIGHT(p, "mld_download_open_nodes");
     if (!p || p->batch < 1 || !p->solved || !p->want_open) { mld_set_error("mld_download_open_nodes: no finished solve with mld_record_open_nodes enabled"); return MLD_ERR_INVALID; }
     const size_t b = p->batch, nb = std::max(1, p->nb);
-    if (depth_out) HIP_TRY(hipMemcpy(depth_out, p->d_open_depth, sizeof(int) * b, hipMemcpyDeviceToHost));
-    if (var_out) HIP_TRY(hipMemcpy(var_out, p->d_open_var, sizeof(short) * b * nb, hipMemcpyDeviceToHost));
-    if (val_out) HIP_TRY(hipMemcpy(val_out, p->d_open_val, b * nb, hipMemcpyDeviceToHost));
-    if (flag_out) HIP_TRY(hipMemcpy(flag_out, p->d_open_flag, b * nb, hipMemcpyDeviceToHost));
+    if (depth_out) HIP_TRY(hipMemcpy(depth_out, p->bat.open_depth, sizeof(int) * b, hipMemcpyDeviceToHost));
+    if (var_out) HIP_TRY(hipMemcpy(var_out, p->bat.open_var, sizeof(short) * b * nb, hipMemcpyDeviceToHost));
+    if (val_out) HIP_TRY(hipMemcpy(val_out, p->bat.open_val, b * nb, hipMemcpyDeviceToHost));
+    if (flag_out) HIP_TRY(hipMemcpy(flag_out, p->bat.open_flag, b * nb, hipMemcpyDeviceToHost));
     return MLD_OK;
 }
 
@@ -1612,15 +1591,14 @@ int mld_stage_inputs(mld_problem_t *p, int n_sets, const double *x0_sets, const 
     MLD_NOT_IN_FLIGHT(p, "mld_stage_inputs");
     if (!p || p->batch < 1) { mld_set_error("mld_stage_inputs: upload a batch first (it fixes the batch size and model_idx)"); return MLD_ERR_INVALID; }
     if (n_sets < 0 || (n_sets > 0 && ((p->nx && !x0_sets) || (p->nW && !omega_sets)))) { mld_set_error("mld_stage_inputs: bad arguments"); return MLD_ERR_INVALID; }
-    if (p->d_stage_x0) { (void)hipFree(p->d_stage_x0); p->d_stage_x0 = nullptr; }
-    if (p->d_stage_om) { (void)hipFree(p->d_stage_om); p->d_stage_om = nullptr; }
+    p->bat.stage_x0.reset(); p->bat.stage_om.reset();
     p->n_staged = 0; p->staged_batch = 0;
     if (n_sets == 0) return MLD_OK;
     const size_t bx = (size_t)n_sets * p->batch * std::max(1, p->nx), bw = (size_t)n_sets * p->batch * std::max(1, p->nW);
-    HIP_TRY(hipMalloc(&p->d_stage_x0, sizeof(double) * bx));
-    HIP_TRY(hipMalloc(&p->d_stage_om, sizeof(double) * bw));
-    if (p->nx) HIP_TRY(hipMemcpy(p->d_stage_x0, x0_sets, sizeof(double) * (size_t)n_sets * p->batch * p->nx, hipMemcpyHostToDevice));
-    if (p->nW) HIP_TRY(hipMemcpy(p->d_stage_om, omega_sets, sizeof(double) * (size_t)n_sets * p->batch * p->nW, hipMemcpyHostToDevice));
+    HIP_TRY(p->bat.stage_x0.alloc(bx));
+    HIP_TRY(p->bat.stage_om.alloc(bw));
+    if (p->nx) HIP_TRY(hipMemcpy(p->bat.stage_x0, x0_sets, sizeof(double) * (size_t)n_sets * p->batch * p->nx, hipMemcpyHostToDevice));
+    if (p->nW) HIP_TRY(hipMemcpy(p->bat.stage_om, omega_sets, sizeof(double) * (size_t)n_sets * p->batch * p->nW, hipMemcpyHostToDevice));
     p->n_staged = n_sets; p->staged_batch = p->batch;
     return MLD_OK;
 }
@@ -1629,8 +1607,8 @@ int mld_select_inputs(mld_problem_t *p, int set)
 {
     MLD_NOT_IN_FLIGHT(p, "mld_select_inputs");
     if (!p || p->batch < 1 || p->staged_batch != p->batch || set < 0 || set >= p->n_staged) { mld_set_error("mld_select_inputs: set %d not staged for this batch", set); return MLD_ERR_INVALID; }
-    if (p->nx) HIP_TRY(hipMemcpyAsync(p->d_x0, p->d_stage_x0 + (size_t)set * p->batch * p->nx, sizeof(double) * (size_t)p->batch * p->nx, hipMemcpyDeviceToDevice, p->stream));
-    if (p->nW) HIP_TRY(hipMemcpyAsync(p->d_omega, p->d_stage_om + (size_t)set * p->batch * p->nW, sizeof(double) * (size_t)p->batch * p->nW, hipMemcpyDeviceToDevice, p->stream));
+    if (p->nx) HIP_TRY(hipMemcpyAsync(p->bat.x0, p->bat.stage_x0 + (size_t)set * p->batch * p->nx, sizeof(double) * (size_t)p->batch * p->nx, hipMemcpyDeviceToDevice, p->stream));
+    if (p->nW) HIP_TRY(hipMemcpyAsync(p->bat.omega, p->bat.stage_om + (size_t)set * p->batch * p->nW, sizeof(double) * (size_t)p->batch * p->nW, hipMemcpyDeviceToDevice, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));   /* the other entry points copy on the legacy stream, which does not order against a non-blocking one */
     p->n_xcols = 0;      /* extra constraint blocks belonged to the previous inputs */
     p->has_warm = false; p->solved = false; p->advanced = false; p->has_cutoff = false;
@@ -1641,8 +1619,8 @@ int mld_download_inputs(mld_problem_t *p, double *x0, double *omega)
 {
     MLD_NOT_IN_FLIGHT(p, "mld_download_inputs");
     if (!p || p->batch < 1) { mld_set_error("mld_download_inputs: nothing uploaded"); return MLD_ERR_INVALID; }
-    if (x0 && p->nx) HIP_TRY(hipMemcpy(x0, p->d_x0, sizeof(double) * (size_t)p->batch * p->nx, hipMemcpyDeviceToHost));
-    if (omega && p->nW) HIP_TRY(hipMemcpy(omega, p->d_omega, sizeof(double) * (size_t)p->batch * p->nW, hipMemcpyDeviceToHost));
+    if (x0 && p->nx) HIP_TRY(hipMemcpy(x0, p->bat.x0, sizeof(double) * (size_t)p->batch * p->nx, hipMemcpyDeviceToHost));
+    if (omega && p->nW) HIP_TRY(hipMemcpy(omega, p->bat.omega, sizeof(double) * (size_t)p->batch * p->nW, hipMemcpyDeviceToHost));
     return MLD_OK;
 }
 
@@ -1697,29 +1675,29 @@ int mld_rhs_batch(mld_problem_t *p, int batch, int scenarios, const int32_t *mod
     /* temporaries of this call: released on every return path (HIP_TRY returns early) */
     DevBuf<int> d_idx, d_perm; DevBuf<double> d_x, d_w, d_h; DevBuf<RhsGroup> d_groups;
     const size_t b = batch;
-    if (model_idx) { HIP_TRY(d_idx.alloc(b)); HIP_TRY(hipMemcpy(d_idx.p, model_idx, sizeof(int) * b, hipMemcpyHostToDevice)); }
+    if (model_idx) { HIP_TRY(d_idx.alloc(b)); HIP_TRY(hipMemcpy(d_idx, model_idx, sizeof(int) * b, hipMemcpyHostToDevice)); }
     HIP_TRY(d_x.alloc(b * std::max(1, p->nx)));
     HIP_TRY(d_w.alloc(b * scenarios * std::max(1, p->nW)));
     HIP_TRY(d_h.alloc(b * std::max(1, p->m0)));
-    if (p->nx) HIP_TRY(hipMemcpy(d_x.p, x0, sizeof(double) * b * p->nx, hipMemcpyHostToDevice));
-    if (p->nW) HIP_TRY(hipMemcpy(d_w.p, omega, sizeof(double) * b * scenarios * p->nW, hipMemcpyHostToDevice));
+    if (p->nx) HIP_TRY(hipMemcpy(d_x, x0, sizeof(double) * b * p->nx, hipMemcpyHostToDevice));
+    if (p->nW) HIP_TRY(hipMemcpy(d_w, omega, sizeof(double) * b * scenarios * p->nW, hipMemcpyHostToDevice));
     if (p->m0 && scenarios == 1 && rhs_mfma_fits(p->nx, p->nW) && !(p->opts.reserved & 128)) {
         std::vector<int> perm; std::vector<RhsGroup> groups;
         build_rhs_groups(model_idx, batch, p->n_models, perm, groups);
-        if (!perm.empty()) { HIP_TRY(d_perm.alloc(perm.size())); HIP_TRY(hipMemcpy(d_perm.p, perm.data(), sizeof(int) * perm.size(), hipMemcpyHostToDevice)); }
+        if (!perm.empty()) { HIP_TRY(d_perm.alloc(perm.size())); HIP_TRY(hipMemcpy(d_perm, perm.data(), sizeof(int) * perm.size(), hipMemcpyHostToDevice)); }
         HIP_TRY(d_groups.alloc(groups.size()));
-        HIP_TRY(hipMemcpy(d_groups.p, groups.data(), sizeof(RhsGroup) * groups.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_groups, groups.data(), sizeof(RhsGroup) * groups.size(), hipMemcpyHostToDevice));
         launch_rhs_mfma((p->opts.flags & MLD_F32) != 0, (int)groups.size(), p->m0, p->nx, p->nW, m->d_out[O_HX], m->d_out[O_HW], m->d_out[O_H5],
-                        (const double *)nullptr, d_groups.p, d_perm.p, d_x.p, d_w.p, d_h.p);
+                        (const double *)nullptr, d_groups, d_perm, d_x, d_w, d_h);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(h_out, d_h.p, sizeof(double) * b * p->m0, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(h_out, d_h, sizeof(double) * b * p->m0, hipMemcpyDeviceToHost));
     } else if (p->m0) {
         hipLaunchKernelGGL(k_rhs, dim3(batch), dim3(256), 0, 0, p->m0, p->nx, p->nW, m->d_out[O_HX], m->d_out[O_HW], m->d_out[O_H5],
-                           (const double *)nullptr, d_idx.p, d_x.p, d_w.p, d_h.p, scenarios);
+                           (const double *)nullptr, d_idx, d_x, d_w, d_h, scenarios);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(h_out, d_h.p, sizeof(double) * b * p->m0, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(h_out, d_h, sizeof(double) * b * p->m0, hipMemcpyDeviceToHost));
     }
     return MLD_OK;
 }
@@ -1753,15 +1731,14 @@ int mld_comm_init(int n_ranks, int rank, const uint8_t id[MLD_COMM_ID_BYTES])
 int mld_gather(const double *send, int count, double *recv)
 {
     if (!g_comm) { mld_set_error("mld_gather: communicator not initialised"); return MLD_ERR_COMM; }
-    double *d_s = nullptr, *d_r = nullptr;
-    HIP_TRY(hipMalloc(&d_s, sizeof(double) * std::max(1, count)));
-    HIP_TRY(hipMalloc(&d_r, sizeof(double) * std::max(1, count) * g_nranks));
+    DevBuf<double> d_s, d_r;
+    HIP_TRY(d_s.alloc(std::max(1, count)));
+    HIP_TRY(d_r.alloc((size_t)std::max(1, count) * g_nranks));
     hipError_t e = hipMemcpy(d_s, send, sizeof(double) * count, hipMemcpyHostToDevice);
     ncclResult_t r = ncclSuccess;
     if (e == hipSuccess) r = ncclAllGather(d_s, d_r, count, ncclDouble, g_comm, 0);
     if (e == hipSuccess && r == ncclSuccess) e = hipStreamSynchronize(0);
     if (e == hipSuccess && r == ncclSuccess) e = hipMemcpy(recv, d_r, sizeof(double) * count * g_nranks, hipMemcpyDeviceToHost);
-    (void)hipFree(d_s); (void)hipFree(d_r);
     if (r != ncclSuccess) { mld_set_error("ncclAllGather: %s", ncclGetErrorString(r)); return MLD_ERR_COMM; }
     if (e != hipSuccess) { mld_set_error("mld_gather: %s", hipGetErrorString(e)); return MLD_ERR_HIP; }
     return MLD_OK;
@@ -1789,13 +1766,13 @@ extern "C" int mld_gather_results(mld_problem_t *p, double *recv, int *width_out
     /* send / receive buffers live with the problem (a hipFree per call synchronises the whole device: with two handles in flight the gather of
      * one would wait for the other's solve), and pack + all-gather run on the problem's own stream */
     if (p->gather_cap < count * (size_t)(1 + g_nranks)) {
-        if (p->d_gather) { (void)hipFree(p->d_gather); p->d_gather = nullptr; p->gather_cap = 0; }
-        HIP_TRY(hipMalloc(&p->d_gather, sizeof(double) * count * (size_t)(1 + g_nranks)));
+        p->gather_cap = 0;
+        HIP_TRY(p->d_gather.alloc(count * (size_t)(1 + g_nranks)));
         p->gather_cap = count * (size_t)(1 + g_nranks);
     }
     double *d_s = p->d_gather, *d_r = p->d_gather + count;
     const hipStream_t sq = p->stream;
-    hipLaunchKernelGGL(k_pack_results, dim3((unsigned)std::min<size_t>((count + 255) / 256, 65535)), dim3(256), 0, sq, p->batch, p->n, p->nv, p->d_obj, p->d_status, p->d_v, d_s);
+    hipLaunchKernelGGL(k_pack_results, dim3((unsigned)std::min<size_t>((count + 255) / 256, 65535)), dim3(256), 0, sq, p->batch, p->n, p->nv, p->bat.obj, p->bat.status, p->bat.v, d_s);
     hipError_t e = hipGetLastError();
     ncclResult_t r = e == hipSuccess ? ncclAllGather(d_s, d_r, count, ncclDouble, g_comm, sq) : ncclSuccess;
     if (r == ncclSuccess && e == hipSuccess) e = hipMemcpyAsync(recv, d_r, sizeof(double) * count * g_nranks, hipMemcpyDeviceToHost, sq);

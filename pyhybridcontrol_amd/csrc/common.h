@@ -21,6 +21,23 @@ void mld_set_error(const char *fmt, ...);
         }                                                                                      \
     } while (0)
 
+// ---- owning device buffer: every device allocation of a handle lives in one, so that no release list can miss or repeat it --------
+template <typename T> class DevBuf {
+    T *p_ = nullptr;
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; } return *this; }
+    ~DevBuf() { reset(); }
+    /* count elements (at least one); a buffer held before is released first.  hipFree synchronises the device: never on the solve path */
+    hipError_t alloc(size_t count) { reset(); return hipMalloc(&p_, sizeof(T) * (count ? count : 1)); }
+    void reset() { if (p_) (void)hipFree(p_); p_ = nullptr; }
+    T *get() const { return p_; }
+    operator T *() const { return p_; }      /* (kernel arguments, HIP copies and the argument structs take the raw pointer) */
+};
+
 // ---- per-model block store produced by k_condense_blocks ------------------------------------------
 // family f in {0: state (rows nx), 1: output (rows ny), 2: constraint (rows nc)}
 // blkV[f][k][r][c]  k = i-j (0 = diagonal block) ; blkW same with nw columns ; blkX[f][i][r][nx] ; blk5[f][i][r]
@@ -38,24 +55,24 @@ struct CondLayout {
 
 struct mld_model {
     mld_dims dims;
-    int n_models;         // horizons: with tv_N > 0 every horizon is tv_N consecutive step models in d_mats / h_mats / d_pack
-    int tv_N;             // 0 = time-invariant (one model per horizon)
-    int nv;
+    int n_models = 0;     // horizons: with tv_N > 0 every horizon is tv_N consecutive step models in d_mats / h_mats / d_pack
+    int tv_N = 0;         // 0 = time-invariant (one model per horizon)
+    int nv = 0;
     // device copies of the 20 system matrices, each n_models x rows x cols (NULL if zero-sized)
-    double *d_mats[20];
-    size_t mat_size[20];
-    int mat_rows[20], mat_cols[20];
+    DevBuf<double> d_mats[20];
+    size_t mat_size[20] = {};
+    int mat_rows[20] = {}, mat_cols[20] = {};
     std::vector<std::vector<double>> h_mats;   // host copies (needed by the big-M tightening)
-    double *d_pack;       // per model, packed once at creation in the LDS order of k_condense_blocks:
-                          // A, B4, b5, C, D4, d5, E, F4, f5, G, [B1 B2 B3 0], [D1 D2 D3 0], [F1 F2 F3 Psi]
-    size_t pack_len;
+    DevBuf<double> d_pack;  // per model, packed once at creation in the LDS order of k_condense_blocks:
+                            // A, B4, b5, C, D4, d5, E, F4, f5, G, [B1 B2 B3 0], [D1 D2 D3 0], [F1 F2 F3 Psi]
+    size_t pack_len = 0;
     // condensing results (device resident)
-    int cond_N;
+    int cond_N = -1;
     CondLayout lay;
-    double *d_blocks;     // n_models x blk_stride
-    double *d_out[12];    // materialised matrices, each n_models x out_size[k]
-    float *d_out32[12];   // the same in fp32 (mld_condense_f32), allocated on first use
-    double *d_tvQ, *d_tvS; // time-varying horizons: products Q(i,j) (triangular) and the affine chain, written by k_tv_chain
+    DevBuf<double> d_blocks;     // n_models x blk_stride
+    DevBuf<double> d_out[12];    // materialised matrices, each n_models x out_size[k]
+    DevBuf<float> d_out32[12];   // the same in fp32 (mld_condense_f32), allocated on first use
+    DevBuf<double> d_tvQ, d_tvS; // time-varying horizons: products Q(i,j) (triangular) and the affine chain, written by k_tv_chain
 };
 
 // matrix order in d_mats

@@ -908,18 +908,16 @@ int condense_model_device(mld_model *m, int N, double *kernel_ms, hipStream_t st
     if (N < 1) { mld_set_error("N_tilde must be >= 1"); return MLD_ERR_INVALID; }
     if (m->tv_N > 0 && N != m->tv_N) { mld_set_error("time-varying model holds %d step models per horizon, N_tilde = %d asked", m->tv_N, N); return MLD_ERR_INVALID; }
     if (m->cond_N != N) {
-        if (m->d_blocks) { (void)hipFree(m->d_blocks); m->d_blocks = nullptr; }
-        for (int k = 0; k < 12; ++k) if (m->d_out[k]) { (void)hipFree(m->d_out[k]); m->d_out[k] = nullptr; }
-        for (int k = 0; k < 12; ++k) if (m->d_out32[k]) { (void)hipFree(m->d_out32[k]); m->d_out32[k] = nullptr; }
-        if (m->d_tvQ) { (void)hipFree(m->d_tvQ); m->d_tvQ = nullptr; }
-        if (m->d_tvS) { (void)hipFree(m->d_tvS); m->d_tvS = nullptr; }
+        m->d_blocks.reset();
+        for (int k = 0; k < 12; ++k) { m->d_out[k].reset(); m->d_out32[k].reset(); }
+        m->d_tvQ.reset(); m->d_tvS.reset();
         compute_layout(m->dims, N, &m->lay);
-        HIP_TRY(hipMalloc(&m->d_blocks, sizeof(double) * m->lay.blk_stride * m->n_models));
+        HIP_TRY(m->d_blocks.alloc(m->lay.blk_stride * m->n_models));
         for (int k = 0; k < 12; ++k)
-            if (m->lay.out_size[k]) HIP_TRY(hipMalloc(&m->d_out[k], sizeof(double) * m->lay.out_size[k] * m->n_models));
+            if (m->lay.out_size[k]) HIP_TRY(m->d_out[k].alloc(m->lay.out_size[k] * m->n_models));
         m->cond_N = N;
     }
-    if (f32) for (int k = 0; k < 12; ++k) if (m->lay.out_size[k] && !m->d_out32[k]) HIP_TRY(hipMalloc(&m->d_out32[k], sizeof(float) * m->lay.out_size[k] * m->n_models));
+    if (f32) for (int k = 0; k < 12; ++k) if (m->lay.out_size[k] && !m->d_out32[k]) HIP_TRY(m->d_out32[k].alloc(m->lay.out_size[k] * m->n_models));
     CondPtrs P;
     for (int k = 0; k < 20; ++k) { P.mats[k] = m->d_mats[k]; P.mat_size[k] = m->mat_size[k]; }
     P.blocks = m->d_blocks;
@@ -935,7 +933,7 @@ int condense_model_device(mld_model *m, int N, double *kernel_ms, hipStream_t st
         if (wide) {
             const CondLayout &L = m->lay;
             const size_t nn = (size_t)L.nx * L.nx, qlen = (size_t)m->n_models * (N * (N + 1) / 2) * nn, slen = (size_t)m->n_models * N * L.nx;
-            if (!m->d_tvQ) { HIP_TRY(hipMalloc(&m->d_tvQ, sizeof(double) * (qlen ? qlen : 1))); HIP_TRY(hipMalloc(&m->d_tvS, sizeof(double) * (slen ? slen : 1))); }
+            if (!m->d_tvQ) { HIP_TRY(m->d_tvQ.alloc(qlen)); HIP_TRY(m->d_tvS.alloc(slen)); }
             const size_t lds_chain = sizeof(double) * ((size_t)N * nn + (size_t)N * L.nx + 16 * 2 * nn + 16);
             if (lds_chain > 48 * 1024) (void)hipFuncSetAttribute((const void *)k_tv_chain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_chain);
             void (*rows)(CondLayout, CondPtrs, const double *, const double *) = small ? k_tv_rows<8, 10, 4> : k_tv_rows<16, 16, 2>;

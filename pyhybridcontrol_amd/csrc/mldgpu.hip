@@ -92,12 +92,10 @@ static int model_create_impl(mld_model_t **out, const mld_dims *dims, int n_sets
     if (mld_device_count() <= 0) { mld_set_error("no HIP device (libmldgpu has no CPU fallback)"); return MLD_ERR_NO_DEVICE; }
     mld_model *m = new mld_model();
     m->dims = d; m->n_models = n_sets; m->tv_N = tv_N; m->nv = d.nu + d.ndelta + d.nz + d.nmu;
-    m->cond_N = -1; m->d_blocks = nullptr; m->d_pack = nullptr; m->pack_len = 0; m->d_tvQ = m->d_tvS = nullptr;
-    for (int k = 0; k < 12; ++k) { m->d_out[k] = nullptr; m->d_out32[k] = nullptr; }
     m->h_mats.resize(20);
     for (int k = 0; k < 20; ++k) {
         int r, c; mat_shape(d, k, &r, &c);
-        m->mat_rows[k] = r; m->mat_cols[k] = c; m->mat_size[k] = (size_t)r * c; m->d_mats[k] = nullptr;
+        m->mat_rows[k] = r; m->mat_cols[k] = c; m->mat_size[k] = (size_t)r * c;
         const size_t tot = m->mat_size[k] * n_models;
         m->h_mats[k].assign(tot, 0.0);
         if (tot == 0) continue;
@@ -105,7 +103,7 @@ static int model_create_impl(mld_model_t **out, const mld_dims *dims, int n_sets
         bool nonzero = false;
         for (size_t t = 0; t < tot && !nonzero; ++t) nonzero = m->h_mats[k][t] != 0.0;
         if (!nonzero) continue;   // all-zero matrices are skipped like the reference's _all_zero_mats short-cuts
-        hipError_t e = hipMalloc(&m->d_mats[k], sizeof(double) * tot);
+        hipError_t e = m->d_mats[k].alloc(tot);
         if (e == hipSuccess) e = hipMemcpy(m->d_mats[k], m->h_mats[k].data(), sizeof(double) * tot, hipMemcpyHostToDevice);
         if (e != hipSuccess) { mld_set_error("mld_model_create: %s", hipGetErrorString(e)); mld_model_destroy(m); return MLD_ERR_HIP; }
     }
@@ -141,7 +139,7 @@ static int model_create_impl(mld_model_t **out, const mld_dims *dims, int n_sets
                     dst += (size_t)rws[f] * nv;
                 }
             }
-            hipError_t e = hipMalloc(&m->d_pack, sizeof(double) * pack.size());
+            hipError_t e = m->d_pack.alloc(pack.size());
             if (e == hipSuccess) e = hipMemcpy(m->d_pack, pack.data(), sizeof(double) * pack.size(), hipMemcpyHostToDevice);
             if (e != hipSuccess) { mld_set_error("mld_model_create: %s", hipGetErrorString(e)); mld_model_destroy(m); return MLD_ERR_HIP; }
         }
@@ -152,15 +150,7 @@ static int model_create_impl(mld_model_t **out, const mld_dims *dims, int n_sets
 
 int mld_model_destroy(mld_model_t *m)
 {
-    if (!m) return MLD_OK;
-    for (int k = 0; k < 20; ++k) if (m->d_mats[k]) (void)hipFree(m->d_mats[k]);
-    if (m->d_blocks) (void)hipFree(m->d_blocks);
-    if (m->d_pack) (void)hipFree(m->d_pack);
-    if (m->d_tvQ) (void)hipFree(m->d_tvQ);
-    if (m->d_tvS) (void)hipFree(m->d_tvS);
-    for (int k = 0; k < 12; ++k) if (m->d_out[k]) (void)hipFree(m->d_out[k]);
-    for (int k = 0; k < 12; ++k) if (m->d_out32[k]) (void)hipFree(m->d_out32[k]);
-    delete m;
+    delete m;      /* (the device buffers release themselves) */
     return MLD_OK;
 }
 
