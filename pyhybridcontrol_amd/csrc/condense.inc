@@ -927,14 +927,15 @@ int condense_model_device(mld_model *m, int N, double *kernel_ms, hipStream_t st
     HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
     if (m->tv_N > 0) {   // one model per horizon step: block-rows computed and written in one pass
         const size_t lds_rows = condense_tv_rows_lds(m->lay, m->pack_len);
+        const size_t nn = (size_t)m->lay.nx * m->lay.nx;
+        const size_t lds_chain = sizeof(double) * ((size_t)N * nn + (size_t)N * m->lay.nx + 16 * 2 * nn + 16);   // k_tv_chain: all A_i, b5_i + 16 waves x 2 nx^2
         const int wmax = N * (m->lay.nv > m->lay.nw ? m->lay.nv : m->lay.nw);
         const bool small = wmax <= 640 && m->lay.nx <= 8;                      // <8, 10>: row accumulators and B columns in fewer registers
-        const bool wide = m->pack_len && lds_rows <= 144 * 1024 && wmax <= 1024 && m->lay.nx <= 16 && !(getenv("MLD_TV_CHAIN_ONLY"));
+        const bool wide = m->pack_len && lds_rows <= 144 * 1024 && lds_chain <= 160 * 1024 && wmax <= 1024 && m->lay.nx <= 16 && !(getenv("MLD_TV_CHAIN_ONLY"));
         if (wide) {
             const CondLayout &L = m->lay;
-            const size_t nn = (size_t)L.nx * L.nx, qlen = (size_t)m->n_models * (N * (N + 1) / 2) * nn, slen = (size_t)m->n_models * N * L.nx;
+            const size_t qlen = (size_t)m->n_models * (N * (N + 1) / 2) * nn, slen = (size_t)m->n_models * N * L.nx;
             if (!m->d_tvQ) { HIP_TRY(m->d_tvQ.alloc(qlen)); HIP_TRY(m->d_tvS.alloc(slen)); }
-            const size_t lds_chain = sizeof(double) * ((size_t)N * nn + (size_t)N * L.nx + 16 * 2 * nn + 16);
             if (lds_chain > 48 * 1024) (void)hipFuncSetAttribute((const void *)k_tv_chain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_chain);
             void (*rows)(CondLayout, CondPtrs, const double *, const double *) = small ? k_tv_rows<8, 10, 4> : k_tv_rows<16, 16, 2>;
             if (lds_rows > 48 * 1024) (void)hipFuncSetAttribute((const void *)rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rows);
