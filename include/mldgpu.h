@@ -78,21 +78,7 @@ typedef struct {
     int32_t mir_per_round; /* complemented mixed-integer rounding cuts on the original rows per cut round
                               (default -1 = 20 up to 400 binaries, binaries / 5 above; 0 = off) */
     int32_t flags;         /* MLD_F32 (default 0, see below) */
-    int32_t reserved;      /* diagnostics, default 0.  bit0 solver trace (builds with -DMLD_TRACE only), bit1 refactor at every
-                              verification, bit2 never refactor, bit3 no longest-first work queue, bit4 keep maintaining the rows
-                              that cannot bind under the root bounds, bit5 Gomory cuts one at a time (A/B of the wave-parallel
-                              round).  Results are the same up to rounding with every bit; only speed and traces change.
-                              bit6 first-fractional branching instead of penalty branching, bit7 K3 / K4 on the vector ALUs (k_rhs, k_gemm)
-                              instead of the matrix cores, bit8 relaxation-only batches (every binary fixed) on the dense-dictionary kernel instead of
-                              the LDS-resident revised simplex (k_lp_lds), bit9 k_lp_lds with a working-basis capacity of 24 (its overflow fall-back to the
-                              dense kernel then takes most instances), bit11 leave those instances at status -1 instead (counting only),
-                              (bit 10 belonged to the LDS-resident branch-and-cut experiment of rounds 2-3, removed in round 4: DESIGN section 4c), bit12 no per-instance presolve
-                              (A/B of presolve bit2 on the same problem handle),
-                              bit13 no anti-stalling cost
-                              perturbation in the dual simplex (A/B of round 3's change), bit14 no long-step (bound flipping) ratio test in the root LP (A/B),
-                              bit15 rounding cuts built one at a time by the whole workgroup instead of a wave per cut (A/B of round 4's change),
-                              bit16 no root restart (more cut rounds at the root of a cold instance once an incumbent leaves a gap of at most three tolerances; A/B of round 4's change),
-                              bit17 a MIP start is evaluated lazily (round 3: only when the deepening passes end without an incumbent) instead of before the root LP (A/B). */
+    int32_t reserved;      /* diagnostics, default 0: the bits of mld_reserved_bit below */
     double time_limit;     /* seconds per INSTANCE on the device clock (Gurobi TimeLimit; the reference passes TimeLimit=20 with every solve,
                               examples/residential_mg_with_pv_and_dewhs/micro_grid_control_simulation.py:232, forwarded by
                               controllers/controller_base.py:509-512): the branch-and-bound of an instance ends once it has run that long, like
@@ -102,6 +88,36 @@ typedef struct {
                               dive), so ONE instance ends within its limit plus its root LP and a few pivots; the limit is per instance, not per call: a batch larger than
                               the number of resident workgroups takes (instances / workgroups) x time_limit at worst.  0 (default) = no limit. */
 } mld_opts;
+
+/* mld_opts.reserved: diagnostic switches.  With bits 0-5 results are the same up to rounding; only speed and traces change. */
+typedef enum {
+    MLD_DBG_TRACE = 1 << 0,             /* solver trace (builds with -DMLD_TRACE only) */
+    MLD_DBG_REFACTOR_ALWAYS = 1 << 1,   /* refactor at every verification */
+    MLD_DBG_REFACTOR_NEVER = 1 << 2,    /* never refactor */
+    MLD_DBG_NO_ORDER = 1 << 3,          /* no longest-first work queue */
+    MLD_DBG_KEEP_DEAD_ROWS = 1 << 4,    /* keep maintaining the rows that cannot bind under the root bounds */
+    MLD_DBG_GMI_SERIAL = 1 << 5,        /* Gomory cuts one at a time (A/B of the wave-parallel round) */
+    MLD_DBG_FIRST_FRACTIONAL = 1 << 6,  /* first-fractional branching instead of penalty branching */
+    MLD_DBG_GEMM_VALU = 1 << 7,         /* K3 / K4 on the vector ALUs (k_rhs, k_gemm) instead of the matrix cores */
+    MLD_DBG_NO_LP_LDS = 1 << 8,         /* relaxation-only batches (every binary fixed) on the dense-dictionary kernel instead of the
+                                           LDS-resident revised simplex (k_lp_lds) */
+    MLD_DBG_LP_LDS_K24 = 1 << 9,        /* k_lp_lds with a working-basis capacity of 24 (its overflow fall-back to the dense kernel then
+                                           takes most instances) */
+                                        /* (bit 10 belonged to the LDS-resident branch-and-cut experiment of rounds 2-3, removed in
+                                           round 4: DESIGN section 4c) */
+    MLD_DBG_LP_LDS_NO_REDO = 1 << 11,   /* leave the k_lp_lds overflow instances at status -1 instead of re-solving them (counting only) */
+    MLD_DBG_NO_PRESOLVE = 1 << 12,      /* no per-instance presolve (A/B of presolve bit2 on the same problem handle) */
+    MLD_DBG_NO_PERTURB = 1 << 13,       /* no anti-stalling cost perturbation in the dual simplex (A/B of round 3's change) */
+    MLD_DBG_NO_LONG_STEP = 1 << 14,     /* no long-step (bound flipping) ratio test in the root LP (A/B) */
+    MLD_DBG_MIR_SERIAL = 1 << 15,       /* rounding cuts built one at a time by the whole workgroup instead of a wave per cut (A/B of
+                                           round 4's change) */
+    MLD_DBG_NO_RESTART = 1 << 16,       /* no root restart (more cut rounds at the root of a cold instance once an incumbent leaves a gap
+                                           of at most three tolerances; A/B of round 4's change) */
+    MLD_DBG_LAZY_START = 1 << 17,       /* a MIP start is evaluated lazily (round 3: only when the deepening passes end without an
+                                           incumbent) instead of before the root LP (A/B) */
+    MLD_DBG_NO_SWEEP = 1 << 19,         /* no closing sweep before the in-kernel hand-off publishes a stopped search's open nodes */
+    MLD_DBG_ASSERT_POSCTL = 1 << 20     /* positive control of the assertion build (-DMLD_ASSERT): one index check fails */
+} mld_reserved_bit;
 
 /* Linear cost in tiled horizon form (the Python layer parses the reference's string-keyed atoms,
  * controllers/components/objective_atoms.py:453-521, and tiles per-step weights :118-137).
@@ -255,7 +271,7 @@ int mld_advance_batch2(mld_problem_t *, int32_t *n_skipped_out);
  * clears the start.  The start is evaluated FIRST (binaries fixed, one LP from the slack basis, verified against the original rows; the root
  * relaxation is then solved from that leaf's basis): a feasible start becomes the incumbent, the cut loop stops as soon as the bound is within
  * the gap of it, and the search -- if one is still needed -- starts around it (RINS, then the guided depth-first search).  (Round 3 evaluated it only when the first passes ended without an incumbent:
- * opts.reserved bit 17.)  Any upload / selection of new inputs clears the start. */
+ * MLD_DBG_LAZY_START.)  Any upload / selection of new inputs clears the start. */
 int mld_set_warm_start(mld_problem_t *, const uint8_t *bin_start);
 /* The start built on the device from the last solution of the resident batch: shift = 0 takes the plan as it is (what warm_start=True means
  * to the reference's backend: the variables' previous values), shift = k > 0 moves it k steps towards the present and repeats its last step

@@ -524,7 +524,7 @@ static int set_cost_impl(mld_problem *p, const mld_cost *cost)
             // T = Ws * Mv (len x n) ; P += Mv' T ; Qx += (Ws Mx)' ... computed as Mv' (Ws Mx)
             const dim3 blk(256);
             auto gemm = [&](int Mm, int Nn, int K, int tA, const double *A, size_t sA, const double *Bp, size_t sB, double *Cp, size_t sC, double beta) {
-                if (p->opts.reserved & 128) hipLaunchKernelGGL(k_gemm, dim3((Nn + 15) / 16, (Mm + 15) / 16, M), blk, 0, sq, Mm, Nn, K, tA, A, sA, Bp, sB, Cp, sC, 1.0, beta);
+                if (p->opts.reserved & MLD_DBG_GEMM_VALU) hipLaunchKernelGGL(k_gemm, dim3((Nn + 15) / 16, (Mm + 15) / 16, M), blk, 0, sq, Mm, Nn, K, tA, A, sA, Bp, sB, Cp, sC, 1.0, beta);
                 else if (p->opts.flags & MLD_F32) hipLaunchKernelGGL(k_gemm_mfma<true>, dim3((Nn + GM_T - 1) / GM_T, (Mm + GM_T - 1) / GM_T, M), blk, 0, sq, Mm, Nn, K, tA, A, sA, Bp, sB, Cp, sC, 1.0, beta);
                 else hipLaunchKernelGGL(k_gemm_mfma<false>, dim3((Nn + GM_T - 1) / GM_T, (Mm + GM_T - 1) / GM_T, M), blk, 0, sq, Mm, Nn, K, tA, A, sA, Bp, sB, Cp, sC, 1.0, beta);
             };
@@ -780,7 +780,7 @@ int mld_problem_create(mld_problem_t **out, mld_model_t *model, int N_p, int N_t
             auto dbl_for = [&](int kc) { return (size_t)N * nc * nv + (size_t)kc * (kc + 1) + 3 * (size_t)n + m0 + 6 * (size_t)kc + (2 * ((size_t)n + m0 + 4 * (size_t)kc) + 3 * (size_t)n + m0 + 7) / 8 + 1; };   /* doubles before the fp32 bounds */
             auto lds_for = [&](int kc) { return sizeof(double) * dbl_for(kc) + sizeof(float) * 2 * (size_t)n + 64; };
             int kc = std::min(128, std::min(n, m0));
-            if (p->opts.reserved & 512) kc = std::min(kc, 24);      /* diagnostics: a small working-basis capacity so that the overflow fall-back runs */
+            if (p->opts.reserved & MLD_DBG_LP_LDS_K24) kc = std::min(kc, 24);      /* diagnostics: a small working-basis capacity so that the overflow fall-back runs */
             while (kc >= 8 && lds_for(kc) > budget) kc -= 4;
             if (kc >= 8 && n < 32767 && m0 < 32767) {
                 LS.kcap = kc; LS.ldw = kc + 1; LS.f32_off = (int)dbl_for(kc); p->lp_lds_bytes = lds_for(kc);
@@ -1124,7 +1124,7 @@ static int launch_lds_lp(mld_problem *p, std::vector<int> &redo)
     std::vector<int> stat(batch);
     HIP_TRY(hipMemcpy(stat.data(), p->bat.status, sizeof(int) * batch, hipMemcpyDeviceToHost));
     redo.clear();
-    if (!(p->opts.reserved & 2048))      /* diagnostics: bit 11 leaves status -1 visible instead of re-solving */
+    if (!(p->opts.reserved & MLD_DBG_LP_LDS_NO_REDO))      /* diagnostics: leave status -1 visible instead of re-solving */
         for (int i = 0; i < batch; ++i) if (stat[i] == -1) redo.push_back(i);
     return MLD_OK;
 }
@@ -1138,7 +1138,7 @@ static int launch_rhs_cost(mld_problem *p)
     const int *midx = p->has_midx ? p->bat.model_idx.get() : nullptr;
     if (p->m0 && !p->std_block)        /* no standard block: every row starts without a right-hand side; the extra blocks' row-wise minimum follows */
         hipLaunchKernelGGL(k_fill_f64, dim3((unsigned)(((size_t)batch * p->m0 + 255) / 256)), dim3(256), 0, sq, (size_t)batch * p->m0, 1.0e30, p->bat.hs);
-    else if (p->m0 && rhs_mfma_fits(p->nx, p->nW) && !(p->opts.reserved & 128))     /* K3 as one GEMM per model on the matrix cores */
+    else if (p->m0 && rhs_mfma_fits(p->nx, p->nW) && !(p->opts.reserved & MLD_DBG_GEMM_VALU))     /* K3 as one GEMM per model on the matrix cores */
         launch_rhs_mfma((p->opts.flags & MLD_F32) != 0, p->n_groups, p->m0, p->nx, p->nW, t->d_out[O_HX], t->d_out[O_HW], t->d_out[O_H5], p->d_rs,
                         p->bat.groups, p->bat.perm, p->bat.x0, p->bat.omega, p->bat.hs, sq);
     else if (p->m0)
@@ -1187,7 +1187,7 @@ static BatchDev batch_dev(const mld_problem *p, bool ho)
     B.status_out = b.status; B.nodes_out = b.nodes; B.pivots_out = b.pivots; B.cuts_out = b.cuts; B.refac_out = b.refac;
     B.ticks_out = b.ticks; B.rows_out = b.rows; B.prof_out = b.prof; B.trace = p->d_trace;
     B.counter = p->d_counter;
-    B.order = (p->order_batch == p->batch && !(p->opts.reserved & 8)) ? b.order.get() : nullptr;
+    B.order = (p->order_batch == p->batch && !(p->opts.reserved & MLD_DBG_NO_ORDER)) ? b.order.get() : nullptr;
     B.ho = ho ? 1 | (p->has_fixed ? 0 : 2) : 0; B.cap = p->batch_cap; B.tail = b.ho.tail; B.finished = b.ho.finished;
     B.ho_sub_nodes = p->ho_sub_nodes > 0 ? p->ho_sub_nodes : p->opts.max_nodes; B.ho_max_gen = p->ho_max_gen; B.ho_max_children = p->ho_max_children;
     B.item_src = b.ho.item_src; B.item_root = b.ho.item_root; B.item_gen = b.ho.item_gen; B.item_label = b.ho.item_label; B.item_ready = b.ho.item_ready;
@@ -1257,7 +1257,7 @@ static int launch(mld_problem *p)
     if (p->flight != Flight::idle) { mld_set_error("mld_solve_launch: the previous launch has not been finished"); return MLD_ERR_INVALID; }
     HIP_TRY(hipMemsetAsync(p->d_counter, 0, sizeof(int), sq));
     HIP_TRY(hipEventRecord(p->ev[0], sq));
-    const bool lp_path = p->lp_ok && p->all_fixed && !(p->opts.reserved & 256) && p->std_block && !p->has_quad && rhs_mfma_fits(p->nx, p->nW);
+    const bool lp_path = p->lp_ok && p->all_fixed && !(p->opts.reserved & MLD_DBG_NO_LP_LDS) && p->std_block && !p->has_quad && rhs_mfma_fits(p->nx, p->nW);
     std::vector<int> redo;      /* LP path: the overflow instances, re-solved by k_solve */
     int rc;
     if (lp_path && (rc = launch_lds_lp(p, redo))) return rc;
@@ -1323,7 +1323,7 @@ static int finish(mld_problem *p, mld_stats *st)
         st->nodes = h[0]; st->pivots = h[1]; st->cuts = h[2]; st->refactors = h[3];
         st->n_optimal = (int)h[4]; st->n_infeasible = (int)h[5]; st->n_node_limit = (int)h[6]; st->n_numerical = (int)h[7];
     }
-    if (dense && batch > p->n_slots && !(p->opts.reserved & 8)) {
+    if (dense && batch > p->n_slots && !(p->opts.reserved & MLD_DBG_NO_ORDER)) {
         /* Work-queue order for the next solve of this batch size: longest first (LPT).  Consecutive MPC steps solve
          * nearly the same instances, so the previous in-kernel time predicts the next one; starting the long
          * branch-and-bound runs first removes the partially idle tail of the persistent grid.  Results do not depend
@@ -1681,7 +1681,7 @@ int mld_rhs_batch(mld_problem_t *p, int batch, int scenarios, const int32_t *mod
     HIP_TRY(d_h.alloc(b * std::max(1, p->m0)));
     if (p->nx) HIP_TRY(hipMemcpy(d_x, x0, sizeof(double) * b * p->nx, hipMemcpyHostToDevice));
     if (p->nW) HIP_TRY(hipMemcpy(d_w, omega, sizeof(double) * b * scenarios * p->nW, hipMemcpyHostToDevice));
-    if (p->m0 && scenarios == 1 && rhs_mfma_fits(p->nx, p->nW) && !(p->opts.reserved & 128)) {
+    if (p->m0 && scenarios == 1 && rhs_mfma_fits(p->nx, p->nW) && !(p->opts.reserved & MLD_DBG_GEMM_VALU)) {
         std::vector<int> perm; std::vector<RhsGroup> groups;
         build_rhs_groups(model_idx, batch, p->n_models, perm, groups);
         if (!perm.empty()) { HIP_TRY(d_perm.alloc(perm.size())); HIP_TRY(hipMemcpy(d_perm, perm.data(), sizeof(int) * perm.size(), hipMemcpyHostToDevice)); }

@@ -1,4 +1,4 @@
-// solver trace (opts.reserved bit 0) is compiled in only with -DMLD_TRACE: device printf in the kernel costs registers
+// solver trace (opts.reserved MLD_DBG_TRACE) is compiled in only with -DMLD_TRACE: device printf in the kernel costs registers
 #ifdef MLD_TRACE
 #define MLD_PRINTF(...) printf(__VA_ARGS__)
 #else
@@ -28,6 +28,7 @@
                                  // -7 % on every pipelined figure of the bench, whether a restart ran or not, for one more proven instance in 256)
 #endif
 #define S_RESTART_ROUNDS 5        // cut rounds of a root restart
+#define S_RESTART_PATIENCE 3      // ... and rounds without progress of the bound before it gives up
 #ifndef S_RESTART_GAPS
 #define S_RESTART_GAPS 3.0       // the restart runs when the incumbent is within this many gap tolerances of the proven bound (MIPGap 1e-2: 3 %) ...
 #endif
@@ -267,7 +268,7 @@ struct Shared {
     int pivots, refactors, since_check;
     int lp_status;
     int perturbed;             // the cost row carries the anti-stalling perturbation (s_dual_simplex_impl)
-    int bfrt;                  // long-step ratio test in s_dual_simplex_impl (k_solve switches it on for the root LP)
+    int bfrt;                  // long-step ratio test in s_dual_simplex_impl (s_root switches it on for the root LP)
     unsigned long long rows;   // dictionary rows touched by rank-1 updates (traffic accounting)
     int nlive;                 // original rows still maintained (s_mark_dead)
     long long deadline;        // wall_clock64 value at which this instance's time limit ends (0 = none): checked between nodes, between cut rounds and every 128 pivots
@@ -434,6 +435,41 @@ struct Ws {
     double *clo, *chi;               // n: bounds the c-MIR builder and the dead-row test use for the structurals (s_presolve: implied bounds of this instance; the LP's own otherwise)
     int *fx_j;
 };
+
+// Binds the workspace of one slot (this workgroup's part of the solver's workspace, ws_base + blockIdx.x * S.ws_stride) and the LDS: the hot arrays
+// the shape placed in LDS (S.l* >= 0) live there, the rest in the slot
+__device__ __forceinline__ void s_bind_slot(Ws &w, const SolverShape &S, unsigned char *base, double *lds)
+{
+    w.D = (double *)(base + S.oD); w.Gc = (double *)(base + S.oGc); w.hc = (double *)(base + S.oHc);
+    w.lo = (double *)(base + S.oLo); w.hi = (double *)(base + S.oHi); w.xB = (double *)(base + S.oXB);
+    w.xN = (double *)(base + S.oXN); w.basic = (int *)(base + S.oBasic); w.nonbasic = (int *)(base + S.oNonbasic);
+    w.where = (int *)(base + S.oWhere); w.at_upper = base + S.oAtUp; w.skip = base + S.oSkip;
+    w.tmpx = (double *)(base + S.oTmpX); w.g = (double *)(base + S.oG); w.ax = (double *)(base + S.oAx);
+    w.root_lo = (double *)(base + S.oRootLo); w.root_hi = (double *)(base + S.oRootHi);
+    w.stk_j = (int *)(base + S.oStkJ); w.stk_first = base + S.oStkF; w.stk_second = base + S.oStkS;
+    w.sv_j = (int *)(base + S.oSvJ); w.sv_lo = (double *)(base + S.oSvLo); w.sv_hi = (double *)(base + S.oSvHi);
+    w.key = (double *)(base + S.oKey); w.xo = (double *)(base + S.oXo);
+    w.dw = (double *)(base + S.oDw); w.live = (unsigned short *)(base + S.oLive); w.mq = (double *)(base + S.oMq); w.stk_val = base + S.oStkV;
+    w.Y = (double *)(base + S.oY); w.PY = (double *)(base + S.oPY); w.Hm = (double *)(base + S.oHm); w.cm = (double *)(base + S.oCm);
+    w.wm = (double *)(base + S.oWm); w.gcost = (double *)(base + S.oGcost); w.vcur = (double *)(base + S.oVcur); w.Pv = (double *)(base + S.oPv);
+    w.mir_eff = (double *)(base + S.oMirEff); w.mir_delta = (double *)(base + S.oMirDelta); w.mir_cache = (double *)(base + S.oMirCache);
+    w.clo = (double *)(base + S.oClo); w.chi = (double *)(base + S.oChi);
+    w.xroot = (double *)(base + S.oXroot); w.fx_lo = (double *)(base + S.oFxLo); w.fx_hi = (double *)(base + S.oFxHi); w.fx_j = (int *)(base + S.oFxJ);
+    w.n = S.n; w.m0 = S.m0; w.mcap = S.mcap; w.ld = S.ld; w.nb = S.nb; w.dbg = S.debug;
+    w.nv_step = S.nv; w.nc_step = (S.N > 0 && S.m0 % S.N == 0) ? S.m0 / S.N : 0;
+    w.rowr = lds; w.colc = lds + (S.n + 2); w.dabuf = lds + (S.n + 2) + (S.mcap + 2);
+    w.seclist = (unsigned short *)(lds + (S.n + 2) + (S.mcap + 2) + (S.n + 2));
+    w.rowlist = w.seclist + S.seccap;
+    unsigned char *lb8 = (unsigned char *)lds;
+    if (S.lXB >= 0) w.xB = (double *)(lb8 + S.lXB); if (S.lXN >= 0) w.xN = (double *)(lb8 + S.lXN); if (S.lLo >= 0) w.lo = (double *)(lb8 + S.lLo);
+    if (S.lHi >= 0) w.hi = (double *)(lb8 + S.lHi); if (S.lBasic >= 0) w.basic = (int *)(lb8 + S.lBasic); if (S.lNonbasic >= 0) w.nonbasic = (int *)(lb8 + S.lNonbasic);
+    if (S.lAtUp >= 0) w.at_upper = lb8 + S.lAtUp; if (S.lSkip >= 0) w.skip = lb8 + S.lSkip; if (S.lDw >= 0) w.dw = (double *)(lb8 + S.lDw);
+    w.dcost = S.lCost >= 0 ? (double *)(lb8 + S.lCost) : w.D + (size_t)w.mcap * w.ld; w.dc_lds = S.lCost >= 0;
+    w.all_lds = S.lXB >= 0 && S.lXN >= 0 && S.lLo >= 0 && S.lHi >= 0 && S.lBasic >= 0 && S.lNonbasic >= 0 && S.lAtUp >= 0 && S.lSkip >= 0 && S.lDw >= 0 && S.lCost >= 0;
+    w.mir_in_lds = S.lMirCache >= 0;
+    w.mir_line = S.lMirLine >= 0 ? (double *)(lb8 + S.lMirLine) : nullptr; w.mir_cap = S.mir_cap;
+    if (S.lMirCache >= 0) w.mir_cache = (double *)(lb8 + S.lMirCache);
+}
 
 // Typed views of the hot per-basis state for the pivot loop (round 4): when EVERY hot array lives in LDS (Ws::all_lds: the bench shapes) the dual simplex and
 // the rank-1 update are instantiated with address_space(3) pointers -- ds_* instructions on one counter -- instead of the generic pointers of Ws, whose
@@ -1266,7 +1302,7 @@ __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double 
     HOT_VIEW(L, w);
     const int n = w.n, ld = w.ld, tid = threadIdx.x;
     const int m = sh.m;
-    bool pert_ok = !w.P && !(w.dbg & 8192);      // one perturbation per solve (diagnostics: opts.reserved bit 13 switches it off); while the cost row is
+    bool pert_ok = !w.P && !(w.dbg & MLD_DBG_NO_PERTURB);      // one perturbation per solve (diagnostics: MLD_DBG_NO_PERTURB switches it off); while the cost row is
                                                  // perturbed the objective cutoff below is suspended -- the caller compares the true value after s_unperturb, only where no cutoff reads the (perturbed) objective
     for (int i = tid; i < w.mcap; i += SOL_NT) { h_skip[i] &= 2; h_dw[i] = 1.0; }   // bit 1 (row never binding, s_mark_dead) stays; new devex reference framework: this basis
     int stall = 0, par = 0;
@@ -1323,8 +1359,8 @@ __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double 
                 const long long tr0 = wall_clock64();
                 if (tid == 0) sh.since_check = 0;
                 bool bad = s_check_residual(w, sh) > S_RESID_TOL;
-                if (w.dbg & 2) bad = true;       // diagnostics: refactor at every check
-                if (w.dbg & 4) bad = false;      // diagnostics: never refactor
+                if (w.dbg & MLD_DBG_REFACTOR_ALWAYS) bad = true;       // diagnostics: refactor at every check
+                if (w.dbg & MLD_DBG_REFACTOR_NEVER) bad = false;      // diagnostics: never refactor
                 if (bad) s_refactor(w, sh);
                 __syncthreads();
                 if (tid == 0) sh.prof[5] += wall_clock64() - tr0;
@@ -2344,12 +2380,12 @@ __device__ int s_mir_round(const Ws &w, Shared &sh, int max_cuts)
     const long long tcA = wall_clock64();
     if (tid == 0) sh.cprof[0] += tcA - tc_start;
 #endif
-    // ---- phase B (round 4: a wave per cut, eight at a time; opts.reserved bit 15 keeps the one-at-a-time version for an A/B).  The candidates are ranked once
+    // ---- phase B (round 4: a wave per cut, eight at a time; MLD_DBG_MIR_SERIAL keeps the one-at-a-time version for an A/B).  The candidates are ranked once
     //      by (efficacy descending, row ascending) -- the order the one-at-a-time loop takes them in; every wave builds the cut of its candidate with wave-level
     //      reductions only (the block-wide version spent eight barriers and reductions per cut: 11 % of the kernel), the accepted ones are appended in rank order.
     // While the per-wave lines fit LDS (cfg1-4 shapes).  At the cfg5 shape (n = 2303: lines in the slot, several hundred rows to substitute per cut) a wave per cut
     // measured 1.8 x SLOWER than the whole workgroup on one cut (15.5 s against 8.7 s for the 128 goldens): there the block-wide version below stays.
-    if (!(w.dbg & 32768) && w.mir_in_lds) {
+    if (!(w.dbg & MLD_DBG_MIR_SERIAL) && w.mir_in_lds) {
         int nc2 = 0;
         for (int i0 = 0; i0 < m0; i0 += SOL_NT) {
             const int i = i0 + tid;
@@ -2746,7 +2782,7 @@ __device__ __noinline__ bool s_leaf_eval(const Ws &w, Shared &sh, const SolverSh
     MLD_CHECK(w, ns >= 0 && ns <= nb, 128, ns, nb);
     s_set_bounds_list(w, sh, w.sv_j, w.key, w.key, ns);
     const int lpl = s_dual_simplex(w, sh, S_INF, S.max_pivots);
-    if ((S.debug & 1) && tid == 0) MLD_PRINTF("[inst %d] leaf lp=%d ns=%d node=%d\n", inst, lpl, ns, nodes);
+    if ((S.debug & MLD_DBG_TRACE) && tid == 0) MLD_PRINTF("[inst %d] leaf lp=%d ns=%d node=%d\n", inst, lpl, ns, nodes);
     bool leaf_ok = (lpl == LP_OPTIMAL);
     if (leaf_ok && w.P) { double lbq, fvq; leaf_ok = s_sd_relax(w, sh, S_INF, S.max_pivots, &lbq, &fvq) == 0; }
     if (leaf_ok) {
@@ -2789,7 +2825,7 @@ __device__ __noinline__ bool s_leaf_eval(const Ws &w, Shared &sh, const SolverSh
             }
         }
         worst = block_max(sh, worst);
-        if ((S.debug & 1) && tid == 0) MLD_PRINTF("[inst %d] leaf ob=%.12g worst=%.3e best=%.12g node=%d\n", inst, ob, worst, best, nodes);
+        if ((S.debug & MLD_DBG_TRACE) && tid == 0) MLD_PRINTF("[inst %d] leaf ob=%.12g worst=%.3e best=%.12g node=%d\n", inst, ob, worst, best, nodes);
         if (worst <= 1e-6 && ob < best) {
             best = ob; have = true;
             for (int j = tid; j < n; j += SOL_NT) v_out[j] = w.xo[j] * w.cs[j];
@@ -2902,14 +2938,629 @@ __device__ __forceinline__ double s_gtol(const SolverShape &S, double v) { retur
 // one round of cut separation (Gomory, then rounding cuts): called from the root cut loop and from the root restart -- one copy of the code
 __device__ __noinline__ int s_cut_round(const Ws &w, Shared &sh, const SolverShape &S)
 {
-    int k = (S.debug & 32) ? s_gmi_round_serial(w, sh, S.cuts_per_round) : s_gmi_round(w, sh, S.cuts_per_round);
+#ifdef MLD_CUT_PROF
+    const long long t0 = wall_clock64();
+#endif
+    int k = (S.debug & MLD_DBG_GMI_SERIAL) ? s_gmi_round_serial(w, sh, S.cuts_per_round) : s_gmi_round(w, sh, S.cuts_per_round);
+#ifdef MLD_CUT_PROF
+    if (threadIdx.x == 0) sh.cprof[2] += wall_clock64() - t0;
+#endif
     if (S.mir_per_round > 0) k += s_mir_round(w, sh, S.mir_per_round);
     return k;
 }
 
 // ------------------------------------------------------------------------------------------------
-// the persistent solve kernel
+// the persistent solve kernel: a claim loop over queue entries, each solved in inlined stages (a call on the node path costs the callee-saved
+// spills of a 256-VGPR function, DESIGN section 6): s_setup_entry, s_root, s_search, s_write_results
 // ------------------------------------------------------------------------------------------------
+// One queue entry, an instance or an item of the in-kernel hand-off (an open node of another search); read-only once set up.  inst: output row (an item's
+// can exceed a SUB-batch's size: the overflow list of the LDS paths holds instance numbers); isrc: the instance whose inputs (x0, omega, right-hand side,
+// model mdl) it uses; ext_cut: an external cutoff (hand-off: the value of the incumbent the open node was cut out of) -- the search looks only for better
+// points; fixed / warm: fixed binaries (255: free) / MIP start, or null; r_const: c0 + cx.x0 + cw.w (+ quadratic constant; controller_base.py:533-538)
+struct Entry {
+    int inst, isrc, mdl, max_nodes;
+    bool is_item, ext_cut;
+    const unsigned char *fixed, *warm;
+    const double *plb, *pub;
+    double *v_out, r_const;
+    long long t_begin;
+};
+
+// What the entry's solve has found and proven so far: the write-out reports it.
+struct Search {
+    double best = S_INF, root_bound = -S_INF, lb_proven = -S_INF;
+    int status = MLD_STATUS_INFEASIBLE, nodes = 1, cuts = 0;
+    bool have = false, unbounded = false;
+};
+
+// The search: iterative-deepening depth-first branch-and-bound, with a look-ahead dive and RINS for the degenerate instances (phases: see
+// oracle/mld_oracle.c, orc_solve_miqp).  Tree: the state of the phase loop and of its current pass; Node: what the node just evaluated leaves to decide.
+enum { PH_IDS = 0, PH_DIVE, PH_RINS, PH_FINAL };
+struct Tree {
+    int phase, pass = 0, node_budget, ids_cap, rins_rounds = 0, nfix = 0, donations = 0, lp = LP_OPTIMAL;      // lp: status of the last node's LP
+    double T, lbg, restart_best = S_INF, dive_tol;      // T: threshold of the passes; lbg: proven global lower bound (raised by every exhaustive pass)
+    bool limit = false, rescue = false, timed_out = false, started = false, xroot_set = false;
+    bool expanded = false, stopped_complete = false, published_rest = false;      // in-kernel hand-off: items published / the stopped search / all of its rest
+    int depth; double t_next, best_at_start; bool finished, dive_end;      // the current pass
+    // a COMPLETE search (plain depth-first search below the incumbent: FINAL, or the deepening passes once T is infinite) stopped at a limit: the stack
+    // describes everything that is still open -- for every level whose sibling has not been visited the node (path above it, variable flipped), plus the current path
+    __device__ bool complete() const { return limit && !finished && !rescue && (phase == PH_FINAL || (phase == PH_IDS && T == S_INF)); }
+};
+struct Node {
+    int branch_j = -1, force_first = -1; double branch_x = 0.0, obj = S_INF;
+    bool second_done = false, pen_pruned = false;      // penalty branching: preferred side, other side closed
+    bool qp_open = false;      // (quadratic cost: the node's QP relaxation hit the limit -- the node is unsolved, still open)
+};
+// s_leaf_eval on the entry's incumbent (through locals: a member of Search whose address reached the call would keep all of Search in scratch)
+__device__ __forceinline__ bool s_leaf(const Ws &w, Shared &sh, const SolverShape &S, const Entry &e, Search &s, int nodes)
+{
+    double best = s.best; bool have = s.have, unbounded = s.unbounded;
+    const bool ok = s_leaf_eval(w, sh, S, e.plb, e.pub, e.v_out, best, have, unbounded, e.inst, nodes);
+    s.best = best; s.have = have; s.unbounded = unbounded;
+    return ok;
+}
+
+// Entry set-up: the entry's model and inputs, the bounds with its fixings, its objective constant and cutoff, the per-instance presolve and the
+// rows that cannot bind.  Returns false when the presolve finds no point that satisfies the rows under the bounds (nothing to solve).
+__device__ __forceinline__ bool s_setup_entry(Ws &w, Shared &sh, const SolverShape &S, const ProblemDev &P, const BatchDev &B, Entry &e, Search &s)
+{
+    const int tid = threadIdx.x, n = S.n, nb = S.nb, inst = e.inst, isrc = e.isrc;
+    const int mdl = e.mdl = B.model_idx ? B.model_idx[isrc] : 0;
+    w.Gs = P.Gs + (size_t)mdl * S.m0 * n; w.hs = B.hs + (size_t)isrc * S.m0;
+    w.Gp = P.Gp ? P.Gp + (size_t)mdl * S.m0 * n : nullptr;
+    w.csr_ptr = P.csr_ptr ? P.csr_ptr + (size_t)mdl * (S.m0 + 1) : nullptr; w.csr_col = P.csr_ptr ? P.csr_col + (size_t)mdl * P.nnz_cap : nullptr; w.csr_val = P.csr_ptr ? P.csr_val + (size_t)mdl * P.nnz_cap : nullptr;
+    w.qs = B.qs_inst ? B.qs_inst + (size_t)isrc * n : P.qs + (size_t)mdl * n; w.cs = P.cs + (size_t)mdl * n;
+    w.P = (S.qp && P.Ps) ? P.Ps + (size_t)mdl * n * n : nullptr;
+    w.is_int = P.is_int; w.bins = P.bins; w.colperm = P.colperm;
+    e.plb = P.lb + (size_t)mdl * n; e.pub = P.ub + (size_t)mdl * n;
+    e.fixed = (B.fixed && (e.is_item || !(B.ho & 2))) ? B.fixed + (size_t)inst * nb : nullptr;      // (ho bit 1: the caller uploaded no fixings -- only items have them)
+    e.warm = (!e.is_item && B.warm && nb > 0 && B.warm[(size_t)inst * nb] != 255) ? B.warm + (size_t)inst * nb : nullptr;
+    e.v_out = B.v_out + (size_t)inst * n;
+    e.t_begin = wall_clock64();
+    if (tid == 0) { sh.m = S.m0; sh.pivots = 0; sh.refactors = 0; sh.since_check = 0; sh.rows = 0ull; sh.perturbed = 0; sh.bfrt = 0; for (int k = 0; k < 8; ++k) sh.prof[k] = 0;
+        sh.cut_cap = S.first_cap;
+        sh.deadline = 0; sh.timed_out = 0;      // (armed when the search starts: the root LP always runs to its end -- without it there is no answer at all)
+#ifdef MLD_PIVOT_PROF
+        for (int k = 0; k < 5; ++k) sh.pprof[k] = 0;
+#endif
+#ifdef MLD_CUT_PROF
+        sh.cprof[0] = sh.cprof[1] = sh.cprof[2] = 0;
+#endif
+    }
+    for (int j = tid; j < n; j += SOL_NT) { w.lo[j] = e.plb[j]; w.hi[j] = e.pub[j]; e.v_out[j] = 0.0; }
+    for (int i = tid; i < S.mcap; i += SOL_NT) { w.lo[n + i] = 0.0; w.hi[n + i] = S_INF; }
+    __syncthreads();
+    if (e.fixed)
+        for (int k = tid; k < nb; k += SOL_NT) if (e.fixed[k] != 255) { const int j = w.bins[k]; w.lo[j] = w.hi[j] = (double)e.fixed[k]; }
+    __syncthreads();
+    double part = 0.0;
+    if (P.cx) for (int j = tid; j < S.nx; j += SOL_NT) part += P.cx[(size_t)mdl * S.nx + j] * B.x0[(size_t)isrc * S.nx + j];
+    if (P.cw) for (int j = tid; j < S.nW; j += SOL_NT) part += P.cw[(size_t)mdl * S.nW + j] * B.omega[(size_t)isrc * S.nW + j];
+    e.r_const = block_sum(sh, part) + (P.c0 ? P.c0[mdl] : 0.0) + (B.rconst ? B.rconst[isrc] : 0.0);
+    e.ext_cut = B.cutoff && B.cutoff[inst] < 1.0e300;
+    if (e.ext_cut) s.best = B.cutoff[inst] - e.r_const;
+    if (tid == 0 && B.open_depth) B.open_depth[inst] = -1;
+    for (int j = tid; j < n; j += SOL_NT) { w.clo[j] = w.lo[j]; w.chi[j] = w.hi[j]; }
+    const bool pre_on = S.presolve && P.csr_ptr && !(S.debug & MLD_DBG_NO_PRESOLVE);
+    const bool pre_ok = !pre_on || s_presolve(w, sh, P, mdl);
+    if (!pre_ok && e.ext_cut) s.lb_proven = s.best - s_gtol(S, s.best) + 1e-12;      // (status: infeasible)
+    s_mark_dead(w, sh, !(S.debug & MLD_DBG_KEEP_DEAD_ROWS), (!e.fixed && P.act_max) ? P.act_max + (size_t)mdl * S.m0 : nullptr, (pre_on && pre_ok) ? &P : nullptr, mdl);
+    // (round 4: also under a quadratic cost -- a row that cannot bind under the root bounds cannot block a primal ratio test either, and s_primal_simplex skips such rows)
+    return pre_ok;
+}
+
+// Cut rows whose slack still sits basic in its own row (the cut never had to leave) and is clearly positive when a cut loop ends are not maintained
+// below the root (oracle: same rule): dropping a cut is always valid, the rank-1 updates skip the row (measured on the bench shard: 9.5 % fewer row
+// updates, 3.8 % less kernel time, proven share unchanged)
+__device__ __forceinline__ void s_purge_slack_cuts(const Ws &w, Shared &sh)
+{
+    __syncthreads(); for (int i = w.m0 + threadIdx.x; i < sh.m; i += SOL_NT) if (w.basic[i] == w.n + i && w.xB[i] > S_PURGE_SLACK) w.skip[i] = 2; __syncthreads();
+}
+
+// Cut rounds at an optimal root LP, each re-solved under `cutoff`: they end when a round finds no cut, after `rounds` rounds, after `patience` rounds
+// without progress of the bound, or at an LP that is not optimal (its status is returned).  The root cut loop (root_loop) also ends when an eager
+// start's incumbent is within the gap of the bound and at the TimeLimit; the root restart ends when the cut rows are full.
+__device__ __forceinline__ int s_cut_loop(const Ws &w, Shared &sh, const SolverShape &S, const Entry &e, Search &s, double cutoff, int rounds, int patience, bool root_loop)
+{
+    const int tid = threadIdx.x;
+    int stalled = 0;
+    for (int rnd = 0; rnd < rounds; ++rnd) {
+        if (!root_loop && sh.m >= S.mcap) break;
+        const double before = s_objective(w, sh);
+        const long long tc0 = wall_clock64();
+        if (root_loop) MLD_MARK(w, sh, 10 + rnd);
+        const int k = s_cut_round(w, sh, S);
+        if (tid == 0) sh.prof[2] += wall_clock64() - tc0;
+        if (root_loop) MLD_MARK(w, sh, 50 + rnd);
+        if (!k) break;
+        s.cuts += k;
+        const int cap = sh.pivots + 4 * S.m0 + 200;          // a cut round never needs more than this
+        const int lp = s_dual_simplex(w, sh, cutoff, cap < S.max_pivots ? cap : S.max_pivots);
+        if (lp != LP_OPTIMAL) return lp;
+        const double after = s_objective(w, sh);
+        if (root_loop && s.have && !e.ext_cut && after >= s.best - s_gtol(S, s.best)) break;      // (eager start: the bound is within the gap of the incumbent -- nothing left to prove)
+        if (after - before < 1e-6 * fmax(1.0, fabs(before))) { if (++stalled >= patience) break; } else stalled = 0;
+        if (root_loop && S.time_ticks > 0) {      // TimeLimit between cut rounds: the loop ends, the search takes the rest of the verdict
+            __syncthreads(); if (tid == 0) sh.timed_out = wall_clock64() - e.t_begin > S.time_ticks ? 1 : 0; __syncthreads();
+            if (sh.timed_out) break;
+        }
+    }
+    return LP_OPTIMAL;
+}
+
+// The root: LP + cut rounds.  If the LP breaks down while cutting (iteration cap / false infeasibility on a highly degenerate face), the root is rebuilt
+// from scratch and solved without cuts.  Under a quadratic cost the QP relaxation then gives the root bound.  Returns whether the search can start.
+__device__ __forceinline__ bool s_root(const Ws &w, Shared &sh, const SolverShape &S, const Entry &e, Search &s)
+{
+    const int tid = threadIdx.x, n = S.n, nb = S.nb;
+    bool root_ok = false, eager_done = false;
+    for (int attempt = 0; attempt < 2 && !root_ok; ++attempt) {
+        const bool use_cuts = (attempt == 0) && S.cut_rounds > 0;
+        __syncthreads(); if (tid == 0) sh.m = S.m0; __syncthreads();
+        s_reset_dictionary(w, sh);
+        for (int c = tid; c < n; c += SOL_NT) {   // place every non-basic at its dual-feasible bound
+            const int j = w.nonbasic[c];
+            const double dc = w.qs[j];
+            double lo = w.lo[j], hi = w.hi[j];
+            if (lo == hi) { w.at_upper[c] = 0; w.xN[c] = lo; }
+            else if (dc >= 0) { if (lo == -S_INF) { lo = -S_BIG; w.lo[j] = lo; } w.at_upper[c] = 0; w.xN[c] = lo; }
+            else { if (hi == S_INF) { hi = S_BIG; w.hi[j] = hi; } w.at_upper[c] = 1; w.xN[c] = hi; }
+        }
+        if (w.csr_ptr && sh.m == S.m0) s_refresh_initial(w, sh); else s_refresh(w, sh);
+        if (tid == 0 && attempt == 0) sh.prof[6] += wall_clock64() - e.t_begin;
+        __syncthreads();
+        MLD_MARK(w, sh, 2 + 1000 * attempt);
+        if (e.warm && !eager_done && !(S.debug & MLD_DBG_LAZY_START) && !w.P) {
+            // The MIP start FIRST (round 4; round 3 evaluated it lazily, only when the deepening passes ended without an incumbent -- MLD_DBG_LAZY_START
+            // restores that for an A/B): its leaf LP from the slack basis -- every binary fixed, an easy LP --, then the root relaxation from
+            // the leaf's basis.  In a closed loop the shifted plan is near-optimal, so the relaxation's optimum is a few pivots away from the leaf's
+            // vertex, the incumbent is known before the first cut, and the cut loop stops as soon as the bound is within the gap of it: closed loop
+            // step 24 7.5 k/s instead of 5.4 k/s (pivots per instance 340 instead of 434), step 4 27 k/s instead of 21 k/s, proven share unchanged
+            eager_done = true;
+            __syncthreads(); for (int k = tid; k < nb; k += SOL_NT) w.tmpx[w.bins[k]] = (double)e.warm[k]; __syncthreads();
+            (void)s_leaf(w, sh, S, e, s, 0);      // (a leaf, not a node of the tree: not counted)
+        }
+        if (tid == 0) sh.bfrt = (!w.P && !(S.debug & MLD_DBG_NO_LONG_STEP)) ? 1 : 0;      // long-step ratio test: root LP only
+        __syncthreads();
+        // Under an external cutoff (an open node handed off by another search) the root LP and every cut round stop as soon as the bound passes the
+        // cutoff: "nothing better in this node" is then known for a fraction of a root LP (83 % of the items of a bench shard end exactly so).
+        const double root_cut = e.ext_cut ? s.best - s_gtol(S, s.best) + 1e-12 : S_INF;
+        int lp = s_dual_simplex(w, sh, root_cut, S.max_pivots);
+        __syncthreads(); if (tid == 0) sh.bfrt = 0; __syncthreads();
+        if (lp == LP_CUTOFF) { s.status = MLD_STATUS_INFEASIBLE; s.lb_proven = root_cut; break; }
+        if (lp != LP_OPTIMAL) { s.status = (lp == LP_INFEASIBLE) ? MLD_STATUS_INFEASIBLE : MLD_STATUS_NUMERICAL; break; }
+        root_ok = true;
+        s.cuts = 0;
+        if (use_cuts) {
+            lp = s_cut_loop(w, sh, S, e, s, root_cut, S.cut_rounds, S_CUT_PATIENCE, true);
+            MLD_MARK(w, sh, 70);
+            if (lp == LP_CUTOFF) { s.status = MLD_STATUS_INFEASIBLE; s.lb_proven = root_cut; root_ok = false; break; }     // (external cutoff: the node is closed by its bound)
+            if (lp != LP_OPTIMAL) { root_ok = false; s.status = MLD_STATUS_NUMERICAL; s.cuts = 0; }       // rebuild without cuts
+            else s_purge_slack_cuts(w, sh);
+        }
+    }
+    if (root_ok && w.P) {   // root bound of the QP relaxation
+        // (an item of the in-kernel hand-off stops as soon as the bound passes its cutoff, as its root LP does: "nothing better in this node")
+        const double qcut = (e.is_item && e.ext_cut) ? s.best - s_gtol(S, s.best) + 1e-12 : S_INF;
+        double lbq, fvq;
+        const int rcq = s_sd_relax(w, sh, qcut, S.max_pivots, &lbq, &fvq);
+        if (rcq == 1) { root_ok = false; s.status = MLD_STATUS_INFEASIBLE; s.lb_proven = qcut; }
+        else if (rcq == -1) { root_ok = false; s.status = MLD_STATUS_NUMERICAL; }
+        else s.root_bound = rcq == -2 ? s_objective(w, sh) : lbq;      // (-2: the QP relaxation could not be finished -- the LP(q) value is a bound too)
+    }
+    if (root_ok && !w.P) s.root_bound = s_objective(w, sh);
+    return root_ok;
+}
+
+// Root restart (round 4; oracle: same rule; MLD_DBG_NO_RESTART switches it off for an A/B).  The final search is about to start from the root with
+// an incumbent that is CLOSE to the proven bound but not within the gap -- under the flat mid-day tariff that is the whole unproven tail (reported
+// gaps: median 1.7 %).  More cut rounds at the root, now under the incumbent's cutoff and in the cut rows the root cut loop left free, move the
+// bound the last percent for most of them (256 flat-tariff bench instances on the CPU restatement: 3 -> 1 unproven, -3 % row updates; instances
+// that never get here are untouched).  The cut loop itself may not be longer: ten rounds are what pays on the whole shard (DESIGN section 9).
+// Not for an instance with a MIP start: its cut loop already ran against the start's value (it ends when the bound is within the gap of it), and
+// in the closed loop the restart cost 8 % of the steady-state step for one more proven instance in 10 000.
+// Returns true when the root is closed by its bound under the incumbent's cutoff: nothing better than the incumbent by more than the gap exists.
+__device__ __forceinline__ bool s_root_restart(const Ws &w, Shared &sh, const SolverShape &S, const Entry &e, Search &s, Tree &t)
+{
+    if (!(t.phase == PH_FINAL && s.have && !e.warm && !e.ext_cut && !t.rescue && !w.P && S.cut_rounds > 0 && sh.m < S.mcap && s.best < t.restart_best &&
+          s.best - t.lbg <= S_RESTART_GAPS * s_gtol(S, s.best) && s.nodes >= e.max_nodes / 8 && !(S.debug & MLD_DBG_NO_RESTART)))
+        return false;
+    t.restart_best = s.best;
+    const double rcut = s.best - s_gtol(S, s.best) + 1e-12;
+    __syncthreads(); if (threadIdx.x == 0) sh.cut_cap = S.mcap; __syncthreads();
+    MLD_MARK(w, sh, 90);
+    int lp = s_dual_simplex(w, sh, rcut, S.max_pivots);
+    if (lp == LP_OPTIMAL) lp = s_cut_loop(w, sh, S, e, s, rcut, min(S_RESTART_ROUNDS, S.cut_rounds), S_RESTART_PATIENCE, false);
+    if (lp == LP_CUTOFF) { t.lbg = fmax(t.lbg, s.best - s_gtol(S, s.best)); s.status = MLD_STATUS_OPTIMAL; return true; }
+    if (lp == LP_OPTIMAL) { s_purge_slack_cuts(w, sh); const double ob = s_objective(w, sh); if (ob > t.lbg) t.lbg = ob; }
+    return false;
+}
+
+// RINS: fix the binaries on which incumbent and root relaxation agree for one pass (their root bounds saved in fx_*), and release them after it
+__device__ __forceinline__ void s_rins_fix(const Ws &w, Shared &sh, const Entry &e, Tree &t)
+{
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int nf = 0;
+        for (int k = 0; k < w.nb; ++k) {
+            const int j = w.bins[k];
+            if (w.root_lo[j] != w.root_hi[j] && fabs(w.xroot[k] - e.v_out[j]) <= S_INTTOL) {
+                w.fx_j[nf] = j; w.fx_lo[nf] = w.root_lo[j]; w.fx_hi[nf] = w.root_hi[j]; w.key[nf] = e.v_out[j]; nf++;
+                w.root_lo[j] = w.root_hi[j] = e.v_out[j];
+            }
+        }
+        sh.s_i[0] = nf;
+    }
+    __syncthreads();
+    t.nfix = sh.s_i[0];
+    MLD_CHECK(w, t.nfix >= 0 && t.nfix <= w.nb, 133, t.nfix, w.nb);
+    s_set_bounds_list(w, sh, w.fx_j, w.key, w.key, t.nfix);
+}
+
+__device__ __forceinline__ void s_rins_release(const Ws &w, Shared &sh, Tree &t)
+{
+    __syncthreads(); if (threadIdx.x == 0) for (int k = 0; k < t.nfix; ++k) { const int j = w.fx_j[k]; w.root_lo[j] = w.fx_lo[k]; w.root_hi[j] = w.fx_hi[k]; } __syncthreads();
+    s_set_bounds_list(w, sh, w.fx_j, w.fx_lo, w.fx_hi, t.nfix);
+    t.rins_rounds++;
+}
+
+// Reduced-cost fixing at the true root (no temporary fixings active): a non-basic binary whose reduced cost exceeds the room below the cutoff cannot
+// leave its bound in any solution that still matters; the fixing is permanent (ordered compaction -> deterministic list)
+__device__ __forceinline__ void s_reduced_cost_fixing(const Ws &w, Shared &sh, double room)
+{
+    const int tid = threadIdx.x, n = w.n;
+    const double *dd = w.dcost;
+    int nfx = 0;
+    __syncthreads();
+    for (int c0 = 0; c0 < n; c0 += SOL_NT) {
+        const int c = c0 + tid;
+        bool fx = false; int j = -1; double v = 0.0;
+        if (c < n) {
+            j = w.nonbasic[c];
+            if (j < n && w.is_int[j] && w.lo[j] != w.hi[j]) {
+                const double rc = w.at_upper[c] ? -dd[c] : dd[c];
+                if (rc > room + 1e-9) { fx = true; v = w.xN[c]; }
+            }
+        }
+        int rank;
+        const int tot = block_rank(sh, fx, &rank);
+        if (fx) { w.sv_j[nfx + rank] = j; w.key[nfx + rank] = v; w.root_lo[j] = v; w.root_hi[j] = v; }
+        nfx += tot;
+    }
+    __syncthreads();
+    MLD_CHECK(w, nfx <= w.nb, 132, nfx, w.nb);
+    if (nfx > 0) s_set_bounds_list(w, sh, w.sv_j, w.key, w.key, nfx);
+}
+
+// A node that is not pruned: its point (tmpx) and branching variable, or -- when there is none -- the evaluation of its rounded point as a leaf
+__device__ __forceinline__ void s_branch_or_leaf(const Ws &w, Shared &sh, const SolverShape &S, const Entry &e, Search &s, Tree &t, Node &nd,
+                                                 double obj, double cut, double inc_cut, bool qp_lp)
+{
+    const int tid = threadIdx.x, n = S.n, nb = S.nb;
+    if (w.P && !qp_lp) { __syncthreads(); for (int j = tid; j < n; j += SOL_NT) w.tmpx[j] = w.vcur[j]; __syncthreads(); }
+    else s_gather_x(w, sh, w.tmpx);
+    if (!t.xroot_set) { for (int k = tid; k < nb; k += SOL_NT) w.xroot[k] = w.tmpx[w.bins[k]]; t.xroot_set = true; }
+    if (t.depth == 0 && (s.have || e.ext_cut) && (t.phase == PH_IDS || t.phase == PH_FINAL) && !w.P) s_reduced_cost_fixing(w, sh, inc_cut - obj);
+    if (t.phase == PH_DIVE) {   // fractional binary closest to 1 (smallest index on ties)
+        double mv = -S_INF; int mi = -1;
+        for (int k = tid; k < nb; k += SOL_NT) {
+            const int j = w.bins[k];
+            const double x = w.tmpx[j];
+            // a FIXED binary is never a candidate (round 4): a basic variable with lo == hi can drift off its value by more than the integrality
+            // tolerance while the primal simplex of a QP relaxation (or of s_unperturb) ignores its tiny column entries -- picked again and again
+            // it made a dive of 700 levels on a 200-binary instance (oracle under ASan: the search stack overflowed; here: garbage in the
+            // arrays behind stk_j, an instance ending "infeasible" with 801 nodes)
+            if (fabs(x - rint(x)) > S_INTTOL && x > mv && w.lo[j] != w.hi[j]) { mv = x; mi = j; }
+        }
+        double tmp;
+        nd.branch_j = block_argmax(sh, mv, mi, &tmp);
+    } else if (!w.P && !(S.debug & MLD_DBG_FIRST_FRACTIONAL)) {
+        s_penalty_branch(w, sh, w.tmpx, obj, cut, inc_cut);
+        nd.branch_j = sh.s_i[0]; nd.force_first = sh.s_i[1]; nd.second_done = sh.s_i[2] != 0; nd.pen_pruned = sh.s_i[3] != 0;
+        const double tn = sh.s_d[1];
+        if (tn < t.t_next) t.t_next = tn;
+        __syncthreads();
+    } else {
+        // first fractional binary in index order
+        int key = 0x7fffffff;
+        for (int k = tid; k < nb; k += SOL_NT) {
+            const int j = w.bins[k];
+            if (fabs(w.tmpx[j] - rint(w.tmpx[j])) > S_INTTOL && j < key && w.lo[j] != w.hi[j]) key = j;
+        }
+        nd.branch_j = block_argmin_int(sh, key, key);
+    }
+    MLD_CHECK(w, nd.branch_j < n, 131, nd.branch_j, t.phase);
+    if (nd.branch_j >= 0) nd.branch_x = w.tmpx[nd.branch_j];
+    else if (!nd.pen_pruned) {
+        // leaf: fix every binary at its rounded value, re-solve, verify, restore
+        MLD_MARK(w, sh, 400 + t.phase);
+        const bool leaf_ok = s_leaf(w, sh, S, e, s, s.nodes);
+        if (!leaf_ok) {
+            // The rounded point is not feasible although every binary is within the integrality tolerance (a binary at 1e-6 can carry a whole unit
+            // of a big-M row): the node is NOT a leaf -- branch on the least integral free binary (smallest index on ties).
+            double mv = 1e-12; int mi = -1;
+            for (int k = tid; k < nb; k += SOL_NT) {
+                const int j = w.bins[k];
+                const double f = fabs(w.tmpx[j] - rint(w.tmpx[j]));
+                if (w.lo[j] != w.hi[j] && f > mv) { mv = f; mi = j; }
+            }
+            double tmp;
+            nd.branch_j = block_argmax(sh, mi >= 0 ? mv : -S_INF, mi, &tmp);
+            if (nd.branch_j >= 0) nd.branch_x = w.tmpx[nd.branch_j];
+        }
+    }
+}
+
+// One step of the dive, which does not backtrack: it ends at its first leaf, or when the node is infeasible.  Look-ahead LPs choose the child (not nodes
+// of the tree: NodeLimit counts the nodes a search evaluates, as the reference's backend does -- round 4).  True: the chosen child is evaluated next.
+__device__ __forceinline__ bool s_dive_step(const Ws &w, Shared &sh, const SolverShape &S, Tree &t, const Node &nd)
+{
+    if (nd.branch_j < 0) { t.dive_end = true; return false; }
+    const int j = nd.branch_j;
+    s_set_bounds(w, sh, j, 1.0, 1.0);
+    const int la = s_dual_simplex(w, sh, S_INF, S.max_pivots);
+    const double oa = la == LP_OPTIMAL ? s_objective(w, sh) : S_INF;
+    double take = 1.0;
+    if (la == LP_ITERLIMIT) t.limit = true;
+    else if (!(oa <= nd.obj + t.dive_tol)) {
+        s_set_bounds(w, sh, j, 0.0, 0.0);
+        const int lb2 = s_dual_simplex(w, sh, S_INF, S.max_pivots);
+        const double ob2 = lb2 == LP_OPTIMAL ? s_objective(w, sh) : S_INF;
+        if (lb2 == LP_ITERLIMIT) t.limit = true;
+        else if (ob2 <= oa) { take = 0.0; if (ob2 == S_INF) t.dive_end = true; }
+        else s_set_bounds(w, sh, j, 1.0, 1.0);
+    }
+    __syncthreads();
+    MLD_CHECK(w, t.depth >= 0 && t.depth < S.nb, 130, t.depth, 1);
+    if (t.depth >= S.nb) t.limit = true;      // (cannot happen: every level holds a different free binary; the stack has nb + 2 entries)
+    else { if (threadIdx.x == 0) { w.stk_j[t.depth] = j; w.stk_first[t.depth] = (unsigned char)take; w.stk_second[t.depth] = 1; } t.depth++; }
+    return !t.limit && !t.dive_end;
+}
+
+// End of a pass: what a complete search leaves open is recorded or published (hand-off), then the stack is unwound (entries are distinct variables)
+__device__ __forceinline__ void s_unwind(const Ws &w, Shared &sh, const SolverShape &S, const ProblemDev &P, const BatchDev &B, const Entry &e, Search &s, Tree &t, const Node &nd)
+{
+    const int tid = threadIdx.x, nb = S.nb, inst = e.inst;
+    __syncthreads();
+    const bool complete = t.complete();
+    if (B.open_depth) {      // sub-tree hand-off (mld_download_open_nodes)
+        if (complete)
+            for (int k = tid; k < t.depth; k += SOL_NT) {
+                const int j = w.stk_j[k];
+                B.open_var[(size_t)inst * nb + k] = (short)j; B.open_val[(size_t)inst * nb + k] = (unsigned char)(w.lo[j] > 0.5 ? 1 : 0); B.open_flag[(size_t)inst * nb + k] = w.stk_second[k];
+            }
+        if (tid == 0) B.open_depth[inst] = complete ? t.depth : -1;
+        __syncthreads();
+    }
+    if (B.ho && complete) {
+        // In-kernel hand-off: this COMPLETE search stopped at its node limit.  Everything it leaves open is published as entries of the work queue;
+        // whichever workgroup runs out of instances solves them (root LP and cut loop of their own, this search's incumbent as cutoff).
+        t.stopped_complete = true;
+        // CLOSING SWEEP before anything is published: most open siblings of a stopped search are trivial -- the warm dictionary closes
+        // them in a few pivots each, an item would pay a root LP and cut rounds for the same verdict (83 % of the items of a shard at the
+        // 1e-6 contract ended "nothing better in this node").  The stack is popped level by level; a level whose sibling has not been
+        // visited gets that sibling's LP under the incumbent's cutoff: closed -> accounted for, still open -> it becomes an item.
+        for (int k = tid; k < t.depth; k += SOL_NT) w.stk_val[k] = (unsigned char)(w.lo[w.stk_j[k]] > 0.5 ? 1 : 0);
+        __syncthreads();
+        const bool cur_open = nd.branch_j >= 0 || t.lp == LP_ITERLIMIT || nd.qp_open;      // (a node whose LP -- or QP relaxation -- hit the pivot limit is unsolved: still open)
+        const double sweep_cut = (s.have || e.ext_cut) ? s.best - s_gtol(S, s.best) : S_INF;
+        const int depth_pub = t.depth;
+        if (!(S.debug & MLD_DBG_NO_SWEEP))
+        for (int k = t.depth - 1; k >= 0; --k) {
+            const int j = w.stk_j[k];
+            if (!w.stk_second[k]) {
+                const double v = 1.0 - (double)w.stk_val[k];
+                s_set_bounds(w, sh, j, v, v);
+                const int l2 = s_dual_simplex(w, sh, sweep_cut + 1e-12, S.max_pivots);
+                s.nodes++;
+                bool closed = l2 == LP_CUTOFF || l2 == LP_INFEASIBLE;
+                if (l2 == LP_OPTIMAL) closed = s_objective(w, sh) > sweep_cut;
+                if (l2 == LP_OPTIMAL && !closed && w.P && sweep_cut < S_INF) closed = s_sweep_close_qp(w, sh, sweep_cut, S.max_pivots);
+                __syncthreads(); if (closed && tid == 0) w.stk_second[k] = 1; __syncthreads();
+            }
+            s_set_bounds(w, sh, j, w.root_lo[j], w.root_hi[j]);
+            t.depth = k;
+        }
+        const int pub = s_publish_nodes(w, sh, P, B, nb, inst, e.isrc, e.is_item, e.fixed, depth_pub, true, 0, (s.have || e.ext_cut) ? s.best + e.r_const : S_INF, w.stk_val, cur_open);
+        if (pub >= 0) t.expanded = t.published_rest = true;      // (0: the sweep closed everything that was open -- the search is complete)
+    }
+    for (int k = tid; k < t.depth; k += SOL_NT) { const int j = w.stk_j[k]; w.sv_lo[k] = w.root_lo[j]; w.sv_hi[k] = w.root_hi[j]; }
+    __syncthreads();
+    s_set_bounds_list(w, sh, w.stk_j, w.sv_lo, w.sv_hi, t.depth);
+    t.depth = 0;
+}
+
+// The rescue: one un-thresholded dive (no clock inside its LPs) returns a feasible point; false when there is an incumbent, a cutoff, or it has run
+__device__ __forceinline__ bool s_rescue(const Ws &w, Shared &sh, const Entry &e, const Search &s, Tree &t, bool refactor)
+{
+    if (s.have || t.rescue || e.ext_cut) return false;
+    if (refactor) s_refactor(w, sh);
+    if (threadIdx.x == 0) sh.deadline = 0;
+    t.rescue = true; t.limit = t.timed_out = false; t.T = S_INF; t.phase = PH_FINAL; t.node_budget = s.nodes + 3 * w.nb + 10;
+    return true;
+}
+
+// After a pass: the verdict, or the next pass and its phase.  Returns true when the search goes on.
+__device__ __forceinline__ bool s_next_phase(const Ws &w, Shared &sh, const SolverShape &S, const Entry &e, Search &s, Tree &t)
+{
+    const int nb = S.nb, MAXN = e.max_nodes;
+    if (t.finished) { if (s.unbounded) { s.status = MLD_STATUS_UNBOUNDED; s.best = -S_INF; } else if (!t.rescue) s.status = MLD_STATUS_OPTIMAL; return false; }
+    if (t.lp == LP_ITERLIMIT && !t.timed_out) return false;      // (an LP the TimeLimit interrupted is not a pivot limit: the rescue dive still owes a feasible point)
+    if (t.phase == PH_IDS && t.limit && !s.have && !t.rescue && !t.timed_out && s.nodes < MAXN && e.warm && !t.started) {
+        // MIP start (mld_set_warm_start / mld_warm_start_from_previous; the reference forwards warm_start=True to its backend,
+        // controller_base.py:493,509-512), evaluated lazily (oracle: same rule): only an instance whose deepening passes found no
+        // incumbent pays for it (one leaf); a feasible start takes the place of the dive and the search goes on with RINS around it
+        t.started = true;
+        __syncthreads(); for (int k = threadIdx.x; k < nb; k += SOL_NT) w.tmpx[w.bins[k]] = (double)e.warm[k]; __syncthreads();
+        MLD_MARK(w, sh, 450);
+        (void)s_leaf(w, sh, S, e, s, s.nodes);
+        if (s.have) { t.phase = PH_RINS; t.limit = false; t.T = S_INF; t.node_budget = min(MAXN, s.nodes + MAXN / 4); return true; }
+    }
+    if (t.timed_out) return s_rescue(w, sh, e, s, t, false);      // out of time: no further phase
+    if (t.phase == PH_IDS && t.limit && !s.have && !t.rescue && s.nodes < MAXN) {
+        // the dive may finish even when it outlasts the node budget (it is what guarantees a feasible point)
+        t.phase = PH_DIVE; t.limit = false; t.T = S_INF; t.node_budget = max(MAXN, s.nodes + 3 * nb + 10); return true;
+    }
+    if (t.phase == PH_DIVE) {
+        t.limit = s.nodes >= MAXN;
+        if (s.have && !t.limit) { t.phase = PH_RINS; t.node_budget = min(MAXN, s.nodes + MAXN / 4); return true; }
+        if (!s.have && !t.limit) { t.phase = PH_FINAL; t.node_budget = MAXN; return true; }
+    } else if (t.phase == PH_RINS) {
+        t.limit = s.nodes >= MAXN;
+        if (!t.limit) {
+            if (s.best < t.best_at_start && t.rins_rounds < 2) { t.node_budget = min(MAXN, s.nodes + MAXN / 4); return true; }
+            t.phase = PH_FINAL; t.node_budget = MAXN; return true;
+        }
+    }
+    if (t.limit) return s_rescue(w, sh, e, s, t, false);      // node limit
+    if (s.have && s.best - s_gtol(S, s.best) <= t.T) { s.status = MLD_STATUS_OPTIMAL; return false; }
+    if (t.t_next == S_INF) {
+        if (s_rescue(w, sh, e, s, t, true)) return true;      // every node "infeasible": re-derive the dictionary from the original rows and dive once more
+        s.status = s.have ? (t.rescue ? MLD_STATUS_NODE_LIMIT : MLD_STATUS_OPTIMAL) : MLD_STATUS_INFEASIBLE;
+        return false;
+    }
+    if (t.t_next > t.lbg) t.lbg = t.t_next;
+    if (s.have) t.T = S_INF;
+    else t.T = fmax(t.t_next + 1e-9 * fmax(1.0, fabs(t.t_next)), t.T + ldexp(2.5e-4, 2 * t.pass) * fmax(1.0, fabs(t.T)));
+    return true;
+}
+
+// The search below the root: passes of the phase loop, each a depth-first walk of the tree from the root, then the bound and status it proved.
+__device__ __forceinline__ void s_search(const Ws &w, Shared &sh, const SolverShape &S, const ProblemDev &P, const BatchDev &B, const Entry &e, Search &s)
+{
+    const int tid = threadIdx.x, n = S.n, nb = S.nb, MAXN = e.max_nodes;
+    for (int j = tid; j < n; j += SOL_NT) { w.root_lo[j] = w.lo[j]; w.root_hi[j] = w.hi[j]; }
+    __syncthreads();
+    Tree t;
+    // (under an external cutoff: plain depth-first search below it; with an incumbent from an eager start: RINS around it, then the final search)
+    t.node_budget = MAXN; t.phase = e.ext_cut ? PH_FINAL : (s.have ? PH_RINS : PH_IDS);
+    if (tid == 0) sh.deadline = S.time_ticks > 0 ? e.t_begin + S.time_ticks : 0;      // from here on the clock is also read every 128 pivots inside an LP
+    if (s.have && !e.ext_cut) {      // (the first pass is RINS: it needs the root relaxation's binaries now)
+        t.started = true; t.node_budget = min(MAXN, MAXN / 4);
+        s_gather_x(w, sh, w.tmpx);
+        for (int k = tid; k < nb; k += SOL_NT) w.xroot[k] = w.tmpx[w.bins[k]];
+        __syncthreads();
+        t.xroot_set = true;
+    }
+    t.ids_cap = MAXN / 8 > 16 ? MAXN / 8 : 16;
+    t.lbg = s.root_bound;
+    t.dive_tol = 1e-2 * fmax(1.0, fabs(s.root_bound));
+    t.T = (e.ext_cut || s.have) ? S_INF : s.root_bound + fmax(1e-7 * fmax(1.0, fabs(s.root_bound)), s_gtol(S, s.root_bound));
+    s.status = MLD_STATUS_NODE_LIMIT; s.nodes = 0;
+    do {
+        t.depth = 0; t.t_next = S_INF; t.finished = t.dive_end = false; t.best_at_start = s.best; t.pass++;
+        MLD_MARK(w, sh, 100 + 10 * t.phase + (t.pass < 10 ? t.pass : 9));
+        if (s_root_restart(w, sh, S, e, s, t)) break;
+        if (t.phase == PH_RINS) s_rins_fix(w, sh, e, t);
+        for (;;) {
+            s.nodes++;
+            Node nd;
+            // RINS is a heuristic on a sub-problem: it keeps ANY improvement (round 4; oracle: same rule).  With the proof's cutoff -- "better by more than the
+            // gap" -- it threw away exactly the points that matter at the cfg5 size: the dive's leaf is 0.5-1 % above the best point, the root bound within 1 % of THAT one
+            const double inc_cut = (s.have || e.ext_cut) ? ((t.phase == PH_RINS && s.have) ? s.best - 1e-6 * fmax(1.0, fabs(s.best)) : s.best - s_gtol(S, s.best)) : S_INF;
+            const double cut = fmin(t.T, inc_cut);
+            if (S.debug & MLD_DBG_TRACE) s_debug_dual(w, sh, e.inst, "node entry");
+            t.lp = s_dual_simplex(w, sh, cut + 1e-12, S.max_pivots);
+            if (S.debug & MLD_DBG_TRACE) s_debug_dual(w, sh, e.inst, "node exit");
+            if ((S.debug & MLD_DBG_TRACE) && tid == 0) MLD_PRINTF("[inst %d] node %d ph %d depth %d lp=%d obj=%.12g cut=%.12g T=%.12g pivots=%d\n", e.inst, s.nodes, t.phase, t.depth, t.lp, s_objective_nosync(w), cut, t.T, sh.pivots);
+            if (t.lp == LP_ITERLIMIT) t.limit = true;
+            else if (t.lp == LP_OPTIMAL || t.lp == LP_CUTOFF) {
+                double obj = s_objective(w, sh);      // LP(q) value: a valid bound also when P is PSD
+                bool pruned = (t.lp == LP_CUTOFF || obj > cut), qp_lp = false;
+                nd.obj = obj;
+                if (!pruned && w.P) {
+                    double lbq, fvq;
+                    const int rc = s_sd_relax(w, sh, cut, S.max_pivots, &lbq, &fvq);
+                    if (rc == -1) { t.limit = true; pruned = true; obj = S_INF; nd.qp_open = true; }
+                    else if (rc == -2) qp_lp = true;      // the QP relaxation could not be finished: this node goes on with its LP(q) bound and LP point
+                    else { obj = lbq; pruned = (rc == 1 || obj > cut); }
+                }
+                if (pruned) { if (obj <= inc_cut && obj < t.t_next) t.t_next = obj; }
+                else s_branch_or_leaf(w, sh, S, e, s, t, nd, obj, cut, inc_cut, qp_lp);
+            }
+            if (s.have && (t.rescue || s.unbounded || s.best <= t.lbg + s_gtol(S, s.best))) t.finished = true;
+            if (s.nodes >= ((t.phase == PH_IDS && !s.have && !t.rescue) ? t.ids_cap : t.node_budget)) {
+                t.limit = true;
+                if (B.ho && B.ho_donate > 0 && t.donations < B.ho_rounds && t.lp != LP_ITERLIMIT && !nd.qp_open && t.complete()) {
+                    // Node limit inside a complete search with the in-kernel hand-off on: give the LARGEST open subtrees away -- the shallowest
+                    // open siblings of the stack become items for idle workgroups -- and go on below them with a new budget.  What stays here are
+                    // the deep open nodes, which this dictionary closes in a few pivots each; an item pays a root LP and a cut loop of its own.
+                    const int given = s_publish_nodes(w, sh, P, B, nb, e.inst, e.isrc, e.is_item, e.fixed, t.depth, false, B.ho_donate, (s.have || e.ext_cut) ? s.best + e.r_const : S_INF, nullptr, false);
+                    if (given > 0) t.expanded = true;
+                    t.donations++;
+                    t.node_budget = s.nodes + B.ho_sub_nodes;
+                    t.limit = false;
+                }
+            }
+            if (S.time_ticks > 0 && !t.rescue) {      // TimeLimit (the reference forwards it per call, micro_grid_control_simulation.py:232): ends the search like the node limit
+                __syncthreads(); if (tid == 0) sh.s_i[4] = (wall_clock64() - e.t_begin > S.time_ticks) ? 1 : 0; __syncthreads();
+                if (sh.s_i[4]) { t.limit = true; t.timed_out = true; }
+            }
+            if (t.phase == PH_DIVE && !t.limit && !t.finished && s_dive_step(w, sh, S, t, nd)) continue;     // evaluate the chosen child
+            if (nd.branch_j >= 0 && t.depth >= nb) t.limit = true;      // (cannot happen, see the dive: the search ends rather than write behind its stack)
+            if (nd.branch_j >= 0 && !t.limit && !t.finished && !t.dive_end) {
+                double first = nd.force_first >= 0 ? (double)nd.force_first : (nd.branch_x >= 0.5 ? 1.0 : 0.0);
+                if (s.have && t.phase == PH_FINAL && !nd.second_done) first = rint(e.v_out[nd.branch_j] / w.cs[nd.branch_j]);   // guided (Danna et al. 2005): towards the incumbent first
+                __syncthreads();
+                MLD_CHECK(w, t.depth >= 0 && t.depth < nb && (first == 0.0 || first == 1.0), 130, t.depth, (int)(first * 1000));
+                if (tid == 0) { w.stk_j[t.depth] = nd.branch_j; w.stk_first[t.depth] = (unsigned char)first; w.stk_second[t.depth] = nd.second_done ? 1 : 0; }
+                t.depth++;
+                s_set_bounds(w, sh, nd.branch_j, first, first);
+                continue;
+            }
+            if (t.limit || t.finished || t.dive_end) { s_unwind(w, sh, S, P, B, e, s, t, nd); break; }
+            __syncthreads();
+            while (t.depth > 0 && w.stk_second[t.depth - 1]) { t.depth--; const int j = w.stk_j[t.depth]; s_set_bounds(w, sh, j, w.root_lo[j], w.root_hi[j]); }
+            if (t.depth == 0) break;
+            __syncthreads();
+            if (tid == 0) w.stk_second[t.depth - 1] = 1;
+            { const int j = w.stk_j[t.depth - 1]; const double v = 1.0 - (double)w.stk_first[t.depth - 1]; s_set_bounds(w, sh, j, v, v); }
+        }
+        if (t.phase == PH_RINS) s_rins_release(w, sh, t);
+    } while (s_next_phase(w, sh, S, e, s, t));
+    // every way of ending OPTIMAL has closed all nodes below best - gtol; otherwise the bound is what exhaustive passes proved
+    s.lb_proven = s.status == MLD_STATUS_OPTIMAL ? fmin(s.best, fmax(t.lbg, s.best - s_gtol(S, s.best))) : t.lbg;
+    if (B.ho && !t.expanded && !t.stopped_complete && s.status == MLD_STATUS_NODE_LIMIT && s.have) {
+        // The search stopped at a limit BEFORE it became a plain depth-first search below an incumbent (deepening passes, dive, RINS): no stack
+        // describes what is left, so its one open node is its own root -- published once more, now under the incumbent's value as cutoff (the
+        // item starts as a complete search and can be split).  Without an incumbent there is nothing to gain from running the same search again.
+        if (s_publish_nodes(w, sh, P, B, nb, e.inst, e.isrc, e.is_item, e.fixed, 0, true, 0, s.best + e.r_const, nullptr, true) > 0) t.expanded = t.published_rest = true;
+    }
+    if (t.expanded) {
+        // (internal statuses, merged by k_merge_*: what this entry left open lives on as its items.  Its own rest is closed when the search ended on its
+        // own, or when everything that was left went into items; the bound it reports is the one that holds for its WHOLE node -- a search that
+        // gave subtrees away has proven nothing about them)
+        if (s.status == MLD_STATUS_OPTIMAL || s.status == MLD_STATUS_INFEASIBLE || (s.status == MLD_STATUS_NODE_LIMIT && t.published_rest)) s.status = MLD_STATUS_EXPANDED;
+        else if (s.status == MLD_STATUS_NODE_LIMIT) s.status = MLD_STATUS_EXPANDED_OPEN;
+        s.lb_proven = t.lbg;
+    }
+}
+
+// Write-out: the entry's results (a SKIPPED item reports no work), then, with the in-kernel hand-off, the entry is counted as finished once its results
+// and any items it published are visible: the launch ends when finished == tail.
+__device__ __forceinline__ void s_write_results(Shared &sh, const BatchDev &B, const Entry &e, const Search &s)
+{
+    const bool skipped = s.status == MLD_STATUS_SKIPPED;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int inst = e.inst;
+        B.obj_out[inst] = s.have ? s.best + e.r_const : S_INF;
+        B.lb_out[inst] = s.lb_proven + e.r_const;
+        B.status_out[inst] = s.status;
+        B.nodes_out[inst] = s.nodes; B.pivots_out[inst] = skipped ? 0 : sh.pivots; B.cuts_out[inst] = s.cuts; B.refac_out[inst] = skipped ? 0 : sh.refactors;
+        B.ticks_out[inst] = skipped ? 0 : wall_clock64() - e.t_begin; B.rows_out[inst] = skipped ? 0 : (long long)sh.rows;
+#ifdef MLD_PIVOT_PROF
+        if (B.prof_out && !skipped) { for (int k = 0; k < 5; ++k) B.prof_out[(size_t)inst * 8 + k] = sh.pprof[k]; B.prof_out[(size_t)inst * 8 + 5] = 0; B.prof_out[(size_t)inst * 8 + 6] = 0; B.prof_out[(size_t)inst * 8 + 7] = sh.prof[7]; }
+#else
+        if (B.prof_out && !skipped) for (int k = 0; k < 8; ++k) B.prof_out[(size_t)inst * 8 + k] = sh.prof[k];
+#endif
+#ifdef MLD_CUT_PROF
+        if (B.prof_out && !skipped) { B.prof_out[(size_t)inst * 8 + 3] = sh.cprof[0]; B.prof_out[(size_t)inst * 8 + 4] = sh.cprof[1]; B.prof_out[(size_t)inst * 8 + 7] = sh.cprof[2]; }   // (diagnostic build: slots 3 / 4 / 7 = c-MIR scoring / c-MIR build / Gomory)
+#endif
+    }
+    if (B.ho) { __threadfence(); __syncthreads(); if (threadIdx.x == 0) __hip_atomic_fetch_add(B.finished, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
+}
+
 __global__ void __launch_bounds__(SOL_NT, SOL_WPE) k_solve(SolverShape S, ProblemDev P, BatchDev B, unsigned char *ws_base)
 {
     extern __shared__ double lds[];
@@ -2917,45 +3568,7 @@ __global__ void __launch_bounds__(SOL_NT, SOL_WPE) k_solve(SolverShape S, Proble
     __shared__ int s_inst, s_dead;
     const int tid = threadIdx.x;
     Ws w;
-    {
-        unsigned char *base = ws_base + (size_t)blockIdx.x * S.ws_stride;
-        w.D = (double *)(base + S.oD); w.Gc = (double *)(base + S.oGc); w.hc = (double *)(base + S.oHc);
-        w.lo = (double *)(base + S.oLo); w.hi = (double *)(base + S.oHi); w.xB = (double *)(base + S.oXB);
-        w.xN = (double *)(base + S.oXN); w.basic = (int *)(base + S.oBasic); w.nonbasic = (int *)(base + S.oNonbasic);
-        w.where = (int *)(base + S.oWhere); w.at_upper = base + S.oAtUp; w.skip = base + S.oSkip;
-        w.tmpx = (double *)(base + S.oTmpX); w.g = (double *)(base + S.oG); w.ax = (double *)(base + S.oAx);
-        w.root_lo = (double *)(base + S.oRootLo); w.root_hi = (double *)(base + S.oRootHi);
-        w.stk_j = (int *)(base + S.oStkJ); w.stk_first = base + S.oStkF; w.stk_second = base + S.oStkS;
-        w.sv_j = (int *)(base + S.oSvJ); w.sv_lo = (double *)(base + S.oSvLo); w.sv_hi = (double *)(base + S.oSvHi);
-        w.key = (double *)(base + S.oKey); w.xo = (double *)(base + S.oXo);
-        w.dw = (double *)(base + S.oDw); w.live = (unsigned short *)(base + S.oLive); w.mq = (double *)(base + S.oMq); w.stk_val = base + S.oStkV;
-        w.Y = (double *)(base + S.oY); w.PY = (double *)(base + S.oPY); w.Hm = (double *)(base + S.oHm); w.cm = (double *)(base + S.oCm);
-        w.wm = (double *)(base + S.oWm); w.gcost = (double *)(base + S.oGcost); w.vcur = (double *)(base + S.oVcur); w.Pv = (double *)(base + S.oPv);
-        w.mir_eff = (double *)(base + S.oMirEff); w.mir_delta = (double *)(base + S.oMirDelta); w.mir_cache = (double *)(base + S.oMirCache);
-        w.clo = (double *)(base + S.oClo); w.chi = (double *)(base + S.oChi);
-        w.xroot = (double *)(base + S.oXroot); w.fx_lo = (double *)(base + S.oFxLo); w.fx_hi = (double *)(base + S.oFxHi); w.fx_j = (int *)(base + S.oFxJ);
-        w.n = S.n; w.m0 = S.m0; w.mcap = S.mcap; w.ld = S.ld; w.nb = S.nb; w.dbg = S.debug;
-        w.nv_step = S.nv; w.nc_step = (S.N > 0 && S.m0 % S.N == 0) ? S.m0 / S.N : 0;
-        w.rowr = lds; w.colc = lds + (S.n + 2); w.dabuf = lds + (S.n + 2) + (S.mcap + 2);
-        w.seclist = (unsigned short *)(lds + (S.n + 2) + (S.mcap + 2) + (S.n + 2));
-        w.rowlist = w.seclist + S.seccap;
-        unsigned char *lb8 = (unsigned char *)lds;
-        if (S.lXB >= 0) w.xB = (double *)(lb8 + S.lXB);
-        if (S.lXN >= 0) w.xN = (double *)(lb8 + S.lXN);
-        if (S.lLo >= 0) w.lo = (double *)(lb8 + S.lLo);
-        if (S.lHi >= 0) w.hi = (double *)(lb8 + S.lHi);
-        if (S.lBasic >= 0) w.basic = (int *)(lb8 + S.lBasic);
-        if (S.lNonbasic >= 0) w.nonbasic = (int *)(lb8 + S.lNonbasic);
-        if (S.lAtUp >= 0) w.at_upper = lb8 + S.lAtUp;
-        if (S.lSkip >= 0) w.skip = lb8 + S.lSkip;
-        if (S.lDw >= 0) w.dw = (double *)(lb8 + S.lDw);
-        w.dcost = S.lCost >= 0 ? (double *)(lb8 + S.lCost) : w.D + (size_t)w.mcap * w.ld; w.dc_lds = S.lCost >= 0;
-        w.all_lds = S.lXB >= 0 && S.lXN >= 0 && S.lLo >= 0 && S.lHi >= 0 && S.lBasic >= 0 && S.lNonbasic >= 0 && S.lAtUp >= 0 && S.lSkip >= 0 && S.lDw >= 0 && S.lCost >= 0;
-        w.mir_in_lds = S.lMirCache >= 0;
-        w.mir_line = S.lMirLine >= 0 ? (double *)(lb8 + S.lMirLine) : nullptr; w.mir_cap = S.mir_cap;
-        if (S.lMirCache >= 0) w.mir_cache = (double *)(lb8 + S.lMirCache);
-    }
-    const int n = S.n, nb = S.nb;
+    s_bind_slot(w, S, ws_base + (size_t)blockIdx.x * S.ws_stride, lds);
     for (;;) {
         __syncthreads();
         if (tid == 0) {
@@ -2981,636 +3594,21 @@ __global__ void __launch_bounds__(SOL_NT, SOL_WPE) k_solve(SolverShape S, Proble
         __syncthreads();
         if (s_inst < 0) break;
         if (B.ho) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");             // an item's data was written by another workgroup (every wave: its own view)
-        const int inst = (B.order && s_inst < B.batch) ? B.order[s_inst] : s_inst;
-        const bool is_item = B.ho && s_inst >= B.batch;                         // an open node of another search (in-kernel hand-off; `inst` itself can exceed a
-                                                                                // SUB-batch's size: the overflow list of the LDS paths holds instance numbers)
-        const int isrc = is_item ? B.item_src[inst] : inst;                     // the instance whose inputs (x0, omega, right-hand side, model) this entry uses
-        const int MAXN = is_item ? B.ho_sub_nodes : S.max_nodes;                // node limit of this entry
-        if (is_item && s_dead) {
+        Entry e;
+        e.inst = (B.order && s_inst < B.batch) ? B.order[s_inst] : s_inst; e.is_item = B.ho && s_inst >= B.batch;
+        e.isrc = e.is_item ? B.item_src[e.inst] : e.inst; e.max_nodes = e.is_item ? B.ho_sub_nodes : S.max_nodes;
+        Search s;
+        if (e.is_item && s_dead) {
             // the tree this item belongs to has been given up (too many open nodes): nothing of it is solved any more
-            if (tid == 0) {
-                B.obj_out[inst] = S_INF; B.lb_out[inst] = -S_INF; B.status_out[inst] = MLD_STATUS_SKIPPED; B.nodes_out[inst] = 0; B.pivots_out[inst] = 0; B.cuts_out[inst] = 0;
-                B.refac_out[inst] = 0; B.ticks_out[inst] = 0; B.rows_out[inst] = 0;
-                __threadfence();
-                __hip_atomic_fetch_add(B.finished, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            continue;
+            s.status = MLD_STATUS_SKIPPED; s.nodes = 0; e.r_const = 0.0;
+        } else {
+            w.trace = B.trace ? B.trace + (size_t)blockIdx.x * 16 : nullptr;
+            if (w.trace && tid == 0) { w.trace[0] = e.inst; w.trace[1] = 1; w.trace[2] = 0; w.trace[3] = s_inst; __threadfence_system(); }
+            MLD_CHECK(w, e.inst >= 0 && e.inst < B.batch, 129, e.inst, s_inst);
+            MLD_CHECK(w, !(S.debug & MLD_DBG_ASSERT_POSCTL), 999, e.inst, s_inst);      // (positive control of the assertion build: this one fails)
+            if (s_setup_entry(w, sh, S, P, B, e, s) && s_root(w, sh, S, e, s)) s_search(w, sh, S, P, B, e, s);
+            MLD_MARK(w, sh, 999);
         }
-        w.trace = B.trace ? B.trace + (size_t)blockIdx.x * 16 : nullptr;
-        if (w.trace && tid == 0) { w.trace[0] = inst; w.trace[1] = 1; w.trace[2] = 0; w.trace[3] = s_inst; __threadfence_system(); }
-        MLD_CHECK(w, inst >= 0 && inst < B.batch, 129, inst, s_inst);
-        MLD_CHECK(w, !(S.debug & (1 << 20)), 999, inst, s_inst);      // (positive control of the assertion build: opts.reserved bit 20 makes this one fail)
-        const int mdl = B.model_idx ? B.model_idx[isrc] : 0;
-        w.Gs = P.Gs + (size_t)mdl * S.m0 * n; w.hs = B.hs + (size_t)isrc * S.m0;
-        w.Gp = P.Gp ? P.Gp + (size_t)mdl * S.m0 * n : nullptr;
-        w.csr_ptr = P.csr_ptr ? P.csr_ptr + (size_t)mdl * (S.m0 + 1) : nullptr; w.csr_col = P.csr_ptr ? P.csr_col + (size_t)mdl * P.nnz_cap : nullptr; w.csr_val = P.csr_ptr ? P.csr_val + (size_t)mdl * P.nnz_cap : nullptr;
-        w.qs = B.qs_inst ? B.qs_inst + (size_t)isrc * n : P.qs + (size_t)mdl * n; w.cs = P.cs + (size_t)mdl * n;
-        w.P = (S.qp && P.Ps) ? P.Ps + (size_t)mdl * n * n : nullptr;
-        w.is_int = P.is_int; w.bins = P.bins; w.colperm = P.colperm;
-        const double *plb = P.lb + (size_t)mdl * n, *pub = P.ub + (size_t)mdl * n;
-        const unsigned char *fixed = (B.fixed && (is_item || !(B.ho & 2))) ? B.fixed + (size_t)inst * nb : nullptr;      // (ho bit 1: the caller uploaded no fixings -- only items have them)
-        const unsigned char *warm = (!is_item && B.warm && nb > 0 && B.warm[(size_t)inst * nb] != 255) ? B.warm + (size_t)inst * nb : nullptr;   // MIP start of this instance
-        double *v_out = B.v_out + (size_t)inst * n;
-        // ---- set-up ------------------------------------------------------------------------------
-        const long long t_begin = wall_clock64();
-#ifdef MLD_CUT_PROF
-        if (tid == 0) { sh.cprof[0] = sh.cprof[1] = sh.cprof[2] = 0; }
-#endif
-        if (tid == 0) { sh.m = S.m0; sh.pivots = 0; sh.refactors = 0; sh.since_check = 0; sh.rows = 0ull; sh.perturbed = 0; sh.bfrt = 0; for (int k = 0; k < 8; ++k) sh.prof[k] = 0;
-            sh.cut_cap = S.first_cap;
-            sh.deadline = 0; sh.timed_out = 0;      // (armed when the search starts: the root LP always runs to its end -- without it there is no answer at all)
-#ifdef MLD_PIVOT_PROF
-            for (int k = 0; k < 5; ++k) sh.pprof[k] = 0;
-#endif
-        }
-        for (int j = tid; j < n; j += SOL_NT) { w.lo[j] = plb[j]; w.hi[j] = pub[j]; v_out[j] = 0.0; }
-        for (int i = tid; i < S.mcap; i += SOL_NT) { w.lo[n + i] = 0.0; w.hi[n + i] = S_INF; }
-        __syncthreads();
-        if (fixed)
-            for (int k = tid; k < nb; k += SOL_NT) if (fixed[k] != 255) { const int j = w.bins[k]; w.lo[j] = w.hi[j] = (double)fixed[k]; }
-        __syncthreads();
-        // ---- root LP + cut rounds.  If the LP breaks down while cutting (iteration cap / false infeasibility on a
-        //      highly degenerate face), the root is rebuilt from scratch and solved without cuts.
-        int status = MLD_STATUS_INFEASIBLE, nodes = 1, cuts = 0;
-        double best = S_INF, root_bound = -S_INF, lb_proven = -S_INF;
-        bool have = false, root_ok = false, root_closed = false, eager_done = false, unbounded_pre = false;
-        int nodes_pre = 0;
-        // objective constant of this instance (controller_base.py:533-538 returns the objective WITH it): r = c0 + cx.x0 + cw.w (+ quadratic constant)
-        double r_const;
-        {
-            double part = 0.0;
-            if (P.cx) for (int j = tid; j < S.nx; j += SOL_NT) part += P.cx[(size_t)mdl * S.nx + j] * B.x0[(size_t)isrc * S.nx + j];
-            if (P.cw) for (int j = tid; j < S.nW; j += SOL_NT) part += P.cw[(size_t)mdl * S.nW + j] * B.omega[(size_t)isrc * S.nW + j];
-            r_const = block_sum(sh, part) + (P.c0 ? P.c0[mdl] : 0.0) + (B.rconst ? B.rconst[isrc] : 0.0);
-        }
-        // external cutoff (sub-tree hand-off: the value of the incumbent the open node was cut out of): the search looks only for better points
-        const bool ext_cut = B.cutoff && B.cutoff[inst] < 1.0e300;
-        if (ext_cut) best = B.cutoff[inst] - r_const;
-        if (tid == 0 && B.open_depth) B.open_depth[inst] = -1;
-        int lp = LP_OPTIMAL;
-        for (int j = tid; j < n; j += SOL_NT) { w.clo[j] = w.lo[j]; w.chi[j] = w.hi[j]; }
-        const bool pre_on = S.presolve && P.csr_ptr && !(S.debug & 4096);      // (diagnostics: opts.reserved bit 12 switches the per-instance presolve off for an A/B)
-        bool pre_ok = true;
-        if (pre_on) {
-            pre_ok = s_presolve(w, sh, P, mdl);
-            if (!pre_ok) { status = MLD_STATUS_INFEASIBLE; if (ext_cut) lb_proven = best - s_gtol(S, best) + 1e-12; }      // (no point satisfies the rows under the bounds: nothing to solve)
-        }
-        s_mark_dead(w, sh, !(S.debug & 16), (!fixed && P.act_max) ? P.act_max + (size_t)mdl * S.m0 : nullptr, (pre_on && pre_ok) ? &P : nullptr, mdl);     // (round 4: also under a quadratic cost -- a row that cannot bind
-                                                                                                                          //  under the root bounds cannot block a primal ratio test either, and s_primal_simplex skips such rows)
-        for (int attempt = 0; attempt < 2 && !root_ok && pre_ok; ++attempt) {
-            const bool use_cuts = (attempt == 0) && S.cut_rounds > 0;
-            __syncthreads();
-            if (tid == 0) sh.m = S.m0;
-            __syncthreads();
-            s_reset_dictionary(w, sh);
-            for (int c = tid; c < n; c += SOL_NT) {   // place every non-basic at its dual-feasible bound
-                const int j = w.nonbasic[c];
-                const double dc = w.qs[j];
-                double lo = w.lo[j], hi = w.hi[j];
-                if (lo == hi) { w.at_upper[c] = 0; w.xN[c] = lo; }
-                else if (dc >= 0) { if (lo == -S_INF) { lo = -S_BIG; w.lo[j] = lo; } w.at_upper[c] = 0; w.xN[c] = lo; }
-                else { if (hi == S_INF) { hi = S_BIG; w.hi[j] = hi; } w.at_upper[c] = 1; w.xN[c] = hi; }
-            }
-            if (w.csr_ptr && sh.m == S.m0) s_refresh_initial(w, sh); else s_refresh(w, sh);
-            if (tid == 0 && attempt == 0) sh.prof[6] += wall_clock64() - t_begin;
-            __syncthreads();
-            MLD_MARK(w, sh, 2 + 1000 * attempt);
-            if (warm && !eager_done && !(S.debug & 131072) && !w.P) {
-                // The MIP start FIRST (round 4; round 3 evaluated it lazily, only when the deepening passes ended without an incumbent -- opts.reserved
-                // bit 17 restores that for an A/B): its leaf LP from the slack basis -- every binary fixed, an easy LP --, then the root relaxation from
-                // the leaf's basis.  In a closed loop the shifted plan is near-optimal, so the relaxation's optimum is a few pivots away from the leaf's
-                // vertex, the incumbent is known before the first cut, and the cut loop stops as soon as the bound is within the gap of it: closed loop
-                // step 24 7.5 k/s instead of 5.4 k/s (pivots per instance 340 instead of 434), step 4 27 k/s instead of 21 k/s, proven share unchanged
-                eager_done = true;
-                __syncthreads();
-                for (int k = tid; k < nb; k += SOL_NT) w.tmpx[w.bins[k]] = (double)warm[k];
-                __syncthreads();
-                (void)s_leaf_eval(w, sh, S, plb, pub, v_out, best, have, unbounded_pre, inst, 0);      // (a leaf, not a node of the tree: not counted)
-            }
-            if (tid == 0) sh.bfrt = (!w.P && !(S.debug & 16384)) ? 1 : 0;      // long-step ratio test: root LP only (diagnostics: opts.reserved bit 14 switches it off for an A/B)
-            __syncthreads();
-            // Under an external cutoff (an open node handed off by another search) the root LP and every cut round stop as soon as the bound passes the
-            // cutoff: "nothing better in this node" is then known for a fraction of a root LP (83 % of the items of a bench shard end exactly so).
-            const double root_cut = ext_cut ? best - s_gtol(S, best) + 1e-12 : S_INF;
-            lp = s_dual_simplex(w, sh, root_cut, S.max_pivots);
-            __syncthreads();
-            if (tid == 0) sh.bfrt = 0;
-            __syncthreads();
-            if (lp == LP_CUTOFF) { status = MLD_STATUS_INFEASIBLE; lb_proven = root_cut; break; }
-            if (lp != LP_OPTIMAL) { status = (lp == LP_INFEASIBLE) ? MLD_STATUS_INFEASIBLE : MLD_STATUS_NUMERICAL; break; }
-            root_ok = true;
-            cuts = 0;
-            if (use_cuts) {
-                int stalled = 0;
-                for (int rnd = 0; rnd < S.cut_rounds; ++rnd) {
-                    const double before = s_objective(w, sh);
-                    const long long tc0 = wall_clock64();
-                    MLD_MARK(w, sh, 10 + rnd);
-#ifdef MLD_CUT_PROF
-                    int k = (S.debug & 32) ? s_gmi_round_serial(w, sh, S.cuts_per_round) : s_gmi_round(w, sh, S.cuts_per_round);
-                    if (tid == 0) sh.cprof[2] += wall_clock64() - tc0;
-                    MLD_MARK(w, sh, 30 + rnd);
-                    if (S.mir_per_round > 0) k += s_mir_round(w, sh, S.mir_per_round);
-#else
-                    const int k = s_cut_round(w, sh, S);
-#endif
-                    if (tid == 0) sh.prof[2] += wall_clock64() - tc0;
-                    MLD_MARK(w, sh, 50 + rnd);
-                    if (!k) break;
-                    cuts += k;
-                    const int cap = sh.pivots + 4 * S.m0 + 200;          // a cut round never needs more than this
-                    lp = s_dual_simplex(w, sh, root_cut, cap < S.max_pivots ? cap : S.max_pivots);
-                    if (lp == LP_CUTOFF) { root_closed = true; break; }     // (external cutoff: the node is closed by its bound)
-                    if (lp != LP_OPTIMAL) { root_ok = false; break; }       // rebuild without cuts
-                    const double after = s_objective(w, sh);
-                    if (have && !ext_cut && after >= best - s_gtol(S, best)) break;      // (eager start: the bound is within the gap of the incumbent -- nothing left to prove)
-                    if (after - before < 1e-6 * fmax(1.0, fabs(before))) { if (++stalled >= S_CUT_PATIENCE) break; } else stalled = 0;
-                    if (S.time_ticks > 0) {      // TimeLimit between cut rounds: the loop ends, the search below takes the rest of the verdict
-                        __syncthreads();
-                        if (tid == 0) sh.timed_out = wall_clock64() - t_begin > S.time_ticks ? 1 : 0;
-                        __syncthreads();
-                        if (sh.timed_out) break;
-                    }
-                }
-                MLD_MARK(w, sh, 70);
-                if (root_closed) { status = MLD_STATUS_INFEASIBLE; lb_proven = root_cut; root_ok = false; break; }
-                if (!root_ok) { status = MLD_STATUS_NUMERICAL; cuts = 0; }
-                else {
-                    // cut rows whose slack still sits basic in its own row (the cut never had to leave) and is clearly positive when the cut loop
-                    // ends are not maintained below the root (oracle: same rule): dropping a cut is always valid, the rank-1 updates skip the row
-                    // (measured on the bench shard: 9.5 % fewer row updates, 3.8 % less kernel time, proven share unchanged)
-                    __syncthreads();
-                    for (int i = S.m0 + tid; i < sh.m; i += SOL_NT) if (w.basic[i] == n + i && w.xB[i] > S_PURGE_SLACK) w.skip[i] = 2;
-                    __syncthreads();
-                }
-            }
-        }
-        if (root_ok && w.P) {   // root bound of the QP relaxation
-            // (an item of the in-kernel hand-off stops as soon as the bound passes its cutoff, as its root LP does: "nothing better in this node")
-            const double qcut = (is_item && ext_cut) ? best - s_gtol(S, best) + 1e-12 : S_INF;
-            double lbq, fvq;
-            const int rcq = s_sd_relax(w, sh, qcut, S.max_pivots, &lbq, &fvq);
-            if (rcq == 1) { root_ok = false; status = MLD_STATUS_INFEASIBLE; lb_proven = qcut; }
-            else if (rcq == -1) { root_ok = false; status = MLD_STATUS_NUMERICAL; }
-            else root_bound = rcq == -2 ? s_objective(w, sh) : lbq;      // (-2: the QP relaxation could not be finished -- the LP(q) value is a bound too)
-        }
-        if (root_ok) {
-            if (!w.P) root_bound = s_objective(w, sh);
-            for (int j = tid; j < n; j += SOL_NT) { w.root_lo[j] = w.lo[j]; w.root_hi[j] = w.hi[j]; }
-            __syncthreads();
-            // ---- iterative-deepening depth-first branch-and-bound, with a look-ahead dive and RINS for the
-            //      degenerate instances (phases: see oracle/mld_oracle.c, orc_solve_miqp) ------------------
-            enum { PH_IDS = 0, PH_DIVE, PH_RINS, PH_FINAL };
-            bool limit = false, rescue = false, unbounded = false, timed_out = false, started = false, expanded = false, stopped_complete = false, published_rest = false;
-            int donations = 0;
-            int pass = 0, node_budget = MAXN, phase = ext_cut ? PH_FINAL : (have ? PH_RINS : PH_IDS), rins_rounds = 0, nfix = 0;   // (under an external cutoff: plain depth-first search below it; with an incumbent from an eager start: RINS around it, then the final search)
-            if (tid == 0) sh.deadline = S.time_ticks > 0 ? t_begin + S.time_ticks : 0;      // from here on the clock is also read every 128 pivots inside an LP
-            bool xroot_set = false;
-            if (have && !ext_cut) {      // (the first pass is RINS: it needs the root relaxation's binaries now)
-                started = true; node_budget = min(MAXN, MAXN / 4);
-                s_gather_x(w, sh, w.tmpx);
-                for (int k = tid; k < nb; k += SOL_NT) w.xroot[k] = w.tmpx[w.bins[k]];
-                __syncthreads();
-                xroot_set = true;
-            }
-            const int ids_cap = MAXN / 8 > 16 ? MAXN / 8 : 16;
-            double lbg = root_bound;      // proven global lower bound: raised by every exhaustive pass
-            double restart_best = S_INF;  // incumbent value of the last root restart
-            const double dive_tol = 1e-2 * fmax(1.0, fabs(root_bound));
-            double T = (ext_cut || have) ? S_INF : root_bound + fmax(1e-7 * fmax(1.0, fabs(root_bound)), s_gtol(S, root_bound));
-            status = MLD_STATUS_NODE_LIMIT;
-            nodes = nodes_pre;
-            if (unbounded_pre) unbounded = true;
-            for (;;) {
-                int depth = 0;
-                double t_next = S_INF;
-                bool finished = false, dive_end = false;
-                const double best_at_start = best;
-                pass++;
-                MLD_MARK(w, sh, 100 + 10 * phase + (pass < 10 ? pass : 9));
-                if (phase == PH_FINAL && have && !warm && !ext_cut && !rescue && !w.P && S.cut_rounds > 0 && sh.m < S.mcap && best < restart_best &&
-                    best - lbg <= S_RESTART_GAPS * s_gtol(S, best) && nodes >= MAXN / 8 && !(S.debug & 65536)) {
-                    // Root restart (round 4; oracle: same rule; opts.reserved bit 16 switches it off for an A/B).  The final search is about to start from the root with
-                    // an incumbent that is CLOSE to the proven bound but not within the gap -- under the flat mid-day tariff that is the whole unproven tail (reported
-                    // gaps: median 1.7 %).  More cut rounds at the root, now under the incumbent's cutoff and in the cut rows the root cut loop left free, move the
-                    // bound the last percent for most of them (256 flat-tariff bench instances on the CPU restatement: 3 -> 1 unproven, -3 % row updates; instances
-                    // that never get here are untouched).  The cut loop itself may not be longer: ten rounds are what pays on the whole shard (DESIGN section 9).
-                    // Not for an instance with a MIP start: its cut loop already ran against the start's value (it ends when the bound is within the gap of it), and
-                    // in the closed loop the restart cost 8 % of the steady-state step for one more proven instance in 10 000.
-                    restart_best = best;
-                    const double rcut = best - s_gtol(S, best) + 1e-12;
-                    __syncthreads();
-                    if (tid == 0) sh.cut_cap = S.mcap;
-                    __syncthreads();
-                    MLD_MARK(w, sh, 90);
-                    int lpr = s_dual_simplex(w, sh, rcut, S.max_pivots), stalled = 0;
-                    for (int rnd = 0; rnd < S_RESTART_ROUNDS && rnd < S.cut_rounds && lpr == LP_OPTIMAL && sh.m < S.mcap; ++rnd) {
-                        const double before = s_objective(w, sh);
-                        const long long tc0 = wall_clock64();
-                        const int k = s_cut_round(w, sh, S);
-                        if (tid == 0) sh.prof[2] += wall_clock64() - tc0;
-                        if (!k) break;
-                        cuts += k;
-                        const int cap = sh.pivots + 4 * S.m0 + 200;
-                        lpr = s_dual_simplex(w, sh, rcut, cap < S.max_pivots ? cap : S.max_pivots);
-                        if (lpr != LP_OPTIMAL) break;
-                        if (s_objective(w, sh) - before < 1e-6 * fmax(1.0, fabs(before))) { if (++stalled >= 3) break; } else stalled = 0;
-                    }
-                    if (lpr == LP_CUTOFF) {      // the root is closed by its bound under the incumbent's cutoff: nothing better than the incumbent by more than the gap exists
-                        lbg = fmax(lbg, best - s_gtol(S, best));
-                        status = MLD_STATUS_OPTIMAL;
-                        break;
-                    }
-                    if (lpr == LP_OPTIMAL) {
-                        __syncthreads();
-                        for (int i = S.m0 + tid; i < sh.m; i += SOL_NT) if (w.basic[i] == n + i && w.xB[i] > S_PURGE_SLACK) w.skip[i] = 2;
-                        __syncthreads();
-                        const double ob = s_objective(w, sh);
-                        if (ob > lbg) lbg = ob;
-                    }
-                }
-                if (phase == PH_RINS) {   // fix the binaries on which incumbent and root relaxation agree
-                    __syncthreads();
-                    if (tid == 0) {
-                        int nf = 0;
-                        for (int k = 0; k < nb; ++k) {
-                            const int j = w.bins[k];
-                            if (w.root_lo[j] != w.root_hi[j] && fabs(w.xroot[k] - v_out[j]) <= S_INTTOL) {
-                                w.fx_j[nf] = j; w.fx_lo[nf] = w.root_lo[j]; w.fx_hi[nf] = w.root_hi[j]; w.key[nf] = v_out[j]; nf++;
-                                w.root_lo[j] = w.root_hi[j] = v_out[j];
-                            }
-                        }
-                        sh.s_i[0] = nf;
-                    }
-                    __syncthreads();
-                    nfix = sh.s_i[0];
-                    MLD_CHECK(w, nfix >= 0 && nfix <= nb, 133, nfix, nb);
-                    s_set_bounds_list(w, sh, w.fx_j, w.key, w.key, nfix);
-                }
-                for (;;) {
-                    nodes++;
-                    int branch_j = -1; double branch_x = 0.0;
-                    int force_first = -1; bool second_done = false, pen_pruned = false;   // penalty branching: preferred side, other side closed
-                    bool qp_open = false;      // (quadratic cost: the node's QP relaxation hit the limit -- the node is unsolved, still open)
-                    // RINS is a heuristic on a sub-problem: it keeps ANY improvement (round 4; oracle: same rule).  With the proof's cutoff -- "better by more than the
-                    // gap" -- it threw away exactly the points that matter at the cfg5 size: the dive's leaf is 0.5-1 % above the best point, the root bound within 1 % of THAT one
-                    const double inc_cut = (have || ext_cut) ? ((phase == PH_RINS && have) ? best - 1e-6 * fmax(1.0, fabs(best)) : best - s_gtol(S, best)) : S_INF;
-                    const double cut = fmin(T, inc_cut);
-                    double node_obj = S_INF;
-                    if (S.debug & 1) s_debug_dual(w, sh, inst, "node entry");
-                    lp = s_dual_simplex(w, sh, cut + 1e-12, S.max_pivots);
-                    if (S.debug & 1) s_debug_dual(w, sh, inst, "node exit");
-                    if ((S.debug & 1) && tid == 0) MLD_PRINTF("[inst %d] node %d ph %d depth %d lp=%d obj=%.12g cut=%.12g T=%.12g pivots=%d\n", inst, nodes, phase, depth, lp, s_objective_nosync(w), cut, T, sh.pivots);
-                    if (lp == LP_ITERLIMIT) limit = true;
-                    else if (lp == LP_OPTIMAL || lp == LP_CUTOFF) {
-                        double obj = s_objective(w, sh);      // LP(q) value: a valid bound also when P is PSD
-                        bool pruned = (lp == LP_CUTOFF || obj > cut), qp_lp = false;
-                        node_obj = obj;
-                        if (!pruned && w.P) {
-                            double lbq, fvq;
-                            const int rc = s_sd_relax(w, sh, cut, S.max_pivots, &lbq, &fvq);
-                            if (rc == -1) { limit = true; pruned = true; obj = S_INF; qp_open = true; }
-                            else if (rc == -2) qp_lp = true;      // the QP relaxation could not be finished: this node goes on with its LP(q) bound and LP point
-                            else { obj = lbq; pruned = (rc == 1 || obj > cut); }
-                        }
-                        if (pruned) { if (obj <= inc_cut && obj < t_next) t_next = obj; }
-                        else {
-                            if (w.P && !qp_lp) { __syncthreads(); for (int j = tid; j < n; j += SOL_NT) w.tmpx[j] = w.vcur[j]; __syncthreads(); }
-                            else s_gather_x(w, sh, w.tmpx);
-                            if (!xroot_set) { for (int k = tid; k < nb; k += SOL_NT) w.xroot[k] = w.tmpx[w.bins[k]]; xroot_set = true; }
-                            if (depth == 0 && (have || ext_cut) && (phase == PH_IDS || phase == PH_FINAL) && !w.P) {
-                                // reduced-cost fixing at the true root (no temporary fixings active): a non-basic binary whose
-                                // reduced cost exceeds the room below the cutoff cannot leave its bound in any solution that
-                                // still matters; the fixing is permanent (ordered compaction -> deterministic list)
-                                const double room = inc_cut - obj;
-                                const double *dd = w.dcost;
-                                int nfx = 0;
-                                __syncthreads();
-                                for (int c0 = 0; c0 < n; c0 += SOL_NT) {
-                                    const int c = c0 + tid;
-                                    bool fx = false; int j = -1; double v = 0.0;
-                                    if (c < n) {
-                                        j = w.nonbasic[c];
-                                        if (j < n && w.is_int[j] && w.lo[j] != w.hi[j]) {
-                                            const double rc = w.at_upper[c] ? -dd[c] : dd[c];
-                                            if (rc > room + 1e-9) { fx = true; v = w.xN[c]; }
-                                        }
-                                    }
-                                    int rank;
-                                    const int tot = block_rank(sh, fx, &rank);
-                                    if (fx) { w.sv_j[nfx + rank] = j; w.key[nfx + rank] = v; w.root_lo[j] = v; w.root_hi[j] = v; }
-                                    nfx += tot;
-                                }
-                                __syncthreads();
-                                MLD_CHECK(w, nfx <= nb, 132, nfx, nb);
-                                if (nfx > 0) s_set_bounds_list(w, sh, w.sv_j, w.key, w.key, nfx);
-                            }
-                            if (phase == PH_DIVE) {   // fractional binary closest to 1 (smallest index on ties)
-                                double mv = -S_INF; int mi = -1;
-                                for (int k = tid; k < nb; k += SOL_NT) {
-                                    const int j = w.bins[k];
-                                    const double x = w.tmpx[j];
-                                    // a FIXED binary is never a candidate (round 4): a basic variable with lo == hi can drift off its value by more than the integrality
-                                    // tolerance while the primal simplex of a QP relaxation (or of s_unperturb) ignores its tiny column entries -- picked again and again
-                                    // it made a dive of 700 levels on a 200-binary instance (oracle under ASan: the search stack overflowed; here: garbage in the
-                                    // arrays behind stk_j, an instance ending "infeasible" with 801 nodes)
-                                    if (fabs(x - rint(x)) > S_INTTOL && x > mv && w.lo[j] != w.hi[j]) { mv = x; mi = j; }
-                                }
-                                double tmp;
-                                branch_j = block_argmax(sh, mv, mi, &tmp);
-                            } else if (!w.P && !(S.debug & 64)) {
-                                s_penalty_branch(w, sh, w.tmpx, obj, cut, inc_cut);
-                                branch_j = sh.s_i[0]; force_first = sh.s_i[1]; second_done = sh.s_i[2] != 0; pen_pruned = sh.s_i[3] != 0;
-                                const double tn = sh.s_d[1];
-                                if (tn < t_next) t_next = tn;
-                                __syncthreads();
-                            } else {
-                                // first fractional binary in index order
-                                int key = 0x7fffffff;
-                                for (int k = tid; k < nb; k += SOL_NT) {
-                                    const int j = w.bins[k];
-                                    if (fabs(w.tmpx[j] - rint(w.tmpx[j])) > S_INTTOL && j < key && w.lo[j] != w.hi[j]) key = j;
-                                }
-                                branch_j = block_argmin_int(sh, key, key);
-                            }
-                            MLD_CHECK(w, branch_j < n, 131, branch_j, phase);
-                            if (branch_j >= 0) branch_x = w.tmpx[branch_j];
-                            else if (!pen_pruned) {
-                                // leaf: fix every binary at its rounded value, re-solve, verify, restore
-                                MLD_MARK(w, sh, 400 + phase);
-                                bool leaf_ok = s_leaf_eval(w, sh, S, plb, pub, v_out, best, have, unbounded, inst, nodes);
-                                if (!leaf_ok) {
-                                    // The rounded point is not feasible although every binary is within the integrality
-                                    // tolerance (a binary at 1e-6 can carry a whole unit of a big-M row): the node is NOT a
-                                    // leaf -- branch on the least integral free binary (smallest index on ties).
-                                    double mv = 1e-12; int mi = -1;
-                                    for (int k = tid; k < nb; k += SOL_NT) {
-                                        const int j = w.bins[k];
-                                        const double f = fabs(w.tmpx[j] - rint(w.tmpx[j]));
-                                        if (w.lo[j] != w.hi[j] && f > mv) { mv = f; mi = j; }
-                                    }
-                                    double tmp;
-                                    branch_j = block_argmax(sh, mi >= 0 ? mv : -S_INF, mi, &tmp);
-                                    if (branch_j >= 0) branch_x = w.tmpx[branch_j];
-                                }
-                            }
-                        }
-                    }
-                    if (have && (rescue || unbounded || best <= lbg + s_gtol(S, best))) finished = true;
-                    if (nodes >= ((phase == PH_IDS && !have && !rescue) ? ids_cap : node_budget)) {
-                        limit = true;
-                        if (B.ho && B.ho_donate > 0 && donations < B.ho_rounds && !finished && !rescue && lp != LP_ITERLIMIT && !qp_open && (phase == PH_FINAL || (phase == PH_IDS && T == S_INF))) {
-                            // Node limit inside a complete search with the in-kernel hand-off on: give the LARGEST open subtrees away -- the shallowest
-                            // open siblings of the stack become items for idle workgroups -- and go on below them with a new budget.  What stays here are
-                            // the deep open nodes, which this dictionary closes in a few pivots each; an item pays a root LP and a cut loop of its own.
-                            const int given = s_publish_nodes(w, sh, P, B, nb, inst, isrc, is_item, fixed, depth, false, B.ho_donate, (have || ext_cut) ? best + r_const : S_INF, nullptr, false);
-                            if (given > 0) expanded = true;
-                            donations++;
-                            node_budget = nodes + B.ho_sub_nodes;
-                            limit = false;
-                        }
-                    }
-                    if (S.time_ticks > 0 && !rescue) {      // TimeLimit (the reference forwards it per call, micro_grid_control_simulation.py:232): ends the search like the node limit
-                        __syncthreads();
-                        if (tid == 0) sh.s_i[4] = (wall_clock64() - t_begin > S.time_ticks) ? 1 : 0;
-                        __syncthreads();
-                        if (sh.s_i[4]) { limit = true; timed_out = true; }
-                    }
-                    if (phase == PH_DIVE && !limit && !finished) {
-                        // no backtracking: the dive ends at its first leaf, or when the node is infeasible
-                        if (branch_j < 0) dive_end = true;
-                        else {
-                            s_set_bounds(w, sh, branch_j, 1.0, 1.0);      // (look-ahead LPs are not nodes of the tree: NodeLimit counts the nodes a search evaluates, as the
-                                                                          //  reference's backend does -- round 4; rounds 1-3 counted every LP)
-                            const int la = s_dual_simplex(w, sh, S_INF, S.max_pivots);
-                            const double oa = la == LP_OPTIMAL ? s_objective(w, sh) : S_INF;
-                            double take = 1.0;
-                            if (la == LP_ITERLIMIT) limit = true;
-                            else if (!(oa <= node_obj + dive_tol)) {
-                                s_set_bounds(w, sh, branch_j, 0.0, 0.0);
-                                const int lb2 = s_dual_simplex(w, sh, S_INF, S.max_pivots);
-                                const double ob2 = lb2 == LP_OPTIMAL ? s_objective(w, sh) : S_INF;
-                                if (lb2 == LP_ITERLIMIT) limit = true;
-                                else if (ob2 <= oa) { take = 0.0; if (ob2 == S_INF) dive_end = true; }
-                                else s_set_bounds(w, sh, branch_j, 1.0, 1.0);
-                            }
-                            __syncthreads();
-                            MLD_CHECK(w, depth >= 0 && depth < nb, 130, depth, 1);
-                            if (depth >= nb) limit = true;      // (cannot happen: every level holds a different free binary; the stack has nb + 2 entries)
-                            else { if (tid == 0) { w.stk_j[depth] = branch_j; w.stk_first[depth] = (unsigned char)take; w.stk_second[depth] = 1; } depth++; }
-                            if (!limit && !dive_end) continue;   // evaluate the chosen child
-                        }
-                    }
-                    if (branch_j >= 0 && depth >= nb) limit = true;      // (cannot happen, see the dive: the search ends rather than write behind its stack)
-                    if (branch_j >= 0 && !limit && !finished && !dive_end) {
-                        double first = force_first >= 0 ? (double)force_first : (branch_x >= 0.5 ? 1.0 : 0.0);
-                        if (have && phase == PH_FINAL && !second_done) first = rint(v_out[branch_j] / w.cs[branch_j]);   // guided (Danna et al. 2005): towards the incumbent first
-                        __syncthreads();
-                        MLD_CHECK(w, depth >= 0 && depth < nb && (first == 0.0 || first == 1.0), 130, depth, (int)(first * 1000));
-                        if (tid == 0) { w.stk_j[depth] = branch_j; w.stk_first[depth] = (unsigned char)first; w.stk_second[depth] = second_done ? 1 : 0; }
-                        depth++;
-                        s_set_bounds(w, sh, branch_j, first, first);
-                        continue;
-                    }
-                    if (limit || finished || dive_end) {   // unwind the whole stack in one pass (stack entries are distinct variables)
-                        __syncthreads();
-                        if (B.open_depth) {
-                            // sub-tree hand-off (mld_download_open_nodes): when a COMPLETE search (plain depth-first search below the incumbent: FINAL, or
-                            // the deepening passes once T is infinite) stops at a limit, the stack describes everything that is still open -- for every
-                            // level whose sibling has not been visited the node (path above it, variable flipped), plus the current path itself
-                            const bool complete = limit && !finished && !rescue && (phase == PH_FINAL || (phase == PH_IDS && T == S_INF));
-                            if (complete) {
-                                for (int k = tid; k < depth; k += SOL_NT) {
-                                    const int j = w.stk_j[k];
-                                    B.open_var[(size_t)inst * nb + k] = (short)j;
-                                    B.open_val[(size_t)inst * nb + k] = (unsigned char)(w.lo[j] > 0.5 ? 1 : 0);
-                                    B.open_flag[(size_t)inst * nb + k] = w.stk_second[k];
-                                }
-                            }
-                            if (tid == 0) B.open_depth[inst] = complete ? depth : -1;
-                            __syncthreads();
-                        }
-                        if (B.ho && limit && !finished && !rescue && (phase == PH_FINAL || (phase == PH_IDS && T == S_INF))) {
-                            // In-kernel hand-off: this COMPLETE search stopped at its node limit.  Everything it leaves open -- for every level whose sibling has not
-                            // been visited the node {path above it, that level flipped}, plus the current path itself -- is published as entries of the work
-                            // queue; whichever workgroup runs out of instances solves them (root LP and cut loop of their own, this search's incumbent as cutoff).
-                            stopped_complete = true;
-                            // CLOSING SWEEP before anything is published: most open siblings of a stopped search are trivial -- the warm dictionary closes
-                            // them in a few pivots each, an item would pay a root LP and cut rounds for the same verdict (83 % of the items of a shard at the
-                            // 1e-6 contract ended "nothing better in this node").  The stack is popped level by level; a level whose sibling has not been
-                            // visited gets that sibling's LP under the incumbent's cutoff: closed -> accounted for, still open -> it becomes an item.
-                            for (int k = tid; k < depth; k += SOL_NT) w.stk_val[k] = (unsigned char)(w.lo[w.stk_j[k]] > 0.5 ? 1 : 0);
-                            __syncthreads();
-                            const bool cur_open = branch_j >= 0 || lp == LP_ITERLIMIT || qp_open;      // (a node whose LP -- or QP relaxation -- hit the pivot limit is unsolved: still open)
-                            const double sweep_cut = (have || ext_cut) ? best - s_gtol(S, best) : S_INF;
-                            const int depth_pub = depth;
-                            if (!(S.debug & 524288))
-                            for (int k = depth - 1; k >= 0; --k) {
-                                const int j = w.stk_j[k];
-                                if (!w.stk_second[k]) {
-                                    const double v = 1.0 - (double)w.stk_val[k];
-                                    s_set_bounds(w, sh, j, v, v);
-                                    const int l2 = s_dual_simplex(w, sh, sweep_cut + 1e-12, S.max_pivots);
-                                    nodes++;
-                                    bool closed = l2 == LP_CUTOFF || l2 == LP_INFEASIBLE;
-                                    if (l2 == LP_OPTIMAL) closed = s_objective(w, sh) > sweep_cut;
-                                    if (l2 == LP_OPTIMAL && !closed && w.P && sweep_cut < S_INF) closed = s_sweep_close_qp(w, sh, sweep_cut, S.max_pivots);
-                                    __syncthreads();
-                                    if (closed && tid == 0) w.stk_second[k] = 1;
-                                    __syncthreads();
-                                }
-                                s_set_bounds(w, sh, j, w.root_lo[j], w.root_hi[j]);
-                                depth = k;
-                            }
-                            const int pub = s_publish_nodes(w, sh, P, B, nb, inst, isrc, is_item, fixed, depth_pub, true, 0, (have || ext_cut) ? best + r_const : S_INF, w.stk_val, cur_open);
-                            if (pub >= 0) expanded = published_rest = true;      // (0: the sweep closed everything that was open -- the search is complete)
-                        }
-                        for (int k = tid; k < depth; k += SOL_NT) { const int j = w.stk_j[k]; w.sv_lo[k] = w.root_lo[j]; w.sv_hi[k] = w.root_hi[j]; }
-                        __syncthreads();
-                        s_set_bounds_list(w, sh, w.stk_j, w.sv_lo, w.sv_hi, depth);
-                        depth = 0;
-                        break;
-                    }
-                    __syncthreads();
-                    while (depth > 0 && w.stk_second[depth - 1]) { depth--; const int j = w.stk_j[depth]; s_set_bounds(w, sh, j, w.root_lo[j], w.root_hi[j]); }
-                    if (depth == 0) break;
-                    __syncthreads();
-                    if (tid == 0) w.stk_second[depth - 1] = 1;
-                    { const int j = w.stk_j[depth - 1]; const double v = 1.0 - (double)w.stk_first[depth - 1]; s_set_bounds(w, sh, j, v, v); }
-                }
-                if (phase == PH_RINS) {   // release the fixings
-                    __syncthreads();
-                    if (tid == 0) for (int k = 0; k < nfix; ++k) { const int j = w.fx_j[k]; w.root_lo[j] = w.fx_lo[k]; w.root_hi[j] = w.fx_hi[k]; }
-                    __syncthreads();
-                    s_set_bounds_list(w, sh, w.fx_j, w.fx_lo, w.fx_hi, nfix);
-                    rins_rounds++;
-                }
-                if (finished) { if (unbounded) { status = MLD_STATUS_UNBOUNDED; best = -S_INF; } else if (!rescue) status = MLD_STATUS_OPTIMAL; break; }
-                if (lp == LP_ITERLIMIT && !timed_out) break;      // (an LP the TimeLimit interrupted is not a pivot limit: the rescue dive below still owes a feasible point)
-                if (phase == PH_IDS && limit && !have && !rescue && !timed_out && nodes < MAXN && warm && !started) {
-                    // MIP start (mld_set_warm_start / mld_warm_start_from_previous; the reference forwards warm_start=True to its backend,
-                    // controller_base.py:493,509-512), evaluated lazily (oracle: same rule): only an instance whose deepening passes found no
-                    // incumbent pays for it (one leaf); a feasible start takes the place of the dive and the search goes on with RINS around it
-                    started = true;
-                    __syncthreads();
-                    for (int k = tid; k < nb; k += SOL_NT) w.tmpx[w.bins[k]] = (double)warm[k];
-                    __syncthreads();
-                    MLD_MARK(w, sh, 450);
-                    (void)s_leaf_eval(w, sh, S, plb, pub, v_out, best, have, unbounded, inst, nodes);
-                    if (have) { phase = PH_RINS; limit = false; T = S_INF; node_budget = min(MAXN, nodes + MAXN / 4); continue; }
-                }
-                if (timed_out) {      // out of time: no further phase; without an incumbent one un-thresholded dive still returns a feasible point
-                    if (!have && !rescue && !ext_cut) { rescue = true; if (tid == 0) sh.deadline = 0;      /* (the rescue dive is what guarantees a feasible point: no clock inside its LPs) */  limit = false; timed_out = false; T = S_INF; phase = PH_FINAL; node_budget = nodes + 3 * nb + 10; continue; }
-                    break;
-                }
-                if (phase == PH_IDS && limit && !have && !rescue && nodes < MAXN) {
-                    // the dive may finish even when it outlasts the node budget (it is what guarantees a feasible point)
-                    phase = PH_DIVE; limit = false; T = S_INF; node_budget = max(MAXN, nodes + 3 * nb + 10); continue;
-                }
-                if (phase == PH_DIVE) {
-                    limit = nodes >= MAXN;
-                    if (have && !limit) { phase = PH_RINS; node_budget = min(MAXN, nodes + MAXN / 4); continue; }
-                    if (!have && !limit) { phase = PH_FINAL; node_budget = MAXN; continue; }
-                } else if (phase == PH_RINS) {
-                    limit = nodes >= MAXN;
-                    if (!limit) {
-                        if (best < best_at_start && rins_rounds < 2) { node_budget = min(MAXN, nodes + MAXN / 4); continue; }
-                        phase = PH_FINAL; node_budget = MAXN; continue;
-                    }
-                }
-                if (limit) {
-                    // node limit without an incumbent: one un-thresholded dive so that a feasible point is returned
-                    if (!have && !rescue && !ext_cut) { rescue = true; if (tid == 0) sh.deadline = 0;      /* (the rescue dive is what guarantees a feasible point: no clock inside its LPs) */  limit = false; T = S_INF; phase = PH_FINAL; node_budget = nodes + 3 * nb + 10; continue; }
-                    break;
-                }
-                if (have && best - s_gtol(S, best) <= T) { status = MLD_STATUS_OPTIMAL; break; }
-                if (t_next == S_INF) {
-                    if (!have && !rescue && !ext_cut) {   // every node "infeasible": re-derive the dictionary from the original rows and dive once more
-                        s_refactor(w, sh);
-                        rescue = true; if (tid == 0) sh.deadline = 0;      /* (the rescue dive is what guarantees a feasible point: no clock inside its LPs) */  T = S_INF; phase = PH_FINAL; node_budget = nodes + 3 * nb + 10;
-                        continue;
-                    }
-                    status = have ? (rescue ? MLD_STATUS_NODE_LIMIT : MLD_STATUS_OPTIMAL) : MLD_STATUS_INFEASIBLE;
-                    break;
-                }
-                if (t_next > lbg) lbg = t_next;
-                if (have) T = S_INF;
-                else T = fmax(t_next + 1e-9 * fmax(1.0, fabs(t_next)), T + ldexp(2.5e-4, 2 * pass) * fmax(1.0, fabs(T)));
-            }
-            // every way of ending OPTIMAL has closed all nodes below best - gtol; otherwise the bound is what exhaustive passes proved
-            lb_proven = status == MLD_STATUS_OPTIMAL ? fmin(best, fmax(lbg, best - s_gtol(S, best))) : lbg;
-            if (B.ho && !expanded && !stopped_complete && status == MLD_STATUS_NODE_LIMIT && have) {
-                // The search stopped at a limit BEFORE it became a plain depth-first search below an incumbent (deepening passes, dive, RINS): no stack
-                // describes what is left, so its one open node is its own root -- published once more, now under the incumbent's value as cutoff (the
-                // item starts as a complete search and can be split).  Without an incumbent there is nothing to gain from running the same search again.
-                const int gen = is_item ? B.item_gen[inst] : 0;
-                __syncthreads();
-                if (tid == 0) {
-                    int base = -1;
-                    const int root_t = is_item ? B.item_root[inst] : inst;
-                    bool room_tree = gen < B.ho_max_gen;
-                    if (room_tree && __hip_atomic_fetch_add(&B.tree_count[(size_t)root_t * 9 + gen], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1 > B.ho_max_tree) {
-                        __hip_atomic_store(&B.tree_dead[root_t], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        room_tree = false;
-                    }
-                    if (room_tree) {
-                        int old = __hip_atomic_load(B.tail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        while (old + 1 <= B.cap) {
-                            if (__hip_atomic_compare_exchange_strong(B.tail, &old, old + 1, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { base = old; break; }
-                        }
-                        if (base < 0) __hip_atomic_store(&B.tree_dead[root_t], 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                    sh.s_i[5] = base;
-                }
-                __syncthreads();
-                const int it = sh.s_i[5];
-                if (it >= 0) {
-                    unsigned char *dst = B.fixed + (size_t)it * nb;
-                    for (int b = tid; b < nb; b += SOL_NT) dst[b] = fixed ? fixed[b] : (unsigned char)255;
-                    if (tid == 0) {
-                        B.item_src[it] = isrc; B.item_root[it] = is_item ? B.item_root[inst] : inst; B.item_gen[it] = gen + 1;
-                        B.item_label[it] = (is_item ? B.item_label[inst] : 1ll) * 129 + B.item_children[inst] + 1;
-                        B.cutoff[it] = best + r_const; B.item_children[it] = 0; B.item_children[inst] = B.item_children[inst] + 1;
-                        if (B.open_depth) B.open_depth[it] = -1;
-                    }
-                    __threadfence();
-                    __syncthreads();
-                    if (tid == 0) __hip_atomic_store(&B.item_ready[it], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-                    expanded = published_rest = true;
-                }
-            }
-            if (expanded) {
-                // (internal statuses, merged by k_merge_*: what this entry left open lives on as its items.  Its own rest is closed when the search ended on its
-                // own, or when everything that was left went into items; the bound it reports is the one that holds for its WHOLE node -- a search that
-                // gave subtrees away has proven nothing about them)
-                if (status == MLD_STATUS_OPTIMAL || status == MLD_STATUS_INFEASIBLE || (status == MLD_STATUS_NODE_LIMIT && published_rest)) status = MLD_STATUS_EXPANDED;
-                else if (status == MLD_STATUS_NODE_LIMIT) status = MLD_STATUS_EXPANDED_OPEN;
-                lb_proven = lbg;
-            }
-        }
-        // ---- write results ------------------------------------------------------------------------
-        MLD_MARK(w, sh, 999);
-        __syncthreads();
-        if (tid == 0) {
-            const double r = r_const;
-            B.obj_out[inst] = have ? best + r : S_INF;
-            B.lb_out[inst] = lb_proven + r;
-            B.status_out[inst] = status;
-            B.nodes_out[inst] = nodes; B.pivots_out[inst] = sh.pivots; B.cuts_out[inst] = cuts; B.refac_out[inst] = sh.refactors;
-            B.ticks_out[inst] = wall_clock64() - t_begin; B.rows_out[inst] = (long long)sh.rows;
-#ifdef MLD_PIVOT_PROF
-            if (B.prof_out) { for (int k = 0; k < 5; ++k) B.prof_out[(size_t)inst * 8 + k] = sh.pprof[k]; B.prof_out[(size_t)inst * 8 + 5] = 0; B.prof_out[(size_t)inst * 8 + 6] = 0; B.prof_out[(size_t)inst * 8 + 7] = sh.prof[7]; }
-#else
-            if (B.prof_out) for (int k = 0; k < 8; ++k) B.prof_out[(size_t)inst * 8 + k] = sh.prof[k];
-#endif
-#ifdef MLD_CUT_PROF
-            if (B.prof_out) { B.prof_out[(size_t)inst * 8 + 3] = sh.cprof[0]; B.prof_out[(size_t)inst * 8 + 4] = sh.cprof[1]; B.prof_out[(size_t)inst * 8 + 7] = sh.cprof[2]; }   // (diagnostic build: slots 3 / 4 / 7 = c-MIR scoring / c-MIR build / Gomory)
-#endif
-        }
-        if (B.ho) {      // this entry is complete (its results and any items it published are visible): the launch ends when finished == tail
-            __threadfence();
-            __syncthreads();
-            if (tid == 0) __hip_atomic_fetch_add(B.finished, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        s_write_results(sh, B, e, s);
     }
 }
