@@ -322,6 +322,7 @@ struct mld_problem {
     void *h_trace = nullptr; int *d_trace = nullptr; size_t trace_bytes = 0;   /* mld_debug_trace: file-backed host buffer the kernel writes its stage markers into */
     int mir_cap = 0;            /* integer entries of the widest scaled original row over all models, rounded up to 8 (k_solve's compact c-MIR lines) */
     SolverShape S{};
+    unsigned slot_mask = 0;     /* MLD_SOL_SLOT at creation: the hot arrays build_shape kept in the slot (bit k: SLOT_NAMES[k]) */
     // per-model device arrays
     DevBuf<double> d_Gp;        /* d_Gs with columns in dictionary (position-major) order: coalesced dictionary reset */
     DevBuf<double> d_actmax;    /* n_models x m0: largest row activity under the model's bounds (s_mark_dead) */
@@ -371,8 +372,39 @@ static long long time_limit_ticks(double seconds)
     return t >= 9.0e18 ? (long long)9.0e18 : (long long)std::max(1.0, t);
 }
 
-static void build_shape(mld_problem *p)
+/* MLD_SOL_SLOT (diagnostics and tests): a comma list of the hot arrays that stay in the slot even where they would fit in LDS, or "all"; the rest of the
+ * placement ladder runs as before.  Read when the problem is created (build_shape); an unknown name is an error, so that a typo cannot test the default. */
+static const char *const SLOT_NAMES[] = {"xb", "basic", "skip", "atup", "nonbasic", "xn", "lohi", "dw", "cost", "mirline", "mircache"};
+enum { SLOT_N = (int)(sizeof(SLOT_NAMES) / sizeof(SLOT_NAMES[0])) };
+
+static int sol_slot_mask(unsigned *mask)
 {
+    *mask = 0;
+    const char *env = getenv("MLD_SOL_SLOT");
+    if (!env) return MLD_OK;
+    const std::string all(env);
+    size_t b = 0;
+    while (b <= all.size()) {
+        size_t e = all.find(',', b);
+        if (e == std::string::npos) e = all.size();
+        const std::string name = all.substr(b, e - b);
+        int k = 0;
+        if (name == "all") *mask |= (1u << SLOT_N) - 1u;
+        else if (!name.empty()) {
+            while (k < SLOT_N && name != SLOT_NAMES[k]) ++k;
+            if (k == SLOT_N) { mld_set_error("MLD_SOL_SLOT: unknown array '%s' (xb, basic, skip, atup, nonbasic, xn, lohi, dw, cost, mirline, mircache, all)", name.c_str()); return MLD_ERR_INVALID; }
+            *mask |= 1u << k;
+        }
+        b = e + 1;
+    }
+    return MLD_OK;
+}
+
+static int build_shape(mld_problem *p)
+{
+    unsigned slot = 0;
+    if (int rc = sol_slot_mask(&slot)) return rc;
+    p->slot_mask = slot;
     SolverShape &S = p->S;
     const mld_opts &o = p->opts;
     /* cut rows: max_cuts for the root cut loop + S_RESTART_ROWS (0) that only the root restart may use (k_solve: more cut rounds at the root once an incumbent leaves a
@@ -423,16 +455,18 @@ static void build_shape(mld_problem *p)
 #define SOL_LDS_BUDGET ((SOL_WPE >= 4 ? 78 : 144) * 1024)
 #endif
     const size_t budget = SOL_LDS_BUDGET;
-    auto ltake = [&](size_t bytes) -> int { const size_t b = align_up(bytes, 16); if (loff + b > budget) return -1; const size_t r = loff; loff += b; return (int)r; };
-    S.lXB = ltake(sizeof(double) * mc); S.lBasic = ltake(sizeof(int) * mc); S.lSkip = ltake(mc);
-    S.lAtUp = ltake(n); S.lNonbasic = ltake(sizeof(int) * n); S.lXN = ltake(sizeof(double) * n);
-    S.lLo = ltake(sizeof(double) * nt); S.lHi = S.lLo >= 0 ? ltake(sizeof(double) * nt) : -1;
-    S.lDw = ltake(sizeof(double) * mc);
-    S.lCost = ltake(sizeof(double) * (n + 1));                        /* the reduced-cost row: read by every ratio test, updated by every pivot */
+    /* k: the array's bit in the MLD_SOL_SLOT mask (SLOT_NAMES) */
+    auto ltake = [&](size_t bytes, int k) -> int { const size_t b = align_up(bytes, 16); if ((slot >> k & 1u) || loff + b > budget) return -1; const size_t r = loff; loff += b; return (int)r; };
+    S.lXB = ltake(sizeof(double) * mc, 0); S.lBasic = ltake(sizeof(int) * mc, 1); S.lSkip = ltake(mc, 2);
+    S.lAtUp = ltake(n, 3); S.lNonbasic = ltake(sizeof(int) * n, 4); S.lXN = ltake(sizeof(double) * n, 5);
+    S.lLo = ltake(sizeof(double) * nt, 6); S.lHi = S.lLo >= 0 ? ltake(sizeof(double) * nt, 6) : -1;
+    S.lDw = ltake(sizeof(double) * mc, 7);
+    S.lCost = ltake(sizeof(double) * (n + 1), 8);                     /* the reduced-cost row: read by every ratio test, updated by every pivot */
     S.mir_cap = p->mir_cap; S.lMirLine = -1;
-    if (p->mir_cap > 0 && p->mir_cap < n) S.lMirLine = ltake(sizeof(double) * SOL_NW * 2 * p->mir_cap);     /* compact lines of the c-MIR scoring (a row's free binaries) */
-    S.lMirCache = ltake(sizeof(double) * SOL_NW * 2 * n);                                                  /* full-width lines (Gomory rounds): LDS while it fits */
+    if (p->mir_cap > 0 && p->mir_cap < n) S.lMirLine = ltake(sizeof(double) * SOL_NW * 2 * p->mir_cap, 9);  /* compact lines of the c-MIR scoring (a row's free binaries) */
+    S.lMirCache = ltake(sizeof(double) * SOL_NW * 2 * n, 10);                                              /* full-width lines (Gomory rounds): LDS while it fits */
     p->lds_bytes = loff;
+    return MLD_OK;
 }
 
 /* a host array to a buffer of its own size (an empty array leaves the buffer empty) */
@@ -795,7 +829,7 @@ int mld_problem_create(mld_problem_t **out, mld_model_t *model, int N_p, int N_t
     // 4. cost (K4)
     if ((rc = set_cost_impl(p.get(), cost))) return rc;
     // 5. workspace: one dictionary per resident workgroup
-    build_shape(p.get());
+    if ((rc = build_shape(p.get()))) return rc;
     {
         int dev = 0; hipDeviceProp_t prop;
         (void)hipGetDevice(&dev); (void)hipGetDeviceProperties(&prop, dev);
@@ -1423,6 +1457,20 @@ int mld_debug_profile(mld_problem_t *p, int64_t out[8])
     HIP_TRY(hipMemcpy(t.data(), p->bat.prof, sizeof(long long) * t.size(), hipMemcpyDeviceToHost));
     for (int k = 0; k < 8; ++k) out[k] = 0;
     for (size_t i = 0; i < (size_t)p->batch; ++i) for (int k = 0; k < 8; ++k) out[k] += t[i * 8 + k];
+    return MLD_OK;
+}
+
+/* the solver's shape (internal diagnostics; not part of the public header): [0..7] n, m0, mcap, first_cap, ld, mir_cap, lds_bytes, ws_stride;
+ * [8..19] the LDS byte offsets (-1: in the slot) lXB, lBasic, lSkip, lAtUp, lNonbasic, lXN, lLo, lHi, lDw, lCost, lMirLine, lMirCache;
+ * [20] the LDS budget of the hot arrays, [21] the MLD_SOL_SLOT mask (bit k: SLOT_NAMES[k]), [22] n_slots, [23] 0 */
+int mld_debug_shape(mld_problem_t *p, int64_t out[24])
+{
+    if (!p || !out) { mld_set_error("mld_debug_shape: bad arguments"); return MLD_ERR_INVALID; }
+    const SolverShape &S = p->S;
+    const int64_t v[24] = {S.n, S.m0, S.mcap, S.first_cap, S.ld, S.mir_cap, (int64_t)p->lds_bytes, (int64_t)S.ws_stride,
+                           S.lXB, S.lBasic, S.lSkip, S.lAtUp, S.lNonbasic, S.lXN, S.lLo, S.lHi, S.lDw, S.lCost, S.lMirLine, S.lMirCache,
+                           (int64_t)SOL_LDS_BUDGET, (int64_t)p->slot_mask, p->n_slots, 0};
+    for (int k = 0; k < 24; ++k) out[k] = v[k];
     return MLD_OK;
 }
 

@@ -337,6 +337,22 @@ class GpuProblem(object):
         lib.mld_debug_trace.argtypes = [C.c_void_p, C.c_char_p]
         check(lib.mld_debug_trace(self._h, None if path is None else str(path).encode()))
 
+    _SHAPE_KEYS = ("n", "m0", "mcap", "first_cap", "ld", "mir_cap", "lds_bytes", "ws_stride",
+                   "lXB", "lBasic", "lSkip", "lAtUp", "lNonbasic", "lXN", "lLo", "lHi", "lDw", "lCost", "lMirLine", "lMirCache",
+                   "lds_budget", "slot_mask", "n_slots")
+
+    def debug_shape(self):
+        """diagnostics: the solver's shape as build_shape placed it (internal entry mld_debug_shape) -- dims, LDS bytes, and the LDS byte offset of
+        every hot array (-1: it stays in the slot, e.g. under MLD_SOL_SLOT).  all_lds is true when k_solve runs its typed all-LDS pivot loop."""
+        lib = _lib.load()
+        lib.mld_debug_shape.restype = C.c_int
+        lib.mld_debug_shape.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        out = (C.c_int64 * 24)()
+        check(lib.mld_debug_shape(self._h, out))
+        d = {k: int(out[i]) for i, k in enumerate(self._SHAPE_KEYS)}
+        d["all_lds"] = all(d[k] >= 0 for k in ("lXB", "lXN", "lLo", "lHi", "lBasic", "lNonbasic", "lAtUp", "lSkip", "lDw", "lCost"))
+        return d
+
     def telemetry(self):
         """per-instance in-kernel latency (ns) and dictionary rows updated; row_bytes = bytes per row"""
         b = self.batch

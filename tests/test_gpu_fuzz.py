@@ -8,29 +8,10 @@ from scipy.optimize import Bounds, LinearConstraint, milp
 import condense_np as cn
 import orc
 import tighten_np
+from _paths import fuzz_mld as random_mld
 from pyhybridcontrol_amd import gpu, host
 
 pytestmark = pytest.mark.gpu
-
-
-def random_mld(seed):
-    rng = np.random.Generator(np.random.PCG64(1000 + seed))
-    nx, nu, nd, nz = int(rng.integers(1, 4)), int(rng.integers(1, 4)), int(rng.integers(0, 3)), int(rng.integers(0, 3))
-    nw, ny, nc = int(rng.integers(0, 3)), int(rng.integers(1, 3)), int(rng.integers(3, 7))
-    nmu = nc
-    A = 0.8 * rng.standard_normal((nx, nx)) / max(1, nx) ** 0.5
-    m = dict(A=A, B1=rng.standard_normal((nx, nu)), B2=rng.standard_normal((nx, nd)), B3=0.5 * rng.standard_normal((nx, nz)),
-             B4=rng.standard_normal((nx, nw)), b5=0.1 * rng.standard_normal((nx, 1)),
-             C=rng.standard_normal((ny, nx)), D1=rng.standard_normal((ny, nu)), D2=np.zeros((ny, nd)), D3=np.zeros((ny, nz)),
-             D4=np.zeros((ny, nw)), d5=np.zeros((ny, 1)),
-             E=rng.standard_normal((nc, nx)), F1=3.0 * rng.standard_normal((nc, nu)), F2=5.0 * rng.standard_normal((nc, nd)),
-             F3=rng.standard_normal((nc, nz)), F4=0.3 * rng.standard_normal((nc, nw)), f5=1.0 + rng.random((nc, 1)),
-             G=0.5 * rng.standard_normal((nc, ny)), Psi=-np.eye(nc))
-    dims = dict(nx=nx, nu=nu, ndelta=nd, nz=nz, nmu=nmu, nomega=nw, ny=ny, nc=nc, nu_l=nu, nmu_l=0)
-    atoms = {"q_mu": 5.0 + 10.0 * rng.random(nmu), "q_u": rng.standard_normal(nu)}
-    if nd:
-        atoms["q_delta"] = rng.standard_normal(nd)
-    return m, dims, atoms, rng
 
 
 @pytest.mark.parametrize("seed", range(12))
