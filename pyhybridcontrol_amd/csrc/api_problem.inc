@@ -1246,22 +1246,43 @@ static int handoff_reset(mld_problem *p)
     return MLD_OK;
 }
 
-/* merge the items into their roots after k_solve (deterministic: best objective, smallest tree label on ties) */
-static int handoff_merge(mld_problem *p)
+/* what the merge works on: the per-entry result arrays (cap entries: batch roots, then the items), the items' roots and tree labels, the
+ * give-up marks and the accumulators per root, and the two device counters it reports through.  The solve path fills it from the resident batch
+ * (merge_args), mld_debug_merge from arrays of the caller's. */
+struct MergeArgs {
+    int batch, cap, n; double gap_abs, gap_rel;
+    double *obj, *lbnd, *v; int *status, *nodes, *pivots, *cuts, *refac; long long *rows;
+    const int *tail, *item_root; const long long *item_label; const int *tree_dead;
+    unsigned long long *mg_best, *mg_lbopen, *mg_label; int *mg_open;
+    int *n_unfinished, *n_dead;      /* n_dead: + 1 per tree given up for its size, + 65536 per tree given up because the queue was full */
+};
+
+static MergeArgs merge_args(const mld_problem *p)
 {
-    const hipStream_t sq = p->stream;
-    const int batch = p->batch;
     const BatchBufs &b = p->bat;
     const BatchBufs::Handoff &q = b.ho;
-    const int items = p->batch_cap - batch;
+    MergeArgs a;
+    a.batch = p->batch; a.cap = p->batch_cap; a.n = p->n; a.gap_abs = p->opts.gap_abs; a.gap_rel = p->opts.gap_rel;
+    a.obj = b.obj; a.lbnd = b.lbnd; a.v = b.v; a.status = b.status; a.nodes = b.nodes; a.pivots = b.pivots; a.cuts = b.cuts; a.refac = b.refac; a.rows = b.rows;
+    a.tail = q.tail; a.item_root = q.item_root; a.item_label = q.item_label; a.tree_dead = q.tree_dead;
+    a.mg_best = q.mg_best; a.mg_lbopen = q.mg_lbopen; a.mg_label = q.mg_label; a.mg_open = q.mg_open;
+    a.n_unfinished = b.skipped; a.n_dead = q.finished;      /* (finished: the queue is drained, the counter is free) */
+    return a;
+}
+
+/* merge the items into their roots after k_solve (deterministic: best objective, smallest tree label on ties) */
+static int handoff_merge(const MergeArgs &a, hipStream_t sq)
+{
+    const int batch = a.batch;
+    const int items = a.cap - batch;
     const dim3 gi((items + 255) / 256), gb((batch + 255) / 256), blk(256);
-    HIP_TRY(hipMemsetAsync(b.skipped, 0, sizeof(int), sq));
-    hipLaunchKernelGGL(k_merge_init, gb, blk, 0, sq, batch, b.obj, q.mg_best, q.mg_lbopen, q.mg_label, q.mg_open);
-    hipLaunchKernelGGL(k_merge_a, gi, blk, 0, sq, batch, q.tail, q.item_root, b.obj, b.lbnd, b.status, b.nodes, b.pivots, b.cuts, b.refac, b.rows,
-                       q.mg_best, q.mg_lbopen, q.mg_open, q.tree_dead);
-    hipLaunchKernelGGL(k_merge_b, gi, blk, 0, sq, batch, q.tail, q.item_root, b.obj, q.item_label, q.mg_best, q.mg_label, q.tree_dead);
-    hipLaunchKernelGGL(k_merge_c, dim3(items), blk, 0, sq, batch, q.tail, p->n, q.item_root, b.obj, q.item_label, q.mg_best, q.mg_label, b.v, q.tree_dead);
-    hipLaunchKernelGGL(k_merge_d, gb, blk, 0, sq, batch, p->opts.gap_abs, p->opts.gap_rel, b.obj, b.lbnd, b.status, q.mg_best, q.mg_lbopen, q.mg_open, b.skipped, q.tree_dead, q.finished);      /* (finished: the queue is drained, the counter is free) */
+    HIP_TRY(hipMemsetAsync(a.n_unfinished, 0, sizeof(int), sq));
+    hipLaunchKernelGGL(k_merge_init, gb, blk, 0, sq, batch, a.obj, a.mg_best, a.mg_lbopen, a.mg_label, a.mg_open);
+    hipLaunchKernelGGL(k_merge_a, gi, blk, 0, sq, batch, a.tail, a.item_root, a.obj, a.lbnd, a.status, a.nodes, a.pivots, a.cuts, a.refac, a.rows,
+                       a.mg_best, a.mg_lbopen, a.mg_open, a.tree_dead);
+    hipLaunchKernelGGL(k_merge_b, gi, blk, 0, sq, batch, a.tail, a.item_root, a.obj, a.item_label, a.mg_best, a.mg_label, a.tree_dead);
+    hipLaunchKernelGGL(k_merge_c, dim3(items), blk, 0, sq, batch, a.tail, a.n, a.item_root, a.obj, a.item_label, a.mg_best, a.mg_label, a.v, a.tree_dead);
+    hipLaunchKernelGGL(k_merge_d, gb, blk, 0, sq, batch, a.gap_abs, a.gap_rel, a.obj, a.lbnd, a.status, a.mg_best, a.mg_lbopen, a.mg_open, a.n_unfinished, a.tree_dead, a.n_dead);
     return MLD_OK;
 }
 
@@ -1315,7 +1336,7 @@ static int launch(mld_problem *p)
         if (p->lds_bytes > 48 * 1024)   /* per-function limit: set for THIS problem (several problems of different size may be alive) */
             HIP_TRY(hipFuncSetAttribute((const void *)k_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_bytes));
         hipLaunchKernelGGL(k_solve, dim3(grid), dim3(SOL_NT), p->lds_bytes, sq, p->S, P, B, p->d_ws.get());
-        if (ho && (rc = handoff_merge(p))) return rc;
+        if (ho && (rc = handoff_merge(merge_args(p), sq))) return rc;
         p->ho_ran = ho;
         HIP_TRY(hipEventRecord(p->ev[2], sq));
     }
@@ -1471,6 +1492,71 @@ int mld_debug_shape(mld_problem_t *p, int64_t out[24])
                            S.lXB, S.lBasic, S.lSkip, S.lAtUp, S.lNonbasic, S.lXN, S.lLo, S.lHi, S.lDw, S.lCost, S.lMirLine, S.lMirCache,
                            (int64_t)SOL_LDS_BUDGET, (int64_t)p->slot_mask, p->n_slots, 0};
     for (int k = 0; k < 24; ++k) out[k] = v[k];
+    return MLD_OK;
+}
+
+/* the MIP start of the resident batch as the next solve would read it (internal diagnostics; not part of the public header): out = batch x n_bin bytes
+ * (untouched when there is no start or no binary), *has_warm = 1 when a start is set */
+int mld_debug_warm_start(mld_problem_t *p, uint8_t *out, int *has_warm)
+{
+    MLD_NOT_IN_FLIGHT(p, "mld_debug_warm_start");
+    if (!p || p->batch < 1 || !has_warm) { mld_set_error("mld_debug_warm_start: bad arguments / nothing uploaded"); return MLD_ERR_INVALID; }
+    *has_warm = p->has_warm ? 1 : 0;
+    if (out && p->has_warm && p->nb) HIP_TRY(hipMemcpy(out, p->bat.warm, (size_t)p->batch * p->nb, hipMemcpyDeviceToHost));
+    return MLD_OK;
+}
+
+/* The hand-off merge on a queue of the caller's (internal diagnostics and tests; not part of the public header): per-entry arrays of `cap` entries -- `batch`
+ * roots, then items up to `tail` -- are uploaded, handoff_merge runs on them exactly as after k_solve, and the roots' results come back in place
+ * (obj, lbnd, status, nodes, pivots, cuts, refac, rows: entries < batch; v: rows < batch of cap x n).  item_root / item_label: cap entries, read in
+ * [batch, tail); tree_dead: batch entries (0, 1 = given up for its size, 2 = for a full queue).  n_unfinished, finished: the two device counters, finished
+ * starting at tail as a drained queue leaves it.  Everything a kernel indexes with is validated here. */
+struct mld_debug_merge_io {
+    int32_t batch, cap, n, tail; double gap_abs, gap_rel;
+    double *obj, *lbnd, *v; int32_t *status, *nodes, *pivots, *cuts, *refac; int64_t *rows;
+    const int32_t *item_root; const int64_t *item_label; const int32_t *tree_dead;
+    int32_t n_unfinished, finished;
+};
+int mld_debug_merge(mld_debug_merge_io *io)
+{
+    if (!io || !io->obj || !io->lbnd || !io->v || !io->status || !io->nodes || !io->pivots || !io->cuts || !io->refac || !io->rows || !io->item_root ||
+        !io->item_label || !io->tree_dead) { mld_set_error("mld_debug_merge: null argument"); return MLD_ERR_INVALID; }
+    const int batch = io->batch, cap = io->cap, n = io->n, tail = io->tail;
+    if (batch < 1 || cap <= batch || tail < batch || tail > cap || n < 1 || (size_t)cap * (size_t)n > ((size_t)1 << 28)) {
+        mld_set_error("mld_debug_merge: need 1 <= batch <= tail <= cap, cap > batch, n >= 1 (batch %d, tail %d, cap %d, n %d)", batch, tail, cap, n); return MLD_ERR_INVALID;
+    }
+    if (!(io->gap_abs >= 0.0) || !(io->gap_rel >= 0.0)) { mld_set_error("mld_debug_merge: gaps must be >= 0"); return MLD_ERR_INVALID; }
+    for (int it = batch; it < tail; ++it) if (io->item_root[it] < 0 || io->item_root[it] >= batch) { mld_set_error("mld_debug_merge: item_root[%d] = %d is no root", it, io->item_root[it]); return MLD_ERR_INVALID; }
+    for (int r = 0; r < batch; ++r) if (io->tree_dead[r] < 0 || io->tree_dead[r] > 2) { mld_set_error("mld_debug_merge: tree_dead[%d] = %d", r, io->tree_dead[r]); return MLD_ERR_INVALID; }
+    const size_t c = cap, b = batch;
+    DevBuf<double> obj, lbnd, v; DevBuf<int> status, nodes, pivots, cuts, refac, item_root, tree_dead, tl, unf, fin, mg_open;
+    DevBuf<long long> rows, item_label; DevBuf<unsigned long long> mg_best, mg_lbopen, mg_label;
+    HIP_TRY(obj.alloc(c)); HIP_TRY(lbnd.alloc(c)); HIP_TRY(v.alloc(c * n)); HIP_TRY(status.alloc(c)); HIP_TRY(nodes.alloc(c)); HIP_TRY(pivots.alloc(c));
+    HIP_TRY(cuts.alloc(c)); HIP_TRY(refac.alloc(c)); HIP_TRY(rows.alloc(c)); HIP_TRY(item_root.alloc(c)); HIP_TRY(item_label.alloc(c)); HIP_TRY(tree_dead.alloc(b));
+    HIP_TRY(tl.alloc(1)); HIP_TRY(unf.alloc(1)); HIP_TRY(fin.alloc(1));
+    HIP_TRY(mg_best.alloc(b)); HIP_TRY(mg_lbopen.alloc(b)); HIP_TRY(mg_label.alloc(b)); HIP_TRY(mg_open.alloc(b));
+    HIP_TRY(hipMemcpy(obj, io->obj, sizeof(double) * c, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(lbnd, io->lbnd, sizeof(double) * c, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(v, io->v, sizeof(double) * c * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(status, io->status, sizeof(int) * c, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(nodes, io->nodes, sizeof(int) * c, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(pivots, io->pivots, sizeof(int) * c, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(cuts, io->cuts, sizeof(int) * c, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(refac, io->refac, sizeof(int) * c, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(rows, io->rows, sizeof(long long) * c, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(item_root, io->item_root, sizeof(int) * c, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(item_label, io->item_label, sizeof(long long) * c, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(tree_dead, io->tree_dead, sizeof(int) * b, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(tl, &tail, sizeof(int), hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(fin, &tail, sizeof(int), hipMemcpyHostToDevice));
+    MergeArgs a;
+    a.batch = batch; a.cap = cap; a.n = n; a.gap_abs = io->gap_abs; a.gap_rel = io->gap_rel;
+    a.obj = obj; a.lbnd = lbnd; a.v = v; a.status = status; a.nodes = nodes; a.pivots = pivots; a.cuts = cuts; a.refac = refac; a.rows = rows;
+    a.tail = tl; a.item_root = item_root; a.item_label = item_label; a.tree_dead = tree_dead;
+    a.mg_best = mg_best; a.mg_lbopen = mg_lbopen; a.mg_label = mg_label; a.mg_open = mg_open; a.n_unfinished = unf; a.n_dead = fin;
+    if (int rc = handoff_merge(a, 0)) return rc;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(io->obj, obj, sizeof(double) * b, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(io->lbnd, lbnd, sizeof(double) * b, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(io->v, v, sizeof(double) * b * n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(io->status, status, sizeof(int) * b, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(io->nodes, nodes, sizeof(int) * b, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(io->pivots, pivots, sizeof(int) * b, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(io->cuts, cuts, sizeof(int) * b, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(io->refac, refac, sizeof(int) * b, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(io->rows, rows, sizeof(long long) * b, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&io->n_unfinished, unf, sizeof(int), hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(&io->finished, fin, sizeof(int), hipMemcpyDeviceToHost));
     return MLD_OK;
 }
 

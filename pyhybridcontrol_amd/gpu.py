@@ -128,6 +128,45 @@ def expand_open_nodes(fix, depth, var, val, flag, pos):
     return res
 
 
+class _MergeIO(C.Structure):
+    _fields_ = ([(k, C.c_int32) for k in ("batch", "cap", "n", "tail")] + [("gap_abs", C.c_double), ("gap_rel", C.c_double)] +
+                [(k, C.POINTER(C.c_double)) for k in ("obj", "lbnd", "v")] +
+                [(k, C.POINTER(C.c_int32)) for k in ("status", "nodes", "pivots", "cuts", "refac")] + [("rows", C.POINTER(C.c_int64))] +
+                [("item_root", C.POINTER(C.c_int32)), ("item_label", C.POINTER(C.c_int64)), ("tree_dead", C.POINTER(C.c_int32))] +
+                [("n_unfinished", C.c_int32), ("finished", C.c_int32)])
+
+
+def debug_merge(batch, tail, obj, lbnd, status, nodes, pivots, cuts, refac, rows, v, item_root, item_label, tree_dead, gap_abs=1e-9, gap_rel=0.0):
+    """diagnostics: the in-kernel hand-off's merge (k_merge_*, the function the solve path runs) on a queue of the caller's (internal entry
+    mld_debug_merge).  Per-entry arrays of cap = len(obj) entries: `batch` roots, then the items up to `tail`; v (cap, n); item_root / item_label per
+    entry (read in [batch, tail)); tree_dead per root.  Returns the roots' merged obj, lower_bound, status, nodes, pivots, cuts, refac, rows, v plus
+    n_unfinished and given_up = (trees given up for their size, trees given up for a full queue).  The inputs are not modified."""
+    f64 = lambda a: np.array(a, dtype=np.float64, order="C")
+    i32 = lambda a: np.array(a, dtype=np.int32, order="C")
+    i64 = lambda a: np.array(a, dtype=np.int64, order="C")
+    a = dict(obj=f64(obj), lbnd=f64(lbnd), v=f64(v), status=i32(status), nodes=i32(nodes), pivots=i32(pivots), cuts=i32(cuts), refac=i32(refac),
+             rows=i64(rows), item_root=i32(item_root), item_label=i64(item_label), tree_dead=i32(tree_dead))
+    cap = a["obj"].shape[0]
+    a["v"] = a["v"].reshape(cap, -1)
+    for k in ("lbnd", "status", "nodes", "pivots", "cuts", "refac", "rows", "item_root", "item_label"):
+        if a[k].shape != (cap,):
+            raise ValueError("debug_merge: %s needs %d entries" % (k, cap))
+    if a["tree_dead"].shape != (max(0, int(batch)),):
+        raise ValueError("debug_merge: tree_dead needs one entry per root")
+    io = _MergeIO(batch=int(batch), cap=cap, n=a["v"].shape[1], tail=int(tail), gap_abs=float(gap_abs), gap_rel=float(gap_rel))
+    for k, _ in _MergeIO._fields_:
+        if k in a:
+            setattr(io, k, a[k].ctypes.data_as(dict(_MergeIO._fields_)[k]))
+    lib = _lib.load()
+    lib.mld_debug_merge.restype = C.c_int
+    lib.mld_debug_merge.argtypes = [C.POINTER(_MergeIO)]
+    check(lib.mld_debug_merge(C.byref(io)))
+    b = int(batch)
+    extra = int(io.finished) - int(tail)
+    return dict(obj=a["obj"][:b], lower_bound=a["lbnd"][:b], status=a["status"][:b], nodes=a["nodes"][:b], pivots=a["pivots"][:b], cuts=a["cuts"][:b],
+                refac=a["refac"][:b], rows=a["rows"][:b], v=a["v"][:b], n_unfinished=int(io.n_unfinished), given_up=(extra % 65536, extra // 65536))
+
+
 def make_opts(**kw):
     o = _lib.Opts()
     check(_lib.load().mld_opts_default(C.byref(o)))
@@ -352,6 +391,16 @@ class GpuProblem(object):
         d = {k: int(out[i]) for i, k in enumerate(self._SHAPE_KEYS)}
         d["all_lds"] = all(d[k] >= 0 for k in ("lXB", "lXN", "lLo", "lHi", "lBasic", "lNonbasic", "lAtUp", "lSkip", "lDw", "lCost"))
         return d
+
+    def debug_warm_start(self):
+        """diagnostics: the MIP start the next solve would read (internal entry mld_debug_warm_start) -- (batch, n_bin) uint8, a row starting with 255 = no
+        start for that instance; None when no start is set"""
+        lib = _lib.load()
+        lib.mld_debug_warm_start.restype = C.c_int
+        lib.mld_debug_warm_start.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_int)]
+        out, has = np.zeros((self.batch, self.n_bin), np.uint8), C.c_int(0)
+        check(lib.mld_debug_warm_start(self._h, out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(has)))
+        return out if has.value else None
 
     def telemetry(self):
         """per-instance in-kernel latency (ns) and dictionary rows updated; row_bytes = bytes per row"""
