@@ -330,6 +330,26 @@ int mld_stage_inputs(mld_problem_t *, int n_sets, const double *x0_sets, const d
 int mld_select_inputs(mld_problem_t *, int set);
 int mld_download_inputs(mld_problem_t *, double *x0, double *omega);
 
+/* Per-instance LINEAR cost of the resident batch (price scenarios).  The reference solves one instance per solve() call and rebuilds its
+ * objective from the current tariff before every call (micro_grid_control_simulation.py:194-198,229), so every call may carry other prices;
+ * here every instance of a batch may.  The cost is ADDED to the problem's cost (mld_cost of mld_problem_create / mld_problem_set_cost):
+ *   lin_v (batch, N_tilde*nv)   lin_x (batch, N_tilde*nx)   lin_y (batch, N_tilde*ny)      any may be NULL = zeros
+ * instance b minimises  cost_model(v) + lin_v[b]'v + lin_x[b]'x_tilde + lin_y[b]'y_tilde  -- the common part (e.g. the comfort penalty q_mu)
+ * stays with the model, the scenario part (the tariff q_z) comes per instance; for replacement set the model's linear cost to zero.  Weights on
+ * x_tilde / y_tilde are pulled back through the condensed maps (controllers/components/variables.py:259-275) by one batched GEMM per model on
+ * the matrix cores (fp32 with MLD_F32, vector ALUs with MLD_DBG_GEMM_VALU); with lin_v alone nothing is computed.  It composes with a quadratic
+ * model cost.  Valid until the next mld_upload_batch; all three NULL clears.  Survives mld_select_inputs and mld_advance_batch: the weights
+ * stay, the constant term follows the current x0 / omega (it is evaluated at every launch).  The items of the in-kernel hand-off use their
+ * source instance's cost; relaxation-only batches keep the LDS-resident LP (k_lp_lds reads the per-instance cost under its own column scales,
+ * its overflow re-solve on the dense kernel sees the same cost); time-varying handles work like time-invariant ones (model_idx indexes
+ * horizons).  Memory: batch x (n + nx + N_tilde*nomega + 1) doubles, batch x n with lin_v alone.  Runs on the problem's stream.
+ * MLD_ERR_INVALID, nothing changed: no batch resident; a launched solve not finished; lin_x with nx == 0; lin_y with ny == 0. */
+int mld_upload_instance_cost(mld_problem_t *, const double *lin_v, const double *lin_x, const double *lin_y);
+/* Read-back, the per-instance analogue of mld_cost_assemble: q_out (batch, n) = the UNSCALED per-instance addition to the linear term, pulled
+ * back to v (lin_v + Gamma_v' lin_x + L_v' lin_y); const_out (batch) = its constant term at the current x0 / omega.  Either may be NULL;
+ * zeros when no per-instance cost is resident. */
+int mld_download_instance_cost(mld_problem_t *, double *q_out, double *const_out);
+
 /* Per-instance telemetry of the last solve: time spent inside the solve kernel (device wall clock, ns) and
  * the number of dictionary rows the rank-1 updates touched (x *row_bytes x 2 = bytes streamed by pivots). */
 int mld_download_telemetry(mld_problem_t *, int64_t *latency_ns, int64_t *rows_updated, int64_t *row_bytes);

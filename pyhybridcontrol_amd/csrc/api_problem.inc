@@ -3,6 +3,7 @@
 #include <rccl/rccl.h>
 
 #include "mfma.inc"
+#include "inst_cost.inc"
 #include "lp_lds.inc"
 
 #include <limits>
@@ -179,9 +180,11 @@ __global__ void k_symmetrize(int n, const double *W, double *out, size_t stride)
 }
 
 
-// qs_inst[b][j] = cs[j] * (q0[j] + Qx[j,:] x0_b + Qw[j,:] w_b)   (quadratic atoms on x / y make q depend on the parameters)
+// qs_inst[b][j] = cs[j] * (q0[j] + Qx[j,:] x0_b + Qw[j,:] w_b)   (quadratic atoms on x / y make q depend on the parameters);
+// qadd (batch x ldq, or null): the per-instance linear cost of mld_upload_instance_cost, added to q0
 __global__ void __launch_bounds__(256) k_qinst(int n, int nx, int nW, const double *q0, const double *Qx, const double *Qw, const double *cs,
-                                              const int *model_idx, const double *x0, const double *omega, double *qs_inst)
+                                              const int *model_idx, const double *x0, const double *omega, double *qs_inst,
+                                              const double *qadd, int ldq)
 {
     const int b = blockIdx.x, mdl = model_idx ? model_idx[b] : 0;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwv = blockDim.x >> 6;
@@ -191,7 +194,10 @@ __global__ void __launch_bounds__(256) k_qinst(int n, int nx, int nW, const doub
         if (Qx) { const double *r = Qx + ((size_t)mdl * n + j) * nx; for (int k = lane; k < nx; k += 64) acc += r[k] * xb[k]; }
         if (Qw) { const double *r = Qw + ((size_t)mdl * n + j) * nW; for (int k = lane; k < nW; k += 64) acc += r[k] * wb[k]; }
         for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-        if (lane == 0) qs_inst[(size_t)b * n + j] = (q0[(size_t)mdl * n + j] + acc) * cs[(size_t)mdl * n + j];
+        if (lane == 0) {
+            const double base = qadd ? q0[(size_t)mdl * n + j] + qadd[(size_t)b * ldq + j] : q0[(size_t)mdl * n + j];
+            qs_inst[(size_t)b * n + j] = (base + acc) * cs[(size_t)mdl * n + j];
+        }
     }
 }
 
@@ -303,6 +309,8 @@ struct BatchBufs {
     DevBuf<double> stage_x0, stage_om;                   /* resident input sets (mld_stage_inputs) */
     DevBuf<int> perm; DevBuf<RhsGroup> groups;           /* instances grouped by model for the MFMA right-hand sides (K3) */
     DevBuf<double> xcols, xcols_x; DevBuf<int> xrows;    /* extra constraint blocks; the state every extra column was generated with (explicit x_k) */
+    DevBuf<double> icost, qs_inst_t;                     /* per-instance linear cost (mld_upload_instance_cost): batch x ic_ld, unscaled, pulled back to v
+                                                            [then cx | cw | c0]; qs_inst under the Toeplitz-compatible column scales (k_lp_lds, on first use) */
     struct Handoff {      /* in-kernel sub-tree hand-off queue: allocated only while mld_set_handoff has it on */
         DevBuf<int> tail, finished, item_src, item_root, item_gen, item_ready, item_children; DevBuf<long long> item_label;
         DevBuf<unsigned long long> mg_best, mg_lbopen, mg_label; DevBuf<int> mg_open;   /* merge accumulators per root */
@@ -346,6 +354,7 @@ struct mld_problem {
     bool advanced = false;      /* mld_advance_batch has applied that solve's plan: the next advance needs the next solve */
     bool has_cutoff = false, want_open = false;    /* objective cutoffs (mld_set_cutoffs); record the open-node stacks (mld_record_open_nodes) */
     int n_staged = 0, staged_batch = 0, n_groups = 0, n_xcols = 0, order_batch = 0; size_t xcols_cap = 0; bool has_xcols_x = false;
+    int ic_ld = 0;              /* row length of bat.icost: 0 = no per-instance cost resident, n = weights on v only, n + nx + nW + 1 = with the constant's maps */
     DevBuf<double> d_gather; size_t gather_cap = 0;   /* send + receive buffers of mld_gather_results */
     /* LDS-resident LP path (k_lp_lds): Toeplitz-compatible scaling of the tightened model */
     bool lp_ok = false, all_fixed = false; LpShape LS{}; size_t lp_lds_bytes = 0; int lp_slots = 0;
@@ -486,7 +495,7 @@ static void free_batch(mld_problem *p)
     p->bat = BatchBufs();
     p->n_groups = 0; p->has_warm = false; p->solved = false; p->advanced = false; p->has_cutoff = false;
     p->n_staged = 0; p->staged_batch = 0; p->n_xcols = 0; p->xcols_cap = 0; p->has_xcols_x = false;
-    p->order_batch = 0; p->in_cap = 0; p->batch_cap = 0;
+    p->order_batch = 0; p->in_cap = 0; p->batch_cap = 0; p->ic_ld = 0;
 }
 
 // out[k] = a[k] * b[k]
@@ -969,6 +978,7 @@ int mld_upload_batch(mld_problem_t *p, int batch, const int32_t *model_idx, cons
     p->all_fixed = false;
     if (fixed_bin && p->nb) { bool all = true; const size_t tot = (size_t)batch * p->nb; for (size_t k = 0; k < tot && all; ++k) all = fixed_bin[k] != 255; p->all_fixed = all; }
     p->n_xcols = 0;   /* extra constraint blocks belong to one upload */
+    if (p->ic_ld) { p->bat.icost.reset(); p->bat.qs_inst_t.reset(); p->ic_ld = 0; }   /* so does a per-instance cost */
     if (p->order_batch != batch) p->order_batch = 0;
     {
         std::vector<int> perm; std::vector<RhsGroup> groups;
@@ -1129,6 +1139,24 @@ __global__ void __launch_bounds__(256) k_batch_stats(int batch, const int *statu
     if (threadIdx.x < 8) out[threadIdx.x] = acc[threadIdx.x];
 }
 
+/* the per-instance linear cost of the resident batch as the solve kernels read it, at the CURRENT inputs (staged / advanced ones included):
+ * qs_inst = cs (q0 + q_b) -- under a quadratic cost k_qinst has written it with the Qx x0 + Qw omega term already -- and rconst (+)= the
+ * constant cx_b' x0 + cw_b' omega + c0_b.  lds: also the copy under the Toeplitz-compatible column scales (k_lp_lds). */
+static int launch_inst_cost(mld_problem *p, bool lds)
+{
+    const hipStream_t sq = p->stream;
+    const int batch = p->batch, n = p->n;
+    const size_t tot = (size_t)batch * n;
+    if (!p->has_quad) {
+        if (tot) hipLaunchKernelGGL(k_inst_cost, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, sq, tot, n, p->ic_ld, p->d_q0, p->d_cs, lds ? p->d_cs_t.get() : nullptr,
+                                    p->has_midx ? p->bat.model_idx.get() : nullptr, p->bat.icost, p->bat.qs_inst, lds ? p->bat.qs_inst_t.get() : nullptr);
+        HIP_TRY(hipMemsetAsync(p->bat.rconst, 0, sizeof(double) * batch, sq));
+    }
+    if (p->ic_ld > n)
+        hipLaunchKernelGGL(k_inst_const, dim3((batch + 3) / 4), dim3(256), 0, sq, batch, n, p->nx, p->nW, p->ic_ld, p->bat.icost, p->bat.x0, p->bat.omega, p->bat.rconst);
+    return MLD_OK;
+}
+
 /* LDS-resident LP path -- relaxation-only mode: every binary fixed -> one LP per instance, solved in LDS (k_lp_lds); right-hand sides with the
  * Toeplitz row scales.  Runs to completion: redo lists the instances whose working basis outgrew LDS (status -1), for the dense kernel. */
 static int launch_lds_lp(mld_problem *p, std::vector<int> &redo)
@@ -1141,12 +1169,17 @@ static int launch_lds_lp(mld_problem *p, std::vector<int> &redo)
     if (p->n_xcols > 0)
         hipLaunchKernelGGL(k_rhs_extra, dim3(batch), dim3(256), 0, sq, p->m0, p->nx, p->nW, t->d_out[O_HX], t->d_out[O_HW], t->d_out[O_H5],
                            p->d_rs_t, p->has_midx ? p->bat.model_idx.get() : nullptr, p->bat.x0, p->bat.xcols, p->n_xcols, p->bat.xrows, p->bat.hs, p->has_xcols_x ? p->bat.xcols_x.get() : nullptr);
+    if (p->ic_ld) {      /* per-instance cost under the Toeplitz-compatible column scales, and its constant at the current inputs */
+        if (!p->bat.qs_inst_t) HIP_TRY(p->bat.qs_inst_t.alloc((size_t)batch * std::max(1, p->n)));
+        if (int rc = launch_inst_cost(p, true)) return rc;
+    }
     HIP_TRY(hipEventRecord(p->ev[1], sq));
     LpModelDev LM; LM.blk = p->d_blk_t; LM.qs = p->d_qs_t; LM.lb = p->d_lb_t; LM.ub = p->d_ub_t; LM.cs = p->d_cs_t;
     LM.cx = p->nx ? p->d_cx.get() : nullptr; LM.cw = p->nW ? p->d_cw.get() : nullptr; LM.c0 = p->d_c0; LM.bins = p->d_bins; LM.nb = p->nb; LM.is_int = p->d_is_int;
     LpBatchDev LB; LB.batch = batch; LB.model_idx = p->has_midx ? p->bat.model_idx.get() : nullptr; LB.x0 = p->bat.x0; LB.omega = p->bat.omega; LB.hs = p->bat.hs;
     LB.fixed = p->bat.fixed; LB.v_out = p->bat.v; LB.obj_out = p->bat.obj; LB.lb_out = p->bat.lbnd; LB.status_out = p->bat.status; LB.nodes_out = p->bat.nodes;
     LB.pivots_out = p->bat.pivots; LB.ticks_out = p->bat.ticks; LB.prof_out = p->bat.prof; LB.counter = p->d_counter; LB.cuts_out = p->bat.cuts;
+    LB.qs_inst = p->ic_ld ? p->bat.qs_inst_t.get() : nullptr; LB.rconst = p->ic_ld ? p->bat.rconst.get() : nullptr;
     p->LS.max_pivots = p->opts.max_pivots;
     HIP_TRY(hipMemsetAsync(p->bat.cuts, 0, sizeof(int) * batch, sq));
     HIP_TRY(hipFuncSetAttribute((const void *)k_lp_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lp_lds_bytes));
@@ -1163,7 +1196,7 @@ static int launch_lds_lp(mld_problem *p, std::vector<int> &redo)
     return MLD_OK;
 }
 
-/* right-hand sides of the dense path (K3) with the extra constraint blocks, and the per-instance part of a quadratic cost */
+/* right-hand sides of the dense path (K3) with the extra constraint blocks, and the per-instance part of the cost (quadratic atoms, mld_upload_instance_cost) */
 static int launch_rhs_cost(mld_problem *p)
 {
     const hipStream_t sq = p->stream;
@@ -1183,13 +1216,15 @@ static int launch_rhs_cost(mld_problem *p)
                            p->d_rs, midx, p->bat.x0, p->bat.xcols, p->n_xcols, p->bat.xrows, p->bat.hs, p->has_xcols_x ? p->bat.xcols_x.get() : nullptr);
     if (p->has_quad) {
         const int NX = p->N * p->model->dims.nx, NY = p->N * p->model->dims.ny;
-        hipLaunchKernelGGL(k_qinst, dim3(batch), dim3(256), 0, sq, p->n, p->nx, p->nW, p->d_q0, p->d_Qx, p->d_Qw, p->d_cs, midx, p->bat.x0, p->bat.omega, p->bat.qs_inst);
+        hipLaunchKernelGGL(k_qinst, dim3(batch), dim3(256), 0, sq, p->n, p->nx, p->nW, p->d_q0, p->d_Qx, p->d_Qw, p->d_cs, midx, p->bat.x0, p->bat.omega, p->bat.qs_inst,
+                           p->ic_ld ? p->bat.icost.get() : nullptr, p->ic_ld);
         HIP_TRY(hipMemsetAsync(p->bat.rconst, 0, sizeof(double) * batch, sq));
         if (p->d_Wx && NX) hipLaunchKernelGGL(k_quad_const, dim3(batch), dim3(256), sizeof(double) * NX, sq, NX, p->nx, p->nW, t->d_out[O_PhiX], t->lay.out_size[O_PhiX],
                                               t->d_out[O_GamW], t->lay.out_size[O_GamW], t->d_out[O_Gam5], t->lay.out_size[O_Gam5], p->d_Wx, midx, p->bat.x0, p->bat.omega, p->bat.rconst);
         if (p->d_Wy && NY) hipLaunchKernelGGL(k_quad_const, dim3(batch), dim3(256), sizeof(double) * NY, sq, NY, p->nx, p->nW, t->d_out[O_LX], t->lay.out_size[O_LX],
                                               t->d_out[O_LW], t->lay.out_size[O_LW], t->d_out[O_L5], t->lay.out_size[O_L5], p->d_Wy, midx, p->bat.x0, p->bat.omega, p->bat.rconst);
     }
+    if (p->ic_ld) return launch_inst_cost(p, false);
     return MLD_OK;
 }
 
@@ -1217,7 +1252,8 @@ static BatchDev batch_dev(const mld_problem *p, bool ho)
     B.warm = p->has_warm ? b.warm.get() : nullptr;
     B.cutoff = p->has_cutoff || ho ? b.cutoff.get() : nullptr;
     B.open_depth = p->want_open ? b.open_depth.get() : nullptr; B.open_var = b.open_var; B.open_val = b.open_val; B.open_flag = b.open_flag;
-    B.qs_inst = p->has_quad ? b.qs_inst.get() : nullptr; B.rconst = p->has_quad ? b.rconst.get() : nullptr; B.v_out = b.v; B.obj_out = b.obj; B.lb_out = b.lbnd;
+    const bool inst_q = p->has_quad || p->ic_ld;      /* k_solve takes the QP relaxation on S.qp && P.Ps, never on qs_inst being there */
+    B.qs_inst = inst_q ? b.qs_inst.get() : nullptr; B.rconst = inst_q ? b.rconst.get() : nullptr; B.v_out = b.v; B.obj_out = b.obj; B.lb_out = b.lbnd;
     B.status_out = b.status; B.nodes_out = b.nodes; B.pivots_out = b.pivots; B.cuts_out = b.cuts; B.refac_out = b.refac;
     B.ticks_out = b.ticks; B.rows_out = b.rows; B.prof_out = b.prof; B.trace = p->d_trace;
     B.counter = p->d_counter;
@@ -1755,6 +1791,87 @@ int mld_download_inputs(mld_problem_t *p, double *x0, double *omega)
     if (!p || p->batch < 1) { mld_set_error("mld_download_inputs: nothing uploaded"); return MLD_ERR_INVALID; }
     if (x0 && p->nx) HIP_TRY(hipMemcpy(x0, p->bat.x0, sizeof(double) * (size_t)p->batch * p->nx, hipMemcpyDeviceToHost));
     if (omega && p->nW) HIP_TRY(hipMemcpy(omega, p->bat.omega, sizeof(double) * (size_t)p->batch * p->nW, hipMemcpyDeviceToHost));
+    return MLD_OK;
+}
+
+/* Per-instance linear cost of the resident batch (the reference rebuilds its objective with the current tariff before every solve() call,
+ * micro_grid_control_simulation.py:194-198,229: N calls replaced by one batch may carry N price vectors).  Weights on v are kept as uploaded; weights on
+ * x_tilde / y_tilde are pulled back through the tightened model's condensed maps by ONE GEMM per model (k_inst_pullback; k_inst_pullback_valu under
+ * MLD_DBG_GEMM_VALU) into [q_b | cx_b | cw_b | c0_b].  The new cost is built in a buffer of its own: a call that fails leaves the resident one as it was. */
+int mld_upload_instance_cost(mld_problem_t *p, const double *lin_v, const double *lin_x, const double *lin_y)
+{
+    if (mld_device_count() <= 0) { mld_set_error("no HIP device (libmldgpu has no CPU fallback)"); return MLD_ERR_NO_DEVICE; }
+    MLD_NOT_IN_FLIGHT(p, "mld_upload_instance_cost");
+    if (!p || p->batch < 1) { mld_set_error("mld_upload_instance_cost: upload a batch first (the cost belongs to its instances)"); return MLD_ERR_INVALID; }
+    const int n = p->n, nx = p->nx, nW = p->nW, batch = p->batch;
+    const int NX = p->N * p->model->dims.nx, NY = p->N * p->model->dims.ny;
+    if (lin_x && NX == 0) { mld_set_error("mld_upload_instance_cost: lin_x given but the model has no state (nx = 0)"); return MLD_ERR_INVALID; }
+    if (lin_y && NY == 0) { mld_set_error("mld_upload_instance_cost: lin_y given but the model has no output (ny = 0)"); return MLD_ERR_INVALID; }
+    if (!lin_v && !lin_x && !lin_y) { p->bat.icost.reset(); p->bat.qs_inst_t.reset(); p->ic_ld = 0; return MLD_OK; }
+    const hipStream_t sq = p->stream;
+    const bool pull = lin_x || lin_y;
+    const int ld = pull ? n + nx + nW + 1 : n;      /* weights on v only: no GEMM, cx / cw / c0 are zero and not stored */
+    DevBuf<double> ic, d_w;
+    HIP_TRY(ic.alloc((size_t)batch * std::max(1, ld)));
+    /* everything queued on the stream; the wait below comes on EVERY path, so that the caller's arrays and the temporaries may go when this returns */
+    auto queue = [&]() -> int {
+    if (!lin_v || pull) HIP_TRY(hipMemsetAsync(ic, 0, sizeof(double) * (size_t)batch * std::max(1, ld), sq));
+    if (lin_v && n && !pull) HIP_TRY(hipMemcpyAsync(ic, lin_v, sizeof(double) * (size_t)batch * n, hipMemcpyHostToDevice, sq));      /* rows are contiguous: one plain copy */
+    else if (lin_v && n) HIP_TRY(hipMemcpy2DAsync(ic, sizeof(double) * ld, lin_v, sizeof(double) * n, sizeof(double) * n, batch, hipMemcpyHostToDevice, sq));
+    if (pull) {
+        const int K = NX + NY;
+        const mld_model *t = p->tight.get();
+        HIP_TRY(d_w.alloc((size_t)batch * K));
+        if (!lin_x || !lin_y) HIP_TRY(hipMemsetAsync(d_w, 0, sizeof(double) * (size_t)batch * K, sq));
+        if (lin_x) HIP_TRY(hipMemcpy2DAsync(d_w, sizeof(double) * K, lin_x, sizeof(double) * NX, sizeof(double) * NX, batch, hipMemcpyHostToDevice, sq));
+        if (lin_y) HIP_TRY(hipMemcpy2DAsync(d_w.get() + NX, sizeof(double) * K, lin_y, sizeof(double) * NY, sizeof(double) * NY, batch, hipMemcpyHostToDevice, sq));
+        PbMaps mp;
+        const int oW[4] = {O_GamV, O_PhiX, O_GamW, O_Gam5}, oY[4] = {O_LV, O_LX, O_LW, O_L5};
+        for (int f = 0; f < 4; ++f) {
+            mp.W[f] = NX ? t->d_out[oW[f]].get() : nullptr; mp.sW[f] = t->lay.out_size[oW[f]];
+            mp.Y[f] = NY ? t->d_out[oY[f]].get() : nullptr; mp.sY[f] = t->lay.out_size[oY[f]];
+        }
+        if (p->opts.reserved & MLD_DBG_GEMM_VALU)
+            hipLaunchKernelGGL(k_inst_pullback_valu, dim3(batch), dim3(256), sizeof(double) * K, sq, NX, NY, n, nx, nW, mp, p->has_midx ? p->bat.model_idx.get() : nullptr, d_w.get(), ic.get());
+        else if (p->opts.flags & MLD_F32)
+            hipLaunchKernelGGL(k_inst_pullback<true>, dim3(p->n_groups), dim3(64 * RM_WAVES), 0, sq, NX, NY, n, nx, nW, mp, p->bat.groups.get(), p->bat.perm.get(), d_w.get(), ic.get());
+        else
+            hipLaunchKernelGGL(k_inst_pullback<false>, dim3(p->n_groups), dim3(64 * RM_WAVES), 0, sq, NX, NY, n, nx, nW, mp, p->bat.groups.get(), p->bat.perm.get(), d_w.get(), ic.get());
+        HIP_TRY(hipGetLastError());
+    }
+    return MLD_OK;
+    };
+    const int rc = queue();
+    const hipError_t es = hipStreamSynchronize(sq);
+    if (rc) return rc;
+    HIP_TRY(es);
+    p->bat.icost = std::move(ic); p->ic_ld = ld;
+    return MLD_OK;
+}
+
+int mld_download_instance_cost(mld_problem_t *p, double *q_out, double *const_out)
+{
+    MLD_NOT_IN_FLIGHT(p, "mld_download_instance_cost");
+    if (!p || p->batch < 1) { mld_set_error("mld_download_instance_cost: nothing uploaded"); return MLD_ERR_INVALID; }
+    const size_t b = p->batch, n = p->n;
+    if (!p->ic_ld) {
+        if (q_out) memset(q_out, 0, sizeof(double) * b * n);
+        if (const_out) memset(const_out, 0, sizeof(double) * b);
+        return MLD_OK;
+    }
+    if (q_out && n) HIP_TRY(hipMemcpy2D(q_out, sizeof(double) * n, p->bat.icost, sizeof(double) * p->ic_ld, sizeof(double) * n, b, hipMemcpyDeviceToHost));
+    if (const_out) {
+        memset(const_out, 0, sizeof(double) * b);
+        if (p->ic_ld > p->n) {
+            DevBuf<double> d_c;
+            HIP_TRY(d_c.alloc(b));
+            HIP_TRY(hipMemsetAsync(d_c, 0, sizeof(double) * b, p->stream));
+            hipLaunchKernelGGL(k_inst_const, dim3((p->batch + 3) / 4), dim3(256), 0, p->stream, p->batch, p->n, p->nx, p->nW, p->ic_ld, p->bat.icost, p->bat.x0, p->bat.omega, d_c.get());
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(const_out, d_c, sizeof(double) * b, hipMemcpyDeviceToHost, p->stream));
+            HIP_TRY(hipStreamSynchronize(p->stream));
+        }
+    }
     return MLD_OK;
 }
 

@@ -46,6 +46,7 @@ struct LpBatchDev {
     long long *prof_out;                 // batch x 8 phase ticks (may be null): 0 leaving, 1 rho, 2 pivot row, 3 ratio test, 4 entering column, 5 value updates, 6 W^-1 update, 7 set-up / refresh / verify
     int *counter;
     int *cuts_out;                       // cut rows added (always 0 for an LP; may be null)
+    const double *qs_inst, *rconst;      // per-instance linear cost (mld_upload_instance_cost) or null: batch x n scaled like LpModelDev.qs, instead of it; batch, its constant
 };
 
 // every member points into LDS and says so: generic pointers would compile to flat_load / flat_store, whose latency is several times
@@ -288,7 +289,7 @@ __global__ void __launch_bounds__(LP_NT) k_lp_lds(LpShape S, LpModelDev M, LpBat
             for (int e = tid; e < S.N * S.nc * S.nv; e += LP_NT) L.blk[e] = g[e];
             cur_model = mdl;
         }
-        const double *q = M.qs + (size_t)mdl * n, *plb = M.lb + (size_t)mdl * n, *pub = M.ub + (size_t)mdl * n;
+        const double *q = B.qs_inst ? B.qs_inst + (size_t)inst * n : M.qs + (size_t)mdl * n, *plb = M.lb + (size_t)mdl * n, *pub = M.ub + (size_t)mdl * n;
         const double *h = B.hs + (size_t)inst * m;
         const unsigned char *fixed = B.fixed ? B.fixed + (size_t)inst * M.nb : nullptr;
         // ---- slack basis: every structural non-basic at its dual-feasible bound (free variables boxed only where they must rest)
@@ -571,6 +572,7 @@ __global__ void __launch_bounds__(LP_NT) k_lp_lds(LpShape S, LpModelDev M, LpBat
                 if (M.c0) r += M.c0[mdl];
                 if (M.cx) for (int j = 0; j < S.nx; ++j) r += M.cx[(size_t)mdl * S.nx + j] * B.x0[(size_t)inst * S.nx + j];
                 if (M.cw) for (int j = 0; j < S.nW; ++j) r += M.cw[(size_t)mdl * S.nW + j] * B.omega[(size_t)inst * S.nW + j];
+                if (B.rconst) r += B.rconst[inst];
                 B.obj_out[inst] = ob + r; B.lb_out[inst] = ob + r;
             }
         } else {

@@ -280,6 +280,39 @@ class GpuProblem(object):
                                                          _lib.dptr(xc) if xc is not None else None))
         return n_cols
 
+    def _inst_cost_arrays(self, lin_v=None, lin_x=None, lin_y=None):
+        """(batch, len) float64 arrays of a per-instance cost, a (len,) array broadcast; ValueError on a shape that fits neither"""
+        d, N = self.model.dims, self.N_tilde
+        out = []
+        for name, a, ln in (("lin_v", lin_v, self.n), ("lin_x", lin_x, N * d["nx"]), ("lin_y", lin_y, N * d["ny"])):
+            if a is None:
+                out.append(None)
+                continue
+            a = np.asarray(a, dtype=np.float64)
+            if a.ndim == 2 and a.shape[1] == 1 and a.shape[0] == ln and self.batch != ln:
+                a = a[:, 0]                      # a column vector, as the reference writes its atoms
+            if ln == 0:
+                raise ValueError("%s given but the model has none of that variable" % name)
+            if a.shape == (ln,):
+                a = np.broadcast_to(a, (self.batch, ln))
+            if a.shape != (self.batch, ln):
+                raise ValueError("%s has shape %s, expected (%d, %d) or (%d,)" % (name, a.shape, self.batch, ln, ln))
+            out.append(np.ascontiguousarray(a))
+        return out
+
+    def upload_instance_cost(self, lin_v=None, lin_x=None, lin_y=None):
+        """per-instance LINEAR cost of the resident batch, added to the problem's cost (mld_upload_instance_cost): arrays (batch, len) with len =
+        N_tilde * nv / nx / ny, a (len,) array is the same for every instance; everything None clears.  Valid until the next upload()."""
+        lv, lx, ly = self._inst_cost_arrays(lin_v, lin_x, lin_y)
+        check(_lib.load().mld_upload_instance_cost(self._h, _lib.dptr(lv), _lib.dptr(lx), _lib.dptr(ly)))
+
+    def instance_cost(self):
+        """read-back (mld_download_instance_cost): q (batch, n) the unscaled per-instance addition to the linear term pulled back to v, and const
+        (batch) its constant term at the current x0 / omega"""
+        q, c = np.zeros((self.batch, self.n)), np.zeros(self.batch)
+        check(_lib.load().mld_download_instance_cost(self._h, _lib.dptr(q), _lib.dptr(c)))
+        return dict(q=q, const=c)
+
     def set_opts(self, **opts):
         """limits / tolerances of the existing problem (mld_problem_set_opts): MIPGap, NodeLimit, IterationLimit, gap_abs, cut
         rounds, reserved -- no rebuild, like the per-call solver kwargs of the reference's solve()"""
@@ -411,8 +444,11 @@ class GpuProblem(object):
         check(_lib.load().mld_download_telemetry(self._h, ip(lat), ip(rows), C.byref(rb)))
         return dict(latency_ns=lat, rows_updated=rows, row_bytes=int(rb.value))
 
-    def solve(self, x0, omega, model_idx=None, fixed_bin=None, omega_cols=None, col_rows=None, x_cols=None, warm_start=None):
+    def solve(self, x0, omega, model_idx=None, fixed_bin=None, omega_cols=None, col_rows=None, x_cols=None, warm_start=None, inst_cost=None):
+        """upload, solve, download.  inst_cost: dict(lin_v=..., lin_x=..., lin_y=...) of upload_instance_cost for this batch"""
         self.upload(x0, omega, model_idx, fixed_bin)
+        if inst_cost:
+            self.upload_instance_cost(**inst_cost)
         if omega_cols is not None:
             self.upload_constraint_blocks(omega_cols, col_rows, x_cols)
         if warm_start is not None:
@@ -462,15 +498,18 @@ class GpuProblem(object):
         check(_lib.load().mld_handoff_stats(self._h, out))
         return dict(items=int(out[0]), given_up=int(out[1]), unfinished=int(out[2]), queue_full=int(out[3]))
 
-    def solve_handoff_device(self, x0, omega, model_idx=None, fixed_bin=None, first_nodes=None, sub_nodes=None, max_gen=8, max_children=64, max_tree=160, room_factor=0.0, donate=0, rounds=0):
+    def solve_handoff_device(self, x0, omega, model_idx=None, fixed_bin=None, first_nodes=None, sub_nodes=None, max_gen=8, max_children=64, max_tree=160, room_factor=0.0, donate=0, rounds=0, inst_cost=None):
         """the batch with the hand-off inside ONE launch (set_handoff): upload, solve, download -- the merged results per instance plus `handoff`
-        statistics.  The problem's own limits and the hand-off switch are restored afterwards."""
+        statistics.  The problem's own limits and the hand-off switch are restored afterwards.  inst_cost: as solve() (items use their source
+        instance's cost)."""
         keep_nodes = int(self.opts.max_nodes)
         try:
             if first_nodes is not None:
                 self.set_opts(max_nodes=int(first_nodes))
             self.set_handoff(True, sub_nodes=int(sub_nodes or 0), max_gen=max_gen, max_children=max_children, max_tree=max_tree, room_factor=room_factor, donate=donate, rounds=rounds)
             self.upload(x0, omega, model_idx, fixed_bin)
+            if inst_cost:
+                self.upload_instance_cost(**inst_cost)
             stats = self.solve_resident()
             out = self.download()
             out["stats"] = stats
