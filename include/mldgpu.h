@@ -350,6 +350,24 @@ int mld_upload_instance_cost(mld_problem_t *, const double *lin_v, const double 
  * zeros when no per-instance cost is resident. */
 int mld_download_instance_cost(mld_problem_t *, double *q_out, double *const_out);
 
+/* Predicted state and output trajectories of the resident batch: the variables the reference builds after every solve(),
+ * gen_state_output_vars (controllers/components/variables.py:246-286):
+ *   x_tilde = Phi_x x_k + Gamma_v v_tilde + Gamma_omega omega_tilde + Gamma_5      (:259-265)
+ *   y_tilde = L_x   x_k + L_v     v_tilde + L_omega     omega_tilde + L_5          (:269-275)
+ * for every instance, as one batched GEMM per model on the matrix cores (fp32 with MLD_F32, vector ALUs with MLD_DBG_GEMM_VALU) -- the forward
+ * half of the pull-back of mld_upload_instance_cost.  x_out (batch, N_tilde*nx), y_out (batch, N_tilde*ny): row-major, step-major inside a row
+ * (the reference's var_N_tilde stacking); either may be NULL.
+ *   v == NULL  the resident solution of the last solve.  Needs a finished solve of the CURRENT inputs: MLD_ERR_INVALID, nothing changed, when the
+ *              batch was not solved since its upload / mld_select_inputs, or once mld_advance_batch has moved the inputs on (the plan belongs to
+ *              inputs that are gone).  An instance without a usable plan -- the test mld_advance_batch applies when it counts skipped instances:
+ *              not OPTIMAL / NODE_LIMIT with a finite objective -- gets NaN in every element of its rows.  With the in-kernel hand-off on, the
+ *              instances' rows are read after the device merge.
+ *   v != NULL  (batch, N_tilde*nv): the caller's plans under the batch's current x0 / omega (the `variables=` argument of the reference).  Needs
+ *              only a resident batch: valid before any solve, after mld_select_inputs and after mld_advance_batch.  No NaN masking.
+ * Time-varying handles work like time-invariant ones (model_idx indexes horizons).  Runs on the problem's stream and waits for that stream only.
+ * MLD_ERR_INVALID: no batch resident; a launched solve not finished; x_out with nx == 0; y_out with ny == 0. */
+int mld_predict_batch(mld_problem_t *, const double *v, double *x_out, double *y_out);
+
 /* Per-instance telemetry of the last solve: time spent inside the solve kernel (device wall clock, ns) and
  * the number of dictionary rows the rank-1 updates touched (x *row_bytes x 2 = bytes streamed by pivots). */
 int mld_download_telemetry(mld_problem_t *, int64_t *latency_ns, int64_t *rows_updated, int64_t *row_bytes);

@@ -296,6 +296,8 @@ __global__ void __launch_bounds__(256) k_warm_from_plan(int batch, int nb, int n
     warm[t] = val > 0.5 ? 1 : 0;
 }
 
+#include "trajectory.inc"      // k_trajectory / k_trajectory_valu (mld_predict_batch): they mask with plan_usable, like k_advance
+
 // ------------------------------------------------------------------------------------------------
 /* buffers of the uploaded batch (ensure_batch, mld_upload_batch, mld_upload_constraint_blocks, mld_stage_inputs): released together when the
  * batch is laid out anew.  Inputs have one entry per instance, results one per queue entry (instances, then the items of the in-kernel hand-off). */
@@ -1872,6 +1874,64 @@ int mld_download_instance_cost(mld_problem_t *p, double *q_out, double *const_ou
             HIP_TRY(hipStreamSynchronize(p->stream));
         }
     }
+    return MLD_OK;
+}
+
+/* Predicted state and output trajectories of the resident batch (gen_state_output_vars, controllers/components/variables.py:246-286: x_tilde :259-265,
+ * y_tilde :269-275, with its variables= / x_k= / omega_tilde_k= arguments) as ONE GEMM per model over [v | x0 | omega | 1] (k_trajectory;
+ * k_trajectory_valu under MLD_DBG_GEMM_VALU).  The state and output maps of the tightened model are the original ones (tightening changes F1 / F2 / Psi
+ * and f5 only).  v == NULL: the resident solution, rows of instances without a usable plan all NaN; v given: the caller's plans under the current inputs.
+ * The results are built in buffers of their own and every path waits for the stream, so a call that fails changes nothing. */
+int mld_predict_batch(mld_problem_t *p, const double *v, double *x_out, double *y_out)
+{
+    if (mld_device_count() <= 0) { mld_set_error("no HIP device (libmldgpu has no CPU fallback)"); return MLD_ERR_NO_DEVICE; }
+    MLD_NOT_IN_FLIGHT(p, "mld_predict_batch");
+    if (!p || p->batch < 1) { mld_set_error("mld_predict_batch: no batch resident (mld_upload_batch)"); return MLD_ERR_INVALID; }
+    const mld_dims &d = p->model->dims;
+    const int n = p->n, nx = p->nx, nW = p->nW, batch = p->batch, N = p->N;
+    const int NX = N * d.nx, NY = N * d.ny;
+    if (x_out && NX == 0) { mld_set_error("mld_predict_batch: x_out given but the model has no state (nx = 0)"); return MLD_ERR_INVALID; }
+    if (y_out && NY == 0) { mld_set_error("mld_predict_batch: y_out given but the model has no output (ny = 0)"); return MLD_ERR_INVALID; }
+    if (!v && !p->solved) { mld_set_error("mld_predict_batch: the resident batch has not been solved since its upload / selection (there is no plan to evaluate; pass v)"); return MLD_ERR_INVALID; }
+    if (!v && p->advanced) { mld_set_error("mld_predict_batch: mld_advance_batch has moved the inputs on -- the resident plan belongs to inputs that are gone (solve again, or pass v)"); return MLD_ERR_INVALID; }
+    if (!x_out && !y_out) return MLD_OK;
+    const hipStream_t sq = p->stream;
+    DevBuf<double> d_v, d_x, d_y;
+    if (x_out) HIP_TRY(d_x.alloc((size_t)batch * NX));
+    if (y_out) HIP_TRY(d_y.alloc((size_t)batch * NY));
+    if (v) HIP_TRY(d_v.alloc((size_t)batch * std::max(1, n)));
+    /* everything queued on the stream; the wait below comes on EVERY path, so that the caller's arrays and the temporaries may go when this returns */
+    auto queue = [&]() -> int {
+        if (v && n) HIP_TRY(hipMemcpyAsync(d_v, v, sizeof(double) * (size_t)batch * n, hipMemcpyHostToDevice, sq));
+        const double *pv = v ? d_v.get() : p->bat.v.get();      /* (the resident solution: rows < batch are the instances', hand-off items come after them) */
+        const int *st = v ? nullptr : p->bat.status.get();
+        const double *ob = v ? nullptr : p->bat.obj.get();
+        const mld_model *t = p->tight.get();
+        PbMaps mp;
+        const int oW[4] = {O_GamV, O_PhiX, O_GamW, O_Gam5}, oY[4] = {O_LV, O_LX, O_LW, O_L5};
+        for (int f = 0; f < 4; ++f) {
+            mp.W[f] = NX ? t->d_out[oW[f]].get() : nullptr; mp.sW[f] = t->lay.out_size[oW[f]];
+            mp.Y[f] = NY ? t->d_out[oY[f]].get() : nullptr; mp.sY[f] = t->lay.out_size[oY[f]];
+        }
+        const int r_begin = x_out ? 0 : NX, r_end = y_out ? NX + NY : NX;      /* rows of the stacked maps that are asked for */
+        if (p->opts.reserved & MLD_DBG_GEMM_VALU)
+            hipLaunchKernelGGL(k_trajectory_valu, dim3(batch), dim3(256), sizeof(double) * (n + nx + nW + 1), sq, NX, NY, n, nx, nW, mp,
+                               p->has_midx ? p->bat.model_idx.get() : nullptr, pv, p->bat.x0.get(), p->bat.omega.get(), st, ob, r_begin, r_end, d_x.get(), d_y.get());
+        else if (p->opts.flags & MLD_F32)
+            hipLaunchKernelGGL(k_trajectory<true>, dim3(p->n_groups), dim3(64 * RM_WAVES), 0, sq, N, d.nx, d.ny, p->nv, d.nomega, mp, p->bat.groups.get(), p->bat.perm.get(),
+                               pv, p->bat.x0.get(), p->bat.omega.get(), st, ob, r_begin, r_end, d_x.get(), d_y.get());
+        else
+            hipLaunchKernelGGL(k_trajectory<false>, dim3(p->n_groups), dim3(64 * RM_WAVES), 0, sq, N, d.nx, d.ny, p->nv, d.nomega, mp, p->bat.groups.get(), p->bat.perm.get(),
+                               pv, p->bat.x0.get(), p->bat.omega.get(), st, ob, r_begin, r_end, d_x.get(), d_y.get());
+        HIP_TRY(hipGetLastError());
+        if (x_out) HIP_TRY(hipMemcpyAsync(x_out, d_x, sizeof(double) * (size_t)batch * NX, hipMemcpyDeviceToHost, sq));
+        if (y_out) HIP_TRY(hipMemcpyAsync(y_out, d_y, sizeof(double) * (size_t)batch * NY, hipMemcpyDeviceToHost, sq));
+        return MLD_OK;
+    };
+    const int rc = queue();
+    const hipError_t es = hipStreamSynchronize(sq);
+    if (rc) return rc;
+    HIP_TRY(es);
     return MLD_OK;
 }
 

@@ -313,6 +313,27 @@ class GpuProblem(object):
         check(_lib.load().mld_download_instance_cost(self._h, _lib.dptr(q), _lib.dptr(c)))
         return dict(q=q, const=c)
 
+    def _plan_array(self, v):
+        """(batch, n) float64 array of caller-supplied plans, a (n,) array broadcast; ValueError on a shape that fits neither"""
+        if v is None:
+            return None
+        v = np.asarray(v, dtype=np.float64)
+        if v.shape == (self.n,):
+            v = np.broadcast_to(v, (self.batch, self.n))
+        if v.shape != (self.batch, self.n):
+            raise ValueError("v has shape %s, expected (%d, %d) or (%d,)" % (v.shape, self.batch, self.n, self.n))
+        return np.ascontiguousarray(v)
+
+    def trajectories(self, v=None):
+        """predicted trajectories of the resident batch on device (mld_predict_batch): dict(x=(batch, N_tilde*nx), y=(batch, N_tilde*ny)), step-major
+        rows; a family the model lacks has width 0.  v=None: the last solve's plans (needs a finished solve of the current inputs; instances without
+        a usable plan -- the ones advance() skips -- get NaN rows); v (batch, n) or (n,): these plans under the current x0 / omega, valid without a solve."""
+        v = self._plan_array(v)
+        d, N = self.model.dims, self.N_tilde
+        x, y = np.zeros((self.batch, N * d["nx"])), np.zeros((self.batch, N * d["ny"]))
+        check(_lib.load().mld_predict_batch(self._h, _lib.dptr(v), _lib.dptr(x) if x.shape[1] else None, _lib.dptr(y) if y.shape[1] else None))
+        return dict(x=x, y=y)
+
     def set_opts(self, **opts):
         """limits / tolerances of the existing problem (mld_problem_set_opts): MIPGap, NodeLimit, IterationLimit, gap_abs, cut
         rounds, reserved -- no rebuild, like the per-call solver kwargs of the reference's solve()"""
@@ -444,8 +465,9 @@ class GpuProblem(object):
         check(_lib.load().mld_download_telemetry(self._h, ip(lat), ip(rows), C.byref(rb)))
         return dict(latency_ns=lat, rows_updated=rows, row_bytes=int(rb.value))
 
-    def solve(self, x0, omega, model_idx=None, fixed_bin=None, omega_cols=None, col_rows=None, x_cols=None, warm_start=None, inst_cost=None):
-        """upload, solve, download.  inst_cost: dict(lin_v=..., lin_x=..., lin_y=...) of upload_instance_cost for this batch"""
+    def solve(self, x0, omega, model_idx=None, fixed_bin=None, omega_cols=None, col_rows=None, x_cols=None, warm_start=None, inst_cost=None, trajectories=False):
+        """upload, solve, download.  inst_cost: dict(lin_v=..., lin_x=..., lin_y=...) of upload_instance_cost for this batch; trajectories=True adds
+        the predicted x / y of trajectories() to the result"""
         self.upload(x0, omega, model_idx, fixed_bin)
         if inst_cost:
             self.upload_instance_cost(**inst_cost)
@@ -456,6 +478,8 @@ class GpuProblem(object):
         stats = self.solve_resident()
         out = self.download()
         out["stats"] = stats
+        if trajectories:
+            out.update(self.trajectories())
         return out
 
     # -- sub-tree hand-off ---------------------------------------------------------------------------
@@ -498,10 +522,10 @@ class GpuProblem(object):
         check(_lib.load().mld_handoff_stats(self._h, out))
         return dict(items=int(out[0]), given_up=int(out[1]), unfinished=int(out[2]), queue_full=int(out[3]))
 
-    def solve_handoff_device(self, x0, omega, model_idx=None, fixed_bin=None, first_nodes=None, sub_nodes=None, max_gen=8, max_children=64, max_tree=160, room_factor=0.0, donate=0, rounds=0, inst_cost=None):
+    def solve_handoff_device(self, x0, omega, model_idx=None, fixed_bin=None, first_nodes=None, sub_nodes=None, max_gen=8, max_children=64, max_tree=160, room_factor=0.0, donate=0, rounds=0, inst_cost=None, trajectories=False):
         """the batch with the hand-off inside ONE launch (set_handoff): upload, solve, download -- the merged results per instance plus `handoff`
         statistics.  The problem's own limits and the hand-off switch are restored afterwards.  inst_cost: as solve() (items use their source
-        instance's cost)."""
+        instance's cost).  trajectories=True adds the predicted x / y of the merged plans (read before the resident batch is dropped)."""
         keep_nodes = int(self.opts.max_nodes)
         try:
             if first_nodes is not None:
@@ -514,6 +538,8 @@ class GpuProblem(object):
             out = self.download()
             out["stats"] = stats
             out["handoff"] = self.handoff_stats()
+            if trajectories:
+                out.update(self.trajectories())
             return out
         finally:
             self.set_handoff(False)
