@@ -368,6 +368,40 @@ int mld_download_instance_cost(mld_problem_t *, double *q_out, double *const_out
  * MLD_ERR_INVALID: no batch resident; a launched solve not finished; x_out with nx == 0; y_out with ny == 0. */
 int mld_predict_batch(mld_problem_t *, const double *v, double *x_out, double *y_out);
 
+/* Solution quality of the resident batch: what the reference's backend reports after every solve (Gurobi's ObjVal, ConstrVio, IntVio, BoundVio
+ * behind controllers/controller_base.py:509), for the resident plans or any plans of the caller, and a-posteriori scenario validation: the rows
+ * evaluated under disturbance columns in the layout of gen_evo_constraints (controller_base.py:411-456) WITHOUT making them part of the problem.
+ * ARITHMETIC: everything here is fp64, also on a handle created with MLD_F32 -- a certificate in fp32 certifies nothing.  Matrix cores by
+ * default (k_evaluate), vector ALUs under MLD_DBG_GEMM_VALU (k_evaluate_valu, the independent cross-check).
+ *   v == NULL  the resident solution of the last solve.  Needs a finished solve of the CURRENT inputs (refused like mld_predict_batch: not solved since
+ *              the upload / mld_select_inputs, or mld_advance_batch has moved the inputs on).  An instance without a usable plan (not OPTIMAL /
+ *              NODE_LIMIT with a finite objective) gets NaN in every floating output and -1 in constr_row_out.  With the in-kernel hand-off on, rows
+ *              are read after the device merge.
+ *   v != NULL  (batch, N_tilde*nv): the caller's plans under the current x0 / omega.  Needs only a resident batch; no NaN masking.
+ * ROWS: always those of the ORIGINAL (un-tightened) model, condensed on the device at the problem's N_tilde on first use (as mld_rhs_batch) and
+ * reused.  Residual of row i under column c:  r_i = (H_v v)_i - (H_x x_c + H_omega omega_c + H_5)_i, unscaled, in the rows' own units (Gurobi's
+ * ConstrVio convention); negative = slack.
+ *   n_cols == 0  the problem as posed -- the columns the next mld_solve_resident would enforce: the standard block (the batch's own x0 / omega, all
+ *                rows) unless mld_set_std_block(0), plus the resident blocks of mld_upload_constraint_blocks[_x] with their col_rows / x_cols.
+ *                constr_vio_out (batch) = max r_i over those columns and the rows each applies to, constr_row_out (batch) a row that attains it;
+ *                -inf and -1 where no row exists (no constraint rows, or neither standard block nor blocks).
+ *   n_cols > 0   the caller's validation columns, laid out as for mld_upload_constraint_blocks_x: omega_cols (batch, n_cols, N_tilde*nomega), col_rows
+ *                (n_cols) leading rows a column applies to or NULL = all, x_cols (batch, n_cols, nx) or NULL = the instance's x0.  constr_vio_out and
+ *                constr_row_out are (batch, n_cols), one entry per column (a column of 0 rows: -inf, -1).  The resident blocks are neither used nor changed.
+ * PER INSTANCE, whatever the columns: int_vio_out (batch) = max over the binaries |v_j - rint(v_j)| (0 without binaries); bound_vio_out (batch) = the
+ * largest violation of the declared bounds mu >= 0, binaries in [0, 1] (>= 0; 0 when nothing is bounded); obj_out (batch) = the value a solve would
+ * report for that v at the current inputs, 1/2 v'Pv + (q0 + Qx x0 + Qw omega + q_b)'v + constant, with the cost of the last mld_problem_set_cost, a
+ * resident per-instance cost in q_b and the constant, and the quadratic atoms' value at v = 0 in the constant.
+ * Every output may be NULL; all NULL: success, nothing done.  Memory: batch x N_tilde*nc doubles of H_v v (twice that when nx + N_tilde*nomega > 256),
+ * the results, batch x n doubles for v or a per-instance q, and the caller's columns in slices of at most 256 MB (at least one column) -- it does not
+ * grow with n_cols beyond the results.  Runs on the problem's stream and waits for that stream only; nothing a later solve reads is written.
+ * MLD_ERR_INVALID, nothing changed: no batch resident; a launched solve not finished; n_cols < 0; n_cols > 0 without omega_cols when nomega > 0;
+ * x_cols with nx == 0; a col_rows entry outside [0, N_tilde*nc]. */
+int mld_evaluate_batch(mld_problem_t *, const double *v,
+                       int n_cols, const double *omega_cols, const int32_t *col_rows, const double *x_cols,
+                       double *obj_out, double *constr_vio_out, int32_t *constr_row_out,
+                       double *int_vio_out, double *bound_vio_out);
+
 /* Per-instance telemetry of the last solve: time spent inside the solve kernel (device wall clock, ns) and
  * the number of dictionary rows the rank-1 updates touched (x *row_bytes x 2 = bytes streamed by pivots). */
 int mld_download_telemetry(mld_problem_t *, int64_t *latency_ns, int64_t *rows_updated, int64_t *row_bytes);

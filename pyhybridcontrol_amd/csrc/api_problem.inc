@@ -297,6 +297,7 @@ __global__ void __launch_bounds__(256) k_warm_from_plan(int batch, int nb, int n
 }
 
 #include "trajectory.inc"      // k_trajectory / k_trajectory_valu (mld_predict_batch): they mask with plan_usable, like k_advance
+#include "evaluate.inc"        // k_evaluate / k_evaluate_valu, k_eval_point, k_eval_obj (mld_evaluate_batch): the same masking
 
 // ------------------------------------------------------------------------------------------------
 /* buffers of the uploaded batch (ensure_batch, mld_upload_batch, mld_upload_constraint_blocks, mld_stage_inputs): released together when the
@@ -1929,6 +1930,137 @@ int mld_predict_batch(mld_problem_t *p, const double *v, double *x_out, double *
         return MLD_OK;
     };
     const int rc = queue();
+    const hipError_t es = hipStreamSynchronize(sq);
+    if (rc) return rc;
+    HIP_TRY(es);
+    return MLD_OK;
+}
+
+/* Solution quality of the resident batch: what the reference's backend reports after every solve (ObjVal, ConstrVio, IntVio, BoundVio;
+ * controllers/controller_base.py:509) for the resident or the caller's plans, on the ORIGINAL model's rows (condensed on first use, as mld_rhs_batch
+ * does) and any disturbance columns (the layout of gen_evo_constraints, controller_base.py:411-456).  Kernels: evaluate.inc.  Every result is built
+ * in a buffer of its own and every path waits for the stream, so a call that fails changes nothing; nothing the solve path reads is written. */
+#define EV_SLICE_BYTES ((size_t)256 << 20)      /* device copy of the caller's validation columns: at most this much at a time (at least one column) */
+int mld_evaluate_batch(mld_problem_t *p, const double *v, int n_cols, const double *omega_cols, const int32_t *col_rows, const double *x_cols,
+                       double *obj_out, double *constr_vio_out, int32_t *constr_row_out, double *int_vio_out, double *bound_vio_out)
+{
+    if (mld_device_count() <= 0) { mld_set_error("no HIP device (libmldgpu has no CPU fallback)"); return MLD_ERR_NO_DEVICE; }
+    MLD_NOT_IN_FLIGHT(p, "mld_evaluate_batch");
+    if (!p || p->batch < 1) { mld_set_error("mld_evaluate_batch: no batch resident (mld_upload_batch)"); return MLD_ERR_INVALID; }
+    const mld_dims &d = p->model->dims;
+    const int n = p->n, nx = p->nx, nW = p->nW, batch = p->batch, m0 = p->m0, M = p->n_models;
+    if (n_cols < 0) { mld_set_error("mld_evaluate_batch: n_cols = %d", n_cols); return MLD_ERR_INVALID; }
+    if (n_cols > 0 && nW && !omega_cols) { mld_set_error("mld_evaluate_batch: n_cols = %d without omega_cols (nomega > 0)", n_cols); return MLD_ERR_INVALID; }
+    if (x_cols && nx == 0) { mld_set_error("mld_evaluate_batch: x_cols given but the model has no state (nx = 0)"); return MLD_ERR_INVALID; }
+    if (col_rows) for (int c = 0; c < n_cols; ++c) if (col_rows[c] < 0 || col_rows[c] > m0) { mld_set_error("mld_evaluate_batch: col_rows[%d]=%d outside [0,%d]", c, col_rows[c], m0); return MLD_ERR_INVALID; }
+    if (!v && !p->solved) { mld_set_error("mld_evaluate_batch: the resident batch has not been solved since its upload / selection (there is no plan to evaluate; pass v)"); return MLD_ERR_INVALID; }
+    if (!v && p->advanced) { mld_set_error("mld_evaluate_batch: mld_advance_batch has moved the inputs on -- the resident plan belongs to inputs that are gone (solve again, or pass v)"); return MLD_ERR_INVALID; }
+    if (!obj_out && !constr_vio_out && !constr_row_out && !int_vio_out && !bound_vio_out) return MLD_OK;
+    const hipStream_t sq = p->stream;
+    const bool want_c = constr_vio_out || constr_row_out;
+    const bool valu = (p->opts.reserved & MLD_DBG_GEMM_VALU) != 0;
+    mld_model *mo = p->model;
+    int rc;
+    if (want_c && m0 && (mo->cond_N != p->N || !mo->out64) && (rc = condense_model_device(mo, p->N, nullptr, sq))) return rc;
+    const int *midx = p->has_midx ? p->bat.model_idx.get() : nullptr;
+    const size_t nout = n_cols > 0 ? (size_t)n_cols : 1;      /* constraint results per instance */
+    /* columns of the caller per launch: the device copy of a slice stays within EV_SLICE_BYTES */
+    const size_t col_bytes = sizeof(double) * (size_t)batch * std::max(1, nW + (x_cols ? nx : 0));
+    const int slice = n_cols > 0 ? (int)std::min<size_t>((size_t)n_cols, std::max<size_t>(1, EV_SLICE_BYTES / col_bytes)) : 0;
+    DevBuf<double> d_v, d_hv, d_part, d_om, d_xc, d_vio, d_obj, d_iv, d_bv, d_qi, d_rc, d_one;
+    DevBuf<int> d_rows, d_row;
+    if (v) HIP_TRY(d_v.alloc((size_t)batch * std::max(1, n)));
+    if (want_c) {
+        HIP_TRY(d_hv.alloc((size_t)batch * std::max(1, m0)));
+        if (!valu && nx + nW > EV_KC) HIP_TRY(d_part.alloc((size_t)batch * std::max(1, m0)));
+        HIP_TRY(d_vio.alloc((size_t)batch * nout)); HIP_TRY(d_row.alloc((size_t)batch * nout));
+        if (slice && nW) HIP_TRY(d_om.alloc((size_t)batch * slice * nW));
+        if (slice && x_cols) HIP_TRY(d_xc.alloc((size_t)batch * slice * nx));
+        if (slice && col_rows) HIP_TRY(d_rows.alloc(n_cols));
+    }
+    const bool inst_q = p->has_quad || p->ic_ld;
+    if (obj_out) {
+        HIP_TRY(d_obj.alloc(batch));
+        if (inst_q) { HIP_TRY(d_qi.alloc((size_t)batch * std::max(1, n))); HIP_TRY(d_rc.alloc(batch)); HIP_TRY(d_one.alloc((size_t)std::max(1, n) * M)); }
+    }
+    if (int_vio_out) HIP_TRY(d_iv.alloc(batch));
+    if (bound_vio_out) HIP_TRY(d_bv.alloc(batch));
+    /* everything queued on the stream; the wait below comes on EVERY path, so that the caller's arrays and the temporaries may go when this returns */
+    auto queue = [&]() -> int {
+        if (v && n) HIP_TRY(hipMemcpyAsync(d_v, v, sizeof(double) * (size_t)batch * n, hipMemcpyHostToDevice, sq));
+        const double *pv = v ? d_v.get() : p->bat.v.get();      /* (the resident solution: rows < batch are the instances', after the hand-off's merge) */
+        const int *st = v ? nullptr : p->bat.status.get();
+        const double *ob = v ? nullptr : p->bat.obj.get();
+        if (want_c) {
+            EvCols ec;
+            ec.x0 = p->bat.x0.get(); ec.omega = p->bat.omega.get();
+            const double *Hv = m0 ? mo->d_out[O_HV].get() : nullptr, *Hx = m0 && nx ? mo->d_out[O_HX].get() : nullptr;
+            const double *Hw = m0 && nW ? mo->d_out[O_HW].get() : nullptr, *H5 = m0 ? mo->d_out[O_H5].get() : nullptr;
+            auto launch_ev = [&](int do_v) {
+                if (valu)
+                    hipLaunchKernelGGL(k_evaluate_valu, dim3(batch), dim3(256), sizeof(double) * (n + m0), sq, m0, n, nx, nW, Hv, Hx, Hw, H5, midx, pv, st, ob, do_v, ec,
+                                       d_hv.get(), d_vio.get(), d_row.get());
+                else
+                    hipLaunchKernelGGL(k_evaluate, dim3(p->n_groups), dim3(64 * RM_WAVES), 0, sq, m0, std::max(1, d.nc), p->nv, d.nomega, n, nx, nW, Hv, Hx, Hw, H5,
+                                       p->bat.groups.get(), p->bat.perm.get(), pv, st, ob, do_v, ec, d_hv.get(), d_part.get(), d_vio.get(), d_row.get());
+            };
+            if (n_cols == 0) {      /* the problem as posed: the columns the next solve would enforce */
+                ec.n_cols = p->n_xcols; ec.std = p->std_block ? 1 : 0; ec.per_col = 0; ec.ld_out = 1; ec.col0 = 0;
+                ec.omc = p->bat.xcols.get(); ec.xc = p->has_xcols_x ? p->bat.xcols_x.get() : nullptr; ec.rows = p->n_xcols ? p->bat.xrows.get() : nullptr;
+                launch_ev(1);
+            } else {
+                if (col_rows) HIP_TRY(hipMemcpyAsync(d_rows, col_rows, sizeof(int) * n_cols, hipMemcpyHostToDevice, sq));
+                for (int c0 = 0; c0 < n_cols; c0 += slice) {
+                    const int nc_ = std::min(slice, n_cols - c0);
+                    if (nW) HIP_TRY(hipMemcpy2DAsync(d_om, sizeof(double) * nc_ * nW, omega_cols + (size_t)c0 * nW, sizeof(double) * n_cols * nW, sizeof(double) * nc_ * nW, batch, hipMemcpyHostToDevice, sq));
+                    if (x_cols) HIP_TRY(hipMemcpy2DAsync(d_xc, sizeof(double) * nc_ * nx, x_cols + (size_t)c0 * nx, sizeof(double) * n_cols * nx, sizeof(double) * nc_ * nx, batch, hipMemcpyHostToDevice, sq));
+                    ec.n_cols = nc_; ec.std = 0; ec.per_col = 1; ec.ld_out = n_cols; ec.col0 = c0;
+                    ec.omc = d_om.get(); ec.xc = x_cols ? d_xc.get() : nullptr; ec.rows = col_rows ? d_rows.get() + c0 : nullptr;
+                    launch_ev(c0 == 0);
+                    HIP_TRY(hipGetLastError());
+                }
+            }
+            HIP_TRY(hipGetLastError());
+            if (constr_vio_out) HIP_TRY(hipMemcpyAsync(constr_vio_out, d_vio, sizeof(double) * (size_t)batch * nout, hipMemcpyDeviceToHost, sq));
+            if (constr_row_out) HIP_TRY(hipMemcpyAsync(constr_row_out, d_row, sizeof(int) * (size_t)batch * nout, hipMemcpyDeviceToHost, sq));
+        }
+        if (int_vio_out || bound_vio_out) {
+            hipLaunchKernelGGL(k_eval_point, dim3((batch + 3) / 4), dim3(256), 0, sq, batch, n, p->nv, d.nu, d.nu_l, d.ndelta, d.nz, d.nmu, d.nmu_l, pv, st, ob, d_iv.get(), d_bv.get());
+            HIP_TRY(hipGetLastError());
+            if (int_vio_out) HIP_TRY(hipMemcpyAsync(int_vio_out, d_iv, sizeof(double) * batch, hipMemcpyDeviceToHost, sq));
+            if (bound_vio_out) HIP_TRY(hipMemcpyAsync(bound_vio_out, d_bv, sizeof(double) * batch, hipMemcpyDeviceToHost, sq));
+        }
+        if (obj_out) {
+            /* the per-instance q and constant at the current inputs by the kernels of launch_rhs_cost / launch_inst_cost, with unit column scales and
+             * into buffers of this call (the solve path's qs_inst / rconst are not touched) */
+            if (inst_q) {
+                const size_t tot = (size_t)batch * n, one = (size_t)std::max(1, n) * M;
+                hipLaunchKernelGGL(k_fill_f64, dim3((unsigned)((one + 255) / 256)), dim3(256), 0, sq, one, 1.0, d_one.get());
+                HIP_TRY(hipMemsetAsync(d_rc, 0, sizeof(double) * batch, sq));
+                if (p->has_quad) {
+                    const mld_model *t = p->tight.get();
+                    const int NX = p->N * d.nx, NY = p->N * d.ny;
+                    hipLaunchKernelGGL(k_qinst, dim3(batch), dim3(256), 0, sq, n, nx, nW, p->d_q0, p->d_Qx, p->d_Qw, d_one.get(), midx, p->bat.x0, p->bat.omega, d_qi.get(),
+                                       p->ic_ld ? p->bat.icost.get() : nullptr, p->ic_ld);
+                    if (p->d_Wx && NX) hipLaunchKernelGGL(k_quad_const, dim3(batch), dim3(256), sizeof(double) * NX, sq, NX, nx, nW, t->d_out[O_PhiX], t->lay.out_size[O_PhiX],
+                                                          t->d_out[O_GamW], t->lay.out_size[O_GamW], t->d_out[O_Gam5], t->lay.out_size[O_Gam5], p->d_Wx, midx, p->bat.x0, p->bat.omega, d_rc.get());
+                    if (p->d_Wy && NY) hipLaunchKernelGGL(k_quad_const, dim3(batch), dim3(256), sizeof(double) * NY, sq, NY, nx, nW, t->d_out[O_LX], t->lay.out_size[O_LX],
+                                                          t->d_out[O_LW], t->lay.out_size[O_LW], t->d_out[O_L5], t->lay.out_size[O_L5], p->d_Wy, midx, p->bat.x0, p->bat.omega, d_rc.get());
+                } else if (tot)
+                    hipLaunchKernelGGL(k_inst_cost, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, sq, tot, n, p->ic_ld, p->d_q0, d_one.get(), (const double *)nullptr, midx,
+                                       p->bat.icost, d_qi.get(), (double *)nullptr);
+                if (p->ic_ld > n)
+                    hipLaunchKernelGGL(k_inst_const, dim3((batch + 3) / 4), dim3(256), 0, sq, batch, n, nx, nW, p->ic_ld, p->bat.icost, p->bat.x0, p->bat.omega, d_rc.get());
+            }
+            hipLaunchKernelGGL(k_eval_obj, dim3(batch), dim3(256), sizeof(double) * std::max(1, n), sq, n, nx, nW, p->d_q0.get(), inst_q ? d_qi.get() : nullptr,
+                               p->has_quad ? p->d_P.get() : nullptr, nx ? p->d_cx.get() : nullptr, nW ? p->d_cw.get() : nullptr, p->d_c0.get(),
+                               inst_q ? d_rc.get() : nullptr, midx, pv, p->bat.x0.get(), p->bat.omega.get(), st, ob, d_obj.get());
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(obj_out, d_obj, sizeof(double) * batch, hipMemcpyDeviceToHost, sq));
+        }
+        return MLD_OK;
+    };
+    rc = queue();
     const hipError_t es = hipStreamSynchronize(sq);
     if (rc) return rc;
     HIP_TRY(es);

@@ -68,6 +68,7 @@ struct mld_model {
     size_t pack_len = 0;
     // condensing results (device resident)
     int cond_N = -1;
+    bool out64 = false;          // d_out holds the fp64 maps of cond_N (an fp32-only materialisation, mld_condense_device_f32, fills d_out32 alone)
     CondLayout lay;
     DevBuf<double> d_blocks;     // n_models x blk_stride
     DevBuf<double> d_out[12];    // materialised matrices, each n_models x out_size[k]

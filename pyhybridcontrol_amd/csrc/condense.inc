@@ -915,7 +915,7 @@ int condense_model_device(mld_model *m, int N, double *kernel_ms, hipStream_t st
         HIP_TRY(m->d_blocks.alloc(m->lay.blk_stride * m->n_models));
         for (int k = 0; k < 12; ++k)
             if (m->lay.out_size[k]) HIP_TRY(m->d_out[k].alloc(m->lay.out_size[k] * m->n_models));
-        m->cond_N = N;
+        m->cond_N = N; m->out64 = false;
     }
     if (f32) for (int k = 0; k < 12; ++k) if (m->lay.out_size[k] && !m->d_out32[k]) HIP_TRY(m->d_out32[k].alloc(m->lay.out_size[k] * m->n_models));
     CondPtrs P;
@@ -949,6 +949,7 @@ int condense_model_device(mld_model *m, int N, double *kernel_ms, hipStream_t st
             HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
             if (kernel_ms) *kernel_ms = ms;
             (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+            m->out64 = true;
             return MLD_OK;
         }
         const size_t lds = condense_tv_lds(m->lay, m->pack_len);
@@ -963,6 +964,7 @@ int condense_model_device(mld_model *m, int N, double *kernel_ms, hipStream_t st
         HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
         if (kernel_ms) *kernel_ms = ms;
         (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        m->out64 = true;
         return MLD_OK;
     }
     HIP_TRY(hipEventRecord(e0, stream));
@@ -1014,5 +1016,6 @@ int condense_model_device(mld_model *m, int N, double *kernel_ms, hipStream_t st
     HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
     if (kernel_ms) *kernel_ms = ms;
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    if (!f32) m->out64 = true;
     return MLD_OK;
 }

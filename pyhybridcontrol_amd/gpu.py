@@ -334,6 +334,56 @@ class GpuProblem(object):
         check(_lib.load().mld_predict_batch(self._h, _lib.dptr(v), _lib.dptr(x) if x.shape[1] else None, _lib.dptr(y) if y.shape[1] else None))
         return dict(x=x, y=y)
 
+    def _column_arrays(self, omega_cols=None, col_rows=None, x_cols=None):
+        """validation columns in the layout of upload_constraint_blocks: (n_cols, omega_cols (batch, n_cols, N_tilde*nomega) or None, col_rows (n_cols) int32
+        or None, x_cols (batch, n_cols, nx) or None); ValueError on a shape that does not fit, before any C call"""
+        nx, nW, B = self.model.dims["nx"], self.nW, self.batch
+        if omega_cols is None and x_cols is None:
+            if col_rows is not None:
+                raise ValueError("col_rows given without columns (omega_cols / x_cols)")
+            return 0, None, None, None
+        n_cols = None
+        if omega_cols is not None:
+            omega_cols = np.asarray(omega_cols, dtype=np.float64)
+            if omega_cols.ndim != 3 or omega_cols.shape[0] != B or omega_cols.shape[2] != nW or omega_cols.shape[1] < 1:
+                raise ValueError("omega_cols has shape %s, expected (%d, n_cols, %d)" % (omega_cols.shape, B, nW))
+            n_cols = omega_cols.shape[1]
+        elif nW:
+            raise ValueError("x_cols given without omega_cols, but the model has a disturbance (expected omega_cols of shape (%d, n_cols, %d))" % (B, nW))
+        if x_cols is not None:
+            x_cols = np.asarray(x_cols, dtype=np.float64)
+            if nx == 0:
+                raise ValueError("x_cols has shape %s but the model has no state (nx = 0)" % (x_cols.shape,))
+            if x_cols.ndim != 3 or x_cols.shape[0] != B or x_cols.shape[2] != nx or x_cols.shape[1] != (n_cols or x_cols.shape[1]) or x_cols.shape[1] < 1:
+                raise ValueError("x_cols has shape %s, expected (%d, %s, %d)" % (x_cols.shape, B, n_cols if n_cols else "n_cols", nx))
+            n_cols = x_cols.shape[1]
+            x_cols = np.ascontiguousarray(x_cols)
+        if col_rows is not None:
+            cr = np.asarray(col_rows)
+            if cr.shape != (n_cols,) or not np.issubdtype(cr.dtype, np.integer):
+                raise ValueError("col_rows has shape %s and dtype %s, expected (%d,) integers" % (cr.shape, cr.dtype, n_cols))
+            col_rows = np.ascontiguousarray(cr, dtype=np.int32)
+        if omega_cols is not None:
+            omega_cols = np.ascontiguousarray(omega_cols) if nW else None
+        return n_cols, omega_cols, col_rows, x_cols
+
+    def evaluate(self, v=None, omega_cols=None, col_rows=None, x_cols=None):
+        """solution quality of the resident batch on device (mld_evaluate_batch), fp64 on the ORIGINAL rows: dict(obj, constr_vio, constr_row, int_vio,
+        bound_vio).  v=None: the last solve's plans (needs a finished solve of the current inputs; instances without a usable plan get NaN / -1);
+        v (batch, n) or (n,): these plans under the current x0 / omega.  Without columns the problem as posed (standard block and resident constraint
+        blocks): constr_vio / constr_row (batch,) the largest residual H_v v - h and a row that attains it.  With omega_cols (batch, n_cols,
+        N_tilde*nomega), col_rows (n_cols), x_cols (batch, n_cols, nx) -- the layout of upload_constraint_blocks -- the same per validation column,
+        (batch, n_cols); the resident blocks are neither used nor changed."""
+        v = self._plan_array(v)
+        n_cols, oc, cr, xc = self._column_arrays(omega_cols, col_rows, x_cols)
+        B = self.batch
+        shp = (B, n_cols) if n_cols else (B,)
+        out = dict(obj=np.zeros(B), constr_vio=np.zeros(shp), constr_row=np.zeros(shp, np.int32), int_vio=np.zeros(B), bound_vio=np.zeros(B))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None
+        check(_lib.load().mld_evaluate_batch(self._h, _lib.dptr(v), int(n_cols), _lib.dptr(oc), ip(cr), _lib.dptr(xc), _lib.dptr(out["obj"]),
+                                             _lib.dptr(out["constr_vio"]), ip(out["constr_row"]), _lib.dptr(out["int_vio"]), _lib.dptr(out["bound_vio"])))
+        return out
+
     def set_opts(self, **opts):
         """limits / tolerances of the existing problem (mld_problem_set_opts): MIPGap, NodeLimit, IterationLimit, gap_abs, cut
         rounds, reserved -- no rebuild, like the per-call solver kwargs of the reference's solve()"""
@@ -465,9 +515,10 @@ class GpuProblem(object):
         check(_lib.load().mld_download_telemetry(self._h, ip(lat), ip(rows), C.byref(rb)))
         return dict(latency_ns=lat, rows_updated=rows, row_bytes=int(rb.value))
 
-    def solve(self, x0, omega, model_idx=None, fixed_bin=None, omega_cols=None, col_rows=None, x_cols=None, warm_start=None, inst_cost=None, trajectories=False):
+    def solve(self, x0, omega, model_idx=None, fixed_bin=None, omega_cols=None, col_rows=None, x_cols=None, warm_start=None, inst_cost=None, trajectories=False, quality=False):
         """upload, solve, download.  inst_cost: dict(lin_v=..., lin_x=..., lin_y=...) of upload_instance_cost for this batch; trajectories=True adds
-        the predicted x / y of trajectories() to the result"""
+        the predicted x / y of trajectories() to the result; quality=True adds out["quality"], evaluate() of the plans just computed on the problem
+        as posed"""
         self.upload(x0, omega, model_idx, fixed_bin)
         if inst_cost:
             self.upload_instance_cost(**inst_cost)
@@ -480,6 +531,8 @@ class GpuProblem(object):
         out["stats"] = stats
         if trajectories:
             out.update(self.trajectories())
+        if quality:
+            out["quality"] = self.evaluate()
         return out
 
     # -- sub-tree hand-off ---------------------------------------------------------------------------
@@ -522,10 +575,11 @@ class GpuProblem(object):
         check(_lib.load().mld_handoff_stats(self._h, out))
         return dict(items=int(out[0]), given_up=int(out[1]), unfinished=int(out[2]), queue_full=int(out[3]))
 
-    def solve_handoff_device(self, x0, omega, model_idx=None, fixed_bin=None, first_nodes=None, sub_nodes=None, max_gen=8, max_children=64, max_tree=160, room_factor=0.0, donate=0, rounds=0, inst_cost=None, trajectories=False):
+    def solve_handoff_device(self, x0, omega, model_idx=None, fixed_bin=None, first_nodes=None, sub_nodes=None, max_gen=8, max_children=64, max_tree=160, room_factor=0.0, donate=0, rounds=0, inst_cost=None, trajectories=False, quality=False):
         """the batch with the hand-off inside ONE launch (set_handoff): upload, solve, download -- the merged results per instance plus `handoff`
         statistics.  The problem's own limits and the hand-off switch are restored afterwards.  inst_cost: as solve() (items use their source
-        instance's cost).  trajectories=True adds the predicted x / y of the merged plans (read before the resident batch is dropped)."""
+        instance's cost).  trajectories=True adds the predicted x / y of the merged plans, quality=True out["quality"] = evaluate() of them (both read before the
+        resident batch is dropped)."""
         keep_nodes = int(self.opts.max_nodes)
         try:
             if first_nodes is not None:
@@ -540,6 +594,8 @@ class GpuProblem(object):
             out["handoff"] = self.handoff_stats()
             if trajectories:
                 out.update(self.trajectories())
+            if quality:
+                out["quality"] = self.evaluate()
             return out
         finally:
             self.set_handoff(False)
