@@ -116,7 +116,9 @@ typedef enum {
     MLD_DBG_LAZY_START = 1 << 17,       /* a MIP start is evaluated lazily (round 3: only when the deepening passes end without an
                                            incumbent) instead of before the root LP (A/B) */
     MLD_DBG_NO_SWEEP = 1 << 19,         /* no closing sweep before the in-kernel hand-off publishes a stopped search's open nodes */
-    MLD_DBG_ASSERT_POSCTL = 1 << 20     /* positive control of the assertion build (-DMLD_ASSERT): one index check fails */
+    MLD_DBG_ASSERT_POSCTL = 1 << 20,    /* positive control of the assertion build (-DMLD_ASSERT): one index check fails */
+    MLD_DBG_NO_PIVOT_PAIRS = 1 << 21    /* every dual-simplex pivot updates the dictionary on its own instead of two consecutive pivots sharing
+                                           one pass (A/B on the same binary: results are bit-identical, only rows_updated and speed change) */
 } mld_reserved_bit;
 
 /* Linear cost in tiled horizon form (the Python layer parses the reference's string-keyed atoms,

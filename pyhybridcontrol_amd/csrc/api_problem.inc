@@ -477,6 +477,12 @@ static int build_shape(mld_problem *p)
     S.mir_cap = p->mir_cap; S.lMirLine = -1;
     if (p->mir_cap > 0 && p->mir_cap < n) S.lMirLine = ltake(sizeof(double) * SOL_NW * 2 * p->mir_cap, 9);  /* compact lines of the c-MIR scoring (a row's free binaries) */
     S.lMirCache = ltake(sizeof(double) * SOL_NW * 2 * n, 10);                                              /* full-width lines (Gomory rounds): LDS while it fits */
+    /* Buffers of the second pivot of a fused pair (s_pivot_pair): row, multiplier column, union lists, sector flags.  They need no bytes of their own: the per-wave
+     * lines of lMirCache are scratch of the cut rounds and dead while the dual simplex runs, so the pair's buffers lie over them when every hot array is in LDS. */
+    {
+        const bool all_lds = S.lXB >= 0 && S.lXN >= 0 && S.lLo >= 0 && S.lHi >= 0 && S.lBasic >= 0 && S.lNonbasic >= 0 && S.lAtUp >= 0 && S.lSkip >= 0 && S.lDw >= 0 && S.lCost >= 0;
+        S.lPair = (all_lds && S.lMirCache >= 0 && pair_lds_bytes(S.n, S.mcap) <= sizeof(double) * SOL_NW * 2 * n) ? S.lMirCache : -1;
+    }
     p->lds_bytes = loff;
     return MLD_OK;
 }
@@ -1522,14 +1528,15 @@ int mld_debug_profile(mld_problem_t *p, int64_t out[8])
 
 /* the solver's shape (internal diagnostics; not part of the public header): [0..7] n, m0, mcap, first_cap, ld, mir_cap, lds_bytes, ws_stride;
  * [8..19] the LDS byte offsets (-1: in the slot) lXB, lBasic, lSkip, lAtUp, lNonbasic, lXN, lLo, lHi, lDw, lCost, lMirLine, lMirCache;
- * [20] the LDS budget of the hot arrays, [21] the MLD_SOL_SLOT mask (bit k: SLOT_NAMES[k]), [22] n_slots, [23] 0 */
+ * [20] the LDS budget of the hot arrays, [21] the MLD_SOL_SLOT mask (bit k: SLOT_NAMES[k]), [22] n_slots,
+ * [23] lPair: the LDS byte offset of the second pivot's buffers of a fused pair (over lMirCache), or -1: every pivot updates on its own */
 int mld_debug_shape(mld_problem_t *p, int64_t out[24])
 {
     if (!p || !out) { mld_set_error("mld_debug_shape: bad arguments"); return MLD_ERR_INVALID; }
     const SolverShape &S = p->S;
     const int64_t v[24] = {S.n, S.m0, S.mcap, S.first_cap, S.ld, S.mir_cap, (int64_t)p->lds_bytes, (int64_t)S.ws_stride,
                            S.lXB, S.lBasic, S.lSkip, S.lAtUp, S.lNonbasic, S.lXN, S.lLo, S.lHi, S.lDw, S.lCost, S.lMirLine, S.lMirCache,
-                           (int64_t)SOL_LDS_BUDGET, (int64_t)p->slot_mask, p->n_slots, 0};
+                           (int64_t)SOL_LDS_BUDGET, (int64_t)p->slot_mask, p->n_slots, S.lPair};
     for (int k = 0; k < 24; ++k) out[k] = v[k];
     return MLD_OK;
 }

@@ -86,8 +86,18 @@ struct SolverShape {
     // hot per-basis state kept in LDS when it fits (byte offsets into the dynamic LDS block, -1 = stays in the slot)
     int lLo, lHi, lXB, lXN, lBasic, lNonbasic, lAtUp, lSkip;
     int seccap;                  // entries of the LDS sector list (>= mcap + 8 and >= number of update sectors)
+    int lPair;                   // byte offset of the second pivot's staging buffers in LDS (s_bind_slot; they share the bytes of lMirCache, which
+                                 // only the cut rounds use), or -1: every pivot updates the dictionary on its own (s_dual_simplex_impl)
     long long time_ticks;        // per-instance budget in wall_clock64 ticks (mld_opts.time_limit; 0 = none): ends the search like max_nodes does
 };
+
+// LDS bytes of the second pivot's buffers, in the order s_bind_slot lays them out: the pivot row (n + 2 doubles), the multiplier column (it stages the
+// eligible |a| of the look-ahead ratio test first: max(mcap, n) + 2 doubles), the union row and sector lists, one flag byte per update sector
+__host__ __device__ inline size_t pair_lds_bytes(int n, int mcap)
+{
+    const size_t nsec = (size_t)(n + 8) / 8;
+    return sizeof(double) * ((size_t)n + 2 + (size_t)(mcap > n ? mcap : n) + 2) + sizeof(unsigned short) * ((size_t)mcap + 8 + nsec + 8) + nsec + 8;
+}
 
 struct ProblemDev {               // per-problem read-only device data (per model arrays are n_models x ...)
     const double *Gs;             // m0 x n scaled constraint matrix (tightened model)
@@ -232,6 +242,7 @@ typedef double double2_t __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) double lds_f64;
 typedef __attribute__((address_space(3))) double2_t lds_f64x2;
 typedef __attribute__((address_space(3))) unsigned short lds_u16;
+typedef __attribute__((address_space(3))) unsigned char lds_u8;
 typedef __attribute__((address_space(1))) double glb_f64;
 typedef __attribute__((address_space(1))) double2_t glb_f64x2;
 
@@ -420,6 +431,9 @@ struct Ws {
     unsigned short *seclist; // LDS: active 64-byte sectors of the pivot row
     unsigned short *rowlist; // LDS: rows with a non-zero multiplier
     double *dabuf;           // LDS: n doubles (ratio-test staging)
+    // second pivot of a fused pair (SolverShape::lPair; null / 0 when the shape has no room): its row and multiplier column, the union lists of the
+    // fused update and, per update sector, bit 0 = active in the first pivot's row, bit 1 = in the second's
+    double *rowr2, *colc2; unsigned short *rowlist2, *seclist2; unsigned char *secflag; int pair;
     const double *P;         // scaled Hessian of this instance's model (null = LP)
     double *Y, *PY, *Hm, *cm, *wm, *gcost, *vcur, *Pv, *mq;
     double *mir_eff, *mir_delta;     // m0: best c-MIR efficacy / divisor per original row
@@ -461,6 +475,13 @@ __device__ __forceinline__ void s_bind_slot(Ws &w, const SolverShape &S, unsigne
     w.seclist = (unsigned short *)(lds + (S.n + 2) + (S.mcap + 2) + (S.n + 2));
     w.rowlist = w.seclist + S.seccap;
     unsigned char *lb8 = (unsigned char *)lds;
+    w.pair = S.lPair >= 0 && !(S.debug & MLD_DBG_NO_PIVOT_PAIRS);
+    w.rowr2 = w.colc2 = nullptr; w.rowlist2 = w.seclist2 = nullptr; w.secflag = nullptr;
+    if (S.lPair >= 0) {      // (pair_lds_bytes)
+        w.rowr2 = (double *)(lb8 + S.lPair); w.colc2 = w.rowr2 + (S.n + 2);
+        w.rowlist2 = (unsigned short *)(w.colc2 + ((S.mcap > S.n ? S.mcap : S.n) + 2)); w.seclist2 = w.rowlist2 + (S.mcap + 8);
+        w.secflag = (unsigned char *)(w.seclist2 + ((S.n + 8) / 8 + 8));
+    }
     if (S.lXB >= 0) w.xB = (double *)(lb8 + S.lXB); if (S.lXN >= 0) w.xN = (double *)(lb8 + S.lXN); if (S.lLo >= 0) w.lo = (double *)(lb8 + S.lLo);
     if (S.lHi >= 0) w.hi = (double *)(lb8 + S.lHi); if (S.lBasic >= 0) w.basic = (int *)(lb8 + S.lBasic); if (S.lNonbasic >= 0) w.nonbasic = (int *)(lb8 + S.lNonbasic);
     if (S.lAtUp >= 0) w.at_upper = lb8 + S.lAtUp; if (S.lSkip >= 0) w.skip = lb8 + S.lSkip; if (S.lDw >= 0) w.dw = (double *)(lb8 + S.lDw);
@@ -875,6 +896,10 @@ __device__ void s_set_bounds_list(const Ws &w, Shared &sh, const int *js, const 
 #endif
 #define SOL_LPS (SOL_SEC / 2) // lanes per sector (16 bytes each)
 #define SOL_SPW (64 / SOL_LPS) // sectors per wave instruction
+// One element of the rank-1 update, o - mu * rr, as ONE fused multiply-add.  The update of the rows (s_update_rows, s_update_rows2), the look-ahead's ratio-test row
+// (s_look_ahead) and the second pivot's multiplier column (s_pivot_head) all go through here: an entry has the same bits whichever of them computes it.
+__device__ __forceinline__ double s_upd(double o, double mu, double rr) { return __builtin_fma(-mu, rr, o); }
+
 template <int NG>
 __device__ __forceinline__ void s_update_rows(glb_f64 *D, int ld, const lds_f64 *rowr, const lds_f64 *colc, const lds_u16 *rowlist,
                                               const lds_u16 *seclist, int nrows, int nact, int g0, int c, int wave, int lane)
@@ -913,7 +938,7 @@ __device__ __forceinline__ void s_update_rows(glb_f64 *D, int ld, const lds_f64 
                         double2_t o = v[q][g];
                         if (cx[g]) o.x = 0.0;
                         if (cy[g]) o.y = 0.0;
-                        o = o - mu * rr[g];
+                        o.x = s_upd(o.x, mu, rr[g].x); o.y = s_upd(o.y, mu, rr[g].y);
                         *(glb_f64x2 *)(base + koff[g]) = o;
                     }
             }
@@ -921,21 +946,94 @@ __device__ __forceinline__ void s_update_rows(glb_f64 *D, int ld, const lds_f64 
     }
 }
 
-// the rank-1 update: entering column c, leaving row r, leaving variable goes to leave_value
-template <bool L>
-__device__ __forceinline__ void s_pivot_inl(const Ws &w, Shared &sh, int r, int c, double leave_value)
+// The updates of TWO consecutive pivots in one pass (s_pivot_pair): rows `rowlist` (the union of both pivots' rows, without the second pivot's row) on the sectors
+// `seclist` (the union of both pivot rows' active sectors; secflag[sector] bit 0 = active in the first row, bit 1 = in the second).  A (row, sector) pair is loaded
+// once, takes the first pivot's update if the row has a non-zero first multiplier and the sector is active in the first row, then the second pivot's likewise -- each
+// with its own entering column counted as 0 -- and is stored once; a pair that belongs to neither pivot is not touched.  Every element goes through the same
+// operations in the same order as in two separate passes.
+template <int NG>
+__device__ __forceinline__ void s_update_rows2(glb_f64 *D, int ld, const lds_f64 *rowr1, const lds_f64 *colc1, const lds_f64 *rowr2, const lds_f64 *colc2,
+                                               const lds_u16 *rowlist, const lds_u16 *seclist, const lds_u8 *secflag, int nrows, int nact, int g0,
+                                               int r1, int c1, int c2, int wave, int lane)
+{
+    constexpr int RB = (NG <= 2 ? 16 : (NG == 3 ? 10 : 8)) / (SOL_WPE / 2);
+    const int sub = lane / SOL_LPS, pr = (lane % SOL_LPS) * 2;
+    int koff[NG]; bool a1[NG], a2[NG], cx1[NG], cy1[NG], cx2[NG], cy2[NG]; double2_t rr1[NG], rr2[NG];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        const int si = (g0 + g) * SOL_SPW + sub;
+        const bool ok = si < nact;
+        const int sec = ok ? (int)seclist[si] : 0;
+        const int fl = ok ? (int)secflag[sec] : 0;
+        a1[g] = (fl & 1) != 0; a2[g] = (fl & 2) != 0;
+        koff[g] = sec * SOL_SEC + pr;
+        rr1[g] = a1[g] ? *(const lds_f64x2 *)(rowr1 + koff[g]) : (double2_t){0.0, 0.0};
+        rr2[g] = a2[g] ? *(const lds_f64x2 *)(rowr2 + koff[g]) : (double2_t){0.0, 0.0};
+        cx1[g] = koff[g] == c1; cy1[g] = koff[g] + 1 == c1;
+        cx2[g] = koff[g] == c2; cy2[g] = koff[g] + 1 == c2;
+    }
+    for (int b = wave * RB; b < nrows; b += SOL_NW * RB) {
+        double2_t v[RB][NG];
+        int rowi[RB], rowf[RB];      // row and (wave-uniform) bit 0: it takes the first update, bit 1: the second
+#pragma unroll
+        for (int q = 0; q < RB; ++q) {
+            rowi[q] = b + q < nrows ? __builtin_amdgcn_readfirstlane((int)rowlist[b + q]) : -1;
+            rowf[q] = 0;
+            if (rowi[q] >= 0) {
+                // (the first pivot's own row holds the pivot element in colc1, not a multiplier: it takes the second update only)
+                rowf[q] = __builtin_amdgcn_readfirstlane((int)(rowi[q] != r1 && colc1[rowi[q]] != 0.0) | ((int)(colc2[rowi[q]] != 0.0) << 1));
+                const bool f1 = rowf[q] & 1, f2 = rowf[q] & 2;
+                const glb_f64 *base = D + (size_t)rowi[q] * ld;
+#pragma unroll
+                for (int g = 0; g < NG; ++g) v[q][g] = ((f1 && a1[g]) || (f2 && a2[g])) ? *(const glb_f64x2 *)(base + koff[g]) : (double2_t){0.0, 0.0};
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < RB; ++q) {
+            if (rowi[q] >= 0) {
+                const bool f1 = rowf[q] & 1, f2 = rowf[q] & 2;
+                const double mu1 = colc1[rowi[q]], mu2 = colc2[rowi[q]];
+                glb_f64 *base = D + (size_t)rowi[q] * ld;
+#pragma unroll
+                for (int g = 0; g < NG; ++g) {
+                    const bool u1 = f1 && a1[g], u2 = f2 && a2[g];
+                    if (u1 || u2) {
+                        double2_t o = v[q][g];
+                        if (u1) {
+                            if (cx1[g]) o.x = 0.0;
+                            if (cy1[g]) o.y = 0.0;
+                            o.x = s_upd(o.x, mu1, rr1[g].x); o.y = s_upd(o.y, mu1, rr1[g].y);
+                        }
+                        if (u2) {
+                            if (cx2[g]) o.x = 0.0;
+                            if (cy2[g]) o.y = 0.0;
+                            o.x = s_upd(o.x, mu2, rr2[g].x); o.y = s_upd(o.y, mu2, rr2[g].y);
+                        }
+                        *(glb_f64x2 *)(base + koff[g]) = o;
+                    }
+                }
+            }
+        }
+    }
+}
+
+// First half of a pivot (entering column c, leaving row r, leaving variable goes to leave_value): everything but the update of the other rows.  The multiplier column
+// and the pivot row are staged in LDS (colc, rowr); the row is scaled (LDS and dictionary); x_B, the devex weights, the cost row and the basis maps move on.  All of
+// that reads only the staged row and column and the small per-basis arrays, so the update of the other rows is the LAST thing a pivot does (s_pivot_inl) and the
+// next pivot can be chosen before it (s_pivot_pair).
+// SECOND: the pivot follows one whose row update has not been done yet (its row r1 and column c1 are staged in w.rowr / w.colc, w.secflag bit 0 marks its active
+// sectors).  rowr already holds row r as that update leaves it (s_look_ahead); the column's entries get the same correction.
+template <bool L, bool SECOND>
+__device__ __forceinline__ void s_pivot_head(const Ws &w, Shared &sh, int r, int c, double leave_value, lds_f64 *rowr, lds_f64 *colc, int r1, int c1)
 {
     HOT_VIEW(L, w);
-    const int n = w.n, ld = w.ld, m = sh.m, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const long long tp0 = wall_clock64();
+    const int n = w.n, ld = w.ld, m = sh.m, tid = threadIdx.x;
     glb_f64 *D = (glb_f64 *)w.D;
     glb_f64 *rowr_g = D + (size_t)r * ld;
-    lds_f64 *rowr = (lds_f64 *)w.rowr, *colc = (lds_f64 *)w.colc;
-    lds_u16 *seclist = (lds_u16 *)w.seclist, *rowlist = (lds_u16 *)w.rowlist;
     MLD_CHECK(w, r >= 0 && r < m && c >= 0 && c < n && m <= w.mcap, 101, r, c);
     __syncthreads();
     // stage multiplier column and the pivot row in LDS (raw first: the pivot element is read back from LDS)
-    {   // (rows that can never bind are not maintained: multiplier 0.)  All loads of both gathers are issued before the first LDS store: the
+    if (!SECOND) {   // (rows that can never bind are not maintained: multiplier 0.)  All loads of both gathers are issued before the first LDS store: the
         // column gather is one 64-byte sector per element and each dependent round costs a full memory latency
         const int span = (m > n + 1 ? m : n + 1);
         for (int b0 = 0; b0 < span; b0 += 4 * SOL_NT) {
@@ -951,6 +1049,30 @@ __device__ __forceinline__ void s_pivot_inl(const Ws &w, Shared &sh, int r, int 
                 const int i = b0 + q * SOL_NT + tid;
                 if (i < m) colc[i] = cv[q];
                 if (i <= n) rowr[i] = rv[q];
+            }
+        }
+    } else {
+        const lds_f64 *rowr1 = (const lds_f64 *)w.rowr, *colc1 = (const lds_f64 *)w.colc;
+        const bool act1 = (((const lds_u8 *)w.secflag)[c / SOL_SEC] & 1) != 0;      // the pending update touches column c (of the rows with a non-zero multiplier)
+        const double rr = rowr1[c];
+        for (int b0 = 0; b0 < m; b0 += 4 * SOL_NT) {
+            double cv[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int i = b0 + q * SOL_NT + tid;
+                cv[q] = (i < m && !(h_skip[i] & 2)) ? D[(size_t)i * ld + c] : 0.0;
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int i = b0 + q * SOL_NT + tid;
+                if (i >= m) continue;
+                double v = cv[q];
+                if (i == r1) v = rr;                                  // the first pivot's row is the scaled row
+                else {
+                    const double mu = colc1[i];                       // (0 for a row that is not maintained)
+                    if (act1 && mu != 0.0) v = s_upd(c == c1 ? 0.0 : v, mu, rr);
+                }
+                colc[i] = v;
             }
         }
     }
@@ -972,6 +1094,37 @@ __device__ __forceinline__ void s_pivot_inl(const Ws &w, Shared &sh, int r, int 
         else if (ci != 0.0) { const double f = ci * inv, c2 = f * f * wr; if (c2 > h_dw[i]) h_dw[i] = c2; }
     }
     __syncthreads();
+    {   // cost row: obj = d[n] + sum_c d_c xN_c
+        typename HotT<L>::f64p d = h_d;    // LDS when it fits (SolverShape::lCost), else the row after the last dictionary row
+        const double dc = d[c];
+        if (tid == 0) sh.s_d[0] = dc * theta;      // objective change of this pivot (entering variable moves by theta)
+        __syncthreads();
+        if (dc != 0.0) {
+            for (int k = tid; k < n; k += SOL_NT) d[k] = (k == c) ? -dc * inv : d[k] - dc * rowr[k];
+            if (tid == 0) d[n] += dc * rowr[n];
+        }
+    }
+    if (tid == 0) {
+        const int jb = h_basic[r], jn = h_nonbasic[c];
+        MLD_CHECK(w, jb >= 0 && jb < n + w.mcap && jn >= 0 && jn < n + w.mcap, 109, jb, jn);
+        h_basic[r] = jn; h_nonbasic[c] = jb;
+        w.where[jn] = -1 - r; w.where[jb] = c;
+        h_xB[r] = enter_val;
+        h_xN[c] = leave_value;
+        h_up[c] = (leave_value == h_hi[jb]) && (h_lo[jb] != h_hi[jb]);
+        sh.pivots++; sh.since_check++;
+    }
+    __syncthreads();
+}
+
+// Second half of a pivot whose first half s_pivot_head<L, false> has staged in w.rowr / w.colc: rows with a non-zero multiplier -= multiplier * (scaled pivot row) on
+// the row's active sectors
+__device__ __forceinline__ void s_pivot_update(const Ws &w, Shared &sh, int r, int c, long long tp0)
+{
+    const int n = w.n, ld = w.ld, m = sh.m, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    glb_f64 *D = (glb_f64 *)w.D;
+    lds_f64 *rowr = (lds_f64 *)w.rowr, *colc = (lds_f64 *)w.colc;
+    lds_u16 *seclist = (lds_u16 *)w.seclist, *rowlist = (lds_u16 *)w.rowlist;
 #ifdef MLD_PIVOT_PROF
     const long long tq1 = wall_clock64();
 #endif
@@ -1018,37 +1171,24 @@ __device__ __forceinline__ void s_pivot_inl(const Ws &w, Shared &sh, int r, int 
             default: s_update_rows<4>(D, ld, rowr, colc, rowlist, seclist, nrows, nact, g0, c, wave, lane); break;
             }
         }
-        if (tid == 0) sh.rows += (unsigned long long)nrows * (unsigned long long)nact;   // 64-byte sectors updated
-    }
-#ifdef MLD_PIVOT_PROF
-    __syncthreads();
-    const long long tq4 = wall_clock64();
-#endif
-    {   // cost row: obj = d[n] + sum_c d_c xN_c
-        typename HotT<L>::f64p d = h_d;    // LDS when it fits (SolverShape::lCost), else the row after the last dictionary row
-        const double dc = d[c];
-        if (tid == 0) sh.s_d[0] = dc * theta;      // objective change of this pivot (entering variable moves by theta)
-        __syncthreads();
-        if (dc != 0.0) {
-            for (int k = tid; k < n; k += SOL_NT) d[k] = (k == c) ? -dc * inv : d[k] - dc * rowr[k];
-            if (tid == 0) d[n] += dc * rowr[n];
-        }
     }
     if (tid == 0) {
-        const int jb = h_basic[r], jn = h_nonbasic[c];
-        MLD_CHECK(w, jb >= 0 && jb < n + w.mcap && jn >= 0 && jn < n + w.mcap, 109, jb, jn);
-        h_basic[r] = jn; h_nonbasic[c] = jb;
-        w.where[jn] = -1 - r; w.where[jb] = c;
-        h_xB[r] = enter_val;
-        h_xN[c] = leave_value;
-        h_up[c] = (leave_value == h_hi[jb]) && (h_lo[jb] != h_hi[jb]);
-        sh.pivots++; sh.since_check++;
+        sh.rows += (unsigned long long)nrows * (unsigned long long)nact;   // 64-byte sectors updated
         sh.prof[0] += wall_clock64() - tp0;
 #ifdef MLD_PIVOT_PROF
-        sh.pprof[0] += tq1 - tp0; sh.pprof[1] += tq2 - tq1; sh.pprof[2] += tq3 - tq2; sh.pprof[3] += tq4 - tq3; sh.pprof[4] += wall_clock64() - tq4;
+        sh.pprof[0] += tq1 - tp0; sh.pprof[1] += tq2 - tq1; sh.pprof[2] += tq3 - tq2; sh.pprof[3] += wall_clock64() - tq3;      // ([0] now holds the cost row and the bookkeeping too)
 #endif
     }
     __syncthreads();
+}
+
+// the rank-1 update: entering column c, leaving row r, leaving variable goes to leave_value
+template <bool L>
+__device__ __forceinline__ void s_pivot_inl(const Ws &w, Shared &sh, int r, int c, double leave_value)
+{
+    const long long tp0 = wall_clock64();
+    s_pivot_head<L, false>(w, sh, r, c, leave_value, (lds_f64 *)w.rowr, (lds_f64 *)w.colc, -1, -1);
+    s_pivot_update(w, sh, r, c, tp0);
 }
 
 // out-of-line copy for the cold callers (refactor, primal simplex)
@@ -1296,6 +1436,186 @@ __device__ int s_unperturb(const Ws &w, Shared &sh, int st, int max_pivots)
     return ps == LP_OPTIMAL ? LP_OPTIMAL : LP_ITERLIMIT;
 }
 
+// The NEXT iteration's choice of s_dual_simplex_impl, made before the rows' update of the pivot (r1, c1) whose first half has just run: devex pricing on the x_B,
+// weights, bounds and maps that pivot left behind, then the Harris ratio test on row r2 as the pending update will leave it -- D[r2, k] - colc1[r2] * rowr1[k]
+// through s_upd on the first row's active sectors, the old entry of column c1 counting as 0, exactly as s_update_rows does it; the scaled first row itself if
+// r2 == r1.  The raw row goes to w.rowr2 (k <= n), the eligible |a| to w.colc2, the clamped reduced costs to w.dabuf.  True (with r2, c2 and the leaving variable's
+// target) when that iteration is a plain pivot; false when it does anything else (optimal, cut off, no eligible entry, a row to skip): the caller then finishes the
+// first pivot alone and the loop makes that iteration as ever.  Only scratch is written.  Every thread returns the same.
+template <bool L>
+__device__ __forceinline__ bool s_look_ahead(const Ws &w, Shared &sh, int r1, int c1, double cur, double cutoff, int &par, int &r2, int &c2, double &lv2)
+{
+    HOT_VIEW(L, w);
+    const int n = w.n, ld = w.ld, m = sh.m, tid = threadIdx.x;
+    double myv = -S_INF; int myi = -1;
+    for (int i = tid; i < m; i += SOL_NT) {
+        if (h_skip[i]) continue;
+        const int j = h_basic[i];
+        const double v = fmax(h_lo[j] - h_xB[i], h_xB[i] - h_hi[j]);
+        if (v > S_PTOL) {
+            const double sc = v * v / h_dw[i];
+            if (sc > myv) { myv = sc; myi = i; }
+        }
+    }
+    double worst;
+    const int r = block_argmax1(sh, myv, myi, &worst, par);
+    if (r < 0) return false;
+    if (cur >= cutoff && !sh.perturbed) return false;
+    MLD_CHECK(w, r < m, 105, r, 2);
+    const int jr = h_basic[r];
+    const double vlo = h_lo[jr] - h_xB[r], vhi = h_xB[r] - h_hi[jr];
+    const bool below = vlo > vhi;
+    const double viol = below ? vlo : vhi;
+    const glb_f64 *row = (const glb_f64 *)(w.D + (size_t)r * ld);
+    const lds_f64 *rowr1 = (const lds_f64 *)w.rowr, *colc1 = (const lds_f64 *)w.colc;
+    const lds_u8 *sf = (const lds_u8 *)w.secflag;
+    lds_f64 *raw = (lds_f64 *)w.rowr2, *ea = (lds_f64 *)w.colc2, *dal = (lds_f64 *)w.dabuf;
+    const bool same = r == r1;
+    const double mu = colc1[r];
+    double emax = 0.0;
+    for (int c0 = 0; c0 <= n; c0 += 4 * SOL_NT) {
+        double av[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { const int c = c0 + q * SOL_NT + tid; av[q] = (c <= n && !same) ? row[c] : 0.0; }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int c = c0 + q * SOL_NT + tid;
+            if (c > n) continue;
+            double a;
+            if (same) a = rowr1[c];
+            else {
+                a = av[q];
+                if (mu != 0.0 && (sf[c / SOL_SEC] & 1)) a = s_upd(c == c1 ? 0.0 : a, mu, rowr1[c]);
+            }
+            raw[c] = a;
+            if (c == n) continue;
+            const int j = h_nonbasic[c];
+            MLD_CHECK(w, j >= 0 && j < n + w.mcap, 111, c, j);
+            const bool up = h_up[c];
+            const bool el = (h_lo[j] != h_hi[j]) && (below ? (up ? a > 0 : a < 0) : (up ? a < 0 : a > 0));
+            const double aa = el ? fabs(a) : 0.0;
+            const double dv = h_d[c];
+            ea[c] = aa;
+            dal[c] = fmax(up ? -dv : dv, 0.0);
+            emax = fmax(emax, aa);
+        }
+    }
+    emax = block_max1(sh, emax, par);
+    const double ptol = fmax(S_PIV_ABS, S_PIV_REL * emax);
+    double tmax = S_INF;
+    for (int c = tid; c < n; c += SOL_NT) {
+        const double aa = ea[c];
+        if (aa <= ptol) continue;
+        tmax = fmin(tmax, (dal[c] + S_DTOL) / aa);
+    }
+    tmax = block_min1(sh, tmax, par);
+    if (tmax == S_INF) return false;
+    double bv = -1.0; int bi = -1;
+    for (int c = tid; c < n; c += SOL_NT) {
+        const double aa = ea[c];
+        if (aa <= ptol) continue;
+        if (dal[c] / aa <= tmax && aa > bv) { bv = aa; bi = c; }
+    }
+    double tmp;
+    const int cbest = block_argmax1(sh, bv, bi, &tmp, par);
+    if (cbest < 0) return false;
+    MLD_CHECK(w, cbest < n, 106, cbest, 2);
+    if (ea[cbest] < S_PIV_TINY && viol <= S_PTOL_SKIP) return false;
+    r2 = r; c2 = cbest; lv2 = below ? h_lo[jr] : h_hi[jr];
+    return true;
+}
+
+// A pivot of s_dual_simplex_impl and, when it is a plain one (try_pair: devex pricing, Harris ratio test; all hot arrays in LDS) and the loop's next iteration is one too, that pivot with it:
+// two consecutive dual pivots of a dive or a re-solve repair the same few horizon steps, so most (row, sector) pairs of the second update are pairs of the first.
+// After the first pivot's first half the next iteration is made on what it left in LDS (s_look_ahead), the second pivot's first half runs on corrected entries
+// (s_pivot_head<L, true>), and ONE pass over the union of the two updates applies both in order (s_update_rows2): a shared pair is read and written once.  Nothing is
+// left pending: on return the dictionary is fully updated.  Whatever the loop would do between the two pivots besides counting a stall -- a limit, the deadline, a
+// verification, the perturbation, Bland's rule -- means no pair: the first pivot is finished alone (s_pivot_update) and the loop goes on unchanged.  cur, stall and
+// last_obj leave as two iterations would leave them.
+template <bool L>
+__device__ __forceinline__ void s_pivot_pair(const Ws &w, Shared &sh, int r1, int c1, double lv1, bool try_pair, double cutoff, int max_pivots, double &cur,
+                                             int &stall, double &last_obj, int &par)
+{
+    const long long tp0 = wall_clock64();
+    const int n = w.n, ld = w.ld, m = sh.m, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int nsec = (n + SOL_SEC) / SOL_SEC;
+    lds_f64 *rowr = (lds_f64 *)w.rowr, *colc = (lds_f64 *)w.colc, *rowr2 = (lds_f64 *)w.rowr2, *colc2 = (lds_f64 *)w.colc2;
+    lds_u8 *secflag = (lds_u8 *)w.secflag;
+    s_pivot_head<L, false>(w, sh, r1, c1, lv1, rowr, colc, -1, -1);
+    cur += sh.s_d[0];
+    // the top of the loop's next iteration
+    const int piv = sh.pivots;
+    bool go = try_pair && piv < max_pivots && !(sh.deadline && (piv & 127) == 127) && sh.since_check < 512;
+    int stall2 = stall; double last2 = last_obj;
+    if (cur > last2 + 1e-12 * fmax(1.0, fabs(cur))) { stall2 = 0; last2 = cur; } else stall2++;
+    go = go && stall2 <= 30;
+    int r2 = -1, c2 = -1; double lv2 = 0.0;
+    if (go) {
+        for (int t = tid; t < nsec; t += SOL_NT) {      // active sectors of the first pivot's row (s_look_ahead's first barrier comes before its first use)
+            bool act = false;
+#pragma unroll
+            for (int e = 0; e < SOL_SEC; ++e) { const int k = t * SOL_SEC + e; if (k <= n && rowr[k] != 0.0) act = true; }
+            secflag[t] = act ? 1 : 0;
+        }
+        go = s_look_ahead<L>(w, sh, r1, c1, cur, cutoff, par, r2, c2, lv2);
+    }
+    if (!go) { s_pivot_update(w, sh, r1, c1, tp0); return; }
+    stall = stall2; last_obj = last2;
+    s_pivot_head<L, true>(w, sh, r2, c2, lv2, rowr2, colc2, r1, c1);
+    cur += sh.s_d[0];
+    // union of the two rows' active sectors and of the two row sets (ordered); the counts of each set and of the overlaps, packed into one exact double
+    int nact = 0; double cnt_s = 0.0;
+    for (int t0 = 0; t0 < nsec; t0 += SOL_NT) {
+        const int t = t0 + tid;
+        int f = 0;
+        if (t < nsec) {
+            bool act = false;
+#pragma unroll
+            for (int e = 0; e < SOL_SEC; ++e) { const int k = t * SOL_SEC + e; if (k <= n && rowr2[k] != 0.0) act = true; }
+            f = (secflag[t] & 1) | (act ? 2 : 0);
+            secflag[t] = (unsigned char)f;
+        }
+        cnt_s += (double)(f & 1) + 65536.0 * (double)(f >> 1) + 4294967296.0 * (double)(f == 3);
+        nact = block_compact(sh, f != 0, (unsigned short)t, w.seclist2, nact);
+    }
+    int nrows = 0; double cnt_r = 0.0;
+    for (int i0 = 0; i0 < m; i0 += SOL_NT) {
+        const int i = i0 + tid;
+        const bool in1 = i < m && i != r1 && i != r2 && colc[i] != 0.0, in2 = i < m && i != r2 && colc2[i] != 0.0;
+        cnt_r += (double)in1 + 65536.0 * (double)in2 + 4294967296.0 * (double)(in1 && in2);
+        nrows = block_compact(sh, in1 || in2, (unsigned short)i, w.rowlist2, nrows);
+    }
+    cnt_s = block_sum(sh, cnt_s);
+    cnt_r = block_sum(sh, cnt_r);
+    __syncthreads();
+    const lds_u16 *seclist = (const lds_u16 *)w.seclist2, *rowlist = (const lds_u16 *)w.rowlist2;
+#ifdef MLD_ASSERT
+    MLD_CHECK(w, nact <= nsec && nrows < m, 102, nact, nrows);
+    for (int t = tid; t < nrows; t += SOL_NT) MLD_CHECK(w, (int)rowlist[t] < m && (int)rowlist[t] != r2, 103, t, rowlist[t]);
+    for (int t = tid; t < nact; t += SOL_NT) MLD_CHECK(w, (int)seclist[t] < nsec, 104, t, seclist[t]);
+#endif
+    {
+        glb_f64 *D = (glb_f64 *)w.D;
+        const int ngrp = (nact + SOL_SPW - 1) / SOL_SPW;
+        for (int g0 = 0; g0 < ngrp; g0 += 4) {
+            switch (ngrp - g0) {
+            case 1: s_update_rows2<1>(D, ld, rowr, colc, rowr2, colc2, rowlist, seclist, secflag, nrows, nact, g0, r1, c1, c2, wave, lane); break;
+            case 2: s_update_rows2<2>(D, ld, rowr, colc, rowr2, colc2, rowlist, seclist, secflag, nrows, nact, g0, r1, c1, c2, wave, lane); break;
+            case 3: s_update_rows2<3>(D, ld, rowr, colc, rowr2, colc2, rowlist, seclist, secflag, nrows, nact, g0, r1, c1, c2, wave, lane); break;
+            default: s_update_rows2<4>(D, ld, rowr, colc, rowr2, colc2, rowlist, seclist, secflag, nrows, nact, g0, r1, c1, c2, wave, lane); break;
+            }
+        }
+    }
+    if (tid == 0) {
+        // 64-byte sectors moved: |R1 x S1| + |R2 x S2| - |(R1 and R2) x (S1 and S2)|
+        const unsigned long long cs = (unsigned long long)cnt_s, cr = (unsigned long long)cnt_r;
+        const unsigned long long s1 = cs & 0xffffull, s2 = (cs >> 16) & 0xffffull, s12 = cs >> 32, n1 = cr & 0xffffull, n2 = (cr >> 16) & 0xffffull, n12 = cr >> 32;
+        sh.rows += n1 * s1 + n2 * s2 - n12 * s12;
+        sh.prof[0] += wall_clock64() - tp0;
+    }
+    __syncthreads();
+}
+
 template <bool L>
 __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double cutoff, int max_pivots)
 {
@@ -1451,6 +1771,7 @@ __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double 
         }
         // entering column
         int cbest;
+        bool long_step = false;
         if (bland) {
             rmin = block_min(sh, rmin);
             int key = 0x7fffffff, pay = -1;
@@ -1549,9 +1870,7 @@ __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double 
             if (cbest >= 0 && a_best < S_PIV_TINY && viol <= S_PTOL_SKIP && nflip_groups == 0) { __syncthreads(); if (tid == 0) h_skip[r] |= 1; continue; }
             if (cbest < 0) return s_unperturb(w, sh, LP_INFEASIBLE, max_pivots);
             MLD_CHECK(w, cbest < n, 106, cbest, 1);
-            s_pivot_inl<L>(w, sh, r, cbest, below ? h_lo[jr] : h_hi[jr]);
-            cur += sh.s_d[0];
-            continue;
+            long_step = true;      // (the guards below are the other branches'; the pivot itself is the common one)
         } else {
             double bv = -1.0; int bi = -1;
             for (int c = tid; c < n; c += SOL_NT) {
@@ -1564,14 +1883,15 @@ __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double 
         }
         if (cbest < 0) return s_unperturb(w, sh, LP_INFEASIBLE, max_pivots);   // cannot happen (tmax finite), kept as a guard
         MLD_CHECK(w, cbest < n, 106, cbest, 0);
-        if (ea[cbest] < S_PIV_TINY && viol <= S_PTOL_SKIP) {
+        if (!long_step && ea[cbest] < S_PIV_TINY && viol <= S_PTOL_SKIP) {
             // a violation within the skip tolerance whose only pivots are tiny: the dual step d_q / |a_q| would be huge and the
             // entries the ratio test ignored (|a| <= ptol) would carry it into their reduced costs -- dual feasibility, and with
             // it the bound, is lost (seen: violation 5e-8, pivot 1.7e-7, step 3e9).  The row counts as satisfied.
             __syncthreads(); if (tid == 0) h_skip[r] |= 1; continue;
         }
-        s_pivot_inl<L>(w, sh, r, cbest, below ? h_lo[jr] : h_hi[jr]);
-        cur += sh.s_d[0];
+        // the pivot, and the next one with it where both are plain (devex pricing and Harris test: not under Bland's rule, not in the root LP's long-step test, not with
+        // a quadratic cost) and the shape has the LDS for it
+        s_pivot_pair<L>(w, sh, r, cbest, below ? h_lo[jr] : h_hi[jr], L && w.pair && !bland && !long_step && !w.P, cutoff, max_pivots, cur, stall, last_obj, par);
     }
 }
 

@@ -482,7 +482,7 @@ class GpuProblem(object):
 
     _SHAPE_KEYS = ("n", "m0", "mcap", "first_cap", "ld", "mir_cap", "lds_bytes", "ws_stride",
                    "lXB", "lBasic", "lSkip", "lAtUp", "lNonbasic", "lXN", "lLo", "lHi", "lDw", "lCost", "lMirLine", "lMirCache",
-                   "lds_budget", "slot_mask", "n_slots")
+                   "lds_budget", "slot_mask", "n_slots", "lPair")
 
     def debug_shape(self):
         """diagnostics: the solver's shape as build_shape placed it (internal entry mld_debug_shape) -- dims, LDS bytes, and the LDS byte offset of

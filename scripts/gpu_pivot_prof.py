@@ -11,6 +11,6 @@ prob=gpu.GpuProblem(model, N_p, N_t, host.stack_costs([host.cost_from_atoms(a['a
 prob.upload(x0, om, midx); st=prob.solve_resident(); st=prob.solve_resident()
 out=(C.c_int64*8)(); _lib.load().mld_debug_profile(prob._h, out)
 t=np.array(list(out),dtype=float)
-names=['stage row/col','sector list','xB,row writeback,rowlist','update loop','cost row+bookkeeping']
+names=['stage row/col, xB, cost row, bookkeeping','sector list','row list','update loop','(unused)']      # single pivots only: a fused pair (s_pivot_pair) is not split -- run with opts.reserved bit 21
 print('solve_ms',st['solve_ms'],'pivots',st['pivots'])
 for n_,v in zip(names,t[:5]): print('%-28s %6.2f us/pivot'%(n_, v/1e8/st['pivots']*1e6))
