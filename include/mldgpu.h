@@ -117,8 +117,11 @@ typedef enum {
                                            incumbent) instead of before the root LP (A/B) */
     MLD_DBG_NO_SWEEP = 1 << 19,         /* no closing sweep before the in-kernel hand-off publishes a stopped search's open nodes */
     MLD_DBG_ASSERT_POSCTL = 1 << 20,    /* positive control of the assertion build (-DMLD_ASSERT): one index check fails */
-    MLD_DBG_NO_PIVOT_PAIRS = 1 << 21    /* every dual-simplex pivot updates the dictionary on its own instead of two consecutive pivots sharing
+    MLD_DBG_NO_PIVOT_PAIRS = 1 << 21,   /* every dual-simplex pivot updates the dictionary on its own instead of two consecutive pivots sharing
                                            one pass (A/B on the same binary: results are bit-identical, only rows_updated and speed change) */
+    MLD_DBG_CUTS_R4 = 1 << 22           /* the wave-per-cut Gomory and c-MIR rounds as round 4 built them: one slack row / eight dictionary rows of
+                                           one column chunk in flight, generic pointers (A/B on the same binary of the grouped loads and the
+                                           LDS-typed views: results are bit-identical, only speed changes) */
 } mld_reserved_bit;
 
 /* Linear cost in tiled horizon form (the Python layer parses the reference's string-keyed atoms,

@@ -290,9 +290,17 @@ struct Shared {
 #endif
     long long prof[8];         // ticks: 0 pivot update, 1 simplex selection, 2 cuts, 3 leaf, 4 set_bounds, 5 residual/refactor, 6 setup
 #ifdef MLD_CUT_PROF
-    long long cprof[3];        // cut separation split: c-MIR scoring (phase A), c-MIR build (phase B), Gomory round
+    long long cprof[11];       // cut separation split: c-MIR scoring (phase A), c-MIR build (phase B), Gomory round; from 3: counts (CUT_COUNT sites) -- cut rounds,
+                               // Gomory cuts derived, slack columns substituted in them, c-MIR cuts built, rows substituted in them (nbr), rows scored, their list
+                               // entries, (row, divisor) pairs scored
 #endif
 };
+// counts of the diagnostic build -DMLD_CUT_PROF=2 (they replace the clocks in mld_debug_profile, see k_solve): the first lane of a wave adds v to slot k
+#ifdef MLD_CUT_PROF
+#define CUT_COUNT(sh_, k_, v_) do { if ((threadIdx.x & 63) == 0) atomicAdd((unsigned long long *)&(sh_).cprof[k_], (unsigned long long)(v_)); } while (0)
+#else
+#define CUT_COUNT(sh_, k_, v_) ((void)0)
+#endif
 
 __device__ __forceinline__ double block_sum(Shared &sh, double v)
 {
@@ -500,6 +508,13 @@ template <> struct HotT<true> {
     typedef __attribute__((address_space(3))) double *f64p; typedef __attribute__((address_space(3))) int *i32p; typedef __attribute__((address_space(3))) unsigned char *u8p;
 };
 template <> struct HotT<false> { typedef double *f64p; typedef int *i32p; typedef unsigned char *u8p; };
+// the same for what the cut rounds read besides: read-only instance data in global memory and the workgroup's lists in LDS
+template <bool L> struct CutT;
+template <> struct CutT<true> {
+    typedef const __attribute__((address_space(1))) unsigned char *cu8p; typedef const __attribute__((address_space(1))) double *cf64p;
+    typedef __attribute__((address_space(1))) double *gf64p; typedef __attribute__((address_space(3))) unsigned short *u16p;
+};
+template <> struct CutT<false> { typedef const unsigned char *cu8p; typedef const double *cf64p; typedef double *gf64p; typedef unsigned short *u16p; };
 #define HOT_VIEW(L_, w_) \
     typename HotT<L_>::f64p h_xB = (typename HotT<L_>::f64p)(w_).xB, h_xN = (typename HotT<L_>::f64p)(w_).xN, h_lo = (typename HotT<L_>::f64p)(w_).lo, h_hi = (typename HotT<L_>::f64p)(w_).hi, \
                             h_dw = (typename HotT<L_>::f64p)(w_).dw, h_d = (typename HotT<L_>::f64p)(w_).dcost; \
@@ -2223,12 +2238,24 @@ __device__ __forceinline__ double wave_all_min(double v) { for (int o = 32; o > 
 // structural space), and the batch is committed in candidate order.  Candidates in the order the oracle takes them:
 // |f0 - 1/2| ascending, row index on ties.  Same cuts, same order as the one-at-a-time version (s_gmi_round_serial).
 #define GMI_KC 16
+// the grouped slack substitution (every hot array in LDS): column chunks a lane accumulates in registers per pass (n <= 576: one pass) and slack rows
+// whose loads are in flight together (GMI_GROUP x GMI_KC2 loads per lane)
+#define GMI_KC2 9
+#ifndef GMI_GROUP
+#define GMI_GROUP 4
+#endif
 // a wave's own phases exchange data between lanes through its lines (LDS, or the slot when they do not fit): drain the wave's
 // outstanding memory operations and keep the compiler from moving accesses across
 #define WAVE_MEM_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_s_waitcnt(0); __builtin_amdgcn_wave_barrier(); } while (0)
-__device__ int s_gmi_round(const Ws &w, Shared &sh, int max_cuts)
+template <bool L>
+__device__ __forceinline__ int s_gmi_round_t(const Ws &w, Shared &sh, int max_cuts)
 {
     const int n = w.n, ld = w.ld, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    HOT_VIEW(L, w);
+    (void)h_dw; (void)h_d; (void)h_skip;
+    const typename CutT<L>::cu8p is_int = (typename CutT<L>::cu8p)w.is_int;
+    const typename CutT<L>::u16p c_rowlist = (typename CutT<L>::u16p)w.rowlist, c_seclist = (typename CutT<L>::u16p)w.seclist;
+    const typename HotT<L>::f64p c_colc = (typename HotT<L>::f64p)w.colc;
     const int m_start = sh.m;
     __syncthreads();
     // candidates (fractional integer basics), compacted in row order, then ranked by (key, row)
@@ -2237,9 +2264,9 @@ __device__ int s_gmi_round(const Ws &w, Shared &sh, int max_cuts)
         const int r = r0 + tid;
         bool cand = false; double key = S_INF;
         if (r < m_start) {
-            const int j = w.basic[r];
-            if (j < n && w.is_int[j]) {
-                const double f0 = w.xB[r] - floor(w.xB[r]);
+            const int j = h_basic[r];
+            if (j < n && is_int[j]) {
+                const double f0 = h_xB[r] - floor(h_xB[r]);
                 if (f0 > 1e-3 && f0 < 1 - 1e-3) { cand = true; key = fabs(f0 - 0.5); }
             }
             w.key[r] = key;
@@ -2248,17 +2275,17 @@ __device__ int s_gmi_round(const Ws &w, Shared &sh, int max_cuts)
     }
     s_gather_x(w, sh, w.tmpx);
     MLD_CHECK(w, C <= m_start && m_start <= w.mcap && C <= (int)(w.rowlist - w.seclist), 116, C, m_start);
-    for (int t = tid; t < C; t += SOL_NT) w.colc[t] = w.key[w.rowlist[t]];
+    for (int t = tid; t < C; t += SOL_NT) c_colc[t] = w.key[c_rowlist[t]];
     __syncthreads();
     for (int t = tid; t < C; t += SOL_NT) {
-        const int r = w.rowlist[t];
-        const double k = w.colc[t];
+        const int r = c_rowlist[t];
+        const double k = c_colc[t];
         int rank = 0;
-        for (int u = 0; u < C; ++u) { const int ru = w.rowlist[u]; const double ku = w.colc[u]; rank += (ku < k) || (ku == k && ru < r); }
-        w.seclist[rank] = (unsigned short)r;
+        for (int u = 0; u < C; ++u) { const int ru = c_rowlist[u]; const double ku = c_colc[u]; rank += (ku < k) || (ku == k && ru < r); }
+        c_seclist[rank] = (unsigned short)r;
     }
     __syncthreads();
-    double *gw = w.mir_cache + (size_t)wave * 2 * n, *axw = gw + n;
+    const typename HotT<L>::f64p gw = (typename HotT<L>::f64p)w.mir_cache + (size_t)wave * 2 * n, axw = gw + n;
     int added = 0;
     for (int pos = 0; pos < C; pos += SOL_NW) {
         if (m_start + added >= sh.cut_cap || added >= max_cuts) break;
@@ -2266,8 +2293,8 @@ __device__ int s_gmi_round(const Ws &w, Shared &sh, int max_cuts)
         bool ok = t < C;
         double bx = 0.0, nrm = 0.0;
         if (ok) {
-            const int r = w.seclist[t];
-            const double f0 = w.xB[r] - floor(w.xB[r]);
+            const int r = c_seclist[t];
+            const double f0 = h_xB[r] - floor(h_xB[r]);
             const glb_f64 *row = (const glb_f64 *)(w.D + (size_t)r * ld);
             double gmin = S_INF, gmax = 0.0;
             for (int c0 = 0; c0 < n; c0 += 512) {      // eight independent loads of the dictionary row in flight
@@ -2278,14 +2305,14 @@ __device__ int s_gmi_round(const Ws &w, Shared &sh, int max_cuts)
             for (int q = 0; q < 8; ++q) {
                 const int c = c0 + q * 64 + lane;
                 if (c >= n) continue;
-                const int j = w.nonbasic[c];
-                double a = (w.lo[j] == w.hi[j]) ? 0.0 : (w.at_upper[c] ? -rv[q] : rv[q]);
+                const int j = h_nonbasic[c];
+                double a = (h_lo[j] == h_hi[j]) ? 0.0 : (h_up[c] ? -rv[q] : rv[q]);
                 // Coefficients below 1e-9 are dropped (round-off of the dictionary).  Dropping strengthens the cut by |a| t_j: harmless for a column
                 // whose displacement t_j is O(1), NOT for a free variable resting on the artificial box (t_j up to 2e7): such a cut is not derived.
                 bool unsafe = false;
-                if (fabs(a) < S_COEF_ZERO) { unsafe = a != 0.0 && j < n && fabs(w.at_upper[c] ? w.hi[j] : w.lo[j]) >= 0.5 * S_BIG; a = 0.0; }
+                if (fabs(a) < S_COEF_ZERO) { unsafe = a != 0.0 && j < n && fabs(h_up[c] ? h_hi[j] : h_lo[j]) >= 0.5 * S_BIG; a = 0.0; }
                 double gc;
-                if (j < n && w.is_int[j]) {
+                if (j < n && is_int[j]) {
                     double fj = a - floor(a);
                     if (fj < S_COEF_ZERO || fj > 1 - S_COEF_ZERO) fj = 0.0;
                     gc = fj <= f0 ? fj / f0 : (1 - fj) / (1 - f0);
@@ -2305,12 +2332,63 @@ __device__ int s_gmi_round(const Ws &w, Shared &sh, int max_cuts)
                 for (int c = lane; c < n; c += 64) {
                     const double gc = gw[c];
                     if (gc <= 0) continue;
-                    const int j = w.nonbasic[c];
-                    const double sg = w.at_upper[c] ? -1.0 : 1.0;
-                    if (j < n) { const double bnd = w.at_upper[c] ? w.hi[j] : w.lo[j]; axw[j] = -gc * sg; bx_part -= gc * sg * bnd; }
-                    else bx_part += gc * orig_rhs(w, j - n);
+                    const int j = h_nonbasic[c];
+                    const double sg = h_up[c] ? -1.0 : 1.0;
+                    if (j < n) { const double bnd = h_up[c] ? h_hi[j] : h_lo[j]; axw[j] = -gc * sg; bx_part -= gc * sg * bnd; }
+                    else bx_part += gc * (j - n < w.m0 ? ((typename CutT<L>::cf64p)w.hs)[j - n] : ((typename CutT<L>::cf64p)w.hc)[j - n - w.m0]);      // (orig_rhs)
                 }
                 WAVE_MEM_SYNC();
+                if constexpr (L) {
+                // slack columns: ax += g_c * (original row of that slack), ascending c -- the same sequence of acc += g_c * value per structural column as the
+                // round-4 loop below, but GMI_GROUP slack rows at a time: the set columns are taken in ascending order across the 64-column chunks, the loads
+                // of all rows of a group are issued before the first multiply-add (one memory latency per group instead of one per slack column), and the rows
+                // are read through global pointers (w.Gs / w.Gc: address space known), g_c and the column's variable through the LDS views
+                const glb_f64 *Gs = (const glb_f64 *)w.Gs, *Gc = (const glb_f64 *)w.Gc;
+                const int m0 = w.m0;
+                for (int k0 = 0; k0 < n; k0 += 64 * GMI_KC2) {
+                    double acc[GMI_KC2];
+#pragma unroll
+                    for (int q = 0; q < GMI_KC2; ++q) { const int k = k0 + q * 64 + lane; acc[q] = k < n ? axw[k] : 0.0; }
+                    int c0 = 0;
+                    unsigned long long mask = __ballot(lane < n && h_nonbasic[lane < n ? lane : 0] >= n && gw[lane < n ? lane : 0] > 0);
+                    for (;;) {
+                        int ri[GMI_GROUP]; double gs[GMI_GROUP];
+#pragma unroll
+                        for (int u = 0; u < GMI_GROUP; ++u) {
+                            while (!mask && c0 + 64 < n) {
+                                c0 += 64;
+                                const int c = c0 + lane, cc = c < n ? c : 0;
+                                mask = __ballot(c < n && h_nonbasic[cc] >= n && gw[cc] > 0);
+                            }
+                            ri[u] = -1; gs[u] = 0.0;
+                            if (mask) {
+                                const int cs = c0 + __ffsll((long long)mask) - 1;       // wave-uniform
+                                mask &= mask - 1ull;
+                                gs[u] = gw[cs];
+                                ri[u] = __builtin_amdgcn_readfirstlane(h_nonbasic[cs]) - n;
+                                MLD_CHECK(w, ri[u] >= 0 && ri[u] < m_start, 119, ri[u] + n, m_start);
+                            }
+                        }
+                        if (ri[0] < 0) break;
+                        double v[GMI_GROUP][GMI_KC2];
+#pragma unroll
+                        for (int u = 0; u < GMI_GROUP; ++u) {
+                            const int i = ri[u] < 0 ? 0 : ri[u];
+                            const glb_f64 *orow = i < m0 ? Gs + (size_t)i * n : Gc + (size_t)(i - m0) * n;
+#pragma unroll
+                            for (int q = 0; q < GMI_KC2; ++q) { const int k = k0 + q * 64 + lane; v[u][q] = (ri[u] >= 0 && k < n) ? orow[k] : 0.0; }
+                        }
+#pragma unroll
+                        for (int u = 0; u < GMI_GROUP; ++u) {
+                            if (ri[u] < 0) continue;
+#pragma unroll
+                            for (int q = 0; q < GMI_KC2; ++q) if (k0 + q * 64 < n) acc[q] += gs[u] * v[u][q];
+                        }
+                    }
+#pragma unroll
+                    for (int q = 0; q < GMI_KC2; ++q) { const int k = k0 + q * 64 + lane; if (k < n) axw[k] = acc[q]; }
+                }
+                } else {
                 // slack columns: ax += g_c * (original row of that slack), ascending c; a chunk of 64 * GMI_KC structural columns
                 // is accumulated in registers, 16 independent loads per slack row
                 for (int k0 = 0; k0 < n; k0 += 64 * GMI_KC) {
@@ -2320,7 +2398,7 @@ __device__ int s_gmi_round(const Ws &w, Shared &sh, int max_cuts)
                     for (int c0 = 0; c0 < n; c0 += 64) {
                         const int c = c0 + lane;
                         int jn = 0; double gc = 0.0;
-                        if (c < n) { jn = w.nonbasic[c]; gc = gw[c]; }
+                        if (c < n) { jn = h_nonbasic[c]; gc = gw[c]; }
                         unsigned long long mask = __ballot(c < n && jn >= n && gc > 0);
                         while (mask) {
                             const int src = __ffsll((long long)mask) - 1;
@@ -2335,6 +2413,7 @@ __device__ int s_gmi_round(const Ws &w, Shared &sh, int max_cuts)
 #pragma unroll
                     for (int q = 0; q < GMI_KC; ++q) { const int k = k0 + q * 64 + lane; if (k < n) axw[k] = acc[q]; }
                 }
+                }
                 WAVE_MEM_SYNC();
                 bx = wave_all_sum(bx_part) - 1.0;
                 double nm = 0.0;
@@ -2342,6 +2421,12 @@ __device__ int s_gmi_round(const Ws &w, Shared &sh, int max_cuts)
                 nrm = wave_all_max(nm);
                 ok = nrm > 0.0;
                 nrm = fmax(nrm, gmax);       // keep the dictionary row (coefficients g) O(1) as well as the structural row
+#ifdef MLD_CUT_PROF
+                int nsl = 0;
+                for (int c0 = 0; c0 < n; c0 += 64) { const int c = c0 + lane, cc = c < n ? c : 0; nsl += __popcll(__ballot(c < n && h_nonbasic[cc] >= n && gw[cc] > 0)); }
+                CUT_COUNT(sh, 5, nsl);
+                CUT_COUNT(sh, 4, 1);
+#endif
             }
         }
         if (lane == 0) sh.s_i[wave] = ok ? 1 : 0;
@@ -2352,25 +2437,26 @@ __device__ int s_gmi_round(const Ws &w, Shared &sh, int max_cuts)
         if (ok && before < room) {
             const int kc = m_start + added + before;            // new row index
             MLD_CHECK(w, kc >= w.m0 && kc < w.mcap, 117, kc, added);
-            double *gk = w.Gc + (size_t)(kc - w.m0) * n, *dk = w.D + (size_t)kc * ld;
+            const typename CutT<L>::gf64p gk = (typename CutT<L>::gf64p)(w.Gc + (size_t)(kc - w.m0) * n), dk = (typename CutT<L>::gf64p)(w.D + (size_t)kc * ld);
+            const typename CutT<L>::cf64p tmpx = (typename CutT<L>::cf64p)w.tmpx;
             double sp = 0.0, dp = 0.0;
             for (int k = lane; k < n; k += 64) {
                 const double a = axw[k] / nrm;
                 gk[k] = a;
-                sp += a * w.tmpx[k];
-                const double sg = w.at_upper[k] ? -1.0 : 1.0;
+                sp += a * tmpx[k];
+                const double sg = h_up[k] ? -1.0 : 1.0;
                 const double dv = -(gw[k] / nrm) * sg;
                 dk[k] = dv;
-                dp += dv * w.xN[k];
+                dp += dv * h_xN[k];
             }
             const double s_now = bx / nrm - wave_all_sum(sp);
             const double dsum = wave_all_sum(dp);
             if (lane == 0) {
                 w.hc[kc - w.m0] = bx / nrm;
                 dk[n] = s_now + dsum;
-                w.basic[kc] = n + kc; w.where[n + kc] = -1 - kc;
-                w.xB[kc] = s_now;
-                w.lo[n + kc] = 0.0; w.hi[n + kc] = S_INF;
+                h_basic[kc] = n + kc; w.where[n + kc] = -1 - kc;
+                h_xB[kc] = s_now;
+                h_lo[n + kc] = 0.0; h_hi[n + kc] = S_INF;
             }
         }
         added += total < room ? total : room;
@@ -2380,6 +2466,12 @@ __device__ int s_gmi_round(const Ws &w, Shared &sh, int max_cuts)
     if (tid == 0) sh.m = m_start + added;
     __syncthreads();
     return added;
+}
+
+// the typed, grouped instantiation when every hot array and the per-wave lines are in LDS (the bench shapes); MLD_DBG_CUTS_R4 keeps round 4's
+__device__ int s_gmi_round(const Ws &w, Shared &sh, int max_cuts)
+{
+    return (w.all_lds && w.mir_in_lds && !(w.dbg & MLD_DBG_CUTS_R4)) ? s_gmi_round_t<true>(w, sh, max_cuts) : s_gmi_round_t<false>(w, sh, max_cuts);
 }
 
 __device__ int s_gmi_round_serial(const Ws &w, Shared &sh, int max_cuts)
@@ -2550,8 +2642,110 @@ __device__ __forceinline__ void s_mir_score4(GB ga, GB gx, int cnt, int lane, do
     }
 }
 
+// The same scores with the wave split into 64 / W sub-groups of W lanes (W = 32 for a list of at most 32 entries, 16 for at most 16): every sub-group
+// scores another divisor of the row, 64 / W fractional binaries of `mask` (ascending) at a time.  Bit for bit the results of s_mir_score4 one divisor
+// after the other:
+//  * per entry and q the same operations (the four divisions a0 / (d0 / 2^q) are kept as they are);
+//  * wave_sum is v += shfl_down(v, o) for o = 32 .. 1, and there every lane from cnt on holds +0.0 (its sum never started) while no partial sum is -0.0
+//    (each starts from +0.0), so the steps o >= W add +0.0 to what lane 0 ends with and the steps o < W read lanes below W only: the same tree run
+//    from o = W / 2 gives a sub-group's first lane exactly that value;
+//  * (best, bdelta) takes "the first strictly greater" in the order (divisor ascending, q ascending): a sub-group keeps the first strictly greater of
+//    its q = 0 .. 3 (every efficacy that gets there is > 0), the sub-groups are then taken in ascending divisor order with the same strict test -- the
+//    first occurrence of the maximum either way.
+template <int W, typename GB>
+__device__ __forceinline__ void s_mir_score_sub(GB ga, GB gx, int cnt, int lane, double rhs, double sval, double S2, unsigned long long mask,
+                                                double &best, double &bdelta)
+{
+    const int sub = lane / W, sl = lane % W;
+    double a0 = 0.0, x = 0.0;
+    if (sl < cnt) { a0 = ga[sl]; x = gx[sl]; }
+    while (mask) {
+        int src = -1;
+#pragma unroll
+        for (int g = 0; g < 64 / W; ++g) if (mask) { const int s1 = __ffsll((long long)mask) - 1; mask &= mask - 1ull; if (sub == g) src = s1; }
+        const bool act = src >= 0;
+        const double d0 = fabs(__shfl(a0, act ? src : 0, 64));
+        double f[4], fb[4], inv1f[4], lhs[4], nrm2[4]; bool use[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const double delta = d0 / (double)(1 << q);
+            const double b = rhs / delta;
+            fb[q] = floor(b); f[q] = b - fb[q];
+            use[q] = act && delta >= 1e-9 && f[q] >= S_MIR_FMIN && f[q] <= 1.0 - S_MIR_FMIN;
+            inv1f[q] = 1.0 / (1.0 - f[q]);
+            lhs[q] = 0.0; nrm2[q] = 0.0;
+        }
+        if (sl < cnt && (use[0] || use[1] || use[2] || use[3])) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const double a = a0 / (d0 / (double)(1 << q)), fl = floor(a + 1e-12), fj = a - fl;
+                const double cf = fl + (fj > f[q] ? (fj - f[q]) * inv1f[q] : 0.0);
+                lhs[q] += cf * x;
+                nrm2[q] += cf * cf;
+            }
+        }
+        double le = 0.0, ld = 0.0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            double l = lhs[q], m2 = nrm2[q];
+#pragma unroll
+            for (int o = W / 2; o > 0; o >>= 1) { l += __shfl_down(l, o, 64); m2 += __shfl_down(m2, o, 64); }
+            l = __shfl(l, sub * W, 64); m2 = __shfl(m2, sub * W, 64);
+            if (!use[q]) continue;
+            const double delta = d0 / (double)(1 << q), kc = inv1f[q] / delta;
+            const double viol = l - sval * kc - fb[q];
+            m2 += kc * kc * S2;
+            if (viol <= 1e-6 || !(m2 > 0.0)) continue;
+            const double eff = viol / sqrt(m2);
+            if (eff > le) { le = eff; ld = delta; }
+        }
+#pragma unroll
+        for (int g = 0; g < 64 / W; ++g) {
+            const double eg = __shfl(le, g * W, 64), dg = __shfl(ld, g * W, 64);
+            if (eg > best) { best = eg; bdelta = dg; }
+        }
+    }
+}
+
+// every candidate divisor of a row whose compact list is built (ascending j, as the oracle enumerates them): best efficacy and its divisor
 template <typename GB>
-__device__ __forceinline__ void s_mir_phase_a(GB ga, GB gx, int cap, const Ws &w, const lds_f64 *xs, int ncand, int wave, int lane)
+__device__ __forceinline__ void s_mir_score_row(GB ga, GB gx, int cnt, int lane, double rhs, double sval, double S2, int usable, bool split, Shared &sh,
+                                                double &best, double &bdelta)
+{
+    best = 0.0; bdelta = 0.0;
+#ifdef MLD_CUT_PROF
+    if (__ballot(!usable) == 0ull) {
+        int nd = 0;
+        for (int t0 = 0; t0 < cnt; t0 += 64) { const int t = t0 + lane; bool fr = false; if (t < cnt) { const double x = gx[t]; fr = x > 1e-6 && x < 1 - 1e-6; } nd += __popcll(__ballot(fr)); }
+        CUT_COUNT(sh, 8, 1); CUT_COUNT(sh, 9, cnt); CUT_COUNT(sh, 10, nd);
+    }
+#endif
+    if (__ballot(!usable) == 0ull && split && cnt <= 32) {
+        // (a list of at most 32 entries -- every row of the bench shape -- leaves half or three quarters of the wave idle: two or four divisors at once)
+        bool fr = false;
+        if (lane < cnt) { const double x = gx[lane]; fr = x > 1e-6 && x < 1 - 1e-6; }
+        const unsigned long long mask = __ballot(fr);
+        if (cnt <= 16) s_mir_score_sub<16>(ga, gx, cnt, lane, rhs, sval, S2, mask, best, bdelta);
+        else s_mir_score_sub<32>(ga, gx, cnt, lane, rhs, sval, S2, mask, best, bdelta);
+    } else
+    if (__ballot(!usable) == 0ull) {
+        for (int t0 = 0; t0 < cnt; t0 += 64) {           // candidate divisors in ascending j, as the oracle enumerates them
+            const int t = t0 + lane;
+            double a0 = 0.0; bool fr = false;
+            if (t < cnt) { a0 = ga[t]; const double x = gx[t]; fr = x > 1e-6 && x < 1 - 1e-6; }
+            unsigned long long mask = __ballot(fr);
+            while (mask) {
+                const int src = __ffsll((long long)mask) - 1;
+                mask &= mask - 1ull;
+                const double d0 = fabs(__shfl(a0, src, 64));
+                s_mir_score4(ga, gx, cnt, lane, rhs, sval, S2, d0, best, bdelta);
+            }
+        }
+    }
+}
+
+template <typename GB>
+__device__ __forceinline__ void s_mir_phase_a(GB ga, GB gx, int cap, const Ws &w, const lds_f64 *xs, int ncand, int wave, int lane, bool split, Shared &sh)
 {
     const int n = w.n;
     const lds_u16 *rows = (const lds_u16 *)w.rowlist;
@@ -2625,23 +2819,207 @@ __device__ __forceinline__ void s_mir_phase_a(GB ga, GB gx, int cap, const Ws &w
         }
         rhs = wave_sum(rhs); sval = wave_sum(sval); S2 = wave_sum(S2);
         rhs = __shfl(rhs, 0, 64) + w.hs[i]; sval = __shfl(sval, 0, 64); S2 = __shfl(S2, 0, 64);
-        double best = 0.0, bdelta = 0.0;
-        if (__ballot(!usable) == 0ull) {
-            for (int t0 = 0; t0 < cnt; t0 += 64) {           // candidate divisors in ascending j, as the oracle enumerates them
-                const int t = t0 + lane;
-                double a0 = 0.0; bool fr = false;
-                if (t < cnt) { a0 = ga[t]; const double x = gx[t]; fr = x > 1e-6 && x < 1 - 1e-6; }
-                unsigned long long mask = __ballot(fr);
-                while (mask) {
-                    const int src = __ffsll((long long)mask) - 1;
-                    mask &= mask - 1ull;
-                    const double d0 = fabs(__shfl(a0, src, 64));
-                    s_mir_score4(ga, gx, cnt, lane, rhs, sval, S2, d0, best, bdelta);
+        double best, bdelta;
+        s_mir_score_row(ga, gx, cnt, lane, rhs, sval, S2, usable, split, sh, best, bdelta);
+        if (lane == 0) { w.mir_eff[i] = best > 1e-4 ? best : -S_INF; w.mir_delta[i] = bdelta; }
+    }
+}
+
+// column chunks a lane accumulates in registers per pass (n <= 576: one pass) and dictionary rows in flight together in the rows-outermost substitution
+#define MIR_KC 9
+#ifndef MIR_GROUP
+#define MIR_GROUP 4
+#endif
+// phase B of s_mir_round, a wave per cut (see there).  L: every hot array of the pivot loop is in LDS as well as the lines -- LDS-typed views, and the
+// substitution of the basic structurals with the rows outermost (below); L = false is round 4's code on generic pointers (MLD_DBG_CUTS_R4, other shapes).
+template <bool L>
+__device__ __forceinline__ int s_mir_build_waves(const Ws &w, Shared &sh, int max_cuts, int m_start, const lds_f64 *xs)
+{
+    const int n = w.n, ld = w.ld, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, m0 = w.m0;
+    HOT_VIEW(L, w);
+    (void)h_dw; (void)h_d; (void)h_skip; (void)h_up;
+    const typename CutT<L>::cu8p is_int = (typename CutT<L>::cu8p)w.is_int;
+    const typename CutT<L>::u16p c_rowlist = (typename CutT<L>::u16p)w.rowlist, c_seclist = (typename CutT<L>::u16p)w.seclist;
+    const typename HotT<L>::f64p c_colc = (typename HotT<L>::f64p)w.colc;
+    const typename CutT<L>::cf64p clo = (typename CutT<L>::cf64p)w.clo, chi = (typename CutT<L>::cf64p)w.chi;
+    const typename CutT<L>::gf64p mir_eff = (typename CutT<L>::gf64p)w.mir_eff, mir_delta = (typename CutT<L>::gf64p)w.mir_delta;
+    int nc2 = 0;
+    for (int i0 = 0; i0 < m0; i0 += SOL_NT) {
+        const int i = i0 + tid;
+        nc2 = block_compact(sh, i < m0 && mir_eff[i] > -S_INF, (unsigned short)i, w.rowlist, nc2);
+    }
+    __syncthreads();
+    for (int t = tid; t < nc2; t += SOL_NT) c_colc[t] = mir_eff[c_rowlist[t]];
+    __syncthreads();
+    for (int t = tid; t < nc2; t += SOL_NT) {
+        const int i = c_rowlist[t];
+        const double e = c_colc[t];
+        int rank = 0;
+        for (int u = 0; u < nc2; ++u) { const double eu = c_colc[u]; rank += (eu > e) || (eu == e && (int)c_rowlist[u] < i); }
+        c_seclist[rank] = (unsigned short)i;
+    }
+    __syncthreads();
+    MLD_CHECK(w, nc2 <= m0 && nc2 <= (int)(w.rowlist - w.seclist), 121, nc2, m0);
+    const typename HotT<L>::f64p axw = (typename HotT<L>::f64p)w.mir_cache + (size_t)wave * 2 * n;
+    const typename CutT<L>::u16p rl = (typename CutT<L>::u16p)(axw + n);          // rows whose basic structural has a non-zero cut coefficient (at most n of them)
+    int added = 0;
+    for (int pos = 0; pos < nc2; pos += SOL_NW) {
+        if (m_start + added >= sh.cut_cap || added >= max_cuts) break;
+        const int t = pos + wave;
+        bool ok = t < nc2;
+        double bx = 0.0, nrm = 0.0, s_now = 0.0;
+        if (ok) {
+            const int i = c_seclist[t];
+            const double delta = mir_delta[i];
+            const typename CutT<L>::cf64p g = (typename CutT<L>::cf64p)(w.Gs + (size_t)i * n);
+            const int jmax = w.nc_step > 0 ? min(n, (i / w.nc_step + 1) * w.nv_step) : n;      // causal rows (s_mir_phase_a)
+            // right-hand side after complementing / bound substitution
+            double rp = 0.0;
+            for (int j = lane; j < jmax; j += 64) {
+                const double gj = g[j];
+                if (gj == 0.0) continue;
+                if (is_int[j]) { const double lo = h_lo[j], hi = h_hi[j]; if (lo == hi) rp -= gj * lo; else if (xs[j] > 0.5) rp -= gj; }
+                else { const double lo = clo[j], hi = chi[j]; rp -= gj * (lo > -0.5 * S_BIG ? lo : hi); }
+            }
+            const double rhs = wave_all_sum(rp) + ((typename CutT<L>::cf64p)w.hs)[i];
+            const double b = rhs / delta, fb = floor(b), f = b - fb;
+            ok = !(f < S_MIR_FMIN || f > 1.0 - S_MIR_FMIN);
+            if (ok) {
+                const double kc = 1.0 / (delta * (1.0 - f));
+                double bp = 0.0, nm = 0.0;
+                for (int j = lane; j < n; j += 64) {
+                    double a = 0.0;
+                    const double gj = j < jmax ? g[j] : 0.0;
+                    if (gj != 0.0) {
+                        if (is_int[j]) {
+                            const double lo = h_lo[j], hi = h_hi[j];
+                            if (lo != hi) {
+                                const bool comp = xs[j] > 0.5;
+                                const double aa = (comp ? -gj : gj) / delta, fl = floor(aa + 1e-12), fj = aa - fl;
+                                const double cf = fl + (fj > f ? (fj - f) / (1.0 - f) : 0.0);
+                                if (comp) { a = -cf; bp -= cf; } else a = cf;
+                            }
+                        } else {
+                            const double lo = clo[j], hi = chi[j];
+                            const bool lof = lo > -0.5 * S_BIG, hif = hi < 0.5 * S_BIG;
+                            if (gj > 0) { if (!lof && hif) { a = kc * gj; bp += kc * gj * hi; } }
+                            else { if (lof) { a = -kc * (-gj); bp -= kc * (-gj) * lo; } }
+                        }
+                    }
+                    axw[j] = a;
+                    nm = fmax(nm, fabs(a));
+                }
+                bx = fb + wave_all_sum(bp);
+                nrm = wave_all_max(nm);
+                ok = nrm > 0.0;
+                if (ok) {
+                    double sp = 0.0;
+                    for (int j = lane; j < n; j += 64) { const double a = axw[j] / nrm; axw[j] = a; sp += a * xs[j]; }
+                    s_now = bx / nrm - wave_all_sum(sp);
+                    ok = s_now < -1e-9;               // not violated after all (rounding): skip
                 }
             }
         }
-        if (lane == 0) { w.mir_eff[i] = best > 1e-4 ? best : -S_INF; w.mir_delta[i] = bdelta; }
+        WAVE_MEM_SYNC();
+        if (lane == 0) sh.s_i[wave] = ok ? 1 : 0;
+        __syncthreads();
+        int before = 0, total = 0;
+        for (int u = 0; u < SOL_NW; ++u) { const int fl2 = sh.s_i[u]; if (u < wave) before += fl2; total += fl2; }
+        const int room = min(sh.cut_cap - (m_start + added), max_cuts - added);
+        if (ok && before < room) {
+            const int kcut = m_start + added + before;
+            MLD_CHECK(w, kcut >= m0 && kcut < w.mcap, 123, t, kcut);
+            const typename CutT<L>::gf64p gk = (typename CutT<L>::gf64p)(w.Gc + (size_t)(kcut - m0) * n), dk = (typename CutT<L>::gf64p)(w.D + (size_t)kcut * ld);
+            for (int j = lane; j < n; j += 64) gk[j] = axw[j];
+            // dictionary row of the new slack: the cut row with the basic structurals substituted, dk = gk_N - sum_r gk[j_r] D[r,:] (rows of this round's
+            // cuts have slack basics: only rows below m_start can qualify)
+            int nbr = 0;
+            for (int r0 = 0; r0 < m_start; r0 += 64) {
+                const int r = r0 + lane;
+                bool fl2 = false;
+                if (r < m_start) { const int j = h_basic[r]; fl2 = j < n && axw[j] != 0.0; }
+                const unsigned long long bal = __ballot(fl2);
+                if (fl2) rl[nbr + __popcll(bal & ((1ull << lane) - 1ull))] = (unsigned short)r;
+                nbr += __popcll(bal);
+            }
+            WAVE_MEM_SYNC();
+            MLD_CHECK(w, nbr <= n && nbr <= m_start, 124, nbr, m_start);
+            CUT_COUNT(sh, 6, 1); CUT_COUNT(sh, 7, nbr);
+            const glb_f64 *Dg = (const glb_f64 *)w.D;
+            double dp = 0.0;
+            // Rows outermost when the coefficients fit behind rl in the wave's second line (n doubles: the nbr row indices take (nbr + 3) / 4 of them): the
+            // coefficients axw[basic[rl[u]]] are gathered once, then MIR_GROUP rows at a time have ALL their column chunks in flight (MIR_GROUP x MIR_KC loads
+            // per lane) before the chunks' accumulators are updated in ascending u -- per column the same acc -= cf_u * D[r_u, c] in the same order as the
+            // round-4 nest (column chunk outermost, eight rows of one chunk in flight: MIR_KC x nbr / 8 dependent round trips per cut against nbr / MIR_GROUP),
+            // and dp still adds up in ascending c per lane.
+            bool rows_outer = false;
+            if constexpr (L) rows_outer = (nbr + 3) / 4 + nbr <= n;
+            if constexpr (L) if (rows_outer) {
+                const typename HotT<L>::f64p cfl = (typename HotT<L>::f64p)(axw + n) + (nbr + 3) / 4;
+                for (int u = lane; u < nbr; u += 64) cfl[u] = axw[h_basic[rl[u]]];
+                WAVE_MEM_SYNC();
+                for (int k0 = 0; k0 < n; k0 += 64 * MIR_KC) {
+                    double acc[MIR_KC];
+#pragma unroll
+                    for (int q = 0; q < MIR_KC; ++q) {
+                        const int c = k0 + q * 64 + lane;
+                        acc[q] = 0.0;
+                        if (c < n) { const int j = h_nonbasic[c]; acc[q] = j < n ? axw[j] : 0.0; }
+                    }
+                    for (int u = 0; u < nbr; u += MIR_GROUP) {
+                        double v[MIR_GROUP][MIR_KC], cf[MIR_GROUP];
+#pragma unroll
+                        for (int e = 0; e < MIR_GROUP; ++e) {
+                            const bool have = u + e < nbr;         // wave-uniform
+                            const int r = __builtin_amdgcn_readfirstlane((int)rl[have ? u + e : u]);
+                            const glb_f64 *row = Dg + (size_t)r * ld;
+                            cf[e] = cfl[have ? u + e : u];
+#pragma unroll
+                            for (int q = 0; q < MIR_KC; ++q) { const int c = k0 + q * 64 + lane; v[e][q] = (have && c < n) ? row[c] : 0.0; }
+                        }
+#pragma unroll
+                        for (int e = 0; e < MIR_GROUP; ++e) {
+                            if (u + e >= nbr) continue;
+#pragma unroll
+                            for (int q = 0; q < MIR_KC; ++q) acc[q] -= cf[e] * v[e][q];
+                        }
+                    }
+#pragma unroll
+                    for (int q = 0; q < MIR_KC; ++q) {
+                        const int c = k0 + q * 64 + lane;
+                        if (c < n) { dk[c] = acc[q]; dp += acc[q] * h_xN[c]; }
+                    }
+                }
+            }
+            if (!rows_outer)
+            for (int c = lane; c < n; c += 64) {
+                const int j = h_nonbasic[c];
+                double acc = j < n ? axw[j] : 0.0;
+                int u = 0;
+                for (; u + 8 <= nbr; u += 8) {      // eight independent loads of the rows in flight
+                    double v[8], cf[8];
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) { const int r = rl[u + q]; v[q] = Dg[(size_t)r * ld + c]; cf[q] = axw[h_basic[r]]; }
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) acc -= cf[q] * v[q];
+                }
+                for (; u < nbr; ++u) { const int r = rl[u]; acc -= axw[h_basic[r]] * Dg[(size_t)r * ld + c]; }
+                dk[c] = acc;
+                dp += acc * h_xN[c];
+            }
+            const double dsum = wave_all_sum(dp);
+            if (lane == 0) {
+                w.hc[kcut - m0] = bx / nrm;
+                dk[n] = s_now + dsum;
+                h_basic[kcut] = n + kcut; w.where[n + kcut] = -1 - kcut;
+                h_xB[kcut] = s_now;
+                h_lo[n + kcut] = 0.0; h_hi[n + kcut] = S_INF;
+            }
+        }
+        added += min(total, room);
+        __syncthreads();
     }
+    return added;
 }
 
 __device__ int s_mir_round(const Ws &w, Shared &sh, int max_cuts)
@@ -2691,9 +3069,10 @@ __device__ int s_mir_round(const Ws &w, Shared &sh, int max_cuts)
     __syncthreads();
     MLD_CHECK(w, nF <= w.nb && ncand <= m0, 120, nF, ncand);
     if (ncand > 0) {
-        if (w.mir_line) s_mir_phase_a<lds_f64 *>((lds_f64 *)w.mir_line + (size_t)wave * 2 * w.mir_cap, (lds_f64 *)w.mir_line + (size_t)wave * 2 * w.mir_cap + w.mir_cap, w.mir_cap, w, xs, ncand, wave, lane);
-        else if (w.mir_in_lds) s_mir_phase_a<lds_f64 *>((lds_f64 *)w.mir_cache + (size_t)wave * 2 * n, (lds_f64 *)w.mir_cache + (size_t)wave * 2 * n + n, n, w, xs, ncand, wave, lane);
-        else s_mir_phase_a<double *>(w.mir_cache + (size_t)wave * 2 * n, w.mir_cache + (size_t)wave * 2 * n + n, n, w, xs, ncand, wave, lane);
+        const bool split = w.mir_in_lds && !(w.dbg & MLD_DBG_CUTS_R4);       // several divisors of a row per wave (s_mir_score_sub)
+        if (w.mir_line) s_mir_phase_a<lds_f64 *>((lds_f64 *)w.mir_line + (size_t)wave * 2 * w.mir_cap, (lds_f64 *)w.mir_line + (size_t)wave * 2 * w.mir_cap + w.mir_cap, w.mir_cap, w, xs, ncand, wave, lane, split, sh);
+        else if (w.mir_in_lds) s_mir_phase_a<lds_f64 *>((lds_f64 *)w.mir_cache + (size_t)wave * 2 * n, (lds_f64 *)w.mir_cache + (size_t)wave * 2 * n + n, n, w, xs, ncand, wave, lane, split, sh);
+        else s_mir_phase_a<double *>(w.mir_cache + (size_t)wave * 2 * n, w.mir_cache + (size_t)wave * 2 * n + n, n, w, xs, ncand, wave, lane, false, sh);
     }
     __syncthreads();
 #ifdef MLD_CUT_PROF
@@ -2706,136 +3085,7 @@ __device__ int s_mir_round(const Ws &w, Shared &sh, int max_cuts)
     // While the per-wave lines fit LDS (cfg1-4 shapes).  At the cfg5 shape (n = 2303: lines in the slot, several hundred rows to substitute per cut) a wave per cut
     // measured 1.8 x SLOWER than the whole workgroup on one cut (15.5 s against 8.7 s for the 128 goldens): there the block-wide version below stays.
     if (!(w.dbg & MLD_DBG_MIR_SERIAL) && w.mir_in_lds) {
-        int nc2 = 0;
-        for (int i0 = 0; i0 < m0; i0 += SOL_NT) {
-            const int i = i0 + tid;
-            nc2 = block_compact(sh, i < m0 && w.mir_eff[i] > -S_INF, (unsigned short)i, w.rowlist, nc2);
-        }
-        __syncthreads();
-        for (int t = tid; t < nc2; t += SOL_NT) w.colc[t] = w.mir_eff[w.rowlist[t]];
-        __syncthreads();
-        for (int t = tid; t < nc2; t += SOL_NT) {
-            const int i = w.rowlist[t];
-            const double e = w.colc[t];
-            int rank = 0;
-            for (int u = 0; u < nc2; ++u) { const double eu = w.colc[u]; rank += (eu > e) || (eu == e && (int)w.rowlist[u] < i); }
-            w.seclist[rank] = (unsigned short)i;
-        }
-        __syncthreads();
-        MLD_CHECK(w, nc2 <= m0 && nc2 <= (int)(w.rowlist - w.seclist), 121, nc2, m0);
-        double *axw = w.mir_cache + (size_t)wave * 2 * n;
-        unsigned short *rl = (unsigned short *)(axw + n);          // rows whose basic structural has a non-zero cut coefficient (at most n of them)
-        int added = 0;
-        for (int pos = 0; pos < nc2; pos += SOL_NW) {
-            if (m_start + added >= sh.cut_cap || added >= max_cuts) break;
-            const int t = pos + wave;
-            bool ok = t < nc2;
-            double bx = 0.0, nrm = 0.0, s_now = 0.0;
-            if (ok) {
-                const int i = w.seclist[t];
-                const double delta = w.mir_delta[i];
-                const double *g = w.Gs + (size_t)i * n;
-                const int jmax = w.nc_step > 0 ? min(n, (i / w.nc_step + 1) * w.nv_step) : n;      // causal rows (s_mir_phase_a)
-                // right-hand side after complementing / bound substitution
-                double rp = 0.0;
-                for (int j = lane; j < jmax; j += 64) {
-                    const double gj = g[j];
-                    if (gj == 0.0) continue;
-                    if (w.is_int[j]) { const double lo = w.lo[j], hi = w.hi[j]; if (lo == hi) rp -= gj * lo; else if (xs[j] > 0.5) rp -= gj; }
-                    else { const double lo = w.clo[j], hi = w.chi[j]; rp -= gj * (lo > -0.5 * S_BIG ? lo : hi); }
-                }
-                const double rhs = wave_all_sum(rp) + w.hs[i];
-                const double b = rhs / delta, fb = floor(b), f = b - fb;
-                ok = !(f < S_MIR_FMIN || f > 1.0 - S_MIR_FMIN);
-                if (ok) {
-                    const double kc = 1.0 / (delta * (1.0 - f));
-                    double bp = 0.0, nm = 0.0;
-                    for (int j = lane; j < n; j += 64) {
-                        double a = 0.0;
-                        const double gj = j < jmax ? g[j] : 0.0;
-                        if (gj != 0.0) {
-                            if (w.is_int[j]) {
-                                const double lo = w.lo[j], hi = w.hi[j];
-                                if (lo != hi) {
-                                    const bool comp = xs[j] > 0.5;
-                                    const double aa = (comp ? -gj : gj) / delta, fl = floor(aa + 1e-12), fj = aa - fl;
-                                    const double cf = fl + (fj > f ? (fj - f) / (1.0 - f) : 0.0);
-                                    if (comp) { a = -cf; bp -= cf; } else a = cf;
-                                }
-                            } else {
-                                const double lo = w.clo[j], hi = w.chi[j];
-                                const bool lof = lo > -0.5 * S_BIG, hif = hi < 0.5 * S_BIG;
-                                if (gj > 0) { if (!lof && hif) { a = kc * gj; bp += kc * gj * hi; } }
-                                else { if (lof) { a = -kc * (-gj); bp -= kc * (-gj) * lo; } }
-                            }
-                        }
-                        axw[j] = a;
-                        nm = fmax(nm, fabs(a));
-                    }
-                    bx = fb + wave_all_sum(bp);
-                    nrm = wave_all_max(nm);
-                    ok = nrm > 0.0;
-                    if (ok) {
-                        double sp = 0.0;
-                        for (int j = lane; j < n; j += 64) { const double a = axw[j] / nrm; axw[j] = a; sp += a * xs[j]; }
-                        s_now = bx / nrm - wave_all_sum(sp);
-                        ok = s_now < -1e-9;               // not violated after all (rounding): skip
-                    }
-                }
-            }
-            WAVE_MEM_SYNC();
-            if (lane == 0) sh.s_i[wave] = ok ? 1 : 0;
-            __syncthreads();
-            int before = 0, total = 0;
-            for (int u = 0; u < SOL_NW; ++u) { const int fl2 = sh.s_i[u]; if (u < wave) before += fl2; total += fl2; }
-            const int room = min(sh.cut_cap - (m_start + added), max_cuts - added);
-            if (ok && before < room) {
-                const int kcut = m_start + added + before;
-                MLD_CHECK(w, kcut >= m0 && kcut < w.mcap, 123, t, kcut);
-                double *gk = w.Gc + (size_t)(kcut - m0) * n, *dk = w.D + (size_t)kcut * ld;
-                for (int j = lane; j < n; j += 64) gk[j] = axw[j];
-                // dictionary row of the new slack: the cut row with the basic structurals substituted, dk = gk_N - sum_r gk[j_r] D[r,:] (rows of this round's
-                // cuts have slack basics: only rows below m_start can qualify)
-                int nbr = 0;
-                for (int r0 = 0; r0 < m_start; r0 += 64) {
-                    const int r = r0 + lane;
-                    bool fl2 = false;
-                    if (r < m_start) { const int j = w.basic[r]; fl2 = j < n && axw[j] != 0.0; }
-                    const unsigned long long bal = __ballot(fl2);
-                    if (fl2) rl[nbr + __popcll(bal & ((1ull << lane) - 1ull))] = (unsigned short)r;
-                    nbr += __popcll(bal);
-                }
-                WAVE_MEM_SYNC();
-                MLD_CHECK(w, nbr <= n && nbr <= m_start, 124, nbr, m_start);
-                const glb_f64 *Dg = (const glb_f64 *)w.D;
-                double dp = 0.0;
-                for (int c = lane; c < n; c += 64) {
-                    const int j = w.nonbasic[c];
-                    double acc = j < n ? axw[j] : 0.0;
-                    int u = 0;
-                    for (; u + 8 <= nbr; u += 8) {      // eight independent loads of the rows in flight
-                        double v[8], cf[8];
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) { const int r = rl[u + q]; v[q] = Dg[(size_t)r * ld + c]; cf[q] = axw[w.basic[r]]; }
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) acc -= cf[q] * v[q];
-                    }
-                    for (; u < nbr; ++u) { const int r = rl[u]; acc -= axw[w.basic[r]] * Dg[(size_t)r * ld + c]; }
-                    dk[c] = acc;
-                    dp += acc * w.xN[c];
-                }
-                const double dsum = wave_all_sum(dp);
-                if (lane == 0) {
-                    w.hc[kcut - m0] = bx / nrm;
-                    dk[n] = s_now + dsum;
-                    w.basic[kcut] = n + kcut; w.where[n + kcut] = -1 - kcut;
-                    w.xB[kcut] = s_now;
-                    w.lo[n + kcut] = 0.0; w.hi[n + kcut] = S_INF;
-                }
-            }
-            added += min(total, room);
-            __syncthreads();
-        }
+        const int added = (w.all_lds && !(w.dbg & MLD_DBG_CUTS_R4)) ? s_mir_build_waves<true>(w, sh, max_cuts, m_start, xs) : s_mir_build_waves<false>(w, sh, max_cuts, m_start, xs);
         __syncthreads();
         if (tid == 0) sh.m = m_start + added;
 #ifdef MLD_CUT_PROF
@@ -3263,7 +3513,7 @@ __device__ __noinline__ int s_cut_round(const Ws &w, Shared &sh, const SolverSha
 #endif
     int k = (S.debug & MLD_DBG_GMI_SERIAL) ? s_gmi_round_serial(w, sh, S.cuts_per_round) : s_gmi_round(w, sh, S.cuts_per_round);
 #ifdef MLD_CUT_PROF
-    if (threadIdx.x == 0) sh.cprof[2] += wall_clock64() - t0;
+    if (threadIdx.x == 0) { sh.cprof[2] += wall_clock64() - t0; sh.cprof[3] += 1; }
 #endif
     if (S.mir_per_round > 0) k += s_mir_round(w, sh, S.mir_per_round);
     return k;
@@ -3344,7 +3594,7 @@ __device__ __forceinline__ bool s_setup_entry(Ws &w, Shared &sh, const SolverSha
         for (int k = 0; k < 5; ++k) sh.pprof[k] = 0;
 #endif
 #ifdef MLD_CUT_PROF
-        sh.cprof[0] = sh.cprof[1] = sh.cprof[2] = 0;
+        for (int k = 0; k < 11; ++k) sh.cprof[k] = 0;
 #endif
     }
     for (int j = tid; j < n; j += SOL_NT) { w.lo[j] = e.plb[j]; w.hi[j] = e.pub[j]; e.v_out[j] = 0.0; }
@@ -3876,6 +4126,9 @@ __device__ __forceinline__ void s_write_results(Shared &sh, const BatchDev &B, c
 #endif
 #ifdef MLD_CUT_PROF
         if (B.prof_out && !skipped) { B.prof_out[(size_t)inst * 8 + 3] = sh.cprof[0]; B.prof_out[(size_t)inst * 8 + 4] = sh.cprof[1]; B.prof_out[(size_t)inst * 8 + 7] = sh.cprof[2]; }   // (diagnostic build: slots 3 / 4 / 7 = c-MIR scoring / c-MIR build / Gomory)
+#if MLD_CUT_PROF == 2
+        if (B.prof_out && !skipped) for (int k = 0; k < 8; ++k) B.prof_out[(size_t)inst * 8 + k] = sh.cprof[3 + k];      // (the counts instead: scripts/gpu_cut_prof.py counts)
+#endif
 #endif
     }
     if (B.ho) { __threadfence(); __syncthreads(); if (threadIdx.x == 0) __hip_atomic_fetch_add(B.finished, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
