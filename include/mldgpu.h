@@ -407,6 +407,52 @@ int mld_evaluate_batch(mld_problem_t *, const double *v,
                        double *obj_out, double *constr_vio_out, int32_t *constr_row_out,
                        double *int_vio_out, double *bound_vio_out);
 
+/* ---- resident disturbance profiles: forecasts and scenario columns by index ---------------------------------------------------------------------
+ * Every disturbance window the reference hands a controller is a slice of a time series it holds once:
+ *   get_omega_tilde_k_hat / _act   profile.values[start:start + N_tilde].flatten()    (examples/.../modelling/micro_grid_agents.py:236-298)
+ *   get_omega_tilde_scenario       scenarios.ravel(order='F')[flat_index : flat_index + N_tilde*nomega]   (:206-232; the F-order ravel of its
+ *                                  (intervals_per_day*nomega, n_days) matrix is the original (n, nomega) series, row-major)
+ * and its scenario-based controllers draw 20 such columns per device at every step (examples/.../micro_grid_control_simulation.py:200-227).  A window is
+ * (offset into a flat series, length): with the series resident in HBM, 20 columns of 200 doubles cross the bus as 20 integers.
+ *
+ * mld_upload_profiles: a flat library of lib_len doubles, owned by the PROBLEM and independent of the batch -- it survives mld_upload_batch at any batch
+ * size, mld_select_inputs and mld_advance_batch.  A second call replaces it and invalidates every resident start array below; lib_len = 0 frees it;
+ * mld_problem_destroy frees it.  group_width: n_groups positive widths that sum to nomega; they partition the disturbance channels 0 .. nomega-1 in order,
+ * one group per fused device (NULL / n_groups = 0: one group of width nomega).  A series of group g is stored row-major (time, width_g), as the reference
+ * stores a device's profile; where the series of a group begin inside the library is the caller's business (the starts say so).
+ * MLD_ERR_INVALID, nothing changed: nomega == 0; widths that are not positive or do not sum to nomega; lib_len < 0; lib == NULL with lib_len > 0.
+ *
+ * THE WINDOW RULE.  For a start s of group g (first channel goff_g) and a step offset `step`, for k < N_tilde and channel j of group g
+ *     omega[k*nomega + j] = lib[s + (step + k)*width_g + (j - goff_g)]
+ * A start is valid iff s >= 0 and s + (step + N_tilde)*width_g <= lib_len.  Every start of every call is tested on the host BEFORE anything is queued --
+ * the first offender is named (instance, column, group) -- and per group the largest start of a resident array is remembered on the host, so that a call
+ * with start == NULL is tested without reading the device: no kernel is ever launched with an offset that has not passed.  All entry points: run on the
+ * problem's stream and wait for that stream only; MLD_ERR_NO_DEVICE without a device; MLD_ERR_INVALID with nothing changed for no library, step < 0, an
+ * invalid start, no batch resident, or a launched solve not finished. */
+int mld_upload_profiles(mld_problem_t *, int64_t lib_len, const double *lib, int n_groups, const int32_t *group_width);
+/* The forecast omega of EVERY instance of the resident batch replaced by its window; start (batch, n_groups).  x0, model_idx and fixed_bin stay.  The starts
+ * stay resident: start == NULL re-uses them with another step -- how a closed loop slides every instance's window along its own series (NULL without
+ * resident starts for this batch size is refused; the starts belong to a batch size and outlive an upload of the same size).
+ * Between mld_advance_batch and the next solve only the forecast is touched: the batch stays advanced, the plan stays readable by
+ * mld_warm_start_from_previous, and a MIP start built from it stays -- a start is a hint that is verified against the new rows.  All instances get the new
+ * forecast, ALSO those the advance skipped (they kept their state, but time moves on for them too).  In every other state the call is
+ * mld_select_inputs: new inputs, so the constraint blocks, the MIP start, the cutoffs and the solved state are cleared. */
+int mld_forecast_from_profiles(mld_problem_t *, const int64_t *start, int step);
+/* mld_upload_constraint_blocks_x with the columns gathered on the device: start (batch, n_cols, n_groups); col_rows and x_cols as there (same meaning,
+ * same checks).  Fills the same resident blocks, so the solve, mld_evaluate_batch with n_cols == 0 and the in-kernel hand-off see no difference.  A column
+ * with reduced col_rows still reads a FULL window: the rows beyond are never used, but the bounds test covers all N_tilde steps.  start == NULL re-uses
+ * the resident column starts (same n_cols, else refused) with another step, e.g. min / max profiles sliding one step; n_cols = 0 clears the blocks. */
+int mld_constraint_blocks_from_profiles(mld_problem_t *, int n_cols, const int64_t *start, int step, const int32_t *col_rows, const double *x_cols);
+/* mld_evaluate_batch (above) with n_cols >= 1 validation columns gathered on the device instead of uploaded: start (batch, n_cols, n_groups), required;
+ * everything else as there -- the same slices of columns, the same launches, the same results.  The resident blocks and resident starts are neither used
+ * nor changed. */
+int mld_evaluate_batch_profiles(mld_problem_t *, const double *v, int n_cols, const int64_t *start, int step, const int32_t *col_rows, const double *x_cols,
+                                double *obj_out, double *constr_vio_out, int32_t *constr_row_out, double *int_vio_out, double *bound_vio_out);
+/* Read-back of the resident constraint blocks however they got there (the counterpart of mld_download_inputs): *n_cols_out columns, omega_cols (batch,
+ * n_cols, N_tilde*nomega), col_rows (n_cols; N_tilde*nc for blocks uploaded without col_rows), x_cols (batch, n_cols, nx; MLD_ERR_INVALID when the
+ * resident blocks have none).  Every argument may be NULL; with all arrays NULL only the count is reported. */
+int mld_download_constraint_blocks(mld_problem_t *, int32_t *n_cols_out, double *omega_cols, int32_t *col_rows, double *x_cols);
+
 /* Per-instance telemetry of the last solve: time spent inside the solve kernel (device wall clock, ns) and
  * the number of dictionary rows the rank-1 updates touched (x *row_bytes x 2 = bytes streamed by pivots). */
 int mld_download_telemetry(mld_problem_t *, int64_t *latency_ns, int64_t *rows_updated, int64_t *row_bytes);

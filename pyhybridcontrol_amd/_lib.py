@@ -53,6 +53,7 @@ EXPORTS = ("mld_device_count", "mld_set_device", "mld_last_error", "mld_version"
            "mld_problem_create", "mld_problem_set_cost", "mld_problem_destroy", "mld_cost_assemble",
            "mld_solve_batch", "mld_upload_batch", "mld_upload_constraint_blocks", "mld_upload_constraint_blocks_x", "mld_solve_resident", "mld_problem_use_stream", "mld_solve_launch", "mld_solve_finish", "mld_download_results", "mld_download_telemetry",
            "mld_rhs_batch", "mld_problem_set_opts", "mld_problem_get_opts", "mld_advance_batch", "mld_advance_batch2", "mld_set_warm_start", "mld_warm_start_from_previous", "mld_set_cutoffs", "mld_record_open_nodes", "mld_download_open_nodes", "mld_set_handoff", "mld_handoff_stats", "mld_set_handoff_policy", "mld_set_std_block", "mld_download_inputs", "mld_stage_inputs", "mld_select_inputs", "mld_upload_instance_cost", "mld_download_instance_cost", "mld_predict_batch", "mld_evaluate_batch", "mld_gather_results",
+           "mld_upload_profiles", "mld_forecast_from_profiles", "mld_constraint_blocks_from_profiles", "mld_evaluate_batch_profiles", "mld_download_constraint_blocks",
            "mld_comm_unique_id", "mld_comm_init", "mld_gather", "mld_comm_destroy")
 
 
@@ -73,6 +74,12 @@ def load():
             fn.restype = C.c_int
     dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
     lib.mld_evaluate_batch.argtypes = [C.c_void_p, dp, C.c_int, dp, ip, dp, dp, dp, ip, dp, dp]
+    lp = C.POINTER(C.c_int64)
+    lib.mld_upload_profiles.argtypes = [C.c_void_p, C.c_int64, dp, C.c_int, ip]
+    lib.mld_forecast_from_profiles.argtypes = [C.c_void_p, lp, C.c_int]
+    lib.mld_constraint_blocks_from_profiles.argtypes = [C.c_void_p, C.c_int, lp, C.c_int, ip, dp]
+    lib.mld_evaluate_batch_profiles.argtypes = [C.c_void_p, dp, C.c_int, lp, C.c_int, ip, dp, dp, dp, ip, dp, dp]
+    lib.mld_download_constraint_blocks.argtypes = [C.c_void_p, ip, dp, ip, dp]
     if int(lib.mld_opts_size()) != C.sizeof(Opts):
         raise MldGpuError("libmldgpu.so was built with another layout of mld_opts (%d bytes, this binding %d): rebuild it (python -m pyhybridcontrol_amd.build)"
                           % (lib.mld_opts_size(), C.sizeof(Opts)))

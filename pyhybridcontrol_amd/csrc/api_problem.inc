@@ -368,6 +368,11 @@ struct mld_problem {
     /* in-kernel sub-tree hand-off (mld_set_handoff) */
     int ho_enable = 0, ho_sub_nodes = 0, ho_max_gen = 0, ho_max_children = 0; double ho_factor = 2.0; bool ho_ran = false;
     int ho_max_tree = 160, ho_donate = 0, ho_rounds = 0;   /* items per tree; shallow open nodes handed off per node-limit, times */
+    /* resident disturbance profiles (mld_upload_profiles): owned by the problem, not by the batch -- free_batch leaves them alone.  The start arrays belong
+     * to a batch SIZE (pf_fbatch / pf_cbatch, 0 = none resident); per group the largest resident start is kept on the host, so that a call with
+     * start == NULL is checked against the window rule without reading the device */
+    DevBuf<double> pf_lib; long long pf_len = 0; int pf_groups = 0; std::vector<int> pf_width; DevBuf<PfChan> pf_chan;
+    DevBuf<long long> pf_fstart, pf_cstart; int pf_fbatch = 0, pf_cbatch = 0, pf_ccols = 0; std::vector<long long> pf_fmax, pf_cmax;
     long long ho_stats[4] = {};  /* last solve: items published, trees split, trees left unfinished, entries the queue had no room for (always 0: such trees stay unfinished) */
 };
 
@@ -1804,6 +1809,213 @@ int mld_download_inputs(mld_problem_t *p, double *x0, double *omega)
     return MLD_OK;
 }
 
+/* ---- resident disturbance profiles ----------------------------------------------------------------------------------------------------------------
+ * The reference cuts every disturbance window out of a series it holds once (get_omega_tilde_k_hat / _act, modelling/micro_grid_agents.py:236-298;
+ * get_omega_tilde_scenario, :206-232); here the series are a flat library in HBM and a window is a start offset (profiles.inc: k_profile_windows and the
+ * window rule).  Every start is tested on the host before anything is queued: no kernel is launched with an offset that has not passed. */
+int mld_upload_profiles(mld_problem_t *p, int64_t lib_len, const double *lib, int n_groups, const int32_t *group_width)
+{
+    if (mld_device_count() <= 0) { mld_set_error("no HIP device (libmldgpu has no CPU fallback)"); return MLD_ERR_NO_DEVICE; }
+    MLD_NOT_IN_FLIGHT(p, "mld_upload_profiles");
+    if (!p) { mld_set_error("mld_upload_profiles: null problem"); return MLD_ERR_INVALID; }
+    const int nomega = p->model->dims.nomega;
+    if (nomega == 0) { mld_set_error("mld_upload_profiles: the model has no disturbance (nomega = 0): there is nothing a profile could fill"); return MLD_ERR_INVALID; }
+    if (lib_len < 0 || (lib_len > 0 && !lib)) { mld_set_error("mld_upload_profiles: lib_len = %lld%s", (long long)lib_len, lib_len > 0 ? " without a library" : ""); return MLD_ERR_INVALID; }
+    if (n_groups < 0 || n_groups > nomega || (n_groups > 0 && !group_width)) { mld_set_error("mld_upload_profiles: n_groups = %d (0 .. nomega = %d, with group_width)", n_groups, nomega); return MLD_ERR_INVALID; }
+    std::vector<int> width;
+    if (n_groups == 0) width.assign(1, nomega);
+    else {
+        long long sum = 0;
+        for (int g = 0; g < n_groups; ++g) {
+            if (group_width[g] < 1) { mld_set_error("mld_upload_profiles: group_width[%d] = %d (every group needs at least one channel)", g, group_width[g]); return MLD_ERR_INVALID; }
+            sum += group_width[g];
+        }
+        if (sum != nomega) { mld_set_error("mld_upload_profiles: the group widths sum to %lld, not to nomega = %d", sum, nomega); return MLD_ERR_INVALID; }
+        width.assign(group_width, group_width + n_groups);
+    }
+    if (lib_len == 0) {      /* frees the library; the start arrays go with it */
+        p->pf_lib.reset(); p->pf_chan.reset(); p->pf_fstart.reset(); p->pf_cstart.reset();
+        p->pf_len = 0; p->pf_groups = 0; p->pf_width.clear(); p->pf_fbatch = p->pf_cbatch = p->pf_ccols = 0;
+        return MLD_OK;
+    }
+    std::vector<PfChan> chan;
+    for (int g = 0; g < (int)width.size(); ++g) for (int o = 0; o < width[g]; ++o) chan.push_back(PfChan{g, o, width[g]});
+    DevBuf<double> d_lib; DevBuf<PfChan> d_chan;      /* built beside the resident library: a call that fails leaves it as it was */
+    HIP_TRY(d_lib.alloc((size_t)lib_len));
+    HIP_TRY(d_chan.alloc(chan.size()));
+    const hipStream_t sq = p->stream;
+    auto queue = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(d_lib, lib, sizeof(double) * (size_t)lib_len, hipMemcpyHostToDevice, sq));
+        HIP_TRY(hipMemcpyAsync(d_chan, chan.data(), sizeof(PfChan) * chan.size(), hipMemcpyHostToDevice, sq));
+        return MLD_OK;
+    };
+    const int rc = queue();
+    const hipError_t es = hipStreamSynchronize(sq);
+    if (rc) return rc;
+    HIP_TRY(es);
+    p->pf_lib = std::move(d_lib); p->pf_chan = std::move(d_chan);
+    p->pf_len = lib_len; p->pf_groups = (int)width.size(); p->pf_width = width;
+    p->pf_fstart.reset(); p->pf_cstart.reset(); p->pf_fbatch = p->pf_cbatch = p->pf_ccols = 0;      /* starts pointed into the library that is gone */
+    return MLD_OK;
+}
+
+/* what the three consumers share: a library and a step the window rule can be tested with */
+static int profile_ready(const mld_problem *p, const char *who, int step)
+{
+    if (!p->pf_len) { mld_set_error("%s: no profile library resident (mld_upload_profiles)", who); return MLD_ERR_INVALID; }
+    if (step < 0 || step > INT_MAX - p->N) { mld_set_error("%s: step = %d (must be >= 0)", who, step); return MLD_ERR_INVALID; }
+    return MLD_OK;
+}
+
+/* every start of a (batch, n_cols, n_groups) array against the window rule; the first offender is named; gmax: per group the largest start */
+static int profile_check_starts(const mld_problem *p, const char *who, const int64_t *start, int batch, int n_cols, int step, std::vector<long long> &gmax)
+{
+    const int G = p->pf_groups;
+    gmax.assign(G, 0);
+    const int64_t *s = start;
+    for (int b = 0; b < batch; ++b)
+        for (int c = 0; c < n_cols; ++c)
+            for (int g = 0; g < G; ++g, ++s) {
+                if (!profile_start_ok(*s, p->pf_len, step, p->N, p->pf_width[g])) {
+                    mld_set_error("%s: start %lld of instance %d, column %d, group %d (width %d) at step %d: the window [%lld, %lld) leaves the library of %lld doubles",
+                                  who, (long long)*s, b, c, g, p->pf_width[g], step, (long long)*s + (long long)step * p->pf_width[g],
+                                  (long long)*s + ((long long)step + p->N) * p->pf_width[g], p->pf_len);
+                    return MLD_ERR_INVALID;
+                }
+                gmax[g] = std::max<long long>(gmax[g], *s);
+            }
+    return MLD_OK;
+}
+
+/* resident starts under another step: the remembered maxima decide (the smallest start was >= 0 when the array was uploaded) */
+static int profile_check_resident(const mld_problem *p, const char *who, const std::vector<long long> &gmax, int step)
+{
+    for (int g = 0; g < p->pf_groups; ++g)
+        if (!profile_start_ok(gmax[g], p->pf_len, step, p->N, p->pf_width[g])) {
+            mld_set_error("%s: step %d moves the largest resident start of group %d (%lld, width %d) past the end of the library: the window would end at %lld of %lld doubles",
+                          who, step, g, gmax[g], p->pf_width[g], gmax[g] + ((long long)step + p->N) * p->pf_width[g], p->pf_len);
+            return MLD_ERR_INVALID;
+        }
+    return MLD_OK;
+}
+
+static void launch_profile_windows(const mld_problem *p, hipStream_t sq, int rows, int cols, int ld_cols, int col0, const long long *d_start, int step, double *dst)
+{
+    const long long total = (long long)rows * p->nW;
+    hipLaunchKernelGGL(k_profile_windows, dim3(profile_grid(total)), dim3(256), 0, sq, rows, p->nW, p->model->dims.nomega, cols, ld_cols, col0, p->pf_groups, d_start,
+                       p->pf_chan.get(), step, p->pf_lib.get(), dst);
+}
+
+int mld_forecast_from_profiles(mld_problem_t *p, const int64_t *start, int step)
+{
+    static const char who[] = "mld_forecast_from_profiles";
+    if (mld_device_count() <= 0) { mld_set_error("no HIP device (libmldgpu has no CPU fallback)"); return MLD_ERR_NO_DEVICE; }
+    MLD_NOT_IN_FLIGHT(p, who);
+    if (!p || p->batch < 1) { mld_set_error("%s: no batch resident (mld_upload_batch)", who); return MLD_ERR_INVALID; }
+    int rc;
+    if ((rc = profile_ready(p, who, step))) return rc;
+    const int batch = p->batch, G = p->pf_groups;
+    std::vector<long long> gmax;
+    if (start) { if ((rc = profile_check_starts(p, who, start, batch, 1, step, gmax))) return rc; }
+    else {
+        if (p->pf_fbatch != batch) { mld_set_error("%s: start == NULL, but no starts of this batch are resident (pass them once)", who); return MLD_ERR_INVALID; }
+        if ((rc = profile_check_resident(p, who, p->pf_fmax, step))) return rc;
+    }
+    DevBuf<long long> d_start;
+    if (start) HIP_TRY(d_start.alloc((size_t)batch * G));
+    const hipStream_t sq = p->stream;
+    /* the new forecast is gathered into the spare input buffer and swapped in once the stream has finished: a call that fails changes nothing */
+    auto queue = [&]() -> int {
+        if (start) HIP_TRY(hipMemcpyAsync(d_start, start, sizeof(long long) * (size_t)batch * G, hipMemcpyHostToDevice, sq));
+        launch_profile_windows(p, sq, batch, 1, 1, 0, start ? d_start.get() : p->pf_fstart.get(), step, p->bat.omegab.get());
+        HIP_TRY(hipGetLastError());
+        return MLD_OK;
+    };
+    rc = queue();
+    const hipError_t es = hipStreamSynchronize(sq);
+    if (rc) return rc;
+    HIP_TRY(es);
+    std::swap(p->bat.omega, p->bat.omegab);
+    if (start) { p->pf_fstart = std::move(d_start); p->pf_fbatch = batch; p->pf_fmax = gmax; }
+    if (!p->advanced) {      /* new inputs, as mld_select_inputs; after mld_advance_batch the blocks are gone already and plan and start stay */
+        p->n_xcols = 0;
+        p->has_warm = false; p->solved = false; p->has_cutoff = false;
+    }
+    return MLD_OK;
+}
+
+int mld_constraint_blocks_from_profiles(mld_problem_t *p, int n_cols, const int64_t *start, int step, const int32_t *col_rows, const double *x_cols)
+{
+    static const char who[] = "mld_constraint_blocks_from_profiles";
+    if (mld_device_count() <= 0) { mld_set_error("no HIP device (libmldgpu has no CPU fallback)"); return MLD_ERR_NO_DEVICE; }
+    MLD_NOT_IN_FLIGHT(p, who);
+    if (!p || p->batch < 1) { mld_set_error("%s: upload the batch first", who); return MLD_ERR_INVALID; }
+    if (n_cols < 0) { mld_set_error("%s: n_cols = %d", who, n_cols); return MLD_ERR_INVALID; }
+    if (n_cols == 0) { p->n_xcols = 0; return MLD_OK; }
+    int rc;
+    if ((rc = profile_ready(p, who, step))) return rc;
+    const int batch = p->batch, G = p->pf_groups;
+    if ((long long)batch * n_cols > INT_MAX) { mld_set_error("%s: batch x n_cols = %lld windows (at most %d)", who, (long long)batch * n_cols, INT_MAX); return MLD_ERR_INVALID; }
+    if (col_rows) for (int c = 0; c < n_cols; ++c) if (col_rows[c] < 0 || col_rows[c] > p->m0) { mld_set_error("%s: col_rows[%d]=%d outside [0,%d]", who, c, col_rows[c], p->m0); return MLD_ERR_INVALID; }
+    std::vector<long long> gmax;
+    if (start) { if ((rc = profile_check_starts(p, who, start, batch, n_cols, step, gmax))) return rc; }
+    else {
+        if (p->pf_cbatch != batch) { mld_set_error("%s: start == NULL, but no column starts of this batch are resident (pass them once)", who); return MLD_ERR_INVALID; }
+        if (p->pf_ccols != n_cols) { mld_set_error("%s: start == NULL with n_cols = %d, but the resident starts are those of %d columns", who, n_cols, p->pf_ccols); return MLD_ERR_INVALID; }
+        if ((rc = profile_check_resident(p, who, p->pf_cmax, step))) return rc;
+    }
+    /* from here on as mld_upload_constraint_blocks_x, with the gather in place of the copy of omega_cols */
+    DevBuf<long long> d_start;
+    if (start) HIP_TRY(d_start.alloc((size_t)batch * n_cols * G));
+    p->n_xcols = 0;
+    const size_t need = (size_t)batch * n_cols * p->nW;
+    if (need > p->xcols_cap) {
+        p->xcols_cap = 0;
+        HIP_TRY(p->bat.xcols.alloc(need));
+        p->xcols_cap = need;
+    }
+    p->bat.xrows.reset();
+    if (col_rows) HIP_TRY(p->bat.xrows.alloc(n_cols));
+    p->has_xcols_x = false;
+    const bool with_x = x_cols && p->nx;
+    const size_t nxs = (size_t)batch * n_cols * p->nx;
+    if (with_x) HIP_TRY(p->bat.xcols_x.alloc(nxs));
+    const hipStream_t sq = p->stream;
+    auto queue = [&]() -> int {
+        if (start) HIP_TRY(hipMemcpyAsync(d_start, start, sizeof(long long) * (size_t)batch * n_cols * G, hipMemcpyHostToDevice, sq));
+        if (col_rows) HIP_TRY(hipMemcpyAsync(p->bat.xrows, col_rows, sizeof(int) * n_cols, hipMemcpyHostToDevice, sq));
+        if (with_x) HIP_TRY(hipMemcpyAsync(p->bat.xcols_x, x_cols, sizeof(double) * nxs, hipMemcpyHostToDevice, sq));
+        launch_profile_windows(p, sq, batch * n_cols, n_cols, n_cols, 0, start ? d_start.get() : p->pf_cstart.get(), step, p->bat.xcols.get());
+        HIP_TRY(hipGetLastError());
+        return MLD_OK;
+    };
+    rc = queue();
+    const hipError_t es = hipStreamSynchronize(sq);
+    if (rc) return rc;
+    HIP_TRY(es);
+    if (start) { p->pf_cstart = std::move(d_start); p->pf_cbatch = batch; p->pf_ccols = n_cols; p->pf_cmax = gmax; }
+    p->has_xcols_x = with_x;
+    p->n_xcols = n_cols;
+    return MLD_OK;
+}
+
+int mld_download_constraint_blocks(mld_problem_t *p, int32_t *n_cols_out, double *omega_cols, int32_t *col_rows, double *x_cols)
+{
+    MLD_NOT_IN_FLIGHT(p, "mld_download_constraint_blocks");
+    if (!p || p->batch < 1) { mld_set_error("mld_download_constraint_blocks: nothing uploaded"); return MLD_ERR_INVALID; }
+    const int nc = p->n_xcols;
+    if (x_cols && nc && !p->has_xcols_x) { mld_set_error("mld_download_constraint_blocks: x_cols asked for, but the resident blocks have none (every column uses the instance's x0)"); return MLD_ERR_INVALID; }
+    if (n_cols_out) *n_cols_out = nc;
+    if (!nc) return MLD_OK;
+    if (omega_cols) HIP_TRY(hipMemcpy(omega_cols, p->bat.xcols, sizeof(double) * (size_t)p->batch * nc * p->nW, hipMemcpyDeviceToHost));
+    if (col_rows) {
+        if (p->bat.xrows) HIP_TRY(hipMemcpy(col_rows, p->bat.xrows, sizeof(int) * nc, hipMemcpyDeviceToHost));
+        else for (int c = 0; c < nc; ++c) col_rows[c] = p->m0;
+    }
+    if (x_cols) HIP_TRY(hipMemcpy(x_cols, p->bat.xcols_x, sizeof(double) * (size_t)p->batch * nc * p->nx, hipMemcpyDeviceToHost));
+    return MLD_OK;
+}
+
 /* Per-instance linear cost of the resident batch (the reference rebuilds its objective with the current tariff before every solve() call,
  * micro_grid_control_simulation.py:194-198,229: N calls replaced by one batch may carry N price vectors).  Weights on v are kept as uploaded; weights on
  * x_tilde / y_tilde are pulled back through the tightened model's condensed maps by ONE GEMM per model (k_inst_pullback; k_inst_pullback_valu under
@@ -1948,26 +2160,38 @@ int mld_predict_batch(mld_problem_t *p, const double *v, double *x_out, double *
  * does) and any disturbance columns (the layout of gen_evo_constraints, controller_base.py:411-456).  Kernels: evaluate.inc.  Every result is built
  * in a buffer of its own and every path waits for the stream, so a call that fails changes nothing; nothing the solve path reads is written. */
 #define EV_SLICE_BYTES ((size_t)256 << 20)      /* device copy of the caller's validation columns: at most this much at a time (at least one column) */
-int mld_evaluate_batch(mld_problem_t *p, const double *v, int n_cols, const double *omega_cols, const int32_t *col_rows, const double *x_cols,
-                       double *obj_out, double *constr_vio_out, int32_t *constr_row_out, double *int_vio_out, double *bound_vio_out)
+/* The columns of a call come from one of two sources: the caller's array (omega_cols, mld_evaluate_batch) or starts into the resident profile library
+ * (start / step, mld_evaluate_batch_profiles: from_profiles).  The sources differ in how a slice of columns reaches the slice buffer d_om -- a strided copy
+ * from the host, or k_profile_windows gathering it there -- and in nothing else: the same slices, the same launches of k_evaluate on the same buffer. */
+static int evaluate_impl(mld_problem_t *p, const char *who, const double *v, int n_cols, const double *omega_cols, bool from_profiles, const int64_t *start, int step,
+                         const int32_t *col_rows, const double *x_cols,
+                         double *obj_out, double *constr_vio_out, int32_t *constr_row_out, double *int_vio_out, double *bound_vio_out)
 {
     if (mld_device_count() <= 0) { mld_set_error("no HIP device (libmldgpu has no CPU fallback)"); return MLD_ERR_NO_DEVICE; }
-    MLD_NOT_IN_FLIGHT(p, "mld_evaluate_batch");
-    if (!p || p->batch < 1) { mld_set_error("mld_evaluate_batch: no batch resident (mld_upload_batch)"); return MLD_ERR_INVALID; }
+    MLD_NOT_IN_FLIGHT(p, who);
+    if (!p || p->batch < 1) { mld_set_error("%s: no batch resident (mld_upload_batch)", who); return MLD_ERR_INVALID; }
     const mld_dims &d = p->model->dims;
     const int n = p->n, nx = p->nx, nW = p->nW, batch = p->batch, m0 = p->m0, M = p->n_models;
-    if (n_cols < 0) { mld_set_error("mld_evaluate_batch: n_cols = %d", n_cols); return MLD_ERR_INVALID; }
-    if (n_cols > 0 && nW && !omega_cols) { mld_set_error("mld_evaluate_batch: n_cols = %d without omega_cols (nomega > 0)", n_cols); return MLD_ERR_INVALID; }
-    if (x_cols && nx == 0) { mld_set_error("mld_evaluate_batch: x_cols given but the model has no state (nx = 0)"); return MLD_ERR_INVALID; }
-    if (col_rows) for (int c = 0; c < n_cols; ++c) if (col_rows[c] < 0 || col_rows[c] > m0) { mld_set_error("mld_evaluate_batch: col_rows[%d]=%d outside [0,%d]", c, col_rows[c], m0); return MLD_ERR_INVALID; }
-    if (!v && !p->solved) { mld_set_error("mld_evaluate_batch: the resident batch has not been solved since its upload / selection (there is no plan to evaluate; pass v)"); return MLD_ERR_INVALID; }
-    if (!v && p->advanced) { mld_set_error("mld_evaluate_batch: mld_advance_batch has moved the inputs on -- the resident plan belongs to inputs that are gone (solve again, or pass v)"); return MLD_ERR_INVALID; }
+    if (n_cols < 0) { mld_set_error("%s: n_cols = %d", who, n_cols); return MLD_ERR_INVALID; }
+    if (!from_profiles && n_cols > 0 && nW && !omega_cols) { mld_set_error("%s: n_cols = %d without omega_cols (nomega > 0)", who, n_cols); return MLD_ERR_INVALID; }
+    if (from_profiles && n_cols < 1) { mld_set_error("%s: n_cols = %d (the profile columns of a call: at least one)", who, n_cols); return MLD_ERR_INVALID; }
+    if (from_profiles && !start) { mld_set_error("%s: start == NULL (the resident column starts belong to the problem's blocks and are not used here)", who); return MLD_ERR_INVALID; }
+    if (x_cols && nx == 0) { mld_set_error("%s: x_cols given but the model has no state (nx = 0)", who); return MLD_ERR_INVALID; }
+    if (col_rows) for (int c = 0; c < n_cols; ++c) if (col_rows[c] < 0 || col_rows[c] > m0) { mld_set_error("%s: col_rows[%d]=%d outside [0,%d]", who, c, col_rows[c], m0); return MLD_ERR_INVALID; }
+    if (!v && !p->solved) { mld_set_error("%s: the resident batch has not been solved since its upload / selection (there is no plan to evaluate; pass v)", who); return MLD_ERR_INVALID; }
+    if (!v && p->advanced) { mld_set_error("%s: mld_advance_batch has moved the inputs on -- the resident plan belongs to inputs that are gone (solve again, or pass v)", who); return MLD_ERR_INVALID; }
+    int rc;
+    if (from_profiles) {      /* every start against the window rule, before anything is queued */
+        std::vector<long long> gmax;
+        if ((rc = profile_ready(p, who, step))) return rc;
+        if ((long long)batch * n_cols > INT_MAX) { mld_set_error("%s: batch x n_cols = %lld windows (at most %d)", who, (long long)batch * n_cols, INT_MAX); return MLD_ERR_INVALID; }
+        if ((rc = profile_check_starts(p, who, start, batch, n_cols, step, gmax))) return rc;
+    }
     if (!obj_out && !constr_vio_out && !constr_row_out && !int_vio_out && !bound_vio_out) return MLD_OK;
     const hipStream_t sq = p->stream;
     const bool want_c = constr_vio_out || constr_row_out;
     const bool valu = (p->opts.reserved & MLD_DBG_GEMM_VALU) != 0;
     mld_model *mo = p->model;
-    int rc;
     if (want_c && m0 && (mo->cond_N != p->N || !mo->out64) && (rc = condense_model_device(mo, p->N, nullptr, sq))) return rc;
     const int *midx = p->has_midx ? p->bat.model_idx.get() : nullptr;
     const size_t nout = n_cols > 0 ? (size_t)n_cols : 1;      /* constraint results per instance */
@@ -1975,7 +2199,7 @@ int mld_evaluate_batch(mld_problem_t *p, const double *v, int n_cols, const doub
     const size_t col_bytes = sizeof(double) * (size_t)batch * std::max(1, nW + (x_cols ? nx : 0));
     const int slice = n_cols > 0 ? (int)std::min<size_t>((size_t)n_cols, std::max<size_t>(1, EV_SLICE_BYTES / col_bytes)) : 0;
     DevBuf<double> d_v, d_hv, d_part, d_om, d_xc, d_vio, d_obj, d_iv, d_bv, d_qi, d_rc, d_one;
-    DevBuf<int> d_rows, d_row;
+    DevBuf<int> d_rows, d_row; DevBuf<long long> d_start;
     if (v) HIP_TRY(d_v.alloc((size_t)batch * std::max(1, n)));
     if (want_c) {
         HIP_TRY(d_hv.alloc((size_t)batch * std::max(1, m0)));
@@ -1984,6 +2208,7 @@ int mld_evaluate_batch(mld_problem_t *p, const double *v, int n_cols, const doub
         if (slice && nW) HIP_TRY(d_om.alloc((size_t)batch * slice * nW));
         if (slice && x_cols) HIP_TRY(d_xc.alloc((size_t)batch * slice * nx));
         if (slice && col_rows) HIP_TRY(d_rows.alloc(n_cols));
+        if (from_profiles) HIP_TRY(d_start.alloc((size_t)batch * n_cols * p->pf_groups));
     }
     const bool inst_q = p->has_quad || p->ic_ld;
     if (obj_out) {
@@ -2017,9 +2242,11 @@ int mld_evaluate_batch(mld_problem_t *p, const double *v, int n_cols, const doub
                 launch_ev(1);
             } else {
                 if (col_rows) HIP_TRY(hipMemcpyAsync(d_rows, col_rows, sizeof(int) * n_cols, hipMemcpyHostToDevice, sq));
+                if (from_profiles) HIP_TRY(hipMemcpyAsync(d_start, start, sizeof(long long) * (size_t)batch * n_cols * p->pf_groups, hipMemcpyHostToDevice, sq));
                 for (int c0 = 0; c0 < n_cols; c0 += slice) {
                     const int nc_ = std::min(slice, n_cols - c0);
-                    if (nW) HIP_TRY(hipMemcpy2DAsync(d_om, sizeof(double) * nc_ * nW, omega_cols + (size_t)c0 * nW, sizeof(double) * n_cols * nW, sizeof(double) * nc_ * nW, batch, hipMemcpyHostToDevice, sq));
+                    if (from_profiles) { launch_profile_windows(p, sq, batch * nc_, nc_, n_cols, c0, d_start.get(), step, d_om.get()); HIP_TRY(hipGetLastError()); }
+                    else if (nW) HIP_TRY(hipMemcpy2DAsync(d_om, sizeof(double) * nc_ * nW, omega_cols + (size_t)c0 * nW, sizeof(double) * n_cols * nW, sizeof(double) * nc_ * nW, batch, hipMemcpyHostToDevice, sq));
                     if (x_cols) HIP_TRY(hipMemcpy2DAsync(d_xc, sizeof(double) * nc_ * nx, x_cols + (size_t)c0 * nx, sizeof(double) * n_cols * nx, sizeof(double) * nc_ * nx, batch, hipMemcpyHostToDevice, sq));
                     ec.n_cols = nc_; ec.std = 0; ec.per_col = 1; ec.ld_out = n_cols; ec.col0 = c0;
                     ec.omc = d_om.get(); ec.xc = x_cols ? d_xc.get() : nullptr; ec.rows = col_rows ? d_rows.get() + c0 : nullptr;
@@ -2072,6 +2299,18 @@ int mld_evaluate_batch(mld_problem_t *p, const double *v, int n_cols, const doub
     if (rc) return rc;
     HIP_TRY(es);
     return MLD_OK;
+}
+
+int mld_evaluate_batch(mld_problem_t *p, const double *v, int n_cols, const double *omega_cols, const int32_t *col_rows, const double *x_cols,
+                       double *obj_out, double *constr_vio_out, int32_t *constr_row_out, double *int_vio_out, double *bound_vio_out)
+{
+    return evaluate_impl(p, "mld_evaluate_batch", v, n_cols, omega_cols, false, nullptr, 0, col_rows, x_cols, obj_out, constr_vio_out, constr_row_out, int_vio_out, bound_vio_out);
+}
+
+int mld_evaluate_batch_profiles(mld_problem_t *p, const double *v, int n_cols, const int64_t *start, int step, const int32_t *col_rows, const double *x_cols,
+                                double *obj_out, double *constr_vio_out, int32_t *constr_row_out, double *int_vio_out, double *bound_vio_out)
+{
+    return evaluate_impl(p, "mld_evaluate_batch_profiles", v, n_cols, nullptr, true, start, step, col_rows, x_cols, obj_out, constr_vio_out, constr_row_out, int_vio_out, bound_vio_out);
 }
 
 int mld_problem_get_opts(mld_problem_t *p, mld_opts *out)

@@ -13,6 +13,7 @@
 #include "common.h"
 #include "condense.inc"
 #include "problem.inc"
+#include "profiles.inc"      // k_profile_windows and the window rule (mld_upload_profiles and its consumers, api_problem.inc)
 
 // ---- errors ------------------------------------------------------------------------------------
 static thread_local char g_err[1024] = "";
@@ -27,7 +28,7 @@ void mld_set_error(const char *fmt, ...)
 extern "C" {
 
 const char *mld_last_error(void) { return g_err; }
-const char *mld_version(void) { return "mldgpu 0.6 (gfx950, fp64 dense-dictionary cut-and-branch, in-kernel sub-tree hand-off, per-instance linear cost, predicted trajectories, solution quality; sizeof(mld_opts) = 64)"; }
+const char *mld_version(void) { return "mldgpu 0.6 (gfx950, fp64 dense-dictionary cut-and-branch, in-kernel sub-tree hand-off, per-instance linear cost, predicted trajectories, solution quality, resident disturbance profiles; sizeof(mld_opts) = 64)"; }
 
 int mld_device_count(void)
 {

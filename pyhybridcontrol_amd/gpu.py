@@ -280,6 +280,120 @@ class GpuProblem(object):
                                                          _lib.dptr(xc) if xc is not None else None))
         return n_cols
 
+    # -- resident disturbance profiles ----------------------------------------------------------------
+    def upload_profiles(self, lib, group_width=None):
+        """flat library of disturbance series resident in HBM (mld_upload_profiles), owned by the problem and independent of the batch.  group_width:
+        positive widths that sum to nomega, one group of channels per fused device (None = one group of width nomega); a series of group g is stored
+        row-major (time, width_g) -- profiles.pack lays series end to end.  A second call replaces the library and invalidates resident starts; an
+        empty library frees it."""
+        nomega = self.model.dims["nomega"]
+        gw = None
+        if group_width is not None:
+            gw = np.asarray(group_width)
+            if gw.ndim != 1 or gw.size < 1 or not np.issubdtype(gw.dtype, np.integer) or np.any(gw < 1) or int(gw.sum()) != nomega:
+                raise ValueError("group_width %s: expected positive integer widths that sum to nomega = %d" % (np.asarray(group_width).tolist(), nomega))
+            gw = np.ascontiguousarray(gw, dtype=np.int32)
+        lib = np.ascontiguousarray(lib, dtype=np.float64)
+        if lib.ndim != 1:
+            raise ValueError("lib has shape %s, expected a flat array (profiles.pack)" % (lib.shape,))
+        check(_lib.load().mld_upload_profiles(self._h, lib.size, _lib.dptr(lib) if lib.size else None, 0 if gw is None else gw.size,
+                                              gw.ctypes.data_as(C.POINTER(C.c_int32)) if gw is not None else None))
+        self._pf_width = None if not lib.size else ([nomega] if gw is None else [int(w) for w in gw])
+        self._pf_ccols = 0
+
+    def _start_array(self, start, n_lead):
+        """int64 starts with n_lead leading axes after the batch -- (batch, n_groups) or (batch, n_cols, n_groups); the same without the batch axis is
+        broadcast over the batch; ValueError on a float dtype or a shape that fits neither, before any C call"""
+        a = np.asarray(start)
+        if not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("start has dtype %s, expected integers (offsets into the profile library)" % a.dtype)
+        width = getattr(self, "_pf_width", None)
+        G = len(width) if width else (a.shape[-1] if a.ndim else 0)
+        want = "(%d, %s%d) or (%s%d)" % (self.batch, "n_cols, " * n_lead, G, "n_cols, " * n_lead, G)
+        if a.ndim == 1 + n_lead:
+            a = np.broadcast_to(a, (self.batch,) + a.shape)
+        if a.ndim != 2 + n_lead or a.shape[0] != self.batch or a.shape[-1] != G or G < 1 or (n_lead and a.shape[1] < 1):
+            raise ValueError("start has shape %s, expected %s" % (np.shape(start), want))
+        return np.ascontiguousarray(a, dtype=np.int64)
+
+    def _column_extras(self, n_cols, col_rows, x_cols):
+        """col_rows (n_cols) int32 and x_cols (batch, n_cols, nx) of profile columns, checked as _column_arrays checks them"""
+        nx, B = self.model.dims["nx"], self.batch
+        if x_cols is not None:
+            x_cols = np.asarray(x_cols, dtype=np.float64)
+            if nx == 0:
+                raise ValueError("x_cols has shape %s but the model has no state (nx = 0)" % (x_cols.shape,))
+            if x_cols.shape != (B, n_cols, nx):
+                raise ValueError("x_cols has shape %s, expected (%d, %d, %d)" % (x_cols.shape, B, n_cols, nx))
+            x_cols = np.ascontiguousarray(x_cols)
+        if col_rows is not None:
+            cr = np.asarray(col_rows)
+            if cr.shape != (n_cols,) or not np.issubdtype(cr.dtype, np.integer):
+                raise ValueError("col_rows has shape %s and dtype %s, expected (%d,) integers" % (cr.shape, cr.dtype, n_cols))
+            col_rows = np.ascontiguousarray(cr, dtype=np.int32)
+        return col_rows, x_cols
+
+    def forecast_from_profiles(self, start=None, step=0):
+        """the forecast of every instance replaced by its window of the resident library (mld_forecast_from_profiles): start (batch, n_groups) or
+        (n_groups,) integer offsets, window = profiles.windows(lib, start, step, N_tilde, group_width).  start=None re-uses the resident starts with
+        another step.  After advance() only the forecast changes (plan and MIP start stay); otherwise the call counts as new inputs, like select()."""
+        st = self._start_array(start, 0) if start is not None else None
+        check(_lib.load().mld_forecast_from_profiles(self._h, st.ctypes.data_as(C.POINTER(C.c_int64)) if st is not None else None, int(step)))
+
+    def constraint_blocks_from_profiles(self, start=None, step=0, col_rows=None, x_cols=None):
+        """extra constraint blocks gathered from the resident library (mld_constraint_blocks_from_profiles): start (batch, n_cols, n_groups) or (n_cols,
+        n_groups); col_rows / x_cols as upload_constraint_blocks.  start=None re-uses the resident column starts with another step.  Returns n_cols."""
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None
+        if start is not None:
+            st = self._start_array(start, 1)
+            n_cols = st.shape[1]
+        else:
+            st = None
+            n_cols = getattr(self, "_pf_ccols", 0) or (len(col_rows) if col_rows is not None else 1)      # (without resident starts the library refuses)
+        cr, xc = self._column_extras(n_cols, col_rows, x_cols)
+        check(_lib.load().mld_constraint_blocks_from_profiles(self._h, n_cols, st.ctypes.data_as(C.POINTER(C.c_int64)) if st is not None else None, int(step),
+                                                              ip(cr), _lib.dptr(xc)))
+        self._pf_ccols = n_cols
+        return n_cols
+
+    def evaluate_profiles(self, start, step=0, v=None, col_rows=None, x_cols=None):
+        """evaluate() under validation columns gathered from the resident library instead of uploaded (mld_evaluate_batch_profiles): start (batch, n_cols,
+        n_groups) or (n_cols, n_groups); the dict of evaluate(omega_cols=...), constr_vio / constr_row (batch, n_cols).  The resident blocks and starts
+        are neither used nor changed."""
+        if start is None:
+            raise ValueError("evaluate_profiles needs start (the resident column starts belong to the problem's blocks)")
+        v = self._plan_array(v)
+        st = self._start_array(start, 1)
+        n_cols = st.shape[1]
+        cr, xc = self._column_extras(n_cols, col_rows, x_cols)
+        B = self.batch
+        out = dict(obj=np.zeros(B), constr_vio=np.zeros((B, n_cols)), constr_row=np.zeros((B, n_cols), np.int32), int_vio=np.zeros(B), bound_vio=np.zeros(B))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None
+        check(_lib.load().mld_evaluate_batch_profiles(self._h, _lib.dptr(v), n_cols, st.ctypes.data_as(C.POINTER(C.c_int64)), int(step), ip(cr), _lib.dptr(xc),
+                                                      _lib.dptr(out["obj"]), _lib.dptr(out["constr_vio"]), ip(out["constr_row"]), _lib.dptr(out["int_vio"]),
+                                                      _lib.dptr(out["bound_vio"])))
+        return out
+
+    def constraint_blocks(self):
+        """the resident constraint blocks however they got there (mld_download_constraint_blocks): dict(omega_cols (batch, n_cols, N_tilde*nomega), col_rows
+        (n_cols,) -- N_tilde*nc for blocks set without col_rows --, x_cols (batch, n_cols, nx) or None when every column uses the instance's x0)"""
+        lib = _lib.load()
+        n = C.c_int32(0)
+        check(lib.mld_download_constraint_blocks(self._h, C.byref(n), None, None, None))
+        n_cols, nx = int(n.value), self.model.dims["nx"]
+        oc, cr = np.zeros((self.batch, n_cols, self.nW)), np.zeros(n_cols, np.int32)
+        xc = None
+        if n_cols:
+            check(lib.mld_download_constraint_blocks(self._h, None, _lib.dptr(oc), cr.ctypes.data_as(C.POINTER(C.c_int32)), None))
+            if nx:      # x_cols is refused (MLD_ERR_INVALID) exactly when the resident blocks have none
+                xc = np.zeros((self.batch, n_cols, nx))
+                rc = lib.mld_download_constraint_blocks(self._h, None, None, None, _lib.dptr(xc))
+                if rc == -1:
+                    xc = None
+                else:
+                    check(rc)
+        return dict(omega_cols=oc, col_rows=cr, x_cols=xc)
+
     def _inst_cost_arrays(self, lin_v=None, lin_x=None, lin_y=None):
         """(batch, len) float64 arrays of a per-instance cost, a (len,) array broadcast; ValueError on a shape that fits neither"""
         d, N = self.model.dims, self.N_tilde
@@ -515,15 +629,21 @@ class GpuProblem(object):
         check(_lib.load().mld_download_telemetry(self._h, ip(lat), ip(rows), C.byref(rb)))
         return dict(latency_ns=lat, rows_updated=rows, row_bytes=int(rb.value))
 
-    def solve(self, x0, omega, model_idx=None, fixed_bin=None, omega_cols=None, col_rows=None, x_cols=None, warm_start=None, inst_cost=None, trajectories=False, quality=False):
-        """upload, solve, download.  inst_cost: dict(lin_v=..., lin_x=..., lin_y=...) of upload_instance_cost for this batch; trajectories=True adds
+    def solve(self, x0, omega, model_idx=None, fixed_bin=None, omega_cols=None, col_rows=None, x_cols=None, warm_start=None, inst_cost=None, trajectories=False, quality=False,
+              col_start=None, col_step=0):
+        """upload, solve, download.  col_start / col_step: the constraint blocks gathered from the resident profile library
+        (constraint_blocks_from_profiles) instead of uploaded as omega_cols -- one or the other.  inst_cost: dict(lin_v=..., lin_x=..., lin_y=...) of upload_instance_cost for this batch; trajectories=True adds
         the predicted x / y of trajectories() to the result; quality=True adds out["quality"], evaluate() of the plans just computed on the problem
         as posed"""
+        if col_start is not None and omega_cols is not None:
+            raise ValueError("col_start and omega_cols both given: the constraint blocks come from the profile library or from the caller, not both")
         self.upload(x0, omega, model_idx, fixed_bin)
         if inst_cost:
             self.upload_instance_cost(**inst_cost)
         if omega_cols is not None:
             self.upload_constraint_blocks(omega_cols, col_rows, x_cols)
+        if col_start is not None:
+            self.constraint_blocks_from_profiles(col_start, col_step, col_rows, x_cols)
         if warm_start is not None:
             self.set_warm_start(warm_start)
         stats = self.solve_resident()
@@ -575,11 +695,15 @@ class GpuProblem(object):
         check(_lib.load().mld_handoff_stats(self._h, out))
         return dict(items=int(out[0]), given_up=int(out[1]), unfinished=int(out[2]), queue_full=int(out[3]))
 
-    def solve_handoff_device(self, x0, omega, model_idx=None, fixed_bin=None, first_nodes=None, sub_nodes=None, max_gen=8, max_children=64, max_tree=160, room_factor=0.0, donate=0, rounds=0, inst_cost=None, trajectories=False, quality=False):
+    def solve_handoff_device(self, x0, omega, model_idx=None, fixed_bin=None, first_nodes=None, sub_nodes=None, max_gen=8, max_children=64, max_tree=160, room_factor=0.0, donate=0, rounds=0, inst_cost=None, trajectories=False, quality=False,
+                             omega_cols=None, col_rows=None, x_cols=None, col_start=None, col_step=0):
         """the batch with the hand-off inside ONE launch (set_handoff): upload, solve, download -- the merged results per instance plus `handoff`
         statistics.  The problem's own limits and the hand-off switch are restored afterwards.  inst_cost: as solve() (items use their source
         instance's cost).  trajectories=True adds the predicted x / y of the merged plans, quality=True out["quality"] = evaluate() of them (both read before the
-        resident batch is dropped)."""
+        resident batch is dropped).  omega_cols / col_start, col_step with col_rows, x_cols: constraint blocks as in solve() (the items see their source
+        instance's blocks)."""
+        if col_start is not None and omega_cols is not None:
+            raise ValueError("col_start and omega_cols both given: the constraint blocks come from the profile library or from the caller, not both")
         keep_nodes = int(self.opts.max_nodes)
         try:
             if first_nodes is not None:
@@ -588,6 +712,10 @@ class GpuProblem(object):
             self.upload(x0, omega, model_idx, fixed_bin)
             if inst_cost:
                 self.upload_instance_cost(**inst_cost)
+            if omega_cols is not None:
+                self.upload_constraint_blocks(omega_cols, col_rows, x_cols)
+            if col_start is not None:
+                self.constraint_blocks_from_profiles(col_start, col_step, col_rows, x_cols)
             stats = self.solve_resident()
             out = self.download()
             out["stats"] = stats
