@@ -119,6 +119,8 @@ typedef enum {
     MLD_DBG_ASSERT_POSCTL = 1 << 20,    /* positive control of the assertion build (-DMLD_ASSERT): one index check fails */
     MLD_DBG_NO_PIVOT_PAIRS = 1 << 21,   /* every dual-simplex pivot updates the dictionary on its own instead of two consecutive pivots sharing
                                            one pass (A/B on the same binary: results are bit-identical, only rows_updated and speed change) */
+    MLD_DBG_SIM_NO_LDS = 1 << 23,       /* k_sim_step (mld_sim_step_batch) reads x, v0, omega and y from global memory instead of staging them in LDS: the path of
+                                           shapes whose staging exceeds the workgroup's LDS, on any shape (results are bit-identical) */
     MLD_DBG_CUTS_R4 = 1 << 22           /* the wave-per-cut Gomory and c-MIR rounds as round 4 built them: one slack row / eight dictionary rows of
                                            one column chunk in flight, generic pointers (A/B on the same binary of the grouped loads and the
                                            LDS-typed views: results are bit-identical, only speed changes) */
@@ -452,6 +454,60 @@ int mld_evaluate_batch_profiles(mld_problem_t *, const double *v, int n_cols, co
  * n_cols, N_tilde*nomega), col_rows (n_cols; N_tilde*nc for blocks uploaded without col_rows), x_cols (batch, n_cols, nx; MLD_ERR_INVALID when the
  * resident blocks have none).  Every argument may be NULL; with all arrays NULL only the count is reported. */
 int mld_download_constraint_blocks(mld_problem_t *, int32_t *n_cols_out, double *omega_cols, int32_t *col_rows, double *x_cols);
+
+/* ---- plant step and simulation log of the resident batch -------------------------------------------------------------------------------------------
+ * The step of the reference's closed loop that follows the solve: ControllerBase.sim_step_k -> MldModel.lsim_k -> MldSimLog (controllers/
+ * controller_base.py:229-253, models/mld_model.py:647-699, controller_base.py:58-146), for every instance of the resident batch, without host traffic.
+ * The operation is lsim_k(x_k, v_k = [u; delta; z; mu], omega_k) (mld_model.py:666-676): the WHOLE step-0 slice is given, no auxiliary is re-derived:
+ *     x_k1 = A x + [B1 B2 B3] (u, delta, z) + B4 omega_k + b5                                                       (:690)
+ *     y    = C x + [D1 D2 D3] (u, delta, z) + D4 omega_k + d5                                                       (:691)
+ *     r    = E x + [F1 F2 F3] (u, delta, z) + F4 omega_k + G y - f5 ,   cons_i = r_i <= 1e-6                        (:692-694: the Psi mu term is zeroed)
+ *     cons_vio = max_i r_i ,  cons_row = the lowest row that attains it     (-inf and -1 when nc == 0; a NaN residual wins the maximum)
+ * on the ORIGINAL model's matrices, in fp64 also on an MLD_F32 handle (k_sim_step).  x_k1 is summed exactly as mld_advance_batch sums it, so an advance
+ * through this entry leaves the same bits.  Under a realised disturbance `cons` says, per row, whether the PLANNED auxiliaries are still consistent with the
+ * model: the test of the equivalence condition mld_advance_batch2 describes above.  Re-deriving delta / z from (x, u, omega) (lsim_k's _compute_aux) is not
+ * done here.  The stage cost is the agent's business in the reference (sim_k.z * prices_k, examples/.../modelling/micro_grid_agents.py:753): it stays a host
+ * product on the downloaded log.
+ *
+ * v0 == NULL  the step-0 slice of the resident plan.  Needs a finished solve of the current inputs that has not been advanced yet (refused exactly where
+ *             mld_predict_batch(v = NULL) is refused); rows are read after the hand-off's device merge.  An instance without a usable plan (not OPTIMAL /
+ *             NODE_LIMIT with a finite objective) is NOT advanced (it keeps state and forecast) and is counted in n_skipped_out; its outputs and its record
+ *             have NaN in v, y, x_k1 and cons_vio, 0 in cons and -1 in cons_row; x, omega, obj, lower_bound, status and nodes are recorded as they are.
+ * v0 != NULL  (batch, nv): the caller's step inputs (a rule-based baseline, another controller).  Needs only a resident batch; no masking, every instance
+ *             advances, n_skipped_out = 0.  The record carries obj = lower_bound = NaN, status = -1, nodes = 0.
+ * omega_k     the forecast's step 0, or with MLD_SIM_ACTUAL one element run of the profile library (mld_upload_profiles): the window rule with ONE step,
+ *             omega_k[j] = lib[s + step*width_g + (j - goff_g)] for channel j of group g with start s.  act_start (batch, n_groups) stays resident in an
+ *             array of its own (separate from the forecast and column starts); NULL re-uses it with another step.  Every start is tested on the host before
+ *             anything is queued (s >= 0, s + (step + 1)*width_g <= lib_len; per group the largest resident start is remembered), the first offender is
+ *             named by instance and group; mld_upload_profiles invalidates the resident starts.
+ * MLD_SIM_ADVANCE  x0 <- x_k1 and the forecast rotated by one step: everything mld_advance_batch2 does.  With the resident plan the handle ends in the state
+ *             mld_advance_batch2 leaves (advanced; constraint blocks, MIP start and cutoffs cleared: mld_warm_start_from_previous and
+ *             mld_forecast_from_profiles(NULL, step + 1) work as after it).  With the caller's v0 it ends as after mld_select_inputs (new inputs: blocks, MIP
+ *             start, cutoffs and solved state cleared).  Without the flag nothing a later solve reads is written: a what-if under another realised value.
+ * MLD_SIM_LOG  this step's record is appended to the resident log, slot n_logged, which then increments.
+ * Outputs (any may be NULL): x_k1_out (batch, nx), y_out (batch, ny), cons_out (batch, nc) bytes 0 / 1, cons_vio_out (batch), cons_row_out (batch).
+ *
+ * THE LOG.  mld_sim_log_begin(capacity) allocates `capacity` records of the resident batch and resets the count (a log held before is replaced; 0 frees):
+ * capacity x batch x ((2 nx + nv + ny + nomega + 3) doubles + nc bytes + 3 ints), the product in size_t; an allocation failure reports an error and changes
+ * nothing.  The log belongs to the resident batch: mld_upload_batch discards it, mld_problem_destroy frees it.  mld_download_sim_log copies records
+ * [first, first + count) into arrays (count, batch, width), any NULL: x, v, y, omega (the omega_k used), x_k1, cons, cons_vio, cons_row as above, and the
+ * solve's obj, lower_bound, status, nodes as mld_download_results reports them.
+ *
+ * Runs on the problem's stream; it waits for that stream only, and only where it has to: for the caller's arrays (v0, act_start), the skip count and the
+ * requested outputs (and after MLD_SIM_ADVANCE on a stream made by mld_problem_use_stream, which the copies of the other entry points do not order against).
+ * MLD_ERR_NO_DEVICE without a device.  MLD_ERR_INVALID, nothing changed: no batch resident; a launched solve not finished; a time-varying handle (as
+ * mld_advance_batch); unknown flag bits; step < 0; MLD_SIM_ACTUAL without a library, with nomega == 0, or with an invalid or missing start (act_start without
+ * the flag too); MLD_SIM_LOG without a begun log or with a full one; a download range outside [0, n_logged]. */
+#define MLD_SIM_ADVANCE 1   /* x0 <- x_k1, forecast rotated by one step: everything mld_advance_batch2 does */
+#define MLD_SIM_ACTUAL  2   /* omega_k from the profile library instead of the forecast's step 0 */
+#define MLD_SIM_LOG     4   /* append this step's record to the resident log */
+int mld_sim_log_begin(mld_problem_t *, int capacity);
+int mld_sim_log_count(mld_problem_t *, int32_t *n_logged, int32_t *capacity);
+int mld_sim_step_batch(mld_problem_t *, const double *v0, const int64_t *act_start, int step, int flags,
+                       double *x_k1_out, double *y_out, uint8_t *cons_out, double *cons_vio_out, int32_t *cons_row_out, int32_t *n_skipped_out);
+int mld_download_sim_log(mld_problem_t *, int first, int count,
+                         double *x, double *v, double *y, double *omega, double *x_k1, uint8_t *cons, double *cons_vio, int32_t *cons_row,
+                         double *obj, double *lower_bound, int32_t *status, int32_t *nodes);
 
 /* Per-instance telemetry of the last solve: time spent inside the solve kernel (device wall clock, ns) and
  * the number of dictionary rows the rank-1 updates touched (x *row_bytes x 2 = bytes streamed by pivots). */

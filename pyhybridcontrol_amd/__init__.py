@@ -14,3 +14,4 @@ from .batch import BatchSolver, shard_range, gather_sharded  # noqa: F401
 from .aux_resolve import AuxResolver  # noqa: F401
 from .compose import fuse  # noqa: F401
 from . import profiles  # noqa: F401
+from . import simlog  # noqa: F401

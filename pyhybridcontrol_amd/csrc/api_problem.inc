@@ -298,6 +298,7 @@ __global__ void __launch_bounds__(256) k_warm_from_plan(int batch, int nb, int n
 
 #include "trajectory.inc"      // k_trajectory / k_trajectory_valu (mld_predict_batch): they mask with plan_usable, like k_advance
 #include "evaluate.inc"        // k_evaluate / k_evaluate_valu, k_eval_point, k_eval_obj (mld_evaluate_batch): the same masking
+#include "sim_step.inc"        // k_sim_step (mld_sim_step_batch): lsim_k with the whole step-0 slice, the same masking
 
 // ------------------------------------------------------------------------------------------------
 /* buffers of the uploaded batch (ensure_batch, mld_upload_batch, mld_upload_constraint_blocks, mld_stage_inputs): released together when the
@@ -312,6 +313,7 @@ struct BatchBufs {
     DevBuf<double> stage_x0, stage_om;                   /* resident input sets (mld_stage_inputs) */
     DevBuf<int> perm; DevBuf<RhsGroup> groups;           /* instances grouped by model for the MFMA right-hand sides (K3) */
     DevBuf<double> xcols, xcols_x; DevBuf<int> xrows;    /* extra constraint blocks; the state every extra column was generated with (explicit x_k) */
+    DevBuf<double> sim_tmp;                              /* scratch of k_sim_step where its staging does not fit LDS: in_cap x (nomega + ny), on first use */
     DevBuf<double> icost, qs_inst_t;                     /* per-instance linear cost (mld_upload_instance_cost): batch x ic_ld, unscaled, pulled back to v
                                                             [then cx | cw | c0]; qs_inst under the Toeplitz-compatible column scales (k_lp_lds, on first use) */
     struct Handoff {      /* in-kernel sub-tree hand-off queue: allocated only while mld_set_handoff has it on */
@@ -373,6 +375,13 @@ struct mld_problem {
      * start == NULL is checked against the window rule without reading the device */
     DevBuf<double> pf_lib; long long pf_len = 0; int pf_groups = 0; std::vector<int> pf_width; DevBuf<PfChan> pf_chan;
     DevBuf<long long> pf_fstart, pf_cstart; int pf_fbatch = 0, pf_cbatch = 0, pf_ccols = 0; std::vector<long long> pf_fmax, pf_cmax;
+    DevBuf<long long> pf_astart; int pf_abatch = 0; std::vector<long long> pf_amax;      /* starts of the REALISED series (mld_sim_step_batch, MLD_SIM_ACTUAL): an array of their own */
+    /* resident simulation log (mld_sim_log_begin): `cap` records of the resident batch, one array per field, each (cap, batch, width).  It belongs to the
+     * resident batch: mld_upload_batch discards it */
+    struct SimLog {
+        DevBuf<double> x, v, y, om, x_k1, vio, obj, lb; DevBuf<unsigned char> cons; DevBuf<int> row, status, nodes;
+        int cap = 0, count = 0;
+    } slog;
     long long ho_stats[4] = {};  /* last solve: items published, trees split, trees left unfinished, entries the queue had no room for (always 0: such trees stay unfinished) */
 };
 
@@ -507,6 +516,7 @@ template <typename T> static int upload(DevBuf<T> &dst, const std::vector<T> &sr
 static void free_batch(mld_problem *p)
 {
     p->bat = BatchBufs();
+    if (p->slog.cap) p->slog = mld_problem::SimLog();
     p->n_groups = 0; p->has_warm = false; p->solved = false; p->advanced = false; p->has_cutoff = false;
     p->n_staged = 0; p->staged_batch = 0; p->n_xcols = 0; p->xcols_cap = 0; p->has_xcols_x = false;
     p->order_batch = 0; p->in_cap = 0; p->batch_cap = 0; p->ic_ld = 0;
@@ -992,6 +1002,7 @@ int mld_upload_batch(mld_problem_t *p, int batch, const int32_t *model_idx, cons
     p->all_fixed = false;
     if (fixed_bin && p->nb) { bool all = true; const size_t tot = (size_t)batch * p->nb; for (size_t k = 0; k < tot && all; ++k) all = fixed_bin[k] != 255; p->all_fixed = all; }
     p->n_xcols = 0;   /* extra constraint blocks belong to one upload */
+    if (p->slog.cap) p->slog = mld_problem::SimLog();      /* so does a simulation log */
     if (p->ic_ld) { p->bat.icost.reset(); p->bat.qs_inst_t.reset(); p->ic_ld = 0; }   /* so does a per-instance cost */
     if (p->order_batch != batch) p->order_batch = 0;
     {
@@ -1834,8 +1845,8 @@ int mld_upload_profiles(mld_problem_t *p, int64_t lib_len, const double *lib, in
         width.assign(group_width, group_width + n_groups);
     }
     if (lib_len == 0) {      /* frees the library; the start arrays go with it */
-        p->pf_lib.reset(); p->pf_chan.reset(); p->pf_fstart.reset(); p->pf_cstart.reset();
-        p->pf_len = 0; p->pf_groups = 0; p->pf_width.clear(); p->pf_fbatch = p->pf_cbatch = p->pf_ccols = 0;
+        p->pf_lib.reset(); p->pf_chan.reset(); p->pf_fstart.reset(); p->pf_cstart.reset(); p->pf_astart.reset();
+        p->pf_len = 0; p->pf_groups = 0; p->pf_width.clear(); p->pf_fbatch = p->pf_cbatch = p->pf_ccols = p->pf_abatch = 0;
         return MLD_OK;
     }
     std::vector<PfChan> chan;
@@ -1855,7 +1866,7 @@ int mld_upload_profiles(mld_problem_t *p, int64_t lib_len, const double *lib, in
     HIP_TRY(es);
     p->pf_lib = std::move(d_lib); p->pf_chan = std::move(d_chan);
     p->pf_len = lib_len; p->pf_groups = (int)width.size(); p->pf_width = width;
-    p->pf_fstart.reset(); p->pf_cstart.reset(); p->pf_fbatch = p->pf_cbatch = p->pf_ccols = 0;      /* starts pointed into the library that is gone */
+    p->pf_fstart.reset(); p->pf_cstart.reset(); p->pf_astart.reset(); p->pf_fbatch = p->pf_cbatch = p->pf_ccols = p->pf_abatch = 0;      /* starts pointed into the library that is gone */
     return MLD_OK;
 }
 
@@ -2311,6 +2322,213 @@ int mld_evaluate_batch_profiles(mld_problem_t *p, const double *v, int n_cols, c
                                 double *obj_out, double *constr_vio_out, int32_t *constr_row_out, double *int_vio_out, double *bound_vio_out)
 {
     return evaluate_impl(p, "mld_evaluate_batch_profiles", v, n_cols, nullptr, true, start, step, col_rows, x_cols, obj_out, constr_vio_out, constr_row_out, int_vio_out, bound_vio_out);
+}
+
+/* ---- plant step and simulation log of the resident batch -------------------------------------------------------------------------------------------
+ * One step of the reference's closed loop after the solve: ControllerBase.sim_step_k -> MldModel.lsim_k -> MldSimLog (controllers/controller_base.py:
+ * 229-253, models/mld_model.py:647-699, controller_base.py:58-146), with the whole step-0 slice v0 = [u; delta; z; mu] given (lsim_k's v_k=, no
+ * auxiliary resolution) -- the resident plan's or the caller's -- under the forecast's step 0 or the REALISED disturbance out of the profile library.
+ * Kernel: sim_step.inc.  Everything is tested on the host before anything is queued, the new inputs are built in the spare buffers and swapped in by
+ * the host, the starts of the realised series in a buffer of their own: a call that is refused changes nothing. */
+int mld_sim_log_begin(mld_problem_t *p, int capacity)
+{
+    static const char who[] = "mld_sim_log_begin";
+    if (mld_device_count() <= 0) { mld_set_error("no HIP device (libmldgpu has no CPU fallback)"); return MLD_ERR_NO_DEVICE; }
+    MLD_NOT_IN_FLIGHT(p, who);
+    if (!p || p->batch < 1) { mld_set_error("%s: no batch resident (mld_upload_batch): the log belongs to a batch", who); return MLD_ERR_INVALID; }
+    if (capacity < 0) { mld_set_error("%s: capacity = %d", who, capacity); return MLD_ERR_INVALID; }
+    if (capacity == 0) { p->slog = mld_problem::SimLog(); return MLD_OK; }
+    const mld_dims &d = p->model->dims;
+    const size_t widest = (size_t)std::max(std::max(std::max(d.nx, p->nv), std::max(d.ny, d.nomega)), std::max(d.nc, 1));
+    const size_t cb = (size_t)capacity * (size_t)p->batch;
+    if (cb > SIZE_MAX / sizeof(double) / widest) { mld_set_error("%s: capacity %d x batch %d x %zu entries does not fit size_t", who, capacity, p->batch, widest); return MLD_ERR_INVALID; }
+    mld_problem::SimLog L;      /* built beside the resident log: an allocation failure leaves that as it was */
+    hipError_t e = hipSuccess;
+    auto take = [&](auto &buf, size_t count) { if (e == hipSuccess) e = buf.alloc(count); };
+    take(L.x, cb * d.nx); take(L.v, cb * p->nv); take(L.y, cb * d.ny); take(L.om, cb * d.nomega); take(L.x_k1, cb * d.nx);
+    take(L.vio, cb); take(L.obj, cb); take(L.lb, cb); take(L.cons, cb * d.nc); take(L.row, cb); take(L.status, cb); take(L.nodes, cb);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        mld_set_error("%s: %s for %d records of %d instances (%zu bytes)", who, hipGetErrorString(e), capacity, p->batch,
+                      cb * ((2 * (size_t)d.nx + p->nv + d.ny + d.nomega + 3) * sizeof(double) + d.nc + 3 * sizeof(int)));
+        return MLD_ERR_HIP;
+    }
+    L.cap = capacity; L.count = 0;
+    p->slog = std::move(L);
+    return MLD_OK;
+}
+
+int mld_sim_log_count(mld_problem_t *p, int32_t *n_logged, int32_t *capacity)
+{
+    if (!p) { mld_set_error("mld_sim_log_count: null problem"); return MLD_ERR_INVALID; }
+    if (n_logged) *n_logged = p->slog.count;
+    if (capacity) *capacity = p->slog.cap;
+    return MLD_OK;
+}
+
+int mld_sim_step_batch(mld_problem_t *p, const double *v0, const int64_t *act_start, int step, int flags,
+                       double *x_k1_out, double *y_out, uint8_t *cons_out, double *cons_vio_out, int32_t *cons_row_out, int32_t *n_skipped_out)
+{
+    static const char who[] = "mld_sim_step_batch";
+    if (mld_device_count() <= 0) { mld_set_error("no HIP device (libmldgpu has no CPU fallback)"); return MLD_ERR_NO_DEVICE; }
+    MLD_NOT_IN_FLIGHT(p, who);
+    if (!p || p->batch < 1) { mld_set_error("%s: no batch resident (mld_upload_batch)", who); return MLD_ERR_INVALID; }
+    mld_model *m = p->model;
+    const mld_dims &d = m->dims;
+    const int batch = p->batch, nx = d.nx, nv = p->nv, nw = d.nomega, ny = d.ny, nc = d.nc;
+    if (flags & ~(MLD_SIM_ADVANCE | MLD_SIM_ACTUAL | MLD_SIM_LOG)) { mld_set_error("%s: unknown flag bits 0x%x (MLD_SIM_ADVANCE | MLD_SIM_ACTUAL | MLD_SIM_LOG)", who, flags); return MLD_ERR_INVALID; }
+    const bool advance = flags & MLD_SIM_ADVANCE, actual = flags & MLD_SIM_ACTUAL, log = flags & MLD_SIM_LOG;
+    if (step < 0 || step == INT_MAX) { mld_set_error("%s: step = %d (must be >= 0)", who, step); return MLD_ERR_INVALID; }
+    if (m->tv_N > 0) { mld_set_error("%s: time-varying models (mld_model_create_tv) are not stepped on the device -- the step models would have to shift with the horizon (as mld_advance_batch)", who); return MLD_ERR_INVALID; }
+    if (!m->d_pack) { mld_set_error("%s: model without matrices", who); return MLD_ERR_INVALID; }
+    if (!v0 && !p->solved) { mld_set_error("%s: the resident batch has not been solved since its upload / selection (there is no plan to apply; pass v0)", who); return MLD_ERR_INVALID; }
+    if (!v0 && p->advanced) { mld_set_error("%s: the last solve's plan has already been applied -- the resident plan belongs to inputs that are gone (solve again, or pass v0)", who); return MLD_ERR_INVALID; }
+    if (act_start && !actual) { mld_set_error("%s: act_start given without MLD_SIM_ACTUAL", who); return MLD_ERR_INVALID; }
+    std::vector<long long> gmax;
+    if (actual) {
+        if (nw == 0) { mld_set_error("%s: MLD_SIM_ACTUAL, but the model has no disturbance (nomega = 0)", who); return MLD_ERR_INVALID; }
+        if (!p->pf_len) { mld_set_error("%s: MLD_SIM_ACTUAL, but no profile library is resident (mld_upload_profiles)", who); return MLD_ERR_INVALID; }
+        /* the window rule with ONE step: s >= 0 and s + (step + 1) * width_g <= lib_len */
+        if (act_start) {
+            gmax.assign(p->pf_groups, 0);
+            const int64_t *s = act_start;
+            for (int b = 0; b < batch; ++b)
+                for (int g = 0; g < p->pf_groups; ++g, ++s) {
+                    if (!profile_start_ok(*s, p->pf_len, step, 1, p->pf_width[g])) {
+                        mld_set_error("%s: actual start %lld of instance %d, group %d (width %d) at step %d: the element [%lld, %lld) leaves the library of %lld doubles",
+                                      who, (long long)*s, b, g, p->pf_width[g], step, (long long)*s + (long long)step * p->pf_width[g],
+                                      (long long)*s + ((long long)step + 1) * p->pf_width[g], p->pf_len);
+                        return MLD_ERR_INVALID;
+                    }
+                    gmax[g] = std::max<long long>(gmax[g], *s);
+                }
+        } else {
+            if (p->pf_abatch != batch) { mld_set_error("%s: act_start == NULL, but no actual starts of this batch are resident (pass them once)", who); return MLD_ERR_INVALID; }
+            for (int g = 0; g < p->pf_groups; ++g)
+                if (!profile_start_ok(p->pf_amax[g], p->pf_len, step, 1, p->pf_width[g])) {
+                    mld_set_error("%s: step %d moves the largest resident actual start of group %d (%lld, width %d) past the end of the library: the element would end at %lld of %lld doubles",
+                                  who, step, g, p->pf_amax[g], p->pf_width[g], p->pf_amax[g] + ((long long)step + 1) * p->pf_width[g], p->pf_len);
+                    return MLD_ERR_INVALID;
+                }
+        }
+    }
+    mld_problem::SimLog &L = p->slog;
+    if (log && !L.cap) { mld_set_error("%s: MLD_SIM_LOG, but no log has been begun for this batch (mld_sim_log_begin)", who); return MLD_ERR_INVALID; }
+    if (log && L.count >= L.cap) { mld_set_error("%s: MLD_SIM_LOG, but the log is full (%d of %d records; mld_download_sim_log, then mld_sim_log_begin)", who, L.count, L.cap); return MLD_ERR_INVALID; }
+    if (!advance && !log && !x_k1_out && !y_out && !cons_out && !cons_vio_out && !cons_row_out && !n_skipped_out && !act_start) return MLD_OK;      /* nothing asked for */
+
+    SimStepArgs a{};
+    a.batch = batch; a.nx = nx; a.nv = nv; a.nmu = d.nmu; a.nw = nw; a.ny = ny; a.nc = nc; a.N = p->N;
+    const size_t stage = sizeof(double) * SS_WAVES * ((size_t)nx + nv + nw + ny);
+    a.lds = stage <= SS_LDS_MAX && !(p->opts.reserved & MLD_DBG_SIM_NO_LDS);
+    a.pack = m->d_pack; a.pack_len = m->pack_len;
+    {   /* offsets inside the packed per-model block: A, B4, b5, C, D4, d5, E, F4, f5, G, [B1 B2 B3 0], [D1 D2 D3 0], [F1 F2 F3 Psi]  (mld_model_create) */
+        size_t o = 0;
+        a.oA = o; o += m->mat_size[MT_A]; a.oB4 = o; o += m->mat_size[MT_B4]; a.ob5 = o; o += m->mat_size[MT_b5];
+        a.oC = o; o += m->mat_size[MT_C]; a.oD4 = o; o += m->mat_size[MT_D4]; a.od5 = o; o += m->mat_size[MT_d5];
+        a.oE = o; o += m->mat_size[MT_E]; a.oF4 = o; o += m->mat_size[MT_F4]; a.of5 = o; o += m->mat_size[MT_f5];
+        a.oG = o; o += m->mat_size[MT_G];
+        a.oBv = o; o += (size_t)nx * nv; a.oDv = o; o += (size_t)ny * nv; a.oFv = o;
+    }
+    a.model_idx = p->has_midx ? p->bat.model_idx.get() : nullptr;
+    a.x0 = p->bat.x0; a.omega = p->bat.omega;
+    const hipStream_t sq = p->stream;
+    DevBuf<double> d_v, d_xk1, d_y, d_vio; DevBuf<unsigned char> d_cons; DevBuf<int> d_row; DevBuf<long long> d_start;
+    if (v0) HIP_TRY(d_v.alloc((size_t)batch * std::max(1, nv)));
+    if (act_start) HIP_TRY(d_start.alloc((size_t)batch * p->pf_groups));
+    if (!a.lds && !p->bat.sim_tmp) HIP_TRY(p->bat.sim_tmp.alloc((size_t)p->in_cap * std::max(1, nw + ny)));      /* sized like the input buffers (any batch up to in_cap); free_batch releases it with them */
+    if (!a.lds) { a.w_tmp = p->bat.sim_tmp; a.y_tmp = p->bat.sim_tmp.get() + (size_t)batch * nw; }
+    if (v0) { a.v = d_v; a.v_stride = (size_t)nv; }
+    else {      /* the resident plans: rows < batch are the instances' (after the hand-off's device merge), hand-off items come after them */
+        a.v = p->bat.v; a.v_stride = (size_t)p->n;
+        a.status = p->bat.status; a.obj = p->bat.obj; a.lbnd = p->bat.lbnd; a.nodes = p->bat.nodes;
+    }
+    if (actual) { a.act_start = act_start ? d_start.get() : p->pf_astart.get(); a.chan = p->pf_chan; a.n_groups = p->pf_groups; a.step = step; a.lib = p->pf_lib; }
+    if (advance) { a.x0_new = p->bat.x0b; a.omega_new = p->bat.omegab; }
+    const size_t slot = log ? (size_t)L.count * batch : 0;
+    if (log) {
+        a.x_k1 = L.x_k1.get() + slot * nx; a.y = L.y.get() + slot * ny; a.vio = L.vio.get() + slot; a.cons = L.cons.get() + slot * nc; a.row = L.row.get() + slot;
+        a.rec_x = L.x.get() + slot * nx; a.rec_v = L.v.get() + slot * nv; a.rec_om = L.om.get() + slot * nw;
+        a.rec_obj = L.obj.get() + slot; a.rec_lb = L.lb.get() + slot; a.rec_status = L.status.get() + slot; a.rec_nodes = L.nodes.get() + slot;
+    } else {
+        if (x_k1_out && nx) { HIP_TRY(d_xk1.alloc((size_t)batch * nx)); a.x_k1 = d_xk1; }
+        if (y_out && ny) { HIP_TRY(d_y.alloc((size_t)batch * ny)); a.y = d_y; }
+        if (cons_out && nc) { HIP_TRY(d_cons.alloc((size_t)batch * nc)); a.cons = d_cons; }
+        if (cons_vio_out) { HIP_TRY(d_vio.alloc(batch)); a.vio = d_vio; }
+        if (cons_row_out) { HIP_TRY(d_row.alloc(batch)); a.row = d_row; }
+    }
+    const bool count_skipped = !v0 && (n_skipped_out != nullptr);
+    if (count_skipped) a.n_skipped = p->bat.skipped;
+    int skipped = 0;
+    /* the host waits where it has to: for the caller's arrays (theirs again when this returns), the skip count and the requested outputs; and after an
+     * advance on a stream of the problem's own, because the other entry points copy on the legacy stream, which does not order against that one */
+    const bool wait = v0 || act_start || count_skipped || x_k1_out || y_out || cons_out || cons_vio_out || cons_row_out || (advance && p->own_stream);
+    auto queue = [&]() -> int {
+        if (v0 && nv) HIP_TRY(hipMemcpyAsync(d_v, v0, sizeof(double) * (size_t)batch * nv, hipMemcpyHostToDevice, sq));
+        if (act_start) HIP_TRY(hipMemcpyAsync(d_start, act_start, sizeof(long long) * (size_t)batch * p->pf_groups, hipMemcpyHostToDevice, sq));
+        if (count_skipped) HIP_TRY(hipMemsetAsync(p->bat.skipped, 0, sizeof(int), sq));
+        const int grid = (int)std::min<long long>(((long long)batch + SS_WAVES - 1) / SS_WAVES, 8192);
+        hipLaunchKernelGGL(k_sim_step, dim3(grid), dim3(64 * SS_WAVES), a.lds ? stage : 0, sq, a);
+        HIP_TRY(hipGetLastError());
+        if (x_k1_out && nx) HIP_TRY(hipMemcpyAsync(x_k1_out, a.x_k1, sizeof(double) * (size_t)batch * nx, hipMemcpyDeviceToHost, sq));
+        if (y_out && ny) HIP_TRY(hipMemcpyAsync(y_out, a.y, sizeof(double) * (size_t)batch * ny, hipMemcpyDeviceToHost, sq));
+        if (cons_out && nc) HIP_TRY(hipMemcpyAsync(cons_out, a.cons, (size_t)batch * nc, hipMemcpyDeviceToHost, sq));
+        if (cons_vio_out) HIP_TRY(hipMemcpyAsync(cons_vio_out, a.vio, sizeof(double) * batch, hipMemcpyDeviceToHost, sq));
+        if (cons_row_out) HIP_TRY(hipMemcpyAsync(cons_row_out, a.row, sizeof(int) * batch, hipMemcpyDeviceToHost, sq));
+        if (count_skipped) HIP_TRY(hipMemcpyAsync(&skipped, p->bat.skipped, sizeof(int), hipMemcpyDeviceToHost, sq));
+        return MLD_OK;
+    };
+    const int rc = queue();
+    if (rc || wait) {
+        const hipError_t es = hipStreamSynchronize(sq);
+        if (rc) return rc;
+        HIP_TRY(es);
+    }
+    /* queued without an error: the handle moves on */
+    if (act_start) { p->pf_astart = std::move(d_start); p->pf_abatch = batch; p->pf_amax = gmax; }
+    if (log) ++L.count;
+    if (advance) {
+        std::swap(p->bat.x0, p->bat.x0b); std::swap(p->bat.omega, p->bat.omegab);
+        p->n_xcols = 0;      /* extra constraint blocks belonged to the previous step's data */
+        p->has_warm = false; /* a start belongs to one set of inputs (mld_warm_start_from_previous builds the next one from the plan) */
+        p->has_cutoff = false;
+        if (v0) { p->solved = false; p->advanced = false; }      /* the caller's inputs: new inputs, as after mld_select_inputs */
+        else p->advanced = true;                                 /* the resident plan has been applied, as after mld_advance_batch */
+    }
+    if (n_skipped_out) *n_skipped_out = skipped;
+    return MLD_OK;
+}
+
+int mld_download_sim_log(mld_problem_t *p, int first, int count, double *x, double *v, double *y, double *omega, double *x_k1, uint8_t *cons, double *cons_vio,
+                         int32_t *cons_row, double *obj, double *lower_bound, int32_t *status, int32_t *nodes)
+{
+    static const char who[] = "mld_download_sim_log";
+    if (mld_device_count() <= 0) { mld_set_error("no HIP device (libmldgpu has no CPU fallback)"); return MLD_ERR_NO_DEVICE; }
+    MLD_NOT_IN_FLIGHT(p, who);
+    if (!p || p->batch < 1) { mld_set_error("%s: no batch resident (mld_upload_batch)", who); return MLD_ERR_INVALID; }
+    const mld_problem::SimLog &L = p->slog;
+    if (first < 0 || count < 0 || (long long)first + count > L.count) { mld_set_error("%s: records [%d, %lld) asked for, %d logged", who, first, (long long)first + count, L.count); return MLD_ERR_INVALID; }
+    if (count == 0) return MLD_OK;
+    const mld_dims &d = p->model->dims;
+    const size_t off = (size_t)first * p->batch, len = (size_t)count * p->batch;
+    const hipStream_t sq = p->stream;
+    auto queue = [&]() -> int {
+        auto get = [&](void *dst, const void *src, size_t width, size_t elem) -> hipError_t {
+            if (!dst || !width) return hipSuccess;
+            return hipMemcpyAsync(dst, (const char *)src + off * width * elem, len * width * elem, hipMemcpyDeviceToHost, sq);
+        };
+        HIP_TRY(get(x, L.x.get(), d.nx, sizeof(double))); HIP_TRY(get(v, L.v.get(), p->nv, sizeof(double))); HIP_TRY(get(y, L.y.get(), d.ny, sizeof(double)));
+        HIP_TRY(get(omega, L.om.get(), d.nomega, sizeof(double))); HIP_TRY(get(x_k1, L.x_k1.get(), d.nx, sizeof(double))); HIP_TRY(get(cons, L.cons.get(), d.nc, 1));
+        HIP_TRY(get(cons_vio, L.vio.get(), 1, sizeof(double))); HIP_TRY(get(cons_row, L.row.get(), 1, sizeof(int)));
+        HIP_TRY(get(obj, L.obj.get(), 1, sizeof(double))); HIP_TRY(get(lower_bound, L.lb.get(), 1, sizeof(double)));
+        HIP_TRY(get(status, L.status.get(), 1, sizeof(int))); HIP_TRY(get(nodes, L.nodes.get(), 1, sizeof(int)));
+        return MLD_OK;
+    };
+    const int rc = queue();
+    const hipError_t es = hipStreamSynchronize(sq);
+    if (rc) return rc;
+    HIP_TRY(es);
+    return MLD_OK;
 }
 
 int mld_problem_get_opts(mld_problem_t *p, mld_opts *out)

@@ -521,6 +521,78 @@ class GpuProblem(object):
         check(_lib.load().mld_advance_batch2(self._h, C.byref(skipped)))
         return int(skipped.value)
 
+    # -- plant step and simulation log ------------------------------------------------------------------
+    def sim_log_begin(self, capacity):
+        """a resident log of `capacity` steps of the resident batch (mld_sim_log_begin): resets the count, 0 frees; upload() discards the log"""
+        check(_lib.load().mld_sim_log_begin(self._h, int(capacity)))
+
+    def sim_log_count(self):
+        """(steps logged, capacity) of the resident log; (0, 0) without one"""
+        n, cap = C.c_int32(0), C.c_int32(0)
+        check(_lib.load().mld_sim_log_count(self._h, C.byref(n), C.byref(cap)))
+        return int(n.value), int(cap.value)
+
+    def sim_step(self, v0=None, act_start=None, step=0, actual=None, advance=True, log=None, outputs=False):
+        """one plant step of the resident batch on device (mld_sim_step_batch): the reference's lsim_k(x_k, v_k=, omega_k) with the whole step-0 slice --
+        of the last solve's plans (v0=None; instances without a usable plan are skipped and counted) or the caller's v0 (batch, nv) / (nv,) -- under the
+        forecast's step 0 or, with actual, the element `step` of the realised series at act_start (batch, n_groups) / (n_groups,) of the resident profile
+        library (None re-uses the resident actual starts).  actual defaults to `act_start is not None`, log to "a log has begun".  advance: x0 <- x_k1
+        and the forecast rotated, as advance(); False is a what-if that changes nothing.  Returns the number of skipped instances, or with outputs=True
+        dict(x_k1, y, cons (bool), cons_vio, cons_row, n_skipped)."""
+        d, B = self.model.dims, self.batch
+        nv = self.model.nv
+        if v0 is not None:
+            v0 = np.asarray(v0, dtype=np.float64)
+            if v0.shape == (nv,):
+                v0 = np.broadcast_to(v0, (B, nv))
+            if v0.shape != (B, nv):
+                raise ValueError("v0 has shape %s, expected (%d, %d) or (%d,)" % (v0.shape, B, nv, nv))
+            v0 = np.ascontiguousarray(v0)
+        st = self._start_array(act_start, 0) if act_start is not None else None
+        if actual is None:
+            actual = act_start is not None
+        if log is None:
+            log = self.sim_log_count()[1] > 0
+        flags = (_lib.MLD_SIM_ADVANCE if advance else 0) | (_lib.MLD_SIM_ACTUAL if actual else 0) | (_lib.MLD_SIM_LOG if log else 0)
+        skipped = C.c_int32(0)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None
+        out = None
+        if outputs:
+            out = dict(x_k1=np.zeros((B, d["nx"])), y=np.zeros((B, d["ny"])), cons=np.zeros((B, d["nc"]), np.uint8), cons_vio=np.zeros(B),
+                       cons_row=np.zeros(B, np.int32))
+        check(_lib.load().mld_sim_step_batch(
+            self._h, _lib.dptr(v0), st.ctypes.data_as(C.POINTER(C.c_int64)) if st is not None else None, int(step), flags,
+            _lib.dptr(out["x_k1"]) if out else None, _lib.dptr(out["y"]) if out else None,
+            out["cons"].ctypes.data_as(C.POINTER(C.c_uint8)) if out else None, _lib.dptr(out["cons_vio"]) if out else None,
+            ip(out["cons_row"]) if out else None, C.byref(skipped)))
+        if not outputs:
+            return int(skipped.value)
+        out["cons"] = out["cons"].astype(bool)
+        out["n_skipped"] = int(skipped.value)
+        return out
+
+    def sim_log(self, first=0, count=None):
+        """records [first, first + count) of the resident log (mld_download_sim_log; count=None: all from first): dict of arrays (count, batch, width) --
+        x, v, y, omega, x_k1, cons (bool), cons_vio, cons_row, obj, lower_bound, status, nodes.  simlog.to_mld_sim_log turns one instance into the
+        reference's MldSimLog."""
+        d, B = self.model.dims, self.batch
+        first = int(first)
+        if count is None:
+            count = self.sim_log_count()[0] - first
+        K = int(count)
+        if K < 0:
+            raise ValueError("sim_log: first = %d lies beyond the %d logged steps" % (first, K + first))
+        out = dict(x=np.zeros((K, B, d["nx"])), v=np.zeros((K, B, self.model.nv)), y=np.zeros((K, B, d["ny"])), omega=np.zeros((K, B, d["nomega"])),
+                   x_k1=np.zeros((K, B, d["nx"])), cons=np.zeros((K, B, d["nc"]), np.uint8), cons_vio=np.zeros((K, B)), cons_row=np.zeros((K, B), np.int32),
+                   obj=np.zeros((K, B)), lower_bound=np.zeros((K, B)), status=np.zeros((K, B), np.int32), nodes=np.zeros((K, B), np.int32))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        check(_lib.load().mld_download_sim_log(
+            self._h, first, K, _lib.dptr(out["x"]), _lib.dptr(out["v"]), _lib.dptr(out["y"]), _lib.dptr(out["omega"]), _lib.dptr(out["x_k1"]),
+            out["cons"].ctypes.data_as(C.POINTER(C.c_uint8)), _lib.dptr(out["cons_vio"]), ip(out["cons_row"]), _lib.dptr(out["obj"]),
+            _lib.dptr(out["lower_bound"]), ip(out["status"]), ip(out["nodes"])))
+        out["cons"] = out["cons"].astype(bool)
+        return out
+
     def set_warm_start(self, bin_start):
         """MIP start of the resident batch (mld_set_warm_start): (batch, n_bin) values of the binaries, a row starting with 255 = no
         start for that instance; None clears.  A full decision vector (batch, n) is accepted too (its binaries are rounded)."""
