@@ -1,0 +1,590 @@
+// Services on the resident batch between solves: disturbance profiles, per-instance cost, predicted trajectories, solution quality, receding
+// horizon, plant step and simulation log.
+extern "C" {
+
+/* ---- resident disturbance profiles ----------------------------------------------------------------------------------------------------------------
+ * The reference cuts every disturbance window out of a series it holds once (get_omega_tilde_k_hat / _act, modelling/micro_grid_agents.py:236-298;
+ * get_omega_tilde_scenario, :206-232); here the series are a flat library in HBM and a window is a start offset (profiles.inc: k_profile_windows and the
+ * window rule).  Every start is tested on the host before anything is queued: no kernel is launched with an offset that has not passed. */
+int mld_upload_profiles(mld_problem_t *p, int64_t lib_len, const double *lib, int n_groups, const int32_t *group_width)
+{
+    if (int rc = entry_guard(p, "mld_upload_profiles", true, nullptr)) return rc;
+    if (!p) { mld_set_error("mld_upload_profiles: null problem"); return MLD_ERR_INVALID; }
+    const int nomega = p->model->dims.nomega;
+    if (nomega == 0) { mld_set_error("mld_upload_profiles: the model has no disturbance (nomega = 0): there is nothing a profile could fill"); return MLD_ERR_INVALID; }
+    if (lib_len < 0 || (lib_len > 0 && !lib)) { mld_set_error("mld_upload_profiles: lib_len = %lld%s", (long long)lib_len, lib_len > 0 ? " without a library" : ""); return MLD_ERR_INVALID; }
+    if (n_groups < 0 || n_groups > nomega || (n_groups > 0 && !group_width)) { mld_set_error("mld_upload_profiles: n_groups = %d (0 .. nomega = %d, with group_width)", n_groups, nomega); return MLD_ERR_INVALID; }
+    std::vector<int> width;
+    if (n_groups == 0) width.assign(1, nomega);
+    else {
+        long long sum = 0;
+        for (int g = 0; g < n_groups; ++g) {
+            if (group_width[g] < 1) { mld_set_error("mld_upload_profiles: group_width[%d] = %d (every group needs at least one channel)", g, group_width[g]); return MLD_ERR_INVALID; }
+            sum += group_width[g];
+        }
+        if (sum != nomega) { mld_set_error("mld_upload_profiles: the group widths sum to %lld, not to nomega = %d", sum, nomega); return MLD_ERR_INVALID; }
+        width.assign(group_width, group_width + n_groups);
+    }
+    if (lib_len == 0) {      /* frees the library; the start arrays go with it */
+        p->pf_lib.reset(); p->pf_chan.reset(); reset_profile_starts(p);
+        p->pf_len = 0; p->pf_groups = 0; p->pf_width.clear();
+        return MLD_OK;
+    }
+    std::vector<PfChan> chan;
+    for (int g = 0; g < (int)width.size(); ++g) for (int o = 0; o < width[g]; ++o) chan.push_back(PfChan{g, o, width[g]});
+    DevBuf<double> d_lib; DevBuf<PfChan> d_chan;      /* built beside the resident library: a call that fails leaves it as it was */
+    HIP_TRY(d_lib.alloc((size_t)lib_len));
+    HIP_TRY(d_chan.alloc(chan.size()));
+    const hipStream_t sq = p->stream;
+    auto queue = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(d_lib, lib, sizeof(double) * (size_t)lib_len, hipMemcpyHostToDevice, sq));
+        HIP_TRY(hipMemcpyAsync(d_chan, chan.data(), sizeof(PfChan) * chan.size(), hipMemcpyHostToDevice, sq));
+        return MLD_OK;
+    };
+    if (int rc = queue_and_wait(sq, queue)) return rc;
+    p->pf_lib = std::move(d_lib); p->pf_chan = std::move(d_chan);
+    p->pf_len = lib_len; p->pf_groups = (int)width.size(); p->pf_width = width;
+    reset_profile_starts(p);      /* they pointed into the library that is gone */
+    return MLD_OK;
+}
+
+static void launch_profile_windows(const mld_problem *p, hipStream_t sq, int rows, int cols, int ld_cols, int col0, const long long *d_start, int step, double *dst)
+{
+    const long long total = (long long)rows * p->nW;
+    hipLaunchKernelGGL(k_profile_windows, dim3(profile_grid(total)), dim3(256), 0, sq, rows, p->nW, p->model->dims.nomega, cols, ld_cols, col0, p->pf_groups, d_start,
+                       p->pf_chan.get(), step, p->pf_lib.get(), dst);
+}
+
+int mld_forecast_from_profiles(mld_problem_t *p, const int64_t *start, int step)
+{
+    static const char who[] = "mld_forecast_from_profiles";
+    if (int rc = entry_guard(p, who, true, "no batch resident (mld_upload_batch)")) return rc;
+    int rc;
+    if ((rc = profile_ready(p, who, step))) return rc;
+    const int batch = p->batch, G = p->pf_groups;
+    std::vector<long long> gmax;
+    if (start) { if ((rc = profile_check_starts(p, who, PF_WINDOW, start, batch, 1, step, p->N, gmax))) return rc; }
+    else {
+        if (p->pf_forecast.batch != batch) { mld_set_error("%s: start == NULL, but no starts of this batch are resident (pass them once)", who); return MLD_ERR_INVALID; }
+        if ((rc = profile_check_resident(p, who, PF_WINDOW, p->pf_forecast.gmax, step, p->N))) return rc;
+    }
+    DevBuf<long long> d_start;
+    if (start) HIP_TRY(d_start.alloc((size_t)batch * G));
+    const hipStream_t sq = p->stream;
+    /* the new forecast is gathered into the spare input buffer and swapped in once the stream has finished: a call that fails changes nothing */
+    auto queue = [&]() -> int {
+        if (start) HIP_TRY(hipMemcpyAsync(d_start, start, sizeof(long long) * (size_t)batch * G, hipMemcpyHostToDevice, sq));
+        launch_profile_windows(p, sq, batch, 1, 1, 0, start ? d_start.get() : p->pf_forecast.d.get(), step, p->bat.omegab.get());
+        HIP_TRY(hipGetLastError());
+        return MLD_OK;
+    };
+    if ((rc = queue_and_wait(sq, queue))) return rc;
+    std::swap(p->bat.omega, p->bat.omegab);
+    if (start) set_starts(p->pf_forecast, std::move(d_start), batch, 1, gmax);
+    forecast_replaced(p);
+    return MLD_OK;
+}
+
+int mld_constraint_blocks_from_profiles(mld_problem_t *p, int n_cols, const int64_t *start, int step, const int32_t *col_rows, const double *x_cols)
+{
+    static const char who[] = "mld_constraint_blocks_from_profiles";
+    if (int rc = entry_guard(p, who, true, "upload the batch first")) return rc;
+    if (n_cols < 0) { mld_set_error("%s: n_cols = %d", who, n_cols); return MLD_ERR_INVALID; }
+    if (n_cols == 0) { p->n_xcols = 0; return MLD_OK; }
+    int rc;
+    if ((rc = profile_ready(p, who, step))) return rc;
+    const int batch = p->batch, G = p->pf_groups;
+    if ((long long)batch * n_cols > INT_MAX) { mld_set_error("%s: batch x n_cols = %lld windows (at most %d)", who, (long long)batch * n_cols, INT_MAX); return MLD_ERR_INVALID; }
+    if ((rc = check_col_rows(p, who, n_cols, col_rows))) return rc;
+    std::vector<long long> gmax;
+    if (start) { if ((rc = profile_check_starts(p, who, PF_WINDOW, start, batch, n_cols, step, p->N, gmax))) return rc; }
+    else {
+        if (p->pf_columns.batch != batch) { mld_set_error("%s: start == NULL, but no column starts of this batch are resident (pass them once)", who); return MLD_ERR_INVALID; }
+        if (p->pf_columns.cols != n_cols) { mld_set_error("%s: start == NULL with n_cols = %d, but the resident starts are those of %d columns", who, n_cols, p->pf_columns.cols); return MLD_ERR_INVALID; }
+        if ((rc = profile_check_resident(p, who, PF_WINDOW, p->pf_columns.gmax, step, p->N))) return rc;
+    }
+    DevBuf<long long> d_start;
+    if (start) HIP_TRY(d_start.alloc((size_t)batch * n_cols * G));
+    const bool with_x = x_cols && p->nx;
+    if ((rc = stage_xcols(p, n_cols, col_rows != nullptr, with_x))) return rc;
+    const hipStream_t sq = p->stream;
+    auto queue = [&]() -> int {
+        if (start) HIP_TRY(hipMemcpyAsync(d_start, start, sizeof(long long) * (size_t)batch * n_cols * G, hipMemcpyHostToDevice, sq));
+        if (col_rows) HIP_TRY(hipMemcpyAsync(p->bat.xrows, col_rows, sizeof(int) * n_cols, hipMemcpyHostToDevice, sq));
+        if (with_x) HIP_TRY(hipMemcpyAsync(p->bat.xcols_x, x_cols, sizeof(double) * (size_t)batch * n_cols * p->nx, hipMemcpyHostToDevice, sq));
+        launch_profile_windows(p, sq, batch * n_cols, n_cols, n_cols, 0, start ? d_start.get() : p->pf_columns.d.get(), step, p->bat.xcols.get());
+        HIP_TRY(hipGetLastError());
+        return MLD_OK;
+    };
+    if ((rc = queue_and_wait(sq, queue))) return rc;
+    if (start) set_starts(p->pf_columns, std::move(d_start), batch, n_cols, gmax);
+    p->n_xcols = n_cols;
+    return MLD_OK;
+}
+
+int mld_download_constraint_blocks(mld_problem_t *p, int32_t *n_cols_out, double *omega_cols, int32_t *col_rows, double *x_cols)
+{
+    if (int rc = entry_guard(p, "mld_download_constraint_blocks", false, "nothing uploaded")) return rc;
+    const int nc = p->n_xcols;
+    if (x_cols && nc && !p->has_xcols_x) { mld_set_error("mld_download_constraint_blocks: x_cols asked for, but the resident blocks have none (every column uses the instance's x0)"); return MLD_ERR_INVALID; }
+    if (n_cols_out) *n_cols_out = nc;
+    if (!nc) return MLD_OK;
+    if (omega_cols) HIP_TRY(hipMemcpy(omega_cols, p->bat.xcols, sizeof(double) * (size_t)p->batch * nc * p->nW, hipMemcpyDeviceToHost));
+    if (col_rows) {
+        if (p->bat.xrows) HIP_TRY(hipMemcpy(col_rows, p->bat.xrows, sizeof(int) * nc, hipMemcpyDeviceToHost));
+        else for (int c = 0; c < nc; ++c) col_rows[c] = p->m0;
+    }
+    if (x_cols) HIP_TRY(hipMemcpy(x_cols, p->bat.xcols_x, sizeof(double) * (size_t)p->batch * nc * p->nx, hipMemcpyDeviceToHost));
+    return MLD_OK;
+}
+
+/* Per-instance linear cost of the resident batch (the reference rebuilds its objective with the current tariff before every solve() call,
+ * micro_grid_control_simulation.py:194-198,229: N calls replaced by one batch may carry N price vectors).  Weights on v are kept as uploaded; weights on
+ * x_tilde / y_tilde are pulled back through the tightened model's condensed maps by ONE GEMM per model (k_inst_pullback; k_inst_pullback_valu under
+ * MLD_DBG_GEMM_VALU) into [q_b | cx_b | cw_b | c0_b].  The new cost is built in a buffer of its own: a call that fails leaves the resident one as it was. */
+int mld_upload_instance_cost(mld_problem_t *p, const double *lin_v, const double *lin_x, const double *lin_y)
+{
+    if (int rc = entry_guard(p, "mld_upload_instance_cost", true, "upload a batch first (the cost belongs to its instances)")) return rc;
+    const int n = p->n, nx = p->nx, nW = p->nW, batch = p->batch;
+    const int NX = p->N * p->model->dims.nx, NY = p->N * p->model->dims.ny;
+    if (lin_x && NX == 0) { mld_set_error("mld_upload_instance_cost: lin_x given but the model has no state (nx = 0)"); return MLD_ERR_INVALID; }
+    if (lin_y && NY == 0) { mld_set_error("mld_upload_instance_cost: lin_y given but the model has no output (ny = 0)"); return MLD_ERR_INVALID; }
+    if (!lin_v && !lin_x && !lin_y) { p->bat.icost.reset(); p->bat.qs_inst_t.reset(); p->ic_ld = 0; return MLD_OK; }
+    const hipStream_t sq = p->stream;
+    const bool pull = lin_x || lin_y;
+    const int ld = pull ? n + nx + nW + 1 : n;      /* weights on v only: no GEMM, cx / cw / c0 are zero and not stored */
+    DevBuf<double> ic, d_w;
+    HIP_TRY(ic.alloc((size_t)batch * std::max(1, ld)));
+    /* everything queued on the stream and waited for on every path (queue_and_wait): the caller's arrays and the temporaries may go when this returns */
+    auto queue = [&]() -> int {
+    if (!lin_v || pull) HIP_TRY(hipMemsetAsync(ic, 0, sizeof(double) * (size_t)batch * std::max(1, ld), sq));
+    if (lin_v && n && !pull) HIP_TRY(hipMemcpyAsync(ic, lin_v, sizeof(double) * (size_t)batch * n, hipMemcpyHostToDevice, sq));      /* rows are contiguous: one plain copy */
+    else if (lin_v && n) HIP_TRY(hipMemcpy2DAsync(ic, sizeof(double) * ld, lin_v, sizeof(double) * n, sizeof(double) * n, batch, hipMemcpyHostToDevice, sq));
+    if (pull) {
+        const int K = NX + NY;
+        HIP_TRY(d_w.alloc((size_t)batch * K));
+        if (!lin_x || !lin_y) HIP_TRY(hipMemsetAsync(d_w, 0, sizeof(double) * (size_t)batch * K, sq));
+        if (lin_x) HIP_TRY(hipMemcpy2DAsync(d_w, sizeof(double) * K, lin_x, sizeof(double) * NX, sizeof(double) * NX, batch, hipMemcpyHostToDevice, sq));
+        if (lin_y) HIP_TRY(hipMemcpy2DAsync(d_w.get() + NX, sizeof(double) * K, lin_y, sizeof(double) * NY, sizeof(double) * NY, batch, hipMemcpyHostToDevice, sq));
+        const PbMaps mp = pullback_maps(p);
+        if (p->opts.reserved & MLD_DBG_GEMM_VALU)
+            hipLaunchKernelGGL(k_inst_pullback_valu, dim3(batch), dim3(256), sizeof(double) * K, sq, NX, NY, n, nx, nW, mp, p->has_midx ? p->bat.model_idx.get() : nullptr, d_w.get(), ic.get());
+        else if (p->opts.flags & MLD_F32)
+            hipLaunchKernelGGL(k_inst_pullback<true>, dim3(p->n_groups), dim3(64 * RM_WAVES), 0, sq, NX, NY, n, nx, nW, mp, p->bat.groups.get(), p->bat.perm.get(), d_w.get(), ic.get());
+        else
+            hipLaunchKernelGGL(k_inst_pullback<false>, dim3(p->n_groups), dim3(64 * RM_WAVES), 0, sq, NX, NY, n, nx, nW, mp, p->bat.groups.get(), p->bat.perm.get(), d_w.get(), ic.get());
+        HIP_TRY(hipGetLastError());
+    }
+    return MLD_OK;
+    };
+    if (int rc = queue_and_wait(sq, queue)) return rc;
+    p->bat.icost = std::move(ic); p->ic_ld = ld;
+    return MLD_OK;
+}
+
+int mld_download_instance_cost(mld_problem_t *p, double *q_out, double *const_out)
+{
+    if (int rc = entry_guard(p, "mld_download_instance_cost", false, "nothing uploaded")) return rc;
+    const size_t b = p->batch, n = p->n;
+    if (!p->ic_ld) {
+        if (q_out) memset(q_out, 0, sizeof(double) * b * n);
+        if (const_out) memset(const_out, 0, sizeof(double) * b);
+        return MLD_OK;
+    }
+    if (q_out && n) HIP_TRY(hipMemcpy2D(q_out, sizeof(double) * n, p->bat.icost, sizeof(double) * p->ic_ld, sizeof(double) * n, b, hipMemcpyDeviceToHost));
+    if (const_out) {
+        memset(const_out, 0, sizeof(double) * b);
+        if (p->ic_ld > p->n) {
+            DevBuf<double> d_c;
+            HIP_TRY(d_c.alloc(b));
+            HIP_TRY(hipMemsetAsync(d_c, 0, sizeof(double) * b, p->stream));
+            hipLaunchKernelGGL(k_inst_const, dim3((p->batch + 3) / 4), dim3(256), 0, p->stream, p->batch, p->n, p->nx, p->nW, p->ic_ld, p->bat.icost, p->bat.x0, p->bat.omega, d_c.get());
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(const_out, d_c, sizeof(double) * b, hipMemcpyDeviceToHost, p->stream));
+            HIP_TRY(hipStreamSynchronize(p->stream));
+        }
+    }
+    return MLD_OK;
+}
+
+/* Predicted state and output trajectories of the resident batch (gen_state_output_vars, controllers/components/variables.py:246-286: x_tilde :259-265,
+ * y_tilde :269-275, with its variables= / x_k= / omega_tilde_k= arguments) as ONE GEMM per model over [v | x0 | omega | 1] (k_trajectory;
+ * k_trajectory_valu under MLD_DBG_GEMM_VALU).  The state and output maps of the tightened model are the original ones (tightening changes F1 / F2 / Psi
+ * and f5 only).  v == NULL: the resident solution, rows of instances without a usable plan all NaN; v given: the caller's plans under the current inputs.
+ * The results are built in buffers of their own and every path waits for the stream, so a call that fails changes nothing. */
+int mld_predict_batch(mld_problem_t *p, const double *v, double *x_out, double *y_out)
+{
+    if (int rc = entry_guard(p, "mld_predict_batch", true, "no batch resident (mld_upload_batch)")) return rc;
+    const mld_dims &d = p->model->dims;
+    const int n = p->n, nx = p->nx, nW = p->nW, batch = p->batch, N = p->N;
+    const int NX = N * d.nx, NY = N * d.ny;
+    if (x_out && NX == 0) { mld_set_error("mld_predict_batch: x_out given but the model has no state (nx = 0)"); return MLD_ERR_INVALID; }
+    if (y_out && NY == 0) { mld_set_error("mld_predict_batch: y_out given but the model has no output (ny = 0)"); return MLD_ERR_INVALID; }
+    if (!v && !p->solved) { mld_set_error("mld_predict_batch: the resident batch has not been solved since its upload / selection (there is no plan to evaluate; pass v)"); return MLD_ERR_INVALID; }
+    if (!v && p->advanced) { mld_set_error("mld_predict_batch: mld_advance_batch has moved the inputs on -- the resident plan belongs to inputs that are gone (solve again, or pass v)"); return MLD_ERR_INVALID; }
+    if (!x_out && !y_out) return MLD_OK;
+    const hipStream_t sq = p->stream;
+    DevBuf<double> d_v, d_x, d_y;
+    if (x_out) HIP_TRY(d_x.alloc((size_t)batch * NX));
+    if (y_out) HIP_TRY(d_y.alloc((size_t)batch * NY));
+    if (v) HIP_TRY(d_v.alloc((size_t)batch * std::max(1, n)));
+    /* everything queued on the stream and waited for on every path (queue_and_wait): the caller's arrays and the temporaries may go when this returns */
+    auto queue = [&]() -> int {
+        if (v && n) HIP_TRY(hipMemcpyAsync(d_v, v, sizeof(double) * (size_t)batch * n, hipMemcpyHostToDevice, sq));
+        const double *pv = v ? d_v.get() : p->bat.v.get();      /* (the resident solution: rows < batch are the instances', hand-off items come after them) */
+        const int *st = v ? nullptr : p->bat.status.get();
+        const double *ob = v ? nullptr : p->bat.obj.get();
+        const PbMaps mp = pullback_maps(p);
+        const int r_begin = x_out ? 0 : NX, r_end = y_out ? NX + NY : NX;      /* rows of the stacked maps that are asked for */
+        if (p->opts.reserved & MLD_DBG_GEMM_VALU)
+            hipLaunchKernelGGL(k_trajectory_valu, dim3(batch), dim3(256), sizeof(double) * (n + nx + nW + 1), sq, NX, NY, n, nx, nW, mp,
+                               p->has_midx ? p->bat.model_idx.get() : nullptr, pv, p->bat.x0.get(), p->bat.omega.get(), st, ob, r_begin, r_end, d_x.get(), d_y.get());
+        else if (p->opts.flags & MLD_F32)
+            hipLaunchKernelGGL(k_trajectory<true>, dim3(p->n_groups), dim3(64 * RM_WAVES), 0, sq, N, d.nx, d.ny, p->nv, d.nomega, mp, p->bat.groups.get(), p->bat.perm.get(),
+                               pv, p->bat.x0.get(), p->bat.omega.get(), st, ob, r_begin, r_end, d_x.get(), d_y.get());
+        else
+            hipLaunchKernelGGL(k_trajectory<false>, dim3(p->n_groups), dim3(64 * RM_WAVES), 0, sq, N, d.nx, d.ny, p->nv, d.nomega, mp, p->bat.groups.get(), p->bat.perm.get(),
+                               pv, p->bat.x0.get(), p->bat.omega.get(), st, ob, r_begin, r_end, d_x.get(), d_y.get());
+        HIP_TRY(hipGetLastError());
+        if (x_out) HIP_TRY(hipMemcpyAsync(x_out, d_x, sizeof(double) * (size_t)batch * NX, hipMemcpyDeviceToHost, sq));
+        if (y_out) HIP_TRY(hipMemcpyAsync(y_out, d_y, sizeof(double) * (size_t)batch * NY, hipMemcpyDeviceToHost, sq));
+        return MLD_OK;
+    };
+    return queue_and_wait(sq, queue);
+}
+
+/* Solution quality of the resident batch: what the reference's backend reports after every solve (ObjVal, ConstrVio, IntVio, BoundVio;
+ * controllers/controller_base.py:509) for the resident or the caller's plans, on the ORIGINAL model's rows (condensed on first use, as mld_rhs_batch
+ * does) and any disturbance columns (the layout of gen_evo_constraints, controller_base.py:411-456).  Kernels: evaluate.inc.  Every result is built
+ * in a buffer of its own and every path waits for the stream, so a call that fails changes nothing; nothing the solve path reads is written. */
+#define EV_SLICE_BYTES ((size_t)256 << 20)      /* device copy of the caller's validation columns: at most this much at a time (at least one column) */
+/* The columns of a call come from one of two sources: the caller's array (omega_cols, mld_evaluate_batch) or starts into the resident profile library
+ * (start / step, mld_evaluate_batch_profiles: from_profiles).  The sources differ in how a slice of columns reaches the slice buffer d_om -- a strided copy
+ * from the host, or k_profile_windows gathering it there -- and in nothing else: the same slices, the same launches of k_evaluate on the same buffer. */
+static int evaluate_impl(mld_problem_t *p, const char *who, const double *v, int n_cols, const double *omega_cols, bool from_profiles, const int64_t *start, int step,
+                         const int32_t *col_rows, const double *x_cols,
+                         double *obj_out, double *constr_vio_out, int32_t *constr_row_out, double *int_vio_out, double *bound_vio_out)
+{
+    if (int rc = entry_guard(p, who, true, "no batch resident (mld_upload_batch)")) return rc;
+    const mld_dims &d = p->model->dims;
+    const int n = p->n, nx = p->nx, nW = p->nW, batch = p->batch, m0 = p->m0, M = p->n_models;
+    if (n_cols < 0) { mld_set_error("%s: n_cols = %d", who, n_cols); return MLD_ERR_INVALID; }
+    if (!from_profiles && n_cols > 0 && nW && !omega_cols) { mld_set_error("%s: n_cols = %d without omega_cols (nomega > 0)", who, n_cols); return MLD_ERR_INVALID; }
+    if (from_profiles && n_cols < 1) { mld_set_error("%s: n_cols = %d (the profile columns of a call: at least one)", who, n_cols); return MLD_ERR_INVALID; }
+    if (from_profiles && !start) { mld_set_error("%s: start == NULL (the resident column starts belong to the problem's blocks and are not used here)", who); return MLD_ERR_INVALID; }
+    if (x_cols && nx == 0) { mld_set_error("%s: x_cols given but the model has no state (nx = 0)", who); return MLD_ERR_INVALID; }
+    if (int rc = check_col_rows(p, who, n_cols, col_rows)) return rc;
+    if (!v && !p->solved) { mld_set_error("%s: the resident batch has not been solved since its upload / selection (there is no plan to evaluate; pass v)", who); return MLD_ERR_INVALID; }
+    if (!v && p->advanced) { mld_set_error("%s: mld_advance_batch has moved the inputs on -- the resident plan belongs to inputs that are gone (solve again, or pass v)", who); return MLD_ERR_INVALID; }
+    int rc;
+    if (from_profiles) {      /* every start against the window rule, before anything is queued */
+        std::vector<long long> gmax;
+        if ((rc = profile_ready(p, who, step))) return rc;
+        if ((long long)batch * n_cols > INT_MAX) { mld_set_error("%s: batch x n_cols = %lld windows (at most %d)", who, (long long)batch * n_cols, INT_MAX); return MLD_ERR_INVALID; }
+        if ((rc = profile_check_starts(p, who, PF_WINDOW, start, batch, n_cols, step, p->N, gmax))) return rc;
+    }
+    if (!obj_out && !constr_vio_out && !constr_row_out && !int_vio_out && !bound_vio_out) return MLD_OK;
+    const hipStream_t sq = p->stream;
+    const bool want_c = constr_vio_out || constr_row_out;
+    const bool valu = (p->opts.reserved & MLD_DBG_GEMM_VALU) != 0;
+    mld_model *mo = p->model;
+    if (want_c && m0 && (mo->cond_N != p->N || !mo->out64) && (rc = condense_model_device(mo, p->N, nullptr, sq))) return rc;
+    const int *midx = p->has_midx ? p->bat.model_idx.get() : nullptr;
+    const size_t nout = n_cols > 0 ? (size_t)n_cols : 1;      /* constraint results per instance */
+    /* columns of the caller per launch: the device copy of a slice stays within EV_SLICE_BYTES */
+    const size_t col_bytes = sizeof(double) * (size_t)batch * std::max(1, nW + (x_cols ? nx : 0));
+    const int slice = n_cols > 0 ? (int)std::min<size_t>((size_t)n_cols, std::max<size_t>(1, EV_SLICE_BYTES / col_bytes)) : 0;
+    DevBuf<double> d_v, d_hv, d_part, d_om, d_xc, d_vio, d_obj, d_iv, d_bv, d_qi, d_rc, d_one;
+    DevBuf<int> d_rows, d_row; DevBuf<long long> d_start;
+    if (v) HIP_TRY(d_v.alloc((size_t)batch * std::max(1, n)));
+    if (want_c) {
+        HIP_TRY(d_hv.alloc((size_t)batch * std::max(1, m0)));
+        if (!valu && nx + nW > EV_KC) HIP_TRY(d_part.alloc((size_t)batch * std::max(1, m0)));
+        HIP_TRY(d_vio.alloc((size_t)batch * nout)); HIP_TRY(d_row.alloc((size_t)batch * nout));
+        if (slice && nW) HIP_TRY(d_om.alloc((size_t)batch * slice * nW));
+        if (slice && x_cols) HIP_TRY(d_xc.alloc((size_t)batch * slice * nx));
+        if (slice && col_rows) HIP_TRY(d_rows.alloc(n_cols));
+        if (from_profiles) HIP_TRY(d_start.alloc((size_t)batch * n_cols * p->pf_groups));
+    }
+    const bool inst_q = p->has_quad || p->ic_ld;
+    if (obj_out) {
+        HIP_TRY(d_obj.alloc(batch));
+        if (inst_q) { HIP_TRY(d_qi.alloc((size_t)batch * std::max(1, n))); HIP_TRY(d_rc.alloc(batch)); HIP_TRY(d_one.alloc((size_t)std::max(1, n) * M)); }
+    }
+    if (int_vio_out) HIP_TRY(d_iv.alloc(batch));
+    if (bound_vio_out) HIP_TRY(d_bv.alloc(batch));
+    /* everything queued on the stream and waited for on every path (queue_and_wait): the caller's arrays and the temporaries may go when this returns */
+    auto queue = [&]() -> int {
+        if (v && n) HIP_TRY(hipMemcpyAsync(d_v, v, sizeof(double) * (size_t)batch * n, hipMemcpyHostToDevice, sq));
+        const double *pv = v ? d_v.get() : p->bat.v.get();      /* (the resident solution: rows < batch are the instances', after the hand-off's merge) */
+        const int *st = v ? nullptr : p->bat.status.get();
+        const double *ob = v ? nullptr : p->bat.obj.get();
+        if (want_c) {
+            EvCols ec;
+            ec.x0 = p->bat.x0.get(); ec.omega = p->bat.omega.get();
+            const double *Hv = m0 ? mo->d_out[O_HV].get() : nullptr, *Hx = m0 && nx ? mo->d_out[O_HX].get() : nullptr;
+            const double *Hw = m0 && nW ? mo->d_out[O_HW].get() : nullptr, *H5 = m0 ? mo->d_out[O_H5].get() : nullptr;
+            auto launch_ev = [&](int do_v) {
+                if (valu)
+                    hipLaunchKernelGGL(k_evaluate_valu, dim3(batch), dim3(256), sizeof(double) * (n + m0), sq, m0, n, nx, nW, Hv, Hx, Hw, H5, midx, pv, st, ob, do_v, ec,
+                                       d_hv.get(), d_vio.get(), d_row.get());
+                else
+                    hipLaunchKernelGGL(k_evaluate, dim3(p->n_groups), dim3(64 * RM_WAVES), 0, sq, m0, std::max(1, d.nc), p->nv, d.nomega, n, nx, nW, Hv, Hx, Hw, H5,
+                                       p->bat.groups.get(), p->bat.perm.get(), pv, st, ob, do_v, ec, d_hv.get(), d_part.get(), d_vio.get(), d_row.get());
+            };
+            if (n_cols == 0) {      /* the problem as posed: the columns the next solve would enforce */
+                ec.n_cols = p->n_xcols; ec.std = p->std_block ? 1 : 0; ec.per_col = 0; ec.ld_out = 1; ec.col0 = 0;
+                ec.omc = p->bat.xcols.get(); ec.xc = p->has_xcols_x ? p->bat.xcols_x.get() : nullptr; ec.rows = p->n_xcols ? p->bat.xrows.get() : nullptr;
+                launch_ev(1);
+            } else {
+                if (col_rows) HIP_TRY(hipMemcpyAsync(d_rows, col_rows, sizeof(int) * n_cols, hipMemcpyHostToDevice, sq));
+                if (from_profiles) HIP_TRY(hipMemcpyAsync(d_start, start, sizeof(long long) * (size_t)batch * n_cols * p->pf_groups, hipMemcpyHostToDevice, sq));
+                for (int c0 = 0; c0 < n_cols; c0 += slice) {
+                    const int nc_ = std::min(slice, n_cols - c0);
+                    if (from_profiles) { launch_profile_windows(p, sq, batch * nc_, nc_, n_cols, c0, d_start.get(), step, d_om.get()); HIP_TRY(hipGetLastError()); }
+                    else if (nW) HIP_TRY(hipMemcpy2DAsync(d_om, sizeof(double) * nc_ * nW, omega_cols + (size_t)c0 * nW, sizeof(double) * n_cols * nW, sizeof(double) * nc_ * nW, batch, hipMemcpyHostToDevice, sq));
+                    if (x_cols) HIP_TRY(hipMemcpy2DAsync(d_xc, sizeof(double) * nc_ * nx, x_cols + (size_t)c0 * nx, sizeof(double) * n_cols * nx, sizeof(double) * nc_ * nx, batch, hipMemcpyHostToDevice, sq));
+                    ec.n_cols = nc_; ec.std = 0; ec.per_col = 1; ec.ld_out = n_cols; ec.col0 = c0;
+                    ec.omc = d_om.get(); ec.xc = x_cols ? d_xc.get() : nullptr; ec.rows = col_rows ? d_rows.get() + c0 : nullptr;
+                    launch_ev(c0 == 0);
+                    HIP_TRY(hipGetLastError());
+                }
+            }
+            HIP_TRY(hipGetLastError());
+            if (constr_vio_out) HIP_TRY(hipMemcpyAsync(constr_vio_out, d_vio, sizeof(double) * (size_t)batch * nout, hipMemcpyDeviceToHost, sq));
+            if (constr_row_out) HIP_TRY(hipMemcpyAsync(constr_row_out, d_row, sizeof(int) * (size_t)batch * nout, hipMemcpyDeviceToHost, sq));
+        }
+        if (int_vio_out || bound_vio_out) {
+            hipLaunchKernelGGL(k_eval_point, dim3((batch + 3) / 4), dim3(256), 0, sq, batch, n, p->nv, d.nu, d.nu_l, d.ndelta, d.nz, d.nmu, d.nmu_l, pv, st, ob, d_iv.get(), d_bv.get());
+            HIP_TRY(hipGetLastError());
+            if (int_vio_out) HIP_TRY(hipMemcpyAsync(int_vio_out, d_iv, sizeof(double) * batch, hipMemcpyDeviceToHost, sq));
+            if (bound_vio_out) HIP_TRY(hipMemcpyAsync(bound_vio_out, d_bv, sizeof(double) * batch, hipMemcpyDeviceToHost, sq));
+        }
+        if (obj_out) {
+            /* the per-instance q and constant at the current inputs as the solve path computes them, with unit column scales and into buffers of this
+             * call (the solve path's qs_inst / rconst are not touched) */
+            if (inst_q) {
+                const size_t one = (size_t)std::max(1, n) * M;
+                hipLaunchKernelGGL(k_fill_f64, dim3((unsigned)((one + 255) / 256)), dim3(256), 0, sq, one, 1.0, d_one.get());
+                if (int rc = launch_instance_cost(p, d_one.get(), d_qi.get(), d_rc.get(), nullptr, nullptr)) return rc;
+            }
+            hipLaunchKernelGGL(k_eval_obj, dim3(batch), dim3(256), sizeof(double) * std::max(1, n), sq, n, nx, nW, p->d_q0.get(), inst_q ? d_qi.get() : nullptr,
+                               p->has_quad ? p->d_P.get() : nullptr, nx ? p->d_cx.get() : nullptr, nW ? p->d_cw.get() : nullptr, p->d_c0.get(),
+                               inst_q ? d_rc.get() : nullptr, midx, pv, p->bat.x0.get(), p->bat.omega.get(), st, ob, d_obj.get());
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(obj_out, d_obj, sizeof(double) * batch, hipMemcpyDeviceToHost, sq));
+        }
+        return MLD_OK;
+    };
+    return queue_and_wait(sq, queue);
+}
+
+int mld_evaluate_batch(mld_problem_t *p, const double *v, int n_cols, const double *omega_cols, const int32_t *col_rows, const double *x_cols,
+                       double *obj_out, double *constr_vio_out, int32_t *constr_row_out, double *int_vio_out, double *bound_vio_out)
+{
+    return evaluate_impl(p, "mld_evaluate_batch", v, n_cols, omega_cols, false, nullptr, 0, col_rows, x_cols, obj_out, constr_vio_out, constr_row_out, int_vio_out, bound_vio_out);
+}
+
+int mld_evaluate_batch_profiles(mld_problem_t *p, const double *v, int n_cols, const int64_t *start, int step, const int32_t *col_rows, const double *x_cols,
+                                double *obj_out, double *constr_vio_out, int32_t *constr_row_out, double *int_vio_out, double *bound_vio_out)
+{
+    return evaluate_impl(p, "mld_evaluate_batch_profiles", v, n_cols, nullptr, true, start, step, col_rows, x_cols, obj_out, constr_vio_out, constr_row_out, int_vio_out, bound_vio_out);
+}
+
+int mld_advance_batch2(mld_problem_t *p, int32_t *n_skipped_out)
+{
+    if (int rc = entry_guard(p, "mld_advance_batch", false, "nothing uploaded / solved")) return rc;
+    if (!p->solved) { mld_set_error("mld_advance_batch: the resident batch has not been solved since its upload / selection (there is no plan to apply)"); return MLD_ERR_INVALID; }
+    if (p->advanced) { mld_set_error("mld_advance_batch: the last solve's plan has already been applied -- solve the advanced batch first (a second advance would apply the same step-0 inputs to a state that has moved on)"); return MLD_ERR_INVALID; }
+    mld_model *m = p->model;
+    const mld_dims &d = m->dims;
+    if (!m->d_pack) { mld_set_error("mld_advance_batch: model without matrices"); return MLD_ERR_INVALID; }
+    if (m->tv_N > 0) { mld_set_error("mld_advance_batch: time-varying models (mld_model_create_tv) are not advanced on the device -- the step models would have to shift with the horizon"); return MLD_ERR_INVALID; }
+    const size_t bx = ((size_t)p->batch * std::max(1, p->nx) + 255) / 256, bw = ((size_t)p->batch * std::max(1, p->nW) + 255) / 256;
+    const int grid = (int)std::max<size_t>(bx, std::min<size_t>(bw, (size_t)1 << 20));   /* the state part is one thread per element, the shift strides */
+    HIP_TRY(hipMemsetAsync(p->bat.skipped, 0, sizeof(int), p->stream));
+    hipLaunchKernelGGL(k_advance, dim3(grid), dim3(256), 0, p->stream, p->batch, p->nx, p->nv, d.nomega, p->N,
+                       m->d_pack, m->pack_len, 1, m->pack_off.A, m->pack_off.B4, m->pack_off.b5, m->pack_off.Bv,
+                       p->has_midx ? p->bat.model_idx : nullptr, p->bat.x0, p->bat.omega, p->bat.v, (size_t)p->n, p->bat.x0b, p->bat.omegab,
+                       p->bat.status, p->bat.obj, p->bat.skipped);
+    HIP_TRY(hipGetLastError());
+    int skipped = 0;
+    HIP_TRY(hipMemcpyAsync(&skipped, p->bat.skipped, sizeof(int), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    std::swap(p->bat.x0, p->bat.x0b); std::swap(p->bat.omega, p->bat.omegab);
+    inputs_advanced_by_plan(p);
+    if (n_skipped_out) *n_skipped_out = skipped;
+    return MLD_OK;
+}
+
+int mld_advance_batch(mld_problem_t *p) { return mld_advance_batch2(p, nullptr); }
+
+/* ---- plant step and simulation log of the resident batch -------------------------------------------------------------------------------------------
+ * One step of the reference's closed loop after the solve: ControllerBase.sim_step_k -> MldModel.lsim_k -> MldSimLog (controllers/controller_base.py:
+ * 229-253, models/mld_model.py:647-699, controller_base.py:58-146), with the whole step-0 slice v0 = [u; delta; z; mu] given (lsim_k's v_k=, no
+ * auxiliary resolution) -- the resident plan's or the caller's -- under the forecast's step 0 or the REALISED disturbance out of the profile library.
+ * Kernel: sim_step.inc.  Everything is tested on the host before anything is queued, the new inputs are built in the spare buffers and swapped in by
+ * the host, the starts of the realised series in a buffer of their own: a call that is refused changes nothing. */
+int mld_sim_log_begin(mld_problem_t *p, int capacity)
+{
+    static const char who[] = "mld_sim_log_begin";
+    if (int rc = entry_guard(p, who, true, "no batch resident (mld_upload_batch): the log belongs to a batch")) return rc;
+    if (capacity < 0) { mld_set_error("%s: capacity = %d", who, capacity); return MLD_ERR_INVALID; }
+    if (capacity == 0) { p->slog = mld_problem::SimLog(); return MLD_OK; }
+    const mld_dims &d = p->model->dims;
+    const size_t widest = (size_t)std::max(std::max(std::max(d.nx, p->nv), std::max(d.ny, d.nomega)), std::max(d.nc, 1));
+    const size_t cb = (size_t)capacity * (size_t)p->batch;
+    if (cb > SIZE_MAX / sizeof(double) / widest) { mld_set_error("%s: capacity %d x batch %d x %zu entries does not fit size_t", who, capacity, p->batch, widest); return MLD_ERR_INVALID; }
+    mld_problem::SimLog L;      /* built beside the resident log: an allocation failure leaves that as it was */
+    hipError_t e = hipSuccess;
+    auto take = [&](auto &buf, size_t count) { if (e == hipSuccess) e = buf.alloc(count); };
+    take(L.x, cb * d.nx); take(L.v, cb * p->nv); take(L.y, cb * d.ny); take(L.om, cb * d.nomega); take(L.x_k1, cb * d.nx);
+    take(L.vio, cb); take(L.obj, cb); take(L.lb, cb); take(L.cons, cb * d.nc); take(L.row, cb); take(L.status, cb); take(L.nodes, cb);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        mld_set_error("%s: %s for %d records of %d instances (%zu bytes)", who, hipGetErrorString(e), capacity, p->batch,
+                      cb * ((2 * (size_t)d.nx + p->nv + d.ny + d.nomega + 3) * sizeof(double) + d.nc + 3 * sizeof(int)));
+        return MLD_ERR_HIP;
+    }
+    L.cap = capacity; L.count = 0;
+    p->slog = std::move(L);
+    return MLD_OK;
+}
+
+int mld_sim_log_count(mld_problem_t *p, int32_t *n_logged, int32_t *capacity)
+{
+    if (!p) { mld_set_error("mld_sim_log_count: null problem"); return MLD_ERR_INVALID; }
+    if (n_logged) *n_logged = p->slog.count;
+    if (capacity) *capacity = p->slog.cap;
+    return MLD_OK;
+}
+
+int mld_sim_step_batch(mld_problem_t *p, const double *v0, const int64_t *act_start, int step, int flags,
+                       double *x_k1_out, double *y_out, uint8_t *cons_out, double *cons_vio_out, int32_t *cons_row_out, int32_t *n_skipped_out)
+{
+    static const char who[] = "mld_sim_step_batch";
+    if (int rc = entry_guard(p, who, true, "no batch resident (mld_upload_batch)")) return rc;
+    mld_model *m = p->model;
+    const mld_dims &d = m->dims;
+    const int batch = p->batch, nx = d.nx, nv = p->nv, nw = d.nomega, ny = d.ny, nc = d.nc;
+    if (flags & ~(MLD_SIM_ADVANCE | MLD_SIM_ACTUAL | MLD_SIM_LOG)) { mld_set_error("%s: unknown flag bits 0x%x (MLD_SIM_ADVANCE | MLD_SIM_ACTUAL | MLD_SIM_LOG)", who, flags); return MLD_ERR_INVALID; }
+    const bool advance = flags & MLD_SIM_ADVANCE, actual = flags & MLD_SIM_ACTUAL, log = flags & MLD_SIM_LOG;
+    if (step < 0 || step == INT_MAX) { mld_set_error("%s: step = %d (must be >= 0)", who, step); return MLD_ERR_INVALID; }
+    if (m->tv_N > 0) { mld_set_error("%s: time-varying models (mld_model_create_tv) are not stepped on the device -- the step models would have to shift with the horizon (as mld_advance_batch)", who); return MLD_ERR_INVALID; }
+    if (!m->d_pack) { mld_set_error("%s: model without matrices", who); return MLD_ERR_INVALID; }
+    if (!v0 && !p->solved) { mld_set_error("%s: the resident batch has not been solved since its upload / selection (there is no plan to apply; pass v0)", who); return MLD_ERR_INVALID; }
+    if (!v0 && p->advanced) { mld_set_error("%s: the last solve's plan has already been applied -- the resident plan belongs to inputs that are gone (solve again, or pass v0)", who); return MLD_ERR_INVALID; }
+    if (act_start && !actual) { mld_set_error("%s: act_start given without MLD_SIM_ACTUAL", who); return MLD_ERR_INVALID; }
+    std::vector<long long> gmax;
+    if (actual) {
+        if (nw == 0) { mld_set_error("%s: MLD_SIM_ACTUAL, but the model has no disturbance (nomega = 0)", who); return MLD_ERR_INVALID; }
+        if (!p->pf_len) { mld_set_error("%s: MLD_SIM_ACTUAL, but no profile library is resident (mld_upload_profiles)", who); return MLD_ERR_INVALID; }
+        /* the window rule with ONE step: s >= 0 and s + (step + 1) * width_g <= lib_len */
+        if (act_start) { if (int rc = profile_check_starts(p, who, PF_ELEMENT, act_start, batch, 1, step, 1, gmax)) return rc; }
+        else {
+            if (p->pf_actual.batch != batch) { mld_set_error("%s: act_start == NULL, but no actual starts of this batch are resident (pass them once)", who); return MLD_ERR_INVALID; }
+            if (int rc = profile_check_resident(p, who, PF_ELEMENT, p->pf_actual.gmax, step, 1)) return rc;
+        }
+    }
+    mld_problem::SimLog &L = p->slog;
+    if (log && !L.cap) { mld_set_error("%s: MLD_SIM_LOG, but no log has been begun for this batch (mld_sim_log_begin)", who); return MLD_ERR_INVALID; }
+    if (log && L.count >= L.cap) { mld_set_error("%s: MLD_SIM_LOG, but the log is full (%d of %d records; mld_download_sim_log, then mld_sim_log_begin)", who, L.count, L.cap); return MLD_ERR_INVALID; }
+    if (!advance && !log && !x_k1_out && !y_out && !cons_out && !cons_vio_out && !cons_row_out && !n_skipped_out && !act_start) return MLD_OK;      /* nothing asked for */
+
+    SimStepArgs a{};
+    a.batch = batch; a.nx = nx; a.nv = nv; a.nmu = d.nmu; a.nw = nw; a.ny = ny; a.nc = nc; a.N = p->N;
+    const size_t stage = sizeof(double) * SS_WAVES * ((size_t)nx + nv + nw + ny);
+    a.lds = stage <= SS_LDS_MAX && !(p->opts.reserved & MLD_DBG_SIM_NO_LDS);
+    a.pack = m->d_pack; a.pack_len = m->pack_len;
+    {
+        const PackOff &o = m->pack_off;
+        a.oA = o.A; a.oB4 = o.B4; a.ob5 = o.b5; a.oC = o.C; a.oD4 = o.D4; a.od5 = o.d5; a.oE = o.E; a.oF4 = o.F4; a.of5 = o.f5; a.oG = o.G;
+        a.oBv = o.Bv; a.oDv = o.Dv; a.oFv = o.Fv;
+    }
+    a.model_idx = p->has_midx ? p->bat.model_idx.get() : nullptr;
+    a.x0 = p->bat.x0; a.omega = p->bat.omega;
+    const hipStream_t sq = p->stream;
+    DevBuf<double> d_v, d_xk1, d_y, d_vio; DevBuf<unsigned char> d_cons; DevBuf<int> d_row; DevBuf<long long> d_start;
+    if (v0) HIP_TRY(d_v.alloc((size_t)batch * std::max(1, nv)));
+    if (act_start) HIP_TRY(d_start.alloc((size_t)batch * p->pf_groups));
+    if (!a.lds && !p->bat.sim_tmp) HIP_TRY(p->bat.sim_tmp.alloc((size_t)p->in_cap * std::max(1, nw + ny)));      /* sized like the input buffers (any batch up to in_cap); free_batch releases it with them */
+    if (!a.lds) { a.w_tmp = p->bat.sim_tmp; a.y_tmp = p->bat.sim_tmp.get() + (size_t)batch * nw; }
+    if (v0) { a.v = d_v; a.v_stride = (size_t)nv; }
+    else {      /* the resident plans: rows < batch are the instances' (after the hand-off's device merge), hand-off items come after them */
+        a.v = p->bat.v; a.v_stride = (size_t)p->n;
+        a.status = p->bat.status; a.obj = p->bat.obj; a.lbnd = p->bat.lbnd; a.nodes = p->bat.nodes;
+    }
+    if (actual) { a.act_start = act_start ? d_start.get() : p->pf_actual.d.get(); a.chan = p->pf_chan; a.n_groups = p->pf_groups; a.step = step; a.lib = p->pf_lib; }
+    if (advance) { a.x0_new = p->bat.x0b; a.omega_new = p->bat.omegab; }
+    const size_t slot = log ? (size_t)L.count * batch : 0;
+    if (log) {
+        a.x_k1 = L.x_k1.get() + slot * nx; a.y = L.y.get() + slot * ny; a.vio = L.vio.get() + slot; a.cons = L.cons.get() + slot * nc; a.row = L.row.get() + slot;
+        a.rec_x = L.x.get() + slot * nx; a.rec_v = L.v.get() + slot * nv; a.rec_om = L.om.get() + slot * nw;
+        a.rec_obj = L.obj.get() + slot; a.rec_lb = L.lb.get() + slot; a.rec_status = L.status.get() + slot; a.rec_nodes = L.nodes.get() + slot;
+    } else {
+        if (x_k1_out && nx) { HIP_TRY(d_xk1.alloc((size_t)batch * nx)); a.x_k1 = d_xk1; }
+        if (y_out && ny) { HIP_TRY(d_y.alloc((size_t)batch * ny)); a.y = d_y; }
+        if (cons_out && nc) { HIP_TRY(d_cons.alloc((size_t)batch * nc)); a.cons = d_cons; }
+        if (cons_vio_out) { HIP_TRY(d_vio.alloc(batch)); a.vio = d_vio; }
+        if (cons_row_out) { HIP_TRY(d_row.alloc(batch)); a.row = d_row; }
+    }
+    const bool count_skipped = !v0 && (n_skipped_out != nullptr);
+    if (count_skipped) a.n_skipped = p->bat.skipped;
+    int skipped = 0;
+    /* the host waits where it has to: for the caller's arrays (theirs again when this returns), the skip count and the requested outputs; and after an
+     * advance on a stream of the problem's own, because the other entry points copy on the legacy stream, which does not order against that one */
+    const bool wait = v0 || act_start || count_skipped || x_k1_out || y_out || cons_out || cons_vio_out || cons_row_out || (advance && p->own_stream);
+    auto queue = [&]() -> int {
+        if (v0 && nv) HIP_TRY(hipMemcpyAsync(d_v, v0, sizeof(double) * (size_t)batch * nv, hipMemcpyHostToDevice, sq));
+        if (act_start) HIP_TRY(hipMemcpyAsync(d_start, act_start, sizeof(long long) * (size_t)batch * p->pf_groups, hipMemcpyHostToDevice, sq));
+        if (count_skipped) HIP_TRY(hipMemsetAsync(p->bat.skipped, 0, sizeof(int), sq));
+        const int grid = (int)std::min<long long>(((long long)batch + SS_WAVES - 1) / SS_WAVES, 8192);
+        hipLaunchKernelGGL(k_sim_step, dim3(grid), dim3(64 * SS_WAVES), a.lds ? stage : 0, sq, a);
+        HIP_TRY(hipGetLastError());
+        if (x_k1_out && nx) HIP_TRY(hipMemcpyAsync(x_k1_out, a.x_k1, sizeof(double) * (size_t)batch * nx, hipMemcpyDeviceToHost, sq));
+        if (y_out && ny) HIP_TRY(hipMemcpyAsync(y_out, a.y, sizeof(double) * (size_t)batch * ny, hipMemcpyDeviceToHost, sq));
+        if (cons_out && nc) HIP_TRY(hipMemcpyAsync(cons_out, a.cons, (size_t)batch * nc, hipMemcpyDeviceToHost, sq));
+        if (cons_vio_out) HIP_TRY(hipMemcpyAsync(cons_vio_out, a.vio, sizeof(double) * batch, hipMemcpyDeviceToHost, sq));
+        if (cons_row_out) HIP_TRY(hipMemcpyAsync(cons_row_out, a.row, sizeof(int) * batch, hipMemcpyDeviceToHost, sq));
+        if (count_skipped) HIP_TRY(hipMemcpyAsync(&skipped, p->bat.skipped, sizeof(int), hipMemcpyDeviceToHost, sq));
+        return MLD_OK;
+    };
+    if (int rc = queue_and_wait(sq, queue, wait)) return rc;
+    /* queued without an error: the handle moves on */
+    if (act_start) set_starts(p->pf_actual, std::move(d_start), batch, 1, gmax);
+    if (log) ++L.count;
+    if (advance) {
+        std::swap(p->bat.x0, p->bat.x0b); std::swap(p->bat.omega, p->bat.omegab);
+        if (v0) inputs_advanced_by_caller(p); else inputs_advanced_by_plan(p);
+    }
+    if (n_skipped_out) *n_skipped_out = skipped;
+    return MLD_OK;
+}
+
+int mld_download_sim_log(mld_problem_t *p, int first, int count, double *x, double *v, double *y, double *omega, double *x_k1, uint8_t *cons, double *cons_vio,
+                         int32_t *cons_row, double *obj, double *lower_bound, int32_t *status, int32_t *nodes)
+{
+    static const char who[] = "mld_download_sim_log";
+    if (int rc = entry_guard(p, who, true, "no batch resident (mld_upload_batch)")) return rc;
+    const mld_problem::SimLog &L = p->slog;
+    if (first < 0 || count < 0 || (long long)first + count > L.count) { mld_set_error("%s: records [%d, %lld) asked for, %d logged", who, first, (long long)first + count, L.count); return MLD_ERR_INVALID; }
+    if (count == 0) return MLD_OK;
+    const mld_dims &d = p->model->dims;
+    const size_t off = (size_t)first * p->batch, len = (size_t)count * p->batch;
+    const hipStream_t sq = p->stream;
+    auto queue = [&]() -> int {
+        auto get = [&](void *dst, const void *src, size_t width, size_t elem) -> hipError_t {
+            if (!dst || !width) return hipSuccess;
+            return hipMemcpyAsync(dst, (const char *)src + off * width * elem, len * width * elem, hipMemcpyDeviceToHost, sq);
+        };
+        HIP_TRY(get(x, L.x.get(), d.nx, sizeof(double))); HIP_TRY(get(v, L.v.get(), p->nv, sizeof(double))); HIP_TRY(get(y, L.y.get(), d.ny, sizeof(double)));
+        HIP_TRY(get(omega, L.om.get(), d.nomega, sizeof(double))); HIP_TRY(get(x_k1, L.x_k1.get(), d.nx, sizeof(double))); HIP_TRY(get(cons, L.cons.get(), d.nc, 1));
+        HIP_TRY(get(cons_vio, L.vio.get(), 1, sizeof(double))); HIP_TRY(get(cons_row, L.row.get(), 1, sizeof(int)));
+        HIP_TRY(get(obj, L.obj.get(), 1, sizeof(double))); HIP_TRY(get(lower_bound, L.lb.get(), 1, sizeof(double)));
+        HIP_TRY(get(status, L.status.get(), 1, sizeof(int))); HIP_TRY(get(nodes, L.nodes.get(), 1, sizeof(int)));
+        return MLD_OK;
+    };
+    return queue_and_wait(sq, queue);
+}
+
+} // extern "C"

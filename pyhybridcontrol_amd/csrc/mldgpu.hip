@@ -13,7 +13,7 @@
 #include "common.h"
 #include "condense.inc"
 #include "problem.inc"
-#include "profiles.inc"      // k_profile_windows and the window rule (mld_upload_profiles and its consumers, api_problem.inc)
+#include "profiles.inc"      // k_profile_windows and the window rule (mld_upload_profiles and its consumers, api_resident.inc)
 
 // ---- errors ------------------------------------------------------------------------------------
 static thread_local char g_err[1024] = "";
@@ -109,15 +109,18 @@ static int model_create_impl(mld_model_t **out, const mld_dims *dims, int n_sets
         if (e != hipSuccess) { mld_set_error("mld_model_create: %s", hipGetErrorString(e)); mld_model_destroy(m); return MLD_ERR_HIP; }
     }
     {   // every per-step matrix the block kernel needs, packed per model in its LDS order (one coalesced sweep instead of
-        // thirteen dependent small copies); the input matrices are stacked horizontally as in mld_evolution_matrices.py:291,355,411
+        // thirteen dependent small copies); the input matrices are stacked horizontally as in mld_evolution_matrices.py:291,355,411.
+        // Order: A, B4, b5, C, D4, d5, E, F4, f5, G, [B1 B2 B3 0], [D1 D2 D3 0], [F1 F2 F3 Psi]; pack_off keeps where each starts
         const int nv = m->nv;
         const int plain[10] = {MT_A, MT_B4, MT_b5, MT_C, MT_D4, MT_d5, MT_E, MT_F4, MT_f5, MT_G};
         const int rws[3] = {d.nx, d.ny, d.nc};
         const int ids[3][4] = {{MT_B1, MT_B2, MT_B3, -1}, {MT_D1, MT_D2, MT_D3, -1}, {MT_F1, MT_F2, MT_F3, MT_Psi}};
         const int cw[4] = {d.nu, d.ndelta, d.nz, d.nmu};
         size_t len = 0;
-        for (int k = 0; k < 10; ++k) len += m->mat_size[plain[k]];
-        for (int f = 0; f < 3; ++f) len += (size_t)rws[f] * nv;
+        size_t *const off[13] = {&m->pack_off.A, &m->pack_off.B4, &m->pack_off.b5, &m->pack_off.C, &m->pack_off.D4, &m->pack_off.d5, &m->pack_off.E,
+                                 &m->pack_off.F4, &m->pack_off.f5, &m->pack_off.G, &m->pack_off.Bv, &m->pack_off.Dv, &m->pack_off.Fv};      /* (the order of the pack) */
+        for (int k = 0; k < 10; ++k) { *off[k] = len; len += m->mat_size[plain[k]]; }
+        for (int f = 0; f < 3; ++f) { *off[10 + f] = len; len += (size_t)rws[f] * nv; }
         m->pack_len = len;
         if (len) {
             std::vector<double> pack(len * n_models, 0.0);
@@ -198,4 +201,21 @@ int mld_condense_f32(mld_model_t *m, int N_tilde, int flags, float *Phi_x, float
 
 } // extern "C"
 
-#include "api_problem.inc"
+// ---- the problem handle and its entry points, by concern -------------------------------------------------------------------------
+#include <rccl/rccl.h>
+
+#include <limits>
+#include <memory>
+
+#include "mfma.inc"
+#include "inst_cost.inc"
+#include "lp_lds.inc"
+
+#include "tighten.inc"          // host big-M tightening (namespace tighten)
+#include "kernels.inc"          // small kernels: cost assembly, receding horizon, MIP start, fills, statistics, result packing
+#include "handle.inc"           // BatchBufs, mld_problem, build_shape, ensure_batch; the host helpers the entry points are written from
+#include "merge.inc"            // in-kernel hand-off: reset of the queue and merge of its items, mld_debug_merge
+#include "api_create.inc"       // mld_problem_create / destroy / set_cost / get_opts / set_opts, mld_cost_assemble, mld_opts_*
+#include "api_solve.inc"        // upload, constraint blocks, launch / finish, downloads, MIP start, cutoffs, hand-off settings, staged inputs, debug hooks
+#include "api_resident.inc"     // between solves: profiles, per-instance cost, trajectories, solution quality, advance, plant step and log
+#include "api_gather.inc"       // RCCL gather

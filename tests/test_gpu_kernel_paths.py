@@ -1,8 +1,8 @@
 """Parity of every dispatch branch of the kernels that build the solver's input -- condensing (K1/K2), constraint right-hand
 sides (K3) and cost pull-back (K4) -- against plain fp64 numpy restatements of the same operation: condense_np.condense /
 condense_tv, h = H_x x + H_w w + H_5 (row-min over scenarios) and _paths.ref_cost.  Each case names the kernel or template
-instantiation it targets and the condition that sends it there (csrc/condense.inc condense_model_device, csrc/api_problem.inc
-mld_rhs_batch / set_cost_impl).  Random models come from _paths.random_mld (fixed seeds, spectral radius of A in [0.9, 1.05])."""
+instantiation it targets and the condition that sends it there (csrc/condense.inc condense_model_device, csrc/api_solve.inc
+mld_rhs_batch / csrc/api_create.inc set_cost_impl).  Random models come from _paths.random_mld (fixed seeds, spectral radius of A in [0.9, 1.05])."""
 import numpy as np
 import pytest
 
