@@ -466,7 +466,7 @@ int mld_download_constraint_blocks(mld_problem_t *, int32_t *n_cols_out, double 
  * on the ORIGINAL model's matrices, in fp64 also on an MLD_F32 handle (k_sim_step).  x_k1 is summed exactly as mld_advance_batch sums it, so an advance
  * through this entry leaves the same bits.  Under a realised disturbance `cons` says, per row, whether the PLANNED auxiliaries are still consistent with the
  * model: the test of the equivalence condition mld_advance_batch2 describes above.  Re-deriving delta / z from (x, u, omega) (lsim_k's _compute_aux) is not
- * done here.  The stage cost is the agent's business in the reference (sim_k.z * prices_k, examples/.../modelling/micro_grid_agents.py:753): it stays a host
+ * done here but by mld_sim_step_resolve below.  The stage cost is the agent's business in the reference (sim_k.z * prices_k, examples/.../modelling/micro_grid_agents.py:753): it stays a host
  * product on the downloaded log.
  *
  * v0 == NULL  the step-0 slice of the resident plan.  Needs a finished solve of the current inputs that has not been advanced yet (refused exactly where
@@ -508,6 +508,42 @@ int mld_sim_step_batch(mld_problem_t *, const double *v0, const int64_t *act_sta
 int mld_download_sim_log(mld_problem_t *, int first, int count,
                          double *x, double *v, double *y, double *omega, double *x_k1, uint8_t *cons, double *cons_vio, int32_t *cons_row,
                          double *obj, double *lower_bound, int32_t *status, int32_t *nodes);
+
+/* ---- the plant step with the auxiliaries re-derived ------------------------------------------------------------------------------------------------
+ * What the reference's closed loop does: ControllerBase.sim_step_k (controllers/controller_base.py:229-253) calls lsim_k(x_k=, u_k=, omega_k=) with u ONLY;
+ * MldModel.lsim_k (models/mld_model.py:683-686) then calls _compute_aux (:701-766), a small feasibility MIP for delta, z, mu under the REALISED omega_k, and
+ * only then forms x_k1, y and cons.  mld_sim_step_resolve is that step for every instance of the resident batch without host traffic: under a realised
+ * disturbance the auxiliaries follow the model (for the microgrid models z = delta y is the grid power that occurred, not the forecast's).
+ *
+ * aux         the resolver's handle, passed with every call (no pointer is kept): a problem over the FOLDED models -- u moved into the disturbance channel,
+ *             omega' = [omega; u], so nu = 0 and nomega' = nomega + nu; every other dimension and n_models as this problem's -- with N_tilde = 1 and the cost
+ *             sum(mu) (aux_resolve.BatchAuxResolver builds it).  Of the feasible points the reference may return, the one with the least total slack is
+ *             taken.  aux == NULL is required iff ndelta + nz + nmu == 0; the step then equals mld_sim_step_batch with v0 = u.
+ * u0 == NULL  the first nu entries of the resident plan's row; refused where mld_sim_step_batch(v0 = NULL) is refused.  An instance is ATTEMPTED iff its plan
+ *             is usable.  u0 != NULL: (batch, nu), the caller's inputs, no plan needed, every instance attempted; tested for finiteness on the host.
+ * omega_k, act_start, step, flags: exactly as mld_sim_step_batch (the resident actual starts are shared with it).
+ * One call:   k_aux_inputs writes the resolver's inputs on the device, x0' = x and omega' = [omega_k; u] (u = 0 for an instance that is not attempted); the
+ *             resolver's resident batch (size, model_idx, RHS groups) is laid out by the call whenever it is not this batch's -- another size, or either handle
+ *             uploaded since --, which costs one device-to-host copy of model_idx and the upload path; the steps in between move nothing over PCIe but what
+ *             the caller passes or asks for (the solve path's own bookkeeping aside).  The resolver solves (its inputs count as replaced, as after
+ *             mld_select_inputs).  k_aux_merge builds v0 = [u; delta; z; mu] per instance and its usable flag: attempted AND the resolver ended OPTIMAL or at
+ *             NODE_LIMIT with a finite objective (a feasible point, all the reference asks for).  k_sim_step steps on v0 with that flag as mask: an unusable
+ *             instance is treated as an instance without a usable plan is by mld_sim_step_batch -- not advanced, counted in n_skipped_out, NaN / 0 / -1 in
+ *             its outputs and NaN in the record's v (the reference returns NaN auxiliaries and hence a NaN x_k1 there, :757-763).  The host waits between
+ *             the three phases; the call is host-synchronous.
+ * Outputs     as mld_sim_step_batch, plus v0_out (batch, nv) the resolved slices (NaN rows where unusable) and aux_status_out (batch) the resolver's status
+ *             per instance, -1 where it was not attempted (0 with aux == NULL).
+ * MLD_SIM_ADVANCE  as mld_sim_step_batch: with u0 == NULL the handle ends `advanced`, with the caller's u0 as after mld_select_inputs.
+ * MLD_SIM_LOG  the usual record, its v the resolved slice, obj / lower_bound / status / nodes the plan's (NaN / NaN / -1 / 0 with u0 given); and aux_status
+ *             in an int array (capacity, batch) that the first resolving step that logs allocates, filled with -2 = "not resolved"; mld_sim_log_begin
+ *             discards it.  mld_download_sim_log_aux copies records [first, first + count): -2 for records mld_sim_step_batch wrote.
+ * MLD_ERR_INVALID before anything is queued, nothing changed on either handle: everything mld_sim_step_batch refuses; aux == the problem itself; aux with a
+ * launched solve, with N_tilde != 1, time-varying, with the in-kernel hand-off on, or whose dimensions are not the fold of this problem's; aux NULL / not
+ * NULL against the rule above; a u0 that is not finite.  An error in a later phase leaves this problem's inputs, log count and actual starts as they were. */
+int mld_sim_step_resolve(mld_problem_t *, mld_problem_t *aux, const double *u0, const int64_t *act_start, int step, int flags,
+                         double *x_k1_out, double *y_out, uint8_t *cons_out, double *cons_vio_out, int32_t *cons_row_out,
+                         double *v0_out, int32_t *aux_status_out, int32_t *n_skipped_out);
+int mld_download_sim_log_aux(mld_problem_t *, int first, int count, int32_t *aux_status);
 
 /* Per-instance telemetry of the last solve: time spent inside the solve kernel (device wall clock, ns) and
  * the number of dictionary rows the rank-1 updates touched (x *row_bytes x 2 = bytes streamed by pivots). */

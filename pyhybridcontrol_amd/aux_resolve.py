@@ -110,3 +110,50 @@ class AuxResolver(object):
             self._problem.close(); self._problem = None
         if self._model is not None:
             self._model.close(); self._model = None
+
+
+def fold_models(mats_list, dims):
+    """the fold of every model of a list with u as the only known: ([mats'], dims'), dims' shared (nu = 0, nomega' = nomega + nu)"""
+    folded = [fold_known(m, dims, _AUX) for m in mats_list]
+    return [f[0] for f in folded], folded[0][1]
+
+
+class BatchAuxResolver(object):
+    """One GPU problem for a LIST of same-shaped models (n_models = len(mats_list)) with delta, z and mu all unknown and u the only known -- what
+    ControllerBase.sim_step_k passes to lsim_k.  It is the resolver handle of ``GpuProblem.sim_step(resolve=...)`` (mld_sim_step_resolve), which feeds it
+    on the device; ``resolve`` is the host-fed route over the same handle.  Without auxiliaries (nv2 == 0) no handle is built: ``problem`` is None."""
+
+    def __init__(self, mats_list, dims, **solver_opts):
+        if isinstance(mats_list, dict):
+            mats_list = [mats_list]
+        self.dims = dict(dims)
+        self.mats2, self.dims2 = fold_models(mats_list, dims)
+        self.nv2 = self.dims2["ndelta"] + self.dims2["nz"] + self.dims2["nmu"]
+        self._model = self.problem = None
+        if self.nv2:
+            atoms = {"q_mu": np.ones((self.dims2["nmu"], 1))} if self.dims2["nmu"] else {}
+            opts = dict(gap_abs=1e-9, gap_rel=0.0, max_nodes=20000)
+            opts.update(solver_opts)
+            self._model = gpu.GpuModel(self.mats2, self.dims2)
+            self.problem = gpu.GpuProblem(self._model, 0, 1, host.cost_from_atoms(atoms, self.dims2, 0, 1), **opts)
+
+    def resolve(self, x, u, omega, model_idx=None):
+        """batched and fed from the host: x (B, nx), u (B, nu), omega (B, nomega), model_idx (B) -> dict(delta, z, mu, v = [delta | z | mu], status).
+        Rows without a feasible point come back as NaN, as the reference does (:757-763)."""
+        d = self.dims
+        x = np.ascontiguousarray(np.asarray(x, np.float64).reshape(-1, d["nx"]))
+        B = x.shape[0]
+        w2 = np.ascontiguousarray(np.hstack([np.asarray(omega, np.float64).reshape(B, d["nomega"]), np.asarray(u, np.float64).reshape(B, d["nu"])]))
+        v, status = np.zeros((B, 0)), np.zeros(B, np.int32)
+        if self.nv2:
+            r = self.problem.solve(x, w2, model_idx)
+            v, status = r["v"], r["status"]
+            v[~(np.isin(status, (0, 2)) & np.isfinite(r["obj"]))] = np.nan
+        o1, o2 = d["ndelta"], d["ndelta"] + d["nz"]
+        return dict(delta=v[:, :o1], z=v[:, o1:o2], mu=v[:, o2:], v=v, status=status)
+
+    def close(self):
+        if self.problem is not None:
+            self.problem.close(); self.problem = None
+        if self._model is not None:
+            self._model.close(); self._model = None

@@ -1,5 +1,5 @@
 // Services on the resident batch between solves: disturbance profiles, per-instance cost, predicted trajectories, solution quality, receding
-// horizon, plant step and simulation log.
+// horizon, plant step (with the planned auxiliaries or with re-derived ones) and simulation log.
 extern "C" {
 
 /* ---- resident disturbance profiles ----------------------------------------------------------------------------------------------------------------
@@ -459,23 +459,20 @@ int mld_sim_log_count(mld_problem_t *p, int32_t *n_logged, int32_t *capacity)
     return MLD_OK;
 }
 
-int mld_sim_step_batch(mld_problem_t *p, const double *v0, const int64_t *act_start, int step, int flags,
-                       double *x_k1_out, double *y_out, uint8_t *cons_out, double *cons_vio_out, int32_t *cons_row_out, int32_t *n_skipped_out)
+/* The host-side tests the two step entry points share, before anything is queued.  own: the caller brings the inputs (`arg`: v0 / u0), so no plan is needed.
+ * gmax: per group the largest start of act_start, for set_starts once the step has been taken. */
+static int sim_step_check(mld_problem_t *p, const char *who, bool own, const char *arg, const int64_t *act_start, int step, int flags, std::vector<long long> &gmax)
 {
-    static const char who[] = "mld_sim_step_batch";
-    if (int rc = entry_guard(p, who, true, "no batch resident (mld_upload_batch)")) return rc;
     mld_model *m = p->model;
-    const mld_dims &d = m->dims;
-    const int batch = p->batch, nx = d.nx, nv = p->nv, nw = d.nomega, ny = d.ny, nc = d.nc;
+    const int batch = p->batch, nw = m->dims.nomega;
     if (flags & ~(MLD_SIM_ADVANCE | MLD_SIM_ACTUAL | MLD_SIM_LOG)) { mld_set_error("%s: unknown flag bits 0x%x (MLD_SIM_ADVANCE | MLD_SIM_ACTUAL | MLD_SIM_LOG)", who, flags); return MLD_ERR_INVALID; }
-    const bool advance = flags & MLD_SIM_ADVANCE, actual = flags & MLD_SIM_ACTUAL, log = flags & MLD_SIM_LOG;
+    const bool actual = flags & MLD_SIM_ACTUAL, log = flags & MLD_SIM_LOG;
     if (step < 0 || step == INT_MAX) { mld_set_error("%s: step = %d (must be >= 0)", who, step); return MLD_ERR_INVALID; }
     if (m->tv_N > 0) { mld_set_error("%s: time-varying models (mld_model_create_tv) are not stepped on the device -- the step models would have to shift with the horizon (as mld_advance_batch)", who); return MLD_ERR_INVALID; }
     if (!m->d_pack) { mld_set_error("%s: model without matrices", who); return MLD_ERR_INVALID; }
-    if (!v0 && !p->solved) { mld_set_error("%s: the resident batch has not been solved since its upload / selection (there is no plan to apply; pass v0)", who); return MLD_ERR_INVALID; }
-    if (!v0 && p->advanced) { mld_set_error("%s: the last solve's plan has already been applied -- the resident plan belongs to inputs that are gone (solve again, or pass v0)", who); return MLD_ERR_INVALID; }
+    if (!own && !p->solved) { mld_set_error("%s: the resident batch has not been solved since its upload / selection (there is no plan to apply; pass %s)", who, arg); return MLD_ERR_INVALID; }
+    if (!own && p->advanced) { mld_set_error("%s: the last solve's plan has already been applied -- the resident plan belongs to inputs that are gone (solve again, or pass %s)", who, arg); return MLD_ERR_INVALID; }
     if (act_start && !actual) { mld_set_error("%s: act_start given without MLD_SIM_ACTUAL", who); return MLD_ERR_INVALID; }
-    std::vector<long long> gmax;
     if (actual) {
         if (nw == 0) { mld_set_error("%s: MLD_SIM_ACTUAL, but the model has no disturbance (nomega = 0)", who); return MLD_ERR_INVALID; }
         if (!p->pf_len) { mld_set_error("%s: MLD_SIM_ACTUAL, but no profile library is resident (mld_upload_profiles)", who); return MLD_ERR_INVALID; }
@@ -486,11 +483,33 @@ int mld_sim_step_batch(mld_problem_t *p, const double *v0, const int64_t *act_st
             if (int rc = profile_check_resident(p, who, PF_ELEMENT, p->pf_actual.gmax, step, 1)) return rc;
         }
     }
-    mld_problem::SimLog &L = p->slog;
+    const mld_problem::SimLog &L = p->slog;
     if (log && !L.cap) { mld_set_error("%s: MLD_SIM_LOG, but no log has been begun for this batch (mld_sim_log_begin)", who); return MLD_ERR_INVALID; }
     if (log && L.count >= L.cap) { mld_set_error("%s: MLD_SIM_LOG, but the log is full (%d of %d records; mld_download_sim_log, then mld_sim_log_begin)", who, L.count, L.cap); return MLD_ERR_INVALID; }
-    if (!advance && !log && !x_k1_out && !y_out && !cons_out && !cons_vio_out && !cons_row_out && !n_skipped_out && !act_start) return MLD_OK;      /* nothing asked for */
+    return MLD_OK;
+}
 
+/* Where a step's slices come from.  Neither pointer: the resident plan.  v0: the caller's (batch, nv) on the host.  d_v0: slices the call has built on the
+ * device (mld_sim_step_resolve) with their usable flag d_mask and resolver statuses d_auxst; by_plan says that their u was the resident plan's, so the record
+ * carries the plan's obj / lower_bound / status / nodes and an advance leaves the handle `advanced`; d_start: act_start is on the device already. */
+struct SimStepSrc {
+    const double *v0 = nullptr, *d_v0 = nullptr; const unsigned char *d_mask = nullptr; const int *d_auxst = nullptr; bool by_plan = false;
+    const AuxStepArgs *merge = nullptr;      /* k_aux_merge fills d_v0, d_mask and d_auxst: queued in front of the step */
+    DevBuf<long long> *d_start = nullptr;
+    double *v0_out = nullptr; int32_t *aux_status_out = nullptr;
+};
+
+/* the step itself, after sim_step_check: k_sim_step on the slices of `src`, the outputs, and -- queued without an error -- the handle moved on */
+static int sim_step_run(mld_problem_t *p, const SimStepSrc &src, const int64_t *act_start, const std::vector<long long> &gmax, int step, int flags,
+                        double *x_k1_out, double *y_out, uint8_t *cons_out, double *cons_vio_out, int32_t *cons_row_out, int32_t *n_skipped_out)
+{
+    mld_model *m = p->model;
+    const mld_dims &d = m->dims;
+    const int batch = p->batch, nx = d.nx, nv = p->nv, nw = d.nomega, ny = d.ny, nc = d.nc;
+    const bool advance = flags & MLD_SIM_ADVANCE, actual = flags & MLD_SIM_ACTUAL, log = flags & MLD_SIM_LOG;
+    const double *v0 = src.v0;
+    const bool resolved = src.d_v0 != nullptr, plan = !v0 && !resolved;
+    mld_problem::SimLog &L = p->slog;
     SimStepArgs a{};
     a.batch = batch; a.nx = nx; a.nv = nv; a.nmu = d.nmu; a.nw = nw; a.ny = ny; a.nc = nc; a.N = p->N;
     const size_t stage = sizeof(double) * SS_WAVES * ((size_t)nx + nv + nw + ny);
@@ -504,16 +523,17 @@ int mld_sim_step_batch(mld_problem_t *p, const double *v0, const int64_t *act_st
     a.model_idx = p->has_midx ? p->bat.model_idx.get() : nullptr;
     a.x0 = p->bat.x0; a.omega = p->bat.omega;
     const hipStream_t sq = p->stream;
-    DevBuf<double> d_v, d_xk1, d_y, d_vio; DevBuf<unsigned char> d_cons; DevBuf<int> d_row; DevBuf<long long> d_start;
+    DevBuf<double> d_v, d_xk1, d_y, d_vio; DevBuf<unsigned char> d_cons; DevBuf<int> d_row; DevBuf<long long> d_own_start;
+    const bool up_start = act_start && !src.d_start;      /* the starts still have to go to the device */
+    DevBuf<long long> &d_start = src.d_start ? *src.d_start : d_own_start;
     if (v0) HIP_TRY(d_v.alloc((size_t)batch * std::max(1, nv)));
-    if (act_start) HIP_TRY(d_start.alloc((size_t)batch * p->pf_groups));
+    if (up_start) HIP_TRY(d_start.alloc((size_t)batch * p->pf_groups));
     if (!a.lds && !p->bat.sim_tmp) HIP_TRY(p->bat.sim_tmp.alloc((size_t)p->in_cap * std::max(1, nw + ny)));      /* sized like the input buffers (any batch up to in_cap); free_batch releases it with them */
     if (!a.lds) { a.w_tmp = p->bat.sim_tmp; a.y_tmp = p->bat.sim_tmp.get() + (size_t)batch * nw; }
     if (v0) { a.v = d_v; a.v_stride = (size_t)nv; }
-    else {      /* the resident plans: rows < batch are the instances' (after the hand-off's device merge), hand-off items come after them */
-        a.v = p->bat.v; a.v_stride = (size_t)p->n;
-        a.status = p->bat.status; a.obj = p->bat.obj; a.lbnd = p->bat.lbnd; a.nodes = p->bat.nodes;
-    }
+    else if (resolved) { a.v = src.d_v0; a.v_stride = (size_t)nv; a.mask = src.d_mask; }
+    else { a.v = p->bat.v; a.v_stride = (size_t)p->n; }      /* the resident plans: rows < batch are the instances' (after the hand-off's device merge), hand-off items come after them */
+    if (plan || (resolved && src.by_plan)) { a.status = p->bat.status; a.obj = p->bat.obj; a.lbnd = p->bat.lbnd; a.nodes = p->bat.nodes; }
     if (actual) { a.act_start = act_start ? d_start.get() : p->pf_actual.d.get(); a.chan = p->pf_chan; a.n_groups = p->pf_groups; a.step = step; a.lib = p->pf_lib; }
     if (advance) { a.x0_new = p->bat.x0b; a.omega_new = p->bat.omegab; }
     const size_t slot = log ? (size_t)L.count * batch : 0;
@@ -532,20 +552,28 @@ int mld_sim_step_batch(mld_problem_t *p, const double *v0, const int64_t *act_st
     if (count_skipped) a.n_skipped = p->bat.skipped;
     int skipped = 0;
     /* the host waits where it has to: for the caller's arrays (theirs again when this returns), the skip count and the requested outputs; and after an
-     * advance on a stream of the problem's own, because the other entry points copy on the legacy stream, which does not order against that one */
-    const bool wait = v0 || act_start || count_skipped || x_k1_out || y_out || cons_out || cons_vio_out || cons_row_out || (advance && p->own_stream);
+     * advance on a stream of the problem's own, because the other entry points copy on the legacy stream, which does not order against that one.  A
+     * resolving step is host-synchronous throughout: its temporaries go when it returns */
+    const bool wait = v0 || resolved || up_start || count_skipped || x_k1_out || y_out || cons_out || cons_vio_out || cons_row_out || (advance && p->own_stream);
     auto queue = [&]() -> int {
         if (v0 && nv) HIP_TRY(hipMemcpyAsync(d_v, v0, sizeof(double) * (size_t)batch * nv, hipMemcpyHostToDevice, sq));
-        if (act_start) HIP_TRY(hipMemcpyAsync(d_start, act_start, sizeof(long long) * (size_t)batch * p->pf_groups, hipMemcpyHostToDevice, sq));
+        if (up_start) HIP_TRY(hipMemcpyAsync(d_start, act_start, sizeof(long long) * (size_t)batch * p->pf_groups, hipMemcpyHostToDevice, sq));
         if (count_skipped) HIP_TRY(hipMemsetAsync(p->bat.skipped, 0, sizeof(int), sq));
+        if (src.merge) {
+            hipLaunchKernelGGL(k_aux_merge, dim3(profile_grid((long long)batch * std::max(1, nv))), dim3(256), 0, sq, *src.merge);
+            HIP_TRY(hipGetLastError());
+        }
         const int grid = (int)std::min<long long>(((long long)batch + SS_WAVES - 1) / SS_WAVES, 8192);
         hipLaunchKernelGGL(k_sim_step, dim3(grid), dim3(64 * SS_WAVES), a.lds ? stage : 0, sq, a);
         HIP_TRY(hipGetLastError());
+        if (resolved && log) HIP_TRY(hipMemcpyAsync(L.aux.get() + slot, src.d_auxst, sizeof(int) * batch, hipMemcpyDeviceToDevice, sq));
         if (x_k1_out && nx) HIP_TRY(hipMemcpyAsync(x_k1_out, a.x_k1, sizeof(double) * (size_t)batch * nx, hipMemcpyDeviceToHost, sq));
         if (y_out && ny) HIP_TRY(hipMemcpyAsync(y_out, a.y, sizeof(double) * (size_t)batch * ny, hipMemcpyDeviceToHost, sq));
         if (cons_out && nc) HIP_TRY(hipMemcpyAsync(cons_out, a.cons, (size_t)batch * nc, hipMemcpyDeviceToHost, sq));
         if (cons_vio_out) HIP_TRY(hipMemcpyAsync(cons_vio_out, a.vio, sizeof(double) * batch, hipMemcpyDeviceToHost, sq));
         if (cons_row_out) HIP_TRY(hipMemcpyAsync(cons_row_out, a.row, sizeof(int) * batch, hipMemcpyDeviceToHost, sq));
+        if (src.v0_out && nv) HIP_TRY(hipMemcpyAsync(src.v0_out, src.d_v0, sizeof(double) * (size_t)batch * nv, hipMemcpyDeviceToHost, sq));
+        if (src.aux_status_out) HIP_TRY(hipMemcpyAsync(src.aux_status_out, src.d_auxst, sizeof(int) * batch, hipMemcpyDeviceToHost, sq));
         if (count_skipped) HIP_TRY(hipMemcpyAsync(&skipped, p->bat.skipped, sizeof(int), hipMemcpyDeviceToHost, sq));
         return MLD_OK;
     };
@@ -555,10 +583,131 @@ int mld_sim_step_batch(mld_problem_t *p, const double *v0, const int64_t *act_st
     if (log) ++L.count;
     if (advance) {
         std::swap(p->bat.x0, p->bat.x0b); std::swap(p->bat.omega, p->bat.omegab);
-        if (v0) inputs_advanced_by_caller(p); else inputs_advanced_by_plan(p);
+        if (plan || src.by_plan) inputs_advanced_by_plan(p); else inputs_advanced_by_caller(p);
     }
     if (n_skipped_out) *n_skipped_out = skipped;
     return MLD_OK;
+}
+
+int mld_sim_step_batch(mld_problem_t *p, const double *v0, const int64_t *act_start, int step, int flags,
+                       double *x_k1_out, double *y_out, uint8_t *cons_out, double *cons_vio_out, int32_t *cons_row_out, int32_t *n_skipped_out)
+{
+    static const char who[] = "mld_sim_step_batch";
+    if (int rc = entry_guard(p, who, true, "no batch resident (mld_upload_batch)")) return rc;
+    std::vector<long long> gmax;
+    if (int rc = sim_step_check(p, who, v0 != nullptr, "v0", act_start, step, flags, gmax)) return rc;
+    if (!(flags & (MLD_SIM_ADVANCE | MLD_SIM_LOG)) && !x_k1_out && !y_out && !cons_out && !cons_vio_out && !cons_row_out && !n_skipped_out && !act_start) return MLD_OK;      /* nothing asked for */
+    SimStepSrc src; src.v0 = v0;
+    return sim_step_run(p, src, act_start, gmax, step, flags, x_k1_out, y_out, cons_out, cons_vio_out, cons_row_out, n_skipped_out);
+}
+
+/* ---- the plant step with the auxiliaries re-derived -------------------------------------------------------------------------------------------------
+ * What the reference's closed loop really does: sim_step_k calls lsim_k(x_k=, u_k=, omega_k=) with u only, and lsim_k solves _compute_aux for delta, z, mu
+ * under the REALISED omega_k before it forms x_k1, y and cons (controllers/controller_base.py:229-253, models/mld_model.py:683-686, 701-766).  `aux` is the
+ * resolver's handle (aux_resolve.BatchAuxResolver: the folded models, N_tilde = 1, min sum(mu)); the call keeps no pointer to it.  Three phases, the host
+ * waiting between them (the two handles may run on streams of their own): k_aux_inputs writes the resolver's inputs; the resolver's launch / finish solves
+ * them; k_aux_merge builds v0 = [u; delta; z; mu] and k_sim_step steps on it.  Kernels: aux_step.inc.  p's inputs, log count and actual starts change only
+ * when the last phase has been queued without an error. */
+int mld_sim_step_resolve(mld_problem_t *p, mld_problem_t *aux, const double *u0, const int64_t *act_start, int step, int flags,
+                         double *x_k1_out, double *y_out, uint8_t *cons_out, double *cons_vio_out, int32_t *cons_row_out,
+                         double *v0_out, int32_t *aux_status_out, int32_t *n_skipped_out)
+{
+    static const char who[] = "mld_sim_step_resolve";
+    if (int rc = entry_guard(p, who, true, "no batch resident (mld_upload_batch)")) return rc;
+    std::vector<long long> gmax;
+    if (int rc = sim_step_check(p, who, u0 != nullptr, "u0", act_start, step, flags, gmax)) return rc;
+    const mld_dims &d = p->model->dims;
+    const int batch = p->batch, nx = d.nx, nu = d.nu, nw = d.nomega, nv = p->nv, nv2 = d.ndelta + d.nz + d.nmu;
+    const bool actual = flags & MLD_SIM_ACTUAL, log = flags & MLD_SIM_LOG;
+    if (!nv2 && aux) { mld_set_error("%s: the model has no auxiliaries (ndelta + nz + nmu = 0), so there is nothing to resolve: aux must be NULL", who); return MLD_ERR_INVALID; }
+    if (nv2 && !aux) { mld_set_error("%s: aux == NULL, but the model has %d auxiliaries to resolve (ndelta + nz + nmu)", who, nv2); return MLD_ERR_INVALID; }
+    if (aux) {
+        if (aux == p) { mld_set_error("%s: aux is the stepped problem itself (the resolver is a handle of its own: the folded models at N_tilde = 1)", who); return MLD_ERR_INVALID; }
+        if (aux->flight != Flight::idle) { mld_set_error("%s: aux has a launched solve that has not been finished (mld_solve_finish)", who); return MLD_ERR_INVALID; }
+        if (aux->N != 1) { mld_set_error("%s: aux has N_tilde = %d (the auxiliary problem is the horizon-1 instance: N_tilde = 1)", who, aux->N); return MLD_ERR_INVALID; }
+        if (aux->model->tv_N > 0) { mld_set_error("%s: aux is time-varying (mld_model_create_tv)", who); return MLD_ERR_INVALID; }
+        if (aux->ho_enable) { mld_set_error("%s: aux has the in-kernel hand-off on (mld_set_handoff): its result rows would come after a merge this call does not run", who); return MLD_ERR_INVALID; }
+        const mld_dims &e = aux->model->dims;
+        if (e.nx != nx || e.nc != d.nc || e.ndelta != d.ndelta || e.nz != d.nz || e.nmu != d.nmu || aux->n_models != p->n_models || e.nu != 0 || e.nomega != nw + nu) {
+            mld_set_error("%s: aux is not the fold of this problem's models: nx %d/%d nc %d/%d ndelta %d/%d nz %d/%d nmu %d/%d n_models %d/%d (aux/problem), nu %d (0), nomega %d (nomega + nu = %d)",
+                          who, e.nx, nx, e.nc, d.nc, e.ndelta, d.ndelta, e.nz, d.nz, e.nmu, d.nmu, aux->n_models, p->n_models, e.nu, e.nomega, nw + nu);
+            return MLD_ERR_INVALID;
+        }
+    }
+    if (u0) for (size_t k = 0; k < (size_t)batch * nu; ++k) if (!std::isfinite(u0[k])) {
+        mld_set_error("%s: u0 of instance %zu, input %zu is not finite (%g)", who, k / nu, k % nu, u0[k]); return MLD_ERR_INVALID;
+    }
+    if (!(flags & (MLD_SIM_ADVANCE | MLD_SIM_LOG)) && !x_k1_out && !y_out && !cons_out && !cons_vio_out && !cons_row_out && !v0_out && !aux_status_out && !n_skipped_out && !act_start) return MLD_OK;      /* nothing asked for */
+
+    const hipStream_t sq = p->stream;
+    mld_problem::SimLog &L = p->slog;
+    if (log && !L.aux) {      /* every record so far was written by mld_sim_step_batch: "not resolved" */
+        DevBuf<int> la;
+        HIP_TRY(la.alloc((size_t)L.cap * batch));
+        auto fill = [&]() -> int { HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)la.get(), -2, (size_t)L.cap * batch, sq)); return MLD_OK; };
+        if (int rc = queue_and_wait(sq, fill)) return rc;
+        L.aux = std::move(la);
+    }
+    DevBuf<double> d_u, d_v0; DevBuf<unsigned char> d_mask; DevBuf<int> d_auxst; DevBuf<long long> d_start;
+    if (u0) HIP_TRY(d_u.alloc((size_t)batch * std::max(1, nu)));
+    if (act_start) HIP_TRY(d_start.alloc((size_t)batch * p->pf_groups));
+    HIP_TRY(d_v0.alloc((size_t)batch * std::max(1, nv))); HIP_TRY(d_mask.alloc(batch)); HIP_TRY(d_auxst.alloc(batch));
+    if (aux && (aux->batch != batch || aux->aux_src_gen != p->batch_gen || aux->aux_own_gen != aux->batch_gen)) {
+        /* the resolver's resident batch: p's size, model_idx and hence RHS groups; its inputs are written on the device */
+        std::vector<int32_t> midx;
+        if (p->has_midx) { midx.resize(batch); HIP_TRY(hipMemcpy(midx.data(), p->bat.model_idx, sizeof(int) * batch, hipMemcpyDeviceToHost)); }
+        if (int rc = lay_out_batch(aux, batch, p->has_midx ? midx.data() : nullptr, nullptr)) return rc;
+        aux->aux_src_gen = p->batch_gen; aux->aux_own_gen = aux->batch_gen;
+    }
+    AuxStepArgs g{};
+    g.batch = batch; g.nx = nx; g.nw = nw; g.nu = nu; g.nv = nv; g.nv2 = nv2; g.N = p->N;
+    g.x0 = p->bat.x0; g.omega = p->bat.omega;
+    if (u0) { g.u = d_u; g.u_stride = (size_t)nu; }
+    else { g.u = p->bat.v; g.u_stride = (size_t)p->n; g.status = p->bat.status; g.obj = p->bat.obj; }
+    if (actual) { g.act_start = act_start ? d_start.get() : p->pf_actual.d.get(); g.chan = p->pf_chan; g.n_groups = p->pf_groups; g.step = step; g.lib = p->pf_lib; }
+    /* ---- gather: the resolver's inputs -------------------------------------------------------------------------------------------------------------- */
+    auto gather = [&]() -> int {
+        if (u0 && nu) HIP_TRY(hipMemcpyAsync(d_u, u0, sizeof(double) * (size_t)batch * nu, hipMemcpyHostToDevice, sq));
+        if (act_start) HIP_TRY(hipMemcpyAsync(d_start, act_start, sizeof(long long) * (size_t)batch * p->pf_groups, hipMemcpyHostToDevice, sq));
+        if (aux) {
+            g.aux_x0 = aux->bat.x0; g.aux_omega = aux->bat.omega;
+            hipLaunchKernelGGL(k_aux_inputs, dim3(profile_grid((long long)batch * (nx + nw + nu))), dim3(256), 0, sq, g);
+            HIP_TRY(hipGetLastError());
+        }
+        return MLD_OK;
+    };
+    if (int rc = queue_and_wait(sq, gather)) return rc;
+    /* ---- the auxiliary solve on the resolver's handle: new inputs, as after mld_select_inputs ----------------------------------------------------------- */
+    if (aux) {
+        inputs_replaced(aux);
+        int rc = launch(aux);
+        if (rc) { (void)hipStreamSynchronize(aux->stream); return rc; }
+        if ((rc = finish(aux, nullptr))) return rc;
+        g.aux_v = aux->bat.v; g.aux_stride = (size_t)aux->n; g.aux_status = aux->bat.status; g.aux_obj = aux->bat.obj;
+    }
+    /* ---- merge, then the step on the merged slices ----------------------------------------------------------------------------------------------------- */
+    g.v0 = d_v0; g.usable = d_mask; g.aux_status_out = d_auxst;
+    SimStepSrc src;
+    src.merge = &g; src.d_v0 = d_v0; src.d_mask = d_mask; src.d_auxst = d_auxst; src.by_plan = u0 == nullptr; src.d_start = act_start ? &d_start : nullptr;
+    src.v0_out = v0_out; src.aux_status_out = aux_status_out;
+    int32_t skipped = 0;
+    if (int rc = sim_step_run(p, src, act_start, gmax, step, flags, x_k1_out, y_out, cons_out, cons_vio_out, cons_row_out, &skipped)) return rc;
+    if (n_skipped_out) *n_skipped_out = skipped;
+    return MLD_OK;
+}
+
+int mld_download_sim_log_aux(mld_problem_t *p, int first, int count, int32_t *aux_status)
+{
+    static const char who[] = "mld_download_sim_log_aux";
+    if (int rc = entry_guard(p, who, true, "no batch resident (mld_upload_batch)")) return rc;
+    const mld_problem::SimLog &L = p->slog;
+    if (first < 0 || count < 0 || (long long)first + count > L.count) { mld_set_error("%s: records [%d, %lld) asked for, %d logged", who, first, (long long)first + count, L.count); return MLD_ERR_INVALID; }
+    if (count == 0 || !aux_status) return MLD_OK;
+    const size_t off = (size_t)first * p->batch, len = (size_t)count * p->batch;
+    if (!L.aux) { std::fill(aux_status, aux_status + len, -2); return MLD_OK; }      /* no resolving step has logged: every record is mld_sim_step_batch's */
+    const hipStream_t sq = p->stream;
+    auto queue = [&]() -> int { HIP_TRY(hipMemcpyAsync(aux_status, L.aux.get() + off, sizeof(int) * len, hipMemcpyDeviceToHost, sq)); return MLD_OK; };
+    return queue_and_wait(sq, queue);
 }
 
 int mld_download_sim_log(mld_problem_t *p, int first, int count, double *x, double *v, double *y, double *omega, double *x_k1, uint8_t *cons, double *cons_vio,

@@ -32,12 +32,10 @@ static void launch_rhs_mfma(bool f32, int n_groups, int m0, int nx, int nW, cons
     else hipLaunchKernelGGL(k_rhs_mfma<false>, dim3(n_groups), dim3(64 * RM_WAVES), lds, stream, m0, nx, nW, Kp, Hx, Hw, H5, rs, groups, perm, x0, omega, hs);
 }
 
-int mld_upload_batch(mld_problem_t *p, int batch, const int32_t *model_idx, const double *x0, const double *omega,
-                     const uint8_t *fixed_bin)
+/* a batch laid out on the handle: buffers, model_idx, RHS groups, fixings -- everything of mld_upload_batch but the inputs themselves, which the caller of
+ * this function fills (mld_upload_batch from the host, mld_sim_step_resolve on the device) */
+static int lay_out_batch(mld_problem_t *p, int batch, const int32_t *model_idx, const uint8_t *fixed_bin)
 {
-    if (int rc = entry_guard(p, "mld_upload_batch", false, nullptr)) return rc;
-    if (!p || batch < 1) { mld_set_error("mld_upload_batch: bad arguments"); return MLD_ERR_INVALID; }
-    if ((p->nx && !x0) || (p->nW && !omega)) { mld_set_error("mld_upload_batch: x0/omega required"); return MLD_ERR_INVALID; }
     if (model_idx) for (int b = 0; b < batch; ++b) if (model_idx[b] < 0 || model_idx[b] >= p->n_models) { mld_set_error("model_idx[%d]=%d out of range", b, model_idx[b]); return MLD_ERR_INVALID; }
     int rc = ensure_batch(p, batch);
     if (rc) { p->batch = 0; return rc; }
@@ -54,9 +52,19 @@ int mld_upload_batch(mld_problem_t *p, int batch, const int32_t *model_idx, cons
         if ((rc = upload(p->bat.perm, perm)) || (rc = upload(p->bat.groups, groups))) return rc;
     }
     if (model_idx) HIP_TRY(hipMemcpy(p->bat.model_idx, model_idx, sizeof(int) * batch, hipMemcpyHostToDevice));
+    if (fixed_bin && p->nb) HIP_TRY(hipMemcpy(p->bat.fixed, fixed_bin, (size_t)batch * p->nb, hipMemcpyHostToDevice));
+    return MLD_OK;
+}
+
+int mld_upload_batch(mld_problem_t *p, int batch, const int32_t *model_idx, const double *x0, const double *omega,
+                     const uint8_t *fixed_bin)
+{
+    if (int rc = entry_guard(p, "mld_upload_batch", false, nullptr)) return rc;
+    if (!p || batch < 1) { mld_set_error("mld_upload_batch: bad arguments"); return MLD_ERR_INVALID; }
+    if ((p->nx && !x0) || (p->nW && !omega)) { mld_set_error("mld_upload_batch: x0/omega required"); return MLD_ERR_INVALID; }
+    if (int rc = lay_out_batch(p, batch, model_idx, fixed_bin)) return rc;
     if (p->nx) HIP_TRY(hipMemcpy(p->bat.x0, x0, sizeof(double) * (size_t)batch * p->nx, hipMemcpyHostToDevice));
     if (p->nW) HIP_TRY(hipMemcpy(p->bat.omega, omega, sizeof(double) * (size_t)batch * p->nW, hipMemcpyHostToDevice));
-    if (fixed_bin && p->nb) HIP_TRY(hipMemcpy(p->bat.fixed, fixed_bin, (size_t)batch * p->nb, hipMemcpyHostToDevice));
     return MLD_OK;
 }
 

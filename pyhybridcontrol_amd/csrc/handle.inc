@@ -89,8 +89,12 @@ struct mld_problem {
      * resident batch: mld_upload_batch discards it */
     struct SimLog {
         DevBuf<double> x, v, y, om, x_k1, vio, obj, lb; DevBuf<unsigned char> cons; DevBuf<int> row, status, nodes;
+        DevBuf<int> aux;        /* (cap, batch) resolver statuses of the records mld_sim_step_resolve wrote, -2 elsewhere: allocated by the first such step that logs */
         int cap = 0, count = 0;
     } slog;
+    /* mld_sim_step_resolve: batch_gen numbers the uploads of all handles (inputs_new_batch), so that a resolver handle can tell whether its resident batch
+     * is still the one laid out for the stepped handle's -- it remembers that handle's number and its own at the time (0 = never laid out) */
+    unsigned long long batch_gen = 0, aux_src_gen = 0, aux_own_gen = 0;
     long long ho_stats[4] = {};  /* last solve: items published, trees split, trees left unfinished, entries the queue had no room for (always 0: such trees stay unfinished) */
 };
 
@@ -101,9 +105,11 @@ struct mld_problem {
 /* new inputs for the same batch (mld_select_inputs): the blocks belonged to the previous inputs, so did the start and the cutoffs; there is no plan */
 static void inputs_replaced(mld_problem *p) { p->n_xcols = 0; p->has_warm = false; p->solved = false; p->advanced = false; p->has_cutoff = false; }
 /* a new batch (mld_upload_batch): nothing of the previous one stays -- the blocks, a simulation log and a per-instance cost belong to one upload */
+static std::atomic<unsigned long long> g_batch_gen{0};
 static void inputs_new_batch(mld_problem *p)
 {
     inputs_replaced(p);
+    p->batch_gen = ++g_batch_gen;
     if (p->slog.cap) p->slog = mld_problem::SimLog();
     if (p->ic_ld) { p->bat.icost.reset(); p->bat.qs_inst_t.reset(); p->ic_ld = 0; }
 }

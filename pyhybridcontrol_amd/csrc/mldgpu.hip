@@ -28,7 +28,7 @@ void mld_set_error(const char *fmt, ...)
 extern "C" {
 
 const char *mld_last_error(void) { return g_err; }
-const char *mld_version(void) { return "mldgpu 0.6 (gfx950, fp64 dense-dictionary cut-and-branch, in-kernel sub-tree hand-off, per-instance linear cost, predicted trajectories, solution quality, resident disturbance profiles, plant step and simulation log; sizeof(mld_opts) = 64)"; }
+const char *mld_version(void) { return "mldgpu 0.6 (gfx950, fp64 dense-dictionary cut-and-branch, in-kernel sub-tree hand-off, per-instance linear cost, predicted trajectories, solution quality, resident disturbance profiles, plant step and simulation log, auxiliaries re-derived on device; sizeof(mld_opts) = 64)"; }
 
 int mld_device_count(void)
 {
@@ -204,6 +204,7 @@ int mld_condense_f32(mld_model_t *m, int N_tilde, int flags, float *Phi_x, float
 // ---- the problem handle and its entry points, by concern -------------------------------------------------------------------------
 #include <rccl/rccl.h>
 
+#include <atomic>
 #include <limits>
 #include <memory>
 

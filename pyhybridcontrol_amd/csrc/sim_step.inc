@@ -29,6 +29,7 @@ struct SimStepArgs {
     const double *x0, *omega;                   /* current inputs: (batch, nx), (batch, N nw) */
     const double *v; size_t v_stride;           /* step-0 slices are the first nv entries of a row */
     const int *status; const double *obj;       /* resident plan: instances without a usable plan are masked; nullptr = the caller's v0, no masking */
+    const unsigned char *mask;                  /* nullptr: the rule above; else the usable flag per instance itself (k_aux_merge), status / obj only go into the record */
     const double *lbnd; const int *nodes;       /* copied into the record (nullptr: NaN / 0) */
     const long long *act_start; const PfChan *chan; int n_groups, step; const double *lib;      /* act_start == nullptr: the forecast's step 0 */
     double *x0_new, *omega_new;                 /* MLD_SIM_ADVANCE: the spare input buffers (nullptr otherwise) */
@@ -50,7 +51,7 @@ __global__ void __launch_bounds__(64 * SS_WAVES) k_sim_step(const SimStepArgs a)
     for (long long base = (long long)blockIdx.x * SS_WAVES; base < a.batch; base += (long long)gridDim.x * SS_WAVES) {      /* uniform over the workgroup */
         const long long b = base + wave;
         const bool live = b < a.batch;
-        const bool usable = live && (!a.status || plan_usable(a.status, a.obj, (int)b));
+        const bool usable = live && (a.mask ? a.mask[b] != 0 : (!a.status || plan_usable(a.status, a.obj, (int)b)));
         const double *xg = a.x0 + (live ? b : 0) * nx, *vg = a.v + (live ? b : 0) * a.v_stride, *fg = a.omega + (live ? b : 0) * nW;
         const double *pk = a.pack + (size_t)(live && a.model_idx ? a.model_idx[b] : 0) * a.pack_len;
         /* ---- inputs: staged in LDS, and copied into the record ------------------------------------------------------------------------------- */

@@ -532,15 +532,31 @@ class GpuProblem(object):
         check(_lib.load().mld_sim_log_count(self._h, C.byref(n), C.byref(cap)))
         return int(n.value), int(cap.value)
 
-    def sim_step(self, v0=None, act_start=None, step=0, actual=None, advance=True, log=None, outputs=False):
+    def sim_step(self, v0=None, act_start=None, step=0, actual=None, advance=True, log=None, outputs=False, resolve=None, u0=None):
         """one plant step of the resident batch on device (mld_sim_step_batch): the reference's lsim_k(x_k, v_k=, omega_k) with the whole step-0 slice --
         of the last solve's plans (v0=None; instances without a usable plan are skipped and counted) or the caller's v0 (batch, nv) / (nv,) -- under the
         forecast's step 0 or, with actual, the element `step` of the realised series at act_start (batch, n_groups) / (n_groups,) of the resident profile
         library (None re-uses the resident actual starts).  actual defaults to `act_start is not None`, log to "a log has begun".  advance: x0 <- x_k1
         and the forecast rotated, as advance(); False is a what-if that changes nothing.  Returns the number of skipped instances, or with outputs=True
-        dict(x_k1, y, cons (bool), cons_vio, cons_row, n_skipped)."""
+        dict(x_k1, y, cons (bool), cons_vio, cons_row, n_skipped).
+        resolve: an aux_resolve.BatchAuxResolver over the same models -- the step of the reference's lsim_k(x_k, u_k=, omega_k) instead
+        (mld_sim_step_resolve): only u is taken -- the plan's (u0=None) or the caller's u0 (batch, nu) / (nu,) -- and delta, z, mu are re-derived on the device
+        under the omega_k used; v0 must be None.  An instance whose auxiliary problem has no feasible point is skipped like one without a plan.
+        outputs=True additionally returns v0 (batch, nv), the resolved slices, and aux_status (batch), the resolver's status, -1 = not attempted."""
         d, B = self.model.dims, self.batch
         nv = self.model.nv
+        if resolve is None and u0 is not None:
+            raise ValueError("u0 given without resolve (the whole slice is v0; u0 goes with a BatchAuxResolver that re-derives the rest)")
+        if resolve is not None:
+            if v0 is not None:
+                raise ValueError("resolve and v0 both given: the resolver re-derives the auxiliaries of u0 (or of the plan's u), a whole slice leaves it nothing")
+            if u0 is not None:
+                u0 = np.asarray(u0, dtype=np.float64)
+                if u0.shape == (d["nu"],):
+                    u0 = np.broadcast_to(u0, (B, d["nu"]))
+                if u0.shape != (B, d["nu"]):
+                    raise ValueError("u0 has shape %s, expected (%d, %d) or (%d,)" % (u0.shape, B, d["nu"], d["nu"]))
+                u0 = np.ascontiguousarray(u0)
         if v0 is not None:
             v0 = np.asarray(v0, dtype=np.float64)
             if v0.shape == (nv,):
@@ -560,6 +576,22 @@ class GpuProblem(object):
         if outputs:
             out = dict(x_k1=np.zeros((B, d["nx"])), y=np.zeros((B, d["ny"])), cons=np.zeros((B, d["nc"]), np.uint8), cons_vio=np.zeros(B),
                        cons_row=np.zeros(B, np.int32))
+        if resolve is not None:
+            if outputs:
+                out.update(v0=np.zeros((B, nv)), aux_status=np.zeros(B, np.int32))
+            aux = resolve.problem._h if resolve.problem is not None else None
+            check(_lib.load().mld_sim_step_resolve(
+                self._h, aux, _lib.dptr(u0), st.ctypes.data_as(C.POINTER(C.c_int64)) if st is not None else None, int(step), flags,
+                _lib.dptr(out["x_k1"]) if out else None, _lib.dptr(out["y"]) if out else None,
+                out["cons"].ctypes.data_as(C.POINTER(C.c_uint8)) if out else None, _lib.dptr(out["cons_vio"]) if out else None,
+                ip(out["cons_row"]) if out else None, _lib.dptr(out["v0"]) if out else None, ip(out["aux_status"]) if out else None, C.byref(skipped)))
+            if resolve.problem is not None:
+                resolve.problem.batch = B      # the call lays the resolver's batch out as this one
+            if not outputs:
+                return int(skipped.value)
+            out["cons"] = out["cons"].astype(bool)
+            out["n_skipped"] = int(skipped.value)
+            return out
         check(_lib.load().mld_sim_step_batch(
             self._h, _lib.dptr(v0), st.ctypes.data_as(C.POINTER(C.c_int64)) if st is not None else None, int(step), flags,
             _lib.dptr(out["x_k1"]) if out else None, _lib.dptr(out["y"]) if out else None,
@@ -591,6 +623,19 @@ class GpuProblem(object):
             out["cons"].ctypes.data_as(C.POINTER(C.c_uint8)), _lib.dptr(out["cons_vio"]), ip(out["cons_row"]), _lib.dptr(out["obj"]),
             _lib.dptr(out["lower_bound"]), ip(out["status"]), ip(out["nodes"])))
         out["cons"] = out["cons"].astype(bool)
+        return out
+
+    def sim_log_aux(self, first=0, count=None):
+        """the resolver's status per record and instance (mld_download_sim_log_aux), (count, batch) int32: what sim_step(resolve=...) returned as aux_status,
+        -2 for the records a plain sim_step wrote"""
+        first = int(first)
+        if count is None:
+            count = self.sim_log_count()[0] - first
+        K = int(count)
+        if K < 0:
+            raise ValueError("sim_log_aux: first = %d lies beyond the %d logged steps" % (first, K + first))
+        out = np.zeros((K, self.batch), np.int32)
+        check(_lib.load().mld_download_sim_log_aux(self._h, first, K, out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out
 
     def set_warm_start(self, bin_start):
