@@ -182,6 +182,8 @@ def make_opts(**kw):
 class GpuProblem(object):
     """mld_problem_t: condensed constraint maps of a GpuModel + cost + solver workspace, on device."""
 
+    _handoff = (False, 2.0)      # the library's in-kernel hand-off switch and room_factor, as set_handoff left them (its defaults)
+
     def __init__(self, model, N_p, N_tilde, cost=None, **opts):
         self.model = model
         self.N_p, self.N_tilde = int(N_p), int(N_tilde)
@@ -800,12 +802,17 @@ class GpuProblem(object):
 
     def set_handoff(self, enable=True, sub_nodes=0, max_gen=8, max_children=64, max_tree=160, room_factor=0.0, donate=0, rounds=0):
         """in-kernel sub-tree hand-off (mld_set_handoff): searches that stop at their node limit publish their open nodes as entries of the same
-        launch's work queue; takes effect with the next upload().  sub_nodes 0 = the problem's max_nodes for items too."""
+        launch's work queue; takes effect with the next upload().  sub_nodes 0 = the problem's max_nodes for items too.  Switching it on or off,
+        or another room_factor while it is on, lays the result arrays out anew: the library drops the resident batch (upload() again before
+        solve_resident()), and so does this handle."""
         lib = _lib.load()
         lib.mld_set_handoff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]
         check(lib.mld_set_handoff(self._h, 1 if enable else 0, int(sub_nodes), int(max_gen), int(max_children), int(max_tree), float(room_factor)))
+        on, factor = self._handoff
+        if bool(enable) != on or (enable and room_factor > 0.0 and float(room_factor) != factor):
+            self.batch = 0
+        self._handoff = (bool(enable), float(room_factor) if room_factor > 0.0 else factor)
         check(lib.mld_set_handoff_policy(self._h, int(donate), int(rounds)))
-        self.batch = 0 if not enable else self.batch
 
     def handoff_stats(self):
         out = (C.c_int64 * 4)()
@@ -815,7 +822,8 @@ class GpuProblem(object):
     def solve_handoff_device(self, x0, omega, model_idx=None, fixed_bin=None, first_nodes=None, sub_nodes=None, max_gen=8, max_children=64, max_tree=160, room_factor=0.0, donate=0, rounds=0, inst_cost=None, trajectories=False, quality=False,
                              omega_cols=None, col_rows=None, x_cols=None, col_start=None, col_step=0):
         """the batch with the hand-off inside ONE launch (set_handoff): upload, solve, download -- the merged results per instance plus `handoff`
-        statistics.  The problem's own limits and the hand-off switch are restored afterwards.  inst_cost: as solve() (items use their source
+        statistics.  The problem's own limits and the hand-off switch are restored afterwards; switching it drops the resident batch, before and
+        after, so a batch that was resident is LOST and none is resident on return (upload() again).  inst_cost: as solve() (items use their source
         instance's cost).  trajectories=True adds the predicted x / y of the merged plans, quality=True out["quality"] = evaluate() of them (both read before the
         resident batch is dropped).  omega_cols / col_start, col_step with col_rows, x_cols: constraint blocks as in solve() (the items see their source
         instance's blocks)."""
@@ -853,7 +861,8 @@ class GpuProblem(object):
         instances of their own (node limit `sub_nodes` each, the parent's incumbent value as cutoff), so the whole device works on the few large
         trees instead of one workgroup per tree (a quadratic cost included: the open nodes and cutoffs carry the instance's quadratic constant
         through its objective).  An instance is proven once every one of its nodes has been closed; one whose open nodes
-        outnumber `max_open` after a pass is given up (NODE_LIMIT with its incumbent and bound).  Returns the dict of
+        outnumber `max_open` after a pass is given up (NODE_LIMIT with its incumbent and bound); a node that comes back unsplit twice, or
+        UNBOUNDED, is dropped -- its tree stays NODE_LIMIT and its bound stays in the tree's.  Returns the dict of
         download() (v, obj, status, lower_bound; nodes / pivots summed over all passes) plus `handoff` statistics; the resident batch afterwards
         is the last pass's sub-batch (upload again before advance() / warm starts)."""
         d = self.model.dims
@@ -893,6 +902,7 @@ class GpuProblem(object):
                 keep_sub = {k: getattr(self.opts, k) for k in sub_opts}
                 self.set_opts(**sub_opts)
             stuck_before = set()
+            dropped_lb, given_up = {}, set()      # tree -> smallest bound among its dropped nodes (they stay open for good); trees given up by max_open
             for r in range(int(rounds)):
                 if not open_list:
                     break
@@ -927,32 +937,32 @@ class GpuProblem(object):
                         # time it stays open for good (the tree ends NODE_LIMIT) instead of being solved again and again with the same budget
                         key = (i, fix[s_].tobytes())
                         if key in stuck_before or ss == 4:
-                            dropped = stats.setdefault("dropped", 0)
-                            stats["dropped"] = dropped + 1
-                            gave = stats.setdefault("_gave", set()); gave.add(i)
+                            stats["dropped"] = stats.get("dropped", 0) + 1
+                            dropped_lb[i] = min(dropped_lb.get(i, np.inf), nl)
                             continue
                         stuck_before.add(key)
                         stuck.add(i)
                         new_open.setdefault(i, []).append((fix[s_], nl))
                 for i in list(open_list):
                     tol = max(gap_abs, gap_rel * abs(obj[i])) if np.isfinite(obj[i]) else 0.0
-                    if i in stats.get("_gave", ()) and i not in new_open:
-                        continue                                    # a node of this tree was dropped unsplit: not proven (stays NODE_LIMIT)
-                    if i not in new_open:                           # every node closed: proven
+                    # what the tree still has open: this round's nodes and every node dropped so far (not proven: the tree stays NODE_LIMIT)
+                    left = [b_ for _, b_ in new_open.get(i, ())] + ([dropped_lb[i]] if i in dropped_lb else [])
+                    if not left:                                    # every node closed: proven
                         status[i] = 0 if np.isfinite(obj[i]) else 1
                         lb[i] = min(obj[i], max(lb[i], obj[i] - tol)) if np.isfinite(obj[i]) else lb[i]
                     else:
-                        lb[i] = max(lb[i], min(min(b_ for _, b_ in new_open[i]), obj[i] - tol if np.isfinite(obj[i]) else np.inf))
+                        lb[i] = max(lb[i], min(min(left), obj[i] - tol if np.isfinite(obj[i]) else np.inf))
                 open_list = {i: lst for i, lst in new_open.items()}
                 if max_open is not None:                            # a tree that keeps growing is given up (it stays NODE_LIMIT with its incumbent and bound)
                     gave_up = [i for i, lst in open_list.items() if len(lst) > max_open]
                     for i in gave_up:
                         del open_list[i]
-                    stats["given_up"] = stats.get("given_up", 0) + len(gave_up)
+                    given_up.update(gave_up)
+                    stats["given_up"] = len(given_up)
                 rstat["parents_left"] = len(open_list)
                 if stuck and all(i in stuck for i in open_list) and r + 1 < rounds:
                     pass                                            # (stuck nodes are simply retried with the next round's budget)
-            stats["unfinished"] = len(open_list) + stats.get("given_up", 0) + len(stats.pop("_gave", ()))
+            stats["unfinished"] = len(set(open_list) | given_up | set(dropped_lb))      # each tree once, whatever kept it from being proven
             return dict(v=v, obj=obj, status=status, lower_bound=lb, nodes=nodes, pivots=pivots, stats=out["stats"], handoff=stats)
         finally:
             self.record_open_nodes(False)

@@ -411,6 +411,7 @@ def test_open_nodes_of_a_stopped_depth_first_search_partition_what_is_left():
     must be pairwise disjoint and cover exactly the leaves not visited yet -- also under fixings the search itself ran with"""
     import itertools
     from pyhybridcontrol_amd.gpu import expand_open_nodes
+    from _handoff_toy import stack_dfs
     rng = np.random.default_rng(11)
     nb = 7
     pos = np.arange(nb)                                      # decision-vector index == binary position in this toy
@@ -421,26 +422,12 @@ def test_open_nodes_of_a_stopped_depth_first_search_partition_what_is_left():
         free = [j for j in range(nb) if fix0[j] == 255]
         total = 2 ** len(free)
         for stop_after in range(0, total + 1, max(1, total // 13)):
-            visited, pruned, stack = [], [], []                 # stack entries: [var, current value, sibling accounted for]
-            state = dict(stopped=None)
+            visited, pruned = [], []
 
-            def assignment():
-                a = fix0.copy()
-                for v_, val_, _ in stack:
-                    a[v_] = val_
-                return a
+            def enter(a):
+                return "stop" if len(visited) + len(pruned) >= stop_after else None     # the node limit hits HERE: the current path is still open
 
-            def dfs():
-                if state["stopped"] is not None:
-                    return
-                if len(visited) + len(pruned) >= stop_after:   # the node limit hits HERE: the current path is still open
-                    state["stopped"] = [list(e) for e in stack]
-                    return
-                a = assignment()
-                rest = [j for j in free if a[j] == 255]
-                if not rest:
-                    visited.append(tuple(int(x) for x in a))
-                    return
+            def choose(a, rest):
                 j = rest[int(rng.integers(len(rest)))]       # the branching variable differs from path to path, as in the solver
                 first = int(rng.integers(0, 2))
                 closed_other = bool(rng.random() < 0.2)      # penalty branching closes the sibling without a node of its own now and then
@@ -448,23 +435,13 @@ def test_open_nodes_of_a_stopped_depth_first_search_partition_what_is_left():
                     b = a.copy(); b[j] = 1 - first
                     for bits in itertools.product((0, 1), repeat=int((b == 255).sum())):
                         c = b.copy(); c[c == 255] = bits; pruned.append(tuple(int(x) for x in c))
-                stack.append([j, first, 1 if closed_other else 0])
-                dfs()
-                if state["stopped"] is not None:
-                    return
-                if not closed_other:
-                    stack[-1][1], stack[-1][2] = 1 - first, 1
-                    dfs()
-                    if state["stopped"] is not None:
-                        return
-                stack.pop()
+                return j, first, closed_other
 
-            dfs()
+            st = stack_dfs(fix0, enter, choose, lambda a: visited.append(tuple(int(x) for x in a)))      # entries: [var, current value, sibling accounted for]
             visited = visited + pruned
-            if state["stopped"] is None:
+            if st is None:
                 assert len(set(visited)) == total
                 continue
-            st = state["stopped"]
             nodes = expand_open_nodes(fix0, len(st), [e[0] for e in st], [e[1] for e in st], [e[2] for e in st], pos)
             covered = []
             for f in nodes:
