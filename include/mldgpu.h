@@ -121,9 +121,13 @@ typedef enum {
                                            one pass (A/B on the same binary: results are bit-identical, only rows_updated and speed change) */
     MLD_DBG_SIM_NO_LDS = 1 << 23,       /* k_sim_step (mld_sim_step_batch) reads x, v0, omega and y from global memory instead of staging them in LDS: the path of
                                            shapes whose staging exceeds the workgroup's LDS, on any shape (results are bit-identical) */
-    MLD_DBG_CUTS_R4 = 1 << 22           /* the wave-per-cut Gomory and c-MIR rounds as round 4 built them: one slack row / eight dictionary rows of
+    MLD_DBG_CUTS_R4 = 1 << 22,          /* the wave-per-cut Gomory and c-MIR rounds as round 4 built them: one slack row / eight dictionary rows of
                                            one column chunk in flight, generic pointers (A/B on the same binary of the grouped loads and the
                                            LDS-typed views: results are bit-identical, only speed changes) */
+    MLD_DBG_WALKS_SERIAL = 1 << 24      /* k_solve's phases outside the pivot loop with one load in flight, as before the grouped walks: the row
+                                           dot products of the refresh / residual check / leaf check, the thread-per-row walks over the sparse
+                                           copy, the x_B update of a bound list and the row-wise screen of the c-MIR scoring (A/B on the same
+                                           binary: results are bit-identical, only speed changes) */
 } mld_reserved_bit;
 
 /* Linear cost in tiled horizon form (the Python layer parses the reference's string-keyed atoms,

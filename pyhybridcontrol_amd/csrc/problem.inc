@@ -245,17 +245,46 @@ typedef __attribute__((address_space(3))) unsigned short lds_u16;
 typedef __attribute__((address_space(3))) unsigned char lds_u8;
 typedef __attribute__((address_space(1))) double glb_f64;
 typedef __attribute__((address_space(1))) double2_t glb_f64x2;
+typedef const __attribute__((address_space(1))) int glb_ci32;
+typedef const __attribute__((address_space(1))) unsigned short glb_cu16;
+typedef const __attribute__((address_space(1))) double glb_cf64;
+// entries a thread-per-row (or per-column) walk over the sparse copy takes together: the column and value loads of a group are issued first, then the loads
+// they index, then the group's updates in entry order (one entry per iteration was two dependent round trips per entry)
+#ifndef WALK_GROUP
+#define WALK_GROUP 8
+#endif
 
-// dot products of up to 4 HBM rows with one LDS vector, a wave per row batch: the 4 x U independent loads are issued
-// before the first use (one dependent load per iteration costs a full memory latency each)
+// dot products of up to 4 HBM rows with one LDS vector, a wave per row batch: the independent loads are issued before the first use (one dependent
+// load per iteration costs a full memory latency each).  All DOT_KC column chunks of the four rows go into registers first (n <= 576: the whole row
+// group in one pass, 36 loads in flight; wider rows take several passes), then the multiply-adds run in ascending j per row.  The interleaved load /
+// multiply-add loop -- the same sums in the same order, but compiled to a wait before every multiply-add -- stays as the path of MLD_DBG_WALKS_SERIAL.
+#ifndef DOT_KC
+#define DOT_KC 9
+#endif
 __device__ __forceinline__ void wave_rows_dot4(const glb_f64 *r0, const glb_f64 *r1, const glb_f64 *r2, const glb_f64 *r3,
-                                               const lds_f64 *x, int n, int lane, double out[4])
+                                               const lds_f64 *x, int n, int lane, double out[4], bool serial)
 {
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    if (serial) {
 #pragma unroll 4
-    for (int j = lane; j < n; j += 64) {
-        const double xv = x[j];
-        s0 += r0[j] * xv; s1 += r1[j] * xv; s2 += r2[j] * xv; s3 += r3[j] * xv;
+        for (int j = lane; j < n; j += 64) {
+            const double xv = x[j];
+            s0 += r0[j] * xv; s1 += r1[j] * xv; s2 += r2[j] * xv; s3 += r3[j] * xv;
+        }
+    } else {
+        for (int j0 = lane; j0 < n; j0 += 64 * DOT_KC) {      // (j0 < n: a lane past the end of the row has no summand, as in the loop above)
+            double v0[DOT_KC], v1[DOT_KC], v2[DOT_KC], v3[DOT_KC];
+#pragma unroll
+            for (int k = 0; k < DOT_KC; ++k) {
+                const int j = j0 + k * 64 < n ? j0 + k * 64 : 0;      // (past the end: entry 0 again, loaded without a branch and not used)
+                v0[k] = r0[j]; v1[k] = r1[j]; v2[k] = r2[j]; v3[k] = r3[j];
+            }
+#pragma unroll
+            for (int k = 0; k < DOT_KC; ++k) {
+                const int j = j0 + k * 64;
+                if (j < n) { const double xv = x[j]; s0 += v0[k] * xv; s1 += v1[k] * xv; s2 += v2[k] * xv; s3 += v3[k] * xv; }
+            }
+        }
     }
     out[0] = s0; out[1] = s1; out[2] = s2; out[3] = s3;
 }
@@ -290,7 +319,8 @@ struct Shared {
 #endif
     long long prof[8];         // ticks: 0 pivot update, 1 simplex selection, 2 cuts, 3 leaf, 4 set_bounds, 5 residual/refactor, 6 setup
 #ifdef MLD_CUT_PROF
-    long long cprof[11];       // cut separation split: c-MIR scoring (phase A), c-MIR build (phase B), Gomory round; from 3: counts (CUT_COUNT sites) -- cut rounds,
+    long long cprof[15];       // (11..14: phase A of the c-MIR round split -- x gather and fractional list, screen, pass 1 with its wave sums, divisor loop; the
+                               // last two on wave 0's clock; -DMLD_CUT_PROF=3 reports them in slots 0..3 of mld_debug_profile) cut separation split: c-MIR scoring (phase A), c-MIR build (phase B), Gomory round; from 3: counts (CUT_COUNT sites) -- cut rounds,
                                // Gomory cuts derived, slack columns substituted in them, c-MIR cuts built, rows substituted in them (nbr), rows scored, their list
                                // entries, (row, divisor) pairs scored
 #endif
@@ -454,6 +484,7 @@ struct Ws {
     double *mir_line; int mir_cap;   // compact per-wave lines of the c-MIR scoring in LDS (SOL_NW x 2 mir_cap), or null
     double *xroot, *fx_lo, *fx_hi;   // nb: root relaxation values of the binaries; saved root bounds of RINS fixings
     const int *csr_ptr; const unsigned short *csr_col; const double *csr_val;      // this instance's model: sparse copy of the scaled original rows (s_presolve), or null
+    const int *csc_ptr; const unsigned short *csc_row;      // the same by columns (row indices only: the screen of s_mir_round), or null
     double *clo, *chi;               // n: bounds the c-MIR builder and the dead-row test use for the structurals (s_presolve: implied bounds of this instance; the LP's own otherwise)
     int *fx_j;
 };
@@ -560,6 +591,10 @@ __device__ __noinline__ bool s_presolve(const Ws &w, Shared &sh, const ProblemDe
     const unsigned short *rc = P.csr_col + (size_t)mdl * P.nnz_cap, *cr = P.csc_row + (size_t)mdl * P.nnz_cap;
     const double *rv = P.csr_val + (size_t)mdl * P.nnz_cap, *cv = P.csc_val + (size_t)mdl * P.nnz_cap;
     double *rtot = w.mir_eff; int *rmeta = (int *)w.mir_delta;      // -1: every term finite, >= 0: the one column with an infinite term, -2: more than one / no such row
+    // typed views of the same arrays for the grouped walks (all in global memory: the model's sparse copies, the instance's right-hand side, this slot)
+    glb_cu16 *grc = (glb_cu16 *)rc, *gcr = (glb_cu16 *)cr; glb_cf64 *grv = (glb_cf64 *)rv, *gcv = (glb_cf64 *)cv;
+    glb_cf64 *glo = (glb_cf64 *)w.clo, *ghi = (glb_cf64 *)w.chi, *gtot = (glb_cf64 *)rtot, *ghs = (glb_cf64 *)w.hs; glb_ci32 *gmeta = (glb_ci32 *)rmeta;
+    const bool serial = (w.dbg & MLD_DBG_WALKS_SERIAL) != 0;
     bool ok = true;
     __syncthreads();
     for (int pass = 0; pass < S_PRE_PASSES; ++pass) {
@@ -570,11 +605,22 @@ __device__ __noinline__ bool s_presolve(const Ws &w, Shared &sh, const ProblemDe
             double sum = 0.0; int ninf = 0, jinf = -1;
             const int e1 = rp[i + 1];
             MLD_CHECK(w, rp[i] >= 0 && e1 <= P.nnz_cap && rp[i] <= e1, 140, rp[i], e1);
+            if (serial)
             for (int e = rp[i]; e < e1; ++e) {
                 const int j = rc[e]; const double g = rv[e];
                 MLD_CHECK(w, j < n, 141, j, n);
                 const double b = g > 0.0 ? w.clo[j] : w.chi[j];
                 if (fabs(b) >= 0.5 * S_BIG) { ninf++; jinf = j; } else sum += g * b;
+            }
+            else
+            for (int e = rp[i]; e < e1; e += WALK_GROUP) {
+                int cj[WALK_GROUP]; double cg[WALK_GROUP], cb[WALK_GROUP];
+#pragma unroll
+                for (int q = 0; q < WALK_GROUP; ++q) { const int eq = min(e + q, e1 - 1); cj[q] = grc[eq]; cg[q] = grv[eq]; MLD_CHECK(w, cj[q] < n, 141, cj[q], n); }
+#pragma unroll
+                for (int q = 0; q < WALK_GROUP; ++q) cb[q] = cg[q] > 0.0 ? glo[cj[q]] : ghi[cj[q]];
+#pragma unroll
+                for (int q = 0; q < WALK_GROUP; ++q) if (e + q < e1) { if (fabs(cb[q]) >= 0.5 * S_BIG) { ninf++; jinf = cj[q]; } else sum += cg[q] * cb[q]; }
             }
             rtot[i] = sum; rmeta[i] = ninf == 0 ? -1 : (ninf == 1 ? jinf : -2);
             if (ninf == 0 && sum > h + 1e-6 * fmax(1.0, fabs(h))) flag = 2.0;
@@ -586,6 +632,7 @@ __device__ __noinline__ bool s_presolve(const Ws &w, Shared &sh, const ProblemDe
             const double lo0 = lo, hi0 = hi;
             const bool isint = w.is_int[j] != 0;
             const int e1 = cp[j + 1];
+            if (serial)
             for (int e = cp[j]; e < e1; ++e) {
                 const int i = cr[e]; const double g = cv[e];
                 MLD_CHECK(w, i < m0, 142, i, m0);
@@ -599,6 +646,29 @@ __device__ __noinline__ bool s_presolve(const Ws &w, Shared &sh, const ProblemDe
                 } else {
                     if (isint) b = ceil(b - 1e-6);
                     if (b > lo + 1e-9 * fmax(1.0, fabs(b))) lo = b;
+                }
+            }
+            else
+            for (int e = cp[j]; e < e1; e += WALK_GROUP) {
+                int ci[WALK_GROUP], cm[WALK_GROUP]; double cg[WALK_GROUP], ct[WALK_GROUP], ch[WALK_GROUP];
+#pragma unroll
+                for (int q = 0; q < WALK_GROUP; ++q) { const int eq = min(e + q, e1 - 1); ci[q] = gcr[eq]; cg[q] = gcv[eq]; MLD_CHECK(w, ci[q] < m0, 142, ci[q], m0); }
+#pragma unroll
+                for (int q = 0; q < WALK_GROUP; ++q) { cm[q] = gmeta[ci[q]]; ct[q] = gtot[ci[q]]; ch[q] = ghs[ci[q]]; }
+#pragma unroll
+                for (int q = 0; q < WALK_GROUP; ++q) {
+                    if (e + q >= e1) continue;
+                    const double g = cg[q]; const int mt = cm[q];
+                    if (mt == -2 || (mt >= 0 && mt != j)) continue;
+                    const double rest = mt == j ? ct[q] : ct[q] - g * (g > 0.0 ? lo0 : hi0);
+                    double b = (ch[q] - rest) / g;
+                    if (g > 0.0) {
+                        if (isint) b = floor(b + 1e-6);
+                        if (b < hi - 1e-9 * fmax(1.0, fabs(b))) hi = b;
+                    } else {
+                        if (isint) b = ceil(b - 1e-6);
+                        if (b > lo + 1e-9 * fmax(1.0, fabs(b))) lo = b;
+                    }
                 }
             }
             if (lo > hi + 1e-6 * fmax(1.0, fabs(lo))) flag = 2.0;
@@ -637,10 +707,23 @@ __device__ void s_mark_dead(const Ws &w, Shared &sh, bool enable, const double *
         for (int i = threadIdx.x; i < w.m0; i += SOL_NT) {
             double act = 0.0; bool inf = false;
             const int e1 = rp[i + 1];
+            if (w.dbg & MLD_DBG_WALKS_SERIAL)
             for (int e = rp[i]; e < e1; ++e) {
                 const int j = rc[e]; const double g = rv[e];
                 const double b = g > 0.0 ? w.chi[j] : w.clo[j];
                 if (fabs(b) >= 0.5 * S_BIG) inf = true; else act += g * b;
+            }
+            else {
+                glb_cu16 *grc = (glb_cu16 *)rc; glb_cf64 *grv = (glb_cf64 *)rv, *glo = (glb_cf64 *)w.clo, *ghi = (glb_cf64 *)w.chi;
+                for (int e = rp[i]; e < e1; e += WALK_GROUP) {
+                    int cj[WALK_GROUP]; double cg[WALK_GROUP], cb[WALK_GROUP];
+#pragma unroll
+                    for (int q = 0; q < WALK_GROUP; ++q) { const int eq = min(e + q, e1 - 1); cj[q] = grc[eq]; cg[q] = grv[eq]; }
+#pragma unroll
+                    for (int q = 0; q < WALK_GROUP; ++q) cb[q] = cg[q] > 0.0 ? ghi[cj[q]] : glo[cj[q]];
+#pragma unroll
+                    for (int q = 0; q < WALK_GROUP; ++q) if (e + q < e1) { if (fabs(cb[q]) >= 0.5 * S_BIG) inf = true; else act += cg[q] * cb[q]; }
+                }
             }
             if (!inf && act <= w.hs[i] - 1e-7) w.skip[i] = 2;
         }
@@ -737,7 +820,20 @@ __device__ void s_reset_dictionary(const Ws &w, Shared &sh)
             const int i = w.live[t];
             double *dst = w.D + (size_t)i * ld;
             const int e1 = w.csr_ptr[i + 1];
-            for (int e = w.csr_ptr[i]; e < e1; ++e) dst[w.where[w.csr_col[e]]] = w.csr_val[e];
+            if (w.dbg & MLD_DBG_WALKS_SERIAL) { for (int e = w.csr_ptr[i]; e < e1; ++e) dst[w.where[w.csr_col[e]]] = w.csr_val[e]; }
+            else {
+                glb_cu16 *rc = (glb_cu16 *)w.csr_col; glb_cf64 *rv = (glb_cf64 *)w.csr_val; glb_ci32 *wh = (glb_ci32 *)w.where;
+                glb_f64 *dg = (glb_f64 *)dst;
+                for (int e = w.csr_ptr[i]; e < e1; e += WALK_GROUP) {       // (a row's entries have distinct columns: the stores of a group do not meet)
+                    int cj[WALK_GROUP], cc[WALK_GROUP]; double cg[WALK_GROUP];
+#pragma unroll
+                    for (int q = 0; q < WALK_GROUP; ++q) { const int eq = min(e + q, e1 - 1); cj[q] = rc[eq]; cg[q] = rv[eq]; }
+#pragma unroll
+                    for (int q = 0; q < WALK_GROUP; ++q) cc[q] = wh[cj[q]];
+#pragma unroll
+                    for (int q = 0; q < WALK_GROUP; ++q) if (e + q < e1) dg[cc[q]] = cg[q];
+                }
+            }
         }
         __syncthreads();
     }
@@ -752,7 +848,21 @@ __device__ void s_refresh_initial(const Ws &w, Shared &sh)
         const int i = w.live[t];
         double acc = w.hs[i];
         const int e1 = w.csr_ptr[i + 1];
-        for (int e = w.csr_ptr[i]; e < e1; ++e) acc -= w.csr_val[e] * w.xN[w.where[w.csr_col[e]]];
+        if (w.dbg & MLD_DBG_WALKS_SERIAL) { for (int e = w.csr_ptr[i]; e < e1; ++e) acc -= w.csr_val[e] * w.xN[w.where[w.csr_col[e]]]; }
+        else {
+            glb_cu16 *rc = (glb_cu16 *)w.csr_col; glb_cf64 *rv = (glb_cf64 *)w.csr_val; glb_ci32 *wh = (glb_ci32 *)w.where;
+            for (int e = w.csr_ptr[i]; e < e1; e += WALK_GROUP) {
+                int cj[WALK_GROUP], cc[WALK_GROUP]; double cg[WALK_GROUP], xv[WALK_GROUP];
+#pragma unroll
+                for (int q = 0; q < WALK_GROUP; ++q) { const int eq = min(e + q, e1 - 1); cj[q] = rc[eq]; cg[q] = rv[eq]; }
+#pragma unroll
+                for (int q = 0; q < WALK_GROUP; ++q) cc[q] = wh[cj[q]];
+#pragma unroll
+                for (int q = 0; q < WALK_GROUP; ++q) xv[q] = w.xN[cc[q]];
+#pragma unroll
+                for (int q = 0; q < WALK_GROUP; ++q) if (e + q < e1) acc -= cg[q] * xv[q];
+            }
+        }
         w.xB[i] = acc;
     }
     __syncthreads();
@@ -773,7 +883,7 @@ __device__ void s_refresh(const Ws &w, Shared &sh)
 #pragma unroll
         for (int q = 0; q < 4; ++q) { ri[q] = live_row(w, sh, t0 + q < nl ? t0 + q : t0); rp[q] = D + (size_t)ri[q] * ld; }
         double s[4];
-        wave_rows_dot4(rp[0], rp[1], rp[2], rp[3], xs, n, lane, s);
+        wave_rows_dot4(rp[0], rp[1], rp[2], rp[3], xs, n, lane, s, (w.dbg & MLD_DBG_WALKS_SERIAL) != 0);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const double t = wave_sum(s[q]);
@@ -887,7 +997,32 @@ __device__ void s_set_bounds_list(const Ws &w, Shared &sh, const int *js, const 
             nmove += tot;
         }
         __syncthreads();
-        if (nmove > 0)
+        if (nmove > 0 && !(w.dbg & MLD_DBG_WALKS_SERIAL)) {
+            // a wave takes four rows at a time (r, r + SOL_NW, ...): the gathers of all four are issued together, their shuffle sums run interleaved, then
+            // the four stores; per row the same sum over the same lanes as the loop below (a row past the end of a tail group adds zeros and stores nothing)
+            const glb_f64 *Dg = (const glb_f64 *)w.D;
+            const int m = sh.m;
+            for (int r0 = wave; r0 < m; r0 += 4 * SOL_NW) {
+                double sa[4] = {0.0, 0.0, 0.0, 0.0}, xb[4];
+                for (int tb = 0; tb < nmove; tb += 64) {
+                    const int t = tb + lane; const bool ok = t < nmove;
+                    const int c = ok ? (int)clist[t] : 0; const double dl = ok ? dlist[t] : 0.0;
+                    double v[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) { const int r = r0 + q * SOL_NW < m ? r0 + q * SOL_NW : r0; v[q] = Dg[(size_t)r * ld + c]; }      // (no branch: a lane past the list reads column 0, a row past the end row r0 again; neither is used)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) if (ok) sa[q] += v[q] * dl;
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) { const int r = r0 + q * SOL_NW; xb[q] = (lane == 0 && r < m) ? w.xB[r] : 0.0; }
+                for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) sa[q] += __shfl_down(sa[q], o, 64);
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) { const int r = r0 + q * SOL_NW; if (lane == 0 && r < m) w.xB[r] = xb[q] - sa[q]; }
+            }
+        } else if (nmove > 0)
             for (int r = wave; r < sh.m; r += SOL_NW) {
                 const double *row = w.D + (size_t)r * ld;
                 double sacc = 0.0;
@@ -1239,7 +1374,19 @@ __device__ __noinline__ double s_check_residual(const Ws &w, Shared &sh)
             const int i = w.live[t];
             double acc = 0.0;
             const int e1 = w.csr_ptr[i + 1];
-            for (int e = w.csr_ptr[i]; e < e1; ++e) acc += w.csr_val[e] * xs[w.csr_col[e]];
+            if (w.dbg & MLD_DBG_WALKS_SERIAL) { for (int e = w.csr_ptr[i]; e < e1; ++e) acc += w.csr_val[e] * xs[w.csr_col[e]]; }
+            else {
+                glb_cu16 *rc = (glb_cu16 *)w.csr_col; glb_cf64 *rv = (glb_cf64 *)w.csr_val;
+                for (int e = w.csr_ptr[i]; e < e1; e += WALK_GROUP) {
+                    int cj[WALK_GROUP]; double cg[WALK_GROUP], xv[WALK_GROUP];
+#pragma unroll
+                    for (int q = 0; q < WALK_GROUP; ++q) { const int eq = min(e + q, e1 - 1); cj[q] = rc[eq]; cg[q] = rv[eq]; }      // (past the end: the last entry again, not used)
+#pragma unroll
+                    for (int q = 0; q < WALK_GROUP; ++q) xv[q] = xs[cj[q]];
+#pragma unroll
+                    for (int q = 0; q < WALK_GROUP; ++q) if (e + q < e1) acc += cg[q] * xv[q];
+                }
+            }
             const int wh = w.where[n + i];
             MLD_CHECK(w, wh < n && -1 - wh < m, 136, i, wh);
             const double v = wh >= 0 ? w.xN[wh] : w.xB[-1 - wh];
@@ -1251,7 +1398,7 @@ __device__ __noinline__ double s_check_residual(const Ws &w, Shared &sh)
 #pragma unroll
         for (int q = 0; q < 4; ++q) { ri[q] = live_row(w, sh, t0 + q < nl ? t0 + q : t0); rp[q] = (const glb_f64 *)orig_row(w, ri[q]); }
         double s[4];
-        wave_rows_dot4(rp[0], rp[1], rp[2], rp[3], xs, n, lane, s);
+        wave_rows_dot4(rp[0], rp[1], rp[2], rp[3], xs, n, lane, s, (w.dbg & MLD_DBG_WALKS_SERIAL) != 0);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const double t = wave_sum(s[q]);
@@ -2751,6 +2898,9 @@ __device__ __forceinline__ void s_mir_phase_a(GB ga, GB gx, int cap, const Ws &w
     const lds_u16 *rows = (const lds_u16 *)w.rowlist;
     for (int qi = wave; qi < ncand; qi += SOL_NW) {
         const int i = rows[qi];
+#ifdef MLD_CUT_PROF
+        const long long tp1 = wall_clock64();
+#endif
         MLD_CHECK(w, i >= 0 && i < w.m0 && cap > 0, 125, i, cap);
         const double *g = w.Gs + (size_t)i * n;
         // pass 1: bound substitution of the continuous entries, complementing of binaries above 1/2; the free binaries are
@@ -2820,8 +2970,89 @@ __device__ __forceinline__ void s_mir_phase_a(GB ga, GB gx, int cap, const Ws &w
         rhs = wave_sum(rhs); sval = wave_sum(sval); S2 = wave_sum(S2);
         rhs = __shfl(rhs, 0, 64) + w.hs[i]; sval = __shfl(sval, 0, 64); S2 = __shfl(S2, 0, 64);
         double best, bdelta;
+#ifdef MLD_CUT_PROF
+        const long long tp2 = wall_clock64();
+        if (wave == 0 && lane == 0) sh.cprof[13] += tp2 - tp1;
+#endif
         s_mir_score_row(ga, gx, cnt, lane, rhs, sval, S2, usable, split, sh, best, bdelta);
         if (lane == 0) { w.mir_eff[i] = best > 1e-4 ? best : -S_INF; w.mir_delta[i] = bdelta; }
+#ifdef MLD_CUT_PROF
+        if (wave == 0 && lane == 0) sh.cprof[14] += wall_clock64() - tp2;
+#endif
+    }
+}
+
+// Phase A over the sparse copy with the row a wave takes next in flight (the path of every handle that has the copy; MLD_DBG_WALKS_SERIAL keeps the loop
+// above).  A scored row was a chain of dependent round trips -- rowlist -> csr_ptr -> (column, value) -> is_int -> bounds, then hs after the wave sums.  Here
+// the csr_ptr pair and hs of row qi + SOL_NW are loaded while row qi is processed, its first 64 entries are issued before row qi's divisor loop starts, and
+// is_int / clo / chi are loaded together behind the column index (the LP bounds of a binary come from LDS when L).  Typed views: global_* for the instance
+// data, ds_* for the workgroup's lists.  A wave without a next row re-reads its own row's pair (nothing past ncand or csr_ptr[m0] is read).  Per row the
+// same operations on the same operands in the same order as above.
+template <typename GB, bool L>
+__device__ __forceinline__ void s_mir_phase_a_pipe(GB ga, GB gx, int cap, const Ws &w, const lds_f64 *xs, int ncand, int wave, int lane, bool split, Shared &sh)
+{
+    const lds_u16 *rows = (const lds_u16 *)w.rowlist;
+    glb_ci32 *ptr = (glb_ci32 *)w.csr_ptr; glb_cu16 *col = (glb_cu16 *)w.csr_col; glb_cf64 *val = (glb_cf64 *)w.csr_val;
+    glb_cf64 *ghs = (glb_cf64 *)w.hs, *gclo = (glb_cf64 *)w.clo, *gchi = (glb_cf64 *)w.chi;
+    const typename CutT<true>::cu8p isint = (typename CutT<true>::cu8p)w.is_int;
+    const typename HotT<L>::f64p h_lo = (typename HotT<L>::f64p)w.lo, h_hi = (typename HotT<L>::f64p)w.hi;
+    if (wave >= ncand) return;
+    int i = rows[wave];
+    int e0 = ptr[i], e1 = ptr[i + 1];
+    double hsv = ghs[i];
+    int jf = 0; double gf = 0.0;
+    if (e0 + lane < e1) { jf = col[e0 + lane]; gf = val[e0 + lane]; }
+    for (int qi = wave; qi < ncand; qi += SOL_NW) {
+#ifdef MLD_CUT_PROF
+        const long long tp1 = wall_clock64();
+#endif
+        MLD_CHECK(w, i >= 0 && i < w.m0 && cap > 0, 125, i, cap);
+        const bool has = qi + SOL_NW < ncand;
+        const int in = has ? (int)rows[qi + SOL_NW] : i;
+        const int e0n = ptr[in], e1n = ptr[in + 1];
+        const double hsn = ghs[in];
+        double rhs = 0.0, sval = 0.0, S2 = 0.0; int usable = 1, cnt = 0;
+        bool over = false;       // wave-uniform
+        for (int eb = e0; eb < e1 && !over; eb += 64) {
+            const int e = eb + lane;
+            bool keep = false; double ac = 0.0, xc = 0.0;
+            if (e < e1) {
+                int j = jf; double gj = gf;
+                if (eb != e0) { j = col[e]; gj = val[e]; }      // (rows of more than 64 entries: the later chunks as before)
+                const unsigned char ii = isint[j];
+                const double cl = gclo[j], ch = gchi[j], bl = h_lo[j], bh = h_hi[j];
+                const double x = xs[j];
+                if (ii) {
+                    const double lo = bl, hi = bh;
+                    if (lo == hi) rhs -= gj * lo;
+                    else { const bool comp = x > 0.5; if (comp) rhs -= gj; keep = true; ac = comp ? -gj : gj; xc = comp ? 1.0 - x : x; }
+                } else {
+                    const double lo = cl, hi = ch;
+                    const bool lof = lo > -0.5 * S_BIG, hif = hi < 0.5 * S_BIG;
+                    if (gj > 0) { if (lof) rhs -= gj * lo; else if (hif) { rhs -= gj * hi; sval += gj * (hi - x); S2 += gj * gj; } else usable = 0; }
+                    else { if (lof) { rhs -= gj * lo; sval += -gj * (x - lo); S2 += gj * gj; } else if (hif) rhs -= gj * hi; else usable = 0; }
+                }
+            }
+            const unsigned long long bal = __ballot(keep);
+            if (cnt + __popcll(bal) > cap) { usable = 0; over = true; break; }
+            if (keep) { const int pos = cnt + __popcll(bal & ((1ull << lane) - 1ull)); ga[pos] = ac; gx[pos] = xc; }
+            cnt += __popcll(bal);
+        }
+        rhs = wave_sum(rhs); sval = wave_sum(sval); S2 = wave_sum(S2);
+        rhs = __shfl(rhs, 0, 64) + hsv; sval = __shfl(sval, 0, 64); S2 = __shfl(S2, 0, 64);
+        int jn = 0; double gn = 0.0;
+        if (has && e0n + lane < e1n) { jn = col[e0n + lane]; gn = val[e0n + lane]; }
+        double best, bdelta;
+#ifdef MLD_CUT_PROF
+        const long long tp2 = wall_clock64();
+        if (wave == 0 && lane == 0) sh.cprof[13] += tp2 - tp1;
+#endif
+        s_mir_score_row(ga, gx, cnt, lane, rhs, sval, S2, usable, split, sh, best, bdelta);
+        if (lane == 0) { w.mir_eff[i] = best > 1e-4 ? best : -S_INF; w.mir_delta[i] = bdelta; }
+#ifdef MLD_CUT_PROF
+        if (wave == 0 && lane == 0) sh.cprof[14] += wall_clock64() - tp2;
+#endif
+        i = in; e0 = e0n; e1 = e1n; hsv = hsn; jf = jn; gf = gn;
     }
 }
 
@@ -3044,10 +3275,42 @@ __device__ int s_mir_round(const Ws &w, Shared &sh, int max_cuts)
         nF = block_compact(sh, fr, (unsigned short)j, w.seclist, nF);
     }
     __syncthreads();
+#ifdef MLD_CUT_PROF
+    const long long tc_list = wall_clock64();
+    if (tid == 0) sh.cprof[11] += tc_list - tc_start;
+#endif
     // screen all rows at once (a thread per row, one load per listed binary): only rows that touch a fractional binary
     // are scored; they are compacted in row order and dealt to the waves
     int ncand = 0;
-    {
+    if (w.csc_ptr && !(w.dbg & MLD_DBG_WALKS_SERIAL)) {
+        // by columns: a thread per listed binary walks its column of the sparse copy and flags the rows it meets -- nF x 25 entries instead of one scattered
+        // load per (live row, listed binary).  Both copies hold exactly the entries != 0.0 of the scaled rows, so a row is flagged if and only if the dense
+        // screen below hits it.  The byte flags live in w.colc (8 mcap >= m0 bytes of LDS): the multiplier column of a pivot is dead between pivots, phase A
+        // does not touch it and phase B overwrites it with its ranking keys after the barrier that ends phase A.
+        const lds_u16 *fl = (const lds_u16 *)w.seclist;
+        lds_u8 *rowflag = (lds_u8 *)w.colc;
+        glb_ci32 *cp = (glb_ci32 *)w.csc_ptr; glb_cu16 *cr = (glb_cu16 *)w.csc_row;
+        for (int i = tid; i < m0; i += SOL_NT) rowflag[i] = 0;
+        __syncthreads();
+        for (int k = tid; k < nF; k += SOL_NT) {
+            const int j = fl[k];
+            const int e0 = cp[j], e1 = cp[j + 1];
+            for (int e = e0; e < e1; e += WALK_GROUP) {
+                int ri[WALK_GROUP];
+#pragma unroll
+                for (int q = 0; q < WALK_GROUP; ++q) ri[q] = cr[min(e + q, e1 - 1)];      // (past the end: the last entry again)
+#pragma unroll
+                for (int q = 0; q < WALK_GROUP; ++q) { MLD_CHECK(w, ri[q] < m0, 143, ri[q], m0); rowflag[ri[q]] = 1; }      // (every writer stores the same value)
+            }
+        }
+        __syncthreads();
+        for (int i0 = 0; i0 < m0; i0 += SOL_NT) {
+            const int i = i0 + tid;
+            const bool hit = i < m0 && nF > 0 && !(w.skip[i] & 2) && rowflag[i] != 0;
+            if (i < m0 && !hit) w.mir_eff[i] = -S_INF;
+            ncand = block_compact(sh, hit, (unsigned short)i, w.rowlist, ncand);
+        }
+    } else {
         const lds_u16 *fl = (const lds_u16 *)w.seclist;
         for (int i0 = 0; i0 < m0; i0 += SOL_NT) {
             const int i = i0 + tid;
@@ -3067,10 +3330,19 @@ __device__ int s_mir_round(const Ws &w, Shared &sh, int max_cuts)
         }
     }
     __syncthreads();
+#ifdef MLD_CUT_PROF
+    if (tid == 0) sh.cprof[12] += wall_clock64() - tc_list;
+#endif
     MLD_CHECK(w, nF <= w.nb && ncand <= m0, 120, nF, ncand);
     if (ncand > 0) {
         const bool split = w.mir_in_lds && !(w.dbg & MLD_DBG_CUTS_R4);       // several divisors of a row per wave (s_mir_score_sub)
-        if (w.mir_line) s_mir_phase_a<lds_f64 *>((lds_f64 *)w.mir_line + (size_t)wave * 2 * w.mir_cap, (lds_f64 *)w.mir_line + (size_t)wave * 2 * w.mir_cap + w.mir_cap, w.mir_cap, w, xs, ncand, wave, lane, split, sh);
+        const bool pipe = w.csr_ptr && !(w.dbg & MLD_DBG_WALKS_SERIAL);      // the sparse copy exists: the pipelined pass 1 (s_mir_phase_a_pipe)
+        lds_f64 *lga = w.mir_line ? (lds_f64 *)w.mir_line + (size_t)wave * 2 * w.mir_cap : (lds_f64 *)w.mir_cache + (size_t)wave * 2 * n;
+        const int lcap = w.mir_line ? w.mir_cap : n;
+        if (pipe && (w.mir_line || w.mir_in_lds) && w.all_lds) s_mir_phase_a_pipe<lds_f64 *, true>(lga, lga + lcap, lcap, w, xs, ncand, wave, lane, split, sh);
+        else if (pipe && (w.mir_line || w.mir_in_lds)) s_mir_phase_a_pipe<lds_f64 *, false>(lga, lga + lcap, lcap, w, xs, ncand, wave, lane, split, sh);
+        else if (pipe) s_mir_phase_a_pipe<double *, false>(w.mir_cache + (size_t)wave * 2 * n, w.mir_cache + (size_t)wave * 2 * n + n, n, w, xs, ncand, wave, lane, false, sh);
+        else if (w.mir_line) s_mir_phase_a<lds_f64 *>((lds_f64 *)w.mir_line + (size_t)wave * 2 * w.mir_cap, (lds_f64 *)w.mir_line + (size_t)wave * 2 * w.mir_cap + w.mir_cap, w.mir_cap, w, xs, ncand, wave, lane, split, sh);
         else if (w.mir_in_lds) s_mir_phase_a<lds_f64 *>((lds_f64 *)w.mir_cache + (size_t)wave * 2 * n, (lds_f64 *)w.mir_cache + (size_t)wave * 2 * n + n, n, w, xs, ncand, wave, lane, split, sh);
         else s_mir_phase_a<double *>(w.mir_cache + (size_t)wave * 2 * n, w.mir_cache + (size_t)wave * 2 * n + n, n, w, xs, ncand, wave, lane, false, sh);
     }
@@ -3341,9 +3613,25 @@ __device__ __noinline__ bool s_leaf_eval(const Ws &w, Shared &sh, const SolverSh
     __syncthreads();
     if (tid == 0) {
         int ns = 0;
+        if (w.dbg & MLD_DBG_WALKS_SERIAL)
         for (int k = 0; k < nb; ++k) {
             const int j = w.bins[k];
             if (w.lo[j] != w.hi[j]) { w.sv_j[ns] = j; w.sv_lo[ns] = w.lo[j]; w.sv_hi[ns] = w.hi[j]; w.key[ns] = fmin(fmax(rint(w.tmpx[j]), w.lo[j]), w.hi[j]); ns++; }
+        }
+        else {
+            // the same list, one thread, WALK_GROUP binaries at a time: their indices, then bounds and values of all of them, then the entries in order (one
+            // binary per iteration was two to three dependent round trips for each of the nb binaries, once per leaf)
+            glb_ci32 *gb = (glb_ci32 *)w.bins; glb_cf64 *gx = (glb_cf64 *)w.tmpx;
+            for (int k0 = 0; k0 < nb; k0 += WALK_GROUP) {
+                int jj[WALK_GROUP]; double lo[WALK_GROUP], hi[WALK_GROUP], tx[WALK_GROUP];
+#pragma unroll
+                for (int q = 0; q < WALK_GROUP; ++q) jj[q] = gb[min(k0 + q, nb - 1)];
+#pragma unroll
+                for (int q = 0; q < WALK_GROUP; ++q) { lo[q] = w.lo[jj[q]]; hi[q] = w.hi[jj[q]]; tx[q] = gx[jj[q]]; }
+#pragma unroll
+                for (int q = 0; q < WALK_GROUP; ++q)
+                    if (k0 + q < nb && lo[q] != hi[q]) { w.sv_j[ns] = jj[q]; w.sv_lo[ns] = lo[q]; w.sv_hi[ns] = hi[q]; w.key[ns] = fmin(fmax(rint(tx[q]), lo[q]), hi[q]); ns++; }
+            }
         }
         sh.s_i[0] = ns;
     }
@@ -3377,7 +3665,19 @@ __device__ __noinline__ bool s_leaf_eval(const Ws &w, Shared &sh, const SolverSh
                 for (int i = tid; i < S.m0; i += SOL_NT) {
                     double acc = 0.0;
                     const int e1 = w.csr_ptr[i + 1];
-                    for (int e = w.csr_ptr[i]; e < e1; ++e) acc += w.csr_val[e] * xs[w.csr_col[e]];
+                    if (w.dbg & MLD_DBG_WALKS_SERIAL) { for (int e = w.csr_ptr[i]; e < e1; ++e) acc += w.csr_val[e] * xs[w.csr_col[e]]; }
+                    else {
+                        glb_cu16 *rc = (glb_cu16 *)w.csr_col; glb_cf64 *rv = (glb_cf64 *)w.csr_val;
+                        for (int e = w.csr_ptr[i]; e < e1; e += WALK_GROUP) {
+                            int cj[WALK_GROUP]; double cg[WALK_GROUP], xv[WALK_GROUP];
+#pragma unroll
+                            for (int q = 0; q < WALK_GROUP; ++q) { const int eq = min(e + q, e1 - 1); cj[q] = rc[eq]; cg[q] = rv[eq]; }
+#pragma unroll
+                            for (int q = 0; q < WALK_GROUP; ++q) xv[q] = xs[cj[q]];
+#pragma unroll
+                            for (int q = 0; q < WALK_GROUP; ++q) if (e + q < e1) acc += cg[q] * xv[q];
+                        }
+                    }
                     worst = fmax(worst, acc - w.hs[i]);
                 }
             } else
@@ -3386,7 +3686,7 @@ __device__ __noinline__ bool s_leaf_eval(const Ws &w, Shared &sh, const SolverSh
 #pragma unroll
                 for (int q = 0; q < 4; ++q) rp[q] = Gg + (size_t)(i0 + q < S.m0 ? i0 + q : i0) * n;
                 double sv[4];
-                wave_rows_dot4(rp[0], rp[1], rp[2], rp[3], xs, n, lane, sv);
+                wave_rows_dot4(rp[0], rp[1], rp[2], rp[3], xs, n, lane, sv, (w.dbg & MLD_DBG_WALKS_SERIAL) != 0);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const double t = wave_sum(sv[q]);
@@ -3579,6 +3879,7 @@ __device__ __forceinline__ bool s_setup_entry(Ws &w, Shared &sh, const SolverSha
     w.Gs = P.Gs + (size_t)mdl * S.m0 * n; w.hs = B.hs + (size_t)isrc * S.m0;
     w.Gp = P.Gp ? P.Gp + (size_t)mdl * S.m0 * n : nullptr;
     w.csr_ptr = P.csr_ptr ? P.csr_ptr + (size_t)mdl * (S.m0 + 1) : nullptr; w.csr_col = P.csr_ptr ? P.csr_col + (size_t)mdl * P.nnz_cap : nullptr; w.csr_val = P.csr_ptr ? P.csr_val + (size_t)mdl * P.nnz_cap : nullptr;
+    w.csc_ptr = (P.csr_ptr && P.csc_ptr) ? P.csc_ptr + (size_t)mdl * (n + 1) : nullptr; w.csc_row = w.csc_ptr ? P.csc_row + (size_t)mdl * P.nnz_cap : nullptr;
     w.qs = B.qs_inst ? B.qs_inst + (size_t)isrc * n : P.qs + (size_t)mdl * n; w.cs = P.cs + (size_t)mdl * n;
     w.P = (S.qp && P.Ps) ? P.Ps + (size_t)mdl * n * n : nullptr;
     w.is_int = P.is_int; w.bins = P.bins; w.colperm = P.colperm;
@@ -3594,7 +3895,7 @@ __device__ __forceinline__ bool s_setup_entry(Ws &w, Shared &sh, const SolverSha
         for (int k = 0; k < 5; ++k) sh.pprof[k] = 0;
 #endif
 #ifdef MLD_CUT_PROF
-        for (int k = 0; k < 11; ++k) sh.cprof[k] = 0;
+        for (int k = 0; k < 15; ++k) sh.cprof[k] = 0;
 #endif
     }
     for (int j = tid; j < n; j += SOL_NT) { w.lo[j] = e.plb[j]; w.hi[j] = e.pub[j]; e.v_out[j] = 0.0; }
@@ -4128,6 +4429,9 @@ __device__ __forceinline__ void s_write_results(Shared &sh, const BatchDev &B, c
         if (B.prof_out && !skipped) { B.prof_out[(size_t)inst * 8 + 3] = sh.cprof[0]; B.prof_out[(size_t)inst * 8 + 4] = sh.cprof[1]; B.prof_out[(size_t)inst * 8 + 7] = sh.cprof[2]; }   // (diagnostic build: slots 3 / 4 / 7 = c-MIR scoring / c-MIR build / Gomory)
 #if MLD_CUT_PROF == 2
         if (B.prof_out && !skipped) for (int k = 0; k < 8; ++k) B.prof_out[(size_t)inst * 8 + k] = sh.cprof[3 + k];      // (the counts instead: scripts/gpu_cut_prof.py counts)
+#endif
+#if MLD_CUT_PROF == 3
+        if (B.prof_out && !skipped) { for (int k = 0; k < 4; ++k) B.prof_out[(size_t)inst * 8 + k] = sh.cprof[11 + k]; B.prof_out[(size_t)inst * 8 + 4] = sh.cprof[0]; B.prof_out[(size_t)inst * 8 + 5] = sh.prof[2]; }      // (phase A's sub-clocks, phase A, all cut separation: scripts/gpu_walks_prof.py)
 #endif
 #endif
     }
