@@ -56,6 +56,17 @@ typedef struct {
  * error ~1e-6 of the largest term) instead of fp64 (v_mfma_f64_16x16x4_f64).  Arrays at the boundary stay `double`; the
  * branch-and-cut itself always runs in fp64 and verifies every returned point against the original fp64 rows. */
 #define MLD_F32 1
+/* mld_opts.flags: small problems are solved by the LDS-resident wave-per-instance kernel (k_small_milp) instead of the dense-dictionary kernel.
+ * Fixed at mld_problem_create like MLD_F32 and composes with it (K3 may run in fp32, the solver stays fp64).  It takes effect when the
+ * problem is ELIGIBLE -- its dense dictionary with the per-basis state and the search stack fits the 16 KB of LDS a wave may use, e.g. the
+ * horizon-1 auxiliary problems of mld_sim_step_resolve --; on any other shape the problem is created normally and every solve takes the dense
+ * path.  A solve goes the small way when, in addition, the batch is not on the LDS-resident LP path, the cost is linear, the in-kernel
+ * hand-off is off, no cutoffs are set, open nodes are not recorded and time_limit == 0; a MIP start is ignored there (it is a hint), fixed
+ * binaries are honoured.  The kernel reads what the dense kernel reads and answers OPTIMAL or INFEASIBLE for the same scaled, tightened
+ * problem, or it DECLINES an instance (pivot or node budget spent, a pivot too small, a point that fails its own residual check, a free
+ * variable resting on the artificial box); declined instances are re-solved by the dense kernel in the same call, so NODE_LIMIT, NUMERICAL
+ * and UNBOUNDED are reported by it alone.  Default off.  mld_small_lds_stats tells which way the last solve went. */
+#define MLD_SMALL_LDS 2
 
 /* Solver options.  max_nodes / gap_rel / time-like limits mirror the Gurobi parameters the reference
  * forwards through **solver_kwargs (NodeLimit, MIPGap; micro_grid_control_simulation.py:232). */
@@ -77,7 +88,7 @@ typedef struct {
     int32_t n_slots;       /* solver slots = persistent workgroups (0 = auto: what is resident at once, one per CU) */
     int32_t mir_per_round; /* complemented mixed-integer rounding cuts on the original rows per cut round
                               (default -1 = 20 up to 400 binaries, binaries / 5 above; 0 = off) */
-    int32_t flags;         /* MLD_F32 (default 0, see below) */
+    int32_t flags;         /* MLD_F32 | MLD_SMALL_LDS (default 0, see above) */
     int32_t reserved;      /* diagnostics, default 0: the bits of mld_reserved_bit below */
     double time_limit;     /* seconds per INSTANCE on the device clock (Gurobi TimeLimit; the reference passes TimeLimit=20 with every solve,
                               examples/residential_mg_with_pv_and_dewhs/micro_grid_control_simulation.py:232, forwarded by
@@ -124,10 +135,12 @@ typedef enum {
     MLD_DBG_CUTS_R4 = 1 << 22,          /* the wave-per-cut Gomory and c-MIR rounds as round 4 built them: one slack row / eight dictionary rows of
                                            one column chunk in flight, generic pointers (A/B on the same binary of the grouped loads and the
                                            LDS-typed views: results are bit-identical, only speed changes) */
-    MLD_DBG_WALKS_SERIAL = 1 << 24      /* k_solve's phases outside the pivot loop with one load in flight, as before the grouped walks: the row
+    MLD_DBG_WALKS_SERIAL = 1 << 24,     /* k_solve's phases outside the pivot loop with one load in flight, as before the grouped walks: the row
                                            dot products of the refresh / residual check / leaf check, the thread-per-row walks over the sparse
                                            copy, the x_B update of a bound list and the row-wise screen of the c-MIR scoring (A/B on the same
                                            binary: results are bit-identical, only speed changes) */
+    MLD_DBG_SMALL_PIVOT_CAP = 1 << 25   /* k_small_milp (MLD_SMALL_LDS) with a pivot budget of 2: most instances decline and are re-solved by
+                                           the dense kernel, so that the overflow route runs on any shape (the MLD_DBG_LP_LDS_K24 idea) */
 } mld_reserved_bit;
 
 /* Linear cost in tiled horizon form (the Python layer parses the reference's string-keyed atoms,
@@ -328,6 +341,11 @@ int mld_download_open_nodes(mld_problem_t *, int32_t *depth_out, int16_t *var_ou
 int mld_set_std_block(mld_problem_t *, int enable);
 int mld_set_handoff(mld_problem_t *, int enable, int sub_nodes, int max_gen, int max_children, int max_tree, double room_factor);
 int mld_handoff_stats(mld_problem_t *, int64_t out[4]);
+/* The small-problem path (MLD_SMALL_LDS): out[0] 1 when the problem is eligible for it (flag set and the shape fits), out[1] instances the last
+ * solve answered in LDS, out[2] instances it declined and the dense kernel re-solved.  out[1] = out[2] = 0 after a solve that took the dense path
+ * or the LP path, and before the first solve.  MLD_ERR_NO_DEVICE without a device; MLD_ERR_INVALID for a null argument or while a launched
+ * solve has not been finished. */
+int mld_small_lds_stats(mld_problem_t *, int64_t out[3]);
 /* How a search that reaches its node limit splits (default 0, 0 = stop and publish everything it leaves open): with donate > 0 it hands off only its
  * `donate` SHALLOWEST open nodes -- the largest open subtrees -- and goes on below them with another sub_nodes nodes, up to `rounds` times, before it
  * stops for good: the deep open nodes, which the warm dictionary closes in a few pivots each, stay where they are cheap. */

@@ -18,6 +18,8 @@ EVO_NAMES = ("Phi_x", "Gamma_v", "Gamma_omega", "Gamma_5", "L_x", "L_v", "L_omeg
 STATUS_NAMES = {0: "optimal", 1: "infeasible", 2: "node_limit", 3: "numerical", 4: "unbounded"}
 COMM_ID_BYTES = 128
 MLD_F32 = 1
+MLD_SMALL_LDS = 2                      # mld_opts.flags: small problems in LDS, a wave per instance (k_small_milp)
+MLD_DBG_SMALL_PIVOT_CAP = 1 << 25      # mld_opts.reserved: k_small_milp with a pivot budget of 2 (its declined instances go to the dense kernel)
 MLD_SIM_ADVANCE, MLD_SIM_ACTUAL, MLD_SIM_LOG = 1, 2, 4      # flags of mld_sim_step_batch / mld_sim_step_resolve
 
 
@@ -53,7 +55,7 @@ EXPORTS = ("mld_device_count", "mld_set_device", "mld_last_error", "mld_version"
            "mld_opts_size", "mld_model_create", "mld_model_create_tv", "mld_model_destroy", "mld_condense_device", "mld_condense", "mld_condense_device_f32", "mld_condense_f32", "mld_opts_default",
            "mld_problem_create", "mld_problem_set_cost", "mld_problem_destroy", "mld_cost_assemble",
            "mld_solve_batch", "mld_upload_batch", "mld_upload_constraint_blocks", "mld_upload_constraint_blocks_x", "mld_solve_resident", "mld_problem_use_stream", "mld_solve_launch", "mld_solve_finish", "mld_download_results", "mld_download_telemetry",
-           "mld_rhs_batch", "mld_problem_set_opts", "mld_problem_get_opts", "mld_advance_batch", "mld_advance_batch2", "mld_set_warm_start", "mld_warm_start_from_previous", "mld_set_cutoffs", "mld_record_open_nodes", "mld_download_open_nodes", "mld_set_handoff", "mld_handoff_stats", "mld_set_handoff_policy", "mld_set_std_block", "mld_download_inputs", "mld_stage_inputs", "mld_select_inputs", "mld_upload_instance_cost", "mld_download_instance_cost", "mld_predict_batch", "mld_evaluate_batch", "mld_gather_results",
+           "mld_rhs_batch", "mld_problem_set_opts", "mld_problem_get_opts", "mld_advance_batch", "mld_advance_batch2", "mld_set_warm_start", "mld_warm_start_from_previous", "mld_set_cutoffs", "mld_record_open_nodes", "mld_download_open_nodes", "mld_set_handoff", "mld_handoff_stats", "mld_small_lds_stats", "mld_set_handoff_policy", "mld_set_std_block", "mld_download_inputs", "mld_stage_inputs", "mld_select_inputs", "mld_upload_instance_cost", "mld_download_instance_cost", "mld_predict_batch", "mld_evaluate_batch", "mld_gather_results",
            "mld_upload_profiles", "mld_forecast_from_profiles", "mld_constraint_blocks_from_profiles", "mld_evaluate_batch_profiles", "mld_download_constraint_blocks",
            "mld_sim_log_begin", "mld_sim_log_count", "mld_sim_step_batch", "mld_download_sim_log",
            "mld_sim_step_resolve", "mld_download_sim_log_aux",

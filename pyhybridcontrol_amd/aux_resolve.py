@@ -18,7 +18,7 @@ of the points the reference may return and makes the result deterministic.  No C
 """
 import numpy as np
 
-from . import gpu, host
+from . import _lib, gpu, host
 
 _AUX = ("delta", "z", "mu")
 _COLS = dict(u=("B1", "D1", "F1"), delta=("B2", "D2", "F2"), z=("B3", "D3", "F3"), mu=(None, None, "Psi"))
@@ -61,7 +61,8 @@ def fold_known(mats, dims, unknown):
 class AuxResolver(object):
     """GPU problem for one numeric MLD model and one set of unknown auxiliaries."""
 
-    def __init__(self, mats, dims, unknown=_AUX, **solver_opts):
+    def __init__(self, mats, dims, unknown=_AUX, small_lds=False, **solver_opts):
+        """small_lds=True: the instances are solved by the LDS-resident wave-per-instance kernel (flags |= MLD_SMALL_LDS; GpuProblem.small_lds_stats)"""
         self.dims = dict(dims)
         self.unknown = tuple(v for v in _AUX if v in unknown and dims["n" + v] > 0)
         self.mats2, self.dims2, self.known = fold_known(mats, dims, self.unknown)
@@ -71,6 +72,8 @@ class AuxResolver(object):
             atoms = {"q_mu": np.ones((self.dims2["nmu"], 1))} if self.dims2["nmu"] else {}
             opts = dict(gap_abs=1e-9, gap_rel=0.0, max_nodes=20000)
             opts.update(solver_opts)
+            if small_lds:
+                opts["flags"] = int(opts.get("flags", 0)) | _lib.MLD_SMALL_LDS
             self._model = gpu.GpuModel([self.mats2], self.dims2)
             self._problem = gpu.GpuProblem(self._model, 0, 1, host.cost_from_atoms(atoms, self.dims2, 0, 1), **opts)
 
@@ -123,7 +126,8 @@ class BatchAuxResolver(object):
     ControllerBase.sim_step_k passes to lsim_k.  It is the resolver handle of ``GpuProblem.sim_step(resolve=...)`` (mld_sim_step_resolve), which feeds it
     on the device; ``resolve`` is the host-fed route over the same handle.  Without auxiliaries (nv2 == 0) no handle is built: ``problem`` is None."""
 
-    def __init__(self, mats_list, dims, **solver_opts):
+    def __init__(self, mats_list, dims, small_lds=False, **solver_opts):
+        """small_lds=True: the instances are solved by the LDS-resident wave-per-instance kernel (flags |= MLD_SMALL_LDS; GpuProblem.small_lds_stats)"""
         if isinstance(mats_list, dict):
             mats_list = [mats_list]
         self.dims = dict(dims)
@@ -134,6 +138,8 @@ class BatchAuxResolver(object):
             atoms = {"q_mu": np.ones((self.dims2["nmu"], 1))} if self.dims2["nmu"] else {}
             opts = dict(gap_abs=1e-9, gap_rel=0.0, max_nodes=20000)
             opts.update(solver_opts)
+            if small_lds:
+                opts["flags"] = int(opts.get("flags", 0)) | _lib.MLD_SMALL_LDS
             self._model = gpu.GpuModel(self.mats2, self.dims2)
             self.problem = gpu.GpuProblem(self._model, 0, 1, host.cost_from_atoms(atoms, self.dims2, 0, 1), **opts)
 

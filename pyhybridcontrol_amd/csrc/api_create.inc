@@ -329,6 +329,21 @@ int mld_problem_create(mld_problem_t **out, mld_model_t *model, int N_p, int N_t
             }
         }
     }
+    // 3c. small-problem path (MLD_SMALL_LDS): eligible when the dictionary with its per-basis state and the search stack fits a wave's share of LDS
+    if ((p->opts.flags & MLD_SMALL_LDS) && m0 && n && sizeof(double) * sm_wave_doubles(n, m0, p->nb) <= SM_WAVE_BUDGET) {
+        SmShape &SS = p->SS;
+        SS.n = n; SS.m = m0; SS.ld = n | 1; SS.nb = p->nb; SS.nx = p->nx; SS.nW = p->nW;
+        SS.cp = 1; SS.cshift = 0;
+        while (SS.cp < 64 && SS.cp < n) { SS.cp <<= 1; SS.cshift++; }
+        SS.wave_doubles = (int)sm_wave_doubles(n, m0, p->nb);
+        p->small_lds_bytes = sizeof(double) * (size_t)SS.wave_doubles * SM_WAVES;
+        int dev = 0, per_cu = 0; hipDeviceProp_t prop;
+        (void)hipGetDevice(&dev); (void)hipGetDeviceProperties(&prop, dev);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_small_milp, SM_NT, p->small_lds_bytes) != hipSuccess || per_cu < 1) per_cu = 1;
+        p->small_slots = per_cu * prop.multiProcessorCount;
+        HIP_TRY(p->d_declined.alloc(1));
+        p->small_ok = true;
+    }
     // 4. cost (K4)
     if ((rc = set_cost_impl(p.get(), cost))) return rc;
     // 5. workspace: one dictionary per resident workgroup
@@ -386,7 +401,7 @@ int mld_problem_set_opts(mld_problem_t *p, const mld_opts *o)
     if (!p || !o) { mld_set_error("mld_problem_set_opts: bad arguments"); return MLD_ERR_INVALID; }
     /* limits and tolerances only: the workspace layout (max_cuts, n_slots) and the tightened model (presolve) stay.  Every check comes BEFORE the first
      * assignment: a refused call changes nothing (ADVICE r3). */
-    if (o->flags != p->opts.flags) { mld_set_error("mld_problem_set_opts: flags (MLD_F32) are fixed at mld_problem_create -- they decide how the cost is assembled"); return MLD_ERR_INVALID; }
+    if (o->flags != p->opts.flags) { mld_set_error("mld_problem_set_opts: flags (MLD_F32, MLD_SMALL_LDS) are fixed at mld_problem_create -- they decide how the cost is assembled and which solve paths exist"); return MLD_ERR_INVALID; }
     if (!(o->gap_abs >= 0.0) || !(o->gap_rel >= 0.0) || o->max_nodes < 1 || o->max_pivots < 1) { mld_set_error("mld_problem_set_opts: gaps must be >= 0, node / pivot limits >= 1"); return MLD_ERR_INVALID; }
     p->opts.gap_abs = o->gap_abs; p->opts.gap_rel = o->gap_rel; p->opts.max_nodes = o->max_nodes; p->opts.max_pivots = o->max_pivots;
     p->opts.reserved = o->reserved;

@@ -128,6 +128,45 @@ static int launch_lds_lp(mld_problem *p, std::vector<int> &redo)
     return MLD_OK;
 }
 
+static ProblemDev problem_dev(const mld_problem *p);
+static BatchDev batch_dev(const mld_problem *p, bool ho);
+static int launch_rhs_cost(mld_problem *p);
+
+/* Small-problem path (MLD_SMALL_LDS): the dense path's right-hand sides and cost, then k_small_milp, a wave per instance.  Runs to completion: the 4-byte
+ * counter of declined instances is read, and only when it is not zero the statuses -- redo lists the declined instances (status -1), for the dense kernel. */
+static int launch_small(mld_problem *p, std::vector<int> &redo)
+{
+    const hipStream_t sq = p->stream;
+    const int batch = p->batch;
+    if (int rc = launch_rhs_cost(p)) return rc;
+    HIP_TRY(hipEventRecord(p->ev[1], sq));
+    const ProblemDev P = problem_dev(p);
+    const BatchDev B = batch_dev(p, false);
+    SmShape SS = p->SS;
+    SS.max_nodes = p->opts.max_nodes; SS.gap_abs = p->opts.gap_abs; SS.gap_rel = p->opts.gap_rel;
+    SS.max_pivots = (p->opts.reserved & MLD_DBG_SMALL_PIVOT_CAP) ? 2 : p->opts.max_pivots;
+    HIP_TRY(hipMemsetAsync(p->d_declined, 0, sizeof(int), sq));
+    HIP_TRY(hipMemsetAsync(p->bat.cuts, 0, sizeof(int) * batch, sq));
+    HIP_TRY(hipMemsetAsync(p->bat.refac, 0, sizeof(int) * batch, sq));
+    HIP_TRY(hipMemsetAsync(p->bat.rows, 0, sizeof(long long) * batch, sq));
+    if (p->small_lds_bytes > 48 * 1024)
+        HIP_TRY(hipFuncSetAttribute((const void *)k_small_milp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->small_lds_bytes));
+    const int grid = std::min((batch + SM_WAVES - 1) / SM_WAVES, p->small_slots);
+    hipLaunchKernelGGL(k_small_milp, dim3(grid), dim3(SM_NT), p->small_lds_bytes, sq, SS, P, B, p->d_declined.get());
+    int declined = 0;
+    HIP_TRY(hipMemcpyAsync(&declined, p->d_declined, sizeof(int), hipMemcpyDeviceToHost, sq));
+    HIP_TRY(hipStreamSynchronize(sq));
+    HIP_TRY(hipGetLastError());
+    redo.clear();
+    if (declined) {
+        std::vector<int> stat(batch);
+        HIP_TRY(hipMemcpy(stat.data(), p->bat.status, sizeof(int) * batch, hipMemcpyDeviceToHost));
+        for (int i = 0; i < batch; ++i) if (stat[i] == -1) redo.push_back(i);
+    }
+    p->small_stats[0] = batch - (long long)redo.size(); p->small_stats[1] = (long long)redo.size();
+    return MLD_OK;
+}
+
 /* right-hand sides of the dense path (K3) with the extra constraint blocks, and the per-instance part of the cost (quadratic atoms, mld_upload_instance_cost) */
 static int launch_rhs_cost(mld_problem *p)
 {
@@ -215,21 +254,26 @@ static int launch(mld_problem *p)
     HIP_TRY(hipMemsetAsync(p->d_counter, 0, sizeof(int), sq));
     HIP_TRY(hipEventRecord(p->ev[0], sq));
     const bool lp_path = p->lp_ok && p->all_fixed && !(p->opts.reserved & MLD_DBG_NO_LP_LDS) && p->std_block && !p->has_quad && rhs_mfma_fits(p->nx, p->nW);
-    std::vector<int> redo;      /* LP path: the overflow instances, re-solved by k_solve */
+    /* small-problem path (MLD_SMALL_LDS): everything k_small_milp does not do stays with the dense kernel */
+    const bool small_path = p->small_ok && !lp_path && !p->has_quad && !p->ho_enable && !p->has_cutoff && !p->want_open && !(p->opts.time_limit > 0.0);
+    const bool lds_path = lp_path || small_path;      /* either way: runs to completion here, the dense kernel takes what it left (redo) */
+    p->small_stats[0] = p->small_stats[1] = 0;
+    std::vector<int> redo;      /* LDS paths: the overflow / declined instances, re-solved by k_solve */
     int rc;
     if (lp_path && (rc = launch_lds_lp(p, redo))) return rc;
-    if (lp_path && redo.empty()) {
+    if (small_path && (rc = launch_small(p, redo))) return rc;
+    if (lds_path && redo.empty()) {
         HIP_TRY(hipEventRecord(p->ev[2], sq));
     } else {
-        if (lp_path) HIP_TRY(hipMemsetAsync(p->d_counter, 0, sizeof(int), sq));
-        if ((rc = launch_rhs_cost(p))) return rc;
-        if (!lp_path) HIP_TRY(hipEventRecord(p->ev[1], sq));
+        if (lds_path) HIP_TRY(hipMemsetAsync(p->d_counter, 0, sizeof(int), sq));
+        if (!small_path && (rc = launch_rhs_cost(p))) return rc;      /* (the small path has run it: the same right-hand sides and cost) */
+        if (!lds_path) HIP_TRY(hipEventRecord(p->ev[1], sq));
         p->S.qp = p->has_quad ? 1 : 0;
-        const bool ho = p->ho_enable && p->bat.ho.tail && !lp_path && p->nb > 0;      /* (a quadratic cost included: items index qs_inst / rconst by their source instance, < batch) */
+        const bool ho = p->ho_enable && p->bat.ho.tail && !lds_path && p->nb > 0;      /* (a quadratic cost included: items index qs_inst / rconst by their source instance, < batch) */
         const ProblemDev P = problem_dev(p);
         BatchDev B = batch_dev(p, ho);
         if (ho && (rc = handoff_reset(p))) return rc;
-        if (lp_path) {      /* only the overflow instances of the LP path */
+        if (lds_path) {      /* only the overflow instances of the LP path / the instances the small path declined */
             HIP_TRY(hipMemcpy(p->bat.order, redo.data(), sizeof(int) * redo.size(), hipMemcpyHostToDevice));
             p->order_batch = 0;
             B.order = p->bat.order; B.batch = (int)redo.size();
@@ -242,7 +286,7 @@ static int launch(mld_problem *p)
         p->ho_ran = ho;
         HIP_TRY(hipEventRecord(p->ev[2], sq));
     }
-    if (!lp_path) { p->flight = Flight::queued; return MLD_OK; }
+    if (!lds_path) { p->flight = Flight::queued; return MLD_OK; }
     if ((rc = wait_solve(p))) return rc;
     p->flight = Flight::lds_done;      /* (mld_solve_finish only reports -- the handle stays in flight until then, like a queued dense solve) */
     return MLD_OK;
@@ -504,6 +548,14 @@ int mld_handoff_stats(mld_problem_t *p, int64_t out[4])
 {
     if (!p || !out) { mld_set_error("mld_handoff_stats: bad arguments"); return MLD_ERR_INVALID; }
     for (int k = 0; k < 4; ++k) out[k] = p->ho_stats[k];
+    return MLD_OK;
+}
+
+int mld_small_lds_stats(mld_problem_t *p, int64_t out[3])
+{
+    if (int rc = entry_guard(p, "mld_small_lds_stats", true, nullptr)) return rc;
+    if (!p || !out) { mld_set_error("mld_small_lds_stats: bad arguments"); return MLD_ERR_INVALID; }
+    out[0] = p->small_ok ? 1 : 0; out[1] = p->small_stats[0]; out[2] = p->small_stats[1];
     return MLD_OK;
 }
 

@@ -75,6 +75,9 @@ struct mld_problem {
     /* LDS-resident LP path (k_lp_lds): Toeplitz-compatible scaling of the tightened model */
     bool lp_ok = false, all_fixed = false; LpShape LS{}; size_t lp_lds_bytes = 0; int lp_slots = 0;
     DevBuf<double> d_blk_t, d_rs_t, d_cs_t, d_lb_t, d_ub_t, d_qs_t;
+    /* small-problem path (k_small_milp, MLD_SMALL_LDS): decided once in mld_problem_create; the device counter of the declined instances; what the last solve did */
+    bool small_ok = false; SmShape SS{}; size_t small_lds_bytes = 0; int small_slots = 0; DevBuf<int> d_declined;
+    long long small_stats[2] = {};   /* last solve: instances answered in LDS, instances the dense kernel re-solved */
     hipEvent_t ev[3] = {}; bool ev_ok = false; DevBuf<long long> d_statbuf;
     hipStream_t stream = 0; bool own_stream = false; Flight flight = Flight::idle;   /* stream of the solve path (0 = the legacy stream); a launched, not yet finished solve */
     bool std_block = true;      /* the standard constraint block (right-hand side from the batch's own omega) is part of the problem (mld_set_std_block) */

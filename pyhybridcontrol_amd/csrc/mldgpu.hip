@@ -211,6 +211,7 @@ int mld_condense_f32(mld_model_t *m, int N_tilde, int flags, float *Phi_x, float
 #include "mfma.inc"
 #include "inst_cost.inc"
 #include "lp_lds.inc"
+#include "small_lds.inc"       // k_small_milp: small MILPs in LDS, a wave per instance (MLD_SMALL_LDS)
 
 #include "tighten.inc"          // host big-M tightening (namespace tighten)
 #include "kernels.inc"          // small kernels: cost assembly, receding horizon, MIP start, fills, statistics, result packing

@@ -510,7 +510,7 @@ class GpuProblem(object):
             if k in ("max_cuts", "n_slots", "presolve") or not hasattr(new, k):
                 raise TypeError("option %r cannot be changed on an existing problem" % k)
             if k == "flags" and int(v) != int(self.opts.flags):
-                raise TypeError("flags (MLD_F32) are fixed when the problem is created")
+                raise TypeError("flags (MLD_F32, MLD_SMALL_LDS) are fixed when the problem is created")
             setattr(new, k, type(getattr(new, k))(v))
         check(_lib.load().mld_problem_set_opts(self._h, C.byref(new)))
         self.opts = new
@@ -818,6 +818,13 @@ class GpuProblem(object):
         out = (C.c_int64 * 4)()
         check(_lib.load().mld_handoff_stats(self._h, out))
         return dict(items=int(out[0]), given_up=int(out[1]), unfinished=int(out[2]), queue_full=int(out[3]))
+
+    def small_lds_stats(self):
+        """the small-problem path (flags=_lib.MLD_SMALL_LDS): eligible (the flag is set and the shape fits a wave's LDS), and of the last solve the
+        instances answered in LDS and the instances it declined, which the dense kernel re-solved (both 0 when the solve took another path)"""
+        out = (C.c_int64 * 3)()
+        check(_lib.load().mld_small_lds_stats(self._h, out))
+        return dict(eligible=bool(out[0]), lds=int(out[1]), dense=int(out[2]))
 
     def solve_handoff_device(self, x0, omega, model_idx=None, fixed_bin=None, first_nodes=None, sub_nodes=None, max_gen=8, max_children=64, max_tree=160, room_factor=0.0, donate=0, rounds=0, inst_cost=None, trajectories=False, quality=False,
                              omega_cols=None, col_rows=None, x_cols=None, col_start=None, col_step=0):
