@@ -567,6 +567,45 @@ int mld_sim_step_resolve(mld_problem_t *, mld_problem_t *aux, const double *u0, 
                          double *v0_out, int32_t *aux_status_out, int32_t *n_skipped_out);
 int mld_download_sim_log_aux(mld_problem_t *, int first, int count, int32_t *aux_status);
 
+/* ---- open-loop rollout of plans under realised disturbances ------------------------------------------------------------------------------------------
+ * The question a scenario-based controller asks after every solve: what does the hybrid plant do over the next K steps if this plan is applied and the
+ * disturbance turns out to be realisation c?  The reference answers with MldModel.lsim, or lsim_k in a loop (models/mld_model.py:543-642, 647-699), which
+ * calls _compute_aux (:701-766) -- one feasibility MIP -- per device, step and realisation.  mld_rollout_batch runs batch x S trajectories of K steps in
+ * ONE launch (k_rollout): a 64-lane wave per trajectory (instance b, realisation c), t = b S + c; per step the resolver's right-hand side, its auxiliary
+ * problem solved in the wave's LDS by the solver of MLD_SMALL_LDS (min sum(mu)), then x_{k+1}, y_k and the hard-constraint residuals with the sums of
+ * mld_sim_step_batch (fp64 on the ORIGINAL matrices, the Psi mu term zeroed, a NaN residual wins the maximum, ties to the lower row).
+ *
+ * aux         the resolver's handle of mld_sim_step_resolve (the folded models, N_tilde = 1), created with MLD_SMALL_LDS and eligible for that path; NULL is
+ *             required iff ndelta + nz + nmu == 0 (the rollout is then a plain lsim).  Only its per-model data is read; nothing on it changes.
+ * u_seq       (batch, K, nu), or NULL: the inputs of the resident plan (K <= N_tilde; needs a finished solve that has not been advanced); an instance
+ *             without a usable plan is not attempted.
+ * omega_seq   (batch, S, K, nomega) realised disturbances, or start (batch, S, n_groups) offsets into the resident profile library with the window rule
+ *             s >= 0, s + (step + K) width_g <= lib_len: exactly one of the two (neither when nomega == 0).
+ * cost_w      (cost_rows, K, nv) weights of cost = sum_k w_k . v_k, a row per model (cost_rows == n_models) or per instance (== batch), or NULL.
+ * Outputs     any may be NULL.  Per step: x_out (batch, S, K + 1, nx) with x_out[.., 0, :] = x0, v_out (batch, S, K, nv) = [u; delta; z; mu],
+ *             y_out (.., ny), cons_vio_out / cons_row_out (batch, S, K).  Per trajectory (batch, S): cost_out, mu_total_out = sum_k sum(mu_k), worst_vio_out
+ *             = the largest cons_vio over the steps (a NaN wins, the earliest step of equals) with worst_step_out, steps_done_out and end_status_out:
+ *                0  complete;
+ *                1  the auxiliary problem of step steps_done has no feasible point: that step and the later ones hold NaN / -1, as the reference returns
+ *                   NaN auxiliaries there (:757-763);
+ *                2  the LDS solver declined at step steps_done (pivot or node budget, a pivot too small ...): the state it stopped at is in
+ *                   x_out[.., steps_done, :], the rest NaN / -1 -- there is no dense fall-back in the kernel; finish such a trajectory stepwise
+ *                   (GpuProblem.rollout does, with the resolver's own solve);
+ *               -1  not attempted (u_seq == NULL and no usable plan): every output NaN / -1, steps_done 0.
+ *             The summaries of a trajectory that did not end 0 are NaN / -1.  stats: trajectories, then those that ended 0, 1 and 2.
+ * The call reads the handle's current x0 and writes nothing a solve reads: inputs, plan, MIP start, log and resident starts are unchanged (the what-if of
+ * mld_sim_step_batch without MLD_SIM_ADVANCE).  MLD_DBG_SMALL_PIVOT_CAP on the resolver's options caps the pivots as in a solve: every trajectory then
+ * ends 2 at step 0.  Host-synchronous.
+ * MLD_ERR_INVALID before anything is queued, nothing changed: no resident batch; a time-varying model; K < 1, S < 1; K > N_tilde, an unsolved or an
+ * advanced batch with u_seq == NULL; aux NULL / not NULL against the rule above, aux == the problem itself, with a launched solve, N_tilde != 1,
+ * time-varying, with the hand-off on, not the fold of this problem's models, not on the small-problem path (the message points to mld_sim_step_resolve),
+ * with a quadratic / per-instance cost or fixed binaries; a staging that does not fit; both or neither of omega_seq / start; no library or a start
+ * outside it; cost_rows that is neither n_models nor batch; a u_seq, omega_seq or cost_w that is not finite. */
+int mld_rollout_batch(mld_problem_t *p, mld_problem_t *aux, int K, int S, const double *u_seq, const double *omega_seq, const int64_t *start, int step,
+                      const double *cost_w, int cost_rows, double *x_out, double *v_out, double *y_out, double *cons_vio_out, int32_t *cons_row_out,
+                      double *cost_out, double *mu_total_out, double *worst_vio_out, int32_t *worst_step_out, int32_t *steps_done_out,
+                      int32_t *end_status_out, int64_t stats[4]);
+
 /* Per-instance telemetry of the last solve: time spent inside the solve kernel (device wall clock, ns) and
  * the number of dictionary rows the rank-1 updates touched (x *row_bytes x 2 = bytes streamed by pivots). */
 int mld_download_telemetry(mld_problem_t *, int64_t *latency_ns, int64_t *rows_updated, int64_t *row_bytes);

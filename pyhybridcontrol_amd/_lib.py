@@ -58,7 +58,7 @@ EXPORTS = ("mld_device_count", "mld_set_device", "mld_last_error", "mld_version"
            "mld_rhs_batch", "mld_problem_set_opts", "mld_problem_get_opts", "mld_advance_batch", "mld_advance_batch2", "mld_set_warm_start", "mld_warm_start_from_previous", "mld_set_cutoffs", "mld_record_open_nodes", "mld_download_open_nodes", "mld_set_handoff", "mld_handoff_stats", "mld_small_lds_stats", "mld_set_handoff_policy", "mld_set_std_block", "mld_download_inputs", "mld_stage_inputs", "mld_select_inputs", "mld_upload_instance_cost", "mld_download_instance_cost", "mld_predict_batch", "mld_evaluate_batch", "mld_gather_results",
            "mld_upload_profiles", "mld_forecast_from_profiles", "mld_constraint_blocks_from_profiles", "mld_evaluate_batch_profiles", "mld_download_constraint_blocks",
            "mld_sim_log_begin", "mld_sim_log_count", "mld_sim_step_batch", "mld_download_sim_log",
-           "mld_sim_step_resolve", "mld_download_sim_log_aux",
+           "mld_sim_step_resolve", "mld_download_sim_log_aux", "mld_rollout_batch",
            "mld_comm_unique_id", "mld_comm_init", "mld_gather", "mld_comm_destroy")
 
 
@@ -92,6 +92,7 @@ def load():
     lib.mld_download_sim_log.argtypes = [C.c_void_p, C.c_int, C.c_int, dp, dp, dp, dp, dp, bp, dp, ip, dp, dp, ip, ip]
     lib.mld_sim_step_resolve.argtypes = [C.c_void_p, C.c_void_p, dp, lp, C.c_int, C.c_int, dp, dp, bp, dp, ip, dp, ip, ip]
     lib.mld_download_sim_log_aux.argtypes = [C.c_void_p, C.c_int, C.c_int, ip]
+    lib.mld_rollout_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, dp, dp, lp, C.c_int, dp, C.c_int, dp, dp, dp, dp, ip, dp, dp, dp, ip, ip, ip, lp]
     if int(lib.mld_opts_size()) != C.sizeof(Opts):
         raise MldGpuError("libmldgpu.so was built with another layout of mld_opts (%d bytes, this binding %d): rebuild it (python -m pyhybridcontrol_amd.build)"
                           % (lib.mld_opts_size(), C.sizeof(Opts)))

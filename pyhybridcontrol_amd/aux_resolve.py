@@ -131,6 +131,7 @@ class BatchAuxResolver(object):
         if isinstance(mats_list, dict):
             mats_list = [mats_list]
         self.dims = dict(dims)
+        self.mats = list(mats_list)      # the models themselves: GpuProblem.rollout finishes what the device declined with simlog.lsim_k_batch on them
         self.mats2, self.dims2 = fold_models(mats_list, dims)
         self.nv2 = self.dims2["ndelta"] + self.dims2["nz"] + self.dims2["nmu"]
         self._model = self.problem = None

@@ -1,0 +1,165 @@
+// Open-loop rollout of the resident batch's plans under realised disturbances (mld_rollout_batch, kernel k_rollout in rollout.inc).
+extern "C" {
+
+/* The a-posteriori step of a scenario-based controller: what the hybrid plant does over the next K steps if the plan's (or the caller's) inputs are applied
+ * and the disturbance turns out to be realisation c -- the reference's MldModel.lsim / lsim_k in a loop (models/mld_model.py:543-642, 647-699) with
+ * _compute_aux (:701-766) at every step, for batch x S trajectories in ONE launch.  Everything is tested on the host before anything is queued; the call
+ * reads p's current x0 and writes nothing a solve reads -- inputs, plan, MIP start, log and resident starts stay (the what-if of mld_sim_step_*) -- and
+ * nothing on the resolver's handle: the kernel reads the resolver's per-model data only.  Host-synchronous. */
+int mld_rollout_batch(mld_problem_t *p, mld_problem_t *aux, int K, int S, const double *u_seq, const double *omega_seq, const int64_t *start, int step,
+                      const double *cost_w, int cost_rows, double *x_out, double *v_out, double *y_out, double *cons_vio_out, int32_t *cons_row_out,
+                      double *cost_out, double *mu_total_out, double *worst_vio_out, int32_t *worst_step_out, int32_t *steps_done_out, int32_t *end_status_out,
+                      int64_t stats[4])
+{
+    static const char who[] = "mld_rollout_batch";
+    if (int rc = entry_guard(p, who, true, "no batch resident (mld_upload_batch)")) return rc;
+    mld_model *mo = p->model;
+    const mld_dims &d = mo->dims;
+    const int batch = p->batch, nx = d.nx, nu = d.nu, nw = d.nomega, nv = p->nv, ny = d.ny, nv2 = d.ndelta + d.nz + d.nmu;
+    if (mo->tv_N > 0) { mld_set_error("%s: time-varying models (mld_model_create_tv) are not rolled out on the device -- the step models would have to shift with the horizon", who); return MLD_ERR_INVALID; }
+    if (!mo->d_pack) { mld_set_error("%s: model without matrices", who); return MLD_ERR_INVALID; }
+    if (K < 1 || S < 1) { mld_set_error("%s: K = %d, S = %d (at least one step and one realisation)", who, K, S); return MLD_ERR_INVALID; }
+    if ((long long)batch * S > INT_MAX) { mld_set_error("%s: batch x S = %lld trajectories (at most %d)", who, (long long)batch * S, INT_MAX); return MLD_ERR_INVALID; }
+    if (step < 0 || step > INT_MAX - K) { mld_set_error("%s: step = %d (must be >= 0)", who, step); return MLD_ERR_INVALID; }
+    if (!nv2 && aux) { mld_set_error("%s: the model has no auxiliaries (ndelta + nz + nmu = 0), so there is nothing to resolve: aux must be NULL", who); return MLD_ERR_INVALID; }
+    if (nv2 && !aux) { mld_set_error("%s: aux == NULL, but the model has %d auxiliaries to resolve (ndelta + nz + nmu)", who, nv2); return MLD_ERR_INVALID; }
+    if (aux) {      /* the dimension test of mld_sim_step_resolve */
+        if (aux == p) { mld_set_error("%s: aux is the rolled-out problem itself (the resolver is a handle of its own: the folded models at N_tilde = 1)", who); return MLD_ERR_INVALID; }
+        if (aux->flight != Flight::idle) { mld_set_error("%s: aux has a launched solve that has not been finished (mld_solve_finish)", who); return MLD_ERR_INVALID; }
+        if (aux->N != 1) { mld_set_error("%s: aux has N_tilde = %d (the auxiliary problem is the horizon-1 instance: N_tilde = 1)", who, aux->N); return MLD_ERR_INVALID; }
+        if (aux->model->tv_N > 0) { mld_set_error("%s: aux is time-varying (mld_model_create_tv)", who); return MLD_ERR_INVALID; }
+        if (aux->ho_enable) { mld_set_error("%s: aux has the in-kernel hand-off on (mld_set_handoff)", who); return MLD_ERR_INVALID; }
+        const mld_dims &e = aux->model->dims;
+        if (e.nx != nx || e.nc != d.nc || e.ndelta != d.ndelta || e.nz != d.nz || e.nmu != d.nmu || aux->n_models != p->n_models || e.nu != 0 || e.nomega != nw + nu) {
+            mld_set_error("%s: aux is not the fold of this problem's models: nx %d/%d nc %d/%d ndelta %d/%d nz %d/%d nmu %d/%d n_models %d/%d (aux/problem), nu %d (0), nomega %d (nomega + nu = %d)",
+                          who, e.nx, nx, e.nc, d.nc, e.ndelta, d.ndelta, e.nz, d.nz, e.nmu, d.nmu, aux->n_models, p->n_models, e.nu, e.nomega, nw + nu);
+            return MLD_ERR_INVALID;
+        }
+        if (!aux->small_ok) {
+            mld_set_error("%s: aux is not on the small-problem path (%s): the rollout solves its auxiliary problems in LDS and has no dense fall-back -- create the resolver with MLD_SMALL_LDS, or step with mld_sim_step_resolve",
+                          who, (aux->opts.flags & MLD_SMALL_LDS) ? "its shape does not fit a wave's share of LDS" : "MLD_SMALL_LDS is not set");
+            return MLD_ERR_INVALID;
+        }
+        if (aux->has_quad || aux->ic_ld || aux->has_fixed) { mld_set_error("%s: aux has a quadratic or per-instance cost, or fixed binaries (the rollout minimises the resolver's model cost, sum(mu), with every binary free)", who); return MLD_ERR_INVALID; }
+    }
+    const size_t stage_d = ro_stage_doubles(nx, nu, nw, aux ? aux->m0 : 0, nv, ny);
+    if (sizeof(double) * stage_d > SM_WAVE_BUDGET) {
+        mld_set_error("%s: the staging of a trajectory (%zu bytes: x, omega', h, v, y, x_k1) does not fit a wave's share of LDS (%d bytes); step with mld_sim_step_resolve", who, sizeof(double) * stage_d, SM_WAVE_BUDGET);
+        return MLD_ERR_INVALID;
+    }
+    if (!u_seq) {      /* the plan-state tests of sim_step_check */
+        if (K > p->N) { mld_set_error("%s: K = %d steps with the resident plan's inputs, but the plan has N_tilde = %d (pass u_seq for a longer rollout)", who, K, p->N); return MLD_ERR_INVALID; }
+        if (!p->solved) { mld_set_error("%s: the resident batch has not been solved since its upload / selection (there is no plan to apply; pass u_seq)", who); return MLD_ERR_INVALID; }
+        if (p->advanced) { mld_set_error("%s: the last solve's plan has already been applied -- the resident plan belongs to inputs that are gone (solve again, or pass u_seq)", who); return MLD_ERR_INVALID; }
+    }
+    if (nw) {
+        if ((omega_seq != nullptr) == (start != nullptr)) { mld_set_error("%s: exactly one of omega_seq and start must be given (%s)", who, omega_seq ? "both are" : "neither is"); return MLD_ERR_INVALID; }
+    } else if (start) { mld_set_error("%s: start given, but the model has no disturbance (nomega = 0)", who); return MLD_ERR_INVALID; }
+    if (cost_w && cost_rows != p->n_models && cost_rows != batch) { mld_set_error("%s: cost_rows = %d (n_models = %d or batch = %d)", who, cost_rows, p->n_models, batch); return MLD_ERR_INVALID; }
+    std::vector<long long> gmax;
+    if (start) {
+        if (!p->pf_len) { mld_set_error("%s: start given, but no profile library is resident (mld_upload_profiles)", who); return MLD_ERR_INVALID; }
+        if (int rc = profile_check_starts(p, who, PF_WINDOW, start, batch, S, step, K, gmax)) return rc;
+    }
+    const size_t T = (size_t)batch * S;
+    if (u_seq) for (size_t k = 0; k < (size_t)batch * K * nu; ++k) if (!std::isfinite(u_seq[k])) {
+        mld_set_error("%s: u_seq of instance %zu, step %zu, input %zu is not finite (%g)", who, k / ((size_t)K * nu), k / nu % K, k % nu, u_seq[k]); return MLD_ERR_INVALID;
+    }
+    if (omega_seq && nw) for (size_t k = 0; k < T * K * nw; ++k) if (!std::isfinite(omega_seq[k])) {
+        mld_set_error("%s: omega_seq of trajectory %zu, step %zu, channel %zu is not finite (%g)", who, k / ((size_t)K * nw), k / nw % K, k % nw, omega_seq[k]); return MLD_ERR_INVALID;
+    }
+    const bool cw_inst = cost_w && cost_rows != p->n_models;      /* (batch == n_models: a row per model) */
+    if (cost_w) for (size_t k = 0; k < (size_t)cost_rows * K * nv; ++k) if (!std::isfinite(cost_w[k])) {
+        mld_set_error("%s: cost_w of row %zu, step %zu, entry %zu is not finite (%g)", who, k / ((size_t)K * nv), k / nv % K, k % nv, cost_w[k]); return MLD_ERR_INVALID;
+    }
+
+    SmShape SS{};
+    size_t wave_d = 0;
+    if (aux) {
+        SS = aux->SS;
+        SS.max_nodes = aux->opts.max_nodes; SS.gap_abs = aux->opts.gap_abs; SS.gap_rel = aux->opts.gap_rel;
+        SS.max_pivots = (aux->opts.reserved & MLD_DBG_SMALL_PIVOT_CAP) ? 2 : aux->opts.max_pivots;
+        wave_d = (size_t)SS.wave_doubles;
+    }
+    const size_t lds_bytes = sizeof(double) * (wave_d + stage_d) * SM_WAVES;
+    const hipStream_t sq = p->stream;
+    const size_t Kz = (size_t)K;
+    DevBuf<double> d_u, d_om, d_cw, d_x, d_v, d_y, d_vio, d_cost, d_mu, d_wv; DevBuf<int> d_row, d_ws, d_sd, d_es; DevBuf<long long> d_start; DevBuf<unsigned long long> d_cnt;
+    if (u_seq) HIP_TRY(d_u.alloc(std::max<size_t>(1, (size_t)batch * Kz * nu)));
+    HIP_TRY(d_om.alloc(std::max<size_t>(1, T * Kz * nw)));
+    if (start) HIP_TRY(d_start.alloc(T * p->pf_groups));
+    if (cost_w) HIP_TRY(d_cw.alloc(std::max<size_t>(1, (size_t)cost_rows * Kz * nv)));
+    if (x_out && nx) HIP_TRY(d_x.alloc(T * (Kz + 1) * nx));
+    if (v_out && nv) HIP_TRY(d_v.alloc(T * Kz * nv));
+    if (y_out && ny) HIP_TRY(d_y.alloc(T * Kz * ny));
+    if (cons_vio_out) HIP_TRY(d_vio.alloc(T * Kz));
+    if (cons_row_out) HIP_TRY(d_row.alloc(T * Kz));
+    if (cost_out) HIP_TRY(d_cost.alloc(T));
+    if (mu_total_out) HIP_TRY(d_mu.alloc(T));
+    if (worst_vio_out) HIP_TRY(d_wv.alloc(T));
+    if (worst_step_out) HIP_TRY(d_ws.alloc(T));
+    if (steps_done_out) HIP_TRY(d_sd.alloc(T));
+    if (end_status_out) HIP_TRY(d_es.alloc(T));
+    HIP_TRY(d_cnt.alloc(4));
+    RoDev a{};
+    a.batch = batch; a.S = S; a.K = K;
+    a.nx = nx; a.nu = nu; a.nw = nw; a.nv = nv; a.nmu = d.nmu; a.ny = ny; a.nc = d.nc; a.m = aux ? aux->m0 : 0; a.n = aux ? aux->n : 0;
+    a.stage_doubles = (int)stage_d;
+    a.pack = mo->d_pack; a.pack_len = mo->pack_len;
+    {
+        const PackOff &o = mo->pack_off;
+        a.oA = o.A; a.oB4 = o.B4; a.ob5 = o.b5; a.oC = o.C; a.oD4 = o.D4; a.od5 = o.d5; a.oE = o.E; a.oF4 = o.F4; a.of5 = o.f5; a.oG = o.G;
+        a.oBv = o.Bv; a.oDv = o.Dv; a.oFv = o.Fv;
+    }
+    a.model_idx = p->has_midx ? p->bat.model_idx.get() : nullptr;
+    a.x0 = p->bat.x0;
+    if (u_seq) { a.u = d_u; a.u_stride = Kz * nu; a.u_step = (size_t)nu; }
+    else { a.u = p->bat.v; a.u_stride = (size_t)p->n; a.u_step = (size_t)nv; a.status = p->bat.status; a.obj = p->bat.obj; }      /* rows < batch are the instances' (after the hand-off's device merge) */
+    a.om = d_om;
+    a.cw = cost_w ? d_cw.get() : nullptr; a.cw_by_inst = cw_inst ? 1 : 0;
+    a.x = d_x; a.v = d_v; a.y = d_y; a.vio = d_vio; a.row = d_row;
+    a.cost = d_cost; a.mu_total = d_mu; a.worst_vio = d_wv; a.worst_step = d_ws; a.steps_done = d_sd; a.end_status = d_es;
+    a.counter = d_cnt;
+    ProblemDev P{};
+    if (aux) P = problem_dev(aux);
+    if (lds_bytes > 48 * 1024)
+        HIP_TRY(hipFuncSetAttribute((const void *)k_rollout, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    int dev = 0, per_cu = 0; hipDeviceProp_t prop;
+    (void)hipGetDevice(&dev); HIP_TRY(hipGetDeviceProperties(&prop, dev));
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_rollout, SM_NT, lds_bytes) != hipSuccess || per_cu < 1) per_cu = 1;
+    const int grid = (int)std::min<size_t>((T + SM_WAVES - 1) / SM_WAVES, (size_t)per_cu * prop.multiProcessorCount);
+    unsigned long long cnt[4] = {};
+    /* everything queued on the stream and waited for on every path (queue_and_wait): the caller's arrays and the temporaries may go when this returns */
+    auto queue = [&]() -> int {
+        HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(cnt), sq));
+        if (u_seq && nu) HIP_TRY(hipMemcpyAsync(d_u, u_seq, sizeof(double) * (size_t)batch * Kz * nu, hipMemcpyHostToDevice, sq));
+        if (cost_w && nv) HIP_TRY(hipMemcpyAsync(d_cw, cost_w, sizeof(double) * (size_t)cost_rows * Kz * nv, hipMemcpyHostToDevice, sq));
+        if (omega_seq && nw) HIP_TRY(hipMemcpyAsync(d_om, omega_seq, sizeof(double) * T * Kz * nw, hipMemcpyHostToDevice, sq));
+        if (start) {      /* the windows of K steps gathered into the buffer omega_seq would be uploaded to: one input layout for the kernel */
+            HIP_TRY(hipMemcpyAsync(d_start, start, sizeof(long long) * T * p->pf_groups, hipMemcpyHostToDevice, sq));
+            hipLaunchKernelGGL(k_profile_windows, dim3(profile_grid((long long)T * K * nw)), dim3(256), 0, sq, (int)T, K * nw, nw, S, S, 0, p->pf_groups, d_start.get(),
+                               p->pf_chan.get(), step, p->pf_lib.get(), d_om.get());
+            HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_rollout, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a);
+        HIP_TRY(hipGetLastError());
+        if (d_x) HIP_TRY(hipMemcpyAsync(x_out, d_x, sizeof(double) * T * (Kz + 1) * nx, hipMemcpyDeviceToHost, sq));
+        if (d_v) HIP_TRY(hipMemcpyAsync(v_out, d_v, sizeof(double) * T * Kz * nv, hipMemcpyDeviceToHost, sq));
+        if (d_y) HIP_TRY(hipMemcpyAsync(y_out, d_y, sizeof(double) * T * Kz * ny, hipMemcpyDeviceToHost, sq));
+        if (d_vio) HIP_TRY(hipMemcpyAsync(cons_vio_out, d_vio, sizeof(double) * T * Kz, hipMemcpyDeviceToHost, sq));
+        if (d_row) HIP_TRY(hipMemcpyAsync(cons_row_out, d_row, sizeof(int) * T * Kz, hipMemcpyDeviceToHost, sq));
+        if (d_cost) HIP_TRY(hipMemcpyAsync(cost_out, d_cost, sizeof(double) * T, hipMemcpyDeviceToHost, sq));
+        if (d_mu) HIP_TRY(hipMemcpyAsync(mu_total_out, d_mu, sizeof(double) * T, hipMemcpyDeviceToHost, sq));
+        if (d_wv) HIP_TRY(hipMemcpyAsync(worst_vio_out, d_wv, sizeof(double) * T, hipMemcpyDeviceToHost, sq));
+        if (d_ws) HIP_TRY(hipMemcpyAsync(worst_step_out, d_ws, sizeof(int) * T, hipMemcpyDeviceToHost, sq));
+        if (d_sd) HIP_TRY(hipMemcpyAsync(steps_done_out, d_sd, sizeof(int) * T, hipMemcpyDeviceToHost, sq));
+        if (d_es) HIP_TRY(hipMemcpyAsync(end_status_out, d_es, sizeof(int) * T, hipMemcpyDeviceToHost, sq));
+        HIP_TRY(hipMemcpyAsync(cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, sq));
+        return MLD_OK;
+    };
+    if (int rc = queue_and_wait(sq, queue)) return rc;
+    if (stats) { stats[0] = (int64_t)T; stats[1] = (int64_t)cnt[1]; stats[2] = (int64_t)cnt[2]; stats[3] = (int64_t)cnt[3]; }
+    return MLD_OK;
+}
+
+} // extern "C"

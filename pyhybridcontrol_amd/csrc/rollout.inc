@@ -1,0 +1,226 @@
+// k_rollout: open-loop rollout of plans under realised disturbances (mld_rollout_batch) -- the reference's MldModel.lsim, or lsim_k in a loop
+// (models/mld_model.py:543-642, 647-699), with _compute_aux (:701-766) re-deriving delta, z, mu at every step: what the hybrid plant does over the next K
+// steps when the inputs u_0 .. u_{K-1} are applied and the disturbance turns out to be realisation c.  A trajectory is (instance b, realisation c),
+// t = b S + c; per step k
+//     omega' = [omega_k; u_k],  h_i = rs_i (Hx[i,:] x + Hw[i,:] omega' + H5[i])          the resolver's right-hand side (K3 up to summation order)
+//     sm_solve on the resolver's scaled, tightened rows with h: min sum(mu)                (small_lds.inc, unchanged)
+//     v_k = [u_k; delta; z; mu],  x_{k+1}, y_k, r with the sums of k_sim_step              (sim_step.inc, term for term)
+// and x never leaves the wave.  The state, omega', h, v_k, y and the next state are staged in the wave's LDS behind the solver's region:
+//     [x (nx) | omega' (nomega + nu) | h (m) | v_k (nv) | y (ny) | x_{k+1} (nx)]
+// (the last block because a lane's rows of x_{k+1} are ready while other lanes still read x).
+//
+// Mapping: one 64-lane wave per trajectory, SM_WAVES per workgroup, trajectories claimed from an atomic counter exactly as k_small_milp claims instances
+// (every lane takes part behind sm_sync(), no lane-dependent branch between the write-out and the broadcast); the waves share nothing and the kernel holds
+// no __syncthreads.  All arithmetic is fp64 on the ORIGINAL matrices of mld_model::d_pack and the resolver's fp64 maps, also on an MLD_F32 handle.  No
+// dimension is a compile-time constant: rows and columns are looped lane, lane + 64, ...  Every store is lane-contiguous.
+//
+// The per-trajectory core ro_run compiles for the host as sm_solve does (SM_HOST: a "wave" is one lane, the staging plain memory).
+#pragma once
+
+#include "small_lds.inc"
+
+struct RoModel {      // one trajectory's model: the step matrices inside the packed block, the resolver's maps and row scales
+    int nx, nu, nw, nv, nmu, ny, nc;
+    int m, n;                                                              // the resolver's rows and unknowns (n = ndelta + nz + nmu; 0: nothing to resolve)
+    const double *A, *B4, *b5, *C, *D4, *d5, *E, *F4, *f5, *G, *Bv, *Dv, *Fv;
+    const double *Hx, *Hw, *H5, *rs;                                       // m x nx, m x (nw + nu), m, m
+};
+struct RoTraj {       // one trajectory's inputs and outputs (any output may be null)
+    int K;
+    const double *x0;                                                      // nx
+    const double *u; size_t u_step;                                        // u_k = u + k u_step
+    const double *om;                                                      // K x nw
+    const double *cw;                                                      // K x nv or null
+    double *x, *v, *y, *vio; int *row;                                     // (K + 1) x nx, K x nv, K x ny, K, K
+};
+struct RoResult { double cost, mu_total, worst_vio; int worst_step, worst_row, steps_done, end_status; };
+enum { RO_COMPLETE = 0, RO_INFEASIBLE = 1, RO_DECLINED = 2, RO_NOT_ATTEMPTED = -1 };
+
+// doubles of staging behind the solver's region (even, so that the next wave's region stays 16-byte aligned)
+static inline size_t ro_stage_doubles(int nx, int nu, int nw, int m, int nv, int ny)
+{
+    return ((size_t)2 * nx + nw + nu + m + nv + ny + 1) & ~(size_t)1;
+}
+
+// everything after step `from` of a trajectory that stopped there: NaN / -1
+SM_FN void ro_blank(const RoModel &M, const RoTraj &T, int lane, int from, bool with_state)
+{
+    const double qnan = __builtin_nan("");
+    const size_t left = (size_t)(T.K - from);
+    if (T.x) { const size_t o = (size_t)(with_state ? from : from + 1) * M.nx; for (size_t e = lane; e < (size_t)(T.K + 1) * M.nx - o; e += SM_W) T.x[o + e] = qnan; }
+    if (T.v) for (size_t e = lane; e < left * M.nv; e += SM_W) T.v[(size_t)from * M.nv + e] = qnan;
+    if (T.y) for (size_t e = lane; e < left * M.ny; e += SM_W) T.y[(size_t)from * M.ny + e] = qnan;
+    if (T.vio) for (size_t e = lane; e < left; e += SM_W) T.vio[from + e] = qnan;
+    if (T.row) for (size_t e = lane; e < left; e += SM_W) T.row[from + e] = -1;
+}
+
+// One trajectory, start to finish.  mem: the solver's region (S.wave_doubles doubles), stg: the staging (ro_stage_doubles); A: the resolver's model
+// (G, q, lb, ub, cs, is_int, bins), its h / v_out / fixed are set here.
+SM_FN void ro_run(const SmShape &S, const RoModel &M, sm_f64 *mem, sm_f64 *stg, SmArgs A, const RoTraj &T, int lane, RoResult &R)
+{
+    const int nx = M.nx, nu = M.nu, nw = M.nw, nv = M.nv, ny = M.ny, nc = M.nc, m = M.m, nw2 = M.nw + M.nu, nf = M.nv - M.nmu;
+    sm_f64 *xs = stg, *ws = xs + nx, *hs = ws + nw2, *vs = hs + m, *ys = vs + nv, *xn = ys + ny;
+    const double qnan = __builtin_nan("");
+    A.h = (const double *)hs; A.v_out = (double *)(vs + nu); A.fixed = nullptr;
+    for (int j = lane; j < nx; j += SM_W) { const double t = T.x0[j]; xs[j] = t; if (T.x) T.x[j] = t; }
+    double cost = 0.0, mu_total = 0.0, worst = -S_INF;
+    int wstep = -1, wrow = -1, end = RO_COMPLETE, k = 0;
+    for (; k < T.K; ++k) {
+        // ---- 1. the step's inputs
+        const double *uk = T.u + (size_t)k * T.u_step, *wk = T.om + (size_t)k * nw;
+        sm_sync();
+        for (int j = lane; j < nw; j += SM_W) ws[j] = wk[j];
+        for (int j = lane; j < nu; j += SM_W) { const double t = uk[j]; ws[nw + j] = t; vs[j] = t; }
+        sm_sync();
+        if (M.n) {
+            // ---- 2. the resolver's right-hand side: lanes on rows, j ascending
+            for (int i = lane; i < m; i += SM_W) {
+                double s = 0.0;
+                for (int j = 0; j < nx; ++j) s += M.Hx[(size_t)i * nx + j] * xs[j];
+                for (int j = 0; j < nw2; ++j) s += M.Hw[(size_t)i * nw2 + j] * ws[j];
+                s += M.H5[i];
+                hs[i] = M.rs[i] * s;
+            }
+            sm_sync();
+            // ---- 3. delta, z, mu of least total slack
+            SmResult res;
+            sm_solve(S, mem, A, lane, res);
+            sm_sync();
+            if (res.status != MLD_STATUS_OPTIMAL) { end = res.status == MLD_STATUS_INFEASIBLE ? RO_INFEASIBLE : RO_DECLINED; break; }
+        }
+        // ---- 4. x_{k+1}, y_k and the residuals: the sums of k_sim_step (sim_step.inc, "state and output rows" and "constraint rows"), term for term
+        for (int i = lane; i < nx; i += SM_W) {
+            double s = M.b5[i];
+            for (int j = 0; j < nx; ++j) s += M.A[(size_t)i * nx + j] * xs[j];
+            for (int j = 0; j < nv; ++j) s += M.Bv[(size_t)i * nv + j] * vs[j];
+            for (int j = 0; j < nw; ++j) s += M.B4[(size_t)i * nw + j] * ws[j];
+            xn[i] = s;
+        }
+        for (int i = lane; i < ny; i += SM_W) {
+            double s = M.d5[i];
+            for (int j = 0; j < nx; ++j) s += M.C[(size_t)i * nx + j] * xs[j];
+            for (int j = 0; j < nv; ++j) s += M.Dv[(size_t)i * nv + j] * vs[j];
+            for (int j = 0; j < nw; ++j) s += M.D4[(size_t)i * nw + j] * ws[j];
+            ys[i] = s;
+            if (T.y) T.y[(size_t)k * ny + i] = s;
+        }
+        sm_sync();
+        double best = -S_INF; int brow = -1;
+        for (int i = lane; i < nc; i += SM_W) {
+            double s = 0.0;
+            for (int j = 0; j < nx; ++j) s += M.E[(size_t)i * nx + j] * xs[j];
+            for (int j = 0; j < nf; ++j) s += M.Fv[(size_t)i * nv + j] * vs[j];      /* (the Psi columns, the last nmu of a row, are skipped) */
+            for (int j = 0; j < nw; ++j) s += M.F4[(size_t)i * nw + j] * ws[j];
+            for (int j = 0; j < ny; ++j) s += M.G[(size_t)i * ny + j] * ys[j];
+            s -= M.f5[i];
+            const bool s_nan = s != s, b_nan = best != best;
+            if (brow < 0 || (!b_nan && (s_nan || s > best))) { best = s; brow = i; }      /* rows ascend: the first of equals stays */
+        }
+        for (int off = SM_W / 2; off; off >>= 1) {      /* a NaN residual wins the maximum, ties go to the lower row (k_sim_step's reduction) */
+            const double ob = sm_xor_f64(best, off); const int orow = sm_xor_i32(brow, off);
+            const bool o_nan = ob != ob, m_nan = best != best;
+            bool take;
+            if (orow < 0) take = false;
+            else if (brow < 0) take = true;
+            else if (o_nan || m_nan) take = o_nan && (!m_nan || orow < brow);
+            else take = ob > best || (ob == best && orow < brow);
+            if (take) { best = ob; brow = orow; }
+        }
+        brow = sm_uniform(brow);
+        // ---- 5. the reductions
+        double pc = 0.0, pm = 0.0;
+        for (int j = lane; j < nv; j += SM_W) {
+            const double t = vs[j];
+            if (T.cw) pc += T.cw[(size_t)k * nv + j] * t;
+            if (j >= nf) pm += t;
+        }
+        if (T.cw) cost += sm_wave_sum(pc);
+        mu_total += sm_wave_sum(pm);
+        {
+            const bool v_nan = best != best, w_nan = worst != worst;
+            if (wstep < 0 || (!w_nan && (v_nan || best > worst))) { worst = best; wstep = k; wrow = brow; }      /* the earliest step of equals stays */
+        }
+        // ---- 6. what was asked for
+        if (T.v) for (int j = lane; j < nv; j += SM_W) T.v[(size_t)k * nv + j] = vs[j];
+        if (lane == 0) { if (T.vio) T.vio[k] = best; if (T.row) T.row[k] = brow; }
+        sm_sync();
+        for (int i = lane; i < nx; i += SM_W) { const double t = xn[i]; xs[i] = t; if (T.x) T.x[(size_t)(k + 1) * nx + i] = t; }
+    }
+    if (end != RO_COMPLETE) ro_blank(M, T, lane, k, false);
+    R.end_status = end; R.steps_done = k;
+    R.cost = end == RO_COMPLETE ? (T.cw ? cost : 0.0) : qnan; R.mu_total = end == RO_COMPLETE ? mu_total : qnan;
+    R.worst_vio = end == RO_COMPLETE ? worst : qnan; R.worst_step = end == RO_COMPLETE ? wstep : -1; R.worst_row = end == RO_COMPLETE ? wrow : -1;
+}
+
+#ifndef SM_HOST
+struct RoDev {
+    int batch, S, K;
+    int nx, nu, nw, nv, nmu, ny, nc, m, n;
+    int stage_doubles;
+    const double *pack; size_t pack_len;
+    size_t oA, oB4, ob5, oC, oD4, od5, oE, oF4, of5, oG, oBv, oDv, oFv;      /* offsets inside a model's packed block (mld_model_create) */
+    const int *model_idx;
+    const double *x0;                               /* (batch, nx): the handle's current state */
+    const double *u; size_t u_stride, u_step;       /* the caller's (batch, K, nu): K nu, nu; the resident plan's rows: n, nv */
+    const int *status; const double *obj;           /* the plan's, masking the instances without a usable one; nullptr = the caller's u */
+    const double *om;                               /* (batch S, K nw) */
+    const double *cw; int cw_by_inst;               /* (rows, K, nv), a row per model or per instance; nullptr = no cost */
+    double *x, *v, *y, *vio; int *row;              /* per trajectory and step, any nullptr */
+    double *cost, *mu_total, *worst_vio; int *worst_step, *steps_done, *end_status;      /* per trajectory, any nullptr */
+    unsigned long long *counter;                    /* [0] the work queue, [1 .. 3] trajectories that ended complete / infeasible / declined */
+};
+
+// Three waves per SIMD asked for: unconstrained the kernel holds 219 VGPRs (two waves) and takes 1.44 x the time; at 168 it spills 42 registers to
+// scratch, outside the pivot loop's hot values (DESIGN section 6).
+__global__ void __launch_bounds__(SM_NT, 3) k_rollout(SmShape S, ProblemDev P, RoDev a)
+{
+    extern __shared__ double ro_lds[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    sm_f64 *mem = (sm_f64 *)ro_lds + (size_t)wave * ((size_t)S.wave_doubles + a.stage_doubles), *stg = mem + S.wave_doubles;
+    const unsigned long long total = (unsigned long long)a.batch * a.S;
+    RoModel M;
+    M.nx = a.nx; M.nu = a.nu; M.nw = a.nw; M.nv = a.nv; M.nmu = a.nmu; M.ny = a.ny; M.nc = a.nc; M.m = a.m; M.n = a.n;
+    for (;;) {
+        // the claim of k_small_milp: every lane takes part behind a convergent barrier (DESIGN section 6, "A trap worth remembering")
+        sm_sync();
+        unsigned long long t = atomicAdd(a.counter, lane == 0 ? 1ull : 0ull);
+        t = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(t >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)t);
+        if (t >= total) break;
+        const long long b = (long long)(t / (unsigned)a.S);
+        const int mdl = a.model_idx ? a.model_idx[b] : 0;
+        const double *pk = a.pack + (size_t)mdl * a.pack_len;
+        M.A = pk + a.oA; M.B4 = pk + a.oB4; M.b5 = pk + a.ob5; M.C = pk + a.oC; M.D4 = pk + a.oD4; M.d5 = pk + a.od5;
+        M.E = pk + a.oE; M.F4 = pk + a.oF4; M.f5 = pk + a.of5; M.G = pk + a.oG; M.Bv = pk + a.oBv; M.Dv = pk + a.oDv; M.Fv = pk + a.oFv;
+        SmArgs A{};
+        if (a.n) {
+            const size_t m = a.m, n = a.n;
+            M.Hx = P.Hx + (size_t)mdl * m * a.nx; M.Hw = P.Hw + (size_t)mdl * m * (a.nw + a.nu); M.H5 = P.H5 + (size_t)mdl * m; M.rs = P.rs + (size_t)mdl * m;
+            A.G = P.Gs + (size_t)mdl * m * n; A.q = P.qs + (size_t)mdl * n;
+            A.lb = P.lb + (size_t)mdl * n; A.ub = P.ub + (size_t)mdl * n; A.cs = P.cs + (size_t)mdl * n;
+            A.is_int = P.is_int; A.bins = P.bins;
+        }
+        RoTraj T;
+        T.K = a.K; T.x0 = a.x0 + (size_t)b * a.nx; T.u = a.u + (size_t)b * a.u_stride; T.u_step = a.u_step;
+        T.om = a.om + (size_t)t * a.K * a.nw;
+        T.cw = a.cw ? a.cw + (size_t)(a.cw_by_inst ? b : mdl) * a.K * a.nv : nullptr;
+        T.x = a.x ? a.x + (size_t)t * (a.K + 1) * a.nx : nullptr; T.v = a.v ? a.v + (size_t)t * a.K * a.nv : nullptr;
+        T.y = a.y ? a.y + (size_t)t * a.K * a.ny : nullptr; T.vio = a.vio ? a.vio + (size_t)t * a.K : nullptr; T.row = a.row ? a.row + (size_t)t * a.K : nullptr;
+        RoResult R;
+        if (a.status && !plan_usable(a.status, a.obj, (int)b)) {      /* uniform over the wave: no plan whose inputs could be applied */
+            const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+            ro_blank(M, T, lane, 0, true);
+            R.cost = R.mu_total = R.worst_vio = qnan; R.worst_step = R.worst_row = -1; R.steps_done = 0; R.end_status = RO_NOT_ATTEMPTED;
+        } else
+            ro_run(S, M, mem, stg, A, T, lane, R);
+        if (lane == 0) {
+            if (a.cost) a.cost[t] = R.cost;
+            if (a.mu_total) a.mu_total[t] = R.mu_total;
+            if (a.worst_vio) a.worst_vio[t] = R.worst_vio;
+            if (a.worst_step) a.worst_step[t] = R.worst_step;
+            if (a.steps_done) a.steps_done[t] = R.steps_done;
+            if (a.end_status) a.end_status[t] = R.end_status;
+            if (R.end_status >= 0) atomicAdd(a.counter + 1 + R.end_status, 1ull);
+        }
+    }
+}
+#endif

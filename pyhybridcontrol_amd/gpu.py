@@ -261,6 +261,7 @@ class GpuProblem(object):
             _lib.dptr(x0) if d["nx"] else None, _lib.dptr(omega) if self.nW else None,
             fb.ctypes.data_as(C.POINTER(C.c_uint8)) if fb is not None else None))
         self.batch = batch
+        self._model_idx = None if mi is None else mi.copy()      # (host copy: rollout() finishes declined trajectories with the instances' models)
         return batch
 
     def upload_constraint_blocks(self, omega_cols, col_rows=None, x_cols=None):
@@ -301,6 +302,7 @@ class GpuProblem(object):
         check(_lib.load().mld_upload_profiles(self._h, lib.size, _lib.dptr(lib) if lib.size else None, 0 if gw is None else gw.size,
                                               gw.ctypes.data_as(C.POINTER(C.c_int32)) if gw is not None else None))
         self._pf_width = None if not lib.size else ([nomega] if gw is None else [int(w) for w in gw])
+        self._pf_lib = lib if lib.size else None      # (the host's array: rollout() cuts the windows of trajectories it finishes on the host out of it)
         self._pf_ccols = 0
 
     def _start_array(self, start, n_lead):
@@ -603,6 +605,106 @@ class GpuProblem(object):
             return int(skipped.value)
         out["cons"] = out["cons"].astype(bool)
         out["n_skipped"] = int(skipped.value)
+        return out
+
+    def rollout(self, resolve, K=None, u_seq=None, omega_seq=None, start=None, step=0, cost_w=None, trajectories=False):
+        """open-loop rollout of the resident batch under S realised disturbances, on device (mld_rollout_batch, kernel k_rollout): the reference's
+        MldModel.lsim / lsim_k in a loop with _compute_aux at every step (models/mld_model.py:543-642, 647-699, 701-766), batch x S trajectories in one launch.
+        resolve: an aux_resolve.BatchAuxResolver(..., small_lds=True) over the same models.  u_seq (batch, K, nu) / (K, nu), or None = the inputs of the
+        resident plan (K <= N_tilde).  Exactly one of omega_seq (batch, S, K, nomega) and start (batch, S, n_groups) / (S, n_groups) offsets into the
+        resident profile library (windows of K steps from `step`).  cost_w (n_models, K, nv), (batch, K, nv) or (K, nv): weights of cost = sum_k w_k . v_k.
+        K=None: N_tilde with the plan's u, u_seq.shape[-2] otherwise.  The handle is not changed (the what-if of sim_step(advance=False)).
+        Returns dict(cost, mu_total, worst_vio, worst_step, steps_done, end_status: (batch, S); stats: dict(trajectories, complete, infeasible, declined,
+        not_attempted, finished_on_host)); trajectories=True adds x (batch, S, K + 1, nx), v (batch, S, K, nv), y, cons_vio, cons_row (batch, S, K).
+        end_status 0 complete, 1 the auxiliary problem of step steps_done is infeasible (NaN / -1 from there on, summaries NaN), -1 not attempted (no usable
+        plan).  Trajectories the device's LDS solver declined (2) are finished on the host -- resolve.resolve per remaining step, whose own solve falls back
+        to the dense kernel, then simlog.lsim_k_batch -- and end 0 or 1; they are counted in stats["finished_on_host"]."""
+        from . import simlog
+        d, B, nv = self.model.dims, self.batch, self.model.nv
+        nx, nu, nw, ny = d["nx"], d["nu"], d["nomega"], d["ny"]
+        if u_seq is not None:
+            u_seq = np.asarray(u_seq, dtype=np.float64)
+            if u_seq.ndim == 2:
+                u_seq = np.broadcast_to(u_seq, (B,) + u_seq.shape)
+            if u_seq.ndim != 3 or u_seq.shape[0] != B or u_seq.shape[2] != nu or (K is not None and u_seq.shape[1] != int(K)):
+                raise ValueError("u_seq has shape %s, expected (%d, K, %d) or (K, %d)%s" % (u_seq.shape, B, nu, nu, "" if K is None else " with K = %d" % int(K)))
+            K = u_seq.shape[1]
+            u_seq = np.ascontiguousarray(u_seq)
+        K = self.N_tilde if K is None else int(K)
+        if (omega_seq is None) == (start is None) and nw:
+            raise ValueError("exactly one of omega_seq and start must be given (%s)" % ("both are" if start is not None else "neither is"))
+        st = None
+        if omega_seq is not None:
+            omega_seq = np.asarray(omega_seq, dtype=np.float64)
+            if omega_seq.ndim != 4 or omega_seq.shape[0] != B or omega_seq.shape[1] < 1 or omega_seq.shape[2:] != (K, nw):
+                raise ValueError("omega_seq has shape %s, expected (%d, S, %d, %d)" % (omega_seq.shape, B, K, nw))
+            omega_seq = np.ascontiguousarray(omega_seq)
+            S = omega_seq.shape[1]
+        elif start is not None:
+            st = self._start_array(start, 1)
+            S = st.shape[1]
+        else:
+            S = 1
+        rows = 0
+        if cost_w is not None:
+            cost_w = np.asarray(cost_w, dtype=np.float64)
+            if cost_w.ndim == 2:
+                cost_w = np.broadcast_to(cost_w, (self.model.n_models,) + cost_w.shape)
+            if cost_w.ndim != 3 or cost_w.shape[0] not in (self.model.n_models, B) or cost_w.shape[1:] != (K, nv):
+                raise ValueError("cost_w has shape %s, expected (%d, %d, %d), (%d, %d, %d) or (%d, %d)" % (cost_w.shape, self.model.n_models, K, nv, B, K, nv, K, nv))
+            cost_w = np.ascontiguousarray(cost_w)
+            rows = cost_w.shape[0]
+        aux = resolve.problem._h if resolve is not None and resolve.problem is not None else None
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None
+        lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64)) if a is not None else None
+
+        def call(full):
+            o = dict(cost=np.zeros((B, S)), mu_total=np.zeros((B, S)), worst_vio=np.zeros((B, S)), worst_step=np.zeros((B, S), np.int32),
+                     steps_done=np.zeros((B, S), np.int32), end_status=np.zeros((B, S), np.int32))
+            if full:
+                o.update(x=np.zeros((B, S, K + 1, nx)), v=np.zeros((B, S, K, nv)), y=np.zeros((B, S, K, ny)), cons_vio=np.zeros((B, S, K)),
+                         cons_row=np.zeros((B, S, K), np.int32))
+            stats = np.zeros(4, np.int64)
+            check(_lib.load().mld_rollout_batch(
+                self._h, aux, K, S, _lib.dptr(u_seq), _lib.dptr(omega_seq) if nw else None, lp(st), int(step), _lib.dptr(cost_w), rows,
+                _lib.dptr(o.get("x")), _lib.dptr(o.get("v")), _lib.dptr(o.get("y")), _lib.dptr(o.get("cons_vio")), ip(o.get("cons_row")),
+                _lib.dptr(o["cost"]), _lib.dptr(o["mu_total"]), _lib.dptr(o["worst_vio"]), ip(o["worst_step"]), ip(o["steps_done"]), ip(o["end_status"]),
+                lp(stats)))
+            return o, stats
+
+        out, stats = call(trajectories)
+        n_host = int(stats[3])
+        if n_host:
+            if not trajectories:
+                out, stats = call(True)      # (the completion continues from the states and slices the device left: it needs the trajectories)
+            midx = getattr(self, "_model_idx", None)
+            midx = np.zeros(B, np.int64) if midx is None else np.asarray(midx, np.int64)
+            if midx.shape != (B,):
+                raise MldGpuError("rollout: the model indices of the resident batch are not known on the host (upload() keeps them)")
+            if u_seq is None:
+                u_all = np.ascontiguousarray(self.download()["v"].reshape(B, self.N_tilde, nv)[:, :K, :nu])
+            else:
+                u_all = u_seq
+            if omega_seq is None and nw:
+                from . import profiles
+                om_all = profiles.windows(self._pf_lib, st.reshape(B * S, -1), int(step), K, self._pf_width).reshape(B, S, K, nw)
+            else:
+                om_all = omega_seq if nw else np.zeros((B, S, K, 0))
+            T = B * S
+            flat = {k: out[k].reshape((T,) + out[k].shape[2:]) for k in out}
+            todo = np.where(flat["end_status"] == 2)[0]
+            n_host = int(todo.size)
+            cw_t = None
+            if cost_w is not None:
+                cw_t = np.repeat(cost_w if rows != self.model.n_models else cost_w[midx], S, axis=0)
+            simlog.rollout_continue(resolve.mats, d, np.repeat(midx, S), np.repeat(u_all, S, axis=0), om_all.reshape(T, K, nw), flat, todo, resolve.resolve, cw_t)
+            out = {k: flat[k].reshape(out[k].shape) for k in out}
+        es = out["end_status"]
+        out["stats"] = dict(trajectories=int(stats[0]), complete=int((es == 0).sum()) if n_host else int(stats[1]), infeasible=int((es == 1).sum()) if n_host else int(stats[2]),
+                            declined=int(stats[3]), not_attempted=int(stats[0] - stats[1] - stats[2] - stats[3]), finished_on_host=n_host)
+        if n_host and not trajectories:
+            for k in ("x", "v", "y", "cons_vio", "cons_row"):
+                del out[k]
         return out
 
     def sim_log(self, first=0, count=None):

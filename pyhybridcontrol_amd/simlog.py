@@ -90,3 +90,107 @@ def to_mld_sim_log(log, instance, dims, k0=0):
         out.set_sim_k(k0 + r, dict(x_k1=log["x_k1"][r, b], x=log["x"][r, b], u=v[:o1], delta=v[o1:o2], z=v[o2:o3], mu=v[o3:], v=v, y=log["y"][r, b],
                                    omega=log["omega"][r, b], cons=np.asarray(log["cons"][r, b], dtype=bool)))
     return out
+
+
+# ---- open-loop rollout: the reference's MldModel.lsim, lsim_k in a loop (models/mld_model.py:543-642, 647-699) with _compute_aux (:701-766) per step ----
+def _worst(vio):
+    """(worst_vio, worst_step) of cons_vio rows (T, K): the largest value, a NaN wins, the earliest step of equals"""
+    vio = np.asarray(vio, dtype=np.float64)
+    nan = np.isnan(vio)
+    step = np.where(nan.any(axis=1), nan.argmax(axis=1), np.where(nan, -np.inf, vio).argmax(axis=1)).astype(np.int32)
+    return vio[np.arange(vio.shape[0]), step], step
+
+
+def lsim_k_reference_order(mats_list, dims, model_idx, x, v0, omega):
+    """lsim_k_batch with every sum in the REFERENCE's order of operations, instance by instance as the reference calls it (models/mld_model.py:690-694):
+    A x + B1 u + B2 delta + B3 z + B4 omega + b5, the same for y, and E x + F1 u + F2 delta + F3 z + F4 omega + G y + Psi (mu * 0) - f5.  The kernels'
+    order (lsim_k_batch) differs from it by rounding only.  Returns dict(x_k1, y, resid, cons, cons_vio, cons_row)."""
+    nx, nu, nd, nz, nmu, nw, ny, nc = (int(dims.get(k, 0)) for k in ("nx", "nu", "ndelta", "nz", "nmu", "nomega", "ny", "nc"))
+    B = int(np.shape(x)[0])
+    o1, o2, o3 = nu, nu + nd, nu + nd + nz
+    midx = np.zeros(B, dtype=np.int64) if model_idx is None else np.asarray(model_idx, dtype=np.int64).reshape(B)
+    out = dict(x_k1=np.zeros((B, nx)), y=np.zeros((B, ny)), resid=np.zeros((B, nc)))
+    for b in range(B):
+        m = mats_list[midx[b]]
+        g = lambda name, r, c: _mat(m, name, r, c)
+        xk, wk = np.asarray(x[b], np.float64).reshape(nx, 1), np.asarray(omega[b], np.float64).reshape(nw, 1)
+        vk = np.asarray(v0[b], np.float64).reshape(-1, 1)
+        u, dl, z, mu = vk[:o1], vk[o1:o2], vk[o2:o3], vk[o3:]
+        out["x_k1"][b] = (g("A", nx, nx) @ xk + g("B1", nx, nu) @ u + g("B2", nx, nd) @ dl + g("B3", nx, nz) @ z + g("B4", nx, nw) @ wk + g("b5", nx, 1))[:, 0]
+        y = g("C", ny, nx) @ xk + g("D1", ny, nu) @ u + g("D2", ny, nd) @ dl + g("D3", ny, nz) @ z + g("D4", ny, nw) @ wk + g("d5", ny, 1)
+        out["y"][b] = y[:, 0]
+        out["resid"][b] = (g("E", nc, nx) @ xk + g("F1", nc, nu) @ u + g("F2", nc, nd) @ dl + g("F3", nc, nz) @ z + g("F4", nc, nw) @ wk + g("G", nc, ny) @ y
+                           + g("Psi", nc, nmu) @ (mu * 0) - g("f5", nc, 1))[:, 0]
+    r = out["resid"]
+    out["cons"] = r <= CONS_TOL
+    if nc:
+        out["cons_vio"], out["cons_row"] = r.max(axis=1), r.argmax(axis=1).astype(np.int32)
+    else:
+        out["cons_vio"], out["cons_row"] = np.full(B, -np.inf), np.full(B, -1, dtype=np.int32)
+    return out
+
+
+def rollout_continue(mats_list, dims, model_idx, u_seq, omega_seq, out, todo, resolve_fn, cost_w=None, step_fn=lsim_k_batch):
+    """continue the flat trajectories `todo` (indices) of `out` in place, each from its step out["steps_done"][t] and the state out["x"][t, steps_done]:
+    model_idx (T,), u_seq (T, K, nu), omega_seq (T, K, nomega), cost_w (T, K, nv) or None; out: x (T, K + 1, nx), v (T, K, nv), y, cons_vio, cons_row (T, K),
+    steps_done, end_status, cost, mu_total, worst_vio, worst_step (T,).  Per step, in the reference's order: resolve_fn(x, u, omega, model_idx) ->
+    dict(v = [delta | z | mu] rows (NaN where there is no feasible point), status) as aux_resolve.BatchAuxResolver.resolve returns it, then step_fn
+    (lsim_k_batch, or lsim_k_reference_order) with v_k = [u_k; delta; z; mu].  A trajectory whose auxiliary problem has no feasible point ends 1 at that step (NaN / -1 from there on, summaries
+    NaN / -1), the others end 0 with their summaries reduced from the finished trajectory."""
+    nu, nv2 = int(dims.get("nu", 0)), sum(int(dims.get(k, 0)) for k in ("ndelta", "nz", "nmu"))
+    nf = nu + int(dims.get("ndelta", 0)) + int(dims.get("nz", 0))
+    todo = np.asarray(todo, dtype=np.int64)
+    midx = np.asarray(model_idx, dtype=np.int64)
+    K = out["v"].shape[1]
+    out["end_status"][todo] = 0
+    for k in range(K):
+        act = todo[(out["steps_done"][todo] == k) & (out["end_status"][todo] == 0)]
+        if not act.size:
+            continue
+        x, uk, wk = out["x"][act, k], u_seq[act, k], omega_seq[act, k]
+        if nv2:
+            r = resolve_fn(x, uk, wk, midx[act])
+            aux = np.asarray(r["v"], dtype=np.float64).reshape(act.size, nv2)
+            ok = np.isin(np.asarray(r["status"]), (0, 2)) & np.all(np.isfinite(aux), axis=1)
+        else:
+            aux, ok = np.zeros((act.size, 0)), np.ones(act.size, bool)
+        bad, good = act[~ok], act[ok]
+        out["end_status"][bad] = 1
+        out["x"][bad, k + 1:] = np.nan; out["v"][bad, k:] = np.nan; out["y"][bad, k:] = np.nan; out["cons_vio"][bad, k:] = np.nan; out["cons_row"][bad, k:] = -1
+        if good.size:
+            v = np.hstack([uk[ok], aux[ok]])
+            st = step_fn(mats_list, dims, midx[good], x[ok], v, wk[ok])
+            out["x"][good, k + 1], out["v"][good, k], out["y"][good, k] = st["x_k1"], v, st["y"]
+            out["cons_vio"][good, k], out["cons_row"][good, k] = st["cons_vio"], st["cons_row"]
+            out["steps_done"][good] = k + 1
+    done = todo[out["end_status"][todo] == 0]
+    dead = todo[out["end_status"][todo] != 0]
+    out["cost"][dead] = out["mu_total"][dead] = out["worst_vio"][dead] = np.nan
+    out["worst_step"][dead] = -1
+    if done.size:
+        v = out["v"][done]
+        out["cost"][done] = np.einsum("tkj,tkj->t", cost_w[done], v) if cost_w is not None else 0.0
+        out["mu_total"][done] = v[:, :, nf:].sum(axis=(1, 2))
+        out["worst_vio"][done], out["worst_step"][done] = _worst(out["cons_vio"][done])
+    return out
+
+
+def rollout_np(mats_list, dims, model_idx, x0, u_seq, omega_seq, resolve_fn, cost_w=None):
+    """GpuProblem.rollout stated in numpy: x0 (B, nx), u_seq (B, K, nu), omega_seq (B, S, K, nomega), model_idx (B,) or None, cost_w (B, K, nv) or None ->
+    dict(x (B, S, K + 1, nx), v (B, S, K, nv), y, cons_vio, cons_row (B, S, K), cost, mu_total, worst_vio, worst_step, steps_done, end_status (B, S)).
+    resolve_fn as rollout_continue takes it.  The chain is the reference's, in its order of operations (lsim_k_reference_order)."""
+    nx, nw, ny = (int(dims.get(k, 0)) for k in ("nx", "nomega", "ny"))
+    nv = sum(int(dims.get(k, 0)) for k in ("nu", "ndelta", "nz", "nmu"))
+    u_seq = np.asarray(u_seq, dtype=np.float64)
+    B, K = u_seq.shape[0], u_seq.shape[1]
+    omega_seq = np.asarray(omega_seq, dtype=np.float64).reshape(B, -1, K, nw)
+    S = omega_seq.shape[1]
+    T = B * S
+    midx = np.zeros(B, dtype=np.int64) if model_idx is None else np.asarray(model_idx, dtype=np.int64)
+    out = dict(x=np.full((T, K + 1, nx), np.nan), v=np.full((T, K, nv), np.nan), y=np.full((T, K, ny), np.nan), cons_vio=np.full((T, K), np.nan),
+               cons_row=np.full((T, K), -1, np.int32), cost=np.zeros(T), mu_total=np.zeros(T), worst_vio=np.zeros(T), worst_step=np.zeros(T, np.int32),
+               steps_done=np.zeros(T, np.int32), end_status=np.zeros(T, np.int32))
+    out["x"][:, 0] = np.repeat(np.asarray(x0, dtype=np.float64).reshape(B, nx), S, axis=0)
+    rollout_continue(mats_list, dims, np.repeat(midx, S), np.repeat(u_seq, S, axis=0), omega_seq.reshape(T, K, nw), out, np.arange(T), resolve_fn,
+                     None if cost_w is None else np.repeat(np.asarray(cost_w, dtype=np.float64).reshape(B, K, nv), S, axis=0), step_fn=lsim_k_reference_order)
+    return {k: a.reshape((B, S) + a.shape[1:]) for k, a in out.items()}
