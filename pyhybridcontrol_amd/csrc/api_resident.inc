@@ -404,7 +404,7 @@ int mld_advance_batch2(mld_problem_t *p, int32_t *n_skipped_out)
     const int grid = (int)std::max<size_t>(bx, std::min<size_t>(bw, (size_t)1 << 20));   /* the state part is one thread per element, the shift strides */
     HIP_TRY(hipMemsetAsync(p->bat.skipped, 0, sizeof(int), p->stream));
     hipLaunchKernelGGL(k_advance, dim3(grid), dim3(256), 0, p->stream, p->batch, p->nx, p->nv, d.nomega, p->N,
-                       m->d_pack, m->pack_len, 1, m->pack_off.A, m->pack_off.B4, m->pack_off.b5, m->pack_off.Bv,
+                       m->d_pack, m->pack_len, m->pack_off,
                        p->has_midx ? p->bat.model_idx : nullptr, p->bat.x0, p->bat.omega, p->bat.v, (size_t)p->n, p->bat.x0b, p->bat.omegab,
                        p->bat.status, p->bat.obj, p->bat.skipped);
     HIP_TRY(hipGetLastError());
@@ -514,12 +514,7 @@ static int sim_step_run(mld_problem_t *p, const SimStepSrc &src, const int64_t *
     a.batch = batch; a.nx = nx; a.nv = nv; a.nmu = d.nmu; a.nw = nw; a.ny = ny; a.nc = nc; a.N = p->N;
     const size_t stage = sizeof(double) * SS_WAVES * ((size_t)nx + nv + nw + ny);
     a.lds = stage <= SS_LDS_MAX && !(p->opts.reserved & MLD_DBG_SIM_NO_LDS);
-    a.pack = m->d_pack; a.pack_len = m->pack_len;
-    {
-        const PackOff &o = m->pack_off;
-        a.oA = o.A; a.oB4 = o.B4; a.ob5 = o.b5; a.oC = o.C; a.oD4 = o.D4; a.od5 = o.d5; a.oE = o.E; a.oF4 = o.F4; a.of5 = o.f5; a.oG = o.G;
-        a.oBv = o.Bv; a.oDv = o.Dv; a.oFv = o.Fv;
-    }
+    a.pack = m->d_pack; a.pack_len = m->pack_len; a.off = m->pack_off;
     a.model_idx = p->has_midx ? p->bat.model_idx.get() : nullptr;
     a.x0 = p->bat.x0; a.omega = p->bat.omega;
     const hipStream_t sq = p->stream;
@@ -601,6 +596,29 @@ int mld_sim_step_batch(mld_problem_t *p, const double *v0, const int64_t *act_st
     return sim_step_run(p, src, act_start, gmax, step, flags, x_k1_out, y_out, cons_out, cons_vio_out, cons_row_out, n_skipped_out);
 }
 
+/* Is `aux` the resolver of p's models -- their fold at N_tilde = 1, idle, without the hand-off -- or NULL exactly when there is nothing to resolve?
+ * (mld_sim_step_resolve, mld_rollout_batch; `what`: the caller's word for p in the message) */
+static int aux_fold_check(const char *who, const char *what, const mld_problem_t *p, const mld_problem_t *aux)
+{
+    const mld_dims &d = p->model->dims;
+    const int nv2 = d.ndelta + d.nz + d.nmu;
+    if (!nv2 && aux) { mld_set_error("%s: the model has no auxiliaries (ndelta + nz + nmu = 0), so there is nothing to resolve: aux must be NULL", who); return MLD_ERR_INVALID; }
+    if (nv2 && !aux) { mld_set_error("%s: aux == NULL, but the model has %d auxiliaries to resolve (ndelta + nz + nmu)", who, nv2); return MLD_ERR_INVALID; }
+    if (!aux) return MLD_OK;
+    if (aux == p) { mld_set_error("%s: aux is the %s problem itself (the resolver is a handle of its own: the folded models at N_tilde = 1)", who, what); return MLD_ERR_INVALID; }
+    if (aux->flight != Flight::idle) { mld_set_error("%s: aux has a launched solve that has not been finished (mld_solve_finish)", who); return MLD_ERR_INVALID; }
+    if (aux->N != 1) { mld_set_error("%s: aux has N_tilde = %d (the auxiliary problem is the horizon-1 instance: N_tilde = 1)", who, aux->N); return MLD_ERR_INVALID; }
+    if (aux->model->tv_N > 0) { mld_set_error("%s: aux is time-varying (mld_model_create_tv)", who); return MLD_ERR_INVALID; }
+    if (aux->ho_enable) { mld_set_error("%s: aux has the in-kernel hand-off on (mld_set_handoff)", who); return MLD_ERR_INVALID; }
+    const mld_dims &e = aux->model->dims;
+    if (e.nx != d.nx || e.nc != d.nc || e.ndelta != d.ndelta || e.nz != d.nz || e.nmu != d.nmu || aux->n_models != p->n_models || e.nu != 0 || e.nomega != d.nomega + d.nu) {
+        mld_set_error("%s: aux is not the fold of this problem's models: nx %d/%d nc %d/%d ndelta %d/%d nz %d/%d nmu %d/%d n_models %d/%d (aux/problem), nu %d (0), nomega %d (nomega + nu = %d)",
+                      who, e.nx, d.nx, e.nc, d.nc, e.ndelta, d.ndelta, e.nz, d.nz, e.nmu, d.nmu, aux->n_models, p->n_models, e.nu, e.nomega, d.nomega + d.nu);
+        return MLD_ERR_INVALID;
+    }
+    return MLD_OK;
+}
+
 /* ---- the plant step with the auxiliaries re-derived -------------------------------------------------------------------------------------------------
  * What the reference's closed loop really does: sim_step_k calls lsim_k(x_k=, u_k=, omega_k=) with u only, and lsim_k solves _compute_aux for delta, z, mu
  * under the REALISED omega_k before it forms x_k1, y and cons (controllers/controller_base.py:229-253, models/mld_model.py:683-686, 701-766).  `aux` is the
@@ -619,21 +637,7 @@ int mld_sim_step_resolve(mld_problem_t *p, mld_problem_t *aux, const double *u0,
     const mld_dims &d = p->model->dims;
     const int batch = p->batch, nx = d.nx, nu = d.nu, nw = d.nomega, nv = p->nv, nv2 = d.ndelta + d.nz + d.nmu;
     const bool actual = flags & MLD_SIM_ACTUAL, log = flags & MLD_SIM_LOG;
-    if (!nv2 && aux) { mld_set_error("%s: the model has no auxiliaries (ndelta + nz + nmu = 0), so there is nothing to resolve: aux must be NULL", who); return MLD_ERR_INVALID; }
-    if (nv2 && !aux) { mld_set_error("%s: aux == NULL, but the model has %d auxiliaries to resolve (ndelta + nz + nmu)", who, nv2); return MLD_ERR_INVALID; }
-    if (aux) {
-        if (aux == p) { mld_set_error("%s: aux is the stepped problem itself (the resolver is a handle of its own: the folded models at N_tilde = 1)", who); return MLD_ERR_INVALID; }
-        if (aux->flight != Flight::idle) { mld_set_error("%s: aux has a launched solve that has not been finished (mld_solve_finish)", who); return MLD_ERR_INVALID; }
-        if (aux->N != 1) { mld_set_error("%s: aux has N_tilde = %d (the auxiliary problem is the horizon-1 instance: N_tilde = 1)", who, aux->N); return MLD_ERR_INVALID; }
-        if (aux->model->tv_N > 0) { mld_set_error("%s: aux is time-varying (mld_model_create_tv)", who); return MLD_ERR_INVALID; }
-        if (aux->ho_enable) { mld_set_error("%s: aux has the in-kernel hand-off on (mld_set_handoff): its result rows would come after a merge this call does not run", who); return MLD_ERR_INVALID; }
-        const mld_dims &e = aux->model->dims;
-        if (e.nx != nx || e.nc != d.nc || e.ndelta != d.ndelta || e.nz != d.nz || e.nmu != d.nmu || aux->n_models != p->n_models || e.nu != 0 || e.nomega != nw + nu) {
-            mld_set_error("%s: aux is not the fold of this problem's models: nx %d/%d nc %d/%d ndelta %d/%d nz %d/%d nmu %d/%d n_models %d/%d (aux/problem), nu %d (0), nomega %d (nomega + nu = %d)",
-                          who, e.nx, nx, e.nc, d.nc, e.ndelta, d.ndelta, e.nz, d.nz, e.nmu, d.nmu, aux->n_models, p->n_models, e.nu, e.nomega, nw + nu);
-            return MLD_ERR_INVALID;
-        }
-    }
+    if (int rc = aux_fold_check(who, "stepped", p, aux)) return rc;
     if (u0) for (size_t k = 0; k < (size_t)batch * nu; ++k) if (!std::isfinite(u0[k])) {
         mld_set_error("%s: u0 of instance %zu, input %zu is not finite (%g)", who, k / nu, k % nu, u0[k]); return MLD_ERR_INVALID;
     }

@@ -15,26 +15,14 @@ int mld_rollout_batch(mld_problem_t *p, mld_problem_t *aux, int K, int S, const 
     if (int rc = entry_guard(p, who, true, "no batch resident (mld_upload_batch)")) return rc;
     mld_model *mo = p->model;
     const mld_dims &d = mo->dims;
-    const int batch = p->batch, nx = d.nx, nu = d.nu, nw = d.nomega, nv = p->nv, ny = d.ny, nv2 = d.ndelta + d.nz + d.nmu;
+    const int batch = p->batch, nx = d.nx, nu = d.nu, nw = d.nomega, nv = p->nv, ny = d.ny;
     if (mo->tv_N > 0) { mld_set_error("%s: time-varying models (mld_model_create_tv) are not rolled out on the device -- the step models would have to shift with the horizon", who); return MLD_ERR_INVALID; }
     if (!mo->d_pack) { mld_set_error("%s: model without matrices", who); return MLD_ERR_INVALID; }
     if (K < 1 || S < 1) { mld_set_error("%s: K = %d, S = %d (at least one step and one realisation)", who, K, S); return MLD_ERR_INVALID; }
     if ((long long)batch * S > INT_MAX) { mld_set_error("%s: batch x S = %lld trajectories (at most %d)", who, (long long)batch * S, INT_MAX); return MLD_ERR_INVALID; }
     if (step < 0 || step > INT_MAX - K) { mld_set_error("%s: step = %d (must be >= 0)", who, step); return MLD_ERR_INVALID; }
-    if (!nv2 && aux) { mld_set_error("%s: the model has no auxiliaries (ndelta + nz + nmu = 0), so there is nothing to resolve: aux must be NULL", who); return MLD_ERR_INVALID; }
-    if (nv2 && !aux) { mld_set_error("%s: aux == NULL, but the model has %d auxiliaries to resolve (ndelta + nz + nmu)", who, nv2); return MLD_ERR_INVALID; }
-    if (aux) {      /* the dimension test of mld_sim_step_resolve */
-        if (aux == p) { mld_set_error("%s: aux is the rolled-out problem itself (the resolver is a handle of its own: the folded models at N_tilde = 1)", who); return MLD_ERR_INVALID; }
-        if (aux->flight != Flight::idle) { mld_set_error("%s: aux has a launched solve that has not been finished (mld_solve_finish)", who); return MLD_ERR_INVALID; }
-        if (aux->N != 1) { mld_set_error("%s: aux has N_tilde = %d (the auxiliary problem is the horizon-1 instance: N_tilde = 1)", who, aux->N); return MLD_ERR_INVALID; }
-        if (aux->model->tv_N > 0) { mld_set_error("%s: aux is time-varying (mld_model_create_tv)", who); return MLD_ERR_INVALID; }
-        if (aux->ho_enable) { mld_set_error("%s: aux has the in-kernel hand-off on (mld_set_handoff)", who); return MLD_ERR_INVALID; }
-        const mld_dims &e = aux->model->dims;
-        if (e.nx != nx || e.nc != d.nc || e.ndelta != d.ndelta || e.nz != d.nz || e.nmu != d.nmu || aux->n_models != p->n_models || e.nu != 0 || e.nomega != nw + nu) {
-            mld_set_error("%s: aux is not the fold of this problem's models: nx %d/%d nc %d/%d ndelta %d/%d nz %d/%d nmu %d/%d n_models %d/%d (aux/problem), nu %d (0), nomega %d (nomega + nu = %d)",
-                          who, e.nx, nx, e.nc, d.nc, e.ndelta, d.ndelta, e.nz, d.nz, e.nmu, d.nmu, aux->n_models, p->n_models, e.nu, e.nomega, nw + nu);
-            return MLD_ERR_INVALID;
-        }
+    if (int rc = aux_fold_check(who, "rolled-out", p, aux)) return rc;
+    if (aux) {
         if (!aux->small_ok) {
             mld_set_error("%s: aux is not on the small-problem path (%s): the rollout solves its auxiliary problems in LDS and has no dense fall-back -- create the resolver with MLD_SMALL_LDS, or step with mld_sim_step_resolve",
                           who, (aux->opts.flags & MLD_SMALL_LDS) ? "its shape does not fit a wave's share of LDS" : "MLD_SMALL_LDS is not set");
@@ -89,28 +77,18 @@ int mld_rollout_batch(mld_problem_t *p, mld_problem_t *aux, int K, int S, const 
     HIP_TRY(d_om.alloc(std::max<size_t>(1, T * Kz * nw)));
     if (start) HIP_TRY(d_start.alloc(T * p->pf_groups));
     if (cost_w) HIP_TRY(d_cw.alloc(std::max<size_t>(1, (size_t)cost_rows * Kz * nv)));
-    if (x_out && nx) HIP_TRY(d_x.alloc(T * (Kz + 1) * nx));
-    if (v_out && nv) HIP_TRY(d_v.alloc(T * Kz * nv));
-    if (y_out && ny) HIP_TRY(d_y.alloc(T * Kz * ny));
-    if (cons_vio_out) HIP_TRY(d_vio.alloc(T * Kz));
-    if (cons_row_out) HIP_TRY(d_row.alloc(T * Kz));
-    if (cost_out) HIP_TRY(d_cost.alloc(T));
-    if (mu_total_out) HIP_TRY(d_mu.alloc(T));
-    if (worst_vio_out) HIP_TRY(d_wv.alloc(T));
-    if (worst_step_out) HIP_TRY(d_ws.alloc(T));
-    if (steps_done_out) HIP_TRY(d_sd.alloc(T));
-    if (end_status_out) HIP_TRY(d_es.alloc(T));
+    /* an output that was asked for and is not empty gets a device buffer (take), and is copied back after the kernel (get) */
+    const size_t cx = T * (Kz + 1) * nx, cv = T * Kz * nv, cy = T * Kz * ny, ck = T * Kz;
+    auto take = [](auto &buf, const void *out, size_t count) -> hipError_t { return out && count ? buf.alloc(count) : hipSuccess; };
+    HIP_TRY(take(d_x, x_out, cx)); HIP_TRY(take(d_v, v_out, cv)); HIP_TRY(take(d_y, y_out, cy)); HIP_TRY(take(d_vio, cons_vio_out, ck)); HIP_TRY(take(d_row, cons_row_out, ck));
+    HIP_TRY(take(d_cost, cost_out, T)); HIP_TRY(take(d_mu, mu_total_out, T)); HIP_TRY(take(d_wv, worst_vio_out, T));
+    HIP_TRY(take(d_ws, worst_step_out, T)); HIP_TRY(take(d_sd, steps_done_out, T)); HIP_TRY(take(d_es, end_status_out, T));
     HIP_TRY(d_cnt.alloc(4));
     RoDev a{};
     a.batch = batch; a.S = S; a.K = K;
     a.nx = nx; a.nu = nu; a.nw = nw; a.nv = nv; a.nmu = d.nmu; a.ny = ny; a.nc = d.nc; a.m = aux ? aux->m0 : 0; a.n = aux ? aux->n : 0;
     a.stage_doubles = (int)stage_d;
-    a.pack = mo->d_pack; a.pack_len = mo->pack_len;
-    {
-        const PackOff &o = mo->pack_off;
-        a.oA = o.A; a.oB4 = o.B4; a.ob5 = o.b5; a.oC = o.C; a.oD4 = o.D4; a.od5 = o.d5; a.oE = o.E; a.oF4 = o.F4; a.of5 = o.f5; a.oG = o.G;
-        a.oBv = o.Bv; a.oDv = o.Dv; a.oFv = o.Fv;
-    }
+    a.pack = mo->d_pack; a.pack_len = mo->pack_len; a.off = mo->pack_off;
     a.model_idx = p->has_midx ? p->bat.model_idx.get() : nullptr;
     a.x0 = p->bat.x0;
     if (u_seq) { a.u = d_u; a.u_stride = Kz * nu; a.u_step = (size_t)nu; }
@@ -143,17 +121,12 @@ int mld_rollout_batch(mld_problem_t *p, mld_problem_t *aux, int K, int S, const 
         }
         hipLaunchKernelGGL(k_rollout, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a);
         HIP_TRY(hipGetLastError());
-        if (d_x) HIP_TRY(hipMemcpyAsync(x_out, d_x, sizeof(double) * T * (Kz + 1) * nx, hipMemcpyDeviceToHost, sq));
-        if (d_v) HIP_TRY(hipMemcpyAsync(v_out, d_v, sizeof(double) * T * Kz * nv, hipMemcpyDeviceToHost, sq));
-        if (d_y) HIP_TRY(hipMemcpyAsync(y_out, d_y, sizeof(double) * T * Kz * ny, hipMemcpyDeviceToHost, sq));
-        if (d_vio) HIP_TRY(hipMemcpyAsync(cons_vio_out, d_vio, sizeof(double) * T * Kz, hipMemcpyDeviceToHost, sq));
-        if (d_row) HIP_TRY(hipMemcpyAsync(cons_row_out, d_row, sizeof(int) * T * Kz, hipMemcpyDeviceToHost, sq));
-        if (d_cost) HIP_TRY(hipMemcpyAsync(cost_out, d_cost, sizeof(double) * T, hipMemcpyDeviceToHost, sq));
-        if (d_mu) HIP_TRY(hipMemcpyAsync(mu_total_out, d_mu, sizeof(double) * T, hipMemcpyDeviceToHost, sq));
-        if (d_wv) HIP_TRY(hipMemcpyAsync(worst_vio_out, d_wv, sizeof(double) * T, hipMemcpyDeviceToHost, sq));
-        if (d_ws) HIP_TRY(hipMemcpyAsync(worst_step_out, d_ws, sizeof(int) * T, hipMemcpyDeviceToHost, sq));
-        if (d_sd) HIP_TRY(hipMemcpyAsync(steps_done_out, d_sd, sizeof(int) * T, hipMemcpyDeviceToHost, sq));
-        if (d_es) HIP_TRY(hipMemcpyAsync(end_status_out, d_es, sizeof(int) * T, hipMemcpyDeviceToHost, sq));
+        auto get = [&](auto *out, const auto &buf, size_t count) -> hipError_t {
+            return buf ? hipMemcpyAsync(out, buf, sizeof(*out) * count, hipMemcpyDeviceToHost, sq) : hipSuccess;
+        };
+        HIP_TRY(get(x_out, d_x, cx)); HIP_TRY(get(v_out, d_v, cv)); HIP_TRY(get(y_out, d_y, cy)); HIP_TRY(get(cons_vio_out, d_vio, ck)); HIP_TRY(get(cons_row_out, d_row, ck));
+        HIP_TRY(get(cost_out, d_cost, T)); HIP_TRY(get(mu_total_out, d_mu, T)); HIP_TRY(get(worst_vio_out, d_wv, T));
+        HIP_TRY(get(worst_step_out, d_ws, T)); HIP_TRY(get(steps_done_out, d_sd, T)); HIP_TRY(get(end_status_out, d_es, T));
         HIP_TRY(hipMemcpyAsync(cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, sq));
         return MLD_OK;
     };

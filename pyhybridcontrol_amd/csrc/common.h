@@ -53,8 +53,7 @@ struct CondLayout {
     size_t out_off[12];   // offset of each matrix family buffer base (each buffer holds n_models copies)
 };
 
-// offsets (in doubles) of the matrices inside one model's block of mld_model::d_pack; Bv = [B1 B2 B3 0], Dv = [D1 D2 D3 0], Fv = [F1 F2 F3 Psi], each nv wide
-struct PackOff { size_t A, B4, b5, C, D4, d5, E, F4, f5, G, Bv, Dv, Fv; };
+#include "plant_step.inc"      // PackOff, and the sums of one plant step (k_advance, k_sim_step, k_rollout)
 
 struct mld_model {
     mld_dims dims;
@@ -69,7 +68,7 @@ struct mld_model {
     DevBuf<double> d_pack;  // per model, packed once at creation in the LDS order of k_condense_blocks:
                             // A, B4, b5, C, D4, d5, E, F4, f5, G, [B1 B2 B3 0], [D1 D2 D3 0], [F1 F2 F3 Psi]
     size_t pack_len = 0;
-    PackOff pack_off{};     // where each of them starts inside a model's block (k_advance, k_sim_step)
+    PackOff pack_off{};     // where each of them starts inside a model's block (k_advance, k_sim_step, k_rollout)
     // condensing results (device resident)
     int cond_N = -1;
     bool out64 = false;          // d_out holds the fp64 maps of cond_N (an fp32-only materialisation, mld_condense_device_f32, fills d_out32 alone)

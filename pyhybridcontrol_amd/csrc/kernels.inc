@@ -120,10 +120,9 @@ __device__ __forceinline__ bool plan_usable(const int *status, const double *obj
     return (s == MLD_STATUS_OPTIMAL || s == MLD_STATUS_NODE_LIMIT) && fabs(obj[b]) < 1.0e300;
 }
 
-__global__ void __launch_bounds__(256) k_advance(int batch, int nx, int nv, int nw, int N, const double *pack, size_t pack_len, int model_stride,
-                                                size_t oA, size_t oB4, size_t ob5, size_t oBv, const int *model_idx, const double *x0,
-                                                const double *omega, const double *v, size_t v_stride, double *x0_new, double *omega_new,
-                                                const int *status, const double *obj, int *n_skipped)
+__global__ void __launch_bounds__(256) k_advance(int batch, int nx, int nv, int nw, int N, const double *pack, size_t pack_len, PackOff off,
+                                                const int *model_idx, const double *x0, const double *omega, const double *v, size_t v_stride,
+                                                double *x0_new, double *omega_new, const int *status, const double *obj, int *n_skipped)
 {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t nW = (size_t)N * nw;
@@ -132,14 +131,9 @@ __global__ void __launch_bounds__(256) k_advance(int batch, int nx, int nv, int 
         const int b = (int)(t / nx), i = (int)(t % nx);
         if (!plan_usable(status, obj, b)) { x0_new[t] = x0[t]; }      // no plan: the plant of this instance is not advanced
         else {
-        const int mdl = (model_idx ? model_idx[b] : 0) * model_stride;
-        const double *pk = pack + (size_t)mdl * pack_len;
+        const double *pk = pack + (size_t)(model_idx ? model_idx[b] : 0) * pack_len;
         const double *xb = x0 + (size_t)b * nx, *wb = omega + (size_t)b * nW, *vb = v + (size_t)b * v_stride;
-        double s = pk[ob5 + i];
-        for (int j = 0; j < nx; ++j) s += pk[oA + (size_t)i * nx + j] * xb[j];
-        for (int j = 0; j < nv; ++j) s += pk[oBv + (size_t)i * nv + j] * vb[j];
-        for (int j = 0; j < nw; ++j) s += pk[oB4 + (size_t)i * nw + j] * wb[j];
-        x0_new[t] = s;
+        x0_new[t] = plant_row(i, pk + off.b5, pk + off.A, pk + off.Bv, pk + off.B4, nx, nv, nw, xb, vb, wb);
         }
     }
     for (size_t e = t; e < (size_t)batch * nW; e += (size_t)gridDim.x * blockDim.x) {

@@ -4,25 +4,26 @@
 // t = b S + c; per step k
 //     omega' = [omega_k; u_k],  h_i = rs_i (Hx[i,:] x + Hw[i,:] omega' + H5[i])          the resolver's right-hand side (K3 up to summation order)
 //     sm_solve on the resolver's scaled, tightened rows with h: min sum(mu)                (small_lds.inc, unchanged)
-//     v_k = [u_k; delta; z; mu],  x_{k+1}, y_k, r with the sums of k_sim_step              (sim_step.inc, term for term)
+//     v_k = [u_k; delta; z; mu],  x_{k+1}, y_k, r by the functions k_sim_step calls        (plant_step.inc: the one definition of the sums)
 // and x never leaves the wave.  The state, omega', h, v_k, y and the next state are staged in the wave's LDS behind the solver's region:
 //     [x (nx) | omega' (nomega + nu) | h (m) | v_k (nv) | y (ny) | x_{k+1} (nx)]
 // (the last block because a lane's rows of x_{k+1} are ready while other lanes still read x).
 //
 // Mapping: one 64-lane wave per trajectory, SM_WAVES per workgroup, trajectories claimed from an atomic counter exactly as k_small_milp claims instances
-// (every lane takes part behind sm_sync(), no lane-dependent branch between the write-out and the broadcast); the waves share nothing and the kernel holds
+// (sm_claim: every lane takes part, no lane-dependent branch between the write-out and the broadcast); the waves share nothing and the kernel holds
 // no __syncthreads.  All arithmetic is fp64 on the ORIGINAL matrices of mld_model::d_pack and the resolver's fp64 maps, also on an MLD_F32 handle.  No
 // dimension is a compile-time constant: rows and columns are looped lane, lane + 64, ...  Every store is lane-contiguous.
 //
 // The per-trajectory core ro_run compiles for the host as sm_solve does (SM_HOST: a "wave" is one lane, the staging plain memory).
 #pragma once
 
+#include "plant_step.inc"
 #include "small_lds.inc"
 
 struct RoModel {      // one trajectory's model: the step matrices inside the packed block, the resolver's maps and row scales
     int nx, nu, nw, nv, nmu, ny, nc;
     int m, n;                                                              // the resolver's rows and unknowns (n = ndelta + nz + nmu; 0: nothing to resolve)
-    const double *A, *B4, *b5, *C, *D4, *d5, *E, *F4, *f5, *G, *Bv, *Dv, *Fv;
+    PlantMats P;                                                           // the step matrices inside the model's packed block (plant_mats)
     const double *Hx, *Hw, *H5, *rs;                                       // m x nx, m x (nw + nu), m, m
 };
 struct RoTraj {       // one trajectory's inputs and outputs (any output may be null)
@@ -60,6 +61,7 @@ SM_FN void ro_run(const SmShape &S, const RoModel &M, sm_f64 *mem, sm_f64 *stg, 
 {
     const int nx = M.nx, nu = M.nu, nw = M.nw, nv = M.nv, ny = M.ny, nc = M.nc, m = M.m, nw2 = M.nw + M.nu, nf = M.nv - M.nmu;
     sm_f64 *xs = stg, *ws = xs + nx, *hs = ws + nw2, *vs = hs + m, *ys = vs + nv, *xn = ys + ny;
+    const PlantMats &P = M.P;
     const double qnan = __builtin_nan("");
     A.h = (const double *)hs; A.v_out = (double *)(vs + nu); A.fixed = nullptr;
     for (int j = lane; j < nx; j += SM_W) { const double t = T.x0[j]; xs[j] = t; if (T.x) T.x[j] = t; }
@@ -88,44 +90,18 @@ SM_FN void ro_run(const SmShape &S, const RoModel &M, sm_f64 *mem, sm_f64 *stg, 
             sm_sync();
             if (res.status != MLD_STATUS_OPTIMAL) { end = res.status == MLD_STATUS_INFEASIBLE ? RO_INFEASIBLE : RO_DECLINED; break; }
         }
-        // ---- 4. x_{k+1}, y_k and the residuals: the sums of k_sim_step (sim_step.inc, "state and output rows" and "constraint rows"), term for term
-        for (int i = lane; i < nx; i += SM_W) {
-            double s = M.b5[i];
-            for (int j = 0; j < nx; ++j) s += M.A[(size_t)i * nx + j] * xs[j];
-            for (int j = 0; j < nv; ++j) s += M.Bv[(size_t)i * nv + j] * vs[j];
-            for (int j = 0; j < nw; ++j) s += M.B4[(size_t)i * nw + j] * ws[j];
-            xn[i] = s;
-        }
+        // ---- 4. x_{k+1}, y_k and the residuals: k_sim_step's, by the same functions (plant_step.inc)
+        for (int i = lane; i < nx; i += SM_W) xn[i] = plant_row(i, P.b5, P.A, P.Bv, P.B4, nx, nv, nw, xs, vs, ws);
         for (int i = lane; i < ny; i += SM_W) {
-            double s = M.d5[i];
-            for (int j = 0; j < nx; ++j) s += M.C[(size_t)i * nx + j] * xs[j];
-            for (int j = 0; j < nv; ++j) s += M.Dv[(size_t)i * nv + j] * vs[j];
-            for (int j = 0; j < nw; ++j) s += M.D4[(size_t)i * nw + j] * ws[j];
+            const double s = plant_row(i, P.d5, P.C, P.Dv, P.D4, nx, nv, nw, xs, vs, ws);
             ys[i] = s;
             if (T.y) T.y[(size_t)k * ny + i] = s;
         }
         sm_sync();
         double best = -S_INF; int brow = -1;
-        for (int i = lane; i < nc; i += SM_W) {
-            double s = 0.0;
-            for (int j = 0; j < nx; ++j) s += M.E[(size_t)i * nx + j] * xs[j];
-            for (int j = 0; j < nf; ++j) s += M.Fv[(size_t)i * nv + j] * vs[j];      /* (the Psi columns, the last nmu of a row, are skipped) */
-            for (int j = 0; j < nw; ++j) s += M.F4[(size_t)i * nw + j] * ws[j];
-            for (int j = 0; j < ny; ++j) s += M.G[(size_t)i * ny + j] * ys[j];
-            s -= M.f5[i];
-            const bool s_nan = s != s, b_nan = best != best;
-            if (brow < 0 || (!b_nan && (s_nan || s > best))) { best = s; brow = i; }      /* rows ascend: the first of equals stays */
-        }
-        for (int off = SM_W / 2; off; off >>= 1) {      /* a NaN residual wins the maximum, ties go to the lower row (k_sim_step's reduction) */
-            const double ob = sm_xor_f64(best, off); const int orow = sm_xor_i32(brow, off);
-            const bool o_nan = ob != ob, m_nan = best != best;
-            bool take;
-            if (orow < 0) take = false;
-            else if (brow < 0) take = true;
-            else if (o_nan || m_nan) take = o_nan && (!m_nan || orow < brow);
-            else take = ob > best || (ob == best && orow < brow);
-            if (take) { best = ob; brow = orow; }
-        }
+        for (int i = lane; i < nc; i += SM_W)
+            plant_worst(plant_residual(i, P.E, P.Fv, P.F4, P.G, P.f5, nx, nv, nf, nw, ny, xs, vs, ws, ys), i, best, brow);
+        for (int off = SM_W / 2; off; off >>= 1) plant_worst_merge(sm_xor_f64(best, off), sm_xor_i32(brow, off), best, brow);
         brow = sm_uniform(brow);
         // ---- 5. the reductions
         double pc = 0.0, pm = 0.0;
@@ -157,8 +133,7 @@ struct RoDev {
     int batch, S, K;
     int nx, nu, nw, nv, nmu, ny, nc, m, n;
     int stage_doubles;
-    const double *pack; size_t pack_len;
-    size_t oA, oB4, ob5, oC, oD4, od5, oE, oF4, of5, oG, oBv, oDv, oFv;      /* offsets inside a model's packed block (mld_model_create) */
+    const double *pack; size_t pack_len; PackOff off;      /* the models' packed blocks and the offsets inside one (mld_model_create) */
     const int *model_idx;
     const double *x0;                               /* (batch, nx): the handle's current state */
     const double *u; size_t u_stride, u_step;       /* the caller's (batch, K, nu): K nu, nu; the resident plan's rows: n, nv */
@@ -181,16 +156,11 @@ __global__ void __launch_bounds__(SM_NT, 3) k_rollout(SmShape S, ProblemDev P, R
     RoModel M;
     M.nx = a.nx; M.nu = a.nu; M.nw = a.nw; M.nv = a.nv; M.nmu = a.nmu; M.ny = a.ny; M.nc = a.nc; M.m = a.m; M.n = a.n;
     for (;;) {
-        // the claim of k_small_milp: every lane takes part behind a convergent barrier (DESIGN section 6, "A trap worth remembering")
-        sm_sync();
-        unsigned long long t = atomicAdd(a.counter, lane == 0 ? 1ull : 0ull);
-        t = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(t >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)t);
+        const unsigned long long t = sm_claim(a.counter, lane);
         if (t >= total) break;
         const long long b = (long long)(t / (unsigned)a.S);
         const int mdl = a.model_idx ? a.model_idx[b] : 0;
-        const double *pk = a.pack + (size_t)mdl * a.pack_len;
-        M.A = pk + a.oA; M.B4 = pk + a.oB4; M.b5 = pk + a.ob5; M.C = pk + a.oC; M.D4 = pk + a.oD4; M.d5 = pk + a.od5;
-        M.E = pk + a.oE; M.F4 = pk + a.oF4; M.f5 = pk + a.of5; M.G = pk + a.oG; M.Bv = pk + a.oBv; M.Dv = pk + a.oDv; M.Fv = pk + a.oFv;
+        M.P = plant_mats(a.pack + (size_t)mdl * a.pack_len, a.off);
         SmArgs A{};
         if (a.n) {
             const size_t m = a.m, n = a.n;
@@ -207,7 +177,7 @@ __global__ void __launch_bounds__(SM_NT, 3) k_rollout(SmShape S, ProblemDev P, R
         T.y = a.y ? a.y + (size_t)t * a.K * a.ny : nullptr; T.vio = a.vio ? a.vio + (size_t)t * a.K : nullptr; T.row = a.row ? a.row + (size_t)t * a.K : nullptr;
         RoResult R;
         if (a.status && !plan_usable(a.status, a.obj, (int)b)) {      /* uniform over the wave: no plan whose inputs could be applied */
-            const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+            const double qnan = __builtin_nan("");
             ro_blank(M, T, lane, 0, true);
             R.cost = R.mu_total = R.worst_vio = qnan; R.worst_step = R.worst_row = -1; R.steps_done = 0; R.end_status = RO_NOT_ATTEMPTED;
         } else

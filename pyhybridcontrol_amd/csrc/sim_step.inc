@@ -7,8 +7,8 @@
 //     cons_vio = max_i r_i ,  cons_row = the lowest row that attains it                              (-inf, -1 without rows; a NaN residual wins: a flag that
 //                                                                                                      cannot be computed must not read as "consistent")
 // omega is the forecast's step 0 or, under MLD_SIM_ACTUAL, one element run of the profile library (the window rule of profiles.inc with one step).
-// Everything is fp64 on the ORIGINAL matrices of mld_model::d_pack, also on an MLD_F32 handle.  The sums of x_k1 are those of k_advance term for term
-// (start from b5_i, then A, Bv, B4, j ascending, s += a * b), so an advance through this kernel leaves the bits k_advance leaves.
+// Everything is fp64 on the ORIGINAL matrices of mld_model::d_pack, also on an MLD_F32 handle.  The sums and the rules of the maximum are plant_step.inc's,
+// the one definition k_advance and k_rollout call too, so an advance through this kernel leaves the bits k_advance leaves.
 //
 // Mapping: one 64-lane wave per instance, four per workgroup, workgroups stride over the batch.  A step is a handful of short dot products per instance
 // (cfg4: 7 + 1 + 20 rows over 38 terms): the model's matrices stay in cache, the traffic is the instance's own [x; v0; omega] and its record.  The wave
@@ -24,7 +24,7 @@
 struct SimStepArgs {
     int batch, nx, nv, nmu, nw, ny, nc, N, lds;
     const double *pack; size_t pack_len;
-    size_t oA, oB4, ob5, oC, oD4, od5, oE, oF4, of5, oG, oBv, oDv, oFv;      /* offsets inside a model's packed block (mld_model_create) */
+    PackOff off;                                /* offsets inside a model's packed block (mld_model_create) */
     const int *model_idx;
     const double *x0, *omega;                   /* current inputs: (batch, nx), (batch, N nw) */
     const double *v; size_t v_stride;           /* step-0 slices are the first nv entries of a row */
@@ -46,7 +46,7 @@ __global__ void __launch_bounds__(64 * SS_WAVES) k_sim_step(const SimStepArgs a)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nx = a.nx, nv = a.nv, nw = a.nw, ny = a.ny, nc = a.nc, nf = a.nv - a.nmu;
     const size_t nW = (size_t)a.N * nw;
-    const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+    const double qnan = __builtin_nan("");
     double *const xs = ss_lds + (size_t)wave * (nx + nv + nw + ny), *const vs = xs + nx, *const ws = vs + nv, *const ys = ws + nw;
     for (long long base = (long long)blockIdx.x * SS_WAVES; base < a.batch; base += (long long)gridDim.x * SS_WAVES) {      /* uniform over the workgroup */
         const long long b = base + wave;
@@ -79,18 +79,12 @@ __global__ void __launch_bounds__(64 * SS_WAVES) k_sim_step(const SimStepArgs a)
         /* ---- state and output rows --------------------------------------------------------------------------------------------------------- */
         if (live) {
             for (int i = lane; i < nx; i += 64) {
-                double s = pk[a.ob5 + i];
-                for (int j = 0; j < nx; ++j) s += pk[a.oA + (size_t)i * nx + j] * xr[j];
-                for (int j = 0; j < nv; ++j) s += pk[a.oBv + (size_t)i * nv + j] * vr[j];
-                for (int j = 0; j < nw; ++j) s += pk[a.oB4 + (size_t)i * nw + j] * wr[j];
+                const double s = plant_row(i, pk + a.off.b5, pk + a.off.A, pk + a.off.Bv, pk + a.off.B4, nx, nv, nw, xr, vr, wr);
                 if (a.x_k1) a.x_k1[b * nx + i] = usable ? s : qnan;
                 if (a.x0_new) a.x0_new[b * nx + i] = usable ? s : xg[i];      /* no plan: the plant of this instance is not advanced */
             }
             for (int i = lane; i < ny; i += 64) {
-                double s = pk[a.od5 + i];
-                for (int j = 0; j < nx; ++j) s += pk[a.oC + (size_t)i * nx + j] * xr[j];
-                for (int j = 0; j < nv; ++j) s += pk[a.oDv + (size_t)i * nv + j] * vr[j];
-                for (int j = 0; j < nw; ++j) s += pk[a.oD4 + (size_t)i * nw + j] * wr[j];
+                const double s = plant_row(i, pk + a.off.d5, pk + a.off.C, pk + a.off.Dv, pk + a.off.D4, nx, nv, nw, xr, vr, wr);
                 if (a.lds) ys[i] = s; else a.y_tmp[b * ny + i] = s;
                 if (a.y) a.y[b * ny + i] = usable ? s : qnan;
             }
@@ -106,27 +100,12 @@ __global__ void __launch_bounds__(64 * SS_WAVES) k_sim_step(const SimStepArgs a)
         double best = -INFINITY; int brow = -1;
         if (live) {
             for (int i = lane; i < nc; i += 64) {
-                double s = 0.0;
-                for (int j = 0; j < nx; ++j) s += pk[a.oE + (size_t)i * nx + j] * xr[j];
-                for (int j = 0; j < nf; ++j) s += pk[a.oFv + (size_t)i * nv + j] * vr[j];      /* (the Psi columns, the last nmu of a row, are skipped) */
-                for (int j = 0; j < nw; ++j) s += pk[a.oF4 + (size_t)i * nw + j] * wr[j];
-                for (int j = 0; j < ny; ++j) s += pk[a.oG + (size_t)i * ny + j] * yr[j];
-                s -= pk[a.of5 + i];
+                const double s = plant_residual(i, pk + a.off.E, pk + a.off.Fv, pk + a.off.F4, pk + a.off.G, pk + a.off.f5, nx, nv, nf, nw, ny, xr, vr, wr, yr);
                 if (a.cons) a.cons[b * nc + i] = (usable && s <= 1.0e-6) ? 1 : 0;
-                const bool s_nan = s != s, b_nan = best != best;
-                if (brow < 0 || (!b_nan && (s_nan || s > best))) { best = s; brow = i; }      /* rows ascend: the first of equals stays */
+                plant_worst(s, i, best, brow);
             }
         }
-        for (int off = 32; off; off >>= 1) {
-            const double ob = __shfl_xor(best, off); const int orow = __shfl_xor(brow, off);
-            const bool o_nan = ob != ob, m_nan = best != best;
-            bool take;
-            if (orow < 0) take = false;
-            else if (brow < 0) take = true;
-            else if (o_nan || m_nan) take = o_nan && (!m_nan || orow < brow);
-            else take = ob > best || (ob == best && orow < brow);
-            if (take) { best = ob; brow = orow; }
-        }
+        for (int off = 32; off; off >>= 1) plant_worst_merge(__shfl_xor(best, off), __shfl_xor(brow, off), best, brow);
         if (live && lane == 0) {
             if (a.vio) a.vio[b] = usable ? best : qnan;
             if (a.row) a.row[b] = usable ? brow : -1;

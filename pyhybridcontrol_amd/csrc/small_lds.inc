@@ -349,6 +349,22 @@ SM_FN void sm_solve(const SmShape &S, sm_f64 *mem, const SmArgs &A, int lane, Sm
 }
 
 #ifndef SM_HOST
+// A wave's next ticket of a work counter, uniform over the wave (k_small_milp's instances, k_rollout's trajectories).
+// Every lane takes part in the claim (lane 0 adds 1, the others 0) behind a convergent barrier.  With `if (lane == 0) t = atomicAdd(...)` at the head
+// of the work loop and an `if (lane == 0)` write-out at its end, the compiler threaded the other 63 lanes round the loop AHEAD of lane 0 (for them
+// t is the constant 0): readfirstlane then read lane 1's zero, and the wave solved instance 0 for ever.
+SM_FN int sm_claim(int *counter, int lane)
+{
+    sm_sync();
+    return sm_uniform(atomicAdd(counter, lane == 0 ? 1 : 0));
+}
+SM_FN unsigned long long sm_claim(unsigned long long *counter, int lane)      // (the broadcast moves 32 bits: two halves)
+{
+    sm_sync();
+    const unsigned long long t = atomicAdd(counter, lane == 0 ? 1ull : 0ull);
+    return ((unsigned long long)(unsigned)sm_uniform((int)(t >> 32)) << 32) | (unsigned)sm_uniform((int)t);
+}
+
 __global__ void __launch_bounds__(SM_NT) k_small_milp(SmShape S, ProblemDev P, BatchDev B, int *declined)
 {
     extern __shared__ double sm_lds[];
@@ -356,12 +372,7 @@ __global__ void __launch_bounds__(SM_NT) k_small_milp(SmShape S, ProblemDev P, B
     sm_f64 *mem = (sm_f64 *)sm_lds + (size_t)wave * S.wave_doubles;
     const int n = S.n, m = S.m;
     for (;;) {
-        // Every lane takes part in the claim (lane 0 adds 1, the others 0) behind a convergent barrier.  With `if (lane == 0) inst = atomicAdd(...)`
-        // here and the `if (lane == 0)` write-out at the loop's end, the compiler threaded the other 63 lanes round the loop AHEAD of lane 0 (for them
-        // inst is the constant 0): readfirstlane then read lane 1's zero, and the wave solved instance 0 for ever.
-        sm_sync();
-        int inst = atomicAdd(B.counter, lane == 0 ? 1 : 0);
-        inst = __builtin_amdgcn_readfirstlane(inst);
+        const int inst = sm_claim(B.counter, lane);
         if (inst >= B.batch) break;
         const long long t_begin = wall_clock64();
         const int mdl = B.model_idx ? B.model_idx[inst] : 0;

@@ -55,7 +55,7 @@ int main()
         S.wave_doubles = (int)sm_wave_doubles(n, m, 1);
         RoModel M{};
         M.nx = nx; M.nu = nu; M.nw = nw; M.nv = nv; M.nmu = nmu; M.ny = ny; M.nc = nc; M.m = m; M.n = n;
-        M.A = A; M.B4 = B4; M.b5 = b5; M.C = C; M.D4 = D4; M.d5 = d5; M.E = E; M.F4 = F4; M.f5 = f5; M.G = Gy; M.Bv = Bv; M.Dv = Dv; M.Fv = Fv.data();
+        M.P = PlantMats{A, B4, b5, C, D4, d5, E, F4, f5, Gy, Bv, Dv, Fv.data()};
         M.Hx = Hx.data(); M.Hw = Hw.data(); M.H5 = H5.data(); M.rs = rs.data();
         SmArgs Aa{};
         Aa.G = G.data(); Aa.q = q; Aa.lb = lb; Aa.ub = ub; Aa.cs = cs; Aa.is_int = is_int; Aa.bins = bins;
@@ -90,7 +90,7 @@ int main()
     {
         const double A[1] = {0.5}, B4[1] = {0}, b5[1] = {0.5}, Bv[1] = {1}, u[3] = {1, 2, 3}, om[3] = {0, 0, 0}, x0[1] = {2};
         RoModel M{};
-        M.nx = 1; M.nu = 1; M.nw = 1; M.nv = 1; M.A = A; M.B4 = B4; M.b5 = b5; M.Bv = Bv;
+        M.nx = 1; M.nu = 1; M.nw = 1; M.nv = 1; M.P.A = A; M.P.B4 = B4; M.P.b5 = b5; M.P.Bv = Bv;
         SmShape S{}; SmArgs Aa{};
         std::vector<double> stg(ro_stage_doubles(1, 1, 1, 0, 1, 0)), x(4), vio(3); std::vector<int> row(3);
         RoTraj T{};

@@ -2,7 +2,9 @@
 lsim_k in a loop (models/mld_model.py:543-642, 647-699) with _compute_aux (:701-766) at every step, batch x S trajectories in one launch.  The yardstick is
 the stepwise route the library already has -- K advancing sim_step(resolve=R) calls per realisation over the same flagged resolver --; every returned step
 is checked against the model in numpy and the closed form of tests/_aux_ref.py; then start against omega_seq, determinism and position independence, the
-reductions, every ending, the host completion of declined trajectories, the untouched handle and every refusal.
+reductions, every ending, the host completion of declined trajectories, the untouched handle and every refusal.  Last, what the one definition of the
+plant step's sums (csrc/plant_step.inc) must keep: the rollout's plant rows equal k_sim_step's bit for bit given the same v_k, also without auxiliaries at
+nc = 70 (lanes take a second row), and the largest residual's NaN and tie rules in both kernels.
 
 Shapes (tests/test_gpu_sim_resolve.py): a10 -- n_h 3, three models interleaved, N_tilde 3, batch 10; a1 -- batch 1 (three of the four waves of the only
 workgroup find no work); b9 -- n_h 7, batch 9.  S = 3 realisations, so batch x S is no multiple of the four waves of a workgroup for a10 and b9."""
@@ -11,8 +13,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import _paths
 import _rollout_ref
-from test_gpu_sim_resolve import SHAPES
+from test_gpu_sim_resolve import NO_LDS, SHAPES
 from test_gpu_small_lds_step import _SmallCtx
 from pyhybridcontrol_amd import gpu, simlog, _lib
 from pyhybridcontrol_amd.aux_resolve import BatchAuxResolver
@@ -405,3 +408,180 @@ def test_refusals_change_nothing(ctx):
     finally:
         plain.close(); tv.close(); tv_model.close()
         p.upload_profiles(np.zeros(0))
+
+
+# ---- the plant step's arithmetic is ONE definition (csrc/plant_step.inc): the rollout's rows against k_sim_step's, bit for bit ----------------------------
+def _by_sim_step(p, got, om_seq, forecast, midx):
+    """per realisation and step the what-if sim_step(v0 = the rollout's v_k) on the rollout's own x_k, with omega_k as the forecast's step 0:
+    dict(x_k1, y, cons_vio, cons_row) shaped (B, S, K, ...) like the rollout's arrays"""
+    K, nw = got["v"].shape[2], om_seq.shape[-1]
+    ref = dict(x_k1=np.zeros_like(got["x"][:, :, 1:]), y=np.zeros_like(got["y"]), cons_vio=np.zeros_like(got["cons_vio"]), cons_row=np.zeros_like(got["cons_row"]))
+    for cc in range(got["v"].shape[1]):
+        for k in range(K):
+            om = forecast.copy()
+            om[:, :nw] = om_seq[:, cc, k]
+            p.upload(np.ascontiguousarray(got["x"][:, cc, k]), om, midx)
+            o = p.sim_step(v0=np.ascontiguousarray(got["v"][:, cc, k]), advance=False, log=False, outputs=True)
+            assert o["n_skipped"] == 0
+            for name in ref:
+                ref[name][:, cc, k] = o[name]
+    return ref
+
+
+def _same_plant_rows(got, ref, what):
+    assert np.array_equal(got["x"][:, :, 1:], ref["x_k1"]), (what, "x_k1")
+    for name in ("y", "cons_vio", "cons_row"):
+        assert np.array_equal(got[name], ref[name], equal_nan=name == "cons_vio"), (what, name)
+
+
+@pytest.mark.parametrize("shape", ["a10", "b9"])
+def test_plant_rows_equal_sim_step_bit_for_bit(ctx, shape):
+    """given the same v_k the two kernels run the same sums (the 1e-6 of the stepwise comparison belongs to the right-hand side's order alone)"""
+    c = ctx(shape)
+    p, K = c.p, 3
+    _, _, _, om_seq, u_seq = _scenario(c, K, 9900 + list(SHAPES).index(shape))
+    p.upload(c.x0, c.om, c.midx)
+    got = p.rollout(c.R, u_seq=u_seq, omega_seq=om_seq, trajectories=True)
+    assert got["stats"]["complete"] == c.B * S and got["x"].shape == (c.B, S, K + 1, c.nx)
+    _same_plant_rows(got, _by_sim_step(p, got, om_seq, c.om, c.midx), shape)
+
+
+# no auxiliaries, a row family above the wave (nc = 70: lanes take a second constraint row) and nx + nv + nomega = 97 staged values (tests/test_gpu_sim_step.py: BIG)
+PLAIN = dict(nx=17, nu=40, nomega=40, ny=4, nc=70)
+PLAIN_N = 2
+J0 = 7      # the disturbance channel that is exactly 0 in test_merge_rules_*
+
+
+class _Plain(object):
+    def __init__(self, mats):
+        self.d = _paths.make_dims(**PLAIN)
+        self.model = gpu.GpuModel(mats, self.d)
+        self.p = gpu.GpuProblem(self.model, PLAIN_N - 1, PLAIN_N, None)
+
+    def close(self):
+        self.p.close(); self.model.close()
+
+
+def _plain_inputs(seed, B, n_real, K, zero_channel=None):
+    rng = np.random.default_rng(seed)
+    x0, forecast = rng.standard_normal((B, PLAIN["nx"])), rng.standard_normal((B, PLAIN_N, PLAIN["nomega"]))
+    u_seq, om_seq = rng.standard_normal((B, K, PLAIN["nu"])), rng.standard_normal((B, n_real, K, PLAIN["nomega"]))
+    if zero_channel is not None:
+        forecast[..., zero_channel] = 0.0
+        om_seq[..., zero_channel] = 0.0
+    return x0, forecast.reshape(B, -1), u_seq, om_seq, (np.arange(B) % 2).astype(np.int32)
+
+
+def test_no_auxiliaries_rows_beyond_the_wave():
+    """aux=None at nc = 70: bit for bit the what-if sim_step(v0=u_k) per realisation and step, and simlog.rollout_np within the bound of
+    tests/test_gpu_sim_step.py::test_kernel_against_numpy -- simlog.sum_bound(dims) times the row's sum of |terms| -- carried along the chain: the state the
+    step starts from may differ by the previous step's bound e, which adds |A| e, |C| e and (|E| + |G| |C|) e to the rows (first order, as the bound itself)"""
+    d = _paths.make_dims(**PLAIN)
+    nx, nu, nw, ny = d["nx"], d["nu"], d["nomega"], d["ny"]
+    assert 8 * ((2 * nx + nw + nu + 0 + nu + ny + 1) & ~1) <= 16 * 1024      # ro_stage_doubles(nx, nu, nw, 0, nv, ny) against SM_WAVE_BUDGET
+    mats = [_paths.random_mld(9910 + i, rho=0.9, **PLAIN)[0] for i in range(2)]
+    B, n_real, K = 5, 3, 2
+    T = B * n_real
+    x0, forecast, u_seq, om_seq, midx = _plain_inputs(9912, B, n_real, K)
+    c = _Plain(mats)
+    try:
+        c.p.upload(x0, forecast, midx)
+        got = c.p.rollout(None, u_seq=u_seq, omega_seq=om_seq, trajectories=True)
+        assert got["stats"] == dict(trajectories=T, complete=T, infeasible=0, declined=0, not_attempted=0, finished_on_host=0)
+        assert np.array_equal(got["v"], np.broadcast_to(u_seq[:, None], got["v"].shape)) and np.all(got["mu_total"] == 0.0) and np.all(got["steps_done"] == K)
+        _same_plant_rows(got, _by_sim_step(c.p, got, om_seq, forecast, midx), "plain")
+    finally:
+        c.close()
+    ref = simlog.rollout_np(mats, d, midx, x0, u_seq, om_seq, None)
+    bound = simlog.sum_bound(d)
+    mT = np.repeat(midx, n_real)
+    absm = {name: np.stack([np.abs(m[name]) for m in mats])[mT] for name in ("A", "C", "E", "G")}
+    through = lambda name, e: np.einsum("tij,tj->ti", absm[name], e)
+    flat = lambda a: a.reshape((T,) + a.shape[2:])
+    e_x = np.zeros((T, nx))
+    for k in range(K):
+        st = simlog.lsim_k_batch(mats, d, mT, flat(ref["x"])[:, k], np.repeat(u_seq[:, k], n_real, axis=0), flat(om_seq)[:, k])
+        tol_x, tol_y = bound * st["terms_x"] + through("A", e_x), bound * st["terms_y"] + through("C", e_x)
+        tol_r = (bound * st["terms_r"] + through("E", e_x) + through("G", through("C", e_x))).max(axis=1)
+        err_x, err_y = np.abs(flat(got["x"])[:, k + 1] - flat(ref["x"])[:, k + 1]), np.abs(flat(got["y"])[:, k] - flat(ref["y"])[:, k])
+        err_r = np.abs(flat(got["cons_vio"])[:, k] - flat(ref["cons_vio"])[:, k])
+        print("step %d: worst err / tolerance  x %.3f  y %.3f  cons_vio %.3f" % (k, (err_x / tol_x).max(), (err_y / tol_y).max(), (err_r / tol_r).max()))
+        assert np.all(err_x <= tol_x) and np.all(err_y <= tol_y) and np.all(err_r <= tol_r), k
+        r = np.sort(st["resid"], axis=1)
+        clear = r[:, -1] - r[:, -2] > 2 * tol_r                                # the largest residual leads by more than both routes' rounding
+        assert clear.any() and np.array_equal(flat(got["cons_row"])[clear, k], flat(ref["cons_row"])[clear, k]), k
+        e_x = tol_x
+
+
+def _edited(seed, edit):
+    mats = {k: np.array(v, copy=True) for k, v in _paths.random_mld(seed, rho=0.9, **PLAIN)[0].items()}
+    edit(mats)
+    return mats
+
+
+def _merge_rules(mats, rows, nan):
+    """sim_step with the LDS staging and without, and the rollout, on two interleaved models whose largest residual sits at rows[model]; nan: it is a NaN"""
+    d = _paths.make_dims(**PLAIN)
+    B, n_real, K = 4, 2, 2
+    x0, forecast, u_seq, om_seq, midx = _plain_inputs(9930, B, n_real, K, zero_channel=J0)
+    om_seq[:, 0, 0] = forecast[:, :d["nomega"]]                                # trajectory (b, 0) starts with the step sim_step takes
+    want = np.array(rows, np.int32)[midx]
+    with np.errstate(invalid="ignore"):
+        st = simlog.lsim_k_batch(mats, d, midx, x0, u_seq[:, 0], forecast[:, :d["nomega"]])
+    at = np.arange(B)
+    if nan:      # the construction: the wanted row is the only NaN, and a finite residual larger than every other sits at row 2
+        assert np.all(np.isnan(st["resid"][at, want])) and np.all(np.isnan(st["resid"]).sum(axis=1) == 1) and np.all(np.nanargmax(st["resid"], axis=1) == 2)
+    else:        # the construction: the maximum is attained twice, first at the wanted row
+        assert np.array_equal(st["cons_row"], want) and np.all((st["resid"] == st["cons_vio"][:, None]).sum(axis=1) == 2)
+    c = _Plain(mats)
+    try:
+        p = c.p
+        p.upload(x0, forecast, midx)
+        steps = []
+        for reserved in (0, NO_LDS):
+            p.set_opts(reserved=reserved)
+            steps.append(p.sim_step(v0=u_seq[:, 0], advance=False, log=False, outputs=True))
+        p.set_opts(reserved=0)
+        got = p.rollout(None, u_seq=u_seq, omega_seq=om_seq, trajectories=True)
+    finally:
+        c.close()
+    for o, what in zip(steps, ("LDS", "global memory")):
+        assert np.array_equal(o["cons_row"], want), what
+        if nan:
+            assert np.all(np.isnan(o["cons_vio"])) and not o["cons"][at, want].any(), what
+        else:
+            assert np.all(np.abs(o["cons_vio"] - st["cons_vio"]) <= simlog.sum_bound(d) * st["terms_r"][at, want]), what
+            assert np.array_equal(o["cons_vio"], steps[0]["cons_vio"]), what
+    assert np.all(got["end_status"] == 0)
+    assert np.array_equal(got["cons_row"], np.broadcast_to(want[:, None, None], got["cons_row"].shape))
+    if nan:
+        assert np.all(np.isnan(got["cons_vio"])) and np.all(np.isnan(got["worst_vio"])) and np.all(got["worst_step"] == 0)      # (the earliest step of equals)
+        assert np.all(np.isfinite(got["x"])) and np.all(np.isfinite(got["y"]))
+    else:
+        assert np.array_equal(got["cons_vio"][:, 0, 0], steps[0]["cons_vio"])
+        assert np.array_equal(got["worst_vio"], got["cons_vio"].max(axis=2)) and np.array_equal(got["worst_step"], got["cons_vio"].argmax(axis=2))
+
+
+def _tie(lo, hi):
+    def edit(m):
+        for name in ("E", "F1", "F4", "G", "f5"):
+            m[name][hi] = m[name][lo]
+        m["f5"][lo] = m["f5"][hi] = -1.0e3      # residual about +1e3: above every other row
+    return edit
+
+
+def _nan(row):
+    def edit(m):
+        m["F4"][row, J0] = np.inf              # against omega[J0] = 0: the residual of `row` is a NaN
+        m["f5"][2] = -1.0e3
+    return edit
+
+
+def test_merge_rules_ties_go_to_the_lower_row():
+    """equal residuals: rows 3 and 67 are two passes of ONE lane (the first of equals stays), rows 9 and 40 sit in two lanes (the merge prefers the lower row)"""
+    _merge_rules([_edited(9920, _tie(3, 67)), _edited(9921, _tie(9, 40))], (3, 9), nan=False)
+
+
+def test_merge_rules_a_nan_wins():
+    """a NaN residual beats the finite larger one at row 2: row 66 is lane 2's own second pass, row 50 another lane's"""
+    _merge_rules([_edited(9922, _nan(66)), _edited(9923, _nan(50))], (66, 50), nan=True)
