@@ -606,6 +606,49 @@ int mld_rollout_batch(mld_problem_t *p, mld_problem_t *aux, int K, int S, const 
                       double *cost_out, double *mu_total_out, double *worst_vio_out, int32_t *worst_step_out, int32_t *steps_done_out,
                       int32_t *end_status_out, int64_t stats[4]);
 
+/* ---- rule-based feedback (thermostat) policies ------------------------------------------------------------------------------------------------------
+ * The reference's simulation campaign quotes every saving of its MPC variants against `thermo`, DewhTheromstatController (examples/
+ * residential_mg_with_pv_and_dewhs/controllers/theromstat_control.py:38-64): a hysteresis rule u_k = f(x_k, u_{k-1}) per tank, stepped through sim_step_k
+ * (controllers/controller_base.py:229-253) like every other controller.  Here the rule is data per model m and input channel j:
+ *     sel (n_models, nu, nx) selector rows; on_at, off_at, u_on, u_off (n_models, nu); mode (n_models, nu): 0 the channel is passed through -- its value
+ *     comes from u_seq / u0 / the resident plan exactly as without a policy --, 1 it is ruled.
+ * For a ruled channel, with s = sum_i sel[m,j,i] x[i] (fp64, i ascending), in this order (:53-58):
+ *     s <= on_at -> u_on;   s >= off_at -> u_off;   u_prev[j] == u_on -> u_on (exact equality, the reference's `== 1`);   otherwise u_off.
+ * A NaN s falls through to the last two lines, as in the reference; on_at <= off_at is required, and at equality the first line wins.
+ *
+ * mld_upload_policy: the tables, n_models rows each, owned by the PROBLEM and independent of the batch, like the profile library; sel == NULL removes the
+ * policy.  Validated on the host: every value finite, on_at <= off_at, mode 0 or 1 (MLD_ERR_INVALID, the resident policy stays).  A new policy resets the
+ * resident policy state.
+ * mld_set_policy_state / mld_download_policy_state: the resident u_prev (batch, nu), the input applied before the next step.  u_prev == NULL resets every
+ * ruled channel to its model's u_off (a passed-through one to 0): the state after any mld_upload_batch -- the reference's first step has no previous
+ * record, so `u_k_neg1 == 1` is false (:57).  MLD_ERR_INVALID: no resident batch, no policy, a u_prev that is not finite.
+ *
+ * mld_rollout_policy: mld_rollout_batch with the rule in the loop (kernel k_rollout_policy, the second instantiation of k_rollout's body) -- the K-step,
+ * S-realisation Monte-Carlo of the baseline in one launch, where the reference runs lsim_k per device, step and realisation.  Trajectories, endings,
+ * statuses and outputs mean what they mean for mld_rollout_batch.  At step k the ruled channels take the rule's value from the trajectory's own x_k and its
+ * own u_{k-1}; before step 0 that is u_prev (batch, nu), or, if NULL, the resident policy state.  u_seq supplies the passed-through channels (its ruled
+ * channels are ignored but must be finite); u_seq == NULL with every channel ruled needs no plan and attempts every instance, with any passed-through
+ * channel it takes those channels from the resident plan under mld_rollout_batch's rules (K <= N_tilde, an unusable plan: -1).  switches_out (batch, S)
+ * int32 counts the (step, ruled channel) pairs with u_k[j] != u_{k-1}[j], -1 unless the trajectory ended 0.  The call changes nothing on the handle, the
+ * resident policy state included.  MLD_ERR_INVALID before anything is queued: everything mld_rollout_batch refuses; no policy; a u_prev that is not finite.
+ *
+ * mld_sim_step_policy: ONE resolving plant step, mld_sim_step_resolve's own phases behind a kernel that writes u (k_policy_inputs, threads on (instance,
+ * channel)) from the handle's current x0, the resident u_prev and the tables into the buffer the step reads its u0 from.  u0 supplies the passed-through
+ * channels; NULL follows the rollout's rules: the resident plan for them, or no plan needed when every channel is ruled.  With MLD_SIM_ADVANCE the resident
+ * u_prev of every ADVANCED instance becomes the u applied (skipped instances keep theirs); without it the state is not written (the what-if).  aux == NULL
+ * for models without auxiliaries: the step is then mld_sim_step_batch with v0 = u.  With MLD_SIM_LOG the record is what the resolving step writes.
+ * Outputs and refusals as mld_sim_step_resolve, plus: no policy uploaded. */
+int mld_upload_policy(mld_problem_t *p, const double *sel, const double *on_at, const double *off_at, const double *u_on, const double *u_off, const int32_t *mode);
+int mld_set_policy_state(mld_problem_t *p, const double *u_prev);
+int mld_download_policy_state(mld_problem_t *p, double *u_prev_out);
+int mld_rollout_policy(mld_problem_t *p, mld_problem_t *aux, int K, int S, const double *u_seq, const double *u_prev, const double *omega_seq, const int64_t *start,
+                       int step, const double *cost_w, int cost_rows, double *x_out, double *v_out, double *y_out, double *cons_vio_out, int32_t *cons_row_out,
+                       double *cost_out, double *mu_total_out, double *worst_vio_out, int32_t *worst_step_out, int32_t *steps_done_out,
+                       int32_t *end_status_out, int32_t *switches_out, int64_t stats[4]);
+int mld_sim_step_policy(mld_problem_t *p, mld_problem_t *aux, const double *u0, const int64_t *act_start, int step, int flags,
+                        double *x_k1_out, double *y_out, uint8_t *cons_out, double *cons_vio_out, int32_t *cons_row_out,
+                        double *v0_out, int32_t *aux_status_out, int32_t *n_skipped_out);
+
 /* Per-instance telemetry of the last solve: time spent inside the solve kernel (device wall clock, ns) and
  * the number of dictionary rows the rank-1 updates touched (x *row_bytes x 2 = bytes streamed by pivots). */
 int mld_download_telemetry(mld_problem_t *, int64_t *latency_ns, int64_t *rows_updated, int64_t *row_bytes);

@@ -59,6 +59,7 @@ EXPORTS = ("mld_device_count", "mld_set_device", "mld_last_error", "mld_version"
            "mld_upload_profiles", "mld_forecast_from_profiles", "mld_constraint_blocks_from_profiles", "mld_evaluate_batch_profiles", "mld_download_constraint_blocks",
            "mld_sim_log_begin", "mld_sim_log_count", "mld_sim_step_batch", "mld_download_sim_log",
            "mld_sim_step_resolve", "mld_download_sim_log_aux", "mld_rollout_batch",
+           "mld_upload_policy", "mld_set_policy_state", "mld_download_policy_state", "mld_rollout_policy", "mld_sim_step_policy",
            "mld_comm_unique_id", "mld_comm_init", "mld_gather", "mld_comm_destroy")
 
 
@@ -93,6 +94,11 @@ def load():
     lib.mld_sim_step_resolve.argtypes = [C.c_void_p, C.c_void_p, dp, lp, C.c_int, C.c_int, dp, dp, bp, dp, ip, dp, ip, ip]
     lib.mld_download_sim_log_aux.argtypes = [C.c_void_p, C.c_int, C.c_int, ip]
     lib.mld_rollout_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, dp, dp, lp, C.c_int, dp, C.c_int, dp, dp, dp, dp, ip, dp, dp, dp, ip, ip, ip, lp]
+    lib.mld_upload_policy.argtypes = [C.c_void_p, dp, dp, dp, dp, dp, ip]
+    lib.mld_set_policy_state.argtypes = [C.c_void_p, dp]
+    lib.mld_download_policy_state.argtypes = [C.c_void_p, dp]
+    lib.mld_rollout_policy.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, dp, dp, dp, lp, C.c_int, dp, C.c_int, dp, dp, dp, dp, ip, dp, dp, dp, ip, ip, ip, ip, lp]
+    lib.mld_sim_step_policy.argtypes = list(lib.mld_sim_step_resolve.argtypes)
     if int(lib.mld_opts_size()) != C.sizeof(Opts):
         raise MldGpuError("libmldgpu.so was built with another layout of mld_opts (%d bytes, this binding %d): rebuild it (python -m pyhybridcontrol_amd.build)"
                           % (lib.mld_opts_size(), C.sizeof(Opts)))

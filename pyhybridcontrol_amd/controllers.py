@@ -697,3 +697,120 @@ class MpcController(object):
         else:
             del lsim_k["x_k1"]
         return lsim_k
+
+
+class ThresholdController(object):
+    """A non-predictive controller: u_k = f(x_k, u_{k-1}) by a policy.ThresholdPolicy, for ONE instance on the host -- the `thermo` baseline of the
+    reference's simulation campaign (its NonPredictiveController subclass, examples/residential_mg_with_pv_and_dewhs/theromstat_control.py:38-70), with
+    solve / feedback / sim_step_k / sim_log / variables_k as MpcController has them, so that it drops in beside the MPC variants.
+
+    solve(k, x_k, omega_tilde_k) takes u_{k-1} from the log's record k - 1 (no record: variables_k_neg1["u"], by default the policy's reset state -- a
+    ruled channel at u_off, so that the reference's `u_k_neg1 == 1` is false), applies the rule (policy.apply_np), and evaluates the plant once with that
+    u through MldModel.lsim_k WITHOUT stepping the state: the result is variables_k, what feedback() returns.  sim_step_k(k, ...) then steps and logs,
+    as MpcController.sim_step_k does.  model_index: the policy's row for this plant; u_pass (nu,): the values of passed-through channels (zeros)."""
+
+    def __init__(self, model, policy, x_k=None, omega_tilde_k=None, N_tilde=1, model_index=0, u_pass=None):
+        from .policy import ThresholdPolicy
+        if not isinstance(model, MldModel):
+            model = MldModel(model)
+        if not isinstance(policy, ThresholdPolicy):
+            raise TypeError("policy must be a policy.ThresholdPolicy, not %r" % type(policy).__name__)
+        info = model.mld_info
+        if (policy.nu, policy.nx) != (info.nu, info.nx) or not 0 <= int(model_index) < policy.n_models:
+            raise ValueError("the policy is shaped (n_models %d, nu %d, nx %d); the model has nu %d, nx %d, model_index %d"
+                             % (policy.n_models, policy.nu, policy.nx, info.nu, info.nx, model_index))
+        self._model = self._sim_model = model
+        self._policy, self._midx = policy, np.array([int(model_index)])
+        self._u_pass = np.zeros(info.nu) if u_pass is None else np.asarray(u_pass, dtype=np.float64).reshape(info.nu)
+        self._N_tilde = int(N_tilde)
+        self._sim_log = MldSimLog()
+        self._solve_time_overall = 0
+        self._solve_time_solver = 0
+        self.reset_components(x_k=x_k, omega_tilde_k=omega_tilde_k)
+
+    def reset_components(self, x_k=None, omega_tilde_k=None):
+        info = self.mld_info_k
+        self._x_k = np.zeros((info.nx, 1))
+        self._omega_tilde_k = np.zeros((info.nomega * self._N_tilde, 1))
+        if x_k is not None:
+            self.x_k = x_k
+        if omega_tilde_k is not None:
+            self.omega_tilde_k = omega_tilde_k
+        self._variables_k = dict(x=self._x_k, omega=self._omega_tilde_k[:info.nomega])
+        self._variables_k_neg1 = dict(u=self._policy.initial_state(self._midx).reshape(-1, 1))
+
+    mld_info_k = property(lambda self: self._model.mld_info)
+    mld_numeric_k = property(lambda self: self._model)
+    N_tilde = property(lambda self: self._N_tilde)
+    N_p = property(lambda self: self._N_tilde - 1)
+    sim_log = property(lambda self: self._sim_log)
+    policy = property(lambda self: self._policy)
+    build_required = property(lambda self: False)
+    variables_k = property(lambda self: self._variables_k)
+
+    def build(self, *args, **kwargs):
+        """nothing to build: the rule is data"""
+
+    @property
+    def x_k(self):
+        return self._x_k
+
+    @x_k.setter
+    def x_k(self, value):
+        self._x_k = MpcController._check_shape("x_k", value, (self.mld_info_k.nx, 1))
+
+    @property
+    def omega_tilde_k(self):
+        return self._omega_tilde_k
+
+    @omega_tilde_k.setter
+    def omega_tilde_k(self, value):
+        self._omega_tilde_k = MpcController._check_shape("omega_tilde_k", value, (self.mld_info_k.nomega * self._N_tilde, 1))
+
+    @property
+    def variables_k_neg1(self):
+        return self._variables_k_neg1
+
+    @variables_k_neg1.setter
+    def variables_k_neg1(self, struct):
+        self._variables_k_neg1.update({name: atleast_2d_col(val) for name, val in dict(struct).items() if val is not None})
+
+    def solve(self, k, x_k=None, omega_tilde_k=None, external_solve=None, solver=None, *args, **kwargs):
+        start = time.time()
+        try:
+            if x_k is not None:
+                self.x_k = x_k
+            if omega_tilde_k is not None:
+                self.omega_tilde_k = omega_tilde_k
+            before = self._sim_log.get(k - 1) if isinstance(k, (int, np.integer)) else None
+            if before is not None and before.get("u") is not None:
+                self._variables_k_neg1 = dict(before)
+            from .policy import apply_np
+            u_prev = np.asarray(self._variables_k_neg1["u"], dtype=np.float64).reshape(1, -1)
+            u_k = apply_np(self._policy, self._midx, self._x_k.reshape(1, -1), u_prev, self._u_pass.reshape(1, -1)).reshape(-1, 1)
+            omega_k = self._omega_tilde_k[:self.mld_info_k.nomega]
+            self._variables_k = self.sim_step_k(k=k, x_k=self._x_k, u_k=u_k, omega_k=omega_k, solver=solver, step_state=False)
+            return None
+        finally:
+            self._solve_time_overall = time.time() - start
+
+    def feedback(self, k, x_k=None, omega_tilde_k=None, external_solve=None, solver=None, *args, **kwargs):
+        self.solve(k=k, x_k=x_k, omega_tilde_k=omega_tilde_k, external_solve=external_solve, solver=solver, *args, **kwargs)
+        return self.variables_k
+
+    def sim_step_k(self, k, x_k=None, u_k=None, omega_k=None, mld_numeric_k=None, solver=None, step_state=True):
+        """one plant step through MldModel.lsim_k(x_k=, u_k=, omega_k=): delta, z, mu re-derived as the reference does at every step.  The defaults are
+        the last solve's x, u and omega; step_state logs the record k and moves x_k on."""
+        var_k = self._variables_k
+        omega_k = omega_k if omega_k is not None else var_k["omega"]
+        x_k = x_k if x_k is not None else var_k["x"]
+        u_k = u_k if u_k is not None else var_k.get("u")
+        sim_model = mld_numeric_k if mld_numeric_k is not None else self._sim_model
+        lsim_k = sim_model.lsim_k(x_k=x_k, u_k=u_k, omega_k=omega_k, solver=solver)
+        if step_state:
+            self._sim_log.set_sim_k(k=k, sim_k=lsim_k)
+            self._sim_log.update_sim_k(k=k, time_solve_overall=self._solve_time_overall, time_in_solver=self._solve_time_solver)
+            self.x_k = lsim_k["x_k1"]
+        else:
+            del lsim_k["x_k1"]
+        return lsim_k

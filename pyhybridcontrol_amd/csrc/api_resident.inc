@@ -625,15 +625,19 @@ static int aux_fold_check(const char *who, const char *what, const mld_problem_t
  * resolver's handle (aux_resolve.BatchAuxResolver: the folded models, N_tilde = 1, min sum(mu)); the call keeps no pointer to it.  Three phases, the host
  * waiting between them (the two handles may run on streams of their own): k_aux_inputs writes the resolver's inputs; the resolver's launch / finish solves
  * them; k_aux_merge builds v0 = [u; delta; z; mu] and k_sim_step steps on it.  Kernels: aux_step.inc.  p's inputs, log count and actual starts change only
- * when the last phase has been queued without an error. */
-int mld_sim_step_resolve(mld_problem_t *p, mld_problem_t *aux, const double *u0, const int64_t *act_start, int step, int flags,
-                         double *x_k1_out, double *y_out, uint8_t *cons_out, double *cons_vio_out, int32_t *cons_row_out,
-                         double *v0_out, int32_t *aux_status_out, int32_t *n_skipped_out)
+ * when the last phase has been queued without an error.
+ *
+ * policy (mld_sim_step_policy): the same phases with one kernel in front -- k_policy_inputs writes the ruled channels of u, from the handle's current x0, the
+ * resident u_prev and the policy tables, into the buffer the phases read u0 from; u0 / the resident plan supply the passed-through channels only, and no plan
+ * is needed when every channel is ruled.  After an advancing step the resident u_prev of every ADVANCED instance becomes the u applied (k_policy_commit). */
+static int sim_step_resolve_impl(const char *who, bool policy, mld_problem_t *p, mld_problem_t *aux, const double *u0, const int64_t *act_start, int step, int flags,
+                                 double *x_k1_out, double *y_out, uint8_t *cons_out, double *cons_vio_out, int32_t *cons_row_out,
+                                 double *v0_out, int32_t *aux_status_out, int32_t *n_skipped_out)
 {
-    static const char who[] = "mld_sim_step_resolve";
-    if (int rc = entry_guard(p, who, true, "no batch resident (mld_upload_batch)")) return rc;
+    if (policy && !p->pol_on) { mld_set_error("%s: no policy uploaded (mld_upload_policy)", who); return MLD_ERR_INVALID; }
+    const bool by_plan = !u0 && !(policy && p->pol_all_ruled);      /* some channel of u is the resident plan's */
     std::vector<long long> gmax;
-    if (int rc = sim_step_check(p, who, u0 != nullptr, "u0", act_start, step, flags, gmax)) return rc;
+    if (int rc = sim_step_check(p, who, !by_plan, "u0", act_start, step, flags, gmax)) return rc;
     const mld_dims &d = p->model->dims;
     const int batch = p->batch, nx = d.nx, nu = d.nu, nw = d.nomega, nv = p->nv, nv2 = d.ndelta + d.nz + d.nmu;
     const bool actual = flags & MLD_SIM_ACTUAL, log = flags & MLD_SIM_LOG;
@@ -653,7 +657,8 @@ int mld_sim_step_resolve(mld_problem_t *p, mld_problem_t *aux, const double *u0,
         L.aux = std::move(la);
     }
     DevBuf<double> d_u, d_v0; DevBuf<unsigned char> d_mask; DevBuf<int> d_auxst; DevBuf<long long> d_start;
-    if (u0) HIP_TRY(d_u.alloc((size_t)batch * std::max(1, nu)));
+    if (policy) { if (int rc = policy_state_ready(p, who)) return rc; }
+    if (u0 || policy) HIP_TRY(d_u.alloc((size_t)batch * std::max(1, nu)));
     if (act_start) HIP_TRY(d_start.alloc((size_t)batch * p->pf_groups));
     HIP_TRY(d_v0.alloc((size_t)batch * std::max(1, nv))); HIP_TRY(d_mask.alloc(batch)); HIP_TRY(d_auxst.alloc(batch));
     if (aux && (aux->batch != batch || aux->aux_src_gen != p->batch_gen || aux->aux_own_gen != aux->batch_gen)) {
@@ -666,13 +671,23 @@ int mld_sim_step_resolve(mld_problem_t *p, mld_problem_t *aux, const double *u0,
     AuxStepArgs g{};
     g.batch = batch; g.nx = nx; g.nw = nw; g.nu = nu; g.nv = nv; g.nv2 = nv2; g.N = p->N;
     g.x0 = p->bat.x0; g.omega = p->bat.omega;
-    if (u0) { g.u = d_u; g.u_stride = (size_t)nu; }
-    else { g.u = p->bat.v; g.u_stride = (size_t)p->n; g.status = p->bat.status; g.obj = p->bat.obj; }
+    if (u0 || policy) { g.u = d_u; g.u_stride = (size_t)nu; }
+    else { g.u = p->bat.v; g.u_stride = (size_t)p->n; }
+    if (by_plan) { g.status = p->bat.status; g.obj = p->bat.obj; }
     if (actual) { g.act_start = act_start ? d_start.get() : p->pf_actual.d.get(); g.chan = p->pf_chan; g.n_groups = p->pf_groups; g.step = step; g.lib = p->pf_lib; }
     /* ---- gather: the resolver's inputs -------------------------------------------------------------------------------------------------------------- */
     auto gather = [&]() -> int {
         if (u0 && nu) HIP_TRY(hipMemcpyAsync(d_u, u0, sizeof(double) * (size_t)batch * nu, hipMemcpyHostToDevice, sq));
         if (act_start) HIP_TRY(hipMemcpyAsync(d_start, act_start, sizeof(long long) * (size_t)batch * p->pf_groups, hipMemcpyHostToDevice, sq));
+        if (policy && nu) {
+            PolicyInputsArgs pa{};
+            pa.batch = batch; pa.nx = nx; pa.nu = nu; pa.model_idx = p->has_midx ? p->bat.model_idx.get() : nullptr;
+            pa.tab = p->pol_tab; pa.tab_len = (size_t)nu * (nx + POL_TAIL); pa.x0 = p->bat.x0; pa.u_prev = p->pol_uprev;
+            if (by_plan) { pa.src = p->bat.v; pa.src_stride = (size_t)p->n; }
+            pa.u = d_u;
+            hipLaunchKernelGGL(k_policy_inputs, dim3(profile_grid((long long)batch * nu)), dim3(256), 0, sq, pa);
+            HIP_TRY(hipGetLastError());
+        }
         if (aux) {
             g.aux_x0 = aux->bat.x0; g.aux_omega = aux->bat.omega;
             hipLaunchKernelGGL(k_aux_inputs, dim3(profile_grid((long long)batch * (nx + nw + nu))), dim3(256), 0, sq, g);
@@ -692,12 +707,29 @@ int mld_sim_step_resolve(mld_problem_t *p, mld_problem_t *aux, const double *u0,
     /* ---- merge, then the step on the merged slices ----------------------------------------------------------------------------------------------------- */
     g.v0 = d_v0; g.usable = d_mask; g.aux_status_out = d_auxst;
     SimStepSrc src;
-    src.merge = &g; src.d_v0 = d_v0; src.d_mask = d_mask; src.d_auxst = d_auxst; src.by_plan = u0 == nullptr; src.d_start = act_start ? &d_start : nullptr;
+    src.merge = &g; src.d_v0 = d_v0; src.d_mask = d_mask; src.d_auxst = d_auxst; src.by_plan = by_plan; src.d_start = act_start ? &d_start : nullptr;
     src.v0_out = v0_out; src.aux_status_out = aux_status_out;
     int32_t skipped = 0;
     if (int rc = sim_step_run(p, src, act_start, gmax, step, flags, x_k1_out, y_out, cons_out, cons_vio_out, cons_row_out, &skipped)) return rc;
     if (n_skipped_out) *n_skipped_out = skipped;
+    if (policy && (flags & MLD_SIM_ADVANCE) && nu) {
+        auto commit = [&]() -> int {
+            hipLaunchKernelGGL(k_policy_commit, dim3(profile_grid((long long)batch * nu)), dim3(256), 0, sq, (long long)batch, nu, d_mask.get(), d_u.get(), p->pol_uprev.get());
+            HIP_TRY(hipGetLastError());
+            return MLD_OK;
+        };
+        if (int rc = queue_and_wait(sq, commit)) return rc;
+    }
     return MLD_OK;
+}
+
+int mld_sim_step_resolve(mld_problem_t *p, mld_problem_t *aux, const double *u0, const int64_t *act_start, int step, int flags,
+                         double *x_k1_out, double *y_out, uint8_t *cons_out, double *cons_vio_out, int32_t *cons_row_out,
+                         double *v0_out, int32_t *aux_status_out, int32_t *n_skipped_out)
+{
+    static const char who[] = "mld_sim_step_resolve";
+    if (int rc = entry_guard(p, who, true, "no batch resident (mld_upload_batch)")) return rc;
+    return sim_step_resolve_impl(who, false, p, aux, u0, act_start, step, flags, x_k1_out, y_out, cons_out, cons_vio_out, cons_row_out, v0_out, aux_status_out, n_skipped_out);
 }
 
 int mld_download_sim_log_aux(mld_problem_t *p, int first, int count, int32_t *aux_status)

@@ -1,23 +1,18 @@
 // Open-loop rollout of the resident batch's plans under realised disturbances (mld_rollout_batch, kernel k_rollout in rollout.inc).
-extern "C" {
-
-/* The a-posteriori step of a scenario-based controller: what the hybrid plant does over the next K steps if the plan's (or the caller's) inputs are applied
- * and the disturbance turns out to be realisation c -- the reference's MldModel.lsim / lsim_k in a loop (models/mld_model.py:543-642, 647-699) with
- * _compute_aux (:701-766) at every step, for batch x S trajectories in ONE launch.  Everything is tested on the host before anything is queued; the call
- * reads p's current x0 and writes nothing a solve reads -- inputs, plan, MIP start, log and resident starts stay (the what-if of mld_sim_step_*) -- and
- * nothing on the resolver's handle: the kernel reads the resolver's per-model data only.  Host-synchronous. */
-int mld_rollout_batch(mld_problem_t *p, mld_problem_t *aux, int K, int S, const double *u_seq, const double *omega_seq, const int64_t *start, int step,
-                      const double *cost_w, int cost_rows, double *x_out, double *v_out, double *y_out, double *cons_vio_out, int32_t *cons_row_out,
-                      double *cost_out, double *mu_total_out, double *worst_vio_out, int32_t *worst_step_out, int32_t *steps_done_out, int32_t *end_status_out,
-                      int64_t stats[4])
+/* The body mld_rollout_batch and mld_rollout_policy share.  pc == nullptr: the open-loop rollout, kernel k_rollout, as it always was.  pc: the policy
+ * instantiation k_rollout_policy -- the ruled channels of u_k by p's resident policy from the trajectory's own x_k and u_{k-1}, u_seq / the plan for the
+ * passed-through ones only (no plan is needed when every channel is ruled), pc->u_prev (batch, nu) or the resident policy state before step 0. */
+static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p, mld_problem_t *aux, int K, int S, const double *u_seq, const double *omega_seq,
+                        const int64_t *start, int step, const double *cost_w, int cost_rows, double *x_out, double *v_out, double *y_out, double *cons_vio_out,
+                        int32_t *cons_row_out, double *cost_out, double *mu_total_out, double *worst_vio_out, int32_t *worst_step_out, int32_t *steps_done_out,
+                        int32_t *end_status_out, int64_t stats[4])
 {
-    static const char who[] = "mld_rollout_batch";
-    if (int rc = entry_guard(p, who, true, "no batch resident (mld_upload_batch)")) return rc;
     mld_model *mo = p->model;
     const mld_dims &d = mo->dims;
     const int batch = p->batch, nx = d.nx, nu = d.nu, nw = d.nomega, nv = p->nv, ny = d.ny;
     if (mo->tv_N > 0) { mld_set_error("%s: time-varying models (mld_model_create_tv) are not rolled out on the device -- the step models would have to shift with the horizon", who); return MLD_ERR_INVALID; }
     if (!mo->d_pack) { mld_set_error("%s: model without matrices", who); return MLD_ERR_INVALID; }
+    if (pc && !p->pol_on) { mld_set_error("%s: no policy uploaded (mld_upload_policy)", who); return MLD_ERR_INVALID; }
     if (K < 1 || S < 1) { mld_set_error("%s: K = %d, S = %d (at least one step and one realisation)", who, K, S); return MLD_ERR_INVALID; }
     if ((long long)batch * S > INT_MAX) { mld_set_error("%s: batch x S = %lld trajectories (at most %d)", who, (long long)batch * S, INT_MAX); return MLD_ERR_INVALID; }
     if (step < 0 || step > INT_MAX - K) { mld_set_error("%s: step = %d (must be >= 0)", who, step); return MLD_ERR_INVALID; }
@@ -35,7 +30,8 @@ int mld_rollout_batch(mld_problem_t *p, mld_problem_t *aux, int K, int S, const 
         mld_set_error("%s: the staging of a trajectory (%zu bytes: x, omega', h, v, y, x_k1) does not fit a wave's share of LDS (%d bytes); step with mld_sim_step_resolve", who, sizeof(double) * stage_d, SM_WAVE_BUDGET);
         return MLD_ERR_INVALID;
     }
-    if (!u_seq) {      /* the plan-state tests of sim_step_check */
+    const bool by_plan = !u_seq && !(pc && p->pol_all_ruled);      /* some channel takes the resident plan's input */
+    if (by_plan) {      /* the plan-state tests of sim_step_check */
         if (K > p->N) { mld_set_error("%s: K = %d steps with the resident plan's inputs, but the plan has N_tilde = %d (pass u_seq for a longer rollout)", who, K, p->N); return MLD_ERR_INVALID; }
         if (!p->solved) { mld_set_error("%s: the resident batch has not been solved since its upload / selection (there is no plan to apply; pass u_seq)", who); return MLD_ERR_INVALID; }
         if (p->advanced) { mld_set_error("%s: the last solve's plan has already been applied -- the resident plan belongs to inputs that are gone (solve again, or pass u_seq)", who); return MLD_ERR_INVALID; }
@@ -56,6 +52,9 @@ int mld_rollout_batch(mld_problem_t *p, mld_problem_t *aux, int K, int S, const 
     if (omega_seq && nw) for (size_t k = 0; k < T * K * nw; ++k) if (!std::isfinite(omega_seq[k])) {
         mld_set_error("%s: omega_seq of trajectory %zu, step %zu, channel %zu is not finite (%g)", who, k / ((size_t)K * nw), k / nw % K, k % nw, omega_seq[k]); return MLD_ERR_INVALID;
     }
+    if (pc && pc->u_prev) for (size_t k = 0; k < (size_t)batch * nu; ++k) if (!std::isfinite(pc->u_prev[k])) {
+        mld_set_error("%s: u_prev of instance %zu, input %zu is not finite (%g)", who, k / nu, k % nu, pc->u_prev[k]); return MLD_ERR_INVALID;
+    }
     const bool cw_inst = cost_w && cost_rows != p->n_models;      /* (batch == n_models: a row per model) */
     if (cost_w) for (size_t k = 0; k < (size_t)cost_rows * K * nv; ++k) if (!std::isfinite(cost_w[k])) {
         mld_set_error("%s: cost_w of row %zu, step %zu, entry %zu is not finite (%g)", who, k / ((size_t)K * nv), k / nv % K, k % nv, cost_w[k]); return MLD_ERR_INVALID;
@@ -72,7 +71,9 @@ int mld_rollout_batch(mld_problem_t *p, mld_problem_t *aux, int K, int S, const 
     const size_t lds_bytes = sizeof(double) * (wave_d + stage_d) * SM_WAVES;
     const hipStream_t sq = p->stream;
     const size_t Kz = (size_t)K;
-    DevBuf<double> d_u, d_om, d_cw, d_x, d_v, d_y, d_vio, d_cost, d_mu, d_wv; DevBuf<int> d_row, d_ws, d_sd, d_es; DevBuf<long long> d_start; DevBuf<unsigned long long> d_cnt;
+    DevBuf<double> d_u, d_om, d_cw, d_x, d_v, d_y, d_vio, d_cost, d_mu, d_wv, d_uprev; DevBuf<int> d_row, d_ws, d_sd, d_es, d_sw; DevBuf<long long> d_start; DevBuf<unsigned long long> d_cnt;
+    if (pc && !pc->u_prev) { if (int rc = policy_state_ready(p, who)) return rc; }      /* (an upload's reset state, laid out on first use: nothing a caller can see changes) */
+    if (pc && pc->u_prev) HIP_TRY(d_uprev.alloc(std::max<size_t>(1, (size_t)batch * nu)));
     if (u_seq) HIP_TRY(d_u.alloc(std::max<size_t>(1, (size_t)batch * Kz * nu)));
     HIP_TRY(d_om.alloc(std::max<size_t>(1, T * Kz * nw)));
     if (start) HIP_TRY(d_start.alloc(T * p->pf_groups));
@@ -83,6 +84,7 @@ int mld_rollout_batch(mld_problem_t *p, mld_problem_t *aux, int K, int S, const 
     HIP_TRY(take(d_x, x_out, cx)); HIP_TRY(take(d_v, v_out, cv)); HIP_TRY(take(d_y, y_out, cy)); HIP_TRY(take(d_vio, cons_vio_out, ck)); HIP_TRY(take(d_row, cons_row_out, ck));
     HIP_TRY(take(d_cost, cost_out, T)); HIP_TRY(take(d_mu, mu_total_out, T)); HIP_TRY(take(d_wv, worst_vio_out, T));
     HIP_TRY(take(d_ws, worst_step_out, T)); HIP_TRY(take(d_sd, steps_done_out, T)); HIP_TRY(take(d_es, end_status_out, T));
+    if (pc) HIP_TRY(take(d_sw, pc->switches_out, T));
     HIP_TRY(d_cnt.alloc(4));
     RoDev a{};
     a.batch = batch; a.S = S; a.K = K;
@@ -92,7 +94,8 @@ int mld_rollout_batch(mld_problem_t *p, mld_problem_t *aux, int K, int S, const 
     a.model_idx = p->has_midx ? p->bat.model_idx.get() : nullptr;
     a.x0 = p->bat.x0;
     if (u_seq) { a.u = d_u; a.u_stride = Kz * nu; a.u_step = (size_t)nu; }
-    else { a.u = p->bat.v; a.u_stride = (size_t)p->n; a.u_step = (size_t)nv; a.status = p->bat.status; a.obj = p->bat.obj; }      /* rows < batch are the instances' (after the hand-off's device merge) */
+    else if (by_plan) { a.u = p->bat.v; a.u_stride = (size_t)p->n; a.u_step = (size_t)nv; a.status = p->bat.status; a.obj = p->bat.obj; }      /* rows < batch are the instances' (after the hand-off's device merge) */
+    else { a.u = p->bat.x0; a.u_stride = 0; a.u_step = 0; }      /* every channel ruled: u is never read (a valid address all the same) */
     a.om = d_om;
     a.cw = cost_w ? d_cw.get() : nullptr; a.cw_by_inst = cw_inst ? 1 : 0;
     a.x = d_x; a.v = d_v; a.y = d_y; a.vio = d_vio; a.row = d_row;
@@ -100,17 +103,21 @@ int mld_rollout_batch(mld_problem_t *p, mld_problem_t *aux, int K, int S, const 
     a.counter = d_cnt;
     ProblemDev P{};
     if (aux) P = problem_dev(aux);
+    RoPolicyDev pd{};
+    if (pc) { pd.tab = p->pol_tab; pd.tab_len = (size_t)nu * (nx + POL_TAIL); pd.u_prev = pc->u_prev ? d_uprev.get() : p->pol_uprev.get(); pd.switches = d_sw; }
+    const void *kernel = pc ? (const void *)k_rollout_policy : (const void *)k_rollout;
     if (lds_bytes > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void *)k_rollout, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     int dev = 0, per_cu = 0; hipDeviceProp_t prop;
     (void)hipGetDevice(&dev); HIP_TRY(hipGetDeviceProperties(&prop, dev));
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_rollout, SM_NT, lds_bytes) != hipSuccess || per_cu < 1) per_cu = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, SM_NT, lds_bytes) != hipSuccess || per_cu < 1) per_cu = 1;
     const int grid = (int)std::min<size_t>((T + SM_WAVES - 1) / SM_WAVES, (size_t)per_cu * prop.multiProcessorCount);
     unsigned long long cnt[4] = {};
     /* everything queued on the stream and waited for on every path (queue_and_wait): the caller's arrays and the temporaries may go when this returns */
     auto queue = [&]() -> int {
         HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(cnt), sq));
         if (u_seq && nu) HIP_TRY(hipMemcpyAsync(d_u, u_seq, sizeof(double) * (size_t)batch * Kz * nu, hipMemcpyHostToDevice, sq));
+        if (pc && pc->u_prev && nu) HIP_TRY(hipMemcpyAsync(d_uprev, pc->u_prev, sizeof(double) * (size_t)batch * nu, hipMemcpyHostToDevice, sq));
         if (cost_w && nv) HIP_TRY(hipMemcpyAsync(d_cw, cost_w, sizeof(double) * (size_t)cost_rows * Kz * nv, hipMemcpyHostToDevice, sq));
         if (omega_seq && nw) HIP_TRY(hipMemcpyAsync(d_om, omega_seq, sizeof(double) * T * Kz * nw, hipMemcpyHostToDevice, sq));
         if (start) {      /* the windows of K steps gathered into the buffer omega_seq would be uploaded to: one input layout for the kernel */
@@ -119,7 +126,8 @@ int mld_rollout_batch(mld_problem_t *p, mld_problem_t *aux, int K, int S, const 
                                p->pf_chan.get(), step, p->pf_lib.get(), d_om.get());
             HIP_TRY(hipGetLastError());
         }
-        hipLaunchKernelGGL(k_rollout, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a);
+        if (pc) hipLaunchKernelGGL(k_rollout_policy, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a, pd);
+        else hipLaunchKernelGGL(k_rollout, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a);
         HIP_TRY(hipGetLastError());
         auto get = [&](auto *out, const auto &buf, size_t count) -> hipError_t {
             return buf ? hipMemcpyAsync(out, buf, sizeof(*out) * count, hipMemcpyDeviceToHost, sq) : hipSuccess;
@@ -127,12 +135,31 @@ int mld_rollout_batch(mld_problem_t *p, mld_problem_t *aux, int K, int S, const 
         HIP_TRY(get(x_out, d_x, cx)); HIP_TRY(get(v_out, d_v, cv)); HIP_TRY(get(y_out, d_y, cy)); HIP_TRY(get(cons_vio_out, d_vio, ck)); HIP_TRY(get(cons_row_out, d_row, ck));
         HIP_TRY(get(cost_out, d_cost, T)); HIP_TRY(get(mu_total_out, d_mu, T)); HIP_TRY(get(worst_vio_out, d_wv, T));
         HIP_TRY(get(worst_step_out, d_ws, T)); HIP_TRY(get(steps_done_out, d_sd, T)); HIP_TRY(get(end_status_out, d_es, T));
+        if (pc) HIP_TRY(get(pc->switches_out, d_sw, T));
         HIP_TRY(hipMemcpyAsync(cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, sq));
         return MLD_OK;
     };
     if (int rc = queue_and_wait(sq, queue)) return rc;
     if (stats) { stats[0] = (int64_t)T; stats[1] = (int64_t)cnt[1]; stats[2] = (int64_t)cnt[2]; stats[3] = (int64_t)cnt[3]; }
     return MLD_OK;
+}
+
+extern "C" {
+
+/* The a-posteriori step of a scenario-based controller: what the hybrid plant does over the next K steps if the plan's (or the caller's) inputs are applied
+ * and the disturbance turns out to be realisation c -- the reference's MldModel.lsim / lsim_k in a loop (models/mld_model.py:543-642, 647-699) with
+ * _compute_aux (:701-766) at every step, for batch x S trajectories in ONE launch.  Everything is tested on the host before anything is queued; the call
+ * reads p's current x0 and writes nothing a solve reads -- inputs, plan, MIP start, log and resident starts stay (the what-if of mld_sim_step_*) -- and
+ * nothing on the resolver's handle: the kernel reads the resolver's per-model data only.  Host-synchronous. */
+int mld_rollout_batch(mld_problem_t *p, mld_problem_t *aux, int K, int S, const double *u_seq, const double *omega_seq, const int64_t *start, int step,
+                      const double *cost_w, int cost_rows, double *x_out, double *v_out, double *y_out, double *cons_vio_out, int32_t *cons_row_out,
+                      double *cost_out, double *mu_total_out, double *worst_vio_out, int32_t *worst_step_out, int32_t *steps_done_out, int32_t *end_status_out,
+                      int64_t stats[4])
+{
+    static const char who[] = "mld_rollout_batch";
+    if (int rc = entry_guard(p, who, true, "no batch resident (mld_upload_batch)")) return rc;
+    return rollout_impl(who, nullptr, p, aux, K, S, u_seq, omega_seq, start, step, cost_w, cost_rows, x_out, v_out, y_out, cons_vio_out, cons_row_out, cost_out,
+                        mu_total_out, worst_vio_out, worst_step_out, steps_done_out, end_status_out, stats);
 }
 
 } // extern "C"

@@ -98,6 +98,10 @@ struct mld_problem {
     /* mld_sim_step_resolve: batch_gen numbers the uploads of all handles (inputs_new_batch), so that a resolver handle can tell whether its resident batch
      * is still the one laid out for the stepped handle's -- it remembers that handle's number and its own at the time (0 = never laid out) */
     unsigned long long batch_gen = 0, aux_src_gen = 0, aux_own_gen = 0;
+    /* rule-based feedback policy (mld_upload_policy): the tables (n_models, nu, nx + 5) -- per channel [sel | on_at | off_at | u_on | u_off | mode] -- on
+     * the device and on the host, owned by the problem like the profile library.  The resident u_prev (batch, nu) belongs to ONE upload of a batch: it is
+     * valid while pol_state_gen == batch_gen, and laid out as the reset state (u_off on the ruled channels) by the first call that needs it after that */
+    DevBuf<double> pol_tab, pol_uprev; std::vector<double> pol_host; bool pol_on = false, pol_all_ruled = false; unsigned long long pol_state_gen = 0;
     long long ho_stats[4] = {};  /* last solve: items published, trees split, trees left unfinished, entries the queue had no room for (always 0: such trees stay unfinished) */
 };
 
@@ -339,6 +343,33 @@ template <typename Queue> static int queue_and_wait(hipStream_t sq, Queue &&queu
     const hipError_t es = hipStreamSynchronize(sq);
     if (rc) return rc;
     HIP_TRY(es);
+    return MLD_OK;
+}
+
+/* What a policy entry point adds to the body it shares with its open-loop neighbour (rollout_impl): the inputs before step 0 (NULL: the resident policy
+ * state) and where the switch counts go */
+struct PolicyCall { const double *u_prev; int32_t *switches_out; };
+
+/* The resident policy state of THIS upload of the batch: if there is none yet (or it belonged to an earlier upload), the reset state -- every ruled channel
+ * at its model's u_off, the reference's first step, which has no previous record (theromstat_control.py:57: `u_k_neg1 == 1` is false); a passed-through
+ * channel at 0.  Host-synchronous on the legacy stream, before the caller queues anything. */
+static int policy_state_ready(mld_problem *p, const char *who)
+{
+    if (!p->pol_on) { mld_set_error("%s: no policy uploaded (mld_upload_policy)", who); return MLD_ERR_INVALID; }
+    if (p->pol_uprev && p->pol_state_gen == p->batch_gen) return MLD_OK;
+    const int batch = p->batch, nu = p->model->dims.nu, row = p->model->dims.nx + POL_TAIL;
+    std::vector<int32_t> midx;
+    if (p->has_midx) { midx.resize(batch); HIP_TRY(hipMemcpy(midx.data(), p->bat.model_idx, sizeof(int) * batch, hipMemcpyDeviceToHost)); }
+    std::vector<double> init((size_t)batch * nu);
+    for (int b = 0; b < batch; ++b)
+        for (int j = 0; j < nu; ++j) {
+            const double *t = p->pol_host.data() + ((size_t)(p->has_midx ? midx[b] : 0) * nu + j) * row + (row - POL_TAIL);
+            init[(size_t)b * nu + j] = t[POL_MODE] != 0.0 ? t[POL_U_OFF] : 0.0;
+        }
+    p->pol_state_gen = 0;
+    HIP_TRY(p->pol_uprev.alloc(std::max<size_t>(1, init.size())));
+    if (!init.empty()) HIP_TRY(hipMemcpy(p->pol_uprev, init.data(), sizeof(double) * init.size(), hipMemcpyHostToDevice));
+    p->pol_state_gen = p->batch_gen;
     return MLD_OK;
 }
 

@@ -15,6 +15,12 @@
 // dimension is a compile-time constant: rows and columns are looped lane, lane + 64, ...  Every store is lane-contiguous.
 //
 // The per-trajectory core ro_run compiles for the host as sm_solve does (SM_HOST: a "wave" is one lane, the staging plain memory).
+//
+// k_rollout_policy (mld_rollout_policy) is the second instantiation of the same body: ro_run<true> replaces step 1's copy of u_k by a feedback rule
+// u_k = f(x_k, u_{k-1}) per input channel -- the reference's thermostat, DewhTheromstatController.feedback (examples/residential_mg_with_pv_and_dewhs/
+// controllers/theromstat_control.py:38-64), stepped through sim_step_k --, lanes on channels, the selector row summed over x in LDS, u_{k-1} read from v's
+// own block before the lane overwrites it: the staging grows by nothing.  The tables are read from global memory per step, nu (nx + 5) doubles per model:
+// per channel [sel (nx) | on_at | off_at | u_on | u_off | mode].  The flag is a template parameter; the open-loop instantiation compiles to what it compiled to.
 #pragma once
 
 #include "plant_step.inc"
@@ -25,6 +31,7 @@ struct RoModel {      // one trajectory's model: the step matrices inside the pa
     int m, n;                                                              // the resolver's rows and unknowns (n = ndelta + nz + nmu; 0: nothing to resolve)
     PlantMats P;                                                           // the step matrices inside the model's packed block (plant_mats)
     const double *Hx, *Hw, *H5, *rs;                                       // m x nx, m x (nw + nu), m, m
+    const double *pol;                                                     // ro_run<true>: the model's policy table, nu x (nx + 5)
 };
 struct RoTraj {       // one trajectory's inputs and outputs (any output may be null)
     int K;
@@ -33,9 +40,23 @@ struct RoTraj {       // one trajectory's inputs and outputs (any output may be 
     const double *om;                                                      // K x nw
     const double *cw;                                                      // K x nv or null
     double *x, *v, *y, *vio; int *row;                                     // (K + 1) x nx, K x nv, K x ny, K, K
+    const double *u_prev;                                                  // ro_run<true>: nu, the input before step 0
 };
-struct RoResult { double cost, mu_total, worst_vio; int worst_step, worst_row, steps_done, end_status; };
+struct RoResult { double cost, mu_total, worst_vio; int worst_step, worst_row, steps_done, end_status, switches; };
 enum { RO_COMPLETE = 0, RO_INFEASIBLE = 1, RO_DECLINED = 2, RO_NOT_ATTEMPTED = -1 };
+enum { POL_ON_AT = 0, POL_OFF_AT = 1, POL_U_ON = 2, POL_U_OFF = 3, POL_MODE = 4, POL_TAIL = 5 };      // a channel's table row behind its nx selector entries
+
+// The rule of one ruled channel (theromstat_control.py:53-58, in that order): tab = the channel's row, s = sel . x with i ascending.  A NaN s falls through
+// to the comparison with the previous input, as it does in the reference; with on_at == off_at the first line wins.
+template <typename X> SM_FN double policy_rule(const double *tab, int nx, const X *x, double prev)
+{
+    double s = 0.0;
+    for (int i = 0; i < nx; ++i) s += tab[i] * x[i];
+    const double *t = tab + nx;
+    if (s <= t[POL_ON_AT]) return t[POL_U_ON];
+    if (s >= t[POL_OFF_AT]) return t[POL_U_OFF];
+    return prev == t[POL_U_ON] ? t[POL_U_ON] : t[POL_U_OFF];
+}
 
 // doubles of staging behind the solver's region (even, so that the next wave's region stays 16-byte aligned)
 static inline size_t ro_stage_doubles(int nx, int nu, int nw, int m, int nv, int ny)
@@ -56,8 +77,9 @@ SM_FN void ro_blank(const RoModel &M, const RoTraj &T, int lane, int from, bool 
 }
 
 // One trajectory, start to finish.  mem: the solver's region (S.wave_doubles doubles), stg: the staging (ro_stage_doubles); A: the resolver's model
-// (G, q, lb, ub, cs, is_int, bins), its h / v_out / fixed are set here.
-SM_FN void ro_run(const SmShape &S, const RoModel &M, sm_f64 *mem, sm_f64 *stg, SmArgs A, const RoTraj &T, int lane, RoResult &R)
+// (G, q, lb, ub, cs, is_int, bins), its h / v_out / fixed are set here.  POLICY: the ruled channels of u_k come from M.pol, x_k and u_{k-1} (T.u_prev before
+// step 0); T.u supplies the passed-through channels only, and R.switches counts the (step, ruled channel) pairs whose input changed.
+template <bool POLICY = false> SM_FN void ro_run(const SmShape &S, const RoModel &M, sm_f64 *mem, sm_f64 *stg, SmArgs A, const RoTraj &T, int lane, RoResult &R)
 {
     const int nx = M.nx, nu = M.nu, nw = M.nw, nv = M.nv, ny = M.ny, nc = M.nc, m = M.m, nw2 = M.nw + M.nu, nf = M.nv - M.nmu;
     sm_f64 *xs = stg, *ws = xs + nx, *hs = ws + nw2, *vs = hs + m, *ys = vs + nv, *xn = ys + ny;
@@ -65,14 +87,25 @@ SM_FN void ro_run(const SmShape &S, const RoModel &M, sm_f64 *mem, sm_f64 *stg, 
     const double qnan = __builtin_nan("");
     A.h = (const double *)hs; A.v_out = (double *)(vs + nu); A.fixed = nullptr;
     for (int j = lane; j < nx; j += SM_W) { const double t = T.x0[j]; xs[j] = t; if (T.x) T.x[j] = t; }
+    if constexpr (POLICY) for (int j = lane; j < nu; j += SM_W) vs[j] = T.u_prev[j];      /* u_{-1}: a lane reads and writes its own channels only */
     double cost = 0.0, mu_total = 0.0, worst = -S_INF;
     int wstep = -1, wrow = -1, end = RO_COMPLETE, k = 0;
+    [[maybe_unused]] int sw = 0;
     for (; k < T.K; ++k) {
         // ---- 1. the step's inputs
         const double *uk = T.u + (size_t)k * T.u_step, *wk = T.om + (size_t)k * nw;
         sm_sync();
         for (int j = lane; j < nw; j += SM_W) ws[j] = wk[j];
-        for (int j = lane; j < nu; j += SM_W) { const double t = uk[j]; ws[nw + j] = t; vs[j] = t; }
+        if constexpr (POLICY) {
+            for (int j = lane; j < nu; j += SM_W) {
+                const double *tab = M.pol + (size_t)j * (nx + POL_TAIL);
+                double t;
+                if (tab[nx + POL_MODE] != 0.0) { const double prev = vs[j]; t = policy_rule(tab, nx, xs, prev); sw += t != prev; }
+                else t = uk[j];
+                ws[nw + j] = t; vs[j] = t;
+            }
+        } else
+            for (int j = lane; j < nu; j += SM_W) { const double t = uk[j]; ws[nw + j] = t; vs[j] = t; }
         sm_sync();
         if (M.n) {
             // ---- 2. the resolver's right-hand side: lanes on rows, j ascending
@@ -126,6 +159,10 @@ SM_FN void ro_run(const SmShape &S, const RoModel &M, sm_f64 *mem, sm_f64 *stg, 
     R.end_status = end; R.steps_done = k;
     R.cost = end == RO_COMPLETE ? (T.cw ? cost : 0.0) : qnan; R.mu_total = end == RO_COMPLETE ? mu_total : qnan;
     R.worst_vio = end == RO_COMPLETE ? worst : qnan; R.worst_step = end == RO_COMPLETE ? wstep : -1; R.worst_row = end == RO_COMPLETE ? wrow : -1;
+    if constexpr (POLICY) {
+        for (int off = SM_W / 2; off; off >>= 1) sw += sm_xor_i32(sw, off);
+        R.switches = end == RO_COMPLETE ? sm_uniform(sw) : -1;
+    }
 }
 
 #ifndef SM_HOST
@@ -144,53 +181,107 @@ struct RoDev {
     double *cost, *mu_total, *worst_vio; int *worst_step, *steps_done, *end_status;      /* per trajectory, any nullptr */
     unsigned long long *counter;                    /* [0] the work queue, [1 .. 3] trajectories that ended complete / infeasible / declined */
 };
+struct RoPolicyDev {      /* what k_rollout_policy takes on top: an argument of its own, so that k_rollout's stay as they are */
+    const double *tab; size_t tab_len;              /* (n_models, nu, nx + 5), tab_len = nu (nx + 5) */
+    const double *u_prev;                           /* (batch, nu): the inputs before step 0 */
+    int *switches;                                  /* per trajectory, or nullptr */
+};
+
+// The kernel body, written once and expanded into both kernels.  (A function template called by the two kernels was tried first: inlined, it left k_rollout
+// with 208 bytes of scratch per lane instead of 156 -- the kernel arguments reach the register allocator by another route.  Expanded in place, the open-loop
+// kernel's listing is the one it had: profiles/policy_rollout_resource_usage.txt.)  POLICY: a literal; `pol`: the kernel's RoPolicyDev (k_rollout: an empty one).
+#define RO_KERNEL_BODY(POLICY)                                                                                                                                     \
+    extern __shared__ double ro_lds[];                                                                                                                             \
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;                                                                                                    \
+    sm_f64 *mem = (sm_f64 *)ro_lds + (size_t)wave * ((size_t)S.wave_doubles + a.stage_doubles), *stg = mem + S.wave_doubles;                                       \
+    const unsigned long long total = (unsigned long long)a.batch * a.S;                                                                                            \
+    RoModel M;                                                                                                                                                     \
+    M.nx = a.nx; M.nu = a.nu; M.nw = a.nw; M.nv = a.nv; M.nmu = a.nmu; M.ny = a.ny; M.nc = a.nc; M.m = a.m; M.n = a.n;                                             \
+    for (;;) {                                                                                                                                                     \
+        const unsigned long long t = sm_claim(a.counter, lane);                                                                                                    \
+        if (t >= total) break;                                                                                                                                     \
+        const long long b = (long long)(t / (unsigned)a.S);                                                                                                        \
+        const int mdl = a.model_idx ? a.model_idx[b] : 0;                                                                                                          \
+        M.P = plant_mats(a.pack + (size_t)mdl * a.pack_len, a.off);                                                                                                \
+        SmArgs A{};                                                                                                                                                \
+        if (a.n) {                                                                                                                                                 \
+            const size_t m = a.m, n = a.n;                                                                                                                         \
+            M.Hx = P.Hx + (size_t)mdl * m * a.nx; M.Hw = P.Hw + (size_t)mdl * m * (a.nw + a.nu); M.H5 = P.H5 + (size_t)mdl * m; M.rs = P.rs + (size_t)mdl * m;     \
+            A.G = P.Gs + (size_t)mdl * m * n; A.q = P.qs + (size_t)mdl * n;                                                                                        \
+            A.lb = P.lb + (size_t)mdl * n; A.ub = P.ub + (size_t)mdl * n; A.cs = P.cs + (size_t)mdl * n;                                                           \
+            A.is_int = P.is_int; A.bins = P.bins;                                                                                                                  \
+        }                                                                                                                                                          \
+        RoTraj T;                                                                                                                                                  \
+        T.K = a.K; T.x0 = a.x0 + (size_t)b * a.nx; T.u = a.u + (size_t)b * a.u_stride; T.u_step = a.u_step;                                                        \
+        T.om = a.om + (size_t)t * a.K * a.nw;                                                                                                                      \
+        T.cw = a.cw ? a.cw + (size_t)(a.cw_by_inst ? b : mdl) * a.K * a.nv : nullptr;                                                                              \
+        T.x = a.x ? a.x + (size_t)t * (a.K + 1) * a.nx : nullptr; T.v = a.v ? a.v + (size_t)t * a.K * a.nv : nullptr;                                              \
+        T.y = a.y ? a.y + (size_t)t * a.K * a.ny : nullptr; T.vio = a.vio ? a.vio + (size_t)t * a.K : nullptr; T.row = a.row ? a.row + (size_t)t * a.K : nullptr;  \
+        if constexpr (POLICY) { M.pol = pol.tab + (size_t)mdl * pol.tab_len; T.u_prev = pol.u_prev + (size_t)b * a.nu; }                                           \
+        RoResult R;                                                                                                                                                \
+        if (a.status && !plan_usable(a.status, a.obj, (int)b)) {      /* uniform over the wave: no plan whose inputs could be applied */                           \
+            const double qnan = __builtin_nan("");                                                                                                                 \
+            ro_blank(M, T, lane, 0, true);                                                                                                                         \
+            R.cost = R.mu_total = R.worst_vio = qnan; R.worst_step = R.worst_row = -1; R.steps_done = 0; R.end_status = RO_NOT_ATTEMPTED;                          \
+            if constexpr (POLICY) R.switches = -1;                                                                                                                 \
+        } else                                                                                                                                                     \
+            ro_run<POLICY>(S, M, mem, stg, A, T, lane, R);                                                                                                         \
+        if (lane == 0) {                                                                                                                                           \
+            if (a.cost) a.cost[t] = R.cost;                                                                                                                        \
+            if (a.mu_total) a.mu_total[t] = R.mu_total;                                                                                                            \
+            if (a.worst_vio) a.worst_vio[t] = R.worst_vio;                                                                                                         \
+            if (a.worst_step) a.worst_step[t] = R.worst_step;                                                                                                      \
+            if (a.steps_done) a.steps_done[t] = R.steps_done;                                                                                                      \
+            if (a.end_status) a.end_status[t] = R.end_status;                                                                                                      \
+            if constexpr (POLICY) if (pol.switches) pol.switches[t] = R.switches;                                                                                  \
+            if (R.end_status >= 0) atomicAdd(a.counter + 1 + R.end_status, 1ull);                                                                                  \
+        }                                                                                                                                                          \
+    }
 
 // Three waves per SIMD asked for: unconstrained the kernel holds 219 VGPRs (two waves) and takes 1.44 x the time; at 168 it spills 42 registers to
 // scratch, outside the pivot loop's hot values (DESIGN section 6).
 __global__ void __launch_bounds__(SM_NT, 3) k_rollout(SmShape S, ProblemDev P, RoDev a)
 {
-    extern __shared__ double ro_lds[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    sm_f64 *mem = (sm_f64 *)ro_lds + (size_t)wave * ((size_t)S.wave_doubles + a.stage_doubles), *stg = mem + S.wave_doubles;
-    const unsigned long long total = (unsigned long long)a.batch * a.S;
-    RoModel M;
-    M.nx = a.nx; M.nu = a.nu; M.nw = a.nw; M.nv = a.nv; M.nmu = a.nmu; M.ny = a.ny; M.nc = a.nc; M.m = a.m; M.n = a.n;
-    for (;;) {
-        const unsigned long long t = sm_claim(a.counter, lane);
-        if (t >= total) break;
-        const long long b = (long long)(t / (unsigned)a.S);
-        const int mdl = a.model_idx ? a.model_idx[b] : 0;
-        M.P = plant_mats(a.pack + (size_t)mdl * a.pack_len, a.off);
-        SmArgs A{};
-        if (a.n) {
-            const size_t m = a.m, n = a.n;
-            M.Hx = P.Hx + (size_t)mdl * m * a.nx; M.Hw = P.Hw + (size_t)mdl * m * (a.nw + a.nu); M.H5 = P.H5 + (size_t)mdl * m; M.rs = P.rs + (size_t)mdl * m;
-            A.G = P.Gs + (size_t)mdl * m * n; A.q = P.qs + (size_t)mdl * n;
-            A.lb = P.lb + (size_t)mdl * n; A.ub = P.ub + (size_t)mdl * n; A.cs = P.cs + (size_t)mdl * n;
-            A.is_int = P.is_int; A.bins = P.bins;
-        }
-        RoTraj T;
-        T.K = a.K; T.x0 = a.x0 + (size_t)b * a.nx; T.u = a.u + (size_t)b * a.u_stride; T.u_step = a.u_step;
-        T.om = a.om + (size_t)t * a.K * a.nw;
-        T.cw = a.cw ? a.cw + (size_t)(a.cw_by_inst ? b : mdl) * a.K * a.nv : nullptr;
-        T.x = a.x ? a.x + (size_t)t * (a.K + 1) * a.nx : nullptr; T.v = a.v ? a.v + (size_t)t * a.K * a.nv : nullptr;
-        T.y = a.y ? a.y + (size_t)t * a.K * a.ny : nullptr; T.vio = a.vio ? a.vio + (size_t)t * a.K : nullptr; T.row = a.row ? a.row + (size_t)t * a.K : nullptr;
-        RoResult R;
-        if (a.status && !plan_usable(a.status, a.obj, (int)b)) {      /* uniform over the wave: no plan whose inputs could be applied */
-            const double qnan = __builtin_nan("");
-            ro_blank(M, T, lane, 0, true);
-            R.cost = R.mu_total = R.worst_vio = qnan; R.worst_step = R.worst_row = -1; R.steps_done = 0; R.end_status = RO_NOT_ATTEMPTED;
-        } else
-            ro_run(S, M, mem, stg, A, T, lane, R);
-        if (lane == 0) {
-            if (a.cost) a.cost[t] = R.cost;
-            if (a.mu_total) a.mu_total[t] = R.mu_total;
-            if (a.worst_vio) a.worst_vio[t] = R.worst_vio;
-            if (a.worst_step) a.worst_step[t] = R.worst_step;
-            if (a.steps_done) a.steps_done[t] = R.steps_done;
-            if (a.end_status) a.end_status[t] = R.end_status;
-            if (R.end_status >= 0) atomicAdd(a.counter + 1 + R.end_status, 1ull);
-        }
+    const RoPolicyDev pol{};
+    RO_KERNEL_BODY(false)
+}
+
+// The policy instantiation: the same body, step 1's inputs by the rule.
+__global__ void __launch_bounds__(SM_NT, 3) k_rollout_policy(SmShape S, ProblemDev P, RoDev a, RoPolicyDev pol)
+{
+    RO_KERNEL_BODY(true)
+}
+#undef RO_KERNEL_BODY
+
+// k_policy_inputs (mld_sim_step_policy): u[b, j] of ONE step for every instance, written into the buffer the resolving step reads its u0 from.  A ruled
+// channel takes the rule's value from the handle's current x0[b] and the resident u_prev[b]; a passed-through one keeps the caller's value (src ==
+// nullptr: already in u) or takes the resident plan's (src = the plan's rows, stride src_stride).  Threads on (instance, channel), 64-bit indices,
+// grid-stride.
+struct PolicyInputsArgs {
+    long long batch; int nx, nu;
+    const int *model_idx;
+    const double *tab; size_t tab_len;
+    const double *x0, *u_prev;                      /* (batch, nx), (batch, nu) */
+    const double *src; size_t src_stride;           /* the passed-through channels where the caller brought none */
+    double *u;                                      /* (batch, nu) */
+};
+__global__ void __launch_bounds__(256) k_policy_inputs(const PolicyInputsArgs a)
+{
+    const long long total = a.batch * a.nu;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const long long b = e / a.nu;
+        const int j = (int)(e - b * a.nu);
+        const double *tab = a.tab + (size_t)(a.model_idx ? a.model_idx[b] : 0) * a.tab_len + (size_t)j * (a.nx + POL_TAIL);
+        if (tab[a.nx + POL_MODE] != 0.0) a.u[e] = policy_rule(tab, a.nx, a.x0 + b * a.nx, a.u_prev[e]);
+        else if (a.src) a.u[e] = a.src[b * (long long)a.src_stride + j];
     }
+}
+
+// After an advancing step: the resident u_prev of every ADVANCED instance becomes the u applied (usable: k_aux_merge's flag, the mask k_sim_step advanced by).
+__global__ void __launch_bounds__(256) k_policy_commit(long long batch, int nu, const unsigned char *usable, const double *u, double *u_prev)
+{
+    const long long total = batch * nu;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256)
+        if (usable[e / nu]) u_prev[e] = u[e];
 }
 #endif

@@ -305,6 +305,40 @@ class GpuProblem(object):
         self._pf_lib = lib if lib.size else None      # (the host's array: rollout() cuts the windows of trajectories it finishes on the host out of it)
         self._pf_ccols = 0
 
+    # -- rule-based feedback policy ------------------------------------------------------------------------
+    def upload_policy(self, P):
+        """a policy.ThresholdPolicy resident on the device (mld_upload_policy), owned by the problem and independent of the batch, like the profile
+        library: rollout(policy=True) and sim_step(resolve=R, policy=True) apply it where the state lives.  None removes it.  A new policy resets the
+        resident policy state."""
+        if P is None:
+            check(_lib.load().mld_upload_policy(self._h, None, None, None, None, None, None))
+            self._policy = None
+            return
+        d = self.model.dims
+        if (P.n_models, P.nu, P.nx) != (self.model.n_models, d["nu"], d["nx"]):
+            raise ValueError("the policy is shaped (n_models %d, nu %d, nx %d), the problem (%d, %d, %d)" % (P.n_models, P.nu, P.nx, self.model.n_models, d["nu"], d["nx"]))
+        check(_lib.load().mld_upload_policy(self._h, _lib.dptr(P.sel), _lib.dptr(P.on_at), _lib.dptr(P.off_at), _lib.dptr(P.u_on), _lib.dptr(P.u_off),
+                                            P.mode.ctypes.data_as(C.POINTER(C.c_int32))))
+        self._policy = P      # (host copy: rollout() applies the rule to the trajectories it finishes on the host)
+
+    def policy_state(self, u_prev=None, reset=False):
+        """the resident u_prev (batch, nu) of the policy: the input applied before the next step (mld_set_policy_state / mld_download_policy_state).
+        u_prev given: set it ((nu,) is broadcast); reset=True: every ruled channel back to its model's u_off, the state after any upload().  Returns the
+        state now resident."""
+        B, nu = self.batch, self.model.dims["nu"]
+        if u_prev is not None:
+            u_prev = np.asarray(u_prev, dtype=np.float64)
+            if u_prev.shape == (nu,):
+                u_prev = np.broadcast_to(u_prev, (B, nu))
+            if u_prev.shape != (B, nu):
+                raise ValueError("u_prev has shape %s, expected (%d, %d) or (%d,)" % (u_prev.shape, B, nu, nu))
+            check(_lib.load().mld_set_policy_state(self._h, _lib.dptr(np.ascontiguousarray(u_prev))))
+        elif reset:
+            check(_lib.load().mld_set_policy_state(self._h, None))
+        out = np.zeros((B, nu))
+        check(_lib.load().mld_download_policy_state(self._h, _lib.dptr(out)))
+        return out
+
     def _start_array(self, start, n_lead):
         """int64 starts with n_lead leading axes after the batch -- (batch, n_groups) or (batch, n_cols, n_groups); the same without the batch axis is
         broadcast over the batch; ValueError on a float dtype or a shape that fits neither, before any C call"""
@@ -536,7 +570,7 @@ class GpuProblem(object):
         check(_lib.load().mld_sim_log_count(self._h, C.byref(n), C.byref(cap)))
         return int(n.value), int(cap.value)
 
-    def sim_step(self, v0=None, act_start=None, step=0, actual=None, advance=True, log=None, outputs=False, resolve=None, u0=None):
+    def sim_step(self, v0=None, act_start=None, step=0, actual=None, advance=True, log=None, outputs=False, resolve=None, u0=None, policy=False):
         """one plant step of the resident batch on device (mld_sim_step_batch): the reference's lsim_k(x_k, v_k=, omega_k) with the whole step-0 slice --
         of the last solve's plans (v0=None; instances without a usable plan are skipped and counted) or the caller's v0 (batch, nv) / (nv,) -- under the
         forecast's step 0 or, with actual, the element `step` of the realised series at act_start (batch, n_groups) / (n_groups,) of the resident profile
@@ -546,9 +580,14 @@ class GpuProblem(object):
         resolve: an aux_resolve.BatchAuxResolver over the same models -- the step of the reference's lsim_k(x_k, u_k=, omega_k) instead
         (mld_sim_step_resolve): only u is taken -- the plan's (u0=None) or the caller's u0 (batch, nu) / (nu,) -- and delta, z, mu are re-derived on the device
         under the omega_k used; v0 must be None.  An instance whose auxiliary problem has no feasible point is skipped like one without a plan.
-        outputs=True additionally returns v0 (batch, nv), the resolved slices, and aux_status (batch), the resolver's status, -1 = not attempted."""
+        outputs=True additionally returns v0 (batch, nv), the resolved slices, and aux_status (batch), the resolver's status, -1 = not attempted.
+        policy=True (with resolve): the ruled channels of u come from the resident policy (upload_policy), written on the device from the current x0 and
+        the resident u_prev (mld_sim_step_policy, kernel k_policy_inputs); u0 / the plan supply the passed-through channels only, and no plan is needed
+        when every channel is ruled.  An advancing step moves the resident u_prev of every advanced instance to the u applied."""
         d, B = self.model.dims, self.batch
         nv = self.model.nv
+        if policy and resolve is None:
+            raise ValueError("policy=True goes with resolve (a BatchAuxResolver re-derives the auxiliaries of the rule's u)")
         if resolve is None and u0 is not None:
             raise ValueError("u0 given without resolve (the whole slice is v0; u0 goes with a BatchAuxResolver that re-derives the rest)")
         if resolve is not None:
@@ -584,7 +623,7 @@ class GpuProblem(object):
             if outputs:
                 out.update(v0=np.zeros((B, nv)), aux_status=np.zeros(B, np.int32))
             aux = resolve.problem._h if resolve.problem is not None else None
-            check(_lib.load().mld_sim_step_resolve(
+            check((_lib.load().mld_sim_step_policy if policy else _lib.load().mld_sim_step_resolve)(
                 self._h, aux, _lib.dptr(u0), st.ctypes.data_as(C.POINTER(C.c_int64)) if st is not None else None, int(step), flags,
                 _lib.dptr(out["x_k1"]) if out else None, _lib.dptr(out["y"]) if out else None,
                 out["cons"].ctypes.data_as(C.POINTER(C.c_uint8)) if out else None, _lib.dptr(out["cons_vio"]) if out else None,
@@ -607,7 +646,7 @@ class GpuProblem(object):
         out["n_skipped"] = int(skipped.value)
         return out
 
-    def rollout(self, resolve, K=None, u_seq=None, omega_seq=None, start=None, step=0, cost_w=None, trajectories=False):
+    def rollout(self, resolve, K=None, u_seq=None, omega_seq=None, start=None, step=0, cost_w=None, trajectories=False, policy=False, u_prev=None):
         """open-loop rollout of the resident batch under S realised disturbances, on device (mld_rollout_batch, kernel k_rollout): the reference's
         MldModel.lsim / lsim_k in a loop with _compute_aux at every step (models/mld_model.py:543-642, 647-699, 701-766), batch x S trajectories in one launch.
         resolve: an aux_resolve.BatchAuxResolver(..., small_lds=True) over the same models.  u_seq (batch, K, nu) / (K, nu), or None = the inputs of the
@@ -618,7 +657,12 @@ class GpuProblem(object):
         not_attempted, finished_on_host)); trajectories=True adds x (batch, S, K + 1, nx), v (batch, S, K, nv), y, cons_vio, cons_row (batch, S, K).
         end_status 0 complete, 1 the auxiliary problem of step steps_done is infeasible (NaN / -1 from there on, summaries NaN), -1 not attempted (no usable
         plan).  Trajectories the device's LDS solver declined (2) are finished on the host -- resolve.resolve per remaining step, whose own solve falls back
-        to the dense kernel, then simlog.lsim_k_batch -- and end 0 or 1; they are counted in stats["finished_on_host"]."""
+        to the dense kernel, then simlog.lsim_k_batch -- and end 0 or 1; they are counted in stats["finished_on_host"].
+        policy=True: the closed loop of the resident rule-based policy instead (upload_policy; mld_rollout_policy, kernel k_rollout_policy) -- at every step
+        the ruled channels of u_k come from the trajectory's own x_k and u_{k-1}, u_seq / the plan supply the passed-through channels only (no plan is
+        needed when every channel is ruled); u_prev (batch, nu) / (nu,) is the input before step 0, None = the resident policy state, which the call
+        leaves as it is.  The result carries switches (batch, S): the (step, ruled channel) pairs whose input changed, -1 unless the trajectory ended 0.
+        The host completion applies the rule too."""
         from . import simlog
         d, B, nv = self.model.dims, self.batch, self.model.nv
         nx, nu, nw, ny = d["nx"], d["nu"], d["nomega"], d["ny"]
@@ -631,6 +675,15 @@ class GpuProblem(object):
             K = u_seq.shape[1]
             u_seq = np.ascontiguousarray(u_seq)
         K = self.N_tilde if K is None else int(K)
+        if u_prev is not None and not policy:
+            raise ValueError("u_prev given without policy=True (the open-loop rollout has no previous input)")
+        if policy and u_prev is not None:
+            u_prev = np.asarray(u_prev, dtype=np.float64)
+            if u_prev.shape == (nu,):
+                u_prev = np.broadcast_to(u_prev, (B, nu))
+            if u_prev.shape != (B, nu):
+                raise ValueError("u_prev has shape %s, expected (%d, %d) or (%d,)" % (u_prev.shape, B, nu, nu))
+            u_prev = np.ascontiguousarray(u_prev)
         if (omega_seq is None) == (start is None) and nw:
             raise ValueError("exactly one of omega_seq and start must be given (%s)" % ("both are" if start is not None else "neither is"))
         st = None
@@ -665,6 +718,14 @@ class GpuProblem(object):
                 o.update(x=np.zeros((B, S, K + 1, nx)), v=np.zeros((B, S, K, nv)), y=np.zeros((B, S, K, ny)), cons_vio=np.zeros((B, S, K)),
                          cons_row=np.zeros((B, S, K), np.int32))
             stats = np.zeros(4, np.int64)
+            if policy:
+                o["switches"] = np.zeros((B, S), np.int32)
+                check(_lib.load().mld_rollout_policy(
+                    self._h, aux, K, S, _lib.dptr(u_seq), _lib.dptr(u_prev), _lib.dptr(omega_seq) if nw else None, lp(st), int(step), _lib.dptr(cost_w), rows,
+                    _lib.dptr(o.get("x")), _lib.dptr(o.get("v")), _lib.dptr(o.get("y")), _lib.dptr(o.get("cons_vio")), ip(o.get("cons_row")),
+                    _lib.dptr(o["cost"]), _lib.dptr(o["mu_total"]), _lib.dptr(o["worst_vio"]), ip(o["worst_step"]), ip(o["steps_done"]), ip(o["end_status"]),
+                    ip(o["switches"]), lp(stats)))
+                return o, stats
             check(_lib.load().mld_rollout_batch(
                 self._h, aux, K, S, _lib.dptr(u_seq), _lib.dptr(omega_seq) if nw else None, lp(st), int(step), _lib.dptr(cost_w), rows,
                 _lib.dptr(o.get("x")), _lib.dptr(o.get("v")), _lib.dptr(o.get("y")), _lib.dptr(o.get("cons_vio")), ip(o.get("cons_row")),
@@ -681,10 +742,18 @@ class GpuProblem(object):
             midx = np.zeros(B, np.int64) if midx is None else np.asarray(midx, np.int64)
             if midx.shape != (B,):
                 raise MldGpuError("rollout: the model indices of the resident batch are not known on the host (upload() keeps them)")
-            if u_seq is None:
+            P = getattr(self, "_policy", None) if policy else None
+            if policy and P is None:
+                raise MldGpuError("rollout: the resident policy is not known on the host (upload_policy() keeps it)")
+            if u_seq is None and P is not None and P.all_ruled:
+                u_all = np.zeros((B, K, nu))      # (never read: every channel is ruled)
+            elif u_seq is None:
                 u_all = np.ascontiguousarray(self.download()["v"].reshape(B, self.N_tilde, nv)[:, :K, :nu])
             else:
                 u_all = u_seq
+            up_t = None
+            if P is not None:
+                up_t = np.repeat(self.policy_state() if u_prev is None else u_prev, S, axis=0)
             if omega_seq is None and nw:
                 from . import profiles
                 om_all = profiles.windows(self._pf_lib, st.reshape(B * S, -1), int(step), K, self._pf_width).reshape(B, S, K, nw)
@@ -697,7 +766,8 @@ class GpuProblem(object):
             cw_t = None
             if cost_w is not None:
                 cw_t = np.repeat(cost_w if rows != self.model.n_models else cost_w[midx], S, axis=0)
-            simlog.rollout_continue(resolve.mats, d, np.repeat(midx, S), np.repeat(u_all, S, axis=0), om_all.reshape(T, K, nw), flat, todo, resolve.resolve, cw_t)
+            simlog.rollout_continue(resolve.mats, d, np.repeat(midx, S), np.repeat(u_all, S, axis=0), om_all.reshape(T, K, nw), flat, todo, resolve.resolve, cw_t,
+                                    policy=P, u_prev=up_t)
             out = {k: flat[k].reshape(out[k].shape) for k in out}
         es = out["end_status"]
         out["stats"] = dict(trajectories=int(stats[0]), complete=int((es == 0).sum()) if n_host else int(stats[1]), infeasible=int((es == 1).sum()) if n_host else int(stats[2]),

@@ -130,13 +130,15 @@ def lsim_k_reference_order(mats_list, dims, model_idx, x, v0, omega):
     return out
 
 
-def rollout_continue(mats_list, dims, model_idx, u_seq, omega_seq, out, todo, resolve_fn, cost_w=None, step_fn=lsim_k_batch):
+def rollout_continue(mats_list, dims, model_idx, u_seq, omega_seq, out, todo, resolve_fn, cost_w=None, step_fn=lsim_k_batch, policy=None, u_prev=None):
     """continue the flat trajectories `todo` (indices) of `out` in place, each from its step out["steps_done"][t] and the state out["x"][t, steps_done]:
     model_idx (T,), u_seq (T, K, nu), omega_seq (T, K, nomega), cost_w (T, K, nv) or None; out: x (T, K + 1, nx), v (T, K, nv), y, cons_vio, cons_row (T, K),
     steps_done, end_status, cost, mu_total, worst_vio, worst_step (T,).  Per step, in the reference's order: resolve_fn(x, u, omega, model_idx) ->
     dict(v = [delta | z | mu] rows (NaN where there is no feasible point), status) as aux_resolve.BatchAuxResolver.resolve returns it, then step_fn
     (lsim_k_batch, or lsim_k_reference_order) with v_k = [u_k; delta; z; mu].  A trajectory whose auxiliary problem has no feasible point ends 1 at that step (NaN / -1 from there on, summaries
-    NaN / -1), the others end 0 with their summaries reduced from the finished trajectory."""
+    NaN / -1), the others end 0 with their summaries reduced from the finished trajectory.
+    policy: a policy.ThresholdPolicy -- the ruled channels of u_k come from policy.apply_np on the trajectory's own x_k and u_{k-1} (out["v"][t, k - 1, :nu],
+    u_prev (T, nu) before step 0), u_seq supplies the passed-through channels only; out["switches"] (T,), if present, is filled like the other summaries."""
     nu, nv2 = int(dims.get("nu", 0)), sum(int(dims.get(k, 0)) for k in ("ndelta", "nz", "nmu"))
     nf = nu + int(dims.get("ndelta", 0)) + int(dims.get("nz", 0))
     todo = np.asarray(todo, dtype=np.int64)
@@ -148,6 +150,9 @@ def rollout_continue(mats_list, dims, model_idx, u_seq, omega_seq, out, todo, re
         if not act.size:
             continue
         x, uk, wk = out["x"][act, k], u_seq[act, k], omega_seq[act, k]
+        if policy is not None:
+            from .policy import apply_np
+            uk = apply_np(policy, midx[act], x, out["v"][act, k - 1, :nu] if k else np.asarray(u_prev, dtype=np.float64)[act], uk)
         if nv2:
             r = resolve_fn(x, uk, wk, midx[act])
             aux = np.asarray(r["v"], dtype=np.float64).reshape(act.size, nv2)
@@ -167,6 +172,11 @@ def rollout_continue(mats_list, dims, model_idx, u_seq, omega_seq, out, todo, re
     dead = todo[out["end_status"][todo] != 0]
     out["cost"][dead] = out["mu_total"][dead] = out["worst_vio"][dead] = np.nan
     out["worst_step"][dead] = -1
+    if policy is not None and "switches" in out:
+        from .policy import switches_np
+        out["switches"][dead] = -1
+        if done.size:
+            out["switches"][done] = switches_np(policy, midx[done], out["v"][done][:, :, :nu], np.asarray(u_prev, dtype=np.float64)[done])
     if done.size:
         v = out["v"][done]
         out["cost"][done] = np.einsum("tkj,tkj->t", cost_w[done], v) if cost_w is not None else 0.0
@@ -175,10 +185,12 @@ def rollout_continue(mats_list, dims, model_idx, u_seq, omega_seq, out, todo, re
     return out
 
 
-def rollout_np(mats_list, dims, model_idx, x0, u_seq, omega_seq, resolve_fn, cost_w=None):
+def rollout_np(mats_list, dims, model_idx, x0, u_seq, omega_seq, resolve_fn, cost_w=None, policy=None, u_prev=None):
     """GpuProblem.rollout stated in numpy: x0 (B, nx), u_seq (B, K, nu), omega_seq (B, S, K, nomega), model_idx (B,) or None, cost_w (B, K, nv) or None ->
     dict(x (B, S, K + 1, nx), v (B, S, K, nv), y, cons_vio, cons_row (B, S, K), cost, mu_total, worst_vio, worst_step, steps_done, end_status (B, S)).
-    resolve_fn as rollout_continue takes it.  The chain is the reference's, in its order of operations (lsim_k_reference_order)."""
+    resolve_fn as rollout_continue takes it.  The chain is the reference's, in its order of operations (lsim_k_reference_order).
+    policy: GpuProblem.rollout(policy=True) instead -- u_seq supplies the passed-through channels, u_prev (B, nu) the inputs before step 0 (None: the
+    policy's reset state), and the result carries switches (B, S)."""
     nx, nw, ny = (int(dims.get(k, 0)) for k in ("nx", "nomega", "ny"))
     nv = sum(int(dims.get(k, 0)) for k in ("nu", "ndelta", "nz", "nmu"))
     u_seq = np.asarray(u_seq, dtype=np.float64)
@@ -190,7 +202,12 @@ def rollout_np(mats_list, dims, model_idx, x0, u_seq, omega_seq, resolve_fn, cos
     out = dict(x=np.full((T, K + 1, nx), np.nan), v=np.full((T, K, nv), np.nan), y=np.full((T, K, ny), np.nan), cons_vio=np.full((T, K), np.nan),
                cons_row=np.full((T, K), -1, np.int32), cost=np.zeros(T), mu_total=np.zeros(T), worst_vio=np.zeros(T), worst_step=np.zeros(T, np.int32),
                steps_done=np.zeros(T, np.int32), end_status=np.zeros(T, np.int32))
+    up = None
+    if policy is not None:
+        out["switches"] = np.zeros(T, np.int32)
+        up = np.repeat(policy.initial_state(midx) if u_prev is None else np.asarray(u_prev, dtype=np.float64).reshape(B, -1), S, axis=0)
     out["x"][:, 0] = np.repeat(np.asarray(x0, dtype=np.float64).reshape(B, nx), S, axis=0)
     rollout_continue(mats_list, dims, np.repeat(midx, S), np.repeat(u_seq, S, axis=0), omega_seq.reshape(T, K, nw), out, np.arange(T), resolve_fn,
-                     None if cost_w is None else np.repeat(np.asarray(cost_w, dtype=np.float64).reshape(B, K, nv), S, axis=0), step_fn=lsim_k_reference_order)
+                     None if cost_w is None else np.repeat(np.asarray(cost_w, dtype=np.float64).reshape(B, K, nv), S, axis=0), step_fn=lsim_k_reference_order,
+                     policy=policy, u_prev=up)
     return {k: a.reshape((B, S) + a.shape[1:]) for k, a in out.items()}
