@@ -292,6 +292,7 @@ __device__ __forceinline__ void wave_rows_dot4(const glb_f64 *r0, const glb_f64 
 // ------------------------------------------------------------------------------------------------
 // small block-level primitives (SOL_NT threads)
 // ------------------------------------------------------------------------------------------------
+#define LIST_NCH 8               // row chunks (SOL_NT rows each) whose counts the pivot's list exchange holds: m <= 4096; a larger shape compacts chunk by chunk
 struct Shared {
     double r2v[2][SOL_NW];     // single-barrier reductions of the simplex loop: two alternating buffers (see block_max1)
     int r2i[2][SOL_NW];
@@ -314,8 +315,12 @@ struct Shared {
     long long deadline;        // wall_clock64 value at which this instance's time limit ends (0 = none): checked between nodes, between cut rounds and every 128 pivots
     int timed_out;
     int cut_cap;               // rows (original + cut) the cut generators may fill right now: S.first_cap in the root cut loop, S.mcap in the root restart
+    // the pivot's own exchange slots: nothing else writes them, so a barrier of the pivot never has to protect them from another primitive's readers
+    double piv_el;             // pivot element, written by the thread that stages it (s_pivot_head)
+    int lcnt[1 + LIST_NCH][SOL_NW];      // per-wave counts of the sector chunk [0] and of the row chunks [1 ..] of the update lists (list_counts)
 #ifdef MLD_PIVOT_PROF
-    long long pprof[5];
+    long long pprof[8];        // ticks: 0 head (stage, scale, x_B, cost row, book-keeping), 1 sector list, 2 row list, 3 update loop of single pivots; 4 .. 7 the same for pairs
+    long long pcnt[8];         // 0 single pivots, 1 pairs, 2 long-step ticks, 3 long-step pivots, 4 groups examined, 5 groups passed, 6 pivots with flips
 #endif
     long long prof[8];         // ticks: 0 pivot update, 1 simplex selection, 2 cuts, 3 leaf, 4 set_bounds, 5 residual/refactor, 6 setup
 #ifdef MLD_CUT_PROF
@@ -448,6 +453,20 @@ __device__ __forceinline__ int block_compact(Shared &sh, bool flag, unsigned sho
     for (int q = 0; q < SOL_NW; ++q) { const int cq = sh.red_i[q]; if (q < wave) off += cq; tot += cq; }
     if (flag) list[base + off + __popcll(bal & ((1ull << lane) - 1ull))] = value;
     return base + tot;
+}
+
+// The update lists of a pivot in ONE exchange (s_pivot_update, s_pivot_pair) instead of two barriers per SOL_NT-wide chunk: every wave writes the counts of
+// its ballots for ALL chunks to its own slots sh.lcnt[chunk][wave], one barrier follows, and every thread sums the slots of a chunk -- the waves before its own
+// (its offset) and all of them (the chunk's total) -- and scatters; the lists come out in the order of block_compact, chunk by chunk.  A slot carries up to
+// three counts of 10 bits (LIST_PACK: flag 1, flag 2, both; a chunk has at most SOL_NT = 512 members, so the sums of a chunk stay inside their fields).
+// sh.lcnt has no other user and two barriers separate its readers from the next pivot's writers (the one before the update and the one after it).
+#define LIST_PACK(b1_, b2_) (__popcll(b1_) | (__popcll(b2_) << 10) | (__popcll((b1_) & (b2_)) << 20))
+#define LIST_UNION(x_) (((x_) & 1023) + (((x_) >> 10) & 1023) - ((x_) >> 20))      // members with flag 1 or flag 2
+__device__ __forceinline__ void list_counts(const Shared &sh, int chunk, int wave, int &off, int &tot)
+{
+    off = 0; tot = 0;
+#pragma unroll
+    for (int q = 0; q < SOL_NW; ++q) { const int cq = sh.lcnt[chunk][q]; if (q < wave) off += cq; tot += cq; }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1173,6 +1192,11 @@ __device__ __forceinline__ void s_update_rows2(glb_f64 *D, int ld, const lds_f64
 // next pivot can be chosen before it (s_pivot_pair).
 // SECOND: the pivot follows one whose row update has not been done yet (its row r1 and column c1 are staged in w.rowr / w.colc, w.secflag bit 0 marks its active
 // sectors).  rowr already holds row r as that update leaves it (s_look_ahead); the column's entries get the same correction.
+// Three block barriers: (1) on entry -- the ratio test's readers of the staging buffers (ea[cbest]) are done; (2) after the staging -- the pivot element, which the
+// thread that staged it left in sh.piv_el, and everything read before it (x_B[r], x_N[c], w[r], d[c]) is in every thread's registers before any of them is written;
+// (3) at the end.  Between (2) and (3) no thread reads what another one writes: a thread scales the rowr[k] and reads the colc[i] it staged itself, updates its own
+// x_B[i], w[i] (the owner of row r writes the entering value) and d[k] from the rowr[k] it scaled (the owner of column n takes d[n]), and thread 0's book-keeping
+// touches scalars nobody reads before (3).  MLD_DBG_PIVOT_SYNC_R5 puts the three barriers that stood between these steps back (DESIGN section 6: hazard table).
 template <bool L, bool SECOND>
 __device__ __forceinline__ void s_pivot_head(const Ws &w, Shared &sh, int r, int c, double leave_value, lds_f64 *rowr, lds_f64 *colc, int r1, int c1)
 {
@@ -1181,8 +1205,9 @@ __device__ __forceinline__ void s_pivot_head(const Ws &w, Shared &sh, int r, int
     glb_f64 *D = (glb_f64 *)w.D;
     glb_f64 *rowr_g = D + (size_t)r * ld;
     MLD_CHECK(w, r >= 0 && r < m && c >= 0 && c < n && m <= w.mcap, 101, r, c);
+    const bool sync_r5 = (w.dbg & MLD_DBG_PIVOT_SYNC_R5) != 0;      // the three barriers this function no longer needs (below), kept selectable
     __syncthreads();
-    // stage multiplier column and the pivot row in LDS (raw first: the pivot element is read back from LDS)
+    // stage multiplier column and the pivot row in LDS (raw first: the pivot element goes to sh.piv_el)
     if (!SECOND) {   // (rows that can never bind are not maintained: multiplier 0.)  All loads of both gathers are issued before the first LDS store: the
         // column gather is one 64-byte sector per element and each dependent round costs a full memory latency
         const int span = (m > n + 1 ? m : n + 1);
@@ -1199,6 +1224,7 @@ __device__ __forceinline__ void s_pivot_head(const Ws &w, Shared &sh, int r, int
                 const int i = b0 + q * SOL_NT + tid;
                 if (i < m) colc[i] = cv[q];
                 if (i <= n) rowr[i] = rv[q];
+                if (i == c) sh.piv_el = rv[q];
             }
         }
     } else {
@@ -1225,33 +1251,35 @@ __device__ __forceinline__ void s_pivot_head(const Ws &w, Shared &sh, int r, int
                 colc[i] = v;
             }
         }
+        if (tid == c % SOL_NT) sh.piv_el = rowr[c];      // (s_look_ahead staged rowr[c] on this thread)
     }
-    const double xBr = h_xB[r], xNc = h_xN[c], wr = h_dw[r];
+    typename HotT<L>::f64p d = h_d;    // cost row: LDS when it fits (SolverShape::lCost), else the row after the last dictionary row
+    const double xBr = h_xB[r], xNc = h_xN[c], wr = h_dw[r], dc = d[c];
     __syncthreads();
-    const double p = rowr[c];
+    const double p = sh.piv_el;
     const double inv = 1.0 / p;
     const double theta = (xBr - leave_value) * inv;
     const double enter_val = xNc + theta;
-    __syncthreads();
+    if (sync_r5) __syncthreads();
     int my_nz = 0;
     for (int k = tid; k <= n; k += SOL_NT) { const double v = (k == c) ? inv : rowr[k] * inv; rowr[k] = v; rowr_g[k] = v; my_nz += (v != 0.0); }
     if (w.dbg && my_nz) atomicAdd((unsigned long long *)&sh.prof[7], (unsigned long long)my_nz);   // pivot-row non-zeros (diagnostic)
     for (int i = tid; i < m; i += SOL_NT) {
         const double ci = colc[i];
-        h_xB[i] -= ci * theta;
         // devex (oracle pivot()): w_i = max(w_i, (alpha_iq / alpha_rq)^2 w_r) on the touched rows, w_r = max(w_r / alpha_rq^2, 1)
-        if (i == r) h_dw[i] = fmax(wr * inv * inv, 1.0);
-        else if (ci != 0.0) { const double f = ci * inv, c2 = f * f * wr; if (c2 > h_dw[i]) h_dw[i] = c2; }
+        if (i == r) { h_xB[i] = enter_val; h_dw[i] = fmax(wr * inv * inv, 1.0); }      // (the entering variable takes the row over)
+        else {
+            h_xB[i] -= ci * theta;
+            if (ci != 0.0) { const double f = ci * inv, c2 = f * f * wr; if (c2 > h_dw[i]) h_dw[i] = c2; }
+        }
     }
-    __syncthreads();
+    if (sync_r5) __syncthreads();
     {   // cost row: obj = d[n] + sum_c d_c xN_c
-        typename HotT<L>::f64p d = h_d;    // LDS when it fits (SolverShape::lCost), else the row after the last dictionary row
-        const double dc = d[c];
         if (tid == 0) sh.s_d[0] = dc * theta;      // objective change of this pivot (entering variable moves by theta)
-        __syncthreads();
-        if (dc != 0.0) {
+        if (sync_r5) __syncthreads();
+        if (dc != 0.0) {      // (every thread reads only the rowr[k] it scaled itself)
             for (int k = tid; k < n; k += SOL_NT) d[k] = (k == c) ? -dc * inv : d[k] - dc * rowr[k];
-            if (tid == 0) d[n] += dc * rowr[n];
+            if (tid == n % SOL_NT) d[n] += dc * rowr[n];
         }
     }
     if (tid == 0) {
@@ -1259,7 +1287,6 @@ __device__ __forceinline__ void s_pivot_head(const Ws &w, Shared &sh, int r, int
         MLD_CHECK(w, jb >= 0 && jb < n + w.mcap && jn >= 0 && jn < n + w.mcap, 109, jb, jn);
         h_basic[r] = jn; h_nonbasic[c] = jb;
         w.where[jn] = -1 - r; w.where[jb] = c;
-        h_xB[r] = enter_val;
         h_xN[c] = leave_value;
         h_up[c] = (leave_value == h_hi[jb]) && (h_lo[jb] != h_hi[jb]);
         sh.pivots++; sh.since_check++;
@@ -1278,11 +1305,49 @@ __device__ __forceinline__ void s_pivot_update(const Ws &w, Shared &sh, int r, i
 #ifdef MLD_PIVOT_PROF
     const long long tq1 = wall_clock64();
 #endif
-    // active 64-byte sectors (8 doubles) of the pivot row: only these columns of the other rows change
-    int nact;
-    {
-        const int nsec = (n + SOL_SEC) / SOL_SEC;
-        nact = 0;
+    // active 64-byte sectors (8 doubles) of the pivot row: only these columns of the other rows change; rows with a non-zero multiplier.  Both as ordered
+    // (ascending, deterministic) LDS lists
+    const int nsec = (n + SOL_SEC) / SOL_SEC;
+    int nact = 0, nrows = 0;
+#ifdef MLD_PIVOT_PROF
+    long long tq2;
+#endif
+    if (!(w.dbg & MLD_DBG_PIVOT_SYNC_R5) && nsec <= SOL_NT && m <= LIST_NCH * SOL_NT) {      // one exchange for all chunks (list_counts)
+        const unsigned long long before = (1ull << lane) - 1ull;
+        bool act = false;
+        if (tid < nsec) {
+#pragma unroll
+            for (int e = 0; e < SOL_SEC; ++e) { const int k = tid * SOL_SEC + e; if (k <= n && rowr[k] != 0.0) act = true; }
+        }
+        const unsigned long long bs = __ballot(act);
+        if (lane == 0) sh.lcnt[0][wave] = __popcll(bs);
+        unsigned long long br[LIST_NCH];
+#pragma unroll
+        for (int k = 0; k < LIST_NCH; ++k) {
+            br[k] = 0ull;
+            if (k * SOL_NT < m) {
+                const int i = k * SOL_NT + tid;
+                br[k] = __ballot(i < m && i != r && colc[i] != 0.0);
+                if (lane == 0) sh.lcnt[1 + k][wave] = __popcll(br[k]);
+            }
+        }
+        __syncthreads();
+#ifdef MLD_PIVOT_PROF
+        tq2 = wall_clock64();      // (on this path [1] is the flags and the exchange, [2] the scatter of both lists)
+#endif
+        int off, tot;
+        list_counts(sh, 0, wave, off, tot);
+        if (act) seclist[off + __popcll(bs & before)] = (unsigned short)tid;
+        nact = tot;
+#pragma unroll
+        for (int k = 0; k < LIST_NCH; ++k) {
+            if (k * SOL_NT < m) {
+                list_counts(sh, 1 + k, wave, off, tot);
+                if ((br[k] >> lane) & 1ull) rowlist[nrows + off + __popcll(br[k] & before)] = (unsigned short)(k * SOL_NT + tid);
+                nrows += tot;
+            }
+        }
+    } else {
         for (int t0 = 0; t0 < nsec; t0 += SOL_NT) {       // ordered compaction, SOL_NT sectors at a time
             const int t = t0 + tid;
             bool act = false;
@@ -1292,15 +1357,13 @@ __device__ __forceinline__ void s_pivot_update(const Ws &w, Shared &sh, int r, i
             }
             nact = block_compact(sh, act, (unsigned short)t, w.seclist, nact);
         }
-    }
 #ifdef MLD_PIVOT_PROF
-    const long long tq2 = wall_clock64();
+        tq2 = wall_clock64();
 #endif
-    // rows with a non-zero multiplier, compacted into an LDS list (ascending, deterministic)
-    int nrows = 0;
-    for (int i0 = 0; i0 < m; i0 += SOL_NT) {
-        const int i = i0 + tid;
-        nrows = block_compact(sh, i < m && i != r && colc[i] != 0.0, (unsigned short)i, w.rowlist, nrows);
+        for (int i0 = 0; i0 < m; i0 += SOL_NT) {
+            const int i = i0 + tid;
+            nrows = block_compact(sh, i < m && i != r && colc[i] != 0.0, (unsigned short)i, w.rowlist, nrows);
+        }
     }
     __syncthreads();
 #ifdef MLD_PIVOT_PROF
@@ -1326,7 +1389,8 @@ __device__ __forceinline__ void s_pivot_update(const Ws &w, Shared &sh, int r, i
         sh.rows += (unsigned long long)nrows * (unsigned long long)nact;   // 64-byte sectors updated
         sh.prof[0] += wall_clock64() - tp0;
 #ifdef MLD_PIVOT_PROF
-        sh.pprof[0] += tq1 - tp0; sh.pprof[1] += tq2 - tq1; sh.pprof[2] += tq3 - tq2; sh.pprof[3] += wall_clock64() - tq3;      // ([0] now holds the cost row and the bookkeeping too)
+        sh.pprof[0] += tq1 - tp0; sh.pprof[1] += tq2 - tq1; sh.pprof[2] += tq3 - tq2; sh.pprof[3] += wall_clock64() - tq3;      // ([0]: with a look-ahead that declined, if any)
+        sh.pcnt[0]++;
 #endif
     }
     __syncthreads();
@@ -1725,31 +1789,91 @@ __device__ __forceinline__ void s_pivot_pair(const Ws &w, Shared &sh, int r1, in
     stall = stall2; last_obj = last2;
     s_pivot_head<L, true>(w, sh, r2, c2, lv2, rowr2, colc2, r1, c1);
     cur += sh.s_d[0];
-    // union of the two rows' active sectors and of the two row sets (ordered); the counts of each set and of the overlaps, packed into one exact double
-    int nact = 0; double cnt_s = 0.0;
-    for (int t0 = 0; t0 < nsec; t0 += SOL_NT) {
-        const int t = t0 + tid;
+#ifdef MLD_PIVOT_PROF
+    const long long tq1 = wall_clock64();
+    long long tq2;
+#endif
+    // union of the two rows' active sectors and of the two row sets (ordered); the counts of each set and of the overlaps (s1, s2, s12 sectors; n1, n2, n12 rows)
+    int nact = 0, nrows = 0;
+    unsigned long long s1, s2, s12, n1, n2, n12;
+    if (!(w.dbg & MLD_DBG_PIVOT_SYNC_R5) && nsec <= SOL_NT && m <= LIST_NCH * SOL_NT) {      // one exchange for all chunks and all six counts (list_counts)
+        const unsigned long long before = (1ull << lane) - 1ull;
         int f = 0;
-        if (t < nsec) {
+        if (tid < nsec) {
             bool act = false;
 #pragma unroll
-            for (int e = 0; e < SOL_SEC; ++e) { const int k = t * SOL_SEC + e; if (k <= n && rowr2[k] != 0.0) act = true; }
-            f = (secflag[t] & 1) | (act ? 2 : 0);
-            secflag[t] = (unsigned char)f;
+            for (int e = 0; e < SOL_SEC; ++e) { const int k = tid * SOL_SEC + e; if (k <= n && rowr2[k] != 0.0) act = true; }
+            f = (secflag[tid] & 1) | (act ? 2 : 0);
+            secflag[tid] = (unsigned char)f;
         }
-        cnt_s += (double)(f & 1) + 65536.0 * (double)(f >> 1) + 4294967296.0 * (double)(f == 3);
-        nact = block_compact(sh, f != 0, (unsigned short)t, w.seclist2, nact);
+        const unsigned long long bs1 = __ballot((f & 1) != 0), bs2 = __ballot((f & 2) != 0);
+        if (lane == 0) sh.lcnt[0][wave] = LIST_PACK(bs1, bs2);
+        unsigned long long br[LIST_NCH];      // rows in either set
+#pragma unroll
+        for (int k = 0; k < LIST_NCH; ++k) {
+            br[k] = 0ull;
+            if (k * SOL_NT < m) {
+                const int i = k * SOL_NT + tid;
+                const bool in1 = i < m && i != r1 && i != r2 && colc[i] != 0.0, in2 = i < m && i != r2 && colc2[i] != 0.0;
+                const unsigned long long b1 = __ballot(in1), b2 = __ballot(in2);
+                br[k] = b1 | b2;
+                if (lane == 0) sh.lcnt[1 + k][wave] = LIST_PACK(b1, b2);
+            }
+        }
+        __syncthreads();
+#ifdef MLD_PIVOT_PROF
+        tq2 = wall_clock64();
+#endif
+        lds_u16 *seclist_w = (lds_u16 *)w.seclist2, *rowlist_w = (lds_u16 *)w.rowlist2;
+        int off, tot;
+        list_counts(sh, 0, wave, off, tot);
+        if (f) seclist_w[LIST_UNION(off) + __popcll((bs1 | bs2) & before)] = (unsigned short)tid;
+        s1 = tot & 1023; s2 = (tot >> 10) & 1023; s12 = tot >> 20;
+        nact = LIST_UNION(tot);
+        n1 = n2 = n12 = 0ull;
+#pragma unroll
+        for (int k = 0; k < LIST_NCH; ++k) {
+            if (k * SOL_NT < m) {
+                list_counts(sh, 1 + k, wave, off, tot);
+                if ((br[k] >> lane) & 1ull) rowlist_w[nrows + LIST_UNION(off) + __popcll(br[k] & before)] = (unsigned short)(k * SOL_NT + tid);
+                n1 += tot & 1023; n2 += (tot >> 10) & 1023; n12 += tot >> 20;
+                nrows += LIST_UNION(tot);
+            }
+        }
+    } else {      // chunk by chunk; the counts packed into one exact double per list
+        double cnt_s = 0.0;
+        for (int t0 = 0; t0 < nsec; t0 += SOL_NT) {
+            const int t = t0 + tid;
+            int f = 0;
+            if (t < nsec) {
+                bool act = false;
+#pragma unroll
+                for (int e = 0; e < SOL_SEC; ++e) { const int k = t * SOL_SEC + e; if (k <= n && rowr2[k] != 0.0) act = true; }
+                f = (secflag[t] & 1) | (act ? 2 : 0);
+                secflag[t] = (unsigned char)f;
+            }
+            cnt_s += (double)(f & 1) + 65536.0 * (double)(f >> 1) + 4294967296.0 * (double)(f == 3);
+            nact = block_compact(sh, f != 0, (unsigned short)t, w.seclist2, nact);
+        }
+#ifdef MLD_PIVOT_PROF
+        tq2 = wall_clock64();
+#endif
+        double cnt_r = 0.0;
+        for (int i0 = 0; i0 < m; i0 += SOL_NT) {
+            const int i = i0 + tid;
+            const bool in1 = i < m && i != r1 && i != r2 && colc[i] != 0.0, in2 = i < m && i != r2 && colc2[i] != 0.0;
+            cnt_r += (double)in1 + 65536.0 * (double)in2 + 4294967296.0 * (double)(in1 && in2);
+            nrows = block_compact(sh, in1 || in2, (unsigned short)i, w.rowlist2, nrows);
+        }
+        cnt_s = block_sum(sh, cnt_s);
+        cnt_r = block_sum(sh, cnt_r);
+        const unsigned long long cs = (unsigned long long)cnt_s, cr = (unsigned long long)cnt_r;
+        s1 = cs & 0xffffull; s2 = (cs >> 16) & 0xffffull; s12 = cs >> 32; n1 = cr & 0xffffull; n2 = (cr >> 16) & 0xffffull; n12 = cr >> 32;
     }
-    int nrows = 0; double cnt_r = 0.0;
-    for (int i0 = 0; i0 < m; i0 += SOL_NT) {
-        const int i = i0 + tid;
-        const bool in1 = i < m && i != r1 && i != r2 && colc[i] != 0.0, in2 = i < m && i != r2 && colc2[i] != 0.0;
-        cnt_r += (double)in1 + 65536.0 * (double)in2 + 4294967296.0 * (double)(in1 && in2);
-        nrows = block_compact(sh, in1 || in2, (unsigned short)i, w.rowlist2, nrows);
-    }
-    cnt_s = block_sum(sh, cnt_s);
-    cnt_r = block_sum(sh, cnt_r);
     __syncthreads();
+#ifdef MLD_PIVOT_PROF
+    const long long tq3 = wall_clock64();
+#endif
     const lds_u16 *seclist = (const lds_u16 *)w.seclist2, *rowlist = (const lds_u16 *)w.rowlist2;
 #ifdef MLD_ASSERT
     MLD_CHECK(w, nact <= nsec && nrows < m, 102, nact, nrows);
@@ -1770,10 +1894,12 @@ __device__ __forceinline__ void s_pivot_pair(const Ws &w, Shared &sh, int r1, in
     }
     if (tid == 0) {
         // 64-byte sectors moved: |R1 x S1| + |R2 x S2| - |(R1 and R2) x (S1 and S2)|
-        const unsigned long long cs = (unsigned long long)cnt_s, cr = (unsigned long long)cnt_r;
-        const unsigned long long s1 = cs & 0xffffull, s2 = (cs >> 16) & 0xffffull, s12 = cs >> 32, n1 = cr & 0xffffull, n2 = (cr >> 16) & 0xffffull, n12 = cr >> 32;
         sh.rows += n1 * s1 + n2 * s2 - n12 * s12;
         sh.prof[0] += wall_clock64() - tp0;
+#ifdef MLD_PIVOT_PROF
+        sh.pprof[4] += tq1 - tp0; sh.pprof[5] += tq2 - tq1; sh.pprof[6] += tq3 - tq2; sh.pprof[7] += wall_clock64() - tq3;      // ([4]: both first halves and the look-ahead)
+        sh.pcnt[1]++;
+#endif
     }
     __syncthreads();
 }
@@ -1953,7 +2079,14 @@ __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double 
             double slope = viol, tm = tmax, a_best = 0.0;
             int nflip_groups = 0;
             cbest = -1;
+#ifdef MLD_PIVOT_PROF
+            const long long tl0 = wall_clock64();
+            int ngroups = 0;
+#endif
             for (;;) {
+#ifdef MLD_PIVOT_PROF
+                ngroups++;
+#endif
                 double drop = 0.0, bv = -1.0; int bi = -1;
                 for (int c = tid; c < n; c += SOL_NT) {
                     const double aa = ea[c];
@@ -2029,6 +2162,9 @@ __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double 
                 fresh_obj = true;                                         // the flips moved the objective: recompute it at the next iteration
                 __syncthreads();
             }
+#ifdef MLD_PIVOT_PROF
+            if (tid == 0) { sh.pcnt[2] += wall_clock64() - tl0; sh.pcnt[3]++; sh.pcnt[4] += ngroups; sh.pcnt[5] += nflip_groups; sh.pcnt[6] += (cbest >= 0 && nflip_groups > 0); }
+#endif
             if (cbest >= 0 && a_best < S_PIV_TINY && viol <= S_PTOL_SKIP && nflip_groups == 0) { __syncthreads(); if (tid == 0) h_skip[r] |= 1; continue; }
             if (cbest < 0) return s_unperturb(w, sh, LP_INFEASIBLE, max_pivots);
             MLD_CHECK(w, cbest < n, 106, cbest, 1);
@@ -3892,7 +4028,7 @@ __device__ __forceinline__ bool s_setup_entry(Ws &w, Shared &sh, const SolverSha
         sh.cut_cap = S.first_cap;
         sh.deadline = 0; sh.timed_out = 0;      // (armed when the search starts: the root LP always runs to its end -- without it there is no answer at all)
 #ifdef MLD_PIVOT_PROF
-        for (int k = 0; k < 5; ++k) sh.pprof[k] = 0;
+        for (int k = 0; k < 8; ++k) sh.pprof[k] = sh.pcnt[k] = 0;
 #endif
 #ifdef MLD_CUT_PROF
         for (int k = 0; k < 15; ++k) sh.cprof[k] = 0;
@@ -4421,7 +4557,8 @@ __device__ __forceinline__ void s_write_results(Shared &sh, const BatchDev &B, c
         B.nodes_out[inst] = s.nodes; B.pivots_out[inst] = skipped ? 0 : sh.pivots; B.cuts_out[inst] = s.cuts; B.refac_out[inst] = skipped ? 0 : sh.refactors;
         B.ticks_out[inst] = skipped ? 0 : wall_clock64() - e.t_begin; B.rows_out[inst] = skipped ? 0 : (long long)sh.rows;
 #ifdef MLD_PIVOT_PROF
-        if (B.prof_out && !skipped) { for (int k = 0; k < 5; ++k) B.prof_out[(size_t)inst * 8 + k] = sh.pprof[k]; B.prof_out[(size_t)inst * 8 + 5] = 0; B.prof_out[(size_t)inst * 8 + 6] = 0; B.prof_out[(size_t)inst * 8 + 7] = sh.prof[7]; }
+        // (-DMLD_PIVOT_PROF: the clocks of the pivot's sub-phases; -DMLD_PIVOT_PROF=2: the counts and the long-step clock of the same launch instead -- scripts/gpu_pivot_prof.py)
+        if (B.prof_out && !skipped) for (int k = 0; k < 8; ++k) B.prof_out[(size_t)inst * 8 + k] = MLD_PIVOT_PROF == 2 ? sh.pcnt[k] : sh.pprof[k];
 #else
         if (B.prof_out && !skipped) for (int k = 0; k < 8; ++k) B.prof_out[(size_t)inst * 8 + k] = sh.prof[k];
 #endif
