@@ -141,9 +141,12 @@ typedef enum {
                                            binary: results are bit-identical, only speed changes) */
     MLD_DBG_SMALL_PIVOT_CAP = 1 << 25,  /* k_small_milp (MLD_SMALL_LDS) with a pivot budget of 2: most instances decline and are re-solved by
                                            the dense kernel, so that the overflow route runs on any shape (the MLD_DBG_LP_LDS_K24 idea) */
-    MLD_DBG_PIVOT_SYNC_R5 = 1 << 26     /* k_solve's pivot with the block barriers it had before they were halved: six in its first half, two per
+    MLD_DBG_PIVOT_SYNC_R5 = 1 << 26,    /* k_solve's pivot with the block barriers it had before they were halved: six in its first half, two per
                                            SOL_NT-wide chunk of the sector and row lists (and two sums for the counts of a pair) instead of three and
                                            one exchange (A/B on the same binary: results and rows_updated are bit-identical, only speed changes) */
+    MLD_DBG_SELECT_R6 = 1 << 27         /* k_solve's choice of (row, column) as it was before its block reductions left the LDS crossbar:
+                                           __shfl_down reductions with a serial combine of the waves' partials, the eligibility test of the
+                                           ratio test as nested branches (A/B on the same binary: results are bit-identical, only speed changes) */
 } mld_reserved_bit;
 
 /* Linear cost in tiled horizon form (the Python layer parses the reference's string-keyed atoms,

@@ -425,6 +425,27 @@ int mld_debug_profile(mld_problem_t *p, int64_t out[8])
     return MLD_OK;
 }
 
+/* the block reductions of k_solve's selection on n_vec caller-supplied vectors of 512 (value, index) lanes (internal diagnostics; not part of the public
+ * header): out_max[4 n_vec] = per vector (block_max1, its DPP version), then per vector (block_min1, its DPP version); out_arg / out_val[2 n_vec] = per
+ * vector the arg-max and its value of (block_argmax1, its DPP version) */
+int mld_debug_reduce(const double *values, const int32_t *index, int n_vec, double *out_max, int32_t *out_arg, double *out_val)
+{
+    if (!values || !index || n_vec < 1 || n_vec > 65535 || !out_max || !out_arg || !out_val) { mld_set_error("mld_debug_reduce: bad arguments"); return MLD_ERR_INVALID; }
+    if (mld_device_count() <= 0) { mld_set_error("no HIP device"); return MLD_ERR_NO_DEVICE; }
+    const size_t len = (size_t)n_vec * SOL_NT;
+    DevBuf<double> dv, dmax, dval; DevBuf<int> di, darg;
+    HIP_TRY(dv.alloc(len)); HIP_TRY(di.alloc(len)); HIP_TRY(dmax.alloc(4 * (size_t)n_vec)); HIP_TRY(dval.alloc(2 * (size_t)n_vec)); HIP_TRY(darg.alloc(2 * (size_t)n_vec));
+    HIP_TRY(hipMemcpy(dv, values, sizeof(double) * len, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(di, index, sizeof(int) * len, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_debug_reduce, dim3(n_vec), dim3(SOL_NT), 0, 0, (const double *)dv, (const int *)di, (double *)dmax, (int *)darg, (double *)dval);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out_max, dmax, sizeof(double) * 4 * n_vec, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_arg, darg, sizeof(int) * 2 * n_vec, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_val, dval, sizeof(double) * 2 * n_vec, hipMemcpyDeviceToHost));
+    return MLD_OK;
+}
+
 /* the solver's shape (internal diagnostics; not part of the public header): [0..7] n, m0, mcap, first_cap, ld, mir_cap, lds_bytes, ws_stride;
  * [8..19] the LDS byte offsets (-1: in the slot) lXB, lBasic, lSkip, lAtUp, lNonbasic, lXN, lLo, lHi, lDw, lCost, lMirLine, lMirCache;
  * [20] the LDS budget of the hot arrays, [21] the MLD_SOL_SLOT mask (bit k: SLOT_NAMES[k]), [22] n_slots,

@@ -321,6 +321,8 @@ struct Shared {
 #ifdef MLD_PIVOT_PROF
     long long pprof[8];        // ticks: 0 head (stage, scale, x_B, cost row, book-keeping), 1 sector list, 2 row list, 3 update loop of single pivots; 4 .. 7 the same for pairs
     long long pcnt[8];         // 0 single pivots, 1 pairs, 2 long-step ticks, 3 long-step pivots, 4 groups examined, 5 groups passed, 6 pivots with flips
+    long long sprof[9];        // ticks of the selection (SEL_CLOCK): 0 loop top, 1 pricing scan and its arg-max, 2 row load, pass 1 and emax, 3 pass 2 and tmax, 4 pass 3 and its
+                               // arg-max (plain pivots only); 5 .. 8 the same four parts of the look-ahead (-DMLD_PIVOT_PROF=3: slots 0 .. 4, =4: slots 5 .. 8)
 #endif
     long long prof[8];         // ticks: 0 pivot update, 1 simplex selection, 2 cuts, 3 leaf, 4 set_bounds, 5 residual/refactor, 6 setup
 #ifdef MLD_CUT_PROF
@@ -335,6 +337,14 @@ struct Shared {
 #define CUT_COUNT(sh_, k_, v_) do { if ((threadIdx.x & 63) == 0) atomicAdd((unsigned long long *)&(sh_).cprof[k_], (unsigned long long)(v_)); } while (0)
 #else
 #define CUT_COUNT(sh_, k_, v_) ((void)0)
+#endif
+// sub-clocks of the selection in the diagnostic build -DMLD_PIVOT_PROF (thread 0's clock, as the pivot's): SEL_CLOCK adds the ticks since t_ to slot k_ and restarts t_
+#ifdef MLD_PIVOT_PROF
+#define SEL_CLOCK_START(t_) long long t_ = wall_clock64()
+#define SEL_CLOCK(sh_, k_, t_) do { const long long now_ = wall_clock64(); if (threadIdx.x == 0) (sh_).sprof[k_] += now_ - (t_); (t_) = now_; } while (0)
+#else
+#define SEL_CLOCK_START(t_) ((void)0)
+#define SEL_CLOCK(sh_, k_, t_) ((void)0)
 #endif
 
 __device__ __forceinline__ double block_sum(Shared &sh, double v)
@@ -420,6 +430,99 @@ __device__ __forceinline__ int block_argmax1(Shared &sh, double v, int idx, doub
     }
     *out = bv;
     return bi;
+}
+
+// The same three reductions without the LDS crossbar and without a branch (the selection of s_dual_simplex_impl and s_look_ahead; MLD_DBG_SELECT_R6 keeps the
+// primitives above).  A wave's maximum is six DPP steps on the two halves of the double -- the lane pairs and quad halves of a quad (quad_perm), the two
+// quads of eight lanes (row_half_mirror), the two halves of a row (row_mirror): every lane of a 16-lane row then holds the row's maximum; row_bcast:15 into
+// rows 1 and 3 and row_bcast:31 into rows 2 and 3 leave the wave's maximum in row 3 -- read from lane 63 into scalar registers.  max and min are exact, so
+// the order of the steps does not matter to the bits as long as no operand is NaN and +0.0 / -0.0 do not meet (every caller: see its comment).
+template <int CTRL, int ROWS> __device__ __forceinline__ int dpp_i32(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, ROWS, 0xf, false); }      // (a row outside ROWS keeps its own value)
+template <int CTRL, int ROWS> __device__ __forceinline__ double dpp_f64(double v)
+{
+    const long long b = __double_as_longlong(v);
+    const int lo = dpp_i32<CTRL, ROWS>((int)b), hi = dpp_i32<CTRL, ROWS>((int)(b >> 32));
+    return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned int)lo);
+}
+#define DPP_XOR1 0xB1            // quad_perm:[1,0,3,2]
+#define DPP_XOR2 0x4E            // quad_perm:[2,3,0,1]
+#define DPP_HALF_MIRROR 0x141
+#define DPP_MIRROR 0x140
+#define DPP_BCAST15 0x142
+#define DPP_BCAST31 0x143
+__device__ __forceinline__ double wave_max_dpp(double v)      // the same value on every lane (it is uniform: scalar registers)
+{
+    v = fmax(v, dpp_f64<DPP_XOR1, 0xf>(v));
+    v = fmax(v, dpp_f64<DPP_XOR2, 0xf>(v));
+    v = fmax(v, dpp_f64<DPP_HALF_MIRROR, 0xf>(v));
+    v = fmax(v, dpp_f64<DPP_MIRROR, 0xf>(v));
+    v = fmax(v, dpp_f64<DPP_BCAST15, 0xa>(v));
+    v = fmax(v, dpp_f64<DPP_BCAST31, 0xc>(v));
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_readlane((int)b, 63), hi = __builtin_amdgcn_readlane((int)(b >> 32), 63);
+    return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned int)lo);
+}
+__device__ __forceinline__ int wave_min_i32_dpp(int v)
+{
+    v = min(v, dpp_i32<DPP_XOR1, 0xf>(v));
+    v = min(v, dpp_i32<DPP_XOR2, 0xf>(v));
+    v = min(v, dpp_i32<DPP_HALF_MIRROR, 0xf>(v));
+    v = min(v, dpp_i32<DPP_MIRROR, 0xf>(v));
+    v = min(v, dpp_i32<DPP_BCAST15, 0xa>(v));
+    v = min(v, dpp_i32<DPP_BCAST31, 0xc>(v));
+    return __builtin_amdgcn_readlane(v, 63);
+}
+// One barrier and the alternating buffers of block_max1; the eight partials are read together and combined in registers.
+__device__ __forceinline__ double block_max1_dpp(Shared &sh, double v, int &par)
+{
+    const double m = wave_max_dpp(v);
+    par ^= 1;
+    if ((threadIdx.x & 63) == 0) sh.r2v[par][threadIdx.x >> 6] = m;
+    __syncthreads();
+    double p[SOL_NW];
+#pragma unroll
+    for (int w = 0; w < SOL_NW; ++w) p[w] = sh.r2v[par][w];
+#pragma unroll
+    for (int s = SOL_NW / 2; s > 0; s >>= 1)
+#pragma unroll
+        for (int w = 0; w < s; ++w) p[w] = fmax(p[w], p[w + s]);
+    return p[0];
+}
+__device__ __forceinline__ double block_min1_dpp(Shared &sh, double v, int &par) { return -block_max1_dpp(sh, -v, par); }
+// block_argmax1's rule -- the largest value; among equal values the smallest index >= 0; -1 when no lane with the largest value has an index -- in two
+// reductions: the maximum of the values, then the minimum over the indices >= 0 of the lanes that hold it (0x7fffffff: none).  block_argmax1's comparison is
+// a total order on (value, has an index, -index), so it returns the largest element under that order whatever the order of its steps, and this is that
+// element, provided no value is NaN.  (+0.0 and -0.0 compare equal in both: only *out could differ in its sign; no caller passes a zero.)
+__device__ __forceinline__ int block_argmax1_dpp(Shared &sh, double v, int idx, double *out, int &par)
+{
+    const double m = wave_max_dpp(v);
+    const int k = wave_min_i32_dpp((v == m && idx >= 0) ? idx : 0x7fffffff);
+    par ^= 1;
+    if ((threadIdx.x & 63) == 0) { sh.r2v[par][threadIdx.x >> 6] = m; sh.r2i[par][threadIdx.x >> 6] = k; }
+    __syncthreads();
+    double p[SOL_NW], q[SOL_NW]; int ki[SOL_NW];
+#pragma unroll
+    for (int w = 0; w < SOL_NW; ++w) { p[w] = q[w] = sh.r2v[par][w]; ki[w] = sh.r2i[par][w]; }
+#pragma unroll
+    for (int s = SOL_NW / 2; s > 0; s >>= 1)
+#pragma unroll
+        for (int w = 0; w < s; ++w) q[w] = fmax(q[w], q[w + s]);
+    const double bv = q[0];
+#pragma unroll
+    for (int w = 0; w < SOL_NW; ++w) ki[w] = p[w] == bv ? ki[w] : 0x7fffffff;
+#pragma unroll
+    for (int s = SOL_NW / 2; s > 0; s >>= 1)
+#pragma unroll
+        for (int w = 0; w < s; ++w) ki[w] = min(ki[w], ki[w + s]);
+    *out = bv;
+    return ki[0] == 0x7fffffff ? -1 : ki[0];
+}
+// the primitive the selection uses (r6: MLD_DBG_SELECT_R6, a constant of the instantiation)
+__device__ __forceinline__ double sel_max1(Shared &sh, double v, int &par, bool r6) { return r6 ? block_max1(sh, v, par) : block_max1_dpp(sh, v, par); }
+__device__ __forceinline__ double sel_min1(Shared &sh, double v, int &par, bool r6) { return r6 ? block_min1(sh, v, par) : block_min1_dpp(sh, v, par); }
+__device__ __forceinline__ int sel_argmax1(Shared &sh, double v, int idx, double *out, int &par, bool r6)
+{
+    return r6 ? block_argmax1(sh, v, idx, out, par) : block_argmax1_dpp(sh, v, idx, out, par);
 }
 
 // arg-min over integer keys (smallest key wins); returns payload of the winner or -1
@@ -1590,7 +1693,13 @@ __device__ void s_refactor(const Ws &w, Shared &sh)
 }
 
 // bounded dual simplex with Harris ratio test and Bland fallback; all threads return the same status
-template <bool L> __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double cutoff, int max_pivots);
+template <bool L, bool R6> __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double cutoff, int max_pivots);
+// (R6 = MLD_DBG_SELECT_R6: the loop with its earlier selection is an instantiation of its own, so that neither carries the other's instructions)
+__device__ __forceinline__ int s_dual_simplex_pick(const Ws &w, Shared &sh, double cutoff, int max_pivots)
+{
+    if (w.dbg & MLD_DBG_SELECT_R6) return w.all_lds ? s_dual_simplex_impl<true, true>(w, sh, cutoff, max_pivots) : s_dual_simplex_impl<false, true>(w, sh, cutoff, max_pivots);
+    return w.all_lds ? s_dual_simplex_impl<true, false>(w, sh, cutoff, max_pivots) : s_dual_simplex_impl<false, false>(w, sh, cutoff, max_pivots);
+}
 __device__ int s_dual_simplex(const Ws &w, Shared &sh, double cutoff, int max_pivots)
 {
     const long long t0 = wall_clock64();
@@ -1599,13 +1708,13 @@ __device__ int s_dual_simplex(const Ws &w, Shared &sh, double cutoff, int max_pi
     // ~300 000 bench instances: 29 167 pivots in one root re-solve, 2 s for the whole step): the dictionary is rebuilt from the original rows and
     // the solve gets one more allowance; after that the instance ends with what it has (LP_ITERLIMIT, as at the global pivot limit).
     const int lp_cap = 4 * (w.m0 + w.n) + 1000;
-    int st = w.all_lds ? s_dual_simplex_impl<true>(w, sh, cutoff, min(max_pivots, sh.pivots + lp_cap)) : s_dual_simplex_impl<false>(w, sh, cutoff, min(max_pivots, sh.pivots + lp_cap));
+    int st = s_dual_simplex_pick(w, sh, cutoff, min(max_pivots, sh.pivots + lp_cap));
     __syncthreads();
     if (st == LP_ITERLIMIT && sh.pivots < max_pivots && !(sh.deadline && sh.timed_out)) {      // (not when the TimeLimit ended it: nothing is cycling)
         __syncthreads();
         s_refactor(w, sh);
         __syncthreads();
-        st = w.all_lds ? s_dual_simplex_impl<true>(w, sh, cutoff, min(max_pivots, sh.pivots + lp_cap)) : s_dual_simplex_impl<false>(w, sh, cutoff, min(max_pivots, sh.pivots + lp_cap));
+        st = s_dual_simplex_pick(w, sh, cutoff, min(max_pivots, sh.pivots + lp_cap));
     }
     __syncthreads();
     if (threadIdx.x == 0) sh.prof[1] += (wall_clock64() - t0) - (sh.prof[0] + sh.prof[5] - p0);
@@ -1668,11 +1777,13 @@ __device__ int s_unperturb(const Ws &w, Shared &sh, int st, int max_pivots)
 // r2 == r1.  The raw row goes to w.rowr2 (k <= n), the eligible |a| to w.colc2, the clamped reduced costs to w.dabuf.  True (with r2, c2 and the leaving variable's
 // target) when that iteration is a plain pivot; false when it does anything else (optimal, cut off, no eligible entry, a row to skip): the caller then finishes the
 // first pivot alone and the loop makes that iteration as ever.  Only scratch is written.  Every thread returns the same.
-template <bool L>
+template <bool L, bool R6>
 __device__ __forceinline__ bool s_look_ahead(const Ws &w, Shared &sh, int r1, int c1, double cur, double cutoff, int &par, int &r2, int &c2, double &lv2)
 {
     HOT_VIEW(L, w);
     const int n = w.n, ld = w.ld, m = sh.m, tid = threadIdx.x;
+    constexpr bool r6 = R6;      // the selection as it was (s_dual_simplex_impl)
+    SEL_CLOCK_START(ts);
     double myv = -S_INF; int myi = -1;
     for (int i = tid; i < m; i += SOL_NT) {
         if (h_skip[i]) continue;
@@ -1684,7 +1795,8 @@ __device__ __forceinline__ bool s_look_ahead(const Ws &w, Shared &sh, int r1, in
         }
     }
     double worst;
-    const int r = block_argmax1(sh, myv, myi, &worst, par);
+    const int r = sel_argmax1(sh, myv, myi, &worst, par, r6);      // (a thread without a candidate: -inf against a score > 0)
+    SEL_CLOCK(sh, 5, ts);
     if (r < 0) return false;
     if (cur >= cutoff && !sh.perturbed) return false;
     MLD_CHECK(w, r < m, 105, r, 2);
@@ -1718,15 +1830,19 @@ __device__ __forceinline__ bool s_look_ahead(const Ws &w, Shared &sh, int r1, in
             const int j = h_nonbasic[c];
             MLD_CHECK(w, j >= 0 && j < n + w.mcap, 111, c, j);
             const bool up = h_up[c];
-            const bool el = (h_lo[j] != h_hi[j]) && (below ? (up ? a > 0 : a < 0) : (up ? a < 0 : a > 0));
+            // (a > 0 is wanted when the row is below its bound and the column at its upper one, or neither; a < 0 otherwise: one compare of +-a, no nested branches)
+            const bool el = r6 ? (h_lo[j] != h_hi[j]) && (below ? (up ? a > 0 : a < 0) : (up ? a < 0 : a > 0))
+                               : (bool)((h_lo[j] != h_hi[j]) & ((below == up ? a : -a) > 0.0));
             const double aa = el ? fabs(a) : 0.0;
             const double dv = h_d[c];
+            const double dc = fmax(up ? -dv : dv, 0.0);
             ea[c] = aa;
-            dal[c] = fmax(up ? -dv : dv, 0.0);
+            dal[c] = dc;
             emax = fmax(emax, aa);
         }
     }
-    emax = block_max1(sh, emax, par);
+    emax = sel_max1(sh, emax, par, r6);      // (|a| or +0.0: no -0.0)
+    SEL_CLOCK(sh, 6, ts);
     const double ptol = fmax(S_PIV_ABS, S_PIV_REL * emax);
     double tmax = S_INF;
     for (int c = tid; c < n; c += SOL_NT) {
@@ -1734,7 +1850,8 @@ __device__ __forceinline__ bool s_look_ahead(const Ws &w, Shared &sh, int r1, in
         if (aa <= ptol) continue;
         tmax = fmin(tmax, (dal[c] + S_DTOL) / aa);
     }
-    tmax = block_min1(sh, tmax, par);
+    tmax = sel_min1(sh, tmax, par, r6);      // (the negated ratios are < 0, or -inf)
+    SEL_CLOCK(sh, 7, ts);
     if (tmax == S_INF) return false;
     double bv = -1.0; int bi = -1;
     for (int c = tid; c < n; c += SOL_NT) {
@@ -1743,7 +1860,8 @@ __device__ __forceinline__ bool s_look_ahead(const Ws &w, Shared &sh, int r1, in
         if (dal[c] / aa <= tmax && aa > bv) { bv = aa; bi = c; }
     }
     double tmp;
-    const int cbest = block_argmax1(sh, bv, bi, &tmp, par);
+    const int cbest = sel_argmax1(sh, bv, bi, &tmp, par, r6);      // (a thread without a candidate: -1.0 against |a| > ptol > 0)
+    SEL_CLOCK(sh, 8, ts);
     if (cbest < 0) return false;
     MLD_CHECK(w, cbest < n, 106, cbest, 2);
     if (ea[cbest] < S_PIV_TINY && viol <= S_PTOL_SKIP) return false;
@@ -1758,7 +1876,7 @@ __device__ __forceinline__ bool s_look_ahead(const Ws &w, Shared &sh, int r1, in
 // left pending: on return the dictionary is fully updated.  Whatever the loop would do between the two pivots besides counting a stall -- a limit, the deadline, a
 // verification, the perturbation, Bland's rule -- means no pair: the first pivot is finished alone (s_pivot_update) and the loop goes on unchanged.  cur, stall and
 // last_obj leave as two iterations would leave them.
-template <bool L>
+template <bool L, bool R6>
 __device__ __forceinline__ void s_pivot_pair(const Ws &w, Shared &sh, int r1, int c1, double lv1, bool try_pair, double cutoff, int max_pivots, double &cur,
                                              int &stall, double &last_obj, int &par)
 {
@@ -1783,7 +1901,7 @@ __device__ __forceinline__ void s_pivot_pair(const Ws &w, Shared &sh, int r1, in
             for (int e = 0; e < SOL_SEC; ++e) { const int k = t * SOL_SEC + e; if (k <= n && rowr[k] != 0.0) act = true; }
             secflag[t] = act ? 1 : 0;
         }
-        go = s_look_ahead<L>(w, sh, r1, c1, cur, cutoff, par, r2, c2, lv2);
+        go = s_look_ahead<L, R6>(w, sh, r1, c1, cur, cutoff, par, r2, c2, lv2);
     }
     if (!go) { s_pivot_update(w, sh, r1, c1, tp0); return; }
     stall = stall2; last_obj = last2;
@@ -1904,7 +2022,7 @@ __device__ __forceinline__ void s_pivot_pair(const Ws &w, Shared &sh, int r1, in
     __syncthreads();
 }
 
-template <bool L>
+template <bool L, bool R6>
 __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double cutoff, int max_pivots)
 {
     HOT_VIEW(L, w);
@@ -1917,7 +2035,12 @@ __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double 
     double last_obj = -S_INF, cur = 0.0;
     bool fresh_obj = true;                 // objective is recomputed at entry and after a refactor, tracked incrementally otherwise
     const double *d = w.dcost;
+    // MLD_DBG_SELECT_R6: the selection as it was before its reductions left the LDS crossbar -- wave reductions through __shfl_down with a serial combine of
+    // the waves' partials, the eligibility test of pass 1 as nested branches (DESIGN section 6).  The pricing scan, the loads of pass 1 and passes 2 and 3 of
+    // the ratio test are the same in both.
+    constexpr bool r6 = R6;
     for (;;) {
+        SEL_CLOCK_START(ts);
         __syncthreads();
         if (sh.pivots >= max_pivots) return s_unperturb(w, sh, LP_ITERLIMIT, max_pivots);
         if (sh.deadline && (sh.pivots & 127) == 127) {      // TimeLimit inside one LP (ADVICE r3: a root LP or a leaf of thousands of pivots must not outlast it)
@@ -1948,6 +2071,7 @@ __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double 
         const bool bland = stall > 30;
         // leaving row: dual devex pricing, largest violation^2 / weight (or smallest variable id while stalling)
         double myv = -S_INF; int myi = -1; int myid = 0x7fffffff, myrow = -1;
+        SEL_CLOCK(sh, 0, ts);
         for (int i = tid; i < m; i += SOL_NT) {
             if (h_skip[i]) continue;
             const int j = h_basic[i];
@@ -1960,7 +2084,8 @@ __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double 
             }
         }
         double worst;
-        int r = block_argmax1(sh, myv, myi, &worst, par);
+        int r = sel_argmax1(sh, myv, myi, &worst, par, r6);      // (a thread without a candidate: -inf against a score > 0)
+        SEL_CLOCK(sh, 1, ts);
         if (r < 0) {
 
             if (since >= 64) {
@@ -2018,14 +2143,17 @@ __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double 
                 MLD_CHECK(w, j >= 0 && j < n + w.mcap, 111, c, j);
                 const double a = av[q];
                 const bool up = h_up[c];
-                const bool el = (h_lo[j] != h_hi[j]) && (below ? (up ? a > 0 : a < 0) : (up ? a < 0 : a > 0));
+                // (a > 0 is wanted when the row is below its bound and the column at its upper one, or neither; a < 0 otherwise: one compare of +-a, no nested branches)
+                const bool el = r6 ? (h_lo[j] != h_hi[j]) && (below ? (up ? a > 0 : a < 0) : (up ? a < 0 : a > 0))
+                                   : (bool)((h_lo[j] != h_hi[j]) & ((below == up ? a : -a) > 0.0));
                 const double aa = el ? fabs(a) : 0.0;
                 ea[c] = aa;
                 dal[c] = fmax(up ? -dv[q] : dv[q], 0.0);
                 emax = fmax(emax, aa);
             }
         }
-        emax = block_max1(sh, emax, par);
+        emax = sel_max1(sh, emax, par, r6);      // (|a| or +0.0: no -0.0)
+        SEL_CLOCK(sh, 2, ts);
         const double ptol = fmax(S_PIV_ABS, S_PIV_REL * emax);
         // Harris bound on the step (tmax) and the exact minimum ratio (rmin)
         double tmax = S_INF, rmin = S_INF;
@@ -2033,9 +2161,10 @@ __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double 
             const double aa = ea[c];
             if (aa <= ptol) continue;
             tmax = fmin(tmax, (dal[c] + S_DTOL) / aa);
-            rmin = fmin(rmin, dal[c] / aa);
+            if (r6 || bland) rmin = fmin(rmin, dal[c] / aa);      // (read under Bland's rule only)
         }
-        tmax = block_min1(sh, tmax, par);
+        tmax = sel_min1(sh, tmax, par, r6);      // (the negated ratios are < 0, or -inf)
+        SEL_CLOCK(sh, 3, ts);
         if (tmax == S_INF) {
             if (viol <= S_PTOL_SKIP) { __syncthreads(); if (tid == 0) h_skip[r] |= 1; continue; }
             if (since > 0 && viol <= 1e-3) {
@@ -2097,7 +2226,7 @@ __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double 
                     if (aa > bv) { bv = aa; bi = c; }
                 }
                 drop = block_sum(sh, drop);
-                cbest = block_argmax1(sh, bv, bi, &a_best, par);
+                cbest = sel_argmax1(sh, bv, bi, &a_best, par, r6);      // (a thread without a candidate: -1.0 against |a| > ptol > 0)
                 if (!(slope - drop > S_PTOL)) break;              // this group holds the entering variable
                 slope -= drop;
                 __syncthreads();
@@ -2112,7 +2241,7 @@ __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double 
                 nflip_groups++;
                 double t2 = S_INF;
                 for (int c = tid; c < n; c += SOL_NT) { const double aa = ea[c]; if (aa > ptol) t2 = fmin(t2, (dal[c] + S_DTOL) / aa); }
-                tm = block_min1(sh, t2, par);
+                tm = sel_min1(sh, t2, par, r6);                   // (the negated ratios are < 0, or -inf)
                 if (tm == S_INF) break;                           // every breakpoint passed: the last group's largest entry enters after all
             }
             if (cbest >= 0 && nflip_groups > 0) {
@@ -2177,7 +2306,8 @@ __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double 
                 if (dal[c] / aa <= tmax && aa > bv) { bv = aa; bi = c; }
             }
             double tmp;
-            cbest = block_argmax1(sh, bv, bi, &tmp, par);
+            cbest = sel_argmax1(sh, bv, bi, &tmp, par, r6);      // (a thread without a candidate: -1.0 against |a| > ptol > 0)
+            SEL_CLOCK(sh, 4, ts);
         }
         if (cbest < 0) return s_unperturb(w, sh, LP_INFEASIBLE, max_pivots);   // cannot happen (tmax finite), kept as a guard
         MLD_CHECK(w, cbest < n, 106, cbest, 0);
@@ -2189,7 +2319,7 @@ __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double 
         }
         // the pivot, and the next one with it where both are plain (devex pricing and Harris test: not under Bland's rule, not in the root LP's long-step test, not with
         // a quadratic cost) and the shape has the LDS for it
-        s_pivot_pair<L>(w, sh, r, cbest, below ? h_lo[jr] : h_hi[jr], L && w.pair && !bland && !long_step && !w.P, cutoff, max_pivots, cur, stall, last_obj, par);
+        s_pivot_pair<L, R6>(w, sh, r, cbest, below ? h_lo[jr] : h_hi[jr], L && w.pair && !bland && !long_step && !w.P, cutoff, max_pivots, cur, stall, last_obj, par);
     }
 }
 
@@ -4029,6 +4159,7 @@ __device__ __forceinline__ bool s_setup_entry(Ws &w, Shared &sh, const SolverSha
         sh.deadline = 0; sh.timed_out = 0;      // (armed when the search starts: the root LP always runs to its end -- without it there is no answer at all)
 #ifdef MLD_PIVOT_PROF
         for (int k = 0; k < 8; ++k) sh.pprof[k] = sh.pcnt[k] = 0;
+        for (int k = 0; k < 9; ++k) sh.sprof[k] = 0;
 #endif
 #ifdef MLD_CUT_PROF
         for (int k = 0; k < 15; ++k) sh.cprof[k] = 0;
@@ -4558,7 +4689,10 @@ __device__ __forceinline__ void s_write_results(Shared &sh, const BatchDev &B, c
         B.ticks_out[inst] = skipped ? 0 : wall_clock64() - e.t_begin; B.rows_out[inst] = skipped ? 0 : (long long)sh.rows;
 #ifdef MLD_PIVOT_PROF
         // (-DMLD_PIVOT_PROF: the clocks of the pivot's sub-phases; -DMLD_PIVOT_PROF=2: the counts and the long-step clock of the same launch instead -- scripts/gpu_pivot_prof.py)
-        if (B.prof_out && !skipped) for (int k = 0; k < 8; ++k) B.prof_out[(size_t)inst * 8 + k] = MLD_PIVOT_PROF == 2 ? sh.pcnt[k] : sh.pprof[k];
+        // (-DMLD_PIVOT_PROF=3 / =4: the selection's sub-clocks of the loop / of the look-ahead in slots 0 .. 4 / 0 .. 3, the selection clock itself in slot 7)
+        if (B.prof_out && !skipped) for (int k = 0; k < 8; ++k)
+            B.prof_out[(size_t)inst * 8 + k] = MLD_PIVOT_PROF == 2 ? sh.pcnt[k] : MLD_PIVOT_PROF == 3 ? (k < 5 ? sh.sprof[k] : k == 7 ? sh.prof[1] : 0)
+                                             : MLD_PIVOT_PROF == 4 ? (k < 4 ? sh.sprof[5 + k] : k == 7 ? sh.prof[1] : 0) : sh.pprof[k];
 #else
         if (B.prof_out && !skipped) for (int k = 0; k < 8; ++k) B.prof_out[(size_t)inst * 8 + k] = sh.prof[k];
 #endif
@@ -4624,5 +4758,25 @@ __global__ void __launch_bounds__(SOL_NT, SOL_WPE) k_solve(SolverShape S, Proble
             MLD_MARK(w, sh, 999);
         }
         s_write_results(sh, B, e, s);
+    }
+}
+
+// Diagnostics (mld_debug_reduce): the block reductions of the selection on caller-supplied vectors of SOL_NT (value, index) lanes, a workgroup per vector -- the
+// primitives over __shfl_down (slot 0) and the DPP ones that replaced them in the simplex loop (slot 1): max2[2 b + s] the block maximum, arg2 / val2 the arg-max
+// and its value.  Three reductions each, alternating buffers as in the loop.
+__global__ void __launch_bounds__(SOL_NT) k_debug_reduce(const double *v, const int *idx, double *max2, int *arg2, double *val2)
+{
+    __shared__ Shared sh;
+    const size_t b = blockIdx.x;
+    const double x = v[b * SOL_NT + threadIdx.x];
+    const int i = idx[b * SOL_NT + threadIdx.x];
+    int par = 0;
+    double o0, o1;
+    const double m0 = block_max1(sh, x, par), m1 = block_max1_dpp(sh, x, par);
+    const int a0 = block_argmax1(sh, x, i, &o0, par), a1 = block_argmax1_dpp(sh, x, i, &o1, par);
+    const double n0 = block_min1(sh, x, par), n1 = block_min1_dpp(sh, x, par);
+    if (threadIdx.x == (blockIdx.x & (SOL_NT - 1))) {      // (every thread holds the results: another thread reports for every vector)
+        max2[2 * b] = m0; max2[2 * b + 1] = m1; arg2[2 * b] = a0; arg2[2 * b + 1] = a1; val2[2 * b] = o0; val2[2 * b + 1] = o1;
+        max2[2 * gridDim.x + 2 * b] = n0; max2[2 * gridDim.x + 2 * b + 1] = n1;
     }
 }
