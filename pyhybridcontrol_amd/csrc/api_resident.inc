@@ -169,10 +169,8 @@ int mld_upload_instance_cost(mld_problem_t *p, const double *lin_v, const double
         const PbMaps mp = pullback_maps(p);
         if (p->opts.reserved & MLD_DBG_GEMM_VALU)
             hipLaunchKernelGGL(k_inst_pullback_valu, dim3(batch), dim3(256), sizeof(double) * K, sq, NX, NY, n, nx, nW, mp, p->has_midx ? p->bat.model_idx.get() : nullptr, d_w.get(), ic.get());
-        else if (p->opts.flags & MLD_F32)
-            hipLaunchKernelGGL(k_inst_pullback<true>, dim3(p->n_groups), dim3(64 * RM_WAVES), 0, sq, NX, NY, n, nx, nW, mp, p->bat.groups.get(), p->bat.perm.get(), d_w.get(), ic.get());
         else
-            hipLaunchKernelGGL(k_inst_pullback<false>, dim3(p->n_groups), dim3(64 * RM_WAVES), 0, sq, NX, NY, n, nx, nW, mp, p->bat.groups.get(), p->bat.perm.get(), d_w.get(), ic.get());
+            LAUNCH_INST_GEMM(k_inst_pullback, p->opts.flags & MLD_F32, p->n_groups, 0, sq, NX, NY, n, nx, nW, mp, p->bat.groups.get(), p->bat.perm.get(), d_w.get(), ic.get());
         HIP_TRY(hipGetLastError());
     }
     return MLD_OK;
@@ -239,12 +237,9 @@ int mld_predict_batch(mld_problem_t *p, const double *v, double *x_out, double *
         if (p->opts.reserved & MLD_DBG_GEMM_VALU)
             hipLaunchKernelGGL(k_trajectory_valu, dim3(batch), dim3(256), sizeof(double) * (n + nx + nW + 1), sq, NX, NY, n, nx, nW, mp,
                                p->has_midx ? p->bat.model_idx.get() : nullptr, pv, p->bat.x0.get(), p->bat.omega.get(), st, ob, r_begin, r_end, d_x.get(), d_y.get());
-        else if (p->opts.flags & MLD_F32)
-            hipLaunchKernelGGL(k_trajectory<true>, dim3(p->n_groups), dim3(64 * RM_WAVES), 0, sq, N, d.nx, d.ny, p->nv, d.nomega, mp, p->bat.groups.get(), p->bat.perm.get(),
-                               pv, p->bat.x0.get(), p->bat.omega.get(), st, ob, r_begin, r_end, d_x.get(), d_y.get());
         else
-            hipLaunchKernelGGL(k_trajectory<false>, dim3(p->n_groups), dim3(64 * RM_WAVES), 0, sq, N, d.nx, d.ny, p->nv, d.nomega, mp, p->bat.groups.get(), p->bat.perm.get(),
-                               pv, p->bat.x0.get(), p->bat.omega.get(), st, ob, r_begin, r_end, d_x.get(), d_y.get());
+            LAUNCH_INST_GEMM(k_trajectory, p->opts.flags & MLD_F32, p->n_groups, 0, sq, N, d.nx, d.ny, p->nv, d.nomega, mp, p->bat.groups.get(), p->bat.perm.get(),
+                             pv, p->bat.x0.get(), p->bat.omega.get(), st, ob, r_begin, r_end, d_x.get(), d_y.get());
         HIP_TRY(hipGetLastError());
         if (x_out) HIP_TRY(hipMemcpyAsync(x_out, d_x, sizeof(double) * (size_t)batch * NX, hipMemcpyDeviceToHost, sq));
         if (y_out) HIP_TRY(hipMemcpyAsync(y_out, d_y, sizeof(double) * (size_t)batch * NY, hipMemcpyDeviceToHost, sq));
@@ -299,7 +294,7 @@ static int evaluate_impl(mld_problem_t *p, const char *who, const double *v, int
     if (v) HIP_TRY(d_v.alloc((size_t)batch * std::max(1, n)));
     if (want_c) {
         HIP_TRY(d_hv.alloc((size_t)batch * std::max(1, m0)));
-        if (!valu && nx + nW > EV_KC) HIP_TRY(d_part.alloc((size_t)batch * std::max(1, m0)));
+        if (!valu && nx + nW > IG_KC) HIP_TRY(d_part.alloc((size_t)batch * std::max(1, m0)));
         HIP_TRY(d_vio.alloc((size_t)batch * nout)); HIP_TRY(d_row.alloc((size_t)batch * nout));
         if (slice && nW) HIP_TRY(d_om.alloc((size_t)batch * slice * nW));
         if (slice && x_cols) HIP_TRY(d_xc.alloc((size_t)batch * slice * nx));

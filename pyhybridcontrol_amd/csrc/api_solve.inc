@@ -23,13 +23,16 @@ static void build_rhs_groups(const int32_t *model_idx, int batch, int n_models, 
 
 static bool rhs_mfma_fits(int nx, int nW) { return ((nx + nW + 3) & ~3) <= RM_KMAX; }
 
+/* launch of a member of the instance-GEMM family (mfma.inc): kern<F32>, a workgroup per RhsGroup */
+#define LAUNCH_INST_GEMM(kern, f32, n_groups, lds, stream, ...) do {                                                             \
+    if (f32) hipLaunchKernelGGL(kern<true>, dim3(n_groups), dim3(64 * RM_WAVES), lds, stream, __VA_ARGS__);                      \
+    else hipLaunchKernelGGL(kern<false>, dim3(n_groups), dim3(64 * RM_WAVES), lds, stream, __VA_ARGS__); } while (0)
 static void launch_rhs_mfma(bool f32, int n_groups, int m0, int nx, int nW, const double *Hx, const double *Hw, const double *H5, const double *rs,
                             const RhsGroup *groups, const int *perm, const double *x0, const double *omega, double *hs, hipStream_t stream = 0)
 {
     const int Kp = (nx + nW + 3) & ~3;
     const size_t lds = sizeof(double) * 16 * (size_t)(Kp + 1);
-    if (f32) hipLaunchKernelGGL(k_rhs_mfma<true>, dim3(n_groups), dim3(64 * RM_WAVES), lds, stream, m0, nx, nW, Kp, Hx, Hw, H5, rs, groups, perm, x0, omega, hs);
-    else hipLaunchKernelGGL(k_rhs_mfma<false>, dim3(n_groups), dim3(64 * RM_WAVES), lds, stream, m0, nx, nW, Kp, Hx, Hw, H5, rs, groups, perm, x0, omega, hs);
+    LAUNCH_INST_GEMM(k_rhs_mfma, f32, n_groups, lds, stream, m0, nx, nW, Kp, Hx, Hw, H5, rs, groups, perm, x0, omega, hs);
 }
 
 /* a batch laid out on the handle: buffers, model_idx, RHS groups, fixings -- everything of mld_upload_batch but the inputs themselves, which the caller of

@@ -2,17 +2,16 @@
 // BoundVio; controllers/controller_base.py:509) for any plans, against the ORIGINAL condensed rows and any set of disturbance columns
 // (the column layout of gen_evo_constraints, controller_base.py:411-456).  The residual of row i of instance b under column c is
 //     r_i = (H_v v_b)_i - (H_x x_c + H_omega omega_c + H_5)_i                       unscaled; negative = slack
-// and the kernel keeps max_i r_i and a row that attains it.  One more member of the K3 / k_inst_pullback / k_trajectory family (mfma.inc, whose lane
-// maps and RhsGroup it uses): a workgroup owns up to RM_NI instances of one model, their inputs are MFMA A fragments (instances along M), 16
-// constraint rows at a time are staged coalesced into an LDS tile of odd stride as the B operand.  Always fp64 (a certificate in fp32 certifies
-// nothing), also on a handle created with MLD_F32.
+// and the kernel keeps max_i r_i and a row that attains it.  A member of the instance-GEMM family (mfma.inc), with row tiles (ig_stage).  What it
+// adds: two products in one launch, the causal skip below, and an epilogue that keeps a running (max, row) instead of storing residuals.  Always
+// fp64 (a certificate in fp32 certifies nothing), also on a handle created with MLD_F32.
 //
-// Two passes in ONE launch, both with the inner dimension in chunks of EV_KC whose A fragments live in registers:
+// Two passes in ONE launch, both with the inner dimension in chunks of IG_KC whose A fragments live in registers:
 //   pass V   hv[b, i] = (H_v v_b)_i, chunk by chunk over n (cfg4: 575 = 3 chunks) -- the part every column shares, computed once.  Like k_trajectory
 //            the accumulator is global memory, written by the first chunk and read and written by the same lane in every later one.
 //   pass C   per column c: (H_x x_c + H_omega omega_c)_i, normally ONE chunk (cfg4: 207), so the residual hv - that - H_5 is complete in the lane
 //            that holds the product: the epilogue stores nothing per row, it keeps a running (max, row) for the lane's four instances, which is
-//            reduced across the 16 lanes that share an instance and written once per (instance, column).  Where nx + N nw > EV_KC the partial
+//            reduced across the 16 lanes that share an instance and written once per (instance, column).  Where nx + N nw > IG_KC the partial
 //            products go through `part` (same lane reads what it wrote) and the last chunk reduces.
 // The lane that owns (instance, row) is the same in both passes, so no synchronisation is needed between them.
 //
@@ -20,10 +19,6 @@
 // tests/test_quality_host.py pins this on the condensed maps, time-varying horizons included).  A 16-row block whose last step is i reads the
 // v / omega columns of steps j <= i only.  Groups of four inner indices are staged and multiplied whole: a group that straddles reads stored zeros.
 #pragma once
-
-#define EV_KC 256
-#define EV_KS (EV_KC / 4)
-#define EV_LD (EV_KC + 1)
 
 struct EvCols {                      // the disturbance columns of one launch
     int n_cols;                      // columns of omc (after the standard one)
@@ -36,13 +31,6 @@ struct EvCols {                      // the disturbance columns of one launch
     const double *xc;                // batch x n_cols x nx, or null = x0
     const int *rows;                 // n_cols leading rows each column applies to, or null = all
 };
-
-__device__ __forceinline__ unsigned long long ev_bits(int lo, int hi)
-{
-    lo = max(lo, 0); hi = min(hi, EV_KS);
-    if (hi <= lo) return 0ull;
-    return (hi - lo == 64 ? ~0ull : (1ull << (hi - lo)) - 1ull) << lo;
-}
 
 // (max, row) of the 16 lanes that share an instance (li = lane & 15), then one store by li == 0; dead instances get NaN / -1
 __device__ __forceinline__ void ev_write(double (&best)[4], int (&brow)[4], const int (&oinst)[4], const bool (&dead)[4], int li, size_t ld, int col,
@@ -64,58 +52,37 @@ __device__ __forceinline__ void ev_write(double (&best)[4], int (&brow)[4], cons
 }
 
 // Hv, Hx, Hw, H5: the original model's condensed rows (n_models x m0 x n / nx / nW / 1; Hx, Hw null when empty).  hv: batch x m0 scratch (pass V's
-// result, kept between the launches of one call: do_v = 0 reuses it); part: batch x m0 scratch, needed only when nx + nW > EV_KC.
+// result, kept between the launches of one call: do_v = 0 reuses it); part: batch x m0 scratch, needed only when nx + nW > IG_KC.
 __global__ void __launch_bounds__(64 * RM_WAVES) k_evaluate(int m0, int nc, int nv, int nw, int n, int nx, int nW, const double *Hv, const double *Hx,
                                                             const double *Hw, const double *H5, const RhsGroup *groups, const int *perm, const double *v,
                                                             const int *status, const double *obj, int do_v, EvCols cols, double *hv, double *part,
                                                             double *vio, int *row_out)
 {
-    __shared__ double ev_tile[16 * EV_LD];
+    __shared__ double ev_tile[16 * IG_LD];
     const RhsGroup g = groups[blockIdx.x];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lk = lane >> 4;
-    static_assert(EV_KS == 64, "a chunk's groups of four are one 64-bit mask");
-    const int slot = wave * 16 + li;
-    const int inst = slot < g.count ? (perm ? perm[g.start + slot] : g.start + slot) : -1;
     int oinst[4]; bool dead[4];
+    const int inst = ig_slots<false>(g, perm, wave, li, lk, oinst);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int oi = wave * 16 + lk + 4 * r;
-        oinst[r] = oi < g.count ? (perm ? perm[g.start + oi] : g.start + oi) : -1;
-        dead[r] = status && oinst[r] >= 0 && !plan_usable(status, obj, oinst[r]);
-    }
+    for (int r = 0; r < 4; ++r) dead[r] = status && oinst[r] >= 0 && !plan_usable(status, obj, oinst[r]);
     const double *hvm = Hv ? Hv + (size_t)g.model * m0 * n : nullptr;
     const double *hxm = Hx ? Hx + (size_t)g.model * m0 * nx : nullptr, *hwm = Hw ? Hw + (size_t)g.model * m0 * nW : nullptr;
     const double *h5m = H5 + (size_t)g.model * m0;
-    double a64[EV_KS];
+    IgFrag<false, IG_KS> a;
 
     // ---- pass V: hv = H_v v ------------------------------------------------------------------------------------------------------------
-    if (do_v) for (int kc0 = 0; kc0 < n || kc0 == 0; kc0 += EV_KC) {
-        const int ks = (min(EV_KC, n - kc0) + 3) >> 2, g0 = kc0 >> 2;
-#pragma unroll
-        for (int s = 0; s < EV_KS; ++s) {
-            const int k = kc0 + 4 * s + lk;
-            a64[s] = (s < ks && inst >= 0 && k < n) ? v[(size_t)inst * n + k] : 0.0;
-        }
+    if (do_v) for (int kc0 = 0; kc0 < n || kc0 == 0; kc0 += IG_KC) {
+        const int ks = (min(IG_KC, n - kc0) + 3) >> 2, g0 = kc0 >> 2;
+        ig_load_a(a, inst, kc0, lk, ks, n, [=](int k) { return v[(size_t)inst * n + k]; });
         for (int rb = 0; rb < m0; rb += 16) {
             const int imax = min(rb + 15, m0 - 1) / nc;                          // the last step among the rows of this block
-            const unsigned long long need = hvm ? ev_bits(-g0, ((min(n, (imax + 1) * nv) + 3) >> 2) - g0) & ev_bits(0, ks) : 0ull;
+            const unsigned long long need = hvm ? ig_bits(-g0, ((min(n, (imax + 1) * nv) + 3) >> 2) - g0) & ig_bits(0, ks) : 0ull;
             if (!need && kc0 > 0) continue;                                      // nothing of this chunk reaches these rows (uniform over the workgroup)
-            rm_f64x4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+            double res[4] = {0.0, 0.0, 0.0, 0.0};
             if (need) {
-                __syncthreads();
-                for (int e = tid; e < 16 * EV_KC; e += 64 * RM_WAVES) {
-                    const int i = e / EV_KC, kk = e % EV_KC, row = rb + i, k = kc0 + kk;
-                    if (!(need >> (kk >> 2) & 1ull)) continue;
-                    ev_tile[i * EV_LD + kk] = (row < m0 && k < n) ? hvm[(size_t)row * n + k] : 0.0;
-                }
-                __syncthreads();
-                const double *brow = ev_tile + li * EV_LD + lk;                  // B[k = 4 s + lk][j = li] = H_v[rb + li][kc0 + k]
-#pragma unroll
-                for (int s = 0; s < EV_KS; s += 2) {
-                    if (need >> s & 1ull) acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a64[s], brow[4 * s], acc0, 0, 0, 0);
-                    if (need >> (s + 1) & 1ull) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a64[s + 1], brow[4 * (s + 1)], acc1, 0, 0, 0);
-                }
+                ig_stage(ev_tile, tid, rb, kc0, need, [=](int row, int k) { return row < m0 && k < n ? hvm[(size_t)row * n + k] : 0.0; });
+                ig_mma<4>(a, ev_tile + li * IG_LD + lk, IgMask{need}, res);               // B = H_v[rb + li][kc0 + k]
             }
             const int row = rb + li;
             if (row < m0) {
@@ -123,7 +90,7 @@ __global__ void __launch_bounds__(64 * RM_WAVES) k_evaluate(int m0, int nc, int 
                 for (int r = 0; r < 4; ++r) {
                     if (oinst[r] < 0) continue;
                     double *dst = hv + (size_t)oinst[r] * m0 + row;
-                    *dst = kc0 ? *dst + (acc0[r] + acc1[r]) : acc0[r] + acc1[r];
+                    *dst = kc0 ? *dst + res[r] : res[r];
                 }
             }
         }
@@ -146,40 +113,24 @@ __global__ void __launch_bounds__(64 * RM_WAVES) k_evaluate(int m0, int nc, int 
 #pragma unroll
             for (int r = 0; r < 4; ++r) { best[r] = ninf; brow_[r] = -1; }
         }
-        for (int kc0 = 0; (kc0 < K2 || kc0 == 0) && rows_c > 0; kc0 += EV_KC) {
-            const int ks = (min(EV_KC, K2 - kc0) + 3) >> 2, g0 = kc0 >> 2;
-            const bool last = kc0 + EV_KC >= K2;
-#pragma unroll
-            for (int s = 0; s < EV_KS; ++s) {
-                const int k = kc0 + 4 * s + lk;
-                double a = 0.0;
-                if (s < ks && inst >= 0 && k < K2) a = k < nx ? xs[k] : ws[k - nx];
-                a64[s] = a;
-            }
+        for (int kc0 = 0; (kc0 < K2 || kc0 == 0) && rows_c > 0; kc0 += IG_KC) {
+            const int ks = (min(IG_KC, K2 - kc0) + 3) >> 2, g0 = kc0 >> 2;
+            const bool last = kc0 + IG_KC >= K2;
+            ig_load_a(a, inst, kc0, lk, ks, K2, [=](int k) { return k < nx ? xs[k] : ws[k - nx]; });
             for (int rb = 0; rb < rows_c; rb += 16) {
                 const int imax = min(rb + 15, m0 - 1) / nc;
                 // (global groups [0, nx / 4 rounded up) of x -- H_x is dense -- and up to the last causal column of omega; a group that holds both is taken whole)
                 unsigned long long need = 0ull;
-                if (hxm) need |= ev_bits(-g0, ((nx + 3) >> 2) - g0);
-                if (hwm) need |= ev_bits((nx >> 2) - g0, ((nx + min(nW, (imax + 1) * nw) + 3) >> 2) - g0);
-                need &= ev_bits(0, ks);
-                rm_f64x4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+                if (hxm) need |= ig_bits(-g0, ((nx + 3) >> 2) - g0);
+                if (hwm) need |= ig_bits((nx >> 2) - g0, ((nx + min(nW, (imax + 1) * nw) + 3) >> 2) - g0);
+                need &= ig_bits(0, ks);
+                double prod[4] = {0.0, 0.0, 0.0, 0.0};
                 if (need) {
-                    __syncthreads();
-                    for (int e = tid; e < 16 * EV_KC; e += 64 * RM_WAVES) {
-                        const int i = e / EV_KC, kk = e % EV_KC, row = rb + i, k = kc0 + kk;
-                        if (!(need >> (kk >> 2) & 1ull)) continue;
-                        double val = 0.0;
-                        if (row < m0 && k < K2) val = k < nx ? (hxm ? hxm[(size_t)row * nx + k] : 0.0) : (hwm ? hwm[(size_t)row * nW + (k - nx)] : 0.0);
-                        ev_tile[i * EV_LD + kk] = val;
-                    }
-                    __syncthreads();
-                    const double *brow = ev_tile + li * EV_LD + lk;
-#pragma unroll
-                    for (int s = 0; s < EV_KS; s += 2) {
-                        if (need >> s & 1ull) acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a64[s], brow[4 * s], acc0, 0, 0, 0);
-                        if (need >> (s + 1) & 1ull) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a64[s + 1], brow[4 * (s + 1)], acc1, 0, 0, 0);
-                    }
+                    ig_stage(ev_tile, tid, rb, kc0, need, [=](int row, int k) {
+                        if (row >= m0 || k >= K2) return 0.0;
+                        return k < nx ? (hxm ? hxm[(size_t)row * nx + k] : 0.0) : (hwm ? hwm[(size_t)row * nW + (k - nx)] : 0.0);
+                    });
+                    ig_mma<4>(a, ev_tile + li * IG_LD + lk, IgMask{need}, prod);
                 }
                 const int row = rb + li;
                 if (row < rows_c) {
@@ -188,7 +139,7 @@ __global__ void __launch_bounds__(64 * RM_WAVES) k_evaluate(int m0, int nc, int 
                     for (int r = 0; r < 4; ++r) {
                         if (oinst[r] < 0) continue;
                         const size_t at = (size_t)oinst[r] * m0 + row;
-                        double rhs = acc0[r] + acc1[r];
+                        double rhs = prod[r];
                         if (kc0) rhs += part[at];
                         if (!last) { part[at] = rhs; continue; }
                         const double res = hv[at] - rhs - c5;

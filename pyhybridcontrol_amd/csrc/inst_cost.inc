@@ -2,15 +2,11 @@
 // the condensed maps (controllers/components/variables.py:259-275; the reference rebuilds its objective per solve() call,
 // micro_grid_control_simulation.py:194-198,229) as ONE GEMM per model
 //     out[b, :] += [lin_x_b | lin_y_b] [W ; Y],   W = [Gamma_v | Phi_x | Gamma_w | Gamma_5],  Y = [L_v | L_x | L_w | L_5]
-// with the instances along M and the n + nx + N nw + 1 output columns along N.  Mirrors k_rhs_mfma (mfma.inc, whose lane maps
-// and RhsGroup it uses): a workgroup owns up to RM_NI instances of one model and holds their weights as MFMA A fragments; the
-// maps are stored (rows x cols) row-major, so a block of 16 output columns is staged as 128-byte row segments into an LDS tile
-// [k][16] (B[k = 4 s + lk][j = li] is then a conflict-free 64-double sweep per MFMA).  Inner dimensions above PB_KC go in
-// chunks: `out` (pre-loaded with lin_v, or zero) is the accumulator, read and written by the same lane in every chunk.
+// with the instances along M and the n + nx + N nw + 1 output columns along N.  A member of the instance-GEMM family (mfma.inc).
+// What it adds: the maps are stored (rows x cols) row-major and the output columns are their columns, so a block of 16 output
+// columns is staged as 128-byte row segments into an LDS tile [k][16] (B[k = 4 s + lk][j = li] is then a conflict-free 64-double
+// sweep per MFMA); and `out` (pre-loaded with lin_v, or zero) is the accumulator, read and written by the same lane in every chunk.
 #pragma once
-
-#define PB_KC 256                    // inner-dimension chunk whose A fragments live in registers
-#define PB_KS (PB_KC / 4)
 
 struct PbMaps {                      // per family [v, x, w, 5]: device pointer (null = zeros) and per-model stride
     const double *W[4], *Y[4];
@@ -30,30 +26,17 @@ template <bool F32>
 __global__ void __launch_bounds__(64 * RM_WAVES) k_inst_pullback(int NX, int NY, int n, int nx, int nW, PbMaps mp, const RhsGroup *groups,
                                                                  const int *perm, const double *wts, double *out)
 {
-    __shared__ double pb_tile[PB_KC * 16];
+    __shared__ double pb_tile[IG_KC * 16];
     const RhsGroup g = groups[blockIdx.x];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lk = lane >> 4;
     const int K = NX + NY, ncol = n + nx + nW + 1;
-    const int slot = wave * 16 + li;
-    const int inst = slot < g.count ? (perm ? perm[g.start + slot] : g.start + slot) : -1;
     int oinst[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int oi = wave * 16 + (F32 ? 4 * lk + r : lk + 4 * r);
-        oinst[r] = oi < g.count ? (perm ? perm[g.start + oi] : g.start + oi) : -1;
-    }
-    for (int kc0 = 0; kc0 < K; kc0 += PB_KC) {
-        const int ks = (min(PB_KC, K - kc0) + 3) >> 2;
-        // A fragments of this chunk: instance (wave, li) x k = kc0 + 4 s + lk
-        double a64[F32 ? 1 : PB_KS]; float a32[F32 ? PB_KS : 1];
-#pragma unroll
-        for (int s = 0; s < PB_KS; ++s) {
-            double v = 0.0;
-            const int k = kc0 + 4 * s + lk;
-            if (s < ks && inst >= 0 && k < K) v = wts[(size_t)inst * K + k];
-            if (F32) a32[s] = (float)v; else a64[s] = v;
-        }
+    const int inst = ig_slots<F32>(g, perm, wave, li, lk, oinst);
+    for (int kc0 = 0; kc0 < K; kc0 += IG_KC) {
+        const int ks = (min(IG_KC, K - kc0) + 3) >> 2;
+        IgFrag<F32, IG_KS> a;
+        ig_load_a(a, inst, kc0, lk, ks, K, [=](int k) { return wts[(size_t)inst * K + k]; });
         for (int cb = 0; cb < ncol; cb += 16) {
             __syncthreads();
             {   // stage rows kc0 .. kc0 + 4 ks of output columns cb .. cb + 15 (a thread keeps its column: 512 = 0 mod 16)
@@ -71,30 +54,12 @@ __global__ void __launch_bounds__(64 * RM_WAVES) k_inst_pullback(int NX, int NY,
                 }
             }
             __syncthreads();
-            const double *brow = pb_tile + lk * 16 + li;          // B[k = 4 s + lk][j = li]
             const int c = cb + li;
-            if (F32) {
-                rm_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+            double res[4];
+            ig_mma<64>(a, pb_tile + lk * 16 + li, IgMask{ig_bits(0, ks)}, res);          // B[k = 4 s + lk][j = li]
+            if (c < ncol) {
 #pragma unroll
-                for (int s = 0; s < PB_KS; s += 2) {
-                    if (s < ks) acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a32[s], (float)brow[64 * s], acc0, 0, 0, 0);
-                    if (s + 1 < ks) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a32[s + 1], (float)brow[64 * (s + 1)], acc1, 0, 0, 0);
-                }
-                if (c < ncol) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) if (oinst[r] >= 0) out[(size_t)oinst[r] * ncol + c] += (double)(acc0[r] + acc1[r]);
-                }
-            } else {
-                rm_f64x4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int s = 0; s < PB_KS; s += 2) {
-                    if (s < ks) acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a64[s], brow[64 * s], acc0, 0, 0, 0);
-                    if (s + 1 < ks) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a64[s + 1], brow[64 * (s + 1)], acc1, 0, 0, 0);
-                }
-                if (c < ncol) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) if (oinst[r] >= 0) out[(size_t)oinst[r] * ncol + c] += acc0[r] + acc1[r];
-                }
+                for (int r = 0; r < 4; ++r) if (oinst[r] >= 0) out[(size_t)oinst[r] * ncol + c] += res[r];
             }
         }
     }

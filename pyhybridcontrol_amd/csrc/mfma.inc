@@ -1,24 +1,114 @@
-// K3 on the matrix cores: the constraint right-hand sides of a whole batch as ONE batched GEMM per model
-//     hs[b, :] = rs .* ([H_x | H_w] [x0_b ; w_b] + H_5)          (controllers/controller_base.py:446-450)
-// with the batch as the N dimension (SURVEY section 2, kernel K3: "[500 x 207] . [207 x B]").  k_rhs re-streams a model's
-// 0.83 MB of H for every instance (measured 13-26x over-fetch); here a workgroup owns up to RM_NI instances of ONE model, keeps
-// their [x0 ; w] columns in registers as MFMA A-fragments (instances along M), and streams H through LDS one 16-row block at a
-// time as the B operand (constraint rows along N), so H is read once per RM_NI instances and the output is written as 128-byte
-// row segments.  v_mfma_f64_16x16x4_f64 (fp64) or v_mfma_f32_16x16x4_f32 (MLD_F32: inputs rounded to fp32, fp32 accumulate).
+// The instance-GEMM core: a batch's per-instance vectors times a model's matrix, as ONE batched GEMM per model with the batch as
+// the M dimension.  A workgroup owns up to RM_NI instances of ONE model (a RhsGroup), keeps their vectors in registers as MFMA
+// A fragments (instances along M), and streams the model's matrix through an LDS tile sixteen rows (or columns) at a time as the
+// B operand, so the matrix is read once per RM_NI instances and the output is written as 128-byte segments.  An inner dimension
+// that does not fit the registers goes in chunks of IG_KC with the output as the accumulator.  v_mfma_f64_16x16x4_f64 (fp64)
+// or v_mfma_f32_16x16x4_f32 (MLD_F32: inputs rounded to fp32, fp32 accumulate).
 // Lane maps (guides/cdna_hip_programming.md): A[i = l & 15][k = l >> 4], B[k = l >> 4][j = l & 15];
 // f64 C/D: col = l & 15, row = (l >> 4) + 4 r;  f32 C/D: col = l & 15, row = 4 (l >> 4) + r.
+// The pieces (all inlined; li = lane & 15, lk = lane >> 4): ig_slots (a lane's instances), ig_load_a (A fragments), ig_stage
+// (sixteen rows into an LDS tile), ig_mma (the MFMA chain), ig_bits (masks of groups of four inner indices).  The members
+// -- k_rhs_mfma below, k_inst_pullback (inst_cost.inc), k_trajectory (trajectory.inc), k_evaluate (evaluate.inc) -- add what
+// they read, the groups they may skip, and their epilogue.
 #pragma once
 
 #define RM_WAVES 8
 #define RM_NI (16 * RM_WAVES)        // instances per workgroup
 #define RM_KMAX 320                  // K = nx + N nw padded to a multiple of 4 (cfg3: 208); larger shapes use k_rhs
 #define RM_KS (RM_KMAX / 4)
+#define IG_KC 256                    // inner-dimension chunk (of the chunked members) whose A fragments live in registers
+#define IG_KS (IG_KC / 4)
+#define IG_LD (IG_KC + 1)            // row stride of a staged [16][IG_KC] tile (odd: few bank conflicts)
 
 typedef double rm_f64x4 __attribute__((ext_vector_type(4)));
 typedef float rm_f32x4 __attribute__((ext_vector_type(4)));
 
 struct RhsGroup { int model, start, count; };    // instances perm[start .. start + count) share `model`
 
+template <bool F32, int KS> struct IgFrag { double a64[F32 ? 1 : KS]; float a32[F32 ? KS : 1]; };      // A fragments of KS groups of four
+
+// the instance whose A fragments this lane holds (the return value) and the instances of its four C/D rows; -1 past the group's end
+template <bool F32>
+__device__ __forceinline__ int ig_slots(const RhsGroup &g, const int *perm, int wave, int li, int lk, int (&oinst)[4])
+{
+    auto at = [=](int slot) { return slot < g.count ? (perm ? perm[g.start + slot] : g.start + slot) : -1; };
+    const int inst = at(wave * 16 + li);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) oinst[r] = at(wave * 16 + (F32 ? 4 * lk + r : lk + 4 * r));
+    return inst;
+}
+
+// A fragments of the chunk that begins at kc0 and has ks groups: a[s] = load(k), k = kc0 + 4 s + lk < K; zero past K and in a lane without
+// an instance.  (The loaders and predicates capture by value: what a lambda reaches through a reference the compiler may leave in memory.)
+template <bool F32, int KS, typename Load>
+__device__ __forceinline__ void ig_load_a(IgFrag<F32, KS> &a, int inst, int kc0, int lk, int ks, int K, Load load)
+{
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+        double v = 0.0;
+        const int k = kc0 + 4 * s + lk;
+        if (s < ks && inst >= 0 && k < K) v = load(k);
+        if (F32) a.a32[s] = (float)v; else a.a64[s] = v;
+    }
+}
+
+// bits lo .. hi - 1 of a chunk's mask of groups of four inner indices (clipped to the IG_KS groups of a chunk)
+static_assert(IG_KS == 64, "a chunk's groups of four are one 64-bit mask");
+__device__ __forceinline__ unsigned long long ig_bits(int lo, int hi)
+{
+    lo = max(lo, 0); hi = min(hi, IG_KS);
+    if (hi <= lo) return 0ull;
+    return (hi - lo == 64 ? ~0ull : (1ull << (hi - lo)) - 1ull) << lo;
+}
+struct IgMask {                      // such a mask as ig_mma's predicate
+    unsigned long long need;
+    __device__ bool operator()(int s) const { return (need >> s & 1ull) != 0; }
+};
+
+// tile[i][kk] = at(rb + i, kc0 + kk) for sixteen rows and the groups of four in `need`, coalesced along each row, between two barriers;
+// skipped groups are neither read nor written
+template <typename At>
+__device__ __forceinline__ void ig_stage(double *tile, int tid, int rb, int kc0, unsigned long long need, At at)
+{
+    __syncthreads();
+    for (int e = tid; e < 16 * IG_KC; e += 64 * RM_WAVES) {
+        const int i = e / IG_KC, kk = e % IG_KC;
+        if (need >> (kk >> 2) & 1ull) tile[i * IG_LD + kk] = at(rb + i, kc0 + kk);
+    }
+    __syncthreads();
+}
+
+// res[r] = sum over the groups s with use(s) of A[.][4 s ..] B[4 s ..][li], B[k = 4 s + lk][j = li] = brow[STRIDE * s].  Two accumulators
+// hide the dependent latency of the chain: even s into one, odd s into the other, summed at the end (in float under F32, then widened).
+template <int STRIDE, bool F32, int KS, typename Use>
+__device__ __forceinline__ void ig_mma(const IgFrag<F32, KS> &a, const double *brow, Use use, double (&res)[4])
+{
+    if (F32) {
+        rm_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < KS; s += 2) {
+            if (use(s)) acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.a32[s], (float)brow[STRIDE * s], acc0, 0, 0, 0);
+            if (use(s + 1)) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.a32[s + 1], (float)brow[STRIDE * (s + 1)], acc1, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) res[r] = (double)(acc0[r] + acc1[r]);
+    } else {
+        rm_f64x4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int s = 0; s < KS; s += 2) {
+            if (use(s)) acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a.a64[s], brow[STRIDE * s], acc0, 0, 0, 0);
+            if (use(s + 1)) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a.a64[s + 1], brow[STRIDE * (s + 1)], acc1, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) res[r] = acc0[r] + acc1[r];
+    }
+}
+
+// K3, the constraint right-hand sides of a whole batch:
+//     hs[b, :] = rs .* ([H_x | H_w] [x0_b ; w_b] + H_5)          (controllers/controller_base.py:446-450)
+// (SURVEY section 2, kernel K3: "[500 x 207] . [207 x B]").  k_rhs re-streams a model's 0.83 MB of H for every instance (measured
+// 13-26x over-fetch).  What it adds to the core: no chunks -- all K <= RM_KMAX of [x0 ; w] in registers, a dynamic tile of all Kp
+// columns -- and the epilogue with H_5 and the row scale.
 template <bool F32>
 __global__ void __launch_bounds__(64 * RM_WAVES) k_rhs_mfma(int m0, int nx, int nW, int Kp, const double *Hx, const double *Hw, const double *H5,
                                                             const double *rs, const RhsGroup *groups, const int *perm, const double *x0,
@@ -31,26 +121,10 @@ __global__ void __launch_bounds__(64 * RM_WAVES) k_rhs_mfma(int m0, int nx, int 
     const int ld = Kp + 1, K = nx + nW, ks = Kp >> 2;
     const double *hx = Hx ? Hx + (size_t)g.model * m0 * nx : nullptr, *hw = Hw ? Hw + (size_t)g.model * m0 * nW : nullptr;
     const double *h5 = H5 + (size_t)g.model * m0, *rsm = rs ? rs + (size_t)g.model * m0 : nullptr;
-    // A fragments: instance (wave, li) x k = 4 s + lk, all K in registers
-    const int slot = wave * 16 + li;
-    const int inst = slot < g.count ? (perm ? perm[g.start + slot] : g.start + slot) : -1;
-    double a64[F32 ? 1 : RM_KS]; float a32[F32 ? RM_KS : 1];
-#pragma unroll
-    for (int s = 0; s < RM_KS; ++s) {
-        double v = 0.0;
-        if (s < ks) {
-            const int k = 4 * s + lk;
-            if (inst >= 0 && k < K) v = k < nx ? x0[(size_t)inst * nx + k] : omega[(size_t)inst * nW + (k - nx)];
-        }
-        if (F32) a32[s] = (float)v; else a64[s] = v;
-    }
-    // the instances this lane's results belong to (C/D rows)
     int oinst[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int oi = wave * 16 + (F32 ? 4 * lk + r : lk + 4 * r);
-        oinst[r] = oi < g.count ? (perm ? perm[g.start + oi] : g.start + oi) : -1;
-    }
+    const int inst = ig_slots<F32>(g, perm, wave, li, lk, oinst);
+    IgFrag<F32, RM_KS> a;
+    ig_load_a(a, inst, 0, lk, ks, K, [=](int k) { return k < nx ? x0[(size_t)inst * nx + k] : omega[(size_t)inst * nW + (k - nx)]; });
     for (int rb = 0; rb < m0; rb += 16) {
         __syncthreads();
         // stage rows rb .. rb+15 of [H_x | H_w] (zero padded), coalesced along each row
@@ -61,32 +135,13 @@ __global__ void __launch_bounds__(64 * RM_WAVES) k_rhs_mfma(int m0, int nx, int 
             rm_tile[i * ld + k] = v;
         }
         __syncthreads();
-        const double *brow = rm_tile + li * ld + lk;          // B[k = 4 s + lk][j = li] = H[rb + li][k]
         const int row = rb + li;
-        if (F32) {
-            rm_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};      // two accumulators hide the 40-cycle dependent latency
+        double res[4];
+        ig_mma<4>(a, rm_tile + li * ld + lk, [ks](int s) { return s < ks; }, res);          // B = H[rb + li][k]
+        if (row < m0) {
+            const double c5 = h5[row], sc = rsm ? rsm[row] : 1.0;
 #pragma unroll
-            for (int s = 0; s < RM_KS; s += 2) {
-                if (s < ks) acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a32[s], (float)brow[4 * s], acc0, 0, 0, 0);
-                if (s + 1 < ks) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a32[s + 1], (float)brow[4 * (s + 1)], acc1, 0, 0, 0);
-            }
-            if (row < m0) {
-                const double c5 = h5[row], sc = rsm ? rsm[row] : 1.0;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) if (oinst[r] >= 0) hs[(size_t)oinst[r] * m0 + row] = ((double)(acc0[r] + acc1[r]) + c5) * sc;
-            }
-        } else {
-            rm_f64x4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int s = 0; s < RM_KS; s += 2) {
-                if (s < ks) acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a64[s], brow[4 * s], acc0, 0, 0, 0);
-                if (s + 1 < ks) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a64[s + 1], brow[4 * (s + 1)], acc1, 0, 0, 0);
-            }
-            if (row < m0) {
-                const double c5 = h5[row], sc = rsm ? rsm[row] : 1.0;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) if (oinst[r] >= 0) hs[(size_t)oinst[r] * m0 + row] = (acc0[r] + acc1[r] + c5) * sc;
-            }
+            for (int r = 0; r < 4; ++r) if (oinst[r] >= 0) hs[(size_t)oinst[r] * m0 + row] = (res[r] + c5) * sc;
         }
     }
 }

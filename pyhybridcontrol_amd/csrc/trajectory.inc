@@ -3,12 +3,11 @@
 //     y_tilde = L_x   x_k + L_v     v_tilde + L_omega     omega_tilde + L_5          (:269-275)
 // as ONE GEMM per model, the forward half of k_inst_pullback (inst_cost.inc):
 //     [x_tilde_b | y_tilde_b] = [v_b | x0_b | omega_b | 1] . [Gamma_v | Phi_x | Gamma_w | Gamma_5 ; L_v | L_x | L_w | L_5]'
-// with the instances along M and the N nx + N ny output rows along N.  Mirrors k_rhs_mfma (mfma.inc, whose lane maps and RhsGroup it uses):
-// a workgroup owns up to RM_NI instances of one model and holds their inputs as MFMA A fragments; the maps are stored (rows x cols) with the
-// inner dimension contiguous, so 16 output rows are staged coalesced along each row into an LDS tile of odd stride and read as the B operand.
-// The constant column (Gamma_5 / L_5 times the trailing 1) is added to the first chunk's result as K3 adds H_5, so the multiplied inner dimension
-// is n + nx + N nw (cfg4: 782).  It goes in chunks of TJ_KC: the output is the accumulator, written by the first chunk and read and written by
-// the same lane in every later one.
+// with the instances along M and the N nx + N ny output rows along N.  A member of the instance-GEMM family (mfma.inc).  What it adds: the
+// eight maps read as one stacked matrix with the inner dimension contiguous (row tiles, ig_stage); the causal skip below; the constant column
+// (Gamma_5 / L_5 times the trailing 1) added to the first chunk's result as K3 adds H_5, so the multiplied inner dimension is n + nx + N nw
+// (cfg4: 782); NaN rows for instances without a usable plan.  The output is the accumulator, written by the first chunk and read and written
+// by the same lane in every later one.
 //
 // Causal skip: block (i, j) of Gamma_v / Gamma_w is zero for j >= i and of L_v / L_w for j > i (the state of step i depends on the inputs of
 // the steps before it, the output also on its own step; tests/test_trajectories_host.py pins this on the condensed maps, time-varying
@@ -16,23 +15,11 @@
 // j <= i only.  Groups of four inner indices are staged and multiplied whole, so a group that straddles the boundary reads stored zeros.
 #pragma once
 
-#define TJ_KC 256                    // inner-dimension chunk whose A fragments live in registers
-#define TJ_KS (TJ_KC / 4)
-#define TJ_LD (TJ_KC + 1)
-
-// bits lo .. hi - 1 of a chunk's mask of groups of four inner indices (clipped to the TJ_KS groups of a chunk)
-__device__ __forceinline__ unsigned long long tj_bits(int lo, int hi)
+// a family's map of this model, or its stride, by number (selects of values, not an indexed array: they stay in registers)
+template <typename T> __device__ __forceinline__ T tj_pick(int f, const T (&a)[4])
 {
-    lo = max(lo, 0); hi = min(hi, TJ_KS);
-    if (hi <= lo) return 0ull;
-    return (hi - lo == 64 ? ~0ull : (1ull << (hi - lo)) - 1ull) << lo;
-}
-
-// a family's map of this model by number (selects, not an indexed array: the pointers stay in registers)
-__device__ __forceinline__ size_t tj_pick2(int f, const size_t (&a)[4]) { return f == 0 ? a[0] : f == 1 ? a[1] : f == 2 ? a[2] : a[3]; }
-__device__ __forceinline__ const double *tj_pick(int f, const double *p0, const double *p1, const double *p2, const double *p3)
-{
-    return f == 0 ? p0 : f == 1 ? p1 : f == 2 ? p2 : p3;
+    const T a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3];
+    return f == 0 ? a0 : f == 1 ? a1 : f == 2 ? a2 : a3;
 }
 
 // status / obj: null = the caller's plans (no masking); else an instance without a usable plan (plan_usable) gets NaN rows
@@ -41,36 +28,23 @@ __global__ void __launch_bounds__(64 * RM_WAVES) k_trajectory(int N, int nxs, in
                                                               const int *perm, const double *v, const double *x0, const double *omega,
                                                               const int *status, const double *obj, int r_begin, int r_end, double *xo, double *yo)
 {
-    __shared__ double tj_tile[16 * TJ_LD];
+    __shared__ double tj_tile[16 * IG_LD];
     const RhsGroup g = groups[blockIdx.x];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lk = lane >> 4;
     const int NX = N * nxs, NY = N * nys, n = N * nv, nx = nxs, nW = N * nw, K = n + nx + nW;
-    static_assert(TJ_KS == 64, "a chunk's groups of four are one 64-bit mask");
-    const int slot = wave * 16 + li;
-    const int inst = slot < g.count ? (perm ? perm[g.start + slot] : g.start + slot) : -1;
     int oinst[4]; bool dead[4];
+    const int inst = ig_slots<F32>(g, perm, wave, li, lk, oinst);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int oi = wave * 16 + (F32 ? 4 * lk + r : lk + 4 * r);
-        oinst[r] = oi < g.count ? (perm ? perm[g.start + oi] : g.start + oi) : -1;
-        dead[r] = status && oinst[r] >= 0 && !plan_usable(status, obj, oinst[r]);
-    }
-    for (int kc0 = 0; kc0 < K || kc0 == 0; kc0 += TJ_KC) {
-        const int ks = (min(TJ_KC, K - kc0) + 3) >> 2, g0 = kc0 >> 2;
-        // A fragments of this chunk: instance (wave, li) x k = kc0 + 4 s + lk of [v | x0 | omega]
-        double a64[F32 ? 1 : TJ_KS]; float a32[F32 ? TJ_KS : 1];
-#pragma unroll
-        for (int s = 0; s < TJ_KS; ++s) {
-            double a = 0.0;
-            const int k = kc0 + 4 * s + lk;
-            if (s < ks && inst >= 0 && k < K) {
-                if (k < n) a = v[(size_t)inst * n + k];
-                else if (k < n + nx) a = x0[(size_t)inst * nx + (k - n)];
-                else a = omega[(size_t)inst * nW + (k - n - nx)];
-            }
-            if (F32) a32[s] = (float)a; else a64[s] = a;
-        }
+    for (int r = 0; r < 4; ++r) dead[r] = status && oinst[r] >= 0 && !plan_usable(status, obj, oinst[r]);
+    for (int kc0 = 0; kc0 < K || kc0 == 0; kc0 += IG_KC) {
+        const int ks = (min(IG_KC, K - kc0) + 3) >> 2, g0 = kc0 >> 2;
+        IgFrag<F32, IG_KS> a;                   // this chunk of [v | x0 | omega]
+        ig_load_a(a, inst, kc0, lk, ks, K, [=](int k) {
+            if (k < n) return v[(size_t)inst * n + k];
+            if (k < n + nx) return x0[(size_t)inst * nx + (k - n)];
+            return omega[(size_t)inst * nW + (k - n - nx)];
+        });
         for (int rb = r_begin; rb < r_end; rb += 16) {
             // the last step among the rows of this block, and with it the groups of four inner indices the block needs
             const int last = min(rb + 15, r_end - 1);
@@ -79,48 +53,25 @@ __global__ void __launch_bounds__(64 * RM_WAVES) k_trajectory(int N, int nxs, in
             if (last >= NX) imax = max(imax, (last - NX) / nys);
             // (global groups [0, ga) of v and [n / 4, gc) of x0 and omega; as bits of this chunk)
             const int ga = (min(n, (imax + 1) * nv) + 3) >> 2, gc = (n + nx + min(nW, (imax + 1) * nw) + 3) >> 2;
-            const unsigned long long need = (tj_bits(-g0, ga - g0) | tj_bits((n >> 2) - g0, gc - g0)) & tj_bits(0, ks);
+            const unsigned long long need = (ig_bits(-g0, ga - g0) | ig_bits((n >> 2) - g0, gc - g0)) & ig_bits(0, ks);
             if (!need && kc0 > 0) continue;         // nothing of this chunk reaches these rows (uniform over the workgroup)
-            __syncthreads();
-            // stage rows rb .. rb + 15 of the stacked maps, inner indices kc0 .. kc0 + 4 ks, coalesced along each row; skipped groups are not read
-            for (int e = tid; e < 16 * TJ_KC; e += 64 * RM_WAVES) {
-                const int i = e / TJ_KC, kk = e % TJ_KC, row = rb + i, k = kc0 + kk;
-                if (!(need >> (kk >> 2) & 1ull)) continue;
+            // rows rb .. rb + 15 of the stacked maps, inner indices kc0 .. kc0 + 4 ks
+            ig_stage(tj_tile, tid, rb, kc0, need, [=](int row, int k) {
                 double val = 0.0;
                 if (row < r_end && k < K) {
                     const bool isx = row < NX;
                     const size_t rr = isx ? row : row - NX;
                     int fam, col, ld;
                     pb_column(k, n, nx, nW, fam, col, ld);
-                    const double *pm = isx ? tj_pick(fam, mp.W[0], mp.W[1], mp.W[2], mp.W[3]) : tj_pick(fam, mp.Y[0], mp.Y[1], mp.Y[2], mp.Y[3]);
-                    const size_t sm = isx ? tj_pick2(fam, mp.sW) : tj_pick2(fam, mp.sY);
+                    const double *pm = isx ? tj_pick(fam, mp.W) : tj_pick(fam, mp.Y);
+                    const size_t sm = isx ? tj_pick(fam, mp.sW) : tj_pick(fam, mp.sY);
                     if (pm) val = pm[(size_t)g.model * sm + rr * ld + col];
                 }
-                tj_tile[i * TJ_LD + kk] = val;
-            }
-            __syncthreads();
-            const double *brow = tj_tile + li * TJ_LD + lk;          // B[k = 4 s + lk][j = li] = map[rb + li][kc0 + k]
+                return val;
+            });
             const int row = rb + li;
             double res[4];
-            if (F32) {
-                rm_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int s = 0; s < TJ_KS; s += 2) {
-                    if (need >> s & 1ull) acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a32[s], (float)brow[4 * s], acc0, 0, 0, 0);
-                    if (need >> (s + 1) & 1ull) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a32[s + 1], (float)brow[4 * (s + 1)], acc1, 0, 0, 0);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) res[r] = (double)(acc0[r] + acc1[r]);
-            } else {
-                rm_f64x4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int s = 0; s < TJ_KS; s += 2) {
-                    if (need >> s & 1ull) acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a64[s], brow[4 * s], acc0, 0, 0, 0);
-                    if (need >> (s + 1) & 1ull) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a64[s + 1], brow[4 * (s + 1)], acc1, 0, 0, 0);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) res[r] = acc0[r] + acc1[r];
-            }
+            ig_mma<4>(a, tj_tile + li * IG_LD + lk, IgMask{need}, res);      // B = map[rb + li][kc0 + k]
             if (row < r_end) {
                 if (kc0 == 0) {      // the constant column
                     const double *p5 = row < NX ? mp.W[3] : mp.Y[3];

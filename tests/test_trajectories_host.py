@@ -100,7 +100,7 @@ def test_causal_zero_blocks_of_time_varying_horizons():
     _assert_causal(cn.condense(ag["mats"], N), N, d, "cfg2")
 
 
-# ---- replay of k_trajectory's skip mask (csrc/trajectory.inc: tj_bits, imax, ga / gc, the chunk offset g0), restated line by line -------
+# ---- replay of k_trajectory's skip mask (csrc/trajectory.inc: imax, ga / gc, the chunk offset g0; csrc/mfma.inc: ig_bits, IG_KC = 256), restated line by line -------
 TJ_KC, TJ_KS = 256, 64
 
 
