@@ -144,9 +144,14 @@ typedef enum {
     MLD_DBG_PIVOT_SYNC_R5 = 1 << 26,    /* k_solve's pivot with the block barriers it had before they were halved: six in its first half, two per
                                            SOL_NT-wide chunk of the sector and row lists (and two sums for the counts of a pair) instead of three and
                                            one exchange (A/B on the same binary: results and rows_updated are bit-identical, only speed changes) */
-    MLD_DBG_SELECT_R6 = 1 << 27         /* k_solve's choice of (row, column) as it was before its block reductions left the LDS crossbar:
+    MLD_DBG_SELECT_R6 = 1 << 27,        /* k_solve's choice of (row, column) as it was before its block reductions left the LDS crossbar:
                                            __shfl_down reductions with a serial combine of the waves' partials, the eligibility test of the
                                            ratio test as nested branches (A/B on the same binary: results are bit-identical, only speed changes) */
+    MLD_DBG_UPDATE_R7 = 1 << 28         /* k_solve's row updates of a pivot and of a fused pair as they were before a unit was cut down to its
+                                           payload: every lane and row predicated, the entering column selected in every unit, rows handed to the
+                                           waves in blocks.  Bits 26, 27 and 28 each take the dual simplex into its legacy instantiation, which
+                                           holds all three earlier variants; with none of them set the loop carries only the code it runs
+                                           (A/B on the same binary: results and rows_updated are bit-identical, only speed changes) */
 } mld_reserved_bit;
 
 /* Linear cost in tiled horizon form (the Python layer parses the reference's string-keyed atoms,

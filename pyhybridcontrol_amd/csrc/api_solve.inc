@@ -449,6 +449,51 @@ int mld_debug_reduce(const double *values, const int32_t *index, int n_vec, doub
     return MLD_OK;
 }
 
+/* the row-block sizes of k_solve's row update (internal diagnostics; not part of the public header; no device needed): out[0..3] = rows a wave takes at a
+ * time when a chunk has 1, 2, 3, 4 groups of 16 sectors, [4] waves per workgroup, [5] sectors per group, [6] doubles per sector, [7] groups per chunk */
+int mld_debug_update_shape(int32_t out[8])
+{
+    if (!out) { mld_set_error("mld_debug_update_shape: bad arguments"); return MLD_ERR_INVALID; }
+    const int32_t v[8] = {s_update_rb(1), s_update_rb(2), s_update_rb(3), s_update_rb(4), SOL_NW, SOL_SPW, SOL_SEC, 4};      // (the templates' own constexpr)
+    for (int k = 0; k < 8; ++k) out[k] = v[k];
+    return MLD_OK;
+}
+
+/* the rows' update of one pivot of k_solve (rowr2 == NULL) or of a fused pair, on a caller-supplied dictionary D (m x ld, row-major; updated in place) (internal
+ * diagnostics; not part of the public header): rowr1[n + 1] / colc1[m] the staged (scaled) pivot row and multiplier column of pivot (r1, c1), rowr2 / colc2 /
+ * (r2, c2) the second pivot's.  The kernel builds the sector and row lists as the solver does and runs the update: reserved = 0 the default instantiation,
+ * MLD_DBG_UPDATE_R7 (and / or MLD_DBG_PIVOT_SYNC_R5) the legacy one.  *rows_updated = the (row, sector) pairs it accounted. */
+int mld_debug_update_rows(double *D, int m, int ld, int n, const double *rowr1, const double *colc1, int r1, int c1,
+                          const double *rowr2, const double *colc2, int r2, int c2, int reserved, int64_t *rows_updated)
+{
+    const bool pair = rowr2 != nullptr;
+    if (!D || !rowr1 || !colc1 || m < 2 || m > DBG_UPD_MAX || ld < SOL_SEC || ld > DBG_UPD_MAX || ld % SOL_SEC || n < 1 || n >= ld || n + 1 + SOL_SEC <= ld || r1 < 0 || r1 >= m || c1 < 0 || c1 >= n ||
+        (pair && (!colc2 || r2 < 0 || r2 >= m || c2 < 0 || c2 >= n)) || (!pair && colc2) || (reserved & ~(MLD_DBG_UPDATE_R7 | MLD_DBG_PIVOT_SYNC_R5))) {
+        mld_set_error("mld_debug_update_rows: bad arguments (2 <= m <= %d, ld = n + 1 rounded up to a multiple of %d, at most %d, pivots inside, reserved = bits 26 / 28 only)", DBG_UPD_MAX, SOL_SEC, DBG_UPD_MAX);
+        return MLD_ERR_INVALID;
+    }
+    if (mld_device_count() <= 0) { mld_set_error("no HIP device"); return MLD_ERR_NO_DEVICE; }
+    DevBuf<double> dD, dr1, dc1, dr2, dc2; DevBuf<unsigned long long> drows;
+    const size_t len = (size_t)m * ld;
+    HIP_TRY(dD.alloc(len)); HIP_TRY(dr1.alloc(n + 1)); HIP_TRY(dc1.alloc(m)); HIP_TRY(drows.alloc(1));
+    HIP_TRY(hipMemcpy(dD, D, sizeof(double) * len, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dr1, rowr1, sizeof(double) * (n + 1), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dc1, colc1, sizeof(double) * m, hipMemcpyHostToDevice));
+    if (pair) {
+        HIP_TRY(dr2.alloc(n + 1)); HIP_TRY(dc2.alloc(m));
+        HIP_TRY(hipMemcpy(dr2, rowr2, sizeof(double) * (n + 1), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(dc2, colc2, sizeof(double) * m, hipMemcpyHostToDevice));
+    }
+    hipLaunchKernelGGL(k_debug_update, dim3(1), dim3(SOL_NT), 0, 0, (double *)dD, m, n, ld, (const double *)dr1, (const double *)dc1, r1, c1,
+                       pair ? (const double *)dr2 : (const double *)nullptr, pair ? (const double *)dc2 : (const double *)nullptr, r2, c2, pair ? 1 : 0, reserved,
+                       (unsigned long long *)drows);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(D, dD, sizeof(double) * len, hipMemcpyDeviceToHost));
+    if (rows_updated) { unsigned long long r = 0; HIP_TRY(hipMemcpy(&r, drows, sizeof(r), hipMemcpyDeviceToHost)); *rows_updated = (int64_t)r; }
+    return MLD_OK;
+}
+
 /* the solver's shape (internal diagnostics; not part of the public header): [0..7] n, m0, mcap, first_cap, ld, mir_cap, lds_bytes, ws_stride;
  * [8..19] the LDS byte offsets (-1: in the slot) lXB, lBasic, lSkip, lAtUp, lNonbasic, lXN, lLo, lHi, lDw, lCost, lMirLine, lMirCache;
  * [20] the LDS budget of the hot arrays, [21] the MLD_SOL_SLOT mask (bit k: SLOT_NAMES[k]), [22] n_slots,

@@ -1172,11 +1172,14 @@ __device__ void s_set_bounds_list(const Ws &w, Shared &sh, const int *js, const 
 // (s_look_ahead) and the second pivot's multiplier column (s_pivot_head) all go through here: an entry has the same bits whichever of them computes it.
 __device__ __forceinline__ double s_upd(double o, double mu, double rr) { return __builtin_fma(-mu, rr, o); }
 
+// rows a wave takes at a time when a chunk has ng groups of sectors: the ONE definition (the four update templates; mld_debug_update_shape reports it)
+__host__ __device__ constexpr int s_update_rb(int ng) { return (ng <= 2 ? 16 : (ng == 3 ? 10 : 8)) / (SOL_WPE / 2); }
+
 template <int NG>
 __device__ __forceinline__ void s_update_rows(glb_f64 *D, int ld, const lds_f64 *rowr, const lds_f64 *colc, const lds_u16 *rowlist,
                                               const lds_u16 *seclist, int nrows, int nact, int g0, int c, int wave, int lane)
 {
-    constexpr int RB = (NG <= 2 ? 16 : (NG == 3 ? 10 : 8)) / (SOL_WPE / 2);
+    constexpr int RB = s_update_rb(NG);
     const int sub = lane / SOL_LPS, pr = (lane % SOL_LPS) * 2;
     int koff[NG]; bool ok[NG], cx[NG], cy[NG]; double2_t rr[NG];
 #pragma unroll
@@ -1228,7 +1231,7 @@ __device__ __forceinline__ void s_update_rows2(glb_f64 *D, int ld, const lds_f64
                                                const lds_u16 *rowlist, const lds_u16 *seclist, const lds_u8 *secflag, int nrows, int nact, int g0,
                                                int r1, int c1, int c2, int wave, int lane)
 {
-    constexpr int RB = (NG <= 2 ? 16 : (NG == 3 ? 10 : 8)) / (SOL_WPE / 2);
+    constexpr int RB = s_update_rb(NG);
     const int sub = lane / SOL_LPS, pr = (lane % SOL_LPS) * 2;
     int koff[NG]; bool a1[NG], a2[NG], cx1[NG], cy1[NG], cx2[NG], cy2[NG]; double2_t rr1[NG], rr2[NG];
 #pragma unroll
@@ -1289,6 +1292,196 @@ __device__ __forceinline__ void s_update_rows2(glb_f64 *D, int ld, const lds_f64
     }
 }
 
+// ---- the same two updates with a unit (one row x one group of 16 sectors: a 16-byte load, the fused multiply-adds, a 16-byte store) close to its payload ----
+// (s_update_rows_r7, s_update_rows2_r7: what the loop runs; MLD_DBG_UPDATE_R7 keeps the two templates above selectable in the legacy instantiation.  Every
+// element sees the operations of the templates above in their order and is stored where they store it; what differs is where the exceptions are paid for.)
+//  * A pivot's last group of 16 sectors is rarely full.  Its lanes past the last active sector repeat that sector: the same address, the same operands, the
+//    same value stored -- no lane of a group is ever switched off, so no unit carries a test for it.
+//  * The entering column belongs to one lane of one group.  That group trades places with the chunk's first (the second pivot's with the chunk's second), so
+//    only slot 0 (and slot 1 for the second pivot) carries the two selects that count the old entry as 0.
+//  * Rows go to the waves round robin (row t of a block of SOL_NW * RB to wave t % SOL_NW): 84 rows are 10 or 11 for each wave instead of 16 for five of them
+//    and none for two.  The LOAD phase of a block has no control flow: a wave that has fewer than RB rows left loads its last row again in the remaining
+//    slots (the same lines, read and never used), so all RB * NG loads are issued back to back before the first use, as in the templates above; a load under a
+//    test of the row count made the compiler wait for the loads in flight before every row.  Only the compute phase tests the row count, a scalar branch per row.
+//  * In the pair, the row's flags (first update, second, both) are wave-uniform: a branch picks one of three bodies instead of selects per lane and unit.
+//  * What is the same in every lane is told to the compiler (S_UNI): the workspace view lives in private memory, so without it the leading dimension, the row
+//    count and the wave's number count as per-lane values, every row test becomes a lane mask and every address a 64-bit vector sum.  With it a row's base is a
+//    scalar pair; a unit's address is that pair plus the lane's byte offset.
+#define S_UNI(x_) __builtin_amdgcn_readfirstlane(x_)
+#ifndef MLD_UPDATE_LEGACY_ALWAYS
+#define MLD_UPDATE_LEGACY_ALWAYS 0      // (-DMLD_UPDATE_LEGACY_ALWAYS=1: a measurement build whose default loop keeps the earlier templates, DESIGN section 6)
+#endif
+__device__ __forceinline__ glb_f64 *s_uni_ptr(glb_f64 *p)
+{
+    const unsigned long long v = (unsigned long long)p;
+    return (glb_f64 *)(((unsigned long long)(unsigned)S_UNI((int)(v >> 32)) << 32) | (unsigned)S_UNI((int)v));
+}
+// (the empty asm keeps the 32-bit offset opaque up to its use: widened once outside the loop it is a register pair per group, and the access a 64-bit vector add
+// plus `global_* v, v[a:b], off`; kept 32-bit it is `global_* v, v_off, s[base]`, one register and no add)
+__device__ __forceinline__ double2_t s_ld16(const glb_f64 *base, unsigned off) { asm volatile("" : "+v"(off)); return *(const glb_f64x2 *)((const __attribute__((address_space(1))) char *)base + off); }
+__device__ __forceinline__ void s_st16(glb_f64 *base, unsigned off, double2_t o) { asm volatile("" : "+v"(off)); *(glb_f64x2 *)((__attribute__((address_space(1))) char *)base + off) = o; }
+// (true when one of the 16 sectors of group `grp` -- as this wave's lanes read them -- is sector `sec`; wave-uniform)
+__device__ __forceinline__ bool s_group_holds(const lds_u16 *seclist, int nact, int grp, int sub, int sec)
+{
+    const int si = min(grp * SOL_SPW + sub, nact - 1);
+    return __ballot((int)seclist[si] == sec) != 0ull;
+}
+
+template <int NG>
+__device__ __forceinline__ void s_update_rows_r7(glb_f64 *D, int ld, const lds_f64 *rowr, const lds_f64 *colc, const lds_u16 *rowlist,
+                                                 const lds_u16 *seclist, int nrows, int nact, int g0, int c, int wave, int lane)
+{
+    constexpr int RB = s_update_rb(NG);
+    const int sub = lane / SOL_LPS, pr = (lane % SOL_LPS) * 2;
+    D = s_uni_ptr(D); ld = S_UNI(ld); wave = S_UNI(wave); nrows = S_UNI(nrows); nact = S_UNI(nact); g0 = S_UNI(g0); c = S_UNI(c);
+    int grp[NG];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) grp[g] = g0 + g;
+#pragma unroll
+    for (int g = 1; g < NG; ++g)
+        if (s_group_holds(seclist, nact, g0 + g, sub, c / SOL_SEC)) { grp[0] = g0 + g; grp[g] = g0; }
+    unsigned koff[NG]; double2_t rr[NG];      // byte offset of the lane's 16 bytes in a row; the pivot row's two entries there
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        const int si = min(grp[g] * SOL_SPW + sub, nact - 1);
+        const int k = (int)seclist[si] * SOL_SEC + pr;      // k and k+1 lie inside the row (ld is a multiple of 8)
+        koff[g] = (unsigned)k * 8u;
+        rr[g] = *(const lds_f64x2 *)(rowr + k);
+    }
+    const bool cx = koff[0] == (unsigned)c * 8u, cy = koff[0] + 8u == (unsigned)c * 8u;   // entering column: old entry counts as 0 (rowr[c] = 1/p)
+    for (int b = wave; b < nrows; b += SOL_NW * RB) {
+        const int nq = min(RB, (nrows - b + SOL_NW - 1) / SOL_NW);      // this wave's rows of the block: b, b + SOL_NW, ...
+        double2_t v[RB][NG];
+        int rowi[RB];
+#pragma unroll
+        for (int q = 0; q < RB; ++q) {      // (no branch in here: slots past the wave's last row repeat it)
+            rowi[q] = S_UNI((int)rowlist[b + min(q, nq - 1) * SOL_NW]);
+            const glb_f64 *base = D + (size_t)rowi[q] * ld;
+#pragma unroll
+            for (int g = 0; g < NG; ++g) v[q][g] = s_ld16(base, koff[g]);
+        }
+#pragma unroll
+        for (int q = 0; q < RB; ++q) {
+            if (q < nq) {
+                const double mu = colc[rowi[q]];
+                glb_f64 *base = D + (size_t)rowi[q] * ld;
+#pragma unroll
+                for (int g = 0; g < NG; ++g) {
+                    double2_t o = v[q][g];
+                    if (g == 0) { if (cx) o.x = 0.0; if (cy) o.y = 0.0; }
+                    o.x = s_upd(o.x, mu, rr[g].x); o.y = s_upd(o.y, mu, rr[g].y);
+                    s_st16(base, koff[g], o);
+                }
+            }
+        }
+    }
+}
+
+// one unit of the pair: the first pivot's update where A1, then the second's where A2 (compile-time: the row's wave-uniform flags), each on the lanes whose sector
+// is active in that pivot's row; Z1 / Z2: the slot can hold that pivot's entering column
+template <bool A1, bool A2, bool Z1, bool Z2>
+__device__ __forceinline__ double2_t s_upd2_unit(double2_t o, bool a1, bool a2, double mu1, double mu2, double2_t rr1, double2_t rr2, bool cx1, bool cy1, bool cx2, bool cy2)
+{
+    if (A1 && a1) {
+        if (Z1) { if (cx1) o.x = 0.0; if (cy1) o.y = 0.0; }
+        o.x = s_upd(o.x, mu1, rr1.x); o.y = s_upd(o.y, mu1, rr1.y);
+    }
+    if (A2 && a2) {
+        if (Z2) { if (cx2) o.x = 0.0; if (cy2) o.y = 0.0; }
+        o.x = s_upd(o.x, mu2, rr2.x); o.y = s_upd(o.y, mu2, rr2.y);
+    }
+    return o;
+}
+
+// (A row of the union list is loaded on all its listed sectors, also where only one of its two updates applies and that pivot's row is not active in the sector:
+// a load that depends on the lane's flags would make every register of the block conditionally defined, and the waits for them would end the loads in flight.
+// Of the sector-rows of a pair 88 % belong to both pivots, DESIGN section 6; what is loaded for nothing is the corners of the union.  Stores are where they were.)
+template <int NG>
+__device__ __forceinline__ void s_update_rows2_r7(glb_f64 *D, int ld, const lds_f64 *rowr1, const lds_f64 *colc1, const lds_f64 *rowr2, const lds_f64 *colc2,
+                                                  const lds_u16 *rowlist, const lds_u16 *seclist, const lds_u8 *secflag, int nrows, int nact, int g0,
+                                                  int r1, int c1, int c2, int wave, int lane)
+{
+    constexpr int RB = s_update_rb(NG);
+    const int sub = lane / SOL_LPS, pr = (lane % SOL_LPS) * 2;
+    D = s_uni_ptr(D); ld = S_UNI(ld); wave = S_UNI(wave); nrows = S_UNI(nrows); nact = S_UNI(nact); g0 = S_UNI(g0); r1 = S_UNI(r1); c1 = S_UNI(c1); c2 = S_UNI(c2);
+    int grp[NG];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) grp[g] = g0 + g;
+#pragma unroll
+    for (int g = 1; g < NG; ++g)      // the first pivot's entering column to slot 0
+        if (s_group_holds(seclist, nact, g0 + g, sub, c1 / SOL_SEC)) { grp[0] = g0 + g; grp[g] = g0; }
+    if constexpr (NG > 2) {      // the second's to slot 1, unless slot 0 or 1 has it
+#pragma unroll
+        for (int g = 2; g < NG; ++g)
+            if (s_group_holds(seclist, nact, grp[g], sub, c2 / SOL_SEC)) { const int t = grp[1]; grp[1] = grp[g]; grp[g] = t; }
+    }
+    unsigned koff[NG]; bool a1[NG], a2[NG]; double2_t rr1[NG], rr2[NG];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        const int si = min(grp[g] * SOL_SPW + sub, nact - 1);
+        const int sec = (int)seclist[si];
+        const int fl = (int)secflag[sec];
+        const int k = sec * SOL_SEC + pr;
+        a1[g] = (fl & 1) != 0; a2[g] = (fl & 2) != 0;
+        koff[g] = (unsigned)k * 8u;
+        rr1[g] = a1[g] ? *(const lds_f64x2 *)(rowr1 + k) : (double2_t){0.0, 0.0};
+        rr2[g] = a2[g] ? *(const lds_f64x2 *)(rowr2 + k) : (double2_t){0.0, 0.0};
+    }
+    constexpr int S1 = NG > 1 ? 1 : 0;      // the slot besides 0 that can hold the second entering column
+    const unsigned b1 = (unsigned)c1 * 8u, b2 = (unsigned)c2 * 8u;
+    const bool cx1 = koff[0] == b1, cy1 = koff[0] + 8u == b1, cx2 = koff[0] == b2, cy2 = koff[0] + 8u == b2;
+    const bool dx2 = koff[S1] == b2, dy2 = koff[S1] + 8u == b2;
+    for (int b = wave; b < nrows; b += SOL_NW * RB) {
+        const int nq = min(RB, (nrows - b + SOL_NW - 1) / SOL_NW);
+        double2_t v[RB][NG];
+        int rowc[RB];      // (wave-uniform) the row
+#pragma unroll
+        for (int q = 0; q < RB; ++q) {      // (no branch in here: slots past the wave's last row repeat it)
+            const int row = S_UNI((int)rowlist[b + min(q, nq - 1) * SOL_NW]);
+            rowc[q] = row;
+            const glb_f64 *base = D + (size_t)row * ld;
+#pragma unroll
+            for (int g = 0; g < NG; ++g) v[q][g] = s_ld16(base, koff[g]);
+        }
+#pragma unroll
+        for (int q = 0; q < RB; ++q) {
+            if (q < nq) {
+                const int row = rowc[q];
+                const double mu1 = colc1[row], mu2 = colc2[row];
+                // (the first pivot's own row holds the pivot element in colc1, not a multiplier: it takes the second update only)
+                const int f = S_UNI((int)(row != r1 && mu1 != 0.0) | ((int)(mu2 != 0.0) << 1));
+                glb_f64 *base = D + (size_t)row * ld;
+                if (f == 3) {      // (every listed sector is active in one of the two rows: every lane stores)
+#pragma unroll
+                    for (int g = 0; g < NG; ++g) {
+                        const double2_t o = g == 0 ? s_upd2_unit<true, true, true, true>(v[q][g], a1[g], a2[g], mu1, mu2, rr1[g], rr2[g], cx1, cy1, cx2, cy2)
+                                          : g == S1 ? s_upd2_unit<true, true, false, true>(v[q][g], a1[g], a2[g], mu1, mu2, rr1[g], rr2[g], false, false, dx2, dy2)
+                                                    : s_upd2_unit<true, true, false, false>(v[q][g], a1[g], a2[g], mu1, mu2, rr1[g], rr2[g], false, false, false, false);
+                        s_st16(base, koff[g], o);
+                    }
+                } else if (f == 1) {
+#pragma unroll
+                    for (int g = 0; g < NG; ++g)
+                        if (a1[g]) {
+                            const double2_t o = g == 0 ? s_upd2_unit<true, false, true, false>(v[q][g], true, false, mu1, mu2, rr1[g], rr2[g], cx1, cy1, false, false)
+                                                       : s_upd2_unit<true, false, false, false>(v[q][g], true, false, mu1, mu2, rr1[g], rr2[g], false, false, false, false);
+                            s_st16(base, koff[g], o);
+                        }
+                } else if (f == 2) {
+#pragma unroll
+                    for (int g = 0; g < NG; ++g)
+                        if (a2[g]) {
+                            const double2_t o = g == 0 ? s_upd2_unit<false, true, false, true>(v[q][g], false, true, mu1, mu2, rr1[g], rr2[g], false, false, cx2, cy2)
+                                              : g == S1 ? s_upd2_unit<false, true, false, true>(v[q][g], false, true, mu1, mu2, rr1[g], rr2[g], false, false, dx2, dy2)
+                                                        : s_upd2_unit<false, true, false, false>(v[q][g], false, true, mu1, mu2, rr1[g], rr2[g], false, false, false, false);
+                            s_st16(base, koff[g], o);
+                        }
+                }
+            }
+        }
+    }
+}
+
 // First half of a pivot (entering column c, leaving row r, leaving variable goes to leave_value): everything but the update of the other rows.  The multiplier column
 // and the pivot row are staged in LDS (colc, rowr); the row is scaled (LDS and dictionary); x_B, the devex weights, the cost row and the basis maps move on.  All of
 // that reads only the staged row and column and the small per-basis arrays, so the update of the other rows is the LAST thing a pivot does (s_pivot_inl) and the
@@ -1300,7 +1493,7 @@ __device__ __forceinline__ void s_update_rows2(glb_f64 *D, int ld, const lds_f64
 // (3) at the end.  Between (2) and (3) no thread reads what another one writes: a thread scales the rowr[k] and reads the colc[i] it staged itself, updates its own
 // x_B[i], w[i] (the owner of row r writes the entering value) and d[k] from the rowr[k] it scaled (the owner of column n takes d[n]), and thread 0's book-keeping
 // touches scalars nobody reads before (3).  MLD_DBG_PIVOT_SYNC_R5 puts the three barriers that stood between these steps back (DESIGN section 6: hazard table).
-template <bool L, bool SECOND>
+template <bool L, bool SECOND, bool LEG>
 __device__ __forceinline__ void s_pivot_head(const Ws &w, Shared &sh, int r, int c, double leave_value, lds_f64 *rowr, lds_f64 *colc, int r1, int c1)
 {
     HOT_VIEW(L, w);
@@ -1308,7 +1501,7 @@ __device__ __forceinline__ void s_pivot_head(const Ws &w, Shared &sh, int r, int
     glb_f64 *D = (glb_f64 *)w.D;
     glb_f64 *rowr_g = D + (size_t)r * ld;
     MLD_CHECK(w, r >= 0 && r < m && c >= 0 && c < n && m <= w.mcap, 101, r, c);
-    const bool sync_r5 = (w.dbg & MLD_DBG_PIVOT_SYNC_R5) != 0;      // the three barriers this function no longer needs (below), kept selectable
+    const bool sync_r5 = LEG && (w.dbg & MLD_DBG_PIVOT_SYNC_R5) != 0;      // the three barriers this function no longer needs (below), kept selectable (legacy instantiation)
     __syncthreads();
     // stage multiplier column and the pivot row in LDS (raw first: the pivot element goes to sh.piv_el)
     if (!SECOND) {   // (rows that can never bind are not maintained: multiplier 0.)  All loads of both gathers are issued before the first LDS store: the
@@ -1399,6 +1592,7 @@ __device__ __forceinline__ void s_pivot_head(const Ws &w, Shared &sh, int r, int
 
 // Second half of a pivot whose first half s_pivot_head<L, false> has staged in w.rowr / w.colc: rows with a non-zero multiplier -= multiplier * (scaled pivot row) on
 // the row's active sectors
+template <bool LEG>
 __device__ __forceinline__ void s_pivot_update(const Ws &w, Shared &sh, int r, int c, long long tp0)
 {
     const int n = w.n, ld = w.ld, m = sh.m, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -1415,7 +1609,7 @@ __device__ __forceinline__ void s_pivot_update(const Ws &w, Shared &sh, int r, i
 #ifdef MLD_PIVOT_PROF
     long long tq2;
 #endif
-    if (!(w.dbg & MLD_DBG_PIVOT_SYNC_R5) && nsec <= SOL_NT && m <= LIST_NCH * SOL_NT) {      // one exchange for all chunks (list_counts)
+    if (!(LEG && (w.dbg & MLD_DBG_PIVOT_SYNC_R5)) && nsec <= SOL_NT && m <= LIST_NCH * SOL_NT) {      // one exchange for all chunks (list_counts)
         const unsigned long long before = (1ull << lane) - 1ull;
         bool act = false;
         if (tid < nsec) {
@@ -1479,12 +1673,23 @@ __device__ __forceinline__ void s_pivot_update(const Ws &w, Shared &sh, int r, i
 #endif
     {
         const int ngrp = (nact + SOL_SPW - 1) / SOL_SPW;
-        for (int g0 = 0; g0 < ngrp; g0 += 4) {
-            switch (ngrp - g0) {
-            case 1: s_update_rows<1>(D, ld, rowr, colc, rowlist, seclist, nrows, nact, g0, c, wave, lane); break;
-            case 2: s_update_rows<2>(D, ld, rowr, colc, rowlist, seclist, nrows, nact, g0, c, wave, lane); break;
-            case 3: s_update_rows<3>(D, ld, rowr, colc, rowlist, seclist, nrows, nact, g0, c, wave, lane); break;
-            default: s_update_rows<4>(D, ld, rowr, colc, rowlist, seclist, nrows, nact, g0, c, wave, lane); break;
+        if (MLD_UPDATE_LEGACY_ALWAYS || (LEG && (w.dbg & MLD_DBG_UPDATE_R7))) {      // the update as it was (legacy instantiation)
+            for (int g0 = 0; g0 < ngrp; g0 += 4) {
+                switch (ngrp - g0) {
+                case 1: s_update_rows<1>(D, ld, rowr, colc, rowlist, seclist, nrows, nact, g0, c, wave, lane); break;
+                case 2: s_update_rows<2>(D, ld, rowr, colc, rowlist, seclist, nrows, nact, g0, c, wave, lane); break;
+                case 3: s_update_rows<3>(D, ld, rowr, colc, rowlist, seclist, nrows, nact, g0, c, wave, lane); break;
+                default: s_update_rows<4>(D, ld, rowr, colc, rowlist, seclist, nrows, nact, g0, c, wave, lane); break;
+                }
+            }
+        } else {
+            for (int g0 = 0; g0 < ngrp; g0 += 4) {
+                switch (ngrp - g0) {
+                case 1: s_update_rows_r7<1>(D, ld, rowr, colc, rowlist, seclist, nrows, nact, g0, c, wave, lane); break;
+                case 2: s_update_rows_r7<2>(D, ld, rowr, colc, rowlist, seclist, nrows, nact, g0, c, wave, lane); break;
+                case 3: s_update_rows_r7<3>(D, ld, rowr, colc, rowlist, seclist, nrows, nact, g0, c, wave, lane); break;
+                default: s_update_rows_r7<4>(D, ld, rowr, colc, rowlist, seclist, nrows, nact, g0, c, wave, lane); break;
+                }
             }
         }
     }
@@ -1500,16 +1705,16 @@ __device__ __forceinline__ void s_pivot_update(const Ws &w, Shared &sh, int r, i
 }
 
 // the rank-1 update: entering column c, leaving row r, leaving variable goes to leave_value
-template <bool L>
+template <bool L, bool LEG>
 __device__ __forceinline__ void s_pivot_inl(const Ws &w, Shared &sh, int r, int c, double leave_value)
 {
     const long long tp0 = wall_clock64();
-    s_pivot_head<L, false>(w, sh, r, c, leave_value, (lds_f64 *)w.rowr, (lds_f64 *)w.colc, -1, -1);
-    s_pivot_update(w, sh, r, c, tp0);
+    s_pivot_head<L, false, LEG>(w, sh, r, c, leave_value, (lds_f64 *)w.rowr, (lds_f64 *)w.colc, -1, -1);
+    s_pivot_update<LEG>(w, sh, r, c, tp0);
 }
 
-// out-of-line copy for the cold callers (refactor, primal simplex)
-__device__ __noinline__ void s_pivot(const Ws &w, Shared &sh, int r, int c, double leave_value) { s_pivot_inl<false>(w, sh, r, c, leave_value); }
+// out-of-line copy for the cold callers (refactor, primal simplex): it keeps every selectable variant (MLD_DBG_PIVOT_SYNC_R5, MLD_DBG_UPDATE_R7)
+__device__ __noinline__ void s_pivot(const Ws &w, Shared &sh, int r, int c, double leave_value) { s_pivot_inl<false, true>(w, sh, r, c, leave_value); }
 
 // structural values (scaled space) into w.tmpx
 __device__ void s_gather_x(const Ws &w, Shared &sh, double *x)
@@ -1600,7 +1805,7 @@ __device__ void s_place_all(const Ws &w)
     __syncthreads();
 }
 
-__device__ void s_refactor(const Ws &w, Shared &sh)
+__device__ __noinline__ void s_refactor(const Ws &w, Shared &sh)      // (out of line: no plain pivot runs it)
 {
     const int n = w.n, m = sh.m, ld = w.ld, tid = threadIdx.x;
     __syncthreads();
@@ -1693,12 +1898,16 @@ __device__ void s_refactor(const Ws &w, Shared &sh)
 }
 
 // bounded dual simplex with Harris ratio test and Bland fallback; all threads return the same status
-template <bool L, bool R6> __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double cutoff, int max_pivots);
-// (R6 = MLD_DBG_SELECT_R6: the loop with its earlier selection is an instantiation of its own, so that neither carries the other's instructions)
+template <bool L, bool R6, bool LEG> __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double cutoff, int max_pivots);
+// (R6 = MLD_DBG_SELECT_R6: the loop with its earlier selection is an instantiation of its own, so that neither carries the other's instructions.
+// LEG: the legacy instantiations, taken whenever MLD_DBG_PIVOT_SYNC_R5, MLD_DBG_SELECT_R6 or MLD_DBG_UPDATE_R7 is set, hold the earlier barriers, lists and
+// row updates and choose among them at run time; the default one holds none of them -- the loop carries only the text it runs.)
+#define MLD_DBG_LEGACY_LOOP (MLD_DBG_PIVOT_SYNC_R5 | MLD_DBG_SELECT_R6 | MLD_DBG_UPDATE_R7)
 __device__ __forceinline__ int s_dual_simplex_pick(const Ws &w, Shared &sh, double cutoff, int max_pivots)
 {
-    if (w.dbg & MLD_DBG_SELECT_R6) return w.all_lds ? s_dual_simplex_impl<true, true>(w, sh, cutoff, max_pivots) : s_dual_simplex_impl<false, true>(w, sh, cutoff, max_pivots);
-    return w.all_lds ? s_dual_simplex_impl<true, false>(w, sh, cutoff, max_pivots) : s_dual_simplex_impl<false, false>(w, sh, cutoff, max_pivots);
+    if (w.dbg & MLD_DBG_SELECT_R6) return w.all_lds ? s_dual_simplex_impl<true, true, true>(w, sh, cutoff, max_pivots) : s_dual_simplex_impl<false, true, true>(w, sh, cutoff, max_pivots);
+    if (w.dbg & MLD_DBG_LEGACY_LOOP) return w.all_lds ? s_dual_simplex_impl<true, false, true>(w, sh, cutoff, max_pivots) : s_dual_simplex_impl<false, false, true>(w, sh, cutoff, max_pivots);
+    return w.all_lds ? s_dual_simplex_impl<true, false, false>(w, sh, cutoff, max_pivots) : s_dual_simplex_impl<false, false, false>(w, sh, cutoff, max_pivots);
 }
 __device__ int s_dual_simplex(const Ws &w, Shared &sh, double cutoff, int max_pivots)
 {
@@ -1731,7 +1940,7 @@ __device__ int s_primal_simplex(const Ws &w, Shared &sh, int max_pivots);
 // pivots were Bland pivots, one cut round of one instance took 2 200 of them; 0.4 % with the perturbation).  When the perturbed problem is
 // optimal the true cost row is restored (s_reprice) and, if some reduced cost then has the wrong sign, the bounded primal simplex finishes
 // from this primal-feasible basis.
-__device__ void s_perturb_costs(const Ws &w, Shared &sh)
+__device__ __noinline__ void s_perturb_costs(const Ws &w, Shared &sh)      // (out of line: once per solve at most)
 {
     const int n = w.n;
     double *d = w.dcost;
@@ -1749,7 +1958,7 @@ __device__ void s_perturb_costs(const Ws &w, Shared &sh)
     __syncthreads();
 }
 
-__device__ int s_unperturb(const Ws &w, Shared &sh, int st, int max_pivots)
+__device__ __noinline__ int s_unperturb(const Ws &w, Shared &sh, int st, int max_pivots)      // (out of line: the loop's five ways out)
 {
     __syncthreads();
     if (!sh.perturbed) return st;
@@ -1876,16 +2085,17 @@ __device__ __forceinline__ bool s_look_ahead(const Ws &w, Shared &sh, int r1, in
 // left pending: on return the dictionary is fully updated.  Whatever the loop would do between the two pivots besides counting a stall -- a limit, the deadline, a
 // verification, the perturbation, Bland's rule -- means no pair: the first pivot is finished alone (s_pivot_update) and the loop goes on unchanged.  cur, stall and
 // last_obj leave as two iterations would leave them.
-template <bool L, bool R6>
+template <bool LEG> __device__ __forceinline__ void s_pair_update(const Ws &w, Shared &sh, int r1, int c1, int r2, int c2, long long tp0);
+template <bool L, bool R6, bool LEG>
 __device__ __forceinline__ void s_pivot_pair(const Ws &w, Shared &sh, int r1, int c1, double lv1, bool try_pair, double cutoff, int max_pivots, double &cur,
                                              int &stall, double &last_obj, int &par)
 {
     const long long tp0 = wall_clock64();
-    const int n = w.n, ld = w.ld, m = sh.m, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int n = w.n, tid = threadIdx.x;
     const int nsec = (n + SOL_SEC) / SOL_SEC;
     lds_f64 *rowr = (lds_f64 *)w.rowr, *colc = (lds_f64 *)w.colc, *rowr2 = (lds_f64 *)w.rowr2, *colc2 = (lds_f64 *)w.colc2;
     lds_u8 *secflag = (lds_u8 *)w.secflag;
-    s_pivot_head<L, false>(w, sh, r1, c1, lv1, rowr, colc, -1, -1);
+    s_pivot_head<L, false, LEG>(w, sh, r1, c1, lv1, rowr, colc, -1, -1);
     cur += sh.s_d[0];
     // the top of the loop's next iteration
     const int piv = sh.pivots;
@@ -1903,10 +2113,22 @@ __device__ __forceinline__ void s_pivot_pair(const Ws &w, Shared &sh, int r1, in
         }
         go = s_look_ahead<L, R6>(w, sh, r1, c1, cur, cutoff, par, r2, c2, lv2);
     }
-    if (!go) { s_pivot_update(w, sh, r1, c1, tp0); return; }
+    if (!go) { s_pivot_update<LEG>(w, sh, r1, c1, tp0); return; }
     stall = stall2; last_obj = last2;
-    s_pivot_head<L, true>(w, sh, r2, c2, lv2, rowr2, colc2, r1, c1);
+    s_pivot_head<L, true, LEG>(w, sh, r2, c2, lv2, rowr2, colc2, r1, c1);
     cur += sh.s_d[0];
+    s_pair_update<LEG>(w, sh, r1, c1, r2, c2, tp0);
+}
+
+// The one pass of a pair: both first halves have run -- rows r1 and r2 and their multiplier columns are staged in w.rowr / w.colc and w.rowr2 / w.colc2, and
+// w.secflag bit 0 marks the first row's active sectors.  Builds the union lists and applies both updates in order (s_update_rows2_r7).
+template <bool LEG>
+__device__ __forceinline__ void s_pair_update(const Ws &w, Shared &sh, int r1, int c1, int r2, int c2, long long tp0)
+{
+    const int n = w.n, ld = w.ld, m = sh.m, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int nsec = (n + SOL_SEC) / SOL_SEC;
+    lds_f64 *rowr = (lds_f64 *)w.rowr, *colc = (lds_f64 *)w.colc, *rowr2 = (lds_f64 *)w.rowr2, *colc2 = (lds_f64 *)w.colc2;
+    lds_u8 *secflag = (lds_u8 *)w.secflag;
 #ifdef MLD_PIVOT_PROF
     const long long tq1 = wall_clock64();
     long long tq2;
@@ -1914,7 +2136,7 @@ __device__ __forceinline__ void s_pivot_pair(const Ws &w, Shared &sh, int r1, in
     // union of the two rows' active sectors and of the two row sets (ordered); the counts of each set and of the overlaps (s1, s2, s12 sectors; n1, n2, n12 rows)
     int nact = 0, nrows = 0;
     unsigned long long s1, s2, s12, n1, n2, n12;
-    if (!(w.dbg & MLD_DBG_PIVOT_SYNC_R5) && nsec <= SOL_NT && m <= LIST_NCH * SOL_NT) {      // one exchange for all chunks and all six counts (list_counts)
+    if (!(LEG && (w.dbg & MLD_DBG_PIVOT_SYNC_R5)) && nsec <= SOL_NT && m <= LIST_NCH * SOL_NT) {      // one exchange for all chunks and all six counts (list_counts)
         const unsigned long long before = (1ull << lane) - 1ull;
         int f = 0;
         if (tid < nsec) {
@@ -2001,12 +2223,23 @@ __device__ __forceinline__ void s_pivot_pair(const Ws &w, Shared &sh, int r1, in
     {
         glb_f64 *D = (glb_f64 *)w.D;
         const int ngrp = (nact + SOL_SPW - 1) / SOL_SPW;
-        for (int g0 = 0; g0 < ngrp; g0 += 4) {
-            switch (ngrp - g0) {
-            case 1: s_update_rows2<1>(D, ld, rowr, colc, rowr2, colc2, rowlist, seclist, secflag, nrows, nact, g0, r1, c1, c2, wave, lane); break;
-            case 2: s_update_rows2<2>(D, ld, rowr, colc, rowr2, colc2, rowlist, seclist, secflag, nrows, nact, g0, r1, c1, c2, wave, lane); break;
-            case 3: s_update_rows2<3>(D, ld, rowr, colc, rowr2, colc2, rowlist, seclist, secflag, nrows, nact, g0, r1, c1, c2, wave, lane); break;
-            default: s_update_rows2<4>(D, ld, rowr, colc, rowr2, colc2, rowlist, seclist, secflag, nrows, nact, g0, r1, c1, c2, wave, lane); break;
+        if (MLD_UPDATE_LEGACY_ALWAYS || (LEG && (w.dbg & MLD_DBG_UPDATE_R7))) {      // the update as it was (legacy instantiation)
+            for (int g0 = 0; g0 < ngrp; g0 += 4) {
+                switch (ngrp - g0) {
+                case 1: s_update_rows2<1>(D, ld, rowr, colc, rowr2, colc2, rowlist, seclist, secflag, nrows, nact, g0, r1, c1, c2, wave, lane); break;
+                case 2: s_update_rows2<2>(D, ld, rowr, colc, rowr2, colc2, rowlist, seclist, secflag, nrows, nact, g0, r1, c1, c2, wave, lane); break;
+                case 3: s_update_rows2<3>(D, ld, rowr, colc, rowr2, colc2, rowlist, seclist, secflag, nrows, nact, g0, r1, c1, c2, wave, lane); break;
+                default: s_update_rows2<4>(D, ld, rowr, colc, rowr2, colc2, rowlist, seclist, secflag, nrows, nact, g0, r1, c1, c2, wave, lane); break;
+                }
+            }
+        } else {
+            for (int g0 = 0; g0 < ngrp; g0 += 4) {
+                switch (ngrp - g0) {
+                case 1: s_update_rows2_r7<1>(D, ld, rowr, colc, rowr2, colc2, rowlist, seclist, secflag, nrows, nact, g0, r1, c1, c2, wave, lane); break;
+                case 2: s_update_rows2_r7<2>(D, ld, rowr, colc, rowr2, colc2, rowlist, seclist, secflag, nrows, nact, g0, r1, c1, c2, wave, lane); break;
+                case 3: s_update_rows2_r7<3>(D, ld, rowr, colc, rowr2, colc2, rowlist, seclist, secflag, nrows, nact, g0, r1, c1, c2, wave, lane); break;
+                default: s_update_rows2_r7<4>(D, ld, rowr, colc, rowr2, colc2, rowlist, seclist, secflag, nrows, nact, g0, r1, c1, c2, wave, lane); break;
+                }
             }
         }
     }
@@ -2022,7 +2255,83 @@ __device__ __forceinline__ void s_pivot_pair(const Ws &w, Shared &sh, int r1, in
     __syncthreads();
 }
 
-template <bool L, bool R6>
+// Blocks of the loop of s_dual_simplex_impl that a plain pivot does not run, out of line, so that the text a plain pivot fetches lies together.
+// (1) The verification of the dictionary against the original rows, with a refactorisation if it has drifted past `tol` (four sites: every 512 pivots, at an
+// optimum, before a cutoff is believed, before a small violation without an eligible entry is).  pre_barrier: every wave must have read sh.since_check before
+// thread 0 resets it.  True when the dictionary was rebuilt (the skip marks are cleared; the caller recomputes the objective and starts the iteration again).
+template <bool L>
+__device__ __noinline__ bool s_loop_verify(const Ws &w, Shared &sh, double tol, bool pre_barrier, bool dbg_decides)
+{
+    HOT_VIEW(L, w);
+    const int tid = threadIdx.x;
+    const long long tr0 = wall_clock64();
+    if (pre_barrier) __syncthreads();
+    if (tid == 0) sh.since_check = 0;
+    bool bad = s_check_residual(w, sh) > tol;
+    if (dbg_decides) {
+        if (w.dbg & MLD_DBG_REFACTOR_ALWAYS) bad = true;       // diagnostics: refactor at every check
+        if (w.dbg & MLD_DBG_REFACTOR_NEVER) bad = false;      // diagnostics: never refactor
+    }
+    if (bad) s_refactor(w, sh);
+    __syncthreads();
+    if (tid == 0) sh.prof[5] += wall_clock64() - tr0;
+    if (bad) for (int i = tid; i < w.mcap; i += SOL_NT) h_skip[i] &= 2;
+    return bad;
+}
+// (2) The flips of the long-step ratio test: the columns marked by dal[c] == -2.0 move to their other bounds.  (The test's group loop stays in the loop: more
+// than a third of the root LP's pivots go through it; flips are what few of them end in.)
+template <bool L>
+__device__ __noinline__ void s_loop_flips(const Ws &w, Shared &sh, int cbest, lds_f64 *ea, lds_f64 *dal)
+{
+    HOT_VIEW(L, w);
+    const int n = w.n, ld = w.ld, m = sh.m, tid = threadIdx.x;
+    // move the passed variables to their other bounds: x_B -= sum_f D[:, c_f] * (new - old), then the bookkeeping of the columns
+    __syncthreads();
+    if (tid == 0 && dal[cbest] == -2.0) dal[cbest] = 0.0;     // (the entering column itself is never flipped)
+    __syncthreads();
+    int nF = 0;
+    for (int c0 = 0; c0 < n; c0 += SOL_NT) {
+        const int c = c0 + tid;
+        nF = block_compact(sh, c < n && dal[c] == -2.0, (unsigned short)c, w.seclist, nF);
+    }
+    __syncthreads();
+    MLD_MARK(w, sh, 5000 + nF);
+    MLD_CHECK(w, nF <= n && nF <= (int)(w.rowlist - w.seclist), 107, nF, cbest);
+#ifdef MLD_ASSERT
+    for (int f = tid; f < nF; f += SOL_NT) MLD_CHECK(w, (int)w.seclist[f] < n, 108, f, w.seclist[f]);
+#endif
+    lds_f64 *dlt = ea;                                        // step of each flipped column (the staged |a| are not needed any more: n + 2 doubles)
+    for (int f = tid; f < nF; f += SOL_NT) {
+        const int c = w.seclist[f], j = h_nonbasic[c];
+        dlt[f] = (h_up[c] ? h_lo[j] : h_hi[j]) - h_xN[c];
+    }
+    __syncthreads();
+    const glb_f64 *Dg = (const glb_f64 *)w.D;
+    for (int i = tid; i < m; i += SOL_NT) {
+        if (h_skip[i] & 2) continue;                          // rows that are not maintained
+        double acc = 0.0;
+        int f = 0;
+        for (; f + 4 <= nF; f += 4) {
+            double v[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = Dg[(size_t)i * ld + w.seclist[f + q]];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc += v[q] * dlt[f + q];
+        }
+        for (; f < nF; ++f) acc += Dg[(size_t)i * ld + w.seclist[f]] * dlt[f];
+        h_xB[i] -= acc;
+    }
+    __syncthreads();
+    for (int f = tid; f < nF; f += SOL_NT) {
+        const int c = w.seclist[f], j = h_nonbasic[c];
+        const bool up = h_up[c];
+        h_xN[c] = up ? h_lo[j] : h_hi[j];
+        h_up[c] = !up;
+    }
+    __syncthreads();
+}
+
+template <bool L, bool R6, bool LEG>
 __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double cutoff, int max_pivots)
 {
     HOT_VIEW(L, w);
@@ -2052,18 +2361,11 @@ __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double 
         }
         const int since = sh.since_check;
         if (since >= 512) {   // a long solve never reaches the verification at an optimum: verify on the way
-            const long long tr0 = wall_clock64();
             // Every wave must have READ sh.since_check before thread 0 resets it (round 4: this barrier was missing -- a wave that arrived late read 0,
             // skipped this block while the others ran its barriers, and the workgroup went on desynchronised: reductions over half-written buffers, a
             // leaving row of -1 or a stale column index used as a row.  The one write-after-read hazard on a shared scalar the audit of DESIGN section 4e
             // found; the other three resets below sit behind a barrier of their own.)
-            __syncthreads();
-            if (tid == 0) sh.since_check = 0;
-            const bool bad = s_check_residual(w, sh) > S_RESID_TOL;
-            if (bad) s_refactor(w, sh);
-            __syncthreads();
-            if (tid == 0) sh.prof[5] += wall_clock64() - tr0;
-            if (bad) { for (int i = tid; i < w.mcap; i += SOL_NT) h_skip[i] &= 2; fresh_obj = true; continue; }
+            if (s_loop_verify<L>(w, sh, S_RESID_TOL, true, false)) { fresh_obj = true; continue; }
         }
         if (fresh_obj) { cur = s_objective(w, sh); fresh_obj = false; }
         if (cur > last_obj + 1e-12 * fmax(1.0, fabs(cur))) { stall = 0; last_obj = cur; } else stall++;
@@ -2089,19 +2391,7 @@ __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double 
         if (r < 0) {
 
             if (since >= 64) {
-                const long long tr0 = wall_clock64();
-                if (tid == 0) sh.since_check = 0;
-                bool bad = s_check_residual(w, sh) > S_RESID_TOL;
-                if (w.dbg & MLD_DBG_REFACTOR_ALWAYS) bad = true;       // diagnostics: refactor at every check
-                if (w.dbg & MLD_DBG_REFACTOR_NEVER) bad = false;      // diagnostics: never refactor
-                if (bad) s_refactor(w, sh);
-                __syncthreads();
-                if (tid == 0) sh.prof[5] += wall_clock64() - tr0;
-                if (bad) {
-                    for (int i = tid; i < w.mcap; i += SOL_NT) h_skip[i] &= 2;
-                    fresh_obj = true;
-                    continue;
-                }
+                if (s_loop_verify<L>(w, sh, S_RESID_TOL, false, true)) { fresh_obj = true; continue; }      // (diagnostics: MLD_DBG_REFACTOR_ALWAYS / _NEVER decide here)
             }
             return s_unperturb(w, sh, LP_OPTIMAL, max_pivots);
         }
@@ -2110,14 +2400,7 @@ __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double 
         if (cur >= cutoff && !sh.perturbed) {
             // a cutoff is a claim about the bound: verify the dictionary first if it has moved since the last check
             if (since >= 64) {
-                const long long tr0 = wall_clock64();
-                __syncthreads();
-                if (tid == 0) sh.since_check = 0;
-                const bool bad = s_check_residual(w, sh) > S_RESID_TOL;
-                if (bad) s_refactor(w, sh);
-                __syncthreads();
-                if (tid == 0) sh.prof[5] += wall_clock64() - tr0;
-                if (bad) { for (int i = tid; i < w.mcap; i += SOL_NT) h_skip[i] &= 2; fresh_obj = true; continue; }
+                if (s_loop_verify<L>(w, sh, S_RESID_TOL, true, false)) { fresh_obj = true; continue; }
             }
             return LP_CUTOFF;
         }
@@ -2171,18 +2454,7 @@ __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double 
                 // a SMALL violation without an eligible entry may be accumulated error (a degenerate basic variable drifting
                 // off its bound) rather than infeasibility: if the dictionary's discrepancy against the original rows is of
                 // the violation's size, re-derive it before believing the row.
-                const long long tr0 = wall_clock64();
-                __syncthreads();
-                if (tid == 0) sh.since_check = 0;
-                const bool bad = s_check_residual(w, sh) > 0.1 * viol;
-                if (bad) s_refactor(w, sh);
-                __syncthreads();
-                if (tid == 0) sh.prof[5] += wall_clock64() - tr0;
-                if (bad) {
-                    for (int i = tid; i < w.mcap; i += SOL_NT) h_skip[i] &= 2;
-                    fresh_obj = true;
-                    continue;
-                }
+                if (s_loop_verify<L>(w, sh, 0.1 * viol, true, false)) { fresh_obj = true; continue; }
             }
             return s_unperturb(w, sh, LP_INFEASIBLE, max_pivots);
         }
@@ -2245,51 +2517,8 @@ __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double 
                 if (tm == S_INF) break;                           // every breakpoint passed: the last group's largest entry enters after all
             }
             if (cbest >= 0 && nflip_groups > 0) {
-                // move the passed variables to their other bounds: x_B -= sum_f D[:, c_f] * (new - old), then the bookkeeping of the columns
-                __syncthreads();
-                if (tid == 0 && dal[cbest] == -2.0) dal[cbest] = 0.0;     // (the entering column itself is never flipped)
-                __syncthreads();
-                int nF = 0;
-                for (int c0 = 0; c0 < n; c0 += SOL_NT) {
-                    const int c = c0 + tid;
-                    nF = block_compact(sh, c < n && dal[c] == -2.0, (unsigned short)c, w.seclist, nF);
-                }
-                __syncthreads();
-                MLD_MARK(w, sh, 5000 + nF);
-                MLD_CHECK(w, nF <= n && nF <= (int)(w.rowlist - w.seclist), 107, nF, cbest);
-#ifdef MLD_ASSERT
-                for (int f = tid; f < nF; f += SOL_NT) MLD_CHECK(w, (int)w.seclist[f] < n, 108, f, w.seclist[f]);
-#endif
-                lds_f64 *dlt = ea;                                        // step of each flipped column (the staged |a| are not needed any more: n + 2 doubles)
-                for (int f = tid; f < nF; f += SOL_NT) {
-                    const int c = w.seclist[f], j = h_nonbasic[c];
-                    dlt[f] = (h_up[c] ? h_lo[j] : h_hi[j]) - h_xN[c];
-                }
-                __syncthreads();
-                const glb_f64 *Dg = (const glb_f64 *)w.D;
-                for (int i = tid; i < m; i += SOL_NT) {
-                    if (h_skip[i] & 2) continue;                          // rows that are not maintained
-                    double acc = 0.0;
-                    int f = 0;
-                    for (; f + 4 <= nF; f += 4) {
-                        double v[4];
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) v[q] = Dg[(size_t)i * ld + w.seclist[f + q]];
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) acc += v[q] * dlt[f + q];
-                    }
-                    for (; f < nF; ++f) acc += Dg[(size_t)i * ld + w.seclist[f]] * dlt[f];
-                    h_xB[i] -= acc;
-                }
-                __syncthreads();
-                for (int f = tid; f < nF; f += SOL_NT) {
-                    const int c = w.seclist[f], j = h_nonbasic[c];
-                    const bool up = h_up[c];
-                    h_xN[c] = up ? h_lo[j] : h_hi[j];
-                    h_up[c] = !up;
-                }
+                s_loop_flips<L>(w, sh, cbest, ea, dal);      // (out of line: the passed variables move to their other bounds)
                 fresh_obj = true;                                         // the flips moved the objective: recompute it at the next iteration
-                __syncthreads();
             }
 #ifdef MLD_PIVOT_PROF
             if (tid == 0) { sh.pcnt[2] += wall_clock64() - tl0; sh.pcnt[3]++; sh.pcnt[4] += ngroups; sh.pcnt[5] += nflip_groups; sh.pcnt[6] += (cbest >= 0 && nflip_groups > 0); }
@@ -2319,7 +2548,7 @@ __device__ __noinline__ int s_dual_simplex_impl(const Ws &w, Shared &sh, double 
         }
         // the pivot, and the next one with it where both are plain (devex pricing and Harris test: not under Bland's rule, not in the root LP's long-step test, not with
         // a quadratic cost) and the shape has the LDS for it
-        s_pivot_pair<L, R6>(w, sh, r, cbest, below ? h_lo[jr] : h_hi[jr], L && w.pair && !bland && !long_step && !w.P, cutoff, max_pivots, cur, stall, last_obj, par);
+        s_pivot_pair<L, R6, LEG>(w, sh, r, cbest, below ? h_lo[jr] : h_hi[jr], L && w.pair && !bland && !long_step && !w.P, cutoff, max_pivots, cur, stall, last_obj, par);
     }
 }
 
@@ -4779,4 +5008,41 @@ __global__ void __launch_bounds__(SOL_NT) k_debug_reduce(const double *v, const 
         max2[2 * b] = m0; max2[2 * b + 1] = m1; arg2[2 * b] = a0; arg2[2 * b + 1] = a1; val2[2 * b] = o0; val2[2 * b + 1] = o1;
         max2[2 * gridDim.x + 2 * b] = n0; max2[2 * gridDim.x + 2 * b + 1] = n1;
     }
+}
+
+// Diagnostics (mld_debug_update_rows): the rows' update of ONE pivot (pair == 0) or of a fused pair on a caller-supplied dictionary D (m x ld) with the staged
+// rows and multiplier columns the caller gives -- the lists are built and the update runs through s_pivot_update / s_pair_update themselves: the templates the
+// default loop runs or, with MLD_DBG_UPDATE_R7 (and MLD_DBG_PIVOT_SYNC_R5) in dbg, the earlier ones.  One workgroup; rows_out = the (row, sector) pairs accounted.
+#define DBG_UPD_MAX 1024      // rows and leading dimension the static LDS of this kernel holds
+__global__ void __launch_bounds__(SOL_NT) k_debug_update(double *D, int m, int n, int ld, const double *rowr1, const double *colc1, int r1, int c1,
+                                                         const double *rowr2, const double *colc2, int r2, int c2, int pair, int dbg, unsigned long long *rows_out)
+{
+    __shared__ Shared sh;
+    __shared__ double s_rowr[2][DBG_UPD_MAX + 8], s_colc[2][DBG_UPD_MAX + 8];
+    __shared__ unsigned short s_sec[2][DBG_UPD_MAX / SOL_SEC + 8], s_row[2][DBG_UPD_MAX + 8];
+    __shared__ unsigned char s_flag[DBG_UPD_MAX / SOL_SEC + 8];
+    const int tid = threadIdx.x;
+    Ws w = {};
+    w.D = D; w.n = n; w.ld = ld; w.mcap = m; w.m0 = m; w.dbg = dbg;
+    w.rowr = s_rowr[0]; w.colc = s_colc[0]; w.seclist = s_sec[0]; w.rowlist = s_row[0];
+    w.rowr2 = s_rowr[1]; w.colc2 = s_colc[1]; w.seclist2 = s_sec[1]; w.rowlist2 = s_row[1]; w.secflag = s_flag; w.pair = pair;
+    if (tid == 0) { sh.m = m; sh.rows = 0ull; sh.prof[0] = 0; }
+    for (int k = tid; k < ld; k += SOL_NT) { s_rowr[0][k] = k <= n ? rowr1[k] : 0.0; s_rowr[1][k] = (pair && k <= n) ? rowr2[k] : 0.0; }      // (the last sector's padding: 0)
+    for (int i = tid; i < m; i += SOL_NT) { s_colc[0][i] = colc1[i]; if (pair) s_colc[1][i] = colc2[i]; }
+    __syncthreads();
+    const long long tp0 = wall_clock64();
+    if (pair) {
+        for (int t = tid; t < (n + SOL_SEC) / SOL_SEC; t += SOL_NT) {      // active sectors of the first pivot's row (as s_pivot_pair marks them)
+            bool act = false;
+#pragma unroll
+            for (int e = 0; e < SOL_SEC; ++e) { const int k = t * SOL_SEC + e; if (k <= n && s_rowr[0][k] != 0.0) act = true; }
+            s_flag[t] = act ? 1 : 0;
+        }
+        __syncthreads();
+        s_pair_update<true>(w, sh, r1, c1, r2, c2, tp0);      // (the instantiation that chooses by w.dbg: without a bit it runs what the default loop runs)
+    } else {
+        s_pivot_update<true>(w, sh, r1, c1, tp0);
+    }
+    __syncthreads();
+    if (tid == 0) *rows_out = sh.rows;
 }

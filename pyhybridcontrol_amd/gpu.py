@@ -1163,3 +1163,42 @@ class GpuProblem(object):
                                         mi.ctypes.data_as(C.POINTER(C.c_int32)) if mi is not None else None,
                                         _lib.dptr(x0) if d["nx"] else None, _lib.dptr(omega) if self.nW else None, _lib.dptr(h)))
         return h
+
+
+def debug_update_shape():
+    """diagnostics: the row-block sizes of k_solve's row update (internal entry mld_debug_update_shape; no device needed) -- RB[k - 1] rows a wave takes at
+    a time when a chunk of the active sectors has k groups, and the constants of the sector grid"""
+    lib = _lib.load()
+    lib.mld_debug_update_shape.restype = C.c_int
+    lib.mld_debug_update_shape.argtypes = [C.POINTER(C.c_int32)]
+    out = (C.c_int32 * 8)()
+    check(lib.mld_debug_update_shape(out))
+    return dict(RB=[int(out[k]) for k in range(4)], waves=int(out[4]), sectors_per_group=int(out[5]), sector_doubles=int(out[6]), groups_per_chunk=int(out[7]))
+
+
+def debug_update_rows(D, n, rowr, colc, r, c, second=None, reserved=0):
+    """diagnostics: the rows' update of one pivot of k_solve -- or, with second = (rowr2, colc2, r2, c2), of a fused pair -- on the dictionary D (m x ld)
+    (internal entry mld_debug_update_rows).  rowr[n + 1] / colc[m]: the staged pivot row and multiplier column of pivot (r, c).  reserved = 0 runs the
+    default instantiation, _lib.MLD_DBG_UPDATE_R7 the earlier templates.  Returns (the updated copy of D, the (row, sector) pairs accounted)."""
+    lib = _lib.load()
+    dp = C.POINTER(C.c_double)
+    lib.mld_debug_update_rows.restype = C.c_int
+    lib.mld_debug_update_rows.argtypes = [dp, C.c_int, C.c_int, C.c_int, dp, dp, C.c_int, C.c_int, dp, dp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+    D = np.array(D, dtype=np.float64, order="C")
+    if D.ndim != 2:
+        raise ValueError("D must be a matrix (rows x ld)")
+    m, ld = D.shape
+    rowr, colc = _lib.as_f64(rowr), _lib.as_f64(colc)
+    if rowr.size != int(n) + 1 or colc.size != m:
+        raise ValueError("rowr needs n + 1 entries and colc one per row")
+    r2 = c2 = -1
+    rowr2 = colc2 = None
+    if second is not None:
+        rowr2, colc2, r2, c2 = second
+        rowr2, colc2 = _lib.as_f64(rowr2), _lib.as_f64(colc2)
+        if rowr2.size != int(n) + 1 or colc2.size != m:
+            raise ValueError("rowr2 needs n + 1 entries and colc2 one per row")
+    rows = C.c_int64(0)
+    check(lib.mld_debug_update_rows(_lib.dptr(D), m, ld, int(n), _lib.dptr(rowr), _lib.dptr(colc), int(r), int(c), _lib.dptr(rowr2), _lib.dptr(colc2),
+                                    int(r2), int(c2), int(reserved), C.byref(rows)))
+    return D, int(rows.value)
