@@ -660,6 +660,53 @@ int mld_sim_step_policy(mld_problem_t *p, mld_problem_t *aux, const double *u0, 
                         double *x_k1_out, double *y_out, uint8_t *cons_out, double *cons_vio_out, int32_t *cons_row_out,
                         double *v0_out, int32_t *aux_status_out, int32_t *n_skipped_out);
 
+/* ---- fallback inputs for instances without a usable plan ----------------------------------------------------------------------------------------------
+ * mld_advance_batch[2], mld_sim_step_batch(v0 = NULL) and mld_sim_step_resolve(u0 = NULL) do not advance an instance whose solve left no usable plan (status
+ * other than OPTIMAL / NODE_LIMIT, or no finite objective): its plant keeps its state while the clock and the profile windows move on for every instance.
+ * The reference never freezes a plant: solve_grid_mpc catches the solver's error, warns "Using last solution, will not be optimal" and goes on (examples/
+ * residential_mg_with_pv_and_dewhs/modelling/micro_grid_agents.py:728-735), and sim_step_k steps the plant with whatever variables_k.u holds (controllers/
+ * controller_base.py:229-253).  mld_sim_step_fallback is the resolving step with the source of u chosen per instance on the device.
+ *
+ * Plan memory  resident and opt-in (mld_plan_memory), owned by the resident batch like the policy state: mem_u (batch, N_tilde, nu) fp64 and mem_age (batch)
+ *             int32.  age = -1: nothing remembered; age = a >= 1: the remembered plan was made a advancing steps ago, so its row a is the input it planned for
+ *             NOW; age = N_tilde: exhausted.  (The reference re-applies the stale plan's step-0 input; row a is the receding-horizon-consistent choice.)
+ * Source of u  at a fallback step, the first that applies, per instance b:
+ *                0  PLAN     the plan is usable                                      the first nu entries of the resident plan's row
+ *                1  MEMORY   MLD_FB_MEMORY in fb and 1 <= age[b] <= N_tilde - 1      mem_u[b, age[b], :]
+ *                2  POLICY   MLD_FB_POLICY in fb                                     the resident policy's rule on the handle's current x0[b] and the resident
+ *                                                                                    u_prev[b] (the arithmetic and branch order of mld_sim_step_policy)
+ *               -1  NONE     none of the above                                       the instance is not attempted, exactly as an instance without a usable
+ *                                                                                    plan is by mld_sim_step_resolve(u0 = NULL)
+ *             An instance is attempted iff its source is >= 0.  From there on the step is mld_sim_step_resolve's own phases, unchanged: k_aux_inputs, the
+ *             resolver's solve, k_aux_merge, k_sim_step under the merged usable mask.  With fb == 0 the call is mld_sim_step_resolve(u0 = NULL) bit for bit,
+ *             and u_source is 0 or -1.
+ * Commit      only with MLD_SIM_ADVANCE, after the step has been queued without an error.  An enabled memory (whether or not fb names it): source 0 ->
+ *             mem_u[b, k, :] = the plan's u of step k for all k and age[b] = 1, whether or not the instance advanced; any other source with age[b] >= 1 ->
+ *             age[b] = min(age[b] + 1, N_tilde); age -1 stays -1.  A resident policy (whether or not fb names it): u_prev of every ADVANCED instance becomes
+ *             the u applied, whatever its source, so the rule's hysteresis state is right when it takes over.  Without MLD_SIM_ADVANCE nothing is written:
+ *             memory, u_prev and inputs all stay.  After an advancing step the handle is as after mld_sim_step_resolve(u0 = NULL): `advanced`.
+ * Validity    the memory is valid only along an unbroken chain of advancing fallback steps.  Every age goes back to -1 with mld_upload_batch,
+ *             mld_select_inputs, any call that replaces x0, and an advance through any other entry point (mld_advance_batch[2], mld_sim_step_batch,
+ *             mld_sim_step_resolve, mld_sim_step_policy); not with mld_forecast_from_profiles, a solve, mld_problem_set_cost or mld_upload_instance_cost.
+ * Outputs     as mld_sim_step_resolve, plus u_source_out (batch).
+ * MLD_SIM_LOG  the usual resolving record -- obj / lower_bound / status / nodes the plan's as they are --, and u_source in an int array (capacity, batch) that
+ *             the first fallback step that logs allocates, filled with -2 = "written by another entry point"; mld_sim_log_begin discards it.
+ *             mld_download_sim_log_source copies records [first, first + count).
+ * mld_plan_memory: enable != 0 allocates the memory and empties it (every age -1), 0 frees it; needs a resident batch.  mld_set_plan_memory seeds or restores
+ * it -- u (batch, N_tilde, nu) finite, age (batch) in {-1, 1 .. N_tilde}, either may be NULL (kept) --, mld_download_plan_memory reads it.
+ * MLD_ERR_INVALID before anything is queued, nothing changed on either handle: everything mld_sim_step_resolve(u0 = NULL) refuses (an unsolved or already
+ * advanced batch, a time-varying handle, a launched solve, the rules for aux); unknown fb bits; MLD_FB_MEMORY without an enabled memory; MLD_FB_POLICY
+ * without a resident policy or with one that passes a channel through (the message says why); nu == 0. */
+#define MLD_FB_MEMORY 1
+#define MLD_FB_POLICY 2
+int mld_plan_memory(mld_problem_t *, int enable);
+int mld_set_plan_memory(mld_problem_t *, const double *u, const int32_t *age);
+int mld_download_plan_memory(mld_problem_t *, double *u_out, int32_t *age_out);
+int mld_sim_step_fallback(mld_problem_t *, mld_problem_t *aux, int fb, const int64_t *act_start, int step, int flags,
+                          double *x_k1_out, double *y_out, uint8_t *cons_out, double *cons_vio_out, int32_t *cons_row_out,
+                          double *v0_out, int32_t *aux_status_out, int32_t *u_source_out, int32_t *n_skipped_out);
+int mld_download_sim_log_source(mld_problem_t *, int first, int count, int32_t *u_source);
+
 /* Per-instance telemetry of the last solve: time spent inside the solve kernel (device wall clock, ns) and
  * the number of dictionary rows the rank-1 updates touched (x *row_bytes x 2 = bytes streamed by pivots). */
 int mld_download_telemetry(mld_problem_t *, int64_t *latency_ns, int64_t *rows_updated, int64_t *row_bytes);

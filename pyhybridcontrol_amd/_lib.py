@@ -24,6 +24,7 @@ MLD_DBG_PIVOT_SYNC_R5 = 1 << 26        # mld_opts.reserved: k_solve's pivot with
 MLD_DBG_SELECT_R6 = 1 << 27            # mld_opts.reserved: k_solve's choice of (row, column) with its earlier block reductions (A/B, bit-identical results)
 MLD_DBG_UPDATE_R7 = 1 << 28            # mld_opts.reserved: k_solve's row updates as they were before a unit was cut down to its payload (A/B, bit-identical results)
 MLD_SIM_ADVANCE, MLD_SIM_ACTUAL, MLD_SIM_LOG = 1, 2, 4      # flags of mld_sim_step_batch / mld_sim_step_resolve
+MLD_FB_MEMORY, MLD_FB_POLICY = 1, 2                         # fb of mld_sim_step_fallback: the sources an instance without a usable plan may take its u from
 
 
 class MldGpuError(RuntimeError):
@@ -63,6 +64,7 @@ EXPORTS = ("mld_device_count", "mld_set_device", "mld_last_error", "mld_version"
            "mld_sim_log_begin", "mld_sim_log_count", "mld_sim_step_batch", "mld_download_sim_log",
            "mld_sim_step_resolve", "mld_download_sim_log_aux", "mld_rollout_batch",
            "mld_upload_policy", "mld_set_policy_state", "mld_download_policy_state", "mld_rollout_policy", "mld_sim_step_policy",
+           "mld_plan_memory", "mld_set_plan_memory", "mld_download_plan_memory", "mld_sim_step_fallback", "mld_download_sim_log_source",
            "mld_comm_unique_id", "mld_comm_init", "mld_gather", "mld_comm_destroy")
 
 
@@ -102,6 +104,11 @@ def load():
     lib.mld_download_policy_state.argtypes = [C.c_void_p, dp]
     lib.mld_rollout_policy.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, dp, dp, dp, lp, C.c_int, dp, C.c_int, dp, dp, dp, dp, ip, dp, dp, dp, ip, ip, ip, ip, lp]
     lib.mld_sim_step_policy.argtypes = list(lib.mld_sim_step_resolve.argtypes)
+    lib.mld_plan_memory.argtypes = [C.c_void_p, C.c_int]
+    lib.mld_set_plan_memory.argtypes = [C.c_void_p, dp, ip]
+    lib.mld_download_plan_memory.argtypes = [C.c_void_p, dp, ip]
+    lib.mld_sim_step_fallback.argtypes = [C.c_void_p, C.c_void_p, C.c_int, lp, C.c_int, C.c_int, dp, dp, bp, dp, ip, dp, ip, ip, ip]
+    lib.mld_download_sim_log_source.argtypes = [C.c_void_p, C.c_int, C.c_int, ip]
     if int(lib.mld_opts_size()) != C.sizeof(Opts):
         raise MldGpuError("libmldgpu.so was built with another layout of mld_opts (%d bytes, this binding %d): rebuild it (python -m pyhybridcontrol_amd.build)"
                           % (lib.mld_opts_size(), C.sizeof(Opts)))

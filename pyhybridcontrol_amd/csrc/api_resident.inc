@@ -624,10 +624,30 @@ static int aux_fold_check(const char *who, const char *what, const mld_problem_t
  *
  * policy (mld_sim_step_policy): the same phases with one kernel in front -- k_policy_inputs writes the ruled channels of u, from the handle's current x0, the
  * resident u_prev and the policy tables, into the buffer the phases read u0 from; u0 / the resident plan supply the passed-through channels only, and no plan
- * is needed when every channel is ruled.  After an advancing step the resident u_prev of every ADVANCED instance becomes the u applied (k_policy_commit). */
+ * is needed when every channel is ruled.  After an advancing step the resident u_prev of every ADVANCED instance becomes the u applied (k_policy_commit).
+ *
+ * fc (mld_sim_step_fallback, api_fallback.inc): the plan's step with one kernel in front -- k_fallback_inputs writes every instance's u from the first source
+ * that applies (plan, plan memory, policy), its u_source and its attempt byte, which replaces the plan_usable test of the phases (AuxStepArgs::attempt).
+ * After an advancing step k_policy_commit (a policy resident) and k_fallback_commit (a memory enabled) move the resident state on. */
+struct FallbackCall { int fb; int32_t *u_source_out; };
+
+/* the (cap, batch) int array beside the log that one kind of step fills (SimLog::aux, SimLog::src): allocated by the first such step that logs, -2 elsewhere */
+static int sim_log_side_array(mld_problem_t *p, DevBuf<int> &arr)
+{
+    if (arr) return MLD_OK;
+    const size_t len = (size_t)p->slog.cap * p->batch;
+    const hipStream_t sq = p->stream;
+    DevBuf<int> la;
+    HIP_TRY(la.alloc(len));
+    auto fill = [&]() -> int { HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)la.get(), -2, len, sq)); return MLD_OK; };
+    if (int rc = queue_and_wait(sq, fill)) return rc;
+    arr = std::move(la);
+    return MLD_OK;
+}
+
 static int sim_step_resolve_impl(const char *who, bool policy, mld_problem_t *p, mld_problem_t *aux, const double *u0, const int64_t *act_start, int step, int flags,
                                  double *x_k1_out, double *y_out, uint8_t *cons_out, double *cons_vio_out, int32_t *cons_row_out,
-                                 double *v0_out, int32_t *aux_status_out, int32_t *n_skipped_out)
+                                 double *v0_out, int32_t *aux_status_out, int32_t *n_skipped_out, const FallbackCall *fc = nullptr)
 {
     if (policy && !p->pol_on) { mld_set_error("%s: no policy uploaded (mld_upload_policy)", who); return MLD_ERR_INVALID; }
     const bool by_plan = !u0 && !(policy && p->pol_all_ruled);      /* some channel of u is the resident plan's */
@@ -640,20 +660,19 @@ static int sim_step_resolve_impl(const char *who, bool policy, mld_problem_t *p,
     if (u0) for (size_t k = 0; k < (size_t)batch * nu; ++k) if (!std::isfinite(u0[k])) {
         mld_set_error("%s: u0 of instance %zu, input %zu is not finite (%g)", who, k / nu, k % nu, u0[k]); return MLD_ERR_INVALID;
     }
-    if (!(flags & (MLD_SIM_ADVANCE | MLD_SIM_LOG)) && !x_k1_out && !y_out && !cons_out && !cons_vio_out && !cons_row_out && !v0_out && !aux_status_out && !n_skipped_out && !act_start) return MLD_OK;      /* nothing asked for */
+    if (!(flags & (MLD_SIM_ADVANCE | MLD_SIM_LOG)) && !x_k1_out && !y_out && !cons_out && !cons_vio_out && !cons_row_out && !v0_out && !aux_status_out && !n_skipped_out && !act_start && !(fc && fc->u_source_out)) return MLD_OK;      /* nothing asked for */
 
     const hipStream_t sq = p->stream;
     mld_problem::SimLog &L = p->slog;
-    if (log && !L.aux) {      /* every record so far was written by mld_sim_step_batch: "not resolved" */
-        DevBuf<int> la;
-        HIP_TRY(la.alloc((size_t)L.cap * batch));
-        auto fill = [&]() -> int { HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)la.get(), -2, (size_t)L.cap * batch, sq)); return MLD_OK; };
-        if (int rc = queue_and_wait(sq, fill)) return rc;
-        L.aux = std::move(la);
-    }
-    DevBuf<double> d_u, d_v0; DevBuf<unsigned char> d_mask; DevBuf<int> d_auxst; DevBuf<long long> d_start;
-    if (policy) { if (int rc = policy_state_ready(p, who)) return rc; }
-    if (u0 || policy) HIP_TRY(d_u.alloc((size_t)batch * std::max(1, nu)));
+    if (log) { if (int rc = sim_log_side_array(p, L.aux)) return rc; }      /* every record so far was written by mld_sim_step_batch: "not resolved" */
+    if (log && fc) { if (int rc = sim_log_side_array(p, L.src)) return rc; }
+    const size_t log_slot = log ? (size_t)L.count * batch : 0;
+    DevBuf<double> d_u, d_v0; DevBuf<unsigned char> d_mask, d_att; DevBuf<int> d_auxst, d_src; DevBuf<long long> d_start;
+    const bool commit_pol = policy || (fc && p->pol_on), commit_mem = fc && p->mem_on;      /* the resident state an advancing step moves on */
+    if (commit_pol) { if (int rc = policy_state_ready(p, who)) return rc; }
+    if (commit_mem) { if (int rc = plan_memory_ready(p, who)) return rc; }
+    if (u0 || policy || fc) HIP_TRY(d_u.alloc((size_t)batch * std::max(1, nu)));
+    if (fc) { HIP_TRY(d_att.alloc(batch)); HIP_TRY(d_src.alloc(batch)); }
     if (act_start) HIP_TRY(d_start.alloc((size_t)batch * p->pf_groups));
     HIP_TRY(d_v0.alloc((size_t)batch * std::max(1, nv))); HIP_TRY(d_mask.alloc(batch)); HIP_TRY(d_auxst.alloc(batch));
     if (aux && (aux->batch != batch || aux->aux_src_gen != p->batch_gen || aux->aux_own_gen != aux->batch_gen)) {
@@ -666,9 +685,18 @@ static int sim_step_resolve_impl(const char *who, bool policy, mld_problem_t *p,
     AuxStepArgs g{};
     g.batch = batch; g.nx = nx; g.nw = nw; g.nu = nu; g.nv = nv; g.nv2 = nv2; g.N = p->N;
     g.x0 = p->bat.x0; g.omega = p->bat.omega;
-    if (u0 || policy) { g.u = d_u; g.u_stride = (size_t)nu; }
+    if (u0 || policy || fc) { g.u = d_u; g.u_stride = (size_t)nu; }
     else { g.u = p->bat.v; g.u_stride = (size_t)p->n; }
     if (by_plan) { g.status = p->bat.status; g.obj = p->bat.obj; }
+    FallbackArgs fa{};
+    if (fc) {
+        g.attempt = d_att;
+        fa.batch = batch; fa.nx = nx; fa.nu = nu; fa.nv = nv; fa.N = p->N; fa.fb = fc->fb;
+        fa.status = p->bat.status; fa.obj = p->bat.obj; fa.v = p->bat.v; fa.v_stride = (size_t)p->n;
+        if (p->mem_on) { fa.mem_u = p->mem_u; fa.mem_age = p->mem_age; }
+        if (p->pol_on) { fa.model_idx = p->has_midx ? p->bat.model_idx.get() : nullptr; fa.tab = p->pol_tab; fa.tab_len = (size_t)nu * (nx + POL_TAIL); fa.u_prev = p->pol_uprev; }
+        fa.x0 = p->bat.x0; fa.u = d_u; fa.source = d_src; fa.attempt = d_att;
+    }
     if (actual) { g.act_start = act_start ? d_start.get() : p->pf_actual.d.get(); g.chan = p->pf_chan; g.n_groups = p->pf_groups; g.step = step; g.lib = p->pf_lib; }
     /* ---- gather: the resolver's inputs -------------------------------------------------------------------------------------------------------------- */
     auto gather = [&]() -> int {
@@ -681,6 +709,10 @@ static int sim_step_resolve_impl(const char *who, bool policy, mld_problem_t *p,
             if (by_plan) { pa.src = p->bat.v; pa.src_stride = (size_t)p->n; }
             pa.u = d_u;
             hipLaunchKernelGGL(k_policy_inputs, dim3(profile_grid((long long)batch * nu)), dim3(256), 0, sq, pa);
+            HIP_TRY(hipGetLastError());
+        }
+        if (fc) {
+            hipLaunchKernelGGL(k_fallback_inputs, dim3(profile_grid((long long)batch * nu)), dim3(256), 0, sq, fa);
             HIP_TRY(hipGetLastError());
         }
         if (aux) {
@@ -707,13 +739,23 @@ static int sim_step_resolve_impl(const char *who, bool policy, mld_problem_t *p,
     int32_t skipped = 0;
     if (int rc = sim_step_run(p, src, act_start, gmax, step, flags, x_k1_out, y_out, cons_out, cons_vio_out, cons_row_out, &skipped)) return rc;
     if (n_skipped_out) *n_skipped_out = skipped;
-    if (policy && (flags & MLD_SIM_ADVANCE) && nu) {
+    const bool advance = flags & MLD_SIM_ADVANCE;
+    if ((commit_pol && advance && nu) || fc) {
         auto commit = [&]() -> int {
-            hipLaunchKernelGGL(k_policy_commit, dim3(profile_grid((long long)batch * nu)), dim3(256), 0, sq, (long long)batch, nu, d_mask.get(), d_u.get(), p->pol_uprev.get());
-            HIP_TRY(hipGetLastError());
+            if (fc && log) HIP_TRY(hipMemcpyAsync(L.src.get() + log_slot, d_src, sizeof(int) * batch, hipMemcpyDeviceToDevice, sq));
+            if (fc && fc->u_source_out) HIP_TRY(hipMemcpyAsync(fc->u_source_out, d_src, sizeof(int) * batch, hipMemcpyDeviceToHost, sq));
+            if (commit_pol && advance && nu) {
+                hipLaunchKernelGGL(k_policy_commit, dim3(profile_grid((long long)batch * nu)), dim3(256), 0, sq, (long long)batch, nu, d_mask.get(), d_u.get(), p->pol_uprev.get());
+                HIP_TRY(hipGetLastError());
+            }
+            if (commit_mem && advance) {
+                hipLaunchKernelGGL(k_fallback_commit, dim3(profile_grid((long long)batch * p->N * nu)), dim3(256), 0, sq, fa);
+                HIP_TRY(hipGetLastError());
+            }
             return MLD_OK;
         };
         if (int rc = queue_and_wait(sq, commit)) return rc;
+        if (commit_mem && advance) p->mem_chain = p->chain_gen;      /* the chain goes on: the advance counted as one more event, and the memory has followed it */
     }
     return MLD_OK;
 }

@@ -20,13 +20,14 @@ struct AuxStepArgs {
     const double *x0, *omega;                   /* its current inputs: (batch, nx), (batch, N nw) */
     const double *u; size_t u_stride;           /* the caller's (batch, nu), or the resident plan's rows (stride n) */
     const int *status; const double *obj;       /* the resident plan's, masking the instances whose u is not usable; nullptr = the caller's u, all attempted */
+    const unsigned char *attempt;               /* nullptr: the rule above; else the attempt byte per instance itself (k_fallback_inputs: some source supplied its u) */
     const long long *act_start; const PfChan *chan; int n_groups, step; const double *lib;      /* act_start == nullptr: the forecast's step 0 */
     double *aux_x0, *aux_omega;                 /* k_aux_inputs writes: the resolver's inputs (batch, nx), (batch, nw + nu) */
     const double *aux_v; size_t aux_stride; const int *aux_status; const double *aux_obj;      /* k_aux_merge reads: the resolver's results (nullptr: nv2 == 0) */
     double *v0; unsigned char *usable; int *aux_status_out;      /* k_aux_merge writes: (batch, nv), (batch), (batch) */
 };
 
-__device__ __forceinline__ bool aux_attempted(const AuxStepArgs &a, int b) { return !a.status || plan_usable(a.status, a.obj, b); }
+__device__ __forceinline__ bool aux_attempted(const AuxStepArgs &a, int b) { return a.attempt ? a.attempt[b] != 0 : (!a.status || plan_usable(a.status, a.obj, b)); }
 
 __global__ void __launch_bounds__(256) k_aux_inputs(const AuxStepArgs a)
 {

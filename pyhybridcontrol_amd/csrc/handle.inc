@@ -93,6 +93,7 @@ struct mld_problem {
     struct SimLog {
         DevBuf<double> x, v, y, om, x_k1, vio, obj, lb; DevBuf<unsigned char> cons; DevBuf<int> row, status, nodes;
         DevBuf<int> aux;        /* (cap, batch) resolver statuses of the records mld_sim_step_resolve wrote, -2 elsewhere: allocated by the first such step that logs */
+        DevBuf<int> src;        /* (cap, batch) u_source of the records mld_sim_step_fallback wrote, -2 elsewhere: allocated by the first such step that logs */
         int cap = 0, count = 0;
     } slog;
     /* mld_sim_step_resolve: batch_gen numbers the uploads of all handles (inputs_new_batch), so that a resolver handle can tell whether its resident batch
@@ -102,6 +103,12 @@ struct mld_problem {
      * the device and on the host, owned by the problem like the profile library.  The resident u_prev (batch, nu) belongs to ONE upload of a batch: it is
      * valid while pol_state_gen == batch_gen, and laid out as the reset state (u_off on the ruled channels) by the first call that needs it after that */
     DevBuf<double> pol_tab, pol_uprev; std::vector<double> pol_host; bool pol_on = false, pol_all_ruled = false; unsigned long long pol_state_gen = 0;
+    /* plan memory (mld_plan_memory, mld_sim_step_fallback): mem_u (batch, N, nu) the u of the last usable plan of every instance, mem_age (batch) the advancing
+     * steps since (-1 nothing remembered, N exhausted).  Like the policy state it belongs to ONE upload of a batch (mem_batch_gen == batch_gen), and it is valid
+     * only along an unbroken chain of advancing fallback steps: chain_gen counts every event that replaces x0 or advances the inputs (inputs_replaced,
+     * inputs_advanced_by_plan); the fallback step adopts the count after its own advance (mem_chain).  Where either number has moved on, the first call that
+     * needs the memory empties it (plan_memory_ready) */
+    DevBuf<double> mem_u; DevBuf<int> mem_age; bool mem_on = false; unsigned long long mem_batch_gen = 0, mem_chain = 0, chain_gen = 0;
     long long ho_stats[4] = {};  /* last solve: items published, trees split, trees left unfinished, entries the queue had no room for (always 0: such trees stay unfinished) */
 };
 
@@ -110,7 +117,7 @@ struct mld_problem {
  * batch (mld_advance_batch, mld_warm_start_from_previous, mld_predict_batch ... need one), `advanced` that its plan has been applied: the next advance needs
  * the next solve, and the plan belongs to inputs that are gone. ---- */
 /* new inputs for the same batch (mld_select_inputs): the blocks belonged to the previous inputs, so did the start and the cutoffs; there is no plan */
-static void inputs_replaced(mld_problem *p) { p->n_xcols = 0; p->has_warm = false; p->solved = false; p->advanced = false; p->has_cutoff = false; }
+static void inputs_replaced(mld_problem *p) { p->n_xcols = 0; p->has_warm = false; p->solved = false; p->advanced = false; p->has_cutoff = false; ++p->chain_gen; }
 /* a new batch (mld_upload_batch): nothing of the previous one stays -- the blocks, a simulation log and a per-instance cost belong to one upload */
 static std::atomic<unsigned long long> g_batch_gen{0};
 static void inputs_new_batch(mld_problem *p)
@@ -122,12 +129,12 @@ static void inputs_new_batch(mld_problem *p)
 }
 /* inputs advanced by the resident plan (mld_advance_batch, mld_sim_step_batch): the blocks belonged to the previous step's data, a start belongs to one set
  * of inputs (mld_warm_start_from_previous builds the next one from the plan, so the batch stays `solved`); the plan has been applied */
-static void inputs_advanced_by_plan(mld_problem *p) { p->n_xcols = 0; p->has_warm = false; p->has_cutoff = false; p->advanced = true; }
+static void inputs_advanced_by_plan(mld_problem *p) { p->n_xcols = 0; p->has_warm = false; p->has_cutoff = false; p->advanced = true; ++p->chain_gen; }
 /* inputs advanced by the caller's v0 (mld_sim_step_batch): the resident plan had no part in them -- new inputs, as after mld_select_inputs */
 static void inputs_advanced_by_caller(mld_problem *p) { inputs_replaced(p); }
 /* the forecast replaced (mld_forecast_from_profiles): new inputs, as mld_select_inputs -- except after an advance, where the new forecast completes the
- * step: the blocks are gone already, and plan and start stay */
-static void forecast_replaced(mld_problem *p) { if (!p->advanced) inputs_replaced(p); }
+ * step: the blocks are gone already, and plan and start stay.  x0 and the clock stay either way, so a plan memory stays valid (chain_gen is kept) */
+static void forecast_replaced(mld_problem *p) { if (!p->advanced) { const unsigned long long chain = p->chain_gen; inputs_replaced(p); p->chain_gen = chain; } }
 
 /* the resident starts point into ONE library: they go with it */
 static void reset_profile_starts(mld_problem *p) { p->pf_forecast.reset(); p->pf_columns.reset(); p->pf_actual.reset(); }
@@ -370,6 +377,29 @@ static int policy_state_ready(mld_problem *p, const char *who)
     HIP_TRY(p->pol_uprev.alloc(std::max<size_t>(1, init.size())));
     if (!init.empty()) HIP_TRY(hipMemcpy(p->pol_uprev, init.data(), sizeof(double) * init.size(), hipMemcpyHostToDevice));
     p->pol_state_gen = p->batch_gen;
+    return MLD_OK;
+}
+
+/* The plan memory of THIS upload of the batch, along an unbroken chain of advancing fallback steps: where the batch has been uploaded anew the buffers are
+ * laid out for its size, and where anything else has replaced x0 or advanced the inputs since the memory was last valid, every age goes back to -1
+ * (nothing remembered).  Host-synchronous, before the caller queues anything. */
+static int plan_memory_ready(mld_problem *p, const char *who)
+{
+    if (!p->mem_on) { mld_set_error("%s: no plan memory enabled (mld_plan_memory)", who); return MLD_ERR_INVALID; }
+    const bool same_batch = p->mem_u && p->mem_batch_gen == p->batch_gen;
+    if (same_batch && p->mem_chain == p->chain_gen) return MLD_OK;
+    const size_t batch = (size_t)p->batch, len = batch * p->N * p->model->dims.nu;
+    const hipStream_t sq = p->stream;
+    DevBuf<double> u; DevBuf<int> age;
+    if (!same_batch) { HIP_TRY(u.alloc(std::max<size_t>(1, len))); HIP_TRY(age.alloc(batch)); }
+    auto fill = [&]() -> int {
+        if (!same_batch) HIP_TRY(hipMemsetAsync(u, 0, sizeof(double) * std::max<size_t>(1, len), sq));
+        HIP_TRY(hipMemsetAsync(same_batch ? p->mem_age.get() : age.get(), 0xff, sizeof(int) * batch, sq));      /* every byte 0xff: -1 */
+        return MLD_OK;
+    };
+    if (int rc = queue_and_wait(sq, fill)) return rc;
+    if (!same_batch) { p->mem_u = std::move(u); p->mem_age = std::move(age); }
+    p->mem_batch_gen = p->batch_gen; p->mem_chain = p->chain_gen;
     return MLD_OK;
 }
 

@@ -5,6 +5,7 @@ import os
 import numpy as np
 
 from . import _lib
+from . import fallback as _fallback
 from ._lib import MAT_NAMES, EVO_NAMES, MldGpuError, check
 
 _MAT_SHAPES = dict(A=("nx", "nx"), B1=("nx", "nu"), B2=("nx", "ndelta"), B3=("nx", "nz"), B4=("nx", "nomega"),
@@ -339,6 +340,36 @@ class GpuProblem(object):
         check(_lib.load().mld_download_policy_state(self._h, _lib.dptr(out)))
         return out
 
+    # -- fallback inputs for instances without a usable plan ----------------------------------------------
+    def plan_memory(self, enable=True):
+        """the resident plan memory of the batch (mld_plan_memory): enable allocates it and empties it (every age -1), False frees it.  An advancing
+        sim_step(resolve=R, fallback=...) remembers every usable plan's inputs in it and ages the others'; fallback=("memory", ...) lets an instance
+        without a usable plan take the remembered row for the current time.  upload(), select(), advance() and an advancing step through any other
+        entry empty it."""
+        check(_lib.load().mld_plan_memory(self._h, 1 if enable else 0))
+
+    def plan_memory_state(self, u=None, age=None):
+        """the plan memory (mld_set_plan_memory / mld_download_plan_memory): u (batch, N_tilde, nu) the remembered plans' inputs, age (batch,) int32 the
+        advancing steps since each was made (-1 nothing remembered, N_tilde exhausted).  u / age given: seed or restore them.  Returns dict(u, age)
+        as now resident."""
+        B, N, nu = self.batch, self.N_tilde, self.model.dims["nu"]
+        if u is not None:
+            u = np.asarray(u, dtype=np.float64)
+            if u.shape != (B, N, nu):
+                raise ValueError("u has shape %s, expected (%d, %d, %d)" % (u.shape, B, N, nu))
+            u = np.ascontiguousarray(u)
+        if age is not None:
+            age = np.asarray(age)
+            if age.shape != (B,) or not np.issubdtype(age.dtype, np.integer):
+                raise ValueError("age has shape %s and dtype %s, expected (%d,) integers" % (age.shape, age.dtype, B))
+            age = np.ascontiguousarray(age, dtype=np.int32)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None
+        if u is not None or age is not None:
+            check(_lib.load().mld_set_plan_memory(self._h, _lib.dptr(u), ip(age)))
+        out = dict(u=np.zeros((B, N, nu)), age=np.zeros(B, np.int32))
+        check(_lib.load().mld_download_plan_memory(self._h, _lib.dptr(out["u"]), ip(out["age"])))
+        return out
+
     def _start_array(self, start, n_lead):
         """int64 starts with n_lead leading axes after the batch -- (batch, n_groups) or (batch, n_cols, n_groups); the same without the batch axis is
         broadcast over the batch; ValueError on a float dtype or a shape that fits neither, before any C call"""
@@ -570,7 +601,7 @@ class GpuProblem(object):
         check(_lib.load().mld_sim_log_count(self._h, C.byref(n), C.byref(cap)))
         return int(n.value), int(cap.value)
 
-    def sim_step(self, v0=None, act_start=None, step=0, actual=None, advance=True, log=None, outputs=False, resolve=None, u0=None, policy=False):
+    def sim_step(self, v0=None, act_start=None, step=0, actual=None, advance=True, log=None, outputs=False, resolve=None, u0=None, policy=False, fallback=None):
         """one plant step of the resident batch on device (mld_sim_step_batch): the reference's lsim_k(x_k, v_k=, omega_k) with the whole step-0 slice --
         of the last solve's plans (v0=None; instances without a usable plan are skipped and counted) or the caller's v0 (batch, nv) / (nv,) -- under the
         forecast's step 0 or, with actual, the element `step` of the realised series at act_start (batch, n_groups) / (n_groups,) of the resident profile
@@ -583,11 +614,22 @@ class GpuProblem(object):
         outputs=True additionally returns v0 (batch, nv), the resolved slices, and aux_status (batch), the resolver's status, -1 = not attempted.
         policy=True (with resolve): the ruled channels of u come from the resident policy (upload_policy), written on the device from the current x0 and
         the resident u_prev (mld_sim_step_policy, kernel k_policy_inputs); u0 / the plan supply the passed-through channels only, and no plan is needed
-        when every channel is ruled.  An advancing step moves the resident u_prev of every advanced instance to the u applied."""
+        when every channel is ruled.  An advancing step moves the resident u_prev of every advanced instance to the u applied.
+        fallback (with resolve, without u0 / policy): any subset of ("memory", "policy") -- the plan's step (mld_sim_step_fallback, kernels
+        k_fallback_inputs / k_fallback_commit) in which an instance WITHOUT a usable plan takes its u from the first source that applies: the plan memory's
+        row for the current time (plan_memory()), then the resident policy's rule (upload_policy, every channel ruled); with neither it is skipped as
+        before.  fallback=() allows no source: the step of sim_step(resolve=R).  outputs=True additionally returns u_source (batch) int32: 0 plan,
+        1 memory, 2 policy, -1 none.  An advancing step remembers the usable plans in an enabled memory, ages the others, and moves a resident policy's
+        u_prev of every advanced instance to the u applied."""
         d, B = self.model.dims, self.batch
         nv = self.model.nv
         if policy and resolve is None:
             raise ValueError("policy=True goes with resolve (a BatchAuxResolver re-derives the auxiliaries of the rule's u)")
+        fb = None
+        if fallback is not None:
+            if resolve is None or u0 is not None or policy:
+                raise ValueError("fallback goes with resolve and the resident plan's u (no u0, no policy=True): it names where an instance without a usable plan takes its u from")
+            fb = _fallback.fb_bits(fallback)
         if resolve is None and u0 is not None:
             raise ValueError("u0 given without resolve (the whole slice is v0; u0 goes with a BatchAuxResolver that re-derives the rest)")
         if resolve is not None:
@@ -623,11 +665,21 @@ class GpuProblem(object):
             if outputs:
                 out.update(v0=np.zeros((B, nv)), aux_status=np.zeros(B, np.int32))
             aux = resolve.problem._h if resolve.problem is not None else None
-            check((_lib.load().mld_sim_step_policy if policy else _lib.load().mld_sim_step_resolve)(
-                self._h, aux, _lib.dptr(u0), st.ctypes.data_as(C.POINTER(C.c_int64)) if st is not None else None, int(step), flags,
-                _lib.dptr(out["x_k1"]) if out else None, _lib.dptr(out["y"]) if out else None,
-                out["cons"].ctypes.data_as(C.POINTER(C.c_uint8)) if out else None, _lib.dptr(out["cons_vio"]) if out else None,
-                ip(out["cons_row"]) if out else None, _lib.dptr(out["v0"]) if out else None, ip(out["aux_status"]) if out else None, C.byref(skipped)))
+            if fb is not None:
+                if outputs:
+                    out["u_source"] = np.zeros(B, np.int32)
+                check(_lib.load().mld_sim_step_fallback(
+                    self._h, aux, fb, st.ctypes.data_as(C.POINTER(C.c_int64)) if st is not None else None, int(step), flags,
+                    _lib.dptr(out["x_k1"]) if out else None, _lib.dptr(out["y"]) if out else None,
+                    out["cons"].ctypes.data_as(C.POINTER(C.c_uint8)) if out else None, _lib.dptr(out["cons_vio"]) if out else None,
+                    ip(out["cons_row"]) if out else None, _lib.dptr(out["v0"]) if out else None, ip(out["aux_status"]) if out else None,
+                    ip(out["u_source"]) if out else None, C.byref(skipped)))
+            else:
+                check((_lib.load().mld_sim_step_policy if policy else _lib.load().mld_sim_step_resolve)(
+                    self._h, aux, _lib.dptr(u0), st.ctypes.data_as(C.POINTER(C.c_int64)) if st is not None else None, int(step), flags,
+                    _lib.dptr(out["x_k1"]) if out else None, _lib.dptr(out["y"]) if out else None,
+                    out["cons"].ctypes.data_as(C.POINTER(C.c_uint8)) if out else None, _lib.dptr(out["cons_vio"]) if out else None,
+                    ip(out["cons_row"]) if out else None, _lib.dptr(out["v0"]) if out else None, ip(out["aux_status"]) if out else None, C.byref(skipped)))
             if resolve.problem is not None:
                 resolve.problem.batch = B      # the call lays the resolver's batch out as this one
             if not outputs:
@@ -810,6 +862,19 @@ class GpuProblem(object):
             raise ValueError("sim_log_aux: first = %d lies beyond the %d logged steps" % (first, K + first))
         out = np.zeros((K, self.batch), np.int32)
         check(_lib.load().mld_download_sim_log_aux(self._h, first, K, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
+    def sim_log_source(self, first=0, count=None):
+        """the source of u per record and instance (mld_download_sim_log_source), (count, batch) int32: what sim_step(resolve=R, fallback=...) returned as
+        u_source (0 plan, 1 memory, 2 policy, -1 none), -2 for the records any other step wrote"""
+        first = int(first)
+        if count is None:
+            count = self.sim_log_count()[0] - first
+        K = int(count)
+        if K < 0:
+            raise ValueError("sim_log_source: first = %d lies beyond the %d logged steps" % (first, K + first))
+        out = np.zeros((K, self.batch), np.int32)
+        check(_lib.load().mld_download_sim_log_source(self._h, first, K, out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out
 
     def set_warm_start(self, bin_start):
