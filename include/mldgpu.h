@@ -499,8 +499,8 @@ int mld_download_constraint_blocks(mld_problem_t *, int32_t *n_cols_out, double 
  * on the ORIGINAL model's matrices, in fp64 also on an MLD_F32 handle (k_sim_step).  x_k1 is summed exactly as mld_advance_batch sums it, so an advance
  * through this entry leaves the same bits.  Under a realised disturbance `cons` says, per row, whether the PLANNED auxiliaries are still consistent with the
  * model: the test of the equivalence condition mld_advance_batch2 describes above.  Re-deriving delta / z from (x, u, omega) (lsim_k's _compute_aux) is not
- * done here but by mld_sim_step_resolve below.  The stage cost is the agent's business in the reference (sim_k.z * prices_k, examples/.../modelling/micro_grid_agents.py:753): it stays a host
- * product on the downloaded log.
+ * done here but by mld_sim_step_resolve below.  The stage cost is the agent's business in the reference (sim_k.z * prices_k, examples/.../modelling/micro_grid_agents.py:753): here it is
+ * written beside the record once mld_sim_log_cost_begin has armed it (resident price profiles, below).
  *
  * v0 == NULL  the step-0 slice of the resident plan.  Needs a finished solve of the current inputs that has not been advanced yet (refused exactly where
  *             mld_predict_batch(v = NULL) is refused); rows are read after the hand-off's device merge.  An instance without a usable plan (not OPTIMAL /
@@ -706,6 +706,66 @@ int mld_sim_step_fallback(mld_problem_t *, mld_problem_t *aux, int fb, const int
                           double *x_k1_out, double *y_out, uint8_t *cons_out, double *cons_vio_out, int32_t *cons_row_out,
                           double *v0_out, int32_t *aux_status_out, int32_t *u_source_out, int32_t *n_skipped_out);
 int mld_download_sim_log_source(mld_problem_t *, int first, int count, int32_t *u_source);
+
+/* ---- resident price profiles: tariff windows into the cost, stage cost in the log -----------------------------------------------------------------------
+ * Every solve of the reference's closed loop starts from a price window and every plant step ends in a price: GridAgentMpc.get_price_tilde_k(k) cuts
+ * price_profile.values[start:start + N_tilde] out of a series it holds once (examples/.../modelling/micro_grid_agents.py:563-606), sim_mpc turns the window
+ * into the objective before every solve() (micro_grid_control_simulation.py:186-198: q_z = prices_tilde, q_mu = sum(prices_tilde) * P_h_Nom * mult), and
+ * sim_step_k multiplies the realised import by the price of the step (micro_grid_agents.py:746-755), summed into total_cost_struct (:239-243).
+ *
+ * mld_upload_prices: a flat library of lib_len doubles, owned by the PROBLEM like the disturbance library and separate from it (prices are not disturbance
+ * channels and have no groups) -- it survives mld_upload_batch, mld_select_inputs and the advances.  n_chan >= 1 price channels; a series is row-major
+ * (time, n_chan), as price_profile.values is.  A second call replaces it, invalidates the resident price starts and disarms a stage cost; the tables below
+ * stay unless n_chan changes (it shapes them).  lib_len = 0 frees the library and everything that hangs on it; mld_problem_destroy frees it.
+ * MLD_ERR_INVALID, nothing changed: lib_len < 0; lib == NULL with lib_len > 0; n_chan < 1; (N_tilde + 1) x n_chan above 6144 doubles (the LDS a row of
+ * k_price_cost is staged in).
+ *
+ * THE WINDOW RULE.  For a start s and a step offset `step`:   price[k, c] = lib[s + (step + k)*n_chan + c]   for k < len, with len = N_tilde for the cost
+ * and 1 for the stage cost.  A start is valid iff s >= 0 and s <= lib_len - (step + len)*n_chan (tested so that nothing overflows).  Every start of every
+ * call is tested on the host BEFORE anything is queued, the first offender is named by instance; the largest resident start is remembered on the host, so
+ * that a call with start == NULL and another step is tested without reading the device.
+ *
+ * THE COST OF A RESIDENT BATCH.  mld_set_price_cost: per-model tables owned by the problem like the policy tables -- a_v and sum_v (n_models, n_chan, nv),
+ * a_y (n_models, n_chan, ny); any NULL = zeros, all NULL clears.  mld_instance_cost_from_prices, start (batch): builds ON THE DEVICE (k_price_cost) exactly
+ * the weights a caller would have uploaded.  With m = model_idx[b] (0 without) and p[k, c] the window of instance b:
+ *     S[c]               = p[0,c] + p[1,c] + ... + p[N_tilde-1,c]                                  (k ascending, one rounding per addition)
+ *     lin_v[b, k*nv + j] = sum_c ( a_v[m,c,j] * p[k,c] )  +  sum_c ( sum_v[m,c,j] * S[c] )         (c ascending in both sums)
+ *     lin_y[b, k*ny + j] = sum_c ( a_y[m,c,j] * p[k,c] )
+ * every product and every addition rounded on its own (no fused multiply-add), so the weights are bit-identical to the numpy restatement
+ * (pyhybridcontrol_amd/prices.py: cost_np) and the resident cost to the one mld_upload_instance_cost(lin_v, NULL, lin_y) leaves.  a_v on the z column with
+ * n_chan = 1 is the reference's q_z = prices_tilde, sum_v on the mu columns its q_mu, a_y a price on an output (exported power).  From there on the call IS
+ * mld_upload_instance_cost: the same resident cost with the same row length, the same pull-back GEMM fed from the device-built weights (none, and
+ * batch x n doubles, without a_y), the same lifetime -- valid until the next mld_upload_batch, replaced by a later mld_upload_instance_cost and vice
+ * versa, kept by mld_select_inputs and the advances, plan and MIP start untouched -- and no consumer sees a difference.  The starts stay resident in an
+ * array of their own: start == NULL re-uses them with another step (NULL without resident starts for this batch size is refused).  It moves 8 bytes per
+ * instance, or nothing, where the upload moves N_tilde*nv doubles per instance.
+ * MLD_ERR_INVALID before anything is queued, nothing changed.  mld_set_price_cost: no price library; a non-finite entry; a_y with ny == 0.
+ * mld_instance_cost_from_prices: no batch resident; a launched solve not finished; no price library; no tables; step < 0; an invalid start; a time-varying
+ * handle (mld_model_create_tv) -- the ONE restriction against mld_upload_instance_cost, which takes such handles: the tables are per model, not per step model.
+ *
+ * THE STAGE COST IN THE SIMULATION LOG.  mld_set_stage_cost: per-model weights w_v (n_models, n_chan, nv), w_y (n_models, n_chan, ny); NULL = zeros, all
+ * NULL clears (and disarms); needs the price library (no library, a non-finite entry, w_y with ny == 0: refused).  mld_sim_log_cost_begin(start (batch))
+ * arms the stage cost for the log that has been begun: cost (capacity, batch) and price (capacity, batch, n_chan) beside the log, filled with NaN, and
+ * total (batch), steps (batch), zeros.  From then on every step that writes a log record -- through mld_sim_step_batch, _resolve, _policy or _fallback --
+ * also writes into that record's slot (k_stage_cost, one launch behind the step's own kernel)
+ *     price[c] = lib[s_b + step*n_chan + c]                              (step: the step call's own argument, the one that slides the realised omega)
+ *     cost     = sum_c price[c] * ( sum_j w_v[m,c,j]*v[j] + sum_j w_y[m,c,j]*y[j] )              (c, j ascending; no fused multiply-add)
+ * with the record's own v (the slice the plant was stepped with, whatever the entry point applied) and y.  A stepped instance gets total[b] += cost and
+ * steps[b] += 1; a skipped one (no usable plan, infeasible auxiliaries) cost = NaN in the record -- price is recorded all the same -- and total and steps
+ * stay.  With w_v on the grid model's z this is the reference's sim_k.z * prices_k, and total its total_cost_struct.  The armed state belongs to the log:
+ * mld_sim_log_begin and mld_upload_batch discard it, mld_upload_prices disarms.  While armed, a logging step also tests s_max + (step + 1)*n_chan <= lib_len
+ * before anything is queued.  Without arming every step entry point queues exactly what it queued before.  Memory: capacity x batch x (1 + n_chan) doubles
+ * and batch x (1 double + 1 int + 1 start).
+ * MLD_ERR_INVALID, nothing changed: arming without a begun log, without a price library, without stage weights, with start == NULL or an invalid start;
+ * mld_download_sim_log_cost -- cost (count, batch), price (count, batch, n_chan), either may be NULL -- with a range outside [0, n_logged] or without an
+ * armed log; mld_download_cost_total -- total (batch), steps (batch) -- without an armed log. */
+int mld_upload_prices(mld_problem_t *, int64_t lib_len, const double *lib, int n_chan);
+int mld_set_price_cost(mld_problem_t *, const double *a_v, const double *sum_v, const double *a_y);
+int mld_instance_cost_from_prices(mld_problem_t *, const int64_t *start, int step);
+int mld_set_stage_cost(mld_problem_t *, const double *w_v, const double *w_y);
+int mld_sim_log_cost_begin(mld_problem_t *, const int64_t *start);
+int mld_download_sim_log_cost(mld_problem_t *, int first, int count, double *cost, double *price);
+int mld_download_cost_total(mld_problem_t *, double *total, int32_t *steps);
 
 /* Per-instance telemetry of the last solve: time spent inside the solve kernel (device wall clock, ns) and
  * the number of dictionary rows the rank-1 updates touched (x *row_bytes x 2 = bytes streamed by pivots). */

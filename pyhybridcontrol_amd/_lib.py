@@ -65,6 +65,8 @@ EXPORTS = ("mld_device_count", "mld_set_device", "mld_last_error", "mld_version"
            "mld_sim_step_resolve", "mld_download_sim_log_aux", "mld_rollout_batch",
            "mld_upload_policy", "mld_set_policy_state", "mld_download_policy_state", "mld_rollout_policy", "mld_sim_step_policy",
            "mld_plan_memory", "mld_set_plan_memory", "mld_download_plan_memory", "mld_sim_step_fallback", "mld_download_sim_log_source",
+           "mld_upload_prices", "mld_set_price_cost", "mld_instance_cost_from_prices", "mld_set_stage_cost", "mld_sim_log_cost_begin", "mld_download_sim_log_cost",
+           "mld_download_cost_total",
            "mld_comm_unique_id", "mld_comm_init", "mld_gather", "mld_comm_destroy")
 
 
@@ -109,6 +111,13 @@ def load():
     lib.mld_download_plan_memory.argtypes = [C.c_void_p, dp, ip]
     lib.mld_sim_step_fallback.argtypes = [C.c_void_p, C.c_void_p, C.c_int, lp, C.c_int, C.c_int, dp, dp, bp, dp, ip, dp, ip, ip, ip]
     lib.mld_download_sim_log_source.argtypes = [C.c_void_p, C.c_int, C.c_int, ip]
+    lib.mld_upload_prices.argtypes = [C.c_void_p, C.c_int64, dp, C.c_int]
+    lib.mld_set_price_cost.argtypes = [C.c_void_p, dp, dp, dp]
+    lib.mld_instance_cost_from_prices.argtypes = [C.c_void_p, lp, C.c_int]
+    lib.mld_set_stage_cost.argtypes = [C.c_void_p, dp, dp]
+    lib.mld_sim_log_cost_begin.argtypes = [C.c_void_p, lp]
+    lib.mld_download_sim_log_cost.argtypes = [C.c_void_p, C.c_int, C.c_int, dp, dp]
+    lib.mld_download_cost_total.argtypes = [C.c_void_p, dp, ip]
     if int(lib.mld_opts_size()) != C.sizeof(Opts):
         raise MldGpuError("libmldgpu.so was built with another layout of mld_opts (%d bytes, this binding %d): rebuild it (python -m pyhybridcontrol_amd.build)"
                           % (lib.mld_opts_size(), C.sizeof(Opts)))

@@ -142,17 +142,36 @@ int mld_download_constraint_blocks(mld_problem_t *p, int32_t *n_cols_out, double
  * micro_grid_control_simulation.py:194-198,229: N calls replaced by one batch may carry N price vectors).  Weights on v are kept as uploaded; weights on
  * x_tilde / y_tilde are pulled back through the tightened model's condensed maps by ONE GEMM per model (k_inst_pullback; k_inst_pullback_valu under
  * MLD_DBG_GEMM_VALU) into [q_b | cx_b | cw_b | c0_b].  The new cost is built in a buffer of its own: a call that fails leaves the resident one as it was. */
+/* The tail the two routes to a per-instance cost share (the caller's weights: mld_upload_instance_cost; weights built on the device from price windows:
+ * mld_instance_cost_from_prices).  inst_cost_ld: the row length of the new cost.  queue_inst_pullback: with the weights on [x_tilde | y_tilde] in d_w
+ * (batch, NX + NY) and lin_v in the first n columns of ic, the GEMM that completes ic.  adopt_inst_cost: the new cost becomes the resident one. */
+static int inst_cost_ld(const mld_problem *p, bool pull) { return pull ? p->n + p->nx + p->nW + 1 : p->n; }      /* weights on v only: no GEMM, cx / cw / c0 are zero and not stored */
+
+static int queue_inst_pullback(mld_problem *p, hipStream_t sq, const double *d_w, double *ic)
+{
+    const int NX = p->N * p->model->dims.nx, NY = p->N * p->model->dims.ny, K = NX + NY;
+    const PbMaps mp = pullback_maps(p);
+    if (p->opts.reserved & MLD_DBG_GEMM_VALU)
+        hipLaunchKernelGGL(k_inst_pullback_valu, dim3(p->batch), dim3(256), sizeof(double) * K, sq, NX, NY, p->n, p->nx, p->nW, mp, p->has_midx ? p->bat.model_idx.get() : nullptr, d_w, ic);
+    else
+        LAUNCH_INST_GEMM(k_inst_pullback, p->opts.flags & MLD_F32, p->n_groups, 0, sq, NX, NY, p->n, p->nx, p->nW, mp, p->bat.groups.get(), p->bat.perm.get(), d_w, ic);
+    HIP_TRY(hipGetLastError());
+    return MLD_OK;
+}
+
+static void adopt_inst_cost(mld_problem *p, DevBuf<double> &&ic, int ld) { p->bat.icost = std::move(ic); p->ic_ld = ld; }
+
 int mld_upload_instance_cost(mld_problem_t *p, const double *lin_v, const double *lin_x, const double *lin_y)
 {
     if (int rc = entry_guard(p, "mld_upload_instance_cost", true, "upload a batch first (the cost belongs to its instances)")) return rc;
-    const int n = p->n, nx = p->nx, nW = p->nW, batch = p->batch;
+    const int n = p->n, batch = p->batch;
     const int NX = p->N * p->model->dims.nx, NY = p->N * p->model->dims.ny;
     if (lin_x && NX == 0) { mld_set_error("mld_upload_instance_cost: lin_x given but the model has no state (nx = 0)"); return MLD_ERR_INVALID; }
     if (lin_y && NY == 0) { mld_set_error("mld_upload_instance_cost: lin_y given but the model has no output (ny = 0)"); return MLD_ERR_INVALID; }
     if (!lin_v && !lin_x && !lin_y) { p->bat.icost.reset(); p->bat.qs_inst_t.reset(); p->ic_ld = 0; return MLD_OK; }
     const hipStream_t sq = p->stream;
     const bool pull = lin_x || lin_y;
-    const int ld = pull ? n + nx + nW + 1 : n;      /* weights on v only: no GEMM, cx / cw / c0 are zero and not stored */
+    const int ld = inst_cost_ld(p, pull);
     DevBuf<double> ic, d_w;
     HIP_TRY(ic.alloc((size_t)batch * std::max(1, ld)));
     /* everything queued on the stream and waited for on every path (queue_and_wait): the caller's arrays and the temporaries may go when this returns */
@@ -166,17 +185,12 @@ int mld_upload_instance_cost(mld_problem_t *p, const double *lin_v, const double
         if (!lin_x || !lin_y) HIP_TRY(hipMemsetAsync(d_w, 0, sizeof(double) * (size_t)batch * K, sq));
         if (lin_x) HIP_TRY(hipMemcpy2DAsync(d_w, sizeof(double) * K, lin_x, sizeof(double) * NX, sizeof(double) * NX, batch, hipMemcpyHostToDevice, sq));
         if (lin_y) HIP_TRY(hipMemcpy2DAsync(d_w.get() + NX, sizeof(double) * K, lin_y, sizeof(double) * NY, sizeof(double) * NY, batch, hipMemcpyHostToDevice, sq));
-        const PbMaps mp = pullback_maps(p);
-        if (p->opts.reserved & MLD_DBG_GEMM_VALU)
-            hipLaunchKernelGGL(k_inst_pullback_valu, dim3(batch), dim3(256), sizeof(double) * K, sq, NX, NY, n, nx, nW, mp, p->has_midx ? p->bat.model_idx.get() : nullptr, d_w.get(), ic.get());
-        else
-            LAUNCH_INST_GEMM(k_inst_pullback, p->opts.flags & MLD_F32, p->n_groups, 0, sq, NX, NY, n, nx, nW, mp, p->bat.groups.get(), p->bat.perm.get(), d_w.get(), ic.get());
-        HIP_TRY(hipGetLastError());
+        if (int rc = queue_inst_pullback(p, sq, d_w.get(), ic.get())) return rc;
     }
     return MLD_OK;
     };
     if (int rc = queue_and_wait(sq, queue)) return rc;
-    p->bat.icost = std::move(ic); p->ic_ld = ld;
+    adopt_inst_cost(p, std::move(ic), ld);
     return MLD_OK;
 }
 
@@ -481,6 +495,8 @@ static int sim_step_check(mld_problem_t *p, const char *who, bool own, const cha
     const mld_problem::SimLog &L = p->slog;
     if (log && !L.cap) { mld_set_error("%s: MLD_SIM_LOG, but no log has been begun for this batch (mld_sim_log_begin)", who); return MLD_ERR_INVALID; }
     if (log && L.count >= L.cap) { mld_set_error("%s: MLD_SIM_LOG, but the log is full (%d of %d records; mld_download_sim_log, then mld_sim_log_begin)", who, L.count, L.cap); return MLD_ERR_INVALID; }
+    /* the stage cost armed (mld_sim_log_cost_begin): the record's price is lib[s + step * n_chan ..], one element run of the price library */
+    if (log && L.cost) { if (int rc = check_resident(price_lib(p), who, PF_PRICE_ELEMENT, std::vector<long long>(1, L.cstart_max), step, 1)) return rc; }
     return MLD_OK;
 }
 
@@ -556,6 +572,16 @@ static int sim_step_run(mld_problem_t *p, const SimStepSrc &src, const int64_t *
         const int grid = (int)std::min<long long>(((long long)batch + SS_WAVES - 1) / SS_WAVES, 8192);
         hipLaunchKernelGGL(k_sim_step, dim3(grid), dim3(64 * SS_WAVES), a.lds ? stage : 0, sq, a);
         HIP_TRY(hipGetLastError());
+        if (log && L.cost) {      /* the stage cost armed: price and cost of the record just written, the running total (k_stage_cost, prices.inc) */
+            StageCostArgs c{};
+            c.batch = batch; c.n_chan = p->pr_chan; c.nv = nv; c.ny = ny; c.step = step; c.model_idx = a.model_idx;
+            c.mask = a.mask; c.status = a.status; c.obj = a.obj;
+            c.start = L.cstart; c.lib = p->pr_lib; c.w_v = p->sc_tab; c.w_y = p->sc_tab.get() + (size_t)p->n_models * p->pr_chan * nv;
+            c.rec_v = a.rec_v; c.rec_y = a.y; c.rec_cost = L.cost.get() + slot; c.rec_price = L.price.get() + slot * p->pr_chan;
+            c.total = L.total; c.steps = L.steps;
+            hipLaunchKernelGGL(k_stage_cost, dim3(profile_grid(batch)), dim3(256), 0, sq, c);
+            HIP_TRY(hipGetLastError());
+        }
         if (resolved && log) HIP_TRY(hipMemcpyAsync(L.aux.get() + slot, src.d_auxst, sizeof(int) * batch, hipMemcpyDeviceToDevice, sq));
         if (x_k1_out && nx) HIP_TRY(hipMemcpyAsync(x_k1_out, a.x_k1, sizeof(double) * (size_t)batch * nx, hipMemcpyDeviceToHost, sq));
         if (y_out && ny) HIP_TRY(hipMemcpyAsync(y_out, a.y, sizeof(double) * (size_t)batch * ny, hipMemcpyDeviceToHost, sq));

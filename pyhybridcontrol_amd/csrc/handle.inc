@@ -88,12 +88,22 @@ struct mld_problem {
      * of the forecast windows, of the constraint columns' windows and of the REALISED series (mld_sim_step_batch, MLD_SIM_ACTUAL), each an array of its own */
     DevBuf<double> pf_lib; long long pf_len = 0; int pf_groups = 0; std::vector<int> pf_width; DevBuf<PfChan> pf_chan;
     PfStarts pf_forecast, pf_columns, pf_actual;
+    /* resident price profiles (mld_upload_prices): a flat library of its own, owned by the problem like the one above; a series is row-major (time, pr_chan).
+     * pr_cost: the resident starts of the cost windows (mld_instance_cost_from_prices).  pr_tab: the tables of mld_set_price_cost, [a_v | sum_v | a_y], each
+     * (n_models, pr_chan, nv / nv / ny), zeros where the caller gave none; pr_ay: a_y was given (the cost then needs the pull-back).  sc_tab: the stage weights
+     * of mld_set_stage_cost, [w_v | w_y], (n_models, pr_chan, nv / ny).  The tables are shaped by pr_chan: a library with another n_chan drops them */
+    DevBuf<double> pr_lib; long long pr_len = 0; int pr_chan = 0; PfStarts pr_cost;
+    DevBuf<double> pr_tab, sc_tab; bool pr_tab_on = false, pr_ay = false, sc_on = false;
     /* resident simulation log (mld_sim_log_begin): `cap` records of the resident batch, one array per field, each (cap, batch, width).  It belongs to the
      * resident batch: mld_upload_batch discards it */
     struct SimLog {
         DevBuf<double> x, v, y, om, x_k1, vio, obj, lb; DevBuf<unsigned char> cons; DevBuf<int> row, status, nodes;
         DevBuf<int> aux;        /* (cap, batch) resolver statuses of the records mld_sim_step_resolve wrote, -2 elsewhere: allocated by the first such step that logs */
         DevBuf<int> src;        /* (cap, batch) u_source of the records mld_sim_step_fallback wrote, -2 elsewhere: allocated by the first such step that logs */
+        /* stage cost (mld_sim_log_cost_begin), armed while `cost` is allocated: cost (cap, batch) and price (cap, batch, pr_chan) beside the records, the
+         * running total and the count of stepped records per instance, the starts into the price library and the largest of them */
+        DevBuf<double> cost, price, total; DevBuf<int> steps; DevBuf<long long> cstart; long long cstart_max = 0;
+        void disarm() { cost.reset(); price.reset(); total.reset(); steps.reset(); cstart.reset(); cstart_max = 0; }
         int cap = 0, count = 0;
     } slog;
     /* mld_sim_step_resolve: batch_gen numbers the uploads of all handles (inputs_new_batch), so that a resolver handle can tell whether its resident batch
@@ -474,9 +484,17 @@ static int launch_instance_cost(mld_problem *p, const double *cs, double *qs, do
 }
 
 // ---- resident profiles: the window rule on the host ------------------------------------------------------------------------------------------------------
-/* the words by which the messages of the window rule differ: a window of N steps behind a start (forecast, columns), or ONE element behind an actual start */
-struct PfWords { const char *start, *window; bool column; };
-static const PfWords PF_WINDOW = {"start", "window", true}, PF_ELEMENT = {"actual start", "element", false};
+/* the words by which the messages of the window rule differ: a window of N steps behind a start (forecast, columns), ONE element behind an actual start,
+ * or a price window behind a start into the price library */
+struct PfWords { const char *start, *window; bool column; const char *lib; };
+static const PfWords PF_WINDOW = {"start", "window", true, "library"}, PF_ELEMENT = {"actual start", "element", false, "library"},
+                     PF_PRICE = {"price start", "price window", false, "price library"}, PF_PRICE_ELEMENT = {"price start", "price", false, "price library"};
+
+/* the library a start array points into, as the window rule sees it: its length and its groups' widths (the disturbance library: one group per fused device;
+ * the price library: ONE group of width n_chan) */
+struct PfLibView { long long len; int groups; const int *width; };
+static PfLibView profile_lib(const mld_problem *p) { return PfLibView{p->pf_len, p->pf_groups, p->pf_width.data()}; }
+static PfLibView price_lib(const mld_problem *p) { return PfLibView{p->pr_len, 1, &p->pr_chan}; }
 
 /* what the three consumers share: a library and a step the window rule can be tested with */
 static int profile_ready(const mld_problem *p, const char *who, int step)
@@ -488,35 +506,43 @@ static int profile_ready(const mld_problem *p, const char *who, int step)
 
 /* every start of a (batch, n_cols, n_groups) array against the window rule for `len` steps (N for a window, 1 for an element); the first offender is named;
  * gmax: per group the largest start */
-static int profile_check_starts(const mld_problem *p, const char *who, const PfWords &w, const int64_t *start, int batch, int n_cols, int step, int len, std::vector<long long> &gmax)
+static int check_starts(const PfLibView &L, const char *who, const PfWords &w, const int64_t *start, int batch, int n_cols, int step, int len, std::vector<long long> &gmax)
 {
-    const int G = p->pf_groups;
+    const int G = L.groups;
     gmax.assign(G, 0);
     const int64_t *s = start;
     for (int b = 0; b < batch; ++b)
         for (int c = 0; c < n_cols; ++c)
             for (int g = 0; g < G; ++g, ++s) {
-                if (!profile_start_ok(*s, p->pf_len, step, len, p->pf_width[g])) {
+                if (!profile_start_ok(*s, L.len, step, len, L.width[g])) {
                     char col[32] = "";
                     if (w.column) snprintf(col, sizeof(col), " column %d,", c);
-                    mld_set_error("%s: %s %lld of instance %d,%s group %d (width %d) at step %d: the %s [%lld, %lld) leaves the library of %lld doubles",
-                                  who, w.start, (long long)*s, b, col, g, p->pf_width[g], step, w.window, (long long)*s + (long long)step * p->pf_width[g],
-                                  (long long)*s + ((long long)step + len) * p->pf_width[g], p->pf_len);
+                    mld_set_error("%s: %s %lld of instance %d,%s group %d (width %d) at step %d: the %s [%lld, %lld) leaves the %s of %lld doubles",
+                                  who, w.start, (long long)*s, b, col, g, L.width[g], step, w.window, (long long)*s + (long long)step * L.width[g],
+                                  (long long)*s + ((long long)step + len) * L.width[g], w.lib, L.len);
                     return MLD_ERR_INVALID;
                 }
                 gmax[g] = std::max<long long>(gmax[g], *s);
             }
     return MLD_OK;
 }
+static int profile_check_starts(const mld_problem *p, const char *who, const PfWords &w, const int64_t *start, int batch, int n_cols, int step, int len, std::vector<long long> &gmax)
+{
+    return check_starts(profile_lib(p), who, w, start, batch, n_cols, step, len, gmax);
+}
 
 /* resident starts under another step: the remembered maxima decide (the smallest start was >= 0 when the array was uploaded) */
-static int profile_check_resident(const mld_problem *p, const char *who, const PfWords &w, const std::vector<long long> &gmax, int step, int len)
+static int check_resident(const PfLibView &L, const char *who, const PfWords &w, const std::vector<long long> &gmax, int step, int len)
 {
-    for (int g = 0; g < p->pf_groups; ++g)
-        if (!profile_start_ok(gmax[g], p->pf_len, step, len, p->pf_width[g])) {
-            mld_set_error("%s: step %d moves the largest resident %s of group %d (%lld, width %d) past the end of the library: the %s would end at %lld of %lld doubles",
-                          who, step, w.start, g, gmax[g], p->pf_width[g], w.window, gmax[g] + ((long long)step + len) * p->pf_width[g], p->pf_len);
+    for (int g = 0; g < L.groups; ++g)
+        if (!profile_start_ok(gmax[g], L.len, step, len, L.width[g])) {
+            mld_set_error("%s: step %d moves the largest resident %s of group %d (%lld, width %d) past the end of the %s: the %s would end at %lld of %lld doubles",
+                          who, step, w.start, g, gmax[g], L.width[g], w.lib, w.window, gmax[g] + ((long long)step + len) * L.width[g], L.len);
             return MLD_ERR_INVALID;
         }
     return MLD_OK;
+}
+static int profile_check_resident(const mld_problem *p, const char *who, const PfWords &w, const std::vector<long long> &gmax, int step, int len)
+{
+    return check_resident(profile_lib(p), who, w, gmax, step, len);
 }

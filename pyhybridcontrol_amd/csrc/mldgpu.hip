@@ -28,7 +28,7 @@ void mld_set_error(const char *fmt, ...)
 extern "C" {
 
 const char *mld_last_error(void) { return g_err; }
-const char *mld_version(void) { return "mldgpu 0.6 (gfx950, fp64 dense-dictionary cut-and-branch, in-kernel sub-tree hand-off, per-instance linear cost, predicted trajectories, solution quality, resident disturbance profiles, plant step and simulation log, auxiliaries re-derived on device, open-loop rollout, rule-based feedback policies, fallback inputs for instances without a usable plan; sizeof(mld_opts) = 64)"; }
+const char *mld_version(void) { return "mldgpu 0.6 (gfx950, fp64 dense-dictionary cut-and-branch, in-kernel sub-tree hand-off, per-instance linear cost, predicted trajectories, solution quality, resident disturbance profiles, plant step and simulation log, auxiliaries re-derived on device, open-loop rollout, rule-based feedback policies, fallback inputs for instances without a usable plan, resident price profiles; sizeof(mld_opts) = 64)"; }
 
 int mld_device_count(void)
 {
@@ -215,6 +215,7 @@ int mld_condense_f32(mld_model_t *m, int N_tilde, int flags, float *Phi_x, float
 
 #include "tighten.inc"          // host big-M tightening (namespace tighten)
 #include "kernels.inc"          // small kernels: cost assembly, receding horizon, MIP start, fills, statistics, result packing
+#include "prices.inc"           // k_price_cost, k_stage_cost and the two formulas they share with the host (mld_upload_prices and its consumers, api_prices.inc)
 #include "handle.inc"           // BatchBufs, mld_problem, build_shape, ensure_batch; the host helpers the entry points are written from
 #include "merge.inc"            // in-kernel hand-off: reset of the queue and merge of its items, mld_debug_merge
 #include "api_create.inc"       // mld_problem_create / destroy / set_cost / get_opts / set_opts, mld_cost_assemble, mld_opts_*
@@ -223,4 +224,5 @@ int mld_condense_f32(mld_model_t *m, int N_tilde, int flags, float *Phi_x, float
 #include "api_rollout.inc"      // open-loop rollout of plans under realised disturbances (k_rollout)
 #include "api_policy.inc"       // rule-based feedback policies: tables, resident u_prev, policy rollout (k_rollout_policy) and policy step (k_policy_inputs)
 #include "api_fallback.inc"     // fallback inputs for instances without a usable plan: plan memory, the fallback step (k_fallback_inputs, k_fallback_commit), its log
+#include "api_prices.inc"       // resident price profiles: the price library, the cost of a batch from price windows, the stage cost in the simulation log
 #include "api_gather.inc"       // RCCL gather

@@ -16,6 +16,7 @@
 
 struct PfChan { int group, off, width; };      // per disturbance channel: its group, its offset inside the group, the group's width
 
+#if defined(__HIPCC__)      /* (the window rule's test below also compiles for a host program without the HIP runtime: scripts/price_cost_host_check.cpp) */
 // dst (rows, nW) contiguous, row r = (instance r / cols, column r % cols); that row's starts are start[((r / cols) * ld_cols + col0 + r % cols) * n_groups ..]:
 // cols == ld_cols, col0 == 0 for a whole array, a slice of `cols` columns from col0 of ld_cols in the evaluate path.
 __global__ void __launch_bounds__(256) k_profile_windows(int rows, int nW, int nomega, int cols, int ld_cols, int col0, int n_groups, const long long *start,
@@ -37,6 +38,7 @@ __global__ void __launch_bounds__(256) k_profile_windows(int rows, int nW, int n
         dst[(long long)r * nW + c] = lib[s + (long long)(step + (int)k) * ch.width + ch.off];
     }
 }
+#endif
 
 static int profile_grid(long long total)
 {

@@ -496,6 +496,98 @@ class GpuProblem(object):
         check(_lib.load().mld_download_instance_cost(self._h, _lib.dptr(q), _lib.dptr(c)))
         return dict(q=q, const=c)
 
+    # -- resident price profiles -------------------------------------------------------------------------
+    def upload_prices(self, lib, n_chan=1):
+        """flat library of price series resident in HBM (mld_upload_prices), owned by the problem and independent of the batch, separate from the
+        disturbance library.  A series is row-major (time, n_chan), as the reference's price_profile.values; profiles.pack lays series end to end.  A
+        second call replaces the library, invalidates the resident price starts and disarms a stage cost; an empty library frees it."""
+        lib = np.ascontiguousarray(lib, dtype=np.float64)
+        if lib.ndim != 1:
+            raise ValueError("lib has shape %s, expected a flat array (profiles.pack)" % (lib.shape,))
+        if int(n_chan) < 1:
+            raise ValueError("n_chan = %r, expected at least one price channel" % (n_chan,))
+        check(_lib.load().mld_upload_prices(self._h, lib.size, _lib.dptr(lib) if lib.size else None, int(n_chan)))
+        self._pr_chan = int(n_chan) if lib.size else 0
+
+    def _price_tables(self, **tables):
+        """per-model tables (n_models, n_chan, width) of the price entry points; (n_chan, width) and (width,) broadcast over models and channels; None stays
+        None.  ValueError on a shape that fits none, before any C call"""
+        M, C = self.model.n_models, getattr(self, "_pr_chan", 0)
+        if not C and any(t is not None for t in tables.values()):
+            raise ValueError("no price library uploaded (upload_prices): its n_chan shapes the tables")
+        widths = dict(a_v=self.model.nv, sum_v=self.model.nv, w_v=self.model.nv, a_y=self.model.dims["ny"], w_y=self.model.dims["ny"])
+        out = []
+        for name, t in tables.items():
+            if t is None:
+                out.append(None)
+                continue
+            W = widths[name]
+            t = np.asarray(t, dtype=np.float64)
+            if W == 0:
+                raise ValueError("%s given but the model has none of that variable" % name)
+            if t.shape not in ((M, C, W), (C, W), (W,)):
+                raise ValueError("%s has shape %s, expected (%d, %d, %d), (%d, %d) or (%d,)" % (name, t.shape, M, C, W, C, W, W))
+            out.append(np.ascontiguousarray(np.broadcast_to(t, (M, C, W))))
+        return out
+
+    def _price_start(self, start):
+        """(batch,) int64 starts into the price library; a scalar or (1,) is broadcast over the batch; ValueError on a float dtype or another shape"""
+        a = np.asarray(start)
+        if not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("start has dtype %s, expected integers (offsets into the price library)" % a.dtype)
+        if a.shape in ((), (1,)):
+            a = np.broadcast_to(a.reshape(()), (self.batch,))
+        if a.shape != (self.batch,):
+            raise ValueError("start has shape %s, expected (%d,), (1,) or a scalar" % (np.shape(start), self.batch))
+        return np.ascontiguousarray(a, dtype=np.int64)
+
+    def set_price_cost(self, a_v=None, sum_v=None, a_y=None):
+        """the tables that turn a price window into linear weights (mld_set_price_cost): a_v / sum_v (n_models, n_chan, nv), a_y (n_models, n_chan, ny);
+        (n_chan, width) and (width,) broadcast; None = zeros, all None clears.  prices.cost_np states what they build."""
+        av, sv, ay = self._price_tables(a_v=a_v, sum_v=sum_v, a_y=a_y)
+        check(_lib.load().mld_set_price_cost(self._h, _lib.dptr(av), _lib.dptr(sv), _lib.dptr(ay)))
+
+    def instance_cost_from_prices(self, start=None, step=0):
+        """the per-instance linear cost of the resident batch built on the device from price windows (mld_instance_cost_from_prices): start (batch,)
+        integer offsets into the price library (a scalar is broadcast), window = prices.windows(lib, start, step, N_tilde, n_chan).  start=None re-uses
+        the resident starts with another step.  The result is the cost upload_instance_cost(*prices.cost_np(...)) leaves, bit for bit."""
+        st = self._price_start(start) if start is not None else None
+        check(_lib.load().mld_instance_cost_from_prices(self._h, st.ctypes.data_as(C.POINTER(C.c_int64)) if st is not None else None, int(step)))
+
+    def set_stage_cost(self, w_v=None, w_y=None):
+        """the weights of the stage cost (mld_set_stage_cost): w_v (n_models, n_chan, nv), w_y (n_models, n_chan, ny), broadcast as set_price_cost's;
+        None = zeros, all None clears and disarms"""
+        wv, wy = self._price_tables(w_v=w_v, w_y=w_y)
+        check(_lib.load().mld_set_stage_cost(self._h, _lib.dptr(wv), _lib.dptr(wy)))
+
+    def sim_log_cost_begin(self, start):
+        """arms the stage cost for the log that has been begun (mld_sim_log_cost_begin): start (batch,) offsets of the realised prices; every logged step
+        then records price[c] = lib[start + step * n_chan + c] and cost = prices.stage_cost_np(...) of its own v and y, and adds it to the instance's total"""
+        if start is None:
+            raise ValueError("sim_log_cost_begin needs start (the offsets of the realised prices, one per instance)")
+        st = self._price_start(start)
+        check(_lib.load().mld_sim_log_cost_begin(self._h, st.ctypes.data_as(C.POINTER(C.c_int64))))
+
+    def sim_log_cost(self, first=0, count=None):
+        """stage cost and price of records [first, first + count) (mld_download_sim_log_cost; count=None: all from first): dict(cost (count, batch),
+        price (count, batch, n_chan)); cost is NaN for a skipped instance"""
+        first = int(first)
+        if count is None:
+            count = self.sim_log_count()[0] - first
+        K = int(count)
+        if K < 0:
+            raise ValueError("sim_log_cost: first = %d lies beyond the %d logged steps" % (first, K + first))
+        out = dict(cost=np.zeros((K, self.batch)), price=np.zeros((K, self.batch, getattr(self, "_pr_chan", 0))))
+        check(_lib.load().mld_download_sim_log_cost(self._h, first, K, _lib.dptr(out["cost"]), _lib.dptr(out["price"])))
+        return out
+
+    def cost_total(self):
+        """the running stage cost per instance since the stage cost was armed (mld_download_cost_total): dict(total (batch,), steps (batch,) int32 the
+        records that counted)"""
+        out = dict(total=np.zeros(self.batch), steps=np.zeros(self.batch, np.int32))
+        check(_lib.load().mld_download_cost_total(self._h, _lib.dptr(out["total"]), out["steps"].ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
     def _plan_array(self, v):
         """(batch, n) float64 array of caller-supplied plans, a (n,) array broadcast; ValueError on a shape that fits neither"""
         if v is None:
@@ -986,16 +1078,21 @@ class GpuProblem(object):
         return dict(latency_ns=lat, rows_updated=rows, row_bytes=int(rb.value))
 
     def solve(self, x0, omega, model_idx=None, fixed_bin=None, omega_cols=None, col_rows=None, x_cols=None, warm_start=None, inst_cost=None, trajectories=False, quality=False,
-              col_start=None, col_step=0):
+              col_start=None, col_step=0, price_start=None, price_step=0):
         """upload, solve, download.  col_start / col_step: the constraint blocks gathered from the resident profile library
-        (constraint_blocks_from_profiles) instead of uploaded as omega_cols -- one or the other.  inst_cost: dict(lin_v=..., lin_x=..., lin_y=...) of upload_instance_cost for this batch; trajectories=True adds
+        (constraint_blocks_from_profiles) instead of uploaded as omega_cols -- one or the other.  price_start / price_step: the per-instance cost built on the device from
+        price windows (instance_cost_from_prices; the tables of set_price_cost) instead of uploaded as inst_cost -- one or the other.  inst_cost: dict(lin_v=..., lin_x=..., lin_y=...) of upload_instance_cost for this batch; trajectories=True adds
         the predicted x / y of trajectories() to the result; quality=True adds out["quality"], evaluate() of the plans just computed on the problem
         as posed"""
         if col_start is not None and omega_cols is not None:
             raise ValueError("col_start and omega_cols both given: the constraint blocks come from the profile library or from the caller, not both")
+        if price_start is not None and inst_cost:
+            raise ValueError("price_start and inst_cost both given: the per-instance cost comes from the price library or from the caller, not both")
         self.upload(x0, omega, model_idx, fixed_bin)
         if inst_cost:
             self.upload_instance_cost(**inst_cost)
+        if price_start is not None:
+            self.instance_cost_from_prices(price_start, price_step)
         if omega_cols is not None:
             self.upload_constraint_blocks(omega_cols, col_rows, x_cols)
         if col_start is not None:
