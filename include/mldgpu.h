@@ -707,6 +707,37 @@ int mld_sim_step_fallback(mld_problem_t *, mld_problem_t *aux, int fb, const int
                           double *v0_out, int32_t *aux_status_out, int32_t *u_source_out, int32_t *n_skipped_out);
 int mld_download_sim_log_source(mld_problem_t *, int first, int count, int32_t *u_source);
 
+/* ---- MIP start from a baseline rollout ------------------------------------------------------------------------------------------------------------------
+ * mld_warm_start_from_previous gives an instance without a usable plan no start (255), and so does the first solve after an upload: exactly the hard
+ * instances enter the search cold.  The reference hands its backend whatever values the variables hold (warm_start=True, controllers/controller_base.py:493,
+ * 509-512).  mld_warm_start_from_rollout builds the start ON THE DEVICE from a rollout of the handle's current x0 under the RESIDENT FORECAST (the omega the
+ * next solve plans against: batch x N_tilde x nomega, step-major, read where it lies), K = N_tilde steps, one trajectory per instance:
+ *   policy = 1   the resident rule-based policy in closed loop (k_rollout_policy) -- a thermostat keeps every tank inside its band; where its plan is feasible
+ *                for the MPC's rows (it need not be for every instance: the solver verifies a start like any other, and one that is not feasible gives no
+ *                incumbent), the start, evaluated first as mld_set_warm_start describes (lazily with a quadratic cost or under MLD_DBG_LAZY_START), is
+ *                an incumbent no worse than the baseline.  u_prev (batch, nu) or
+ *                NULL = the resident policy state, which the call does not write; u_seq (batch, N_tilde, nu) supplies the passed-through channels under
+ *                mld_rollout_policy's rules (NULL with every channel ruled needs no plan).
+ *   policy = 0   the caller's u_seq (batch, N_tilde, nu), required (k_rollout) -- another controller's plan as the start of this one; the auxiliaries are
+ *                re-derived for THIS handle's forecast.
+ * The start (k_warm_from_rollout, threads on (instance, binary)): binary k of instance b, bins[k] = step nv + pos, takes v[b, step, pos] > 0.5 ? 1 : 0 of the
+ * rolled-out v, which is a device temporary and never downloaded.  source_out (batch) int32, or NULL:
+ *      1   start written from the rollout
+ *      0   existing start kept: MLD_START_KEEP in flags, a start is resident, and the row's first byte is not 255
+ *     -1   the auxiliary problem of some step has no feasible point              } the whole row 255 = no start
+ *     -2   the LDS solver declined (this entry has no host completion)           }
+ *     -3   not attempted: a passed-through channel needed the plan and there is none usable
+ * Without MLD_START_KEEP, or with no start resident, every row is written.  stats (or NULL): trajectories, rows written, kept, none.
+ * Afterwards a start is set (as after mld_set_warm_start), unless the problem has no binary: then the call, once every check below has passed, returns
+ * MLD_OK, rolls nothing and writes neither output.  Nothing else changes on the handle -- inputs, plan, solved / advanced, cutoffs, log, policy state, plan memory, resident starts -- and nothing
+ * on aux.  The start is formed from fp64 buffers on every handle (the forecast and the rollout are fp64 also under MLD_F32).
+ * MLD_ERR_INVALID before anything is queued, the resident start as it was: everything mld_rollout_batch / mld_rollout_policy refuse (a time-varying model, a
+ * resolver off the small-problem path, a u_seq or u_prev that is not finite, no policy, ...); policy = 0 with u_seq == NULL; u_prev with policy = 0; unknown
+ * flag bits; a launched solve that has not been finished. */
+#define MLD_START_KEEP 1   /* instances that already have a start keep it */
+int mld_warm_start_from_rollout(mld_problem_t *p, mld_problem_t *aux, int policy, const double *u_seq, const double *u_prev,
+                                int flags, int32_t *source_out, int64_t stats[4]);
+
 /* ---- resident price profiles: tariff windows into the cost, stage cost in the log -----------------------------------------------------------------------
  * Every solve of the reference's closed loop starts from a price window and every plant step ends in a price: GridAgentMpc.get_price_tilde_k(k) cuts
  * price_profile.values[start:start + N_tilde] out of a series it holds once (examples/.../modelling/micro_grid_agents.py:563-606), sim_mpc turns the window

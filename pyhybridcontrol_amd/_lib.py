@@ -24,6 +24,7 @@ MLD_DBG_PIVOT_SYNC_R5 = 1 << 26        # mld_opts.reserved: k_solve's pivot with
 MLD_DBG_SELECT_R6 = 1 << 27            # mld_opts.reserved: k_solve's choice of (row, column) with its earlier block reductions (A/B, bit-identical results)
 MLD_DBG_UPDATE_R7 = 1 << 28            # mld_opts.reserved: k_solve's row updates as they were before a unit was cut down to its payload (A/B, bit-identical results)
 MLD_SIM_ADVANCE, MLD_SIM_ACTUAL, MLD_SIM_LOG = 1, 2, 4      # flags of mld_sim_step_batch / mld_sim_step_resolve
+MLD_START_KEEP = 1                                          # flags of mld_warm_start_from_rollout: instances that already have a start keep it
 MLD_FB_MEMORY, MLD_FB_POLICY = 1, 2                         # fb of mld_sim_step_fallback: the sources an instance without a usable plan may take its u from
 
 
@@ -67,6 +68,7 @@ EXPORTS = ("mld_device_count", "mld_set_device", "mld_last_error", "mld_version"
            "mld_plan_memory", "mld_set_plan_memory", "mld_download_plan_memory", "mld_sim_step_fallback", "mld_download_sim_log_source",
            "mld_upload_prices", "mld_set_price_cost", "mld_instance_cost_from_prices", "mld_set_stage_cost", "mld_sim_log_cost_begin", "mld_download_sim_log_cost",
            "mld_download_cost_total",
+           "mld_warm_start_from_rollout",
            "mld_comm_unique_id", "mld_comm_init", "mld_gather", "mld_comm_destroy")
 
 
@@ -118,6 +120,7 @@ def load():
     lib.mld_sim_log_cost_begin.argtypes = [C.c_void_p, lp]
     lib.mld_download_sim_log_cost.argtypes = [C.c_void_p, C.c_int, C.c_int, dp, dp]
     lib.mld_download_cost_total.argtypes = [C.c_void_p, dp, ip]
+    lib.mld_warm_start_from_rollout.argtypes = [C.c_void_p, C.c_void_p, C.c_int, dp, dp, C.c_int, ip, lp]
     if int(lib.mld_opts_size()) != C.sizeof(Opts):
         raise MldGpuError("libmldgpu.so was built with another layout of mld_opts (%d bytes, this binding %d): rebuild it (python -m pyhybridcontrol_amd.build)"
                           % (lib.mld_opts_size(), C.sizeof(Opts)))

@@ -82,8 +82,8 @@ int mld_rollout_policy(mld_problem_t *p, mld_problem_t *aux, int K, int S, const
     static const char who[] = "mld_rollout_policy";
     if (int rc = entry_guard(p, who, true, "no batch resident (mld_upload_batch)")) return rc;
     const PolicyCall pc{u_prev, switches_out};
-    return rollout_impl(who, &pc, p, aux, K, S, u_seq, omega_seq, start, step, cost_w, cost_rows, x_out, v_out, y_out, cons_vio_out, cons_row_out, cost_out,
-                        mu_total_out, worst_vio_out, worst_step_out, steps_done_out, end_status_out, stats);
+    const RolloutOut out{x_out, v_out, y_out, cons_vio_out, cons_row_out, cost_out, mu_total_out, worst_vio_out, worst_step_out, steps_done_out, end_status_out, stats};
+    return rollout_impl(who, &pc, p, aux, K, S, u_seq, omega_seq, start, step, cost_w, cost_rows, out);
 }
 
 int mld_sim_step_policy(mld_problem_t *p, mld_problem_t *aux, const double *u0, const int64_t *act_start, int step, int flags,

@@ -1,12 +1,18 @@
 // Open-loop rollout of the resident batch's plans under realised disturbances (mld_rollout_batch, kernel k_rollout in rollout.inc).
 /* The body mld_rollout_batch and mld_rollout_policy share.  pc == nullptr: the open-loop rollout, kernel k_rollout, as it always was.  pc: the policy
  * instantiation k_rollout_policy -- the ruled channels of u_k by p's resident policy from the trajectory's own x_k and u_{k-1}, u_seq / the plan for the
- * passed-through ones only (no plan is needed when every channel is ruled), pc->u_prev (batch, nu) or the resident policy state before step 0. */
+ * passed-through ones only (no plan is needed when every channel is ruled), pc->u_prev (batch, nu) or the resident policy state before step 0.
+ * sc (mld_warm_start_from_rollout, api_start.inc): a third way to name the disturbance -- the RESIDENT FORECAST, bat.omega (batch, N_tilde nomega), which is
+ * step-major and so already the (batch, 1, K, nomega) the kernels read: K = N_tilde, S = 1, nothing uploaded or copied -- and v / end_status stay on the device:
+ * k_warm_from_rollout, queued behind the rollout on the same stream, turns them into the MIP start.  The forecast is fp64 on every handle, MLD_F32 included
+ * (the flag moves GEMMs to fp32, never the inputs), so the start comes from the buffers the rollout reads anyway and nothing is converted. */
 static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p, mld_problem_t *aux, int K, int S, const double *u_seq, const double *omega_seq,
-                        const int64_t *start, int step, const double *cost_w, int cost_rows, double *x_out, double *v_out, double *y_out, double *cons_vio_out,
-                        int32_t *cons_row_out, double *cost_out, double *mu_total_out, double *worst_vio_out, int32_t *worst_step_out, int32_t *steps_done_out,
-                        int32_t *end_status_out, int64_t stats[4])
+                        const int64_t *start, int step, const double *cost_w, int cost_rows, const RolloutOut &out, const StartCall *sc = nullptr)
 {
+    double *const x_out = out.x, *const v_out = out.v, *const y_out = out.y, *const cons_vio_out = out.cons_vio, *const cost_out = out.cost,
+           *const mu_total_out = out.mu_total, *const worst_vio_out = out.worst_vio;
+    int32_t *const cons_row_out = out.cons_row, *const worst_step_out = out.worst_step, *const steps_done_out = out.steps_done, *const end_status_out = out.end_status;
+    int64_t *const stats = out.stats;
     mld_model *mo = p->model;
     const mld_dims &d = mo->dims;
     const int batch = p->batch, nx = d.nx, nu = d.nu, nw = d.nomega, nv = p->nv, ny = d.ny;
@@ -36,7 +42,9 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
         if (!p->solved) { mld_set_error("%s: the resident batch has not been solved since its upload / selection (there is no plan to apply; pass u_seq)", who); return MLD_ERR_INVALID; }
         if (p->advanced) { mld_set_error("%s: the last solve's plan has already been applied -- the resident plan belongs to inputs that are gone (solve again, or pass u_seq)", who); return MLD_ERR_INVALID; }
     }
-    if (nw) {
+    if (sc) {
+        if (K != p->N || S != 1 || omega_seq || start || (size_t)K * nw != (size_t)p->nW) { mld_set_error("%s: internal: the resident forecast is (batch, N_tilde, nomega)", who); return MLD_ERR_INVALID; }
+    } else if (nw) {
         if ((omega_seq != nullptr) == (start != nullptr)) { mld_set_error("%s: exactly one of omega_seq and start must be given (%s)", who, omega_seq ? "both are" : "neither is"); return MLD_ERR_INVALID; }
     } else if (start) { mld_set_error("%s: start given, but the model has no disturbance (nomega = 0)", who); return MLD_ERR_INVALID; }
     if (cost_w && cost_rows != p->n_models && cost_rows != batch) { mld_set_error("%s: cost_rows = %d (n_models = %d or batch = %d)", who, cost_rows, p->n_models, batch); return MLD_ERR_INVALID; }
@@ -60,6 +68,8 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
         mld_set_error("%s: cost_w of row %zu, step %zu, entry %zu is not finite (%g)", who, k / ((size_t)K * nv), k / nv % K, k % nv, cost_w[k]); return MLD_ERR_INVALID;
     }
 
+    if (sc && p->nb == 0) return MLD_OK;      /* every check has passed; without a binary there is no start to set, and nothing is rolled out */
+
     SmShape SS{};
     size_t wave_d = 0;
     if (aux) {
@@ -72,10 +82,11 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
     const hipStream_t sq = p->stream;
     const size_t Kz = (size_t)K;
     DevBuf<double> d_u, d_om, d_cw, d_x, d_v, d_y, d_vio, d_cost, d_mu, d_wv, d_uprev; DevBuf<int> d_row, d_ws, d_sd, d_es, d_sw; DevBuf<long long> d_start; DevBuf<unsigned long long> d_cnt;
+    DevBuf<unsigned char> d_old; DevBuf<int> d_src;      /* sc: the resident start as it was (where rows are kept), the source per instance */
     if (pc && !pc->u_prev) { if (int rc = policy_state_ready(p, who)) return rc; }      /* (an upload's reset state, laid out on first use: nothing a caller can see changes) */
     if (pc && pc->u_prev) HIP_TRY(d_uprev.alloc(std::max<size_t>(1, (size_t)batch * nu)));
     if (u_seq) HIP_TRY(d_u.alloc(std::max<size_t>(1, (size_t)batch * Kz * nu)));
-    HIP_TRY(d_om.alloc(std::max<size_t>(1, T * Kz * nw)));
+    if (!sc) HIP_TRY(d_om.alloc(std::max<size_t>(1, T * Kz * nw)));
     if (start) HIP_TRY(d_start.alloc(T * p->pf_groups));
     if (cost_w) HIP_TRY(d_cw.alloc(std::max<size_t>(1, (size_t)cost_rows * Kz * nv)));
     /* an output that was asked for and is not empty gets a device buffer (take), and is copied back after the kernel (get) */
@@ -85,6 +96,14 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
     HIP_TRY(take(d_cost, cost_out, T)); HIP_TRY(take(d_mu, mu_total_out, T)); HIP_TRY(take(d_wv, worst_vio_out, T));
     HIP_TRY(take(d_ws, worst_step_out, T)); HIP_TRY(take(d_sd, steps_done_out, T)); HIP_TRY(take(d_es, end_status_out, T));
     if (pc) HIP_TRY(take(d_sw, pc->switches_out, T));
+    const size_t warm_len = sc ? (size_t)batch * p->nb : 0;
+    const bool keep_rows = sc && sc->keep && p->has_warm;
+    std::vector<int32_t> src_host;
+    if (sc) {
+        HIP_TRY(d_v.alloc(cv)); HIP_TRY(d_es.alloc(T)); HIP_TRY(d_src.alloc((size_t)batch));
+        if (keep_rows) HIP_TRY(d_old.alloc(warm_len));
+        src_host.resize((size_t)batch);
+    }
     HIP_TRY(d_cnt.alloc(4));
     RoDev a{};
     a.batch = batch; a.S = S; a.K = K;
@@ -96,7 +115,7 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
     if (u_seq) { a.u = d_u; a.u_stride = Kz * nu; a.u_step = (size_t)nu; }
     else if (by_plan) { a.u = p->bat.v; a.u_stride = (size_t)p->n; a.u_step = (size_t)nv; a.status = p->bat.status; a.obj = p->bat.obj; }      /* rows < batch are the instances' (after the hand-off's device merge) */
     else { a.u = p->bat.x0; a.u_stride = 0; a.u_step = 0; }      /* every channel ruled: u is never read (a valid address all the same) */
-    a.om = d_om;
+    a.om = sc ? p->bat.omega.get() : d_om.get();
     a.cw = cost_w ? d_cw.get() : nullptr; a.cw_by_inst = cw_inst ? 1 : 0;
     a.x = d_x; a.v = d_v; a.y = d_y; a.vio = d_vio; a.row = d_row;
     a.cost = d_cost; a.mu_total = d_mu; a.worst_vio = d_wv; a.worst_step = d_ws; a.steps_done = d_sd; a.end_status = d_es;
@@ -130,16 +149,30 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
         else hipLaunchKernelGGL(k_rollout, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a);
         HIP_TRY(hipGetLastError());
         auto get = [&](auto *out, const auto &buf, size_t count) -> hipError_t {
-            return buf ? hipMemcpyAsync(out, buf, sizeof(*out) * count, hipMemcpyDeviceToHost, sq) : hipSuccess;
+            return out && buf ? hipMemcpyAsync(out, buf, sizeof(*out) * count, hipMemcpyDeviceToHost, sq) : hipSuccess;
         };
         HIP_TRY(get(x_out, d_x, cx)); HIP_TRY(get(v_out, d_v, cv)); HIP_TRY(get(y_out, d_y, cy)); HIP_TRY(get(cons_vio_out, d_vio, ck)); HIP_TRY(get(cons_row_out, d_row, ck));
         HIP_TRY(get(cost_out, d_cost, T)); HIP_TRY(get(mu_total_out, d_mu, T)); HIP_TRY(get(worst_vio_out, d_wv, T));
         HIP_TRY(get(worst_step_out, d_ws, T)); HIP_TRY(get(steps_done_out, d_sd, T)); HIP_TRY(get(end_status_out, d_es, T));
         if (pc) HIP_TRY(get(pc->switches_out, d_sw, T));
         HIP_TRY(hipMemcpyAsync(cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, sq));
+        if (sc) {
+            if (keep_rows) HIP_TRY(hipMemcpyAsync(d_old, p->bat.warm, warm_len, hipMemcpyDeviceToDevice, sq));
+            hipLaunchKernelGGL(k_warm_from_rollout, dim3((unsigned)((warm_len + 255) / 256)), dim3(256), 0, sq, (long long)batch, p->nb, nv, p->d_bins.get(), d_v.get(),
+                               Kz * nv, d_es.get(), keep_rows ? d_old.get() : nullptr, p->bat.warm.get(), d_src.get());
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(src_host.data(), d_src, sizeof(int32_t) * (size_t)batch, hipMemcpyDeviceToHost, sq));
+        }
         return MLD_OK;
     };
     if (int rc = queue_and_wait(sq, queue)) return rc;
+    if (sc) {      /* the start is set; written / kept / none counted from the sources */
+        p->has_warm = true;
+        int64_t n[3] = {0, 0, 0};
+        for (int32_t s : src_host) ++n[s == WS_WRITTEN ? 0 : (s == WS_KEPT ? 1 : 2)];
+        if (sc->source_out) std::copy(src_host.begin(), src_host.end(), sc->source_out);
+        if (sc->stats) { sc->stats[0] = (int64_t)T; sc->stats[1] = n[0]; sc->stats[2] = n[1]; sc->stats[3] = n[2]; }
+    }
     if (stats) { stats[0] = (int64_t)T; stats[1] = (int64_t)cnt[1]; stats[2] = (int64_t)cnt[2]; stats[3] = (int64_t)cnt[3]; }
     return MLD_OK;
 }
@@ -158,8 +191,8 @@ int mld_rollout_batch(mld_problem_t *p, mld_problem_t *aux, int K, int S, const 
 {
     static const char who[] = "mld_rollout_batch";
     if (int rc = entry_guard(p, who, true, "no batch resident (mld_upload_batch)")) return rc;
-    return rollout_impl(who, nullptr, p, aux, K, S, u_seq, omega_seq, start, step, cost_w, cost_rows, x_out, v_out, y_out, cons_vio_out, cons_row_out, cost_out,
-                        mu_total_out, worst_vio_out, worst_step_out, steps_done_out, end_status_out, stats);
+    const RolloutOut out{x_out, v_out, y_out, cons_vio_out, cons_row_out, cost_out, mu_total_out, worst_vio_out, worst_step_out, steps_done_out, end_status_out, stats};
+    return rollout_impl(who, nullptr, p, aux, K, S, u_seq, omega_seq, start, step, cost_w, cost_rows, out);
 }
 
 } // extern "C"

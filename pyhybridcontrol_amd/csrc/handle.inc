@@ -367,6 +367,18 @@ template <typename Queue> static int queue_and_wait(hipStream_t sq, Queue &&queu
  * state) and where the switch counts go */
 struct PolicyCall { const double *u_prev; int32_t *switches_out; };
 
+/* Where the results of a rollout go on the host, in the order of the entry points' arguments: per trajectory and step x (K + 1 states), v, y, cons_vio,
+ * cons_row; per trajectory cost, mu_total, worst_vio, worst_step, steps_done, end_status; stats[4].  Any may be NULL: not asked for */
+struct RolloutOut {
+    double *x, *v, *y, *cons_vio; int32_t *cons_row;
+    double *cost, *mu_total, *worst_vio; int32_t *worst_step, *steps_done, *end_status;
+    int64_t *stats;
+};
+
+/* What mld_warm_start_from_rollout adds to the same body: the rows that have a start keep it (MLD_START_KEEP), and where the source per instance (batch, or
+ * NULL) and the counts [trajectories, written, kept, none] (or NULL) go */
+struct StartCall { bool keep; int32_t *source_out; int64_t *stats; };
+
 /* The resident policy state of THIS upload of the batch: if there is none yet (or it belonged to an earlier upload), the reset state -- every ruled channel
  * at its model's u_off, the reference's first step, which has no previous record (theromstat_control.py:57: `u_k_neg1 == 1` is false); a passed-through
  * channel at 0.  Host-synchronous on the legacy stream, before the caller queues anything. */

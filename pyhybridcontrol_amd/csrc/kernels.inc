@@ -158,6 +158,20 @@ __global__ void __launch_bounds__(256) k_warm_from_plan(int batch, int nb, int n
     warm[t] = val > 0.5 ? 1 : 0;
 }
 
+// MIP start from a rollout (mld_warm_start_from_rollout): binary k of instance b takes the rounded value of its per-step variable in the rolled-out
+// trajectory's v (batch, N_tilde, nv), a device temporary; an instance whose trajectory did not end complete gets none (the whole row 255), one that keeps
+// its resident start is not written.  Threads on (instance, binary), a 64-bit flat index; the thread of an instance's binary 0 writes its source.  The rule
+// of one element is ws_element (warm_rollout.inc).
+#include "warm_rollout.inc"
+__global__ void __launch_bounds__(256) k_warm_from_rollout(long long batch, int nb, int nv, const int *bins, const double *v, size_t v_stride, const int *end_status,
+                                                          const unsigned char *old, unsigned char *warm, int *source)
+{
+    const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (unsigned long long)batch * (unsigned)nb) return;
+    const int src = ws_element(t, nb, nv, bins, v, v_stride, end_status, old, warm);
+    if (t % (unsigned)nb == 0) source[t / (unsigned)nb] = src;
+}
+
 #include "trajectory.inc"      // k_trajectory / k_trajectory_valu (mld_predict_batch): they mask with plan_usable, like k_advance
 #include "evaluate.inc"        // k_evaluate / k_evaluate_valu, k_eval_point, k_eval_obj (mld_evaluate_batch): the same masking
 #include "sim_step.inc"        // k_sim_step (mld_sim_step_batch): lsim_k with the whole step-0 slice, the same masking

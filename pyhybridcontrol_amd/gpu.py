@@ -790,6 +790,30 @@ class GpuProblem(object):
         out["n_skipped"] = int(skipped.value)
         return out
 
+    def _u_seq_array(self, u_seq, K):
+        """u_seq of rollout() / warm_start_from_rollout(): (batch, K, nu), or (K, nu) for every instance; K=None takes the array's"""
+        B, nu = self.batch, self.model.dims["nu"]
+        u_seq = np.asarray(u_seq, dtype=np.float64)
+        if u_seq.ndim == 2:
+            u_seq = np.broadcast_to(u_seq, (B,) + u_seq.shape)
+        if u_seq.ndim != 3 or u_seq.shape[0] != B or u_seq.shape[2] != nu or (K is not None and u_seq.shape[1] != int(K)):
+            raise ValueError("u_seq has shape %s, expected (%d, K, %d) or (K, %d)%s" % (u_seq.shape, B, nu, nu, "" if K is None else " with K = %d" % int(K)))
+        return np.ascontiguousarray(u_seq)
+
+    def _u_prev_array(self, u_prev, policy):
+        """u_prev of the same two: (batch, nu), or (nu,) for every instance; only with a policy"""
+        B, nu = self.batch, self.model.dims["nu"]
+        if u_prev is None:
+            return None
+        if not policy:
+            raise ValueError("u_prev given without policy=True (the open-loop rollout has no previous input)")
+        u_prev = np.asarray(u_prev, dtype=np.float64)
+        if u_prev.shape == (nu,):
+            u_prev = np.broadcast_to(u_prev, (B, nu))
+        if u_prev.shape != (B, nu):
+            raise ValueError("u_prev has shape %s, expected (%d, %d) or (%d,)" % (u_prev.shape, B, nu, nu))
+        return np.ascontiguousarray(u_prev)
+
     def rollout(self, resolve, K=None, u_seq=None, omega_seq=None, start=None, step=0, cost_w=None, trajectories=False, policy=False, u_prev=None):
         """open-loop rollout of the resident batch under S realised disturbances, on device (mld_rollout_batch, kernel k_rollout): the reference's
         MldModel.lsim / lsim_k in a loop with _compute_aux at every step (models/mld_model.py:543-642, 647-699, 701-766), batch x S trajectories in one launch.
@@ -811,23 +835,10 @@ class GpuProblem(object):
         d, B, nv = self.model.dims, self.batch, self.model.nv
         nx, nu, nw, ny = d["nx"], d["nu"], d["nomega"], d["ny"]
         if u_seq is not None:
-            u_seq = np.asarray(u_seq, dtype=np.float64)
-            if u_seq.ndim == 2:
-                u_seq = np.broadcast_to(u_seq, (B,) + u_seq.shape)
-            if u_seq.ndim != 3 or u_seq.shape[0] != B or u_seq.shape[2] != nu or (K is not None and u_seq.shape[1] != int(K)):
-                raise ValueError("u_seq has shape %s, expected (%d, K, %d) or (K, %d)%s" % (u_seq.shape, B, nu, nu, "" if K is None else " with K = %d" % int(K)))
+            u_seq = self._u_seq_array(u_seq, K)
             K = u_seq.shape[1]
-            u_seq = np.ascontiguousarray(u_seq)
         K = self.N_tilde if K is None else int(K)
-        if u_prev is not None and not policy:
-            raise ValueError("u_prev given without policy=True (the open-loop rollout has no previous input)")
-        if policy and u_prev is not None:
-            u_prev = np.asarray(u_prev, dtype=np.float64)
-            if u_prev.shape == (nu,):
-                u_prev = np.broadcast_to(u_prev, (B, nu))
-            if u_prev.shape != (B, nu):
-                raise ValueError("u_prev has shape %s, expected (%d, %d) or (%d,)" % (u_prev.shape, B, nu, nu))
-            u_prev = np.ascontiguousarray(u_prev)
+        u_prev = self._u_prev_array(u_prev, policy)
         if (omega_seq is None) == (start is None) and nw:
             raise ValueError("exactly one of omega_seq and start must be given (%s)" % ("both are" if start is not None else "neither is"))
         st = None
@@ -985,6 +996,27 @@ class GpuProblem(object):
         """MIP start from the last solution, on device (mld_warm_start_from_previous): shift 0 = the plan as it is (warm_start=True of
         the reference's backend), shift k = moved k steps on with the last step repeated (after advance())"""
         check(_lib.load().mld_warm_start_from_previous(self._h, int(shift)))
+
+    def warm_start_from_rollout(self, resolve, policy=False, u_seq=None, u_prev=None, keep=False):
+        """MIP start from a rollout of the current x0 under the resident forecast, on device (mld_warm_start_from_rollout, kernels k_rollout[_policy] and
+        k_warm_from_rollout): the start for the instances warm_start_from_previous leaves without one, and for the first solve after an upload.
+        policy=True: the resident rule-based policy in closed loop over N_tilde steps (upload_policy; u_prev (batch, nu) / (nu,), None = the resident policy
+        state; u_seq only for passed-through channels); policy=False: the caller's u_seq (batch, N_tilde, nu) / (N_tilde, nu) -- another controller's plan,
+        its auxiliaries re-derived for this handle's forecast.  resolve: as rollout().  keep=True: an instance whose resident start is not 255 keeps it.
+        Returns dict(source (batch,) int32: 1 written, 0 kept, -1 infeasible auxiliaries, -2 the LDS solver declined, -3 not attempted (the last three: row
+        255 = no start); stats: dict(trajectories, written, kept, none)).  Nothing else on the handle changes; a problem without binaries gets no start and
+        an empty stats."""
+        B = self.batch
+        if u_seq is not None:
+            u_seq = self._u_seq_array(u_seq, self.N_tilde)
+        u_prev = self._u_prev_array(u_prev, policy)
+        aux = resolve.problem._h if resolve is not None and resolve.problem is not None else None
+        source, stats = np.zeros(B, np.int32), np.zeros(4, np.int64)
+        check(_lib.load().mld_warm_start_from_rollout(self._h, aux, 1 if policy else 0, _lib.dptr(u_seq), _lib.dptr(u_prev), _lib.MLD_START_KEEP if keep else 0,
+                                                      source.ctypes.data_as(C.POINTER(C.c_int32)), stats.ctypes.data_as(C.POINTER(C.c_int64))))
+        if not self.n_bin:
+            return dict(source=None, stats={})
+        return dict(source=source, stats=dict(trajectories=int(stats[0]), written=int(stats[1]), kept=int(stats[2]), none=int(stats[3])))
 
     def stage(self, x0_sets, omega_sets):
         """input sets of the uploaded batch's size resident in HBM (mld_stage_inputs): x0_sets (n_sets, batch, nx), omega_sets

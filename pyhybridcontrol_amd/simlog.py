@@ -211,3 +211,21 @@ def rollout_np(mats_list, dims, model_idx, x0, u_seq, omega_seq, resolve_fn, cos
                      None if cost_w is None else np.repeat(np.asarray(cost_w, dtype=np.float64).reshape(B, K, nv), S, axis=0), step_fn=lsim_k_reference_order,
                      policy=policy, u_prev=up)
     return {k: a.reshape((B, S) + a.shape[1:]) for k, a in out.items()}
+
+
+def start_from_rollout_np(v, end_status, bins, old=None):
+    """GpuProblem.warm_start_from_rollout's byte rule stated in numpy (kernel k_warm_from_rollout): v (B, N_tilde, nv) or (B, 1, N_tilde, nv) of a rollout with
+    S = 1, end_status (B,) or (B, 1), bins (n_bin,) the binaries' indices step * nv + pos (np.flatnonzero(GpuProblem.is_bin)), old (B, n_bin) the resident
+    start for keep=True, or None.  Row b: kept where old[b, 0] != 255; else v[b].ravel()[bins] > 0.5 (a NaN rounds to 0) where the trajectory ended 0, and
+    255 everywhere for any other ending.  Returns (start (B, n_bin) uint8, source (B,) int32: 1 written, 0 kept, -1 / -2 / -3 for the endings 1 / 2 / -1)."""
+    end = np.asarray(end_status).reshape(-1).astype(np.int64)
+    B = end.size
+    flat = np.asarray(v, dtype=np.float64).reshape(B, -1)
+    bins = np.asarray(bins, dtype=np.int64).reshape(-1)
+    start = np.where(end[:, None] == 0, flat[:, bins] > 0.5, 255).astype(np.uint8)
+    source = np.select([end == 0, end == 1, end == 2], [1, -1, -2], -3).astype(np.int32)
+    if old is not None:
+        old = np.asarray(old, dtype=np.uint8).reshape(B, bins.size)
+        kept = old[:, 0] != 255 if bins.size else np.zeros(B, bool)
+        start[kept], source[kept] = old[kept], 0
+    return start, source
