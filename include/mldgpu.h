@@ -126,6 +126,8 @@ typedef enum {
                                            of at most three tolerances; A/B of round 4's change) */
     MLD_DBG_LAZY_START = 1 << 17,       /* a MIP start is evaluated lazily (round 3: only when the deepening passes end without an
                                            incumbent) instead of before the root LP (A/B) */
+    MLD_DBG_SUMMARY_NO_PREFETCH = 1 << 18,  /* k_log_summary (mld_sim_log_summary) stages a record without the register prefetch of the next one: the path of
+                                           records wider than its registers hold, on any shape (results are bit-identical) */
     MLD_DBG_NO_SWEEP = 1 << 19,         /* no closing sweep before the in-kernel hand-off publishes a stopped search's open nodes */
     MLD_DBG_ASSERT_POSCTL = 1 << 20,    /* positive control of the assertion build (-DMLD_ASSERT): one index check fails */
     MLD_DBG_NO_PIVOT_PAIRS = 1 << 21,   /* every dual-simplex pivot updates the dictionary on its own instead of two consecutive pivots sharing
@@ -797,6 +799,48 @@ int mld_set_stage_cost(mld_problem_t *, const double *w_v, const double *w_y);
 int mld_sim_log_cost_begin(mld_problem_t *, const int64_t *start);
 int mld_download_sim_log_cost(mld_problem_t *, int first, int count, double *cost, double *price);
 int mld_download_cost_total(mld_problem_t *, double *total, int32_t *steps);
+
+/* ---- campaign KPIs: column statistics of the resident log ----------------------------------------------------------------------------------------------
+ * The reference's result of a campaign is grid_sim_dataframe, and every figure its plotting scripts quote is a column statistic of that frame over time
+ * (examples/residential_mg_with_pv_and_dewhs/plotting/plot_multi_sim_campaign.py:69-131): cost.sum(axis=0), p_exp.sum(axis=0) with p_exp = y - z
+ * (modelling/micro_grid_agents.py:750-753), y.sum(axis=0), mu[..., 0].sum(axis=0), mu[..., 1].sum(axis=0).  mld_sim_log_summary reduces records
+ * [first, first + count) of the resident log on the device (k_log_summary) instead of downloading them.
+ *
+ * KPI q (1 <= n_kpi <= MLD_KPI_MAX) of model m = model_idx[b] is a linear functional of a record, given by up to five per-model tables, each
+ * (n_models, n_kpi, width) or NULL: w_x (nx), w_v (nv), w_y (ny), w_omega (nomega), w_xk1 (nx).  A table that was not given adds no term at all.  For the
+ * given ones, in the order x, v, y, omega, x_k1:
+ *     s_t = sum_i w_t[m,q,i] * field_t[i]          (i ascending, from 0.0)
+ *     f   = the sum of the s_t, left to right, beginning with the first given one
+ *     f   = price[k,b,c] * f                        where price_chan[q] = c >= 0 (price_chan (n_kpi) or NULL = none priced): the price record of the armed
+ *                                                   stage cost (mld_sim_log_cost_begin)
+ * every product and every addition rounded on its own (no fused multiply-add), so the results are bit-identical to the numpy restatement
+ * (pyhybridcontrol_amd/simlog.py: summary_np).  thresh (n_models, n_kpi) or NULL = +inf.
+ * A record k counts for instance b -- is STEPPED -- if and only if x_k1[k,b,0] is not NaN: mld_sim_step_batch's own marking of a skipped instance.
+ * Per (b, q), over the stepped records of the range in ascending k -- each output (batch, n_kpi):
+ *     sum        sum = sum + f, from 0.0
+ *     min, min_step / max, max_step    by strict < / >: the first attaining record wins, a NaN never wins; the steps are absolute record indices;
+ *                +inf / -inf / -1 for an instance without a stepped record
+ *     n_above    records with f > thresh[m,q]
+ *     n_changes  stepped records whose f is != the previous stepped record's f in the range: the switch count of an input channel
+ * Per instance -- each output (batch):
+ *     n_stepped; vio_max, vio_step of the records' cons_vio by strict > (-inf / -1 when empty); n_vio: stepped records with cons_vio > vio_tol;
+ *     nodes_total (int64) over ALL records of the range; n_source (batch, 3): records with u_source == 0 / 1 / 2 (mld_download_sim_log_source), every
+ *     entry -1 when the log has no source array.
+ * Any output may be NULL.  count == 0 is valid and gives the empty values.  With w_v = mld_set_stage_cost's weights of channel 0, price_chan = 0 and
+ * n_chan = 1, sum is mld_download_cost_total's total and n_stepped its steps.
+ * The call reads the log and writes nothing on the handle: not the records, the count, the armed totals, the inputs, the plan or the start.  It runs on the
+ * problem's stream and waits for it.  Only the fields whose table is given are read (and element 0 of x_k1, cons_vio, nodes, u_source, and the price record
+ * where a KPI is priced), each byte once.
+ * MLD_ERR_INVALID before anything is queued, the argument named: no batch; a launched solve not finished; no log begun; a range outside [0, n_logged];
+ * n_kpi outside 1 .. MLD_KPI_MAX; all five tables NULL; a table of a variable the model has none of (w_y with ny == 0, w_omega with nomega == 0); a
+ * non-finite weight; a NaN thresh or vio_tol; price_chan[q] >= 0 without an armed stage cost; price_chan[q] >= n_chan; price_chan[q] < -1; a model without
+ * a state (nx == 0: nothing marks the stepped records); a record wider than the kernel's staging (768 doubles). */
+#define MLD_KPI_MAX 64      /* the lanes of a wave: one lane owns one KPI */
+int mld_sim_log_summary(mld_problem_t *, int first, int count, int n_kpi,
+                        const double *w_x, const double *w_v, const double *w_y, const double *w_omega, const double *w_xk1,
+                        const int32_t *price_chan, const double *thresh, double vio_tol,
+                        double *sum, double *min, double *max, int32_t *min_step, int32_t *max_step, int32_t *n_above, int32_t *n_changes,
+                        int32_t *n_stepped, double *vio_max, int32_t *vio_step, int32_t *n_vio, int64_t *nodes_total, int32_t *n_source);
 
 /* Per-instance telemetry of the last solve: time spent inside the solve kernel (device wall clock, ns) and
  * the number of dictionary rows the rank-1 updates touched (x *row_bytes x 2 = bytes streamed by pivots). */

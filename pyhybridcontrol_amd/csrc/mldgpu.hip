@@ -216,6 +216,7 @@ int mld_condense_f32(mld_model_t *m, int N_tilde, int flags, float *Phi_x, float
 #include "tighten.inc"          // host big-M tightening (namespace tighten)
 #include "kernels.inc"          // small kernels: cost assembly, receding horizon, MIP start, fills, statistics, result packing
 #include "prices.inc"           // k_price_cost, k_stage_cost and the two formulas they share with the host (mld_upload_prices and its consumers, api_prices.inc)
+#include "log_summary.inc"      // k_log_summary and the rule it shares with the host (mld_sim_log_summary, api_summary.inc)
 #include "handle.inc"           // BatchBufs, mld_problem, build_shape, ensure_batch; the host helpers the entry points are written from
 #include "merge.inc"            // in-kernel hand-off: reset of the queue and merge of its items, mld_debug_merge
 #include "api_create.inc"       // mld_problem_create / destroy / set_cost / get_opts / set_opts, mld_cost_assemble, mld_opts_*
@@ -226,4 +227,5 @@ int mld_condense_f32(mld_model_t *m, int N_tilde, int flags, float *Phi_x, float
 #include "api_start.inc"        // MIP start from a rollout of the resident forecast (rollout_impl with a StartCall; k_warm_from_rollout)
 #include "api_fallback.inc"     // fallback inputs for instances without a usable plan: plan memory, the fallback step (k_fallback_inputs, k_fallback_commit), its log
 #include "api_prices.inc"       // resident price profiles: the price library, the cost of a batch from price windows, the stage cost in the simulation log
+#include "api_summary.inc"      // campaign KPIs: column statistics of the resident log, reduced on the device
 #include "api_gather.inc"       // RCCL gather

@@ -980,6 +980,40 @@ class GpuProblem(object):
         check(_lib.load().mld_download_sim_log_source(self._h, first, K, out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out
 
+    def sim_log_summary(self, kpis, first=0, count=None, vio_tol=1e-6):
+        """column statistics of records [first, first + count) of the resident log, reduced on the device (mld_sim_log_summary, kernel k_log_summary;
+        count=None: all from first) -- the figures the reference quotes from grid_sim_dataframe, without downloading the records.  kpis: a
+        simlog.KpiTable over this problem's models.  Returns dict(names, sum, min, max (batch, n_kpi), min_step, max_step, n_above, n_changes (batch, n_kpi)
+        int32, n_stepped, vio_step, n_vio (batch,) int32, vio_max (batch,), nodes_total (batch,) int64, n_source (batch, 3) int32); simlog.summary_np
+        states the rule and gives the same bits from the downloaded log.  Nothing on the handle changes."""
+        from .simlog import KPI_TABLES
+        if kpis.n_models != self.model.n_models:
+            raise ValueError("the KPI table has %d models, the problem %d" % (kpis.n_models, self.model.n_models))
+        d = self.model.dims
+        want = dict(w_x=d["nx"], w_v=self.model.nv, w_y=d["ny"], w_omega=d["nomega"], w_xk1=d["nx"])
+        if kpis.widths != want:
+            raise ValueError("the KPI table was built for other dimensions (%s, this problem %s)" % (kpis.widths, want))
+        arr = kpis.arrays()
+        first = int(first)
+        if count is None:
+            count = self.sim_log_count()[0] - first
+        K, B, Q = int(count), self.batch, len(kpis)
+        if K < 0:
+            raise ValueError("sim_log_summary: first = %d lies beyond the %d logged steps" % (first, K + first))
+        out = dict(names=list(kpis.names), sum=np.zeros((B, Q)), min=np.zeros((B, Q)), max=np.zeros((B, Q)), min_step=np.zeros((B, Q), np.int32),
+                   max_step=np.zeros((B, Q), np.int32), n_above=np.zeros((B, Q), np.int32), n_changes=np.zeros((B, Q), np.int32),
+                   n_stepped=np.zeros(B, np.int32), vio_max=np.zeros(B), vio_step=np.zeros(B, np.int32), n_vio=np.zeros(B, np.int32),
+                   nodes_total=np.zeros(B, np.int64), n_source=np.zeros((B, 3), np.int32))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        tabs = [None if arr[k] is None else np.ascontiguousarray(arr[k]) for k in KPI_TABLES]
+        thr = None if arr["thresh"] is None else np.ascontiguousarray(arr["thresh"])
+        check(_lib.load().mld_sim_log_summary(
+            self._h, first, K, Q, *([_lib.dptr(t) for t in tabs] + [ip(arr["price_chan"]), _lib.dptr(thr), float(vio_tol)]),
+            _lib.dptr(out["sum"]), _lib.dptr(out["min"]), _lib.dptr(out["max"]), ip(out["min_step"]), ip(out["max_step"]), ip(out["n_above"]),
+            ip(out["n_changes"]), ip(out["n_stepped"]), _lib.dptr(out["vio_max"]), ip(out["vio_step"]), ip(out["n_vio"]),
+            out["nodes_total"].ctypes.data_as(C.POINTER(C.c_int64)), ip(out["n_source"])))
+        return out
+
     def set_warm_start(self, bin_start):
         """MIP start of the resident batch (mld_set_warm_start): (batch, n_bin) values of the binaries, a row starting with 255 = no
         start for that instance; None clears.  A full decision vector (batch, n) is accepted too (its binaries are rounded)."""

@@ -92,6 +92,174 @@ def to_mld_sim_log(log, instance, dims, k0=0):
     return out
 
 
+# ---- campaign KPIs: column statistics of the log over time (GpuProblem.sim_log_summary, kernel k_log_summary) ------------------------------------------
+KPI_MAX = 64                                                # MLD_KPI_MAX: one lane of a wave owns one KPI
+KPI_TABLES = ("w_x", "w_v", "w_y", "w_omega", "w_xk1")      # the order of the functional's terms
+_KPI_FIELDS = ("x", "v", "y", "omega", "x_k1")
+
+
+class KpiTable(object):
+    """The KPIs of one summary: each a linear functional of a record, f = w_x . x + w_v . v + w_y . y + w_omega . omega + w_xk1 . x_k1 (the given tables
+    only), optionally times the record's price of channel price_chan, with a threshold for n_above.  n_models per-model rows, dims as the model's."""
+
+    def __init__(self, n_models, dims):
+        self.n_models = int(n_models)
+        if self.n_models < 1:
+            raise ValueError("n_models = %r, expected at least one model" % (n_models,))
+        nv = sum(int(dims.get(k, 0)) for k in ("nu", "ndelta", "nz", "nmu"))
+        self.widths = dict(w_x=int(dims.get("nx", 0)), w_v=nv, w_y=int(dims.get("ny", 0)), w_omega=int(dims.get("nomega", 0)), w_xk1=int(dims.get("nx", 0)))
+        self.names, self._rows, self._chan, self._thresh = [], [], [], []
+
+    def __len__(self):
+        return len(self.names)
+
+    def add(self, name, w_x=None, w_v=None, w_y=None, w_omega=None, w_xk1=None, price_chan=None, thresh=None):
+        """one KPI: a vector (width,) broadcasts over the models, a (n_models, width) array gives one row per model; thresh a scalar or (n_models,).
+        ValueError on a duplicate name, a 65th KPI, no table at all, a table of a variable the model has none of, a shape that fits neither, a non-finite
+        weight, a NaN threshold, price_chan < 0."""
+        given = dict(w_x=w_x, w_v=w_v, w_y=w_y, w_omega=w_omega, w_xk1=w_xk1)
+        if name in self.names:
+            raise ValueError("a KPI named %r has been added already" % (name,))
+        if len(self.names) >= KPI_MAX:
+            raise ValueError("a summary holds at most %d KPIs" % KPI_MAX)
+        if all(t is None for t in given.values()):
+            raise ValueError("KPI %r: no table given (w_x, w_v, w_y, w_omega, w_xk1)" % (name,))
+        row = {}
+        for key, t in given.items():
+            if t is None:
+                continue
+            W, M = self.widths[key], self.n_models
+            t = np.asarray(t, dtype=np.float64)
+            if W == 0:
+                raise ValueError("KPI %r: %s given but the model has none of that variable" % (name, key))
+            if t.shape not in ((W,), (M, W)):
+                raise ValueError("KPI %r: %s has shape %s, expected (%d,) or (%d, %d)" % (name, key, t.shape, W, M, W))
+            if not np.all(np.isfinite(t)):
+                raise ValueError("KPI %r: %s has a non-finite entry" % (name, key))
+            row[key] = np.array(np.broadcast_to(t, (M, W)))
+        if price_chan is not None and int(price_chan) < 0:
+            raise ValueError("KPI %r: price_chan = %r, expected a channel >= 0 or None" % (name, price_chan))
+        th = None
+        if thresh is not None:
+            th = np.asarray(thresh, dtype=np.float64)
+            if th.shape not in ((), (self.n_models,)) or np.any(np.isnan(th)):
+                raise ValueError("KPI %r: thresh %r, expected a scalar or (%d,) without NaN" % (name, thresh, self.n_models))
+            th = np.array(np.broadcast_to(th, (self.n_models,)))
+        self.names.append(name)
+        self._rows.append(row)
+        self._chan.append(-1 if price_chan is None else int(price_chan))
+        self._thresh.append(th)
+        return self
+
+    def arrays(self):
+        """the arguments of mld_sim_log_summary: dict(w_x .. w_xk1 (n_models, n_kpi, width) or None where NO KPI gave that table -- a KPI that did not
+        give a table another one gave has zeros there --, price_chan (n_kpi,) int32 with -1 = not priced, thresh (n_models, n_kpi) or None)"""
+        Q, M = len(self.names), self.n_models
+        if Q < 1:
+            raise ValueError("the table holds no KPI")
+        out = {}
+        for key in KPI_TABLES:
+            if not any(key in r for r in self._rows):
+                out[key] = None
+                continue
+            t = np.zeros((M, Q, self.widths[key]))
+            for q, r in enumerate(self._rows):
+                if key in r:
+                    t[:, q, :] = r[key]
+            out[key] = t
+        out["price_chan"] = np.asarray(self._chan, dtype=np.int32)
+        out["thresh"] = None
+        if any(t is not None for t in self._thresh):
+            out["thresh"] = np.stack([np.full(M, np.inf) if t is None else t for t in self._thresh], axis=1)
+        return out
+
+    @classmethod
+    def microgrid(cls, dims, n_models=1, price_chan=None):
+        """the reference's columns for the synthetic.make_agent(tie=True) models, v = [u; delta; z; mu], y = the grid power: p_imp = z, p_exp = y - z
+        (micro_grid_agents.py:750-753), cost = z * price of channel price_chan (:753; left out with price_chan=None), mu_over / mu_under = the comfort
+        violations over and under (mu[0::2], mu[1::2]; n_above counts the records where they are positive), and one selector per input channel u_0 ..
+        whose n_changes is that channel's switch count"""
+        nu, nd, nz, nmu, ny = (int(dims.get(k, 0)) for k in ("nu", "ndelta", "nz", "nmu", "ny"))
+        if nz < 1 or ny < 1:
+            raise ValueError("KpiTable.microgrid needs a model with a grid tie (nz >= 1, ny >= 1), got nz = %d, ny = %d" % (nz, ny))
+        nv, z, mu0 = nu + nd + nz + nmu, nu + nd, nu + nd + nz
+
+        def unit(n, at, val=1.0):
+            e = np.zeros(n)
+            e[at] = val
+            return e
+        t = cls(n_models, dims)
+        t.add("p_imp", w_v=unit(nv, z))
+        t.add("p_exp", w_v=unit(nv, z, -1.0), w_y=unit(ny, 0))
+        if price_chan is not None:
+            t.add("cost", w_v=unit(nv, z), price_chan=price_chan)
+        t.add("mu_over", w_v=unit(nv, np.arange(mu0, nv, 2)), thresh=0.0)
+        t.add("mu_under", w_v=unit(nv, np.arange(mu0 + 1, nv, 2)), thresh=0.0)
+        for j in range(nu):
+            t.add("u_%d" % j, w_v=unit(nv, j))
+        return t
+
+
+def summary_np(log, kpis, model_idx, price=None, source=None, vio_tol=1e-6, first=0):
+    """GpuProblem.sim_log_summary stated in numpy, in the kernel's order: log as GpuProblem.sim_log(first, count) returns it, kpis a KpiTable, model_idx
+    (batch,) or None, price (count, batch, n_chan) = sim_log_cost()["price"] (needed by a priced KPI), source (count, batch) = sim_log_source() or None
+    (the log has no source array: n_source is -1), first: the absolute index of the log's row 0.
+
+    The rule: a record k counts for instance b -- is STEPPED -- iff x_k1[k, b, 0] is not NaN.  s_t = sum_i w_t[m, q, i] * field_t[i] with i ascending
+    from 0.0; f = the s_t of the given tables, x, v, y, omega, x_k1, added left to right beginning with the first; f = price[k, b, c] * f where
+    price_chan[q] = c >= 0.  The loops over k and i are explicit (numpy only spans (b, q), element by element), so every product and every addition is
+    rounded on its own in the stated order."""
+    arr = kpis.arrays()
+    x_k1 = np.asarray(log["x_k1"], dtype=np.float64)
+    K, B = x_k1.shape[0], x_k1.shape[1]
+    Q = len(kpis)
+    midx = np.zeros(B, dtype=np.int64) if model_idx is None else np.asarray(model_idx, dtype=np.int64).reshape(B)
+    chan = arr["price_chan"]
+    if np.any(chan >= 0) and price is None:
+        raise ValueError("a KPI is priced (price_chan >= 0): summary_np needs price (sim_log_cost()['price'])")
+    thr = np.full((B, Q), np.inf) if arr["thresh"] is None else arr["thresh"][midx]
+    out = dict(names=list(kpis.names), sum=np.zeros((B, Q)), min=np.full((B, Q), np.inf), max=np.full((B, Q), -np.inf),
+               min_step=np.full((B, Q), -1, np.int32), max_step=np.full((B, Q), -1, np.int32), n_above=np.zeros((B, Q), np.int32),
+               n_changes=np.zeros((B, Q), np.int32), n_stepped=np.zeros(B, np.int32), vio_max=np.full(B, -np.inf), vio_step=np.full(B, -1, np.int32),
+               n_vio=np.zeros(B, np.int32), nodes_total=np.zeros(B, np.int64), n_source=np.full((B, 3), -1 if source is None else 0, np.int32))
+    prev, have_prev = np.zeros((B, Q)), np.zeros((B, 1), bool)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for k in range(K):
+            step = int(first) + k
+            f, started = np.zeros((B, Q)), False
+            for key, name in zip(KPI_TABLES, _KPI_FIELDS):
+                if arr[key] is None:
+                    continue
+                w, fld = arr[key][midx], np.asarray(log[name][k], dtype=np.float64)      # (B, Q, width), (B, width)
+                s = np.zeros((B, Q))
+                for i in range(w.shape[2]):
+                    t = w[:, :, i] * fld[:, i:i + 1]
+                    s = s + t
+                f = f + s if started else s
+                started = True
+            for q in np.flatnonzero(chan >= 0):
+                f[:, q] = np.asarray(price[k], dtype=np.float64)[:, chan[q]] * f[:, q]
+            stepped = ~np.isnan(x_k1[k, :, 0])
+            on = stepped[:, None]
+            out["sum"] = np.where(on, out["sum"] + f, out["sum"])
+            lo, hi = on & (f < out["min"]), on & (f > out["max"])
+            out["min"], out["min_step"] = np.where(lo, f, out["min"]), np.where(lo, step, out["min_step"]).astype(np.int32)
+            out["max"], out["max_step"] = np.where(hi, f, out["max"]), np.where(hi, step, out["max_step"]).astype(np.int32)
+            out["n_above"] += on & (f > thr)
+            out["n_changes"] += on & have_prev & (f != prev)
+            prev, have_prev = np.where(on, f, prev), have_prev | on
+            vio = np.asarray(log["cons_vio"][k], dtype=np.float64)
+            out["n_stepped"] += stepped
+            worse = stepped & (vio > out["vio_max"])
+            out["vio_max"], out["vio_step"] = np.where(worse, vio, out["vio_max"]), np.where(worse, step, out["vio_step"]).astype(np.int32)
+            out["n_vio"] += stepped & (vio > vio_tol)
+            out["nodes_total"] += np.asarray(log["nodes"][k], dtype=np.int64)
+            if source is not None:
+                for s in range(3):
+                    out["n_source"][:, s] += np.asarray(source[k]) == s
+    return out
+
+
 # ---- open-loop rollout: the reference's MldModel.lsim, lsim_k in a loop (models/mld_model.py:543-642, 647-699) with _compute_aux (:701-766) per step ----
 def _worst(vio):
     """(worst_vio, worst_step) of cons_vio rows (T, K): the largest value, a NaN wins, the earliest step of equals"""
