@@ -842,6 +842,39 @@ int mld_sim_log_summary(mld_problem_t *, int first, int count, int n_kpi,
                         double *sum, double *min, double *max, int32_t *min_step, int32_t *max_step, int32_t *n_above, int32_t *n_changes,
                         int32_t *n_stepped, double *vio_max, int32_t *vio_step, int32_t *n_vio, int64_t *nodes_total, int32_t *n_source);
 
+/* ---- rollout KPIs: the same column statistics per rolled-out trajectory -----------------------------------------------------------------------------------
+ * mld_rollout_kpi is mld_rollout_batch (policy == 0: u_prev and switches_out are ignored, no resident policy is needed) or mld_rollout_policy (policy != 0)
+ * with the KPIs of mld_sim_log_summary reduced inside the rollout kernel (k_rollout_kpi / k_rollout_policy_kpi, two more instantiations of k_rollout's
+ * body): what the reference quotes per MPC variant against `thermo` (plot_multi_sim_campaign.py:69-131), for batch x S trajectories of K steps in one
+ * launch, without a log, a download of the trajectories or an armed stage cost.  Every argument, ending and output of the two means what it means there and
+ * stays available in the same call.
+ *
+ * The record of trajectory (b, c) at step k in [0, K) is x = x_k, v = v_k = [u; delta; z; mu], y = y_k, omega = the nomega realised values of step k (not
+ * the resolver's [omega; u]) and x_k1 = x_{k+1}.  KPI q of model m = model_idx[b] is mld_sim_log_summary's functional of it -- n_kpi, w_x .. w_xk1,
+ * price_chan and thresh as there, the same order of operations, no fused multiply-add -- and where price_chan[q] = ch >= 0
+ *     f = price * f,   price = lib[price_start[b] + (step + k) * n_chan + ch]
+ * of the resident price library (mld_upload_prices): price_start (batch) int64, one tariff for the S realisations of an instance, `step` the rollout's own
+ * step, so that step k sees the price mld_sim_step_*(step = step + k) records in a log armed with the same starts.  The price window is the price library's
+ * window rule with K steps: 0 <= price_start[b] and price_start[b] + (step + K) * n_chan <= lib_len.
+ * Per (b, c, q) over k ascending -- each output (batch, S, n_kpi): sum, min / min_step, max / max_step, n_above, n_changes as mld_sim_log_summary defines
+ * them, the steps being k itself (the record indices of a log begun at 0); per (b, c): n_vio (batch, S), the steps with cons_vio > vio_tol.  The figures
+ * are bit-identical to those of the logged route -- K advancing mld_sim_step_resolve / mld_sim_step_policy steps of realisation c, then
+ * mld_sim_log_summary -- and to simlog.py: rollout_kpis_np on the trajectories.  A trajectory that does not end 0 (infeasible, declined, not attempted)
+ * gets NaN in every double and -1 in every integer, the convention of cost_out / mu_total_out / switches_out.  Any output may be NULL.
+ * The call is host-synchronous and writes nothing on the handle: inputs, plan, MIP start, log, policy state, resident starts and an armed stage cost stay.
+ * MLD_ERR_INVALID before anything is queued, the argument named: everything mld_rollout_batch (and, with policy != 0, mld_rollout_policy) refuses; n_kpi
+ * outside 1 .. MLD_KPI_MAX; all five tables NULL; a table of a variable the model has none of; a non-finite weight; a NaN thresh or vio_tol; price_chan[q]
+ * outside [-1, n_chan); a priced KPI without a resident price library or with price_start == NULL; a price start whose window leaves the library (the
+ * first offender is named); a staging that, with its 6 n_kpi doubles of accumulators, no longer fits a wave's share of LDS. */
+int mld_rollout_kpi(mld_problem_t *p, mld_problem_t *aux, int policy, int K, int S, const double *u_seq, const double *u_prev, const double *omega_seq,
+                    const int64_t *start, int step, const double *cost_w, int cost_rows, int n_kpi,
+                    const double *w_x, const double *w_v, const double *w_y, const double *w_omega, const double *w_xk1,
+                    const int32_t *price_chan, const double *thresh, double vio_tol, const int64_t *price_start,
+                    double *x_out, double *v_out, double *y_out, double *cons_vio_out, int32_t *cons_row_out,
+                    double *cost_out, double *mu_total_out, double *worst_vio_out, int32_t *worst_step_out, int32_t *steps_done_out, int32_t *end_status_out,
+                    int32_t *switches_out, int64_t stats[4],
+                    double *sum, double *min, double *max, int32_t *min_step, int32_t *max_step, int32_t *n_above, int32_t *n_changes, int32_t *n_vio);
+
 /* Per-instance telemetry of the last solve: time spent inside the solve kernel (device wall clock, ns) and
  * the number of dictionary rows the rank-1 updates touched (x *row_bytes x 2 = bytes streamed by pivots). */
 int mld_download_telemetry(mld_problem_t *, int64_t *latency_ns, int64_t *rows_updated, int64_t *row_bytes);

@@ -5,9 +5,13 @@
  * sc (mld_warm_start_from_rollout, api_start.inc): a third way to name the disturbance -- the RESIDENT FORECAST, bat.omega (batch, N_tilde nomega), which is
  * step-major and so already the (batch, 1, K, nomega) the kernels read: K = N_tilde, S = 1, nothing uploaded or copied -- and v / end_status stay on the device:
  * k_warm_from_rollout, queued behind the rollout on the same stream, turns them into the MIP start.  The forecast is fp64 on every handle, MLD_F32 included
- * (the flag moves GEMMs to fp32, never the inputs), so the start comes from the buffers the rollout reads anyway and nothing is converted. */
+ * (the flag moves GEMMs to fp32, never the inputs), so the start comes from the buffers the rollout reads anyway and nothing is converted.
+ * kc (mld_rollout_kpi): the KPI instantiations k_rollout_kpi / k_rollout_policy_kpi -- the column statistics of every trajectory, reduced inside the
+ * kernel.  Its tables are tested as mld_sim_log_summary tests them, its price starts by the price library's window rule with len = K, the weights are laid
+ * out KPI-minor as k_log_summary reads them, and everything it uploads and the kernel writes lives in temporaries of the call. */
 static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p, mld_problem_t *aux, int K, int S, const double *u_seq, const double *omega_seq,
-                        const int64_t *start, int step, const double *cost_w, int cost_rows, const RolloutOut &out, const StartCall *sc = nullptr)
+                        const int64_t *start, int step, const double *cost_w, int cost_rows, const RolloutOut &out, const StartCall *sc = nullptr,
+                        const KpiCall *kc = nullptr)
 {
     double *const x_out = out.x, *const v_out = out.v, *const y_out = out.y, *const cons_vio_out = out.cons_vio, *const cost_out = out.cost,
            *const mu_total_out = out.mu_total, *const worst_vio_out = out.worst_vio;
@@ -31,7 +35,39 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
         }
         if (aux->has_quad || aux->ic_ld || aux->has_fixed) { mld_set_error("%s: aux has a quadratic or per-instance cost, or fixed binaries (the rollout minimises the resolver's model cost, sum(mu), with every binary free)", who); return MLD_ERR_INVALID; }
     }
-    const size_t stage_d = ro_stage_doubles(nx, nu, nw, aux ? aux->m0 : 0, nv, ny);
+    /* the KPI tables: mld_sim_log_summary's tests, where they apply */
+    const int n_kpi = kc ? kc->n_kpi : 0, n_models = p->n_models, C = p->pr_chan;
+    const int kw[5] = {nx, nv, ny, nw, nx};
+    int k_rows = 0; unsigned k_given = 0; bool priced = false;
+    if (kc) {
+        static const char *const names[5] = {"w_x", "w_v", "w_y", "w_omega", "w_xk1"};
+        if (n_kpi < 1 || n_kpi > MLD_KPI_MAX) { mld_set_error("%s: n_kpi = %d (1 .. MLD_KPI_MAX = %d)", who, n_kpi, MLD_KPI_MAX); return MLD_ERR_INVALID; }
+        if (!kc->tab[0] && !kc->tab[1] && !kc->tab[2] && !kc->tab[3] && !kc->tab[4]) { mld_set_error("%s: w_x, w_v, w_y, w_omega and w_xk1 are all NULL: a KPI needs a table", who); return MLD_ERR_INVALID; }
+        for (int t = 0; t < 5; ++t) {
+            if (!kc->tab[t]) continue;
+            if (kw[t] == 0) { mld_set_error("%s: %s given but the model has none of that variable (width 0)", who, names[t]); return MLD_ERR_INVALID; }
+            const size_t len = (size_t)n_models * n_kpi * kw[t];
+            for (size_t i = 0; i < len; ++i) if (!std::isfinite(kc->tab[t][i])) {
+                mld_set_error("%s: %s of model %zu, KPI %zu, entry %zu is not finite (%g)", who, names[t], i / ((size_t)n_kpi * kw[t]), i / kw[t] % n_kpi, i % kw[t], kc->tab[t][i]);
+                return MLD_ERR_INVALID;
+            }
+            k_given |= 1u << t; k_rows += kw[t];
+        }
+        if (kc->thresh) for (size_t i = 0; i < (size_t)n_models * n_kpi; ++i) if (std::isnan(kc->thresh[i])) {
+            mld_set_error("%s: thresh of model %zu, KPI %zu is NaN", who, i / n_kpi, i % n_kpi); return MLD_ERR_INVALID;
+        }
+        if (std::isnan(kc->vio_tol)) { mld_set_error("%s: vio_tol is NaN", who); return MLD_ERR_INVALID; }
+        if (kc->price_chan) for (int q = 0; q < n_kpi; ++q) {
+            const int c = kc->price_chan[q];
+            if (c < -1) { mld_set_error("%s: price_chan[%d] = %d (-1 = not priced, or a channel 0 .. n_chan - 1)", who, q, c); return MLD_ERR_INVALID; }
+            if (c >= 0 && !p->pr_len) { mld_set_error("%s: price_chan[%d] = %d, but no price library is resident (mld_upload_prices)", who, q, c); return MLD_ERR_INVALID; }
+            if (c >= C) { mld_set_error("%s: price_chan[%d] = %d, but the price library has n_chan = %d", who, q, c, C); return MLD_ERR_INVALID; }
+            if (c >= 0 && !kc->price_start) { mld_set_error("%s: price_chan[%d] = %d, but price_start is NULL (the starts of the realised prices, one per instance)", who, q, c); return MLD_ERR_INVALID; }
+            priced = priced || c >= 0;
+        }
+        if (priced) { std::vector<long long> pmax; if (int rc = check_starts(price_lib(p), who, PF_PRICE, kc->price_start, batch, 1, step, K, pmax)) return rc; }
+    }
+    const size_t stage_d = ro_stage_doubles(nx, nu, nw, aux ? aux->m0 : 0, nv, ny, n_kpi);
     if (sizeof(double) * stage_d > SM_WAVE_BUDGET) {
         mld_set_error("%s: the staging of a trajectory (%zu bytes: x, omega', h, v, y, x_k1) does not fit a wave's share of LDS (%d bytes); step with mld_sim_step_resolve", who, sizeof(double) * stage_d, SM_WAVE_BUDGET);
         return MLD_ERR_INVALID;
@@ -82,6 +118,8 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
     const hipStream_t sq = p->stream;
     const size_t Kz = (size_t)K;
     DevBuf<double> d_u, d_om, d_cw, d_x, d_v, d_y, d_vio, d_cost, d_mu, d_wv, d_uprev; DevBuf<int> d_row, d_ws, d_sd, d_es, d_sw; DevBuf<long long> d_start; DevBuf<unsigned long long> d_cnt;
+    DevBuf<double> d_kW, d_kthr, d_ksum, d_kmin, d_kmax; DevBuf<int> d_kpc, d_kmins, d_kmaxs, d_kabove, d_kchg, d_knvio; DevBuf<long long> d_kps;      /* kc */
+    std::vector<double> hW, hthr; std::vector<int> hpc;
     DevBuf<unsigned char> d_old; DevBuf<int> d_src;      /* sc: the resident start as it was (where rows are kept), the source per instance */
     if (pc && !pc->u_prev) { if (int rc = policy_state_ready(p, who)) return rc; }      /* (an upload's reset state, laid out on first use: nothing a caller can see changes) */
     if (pc && pc->u_prev) HIP_TRY(d_uprev.alloc(std::max<size_t>(1, (size_t)batch * nu)));
@@ -104,6 +142,25 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
         if (keep_rows) HIP_TRY(d_old.alloc(warm_len));
         src_host.resize((size_t)batch);
     }
+    const size_t tq = T * (size_t)n_kpi, mq = (size_t)n_models * n_kpi;
+    if (kc) {      /* the tables side by side, KPI-minor: W[m, row, q] (mld_sim_log_summary's layout) */
+        hW.resize((size_t)n_models * k_rows * n_kpi); hthr.assign(mq, std::numeric_limits<double>::infinity()); hpc.assign(n_kpi, -1);
+        for (int m = 0; m < n_models; ++m) {
+            int row = 0;
+            for (int t = 0; t < 5; ++t) {
+                if (!kc->tab[t]) continue;
+                for (int q = 0; q < n_kpi; ++q)
+                    for (int i = 0; i < kw[t]; ++i) hW[((size_t)m * k_rows + row + i) * n_kpi + q] = kc->tab[t][((size_t)m * n_kpi + q) * kw[t] + i];
+                row += kw[t];
+            }
+        }
+        if (kc->thresh) std::copy(kc->thresh, kc->thresh + mq, hthr.begin());
+        if (kc->price_chan) std::copy(kc->price_chan, kc->price_chan + n_kpi, hpc.begin());
+        HIP_TRY(d_kW.alloc(hW.size())); HIP_TRY(d_kthr.alloc(mq)); HIP_TRY(d_kpc.alloc(n_kpi));
+        if (priced) HIP_TRY(d_kps.alloc(batch));
+        HIP_TRY(d_ksum.alloc(tq)); HIP_TRY(d_kmin.alloc(tq)); HIP_TRY(d_kmax.alloc(tq)); HIP_TRY(d_kmins.alloc(tq)); HIP_TRY(d_kmaxs.alloc(tq));
+        HIP_TRY(d_kabove.alloc(tq)); HIP_TRY(d_kchg.alloc(tq)); HIP_TRY(d_knvio.alloc(T));
+    }
     HIP_TRY(d_cnt.alloc(4));
     RoDev a{};
     a.batch = batch; a.S = S; a.K = K;
@@ -124,7 +181,14 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
     if (aux) P = problem_dev(aux);
     RoPolicyDev pd{};
     if (pc) { pd.tab = p->pol_tab; pd.tab_len = (size_t)nu * (nx + POL_TAIL); pd.u_prev = pc->u_prev ? d_uprev.get() : p->pol_uprev.get(); pd.switches = d_sw; }
-    const void *kernel = pc ? (const void *)k_rollout_policy : (const void *)k_rollout;
+    RoKpiDev kd{};
+    if (kc) {
+        kd.n_kpi = n_kpi; kd.rows = k_rows; kd.n_chan = C; kd.step = step; kd.given = k_given; kd.vio_tol = kc->vio_tol;
+        kd.W = d_kW; kd.thresh = d_kthr; kd.price_chan = d_kpc;
+        if (priced) { kd.lib = p->pr_lib; kd.price_start = d_kps; }
+        kd.sum = d_ksum; kd.min = d_kmin; kd.max = d_kmax; kd.min_step = d_kmins; kd.max_step = d_kmaxs; kd.n_above = d_kabove; kd.n_changes = d_kchg; kd.n_vio = d_knvio;
+    }
+    const void *kernel = kc ? (pc ? (const void *)k_rollout_policy_kpi : (const void *)k_rollout_kpi) : (pc ? (const void *)k_rollout_policy : (const void *)k_rollout);
     if (lds_bytes > 48 * 1024)
         HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     int dev = 0, per_cu = 0; hipDeviceProp_t prop;
@@ -145,7 +209,15 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
                                p->pf_chan.get(), step, p->pf_lib.get(), d_om.get());
             HIP_TRY(hipGetLastError());
         }
-        if (pc) hipLaunchKernelGGL(k_rollout_policy, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a, pd);
+        if (kc) {
+            HIP_TRY(hipMemcpyAsync(d_kW, hW.data(), sizeof(double) * hW.size(), hipMemcpyHostToDevice, sq));
+            HIP_TRY(hipMemcpyAsync(d_kthr, hthr.data(), sizeof(double) * mq, hipMemcpyHostToDevice, sq));
+            HIP_TRY(hipMemcpyAsync(d_kpc, hpc.data(), sizeof(int) * n_kpi, hipMemcpyHostToDevice, sq));
+            if (priced) HIP_TRY(hipMemcpyAsync(d_kps, kc->price_start, sizeof(long long) * (size_t)batch, hipMemcpyHostToDevice, sq));
+        }
+        if (kc && pc) hipLaunchKernelGGL(k_rollout_policy_kpi, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a, pd, kd);
+        else if (kc) hipLaunchKernelGGL(k_rollout_kpi, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a, kd);
+        else if (pc) hipLaunchKernelGGL(k_rollout_policy, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a, pd);
         else hipLaunchKernelGGL(k_rollout, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a);
         HIP_TRY(hipGetLastError());
         auto get = [&](auto *out, const auto &buf, size_t count) -> hipError_t {
@@ -155,6 +227,10 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
         HIP_TRY(get(cost_out, d_cost, T)); HIP_TRY(get(mu_total_out, d_mu, T)); HIP_TRY(get(worst_vio_out, d_wv, T));
         HIP_TRY(get(worst_step_out, d_ws, T)); HIP_TRY(get(steps_done_out, d_sd, T)); HIP_TRY(get(end_status_out, d_es, T));
         if (pc) HIP_TRY(get(pc->switches_out, d_sw, T));
+        if (kc) {
+            HIP_TRY(get(kc->sum, d_ksum, tq)); HIP_TRY(get(kc->min, d_kmin, tq)); HIP_TRY(get(kc->max, d_kmax, tq)); HIP_TRY(get(kc->min_step, d_kmins, tq));
+            HIP_TRY(get(kc->max_step, d_kmaxs, tq)); HIP_TRY(get(kc->n_above, d_kabove, tq)); HIP_TRY(get(kc->n_changes, d_kchg, tq)); HIP_TRY(get(kc->n_vio, d_knvio, T));
+        }
         HIP_TRY(hipMemcpyAsync(cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, sq));
         if (sc) {
             if (keep_rows) HIP_TRY(hipMemcpyAsync(d_old, p->bat.warm, warm_len, hipMemcpyDeviceToDevice, sq));
@@ -193,6 +269,25 @@ int mld_rollout_batch(mld_problem_t *p, mld_problem_t *aux, int K, int S, const 
     if (int rc = entry_guard(p, who, true, "no batch resident (mld_upload_batch)")) return rc;
     const RolloutOut out{x_out, v_out, y_out, cons_vio_out, cons_row_out, cost_out, mu_total_out, worst_vio_out, worst_step_out, steps_done_out, end_status_out, stats};
     return rollout_impl(who, nullptr, p, aux, K, S, u_seq, omega_seq, start, step, cost_w, cost_rows, out);
+}
+
+/* mld_rollout_batch (policy == 0) or mld_rollout_policy (policy != 0) with the column statistics of every trajectory reduced inside the kernel
+ * (k_rollout_kpi / k_rollout_policy_kpi): rollout_impl with a KpiCall, so every refusal of the two is made by the same code. */
+int mld_rollout_kpi(mld_problem_t *p, mld_problem_t *aux, int policy, int K, int S, const double *u_seq, const double *u_prev, const double *omega_seq,
+                    const int64_t *start, int step, const double *cost_w, int cost_rows, int n_kpi,
+                    const double *w_x, const double *w_v, const double *w_y, const double *w_omega, const double *w_xk1,
+                    const int32_t *price_chan, const double *thresh, double vio_tol, const int64_t *price_start,
+                    double *x_out, double *v_out, double *y_out, double *cons_vio_out, int32_t *cons_row_out,
+                    double *cost_out, double *mu_total_out, double *worst_vio_out, int32_t *worst_step_out, int32_t *steps_done_out, int32_t *end_status_out,
+                    int32_t *switches_out, int64_t stats[4],
+                    double *sum, double *min, double *max, int32_t *min_step, int32_t *max_step, int32_t *n_above, int32_t *n_changes, int32_t *n_vio)
+{
+    static const char who[] = "mld_rollout_kpi";
+    if (int rc = entry_guard(p, who, true, "no batch resident (mld_upload_batch)")) return rc;
+    const PolicyCall pc{u_prev, switches_out};
+    const RolloutOut out{x_out, v_out, y_out, cons_vio_out, cons_row_out, cost_out, mu_total_out, worst_vio_out, worst_step_out, steps_done_out, end_status_out, stats};
+    const KpiCall kc{n_kpi, {w_x, w_v, w_y, w_omega, w_xk1}, price_chan, thresh, vio_tol, price_start, sum, min, max, min_step, max_step, n_above, n_changes, n_vio};
+    return rollout_impl(who, policy ? &pc : nullptr, p, aux, K, S, u_seq, omega_seq, start, step, cost_w, cost_rows, out, nullptr, &kc);
 }
 
 } // extern "C"

@@ -367,6 +367,15 @@ template <typename Queue> static int queue_and_wait(hipStream_t sq, Queue &&queu
  * state) and where the switch counts go */
 struct PolicyCall { const double *u_prev; int32_t *switches_out; };
 
+/* What mld_rollout_kpi adds to the same body: the KPI tables of mld_sim_log_summary (each (n_models, n_kpi, width) or NULL), the starts into the price
+ * library (batch, or NULL) and where the statistics go: sum, min, max, min_step, max_step, n_above, n_changes (batch, S, n_kpi), n_vio (batch, S); any NULL */
+struct KpiCall {
+    int n_kpi;
+    const double *tab[5];      /* w_x, w_v, w_y, w_omega, w_xk1 */
+    const int32_t *price_chan; const double *thresh; double vio_tol; const int64_t *price_start;
+    double *sum, *min, *max; int32_t *min_step, *max_step, *n_above, *n_changes, *n_vio;
+};
+
 /* Where the results of a rollout go on the host, in the order of the entry points' arguments: per trajectory and step x (K + 1 states), v, y, cons_vio,
  * cons_row; per trajectory cost, mu_total, worst_vio, worst_step, steps_done, end_status; stats[4].  Any may be NULL: not asked for */
 struct RolloutOut {

@@ -41,8 +41,9 @@
 #define LS_NO_CONTRACT _Pragma("STDC FP_CONTRACT OFF")
 #endif
 
-// s = sum_i w[i * w_stride] * f[i], i ascending, from 0.0
-LS_FN double ls_dot(const double *w, size_t w_stride, const double *f, int n)
+// s = sum_i w[i * w_stride] * f[i], i ascending, from 0.0.  F: the field's element type -- double behind a generic pointer (k_log_summary, the host), or the
+// rollout's LDS staging (sm_f64: ro_run's KPI variant, rollout.inc); the arithmetic is the same fp64 either way
+template <typename F> LS_FN double ls_dot(const double *w, size_t w_stride, const F *f, int n)
 {
     LS_NO_CONTRACT
     double s = 0.0;

@@ -21,10 +21,20 @@
 // controllers/theromstat_control.py:38-64), stepped through sim_step_k --, lanes on channels, the selector row summed over x in LDS, u_{k-1} read from v's
 // own block before the lane overwrites it: the staging grows by nothing.  The tables are read from global memory per step, nu (nx + 5) doubles per model:
 // per channel [sel (nx) | on_at | off_at | u_on | u_off | mode].  The flag is a template parameter; the open-loop instantiation compiles to what it compiled to.
+//
+// k_rollout_kpi / k_rollout_policy_kpi (mld_rollout_kpi) are the same body with ro_run's second flag: the campaign's column statistics (log_summary.inc: THE
+// RULE) of every trajectory, reduced where its records already lie.  In step 5 the record of step k -- x_k, v_k, y_k, omega_k, x_{k+1} -- is the staging itself
+// (xs, vs, ys, ws[0 .. nw), xn), so lane q < n_kpi evaluates KPI q from LDS (every lane the same address: broadcasts) against the weights k_log_summary reads,
+// (n_models, rows, n_kpi) KPI-minor, by the functions k_log_summary calls: the figures are the ones the logged stepwise route gives, bit for bit, and the only
+// new HBM traffic is the weights (cached) and one price per step.  A priced KPI multiplies by lib[price_start[b] + (step + k) n_chan + ch], the price
+// sim_step(step = step + k) records.  The accumulators live in the wave's LDS behind x_{k+1}, 6 n_kpi doubles [sum | min | max | prev | min_step, max_step |
+// n_above, n_changes] (ro_stage_doubles): across sm_solve they cost no register -- k_rollout already spills at its bound -- and with SM_HOST one lane walks all
+// n_kpi of them.  A trajectory that does not end 0 gets NaN / -1.
 #pragma once
 
 #include "plant_step.inc"
 #include "small_lds.inc"
+#include "log_summary.inc"
 
 struct RoModel {      // one trajectory's model: the step matrices inside the packed block, the resolver's maps and row scales
     int nx, nu, nw, nv, nmu, ny, nc;
@@ -43,6 +53,15 @@ struct RoTraj {       // one trajectory's inputs and outputs (any output may be 
     const double *u_prev;                                                  // ro_run<true>: nu, the input before step 0
 };
 struct RoResult { double cost, mu_total, worst_vio; int worst_step, worst_row, steps_done, end_status, switches; };
+struct RoKpi {        // ro_run<., true>: one trajectory's KPIs (log_summary.inc: THE RULE)
+    int n_kpi, n_chan;
+    unsigned given;                                                        // bit t: table t of x, v, y, omega, x_k1 is given
+    const double *W, *thresh;                                              // the model's (rows, n_kpi) KPI-minor, rows = the widths of the given tables, and (n_kpi)
+    const int *price_chan;                                                 // n_kpi, -1 = not priced
+    const double *price;                                                   // the instance's price of step 0, channel 0: step k, channel c at price[k n_chan + c]; null = none priced
+    double vio_tol;
+    double *sum, *min, *max; int *min_step, *max_step, *n_above, *n_changes, *n_vio;      // the trajectory's n_kpi entries each, n_vio one
+};
 enum { RO_COMPLETE = 0, RO_INFEASIBLE = 1, RO_DECLINED = 2, RO_NOT_ATTEMPTED = -1 };
 enum { POL_ON_AT = 0, POL_OFF_AT = 1, POL_U_ON = 2, POL_U_OFF = 3, POL_MODE = 4, POL_TAIL = 5 };      // a channel's table row behind its nx selector entries
 
@@ -59,9 +78,36 @@ template <typename X> SM_FN double policy_rule(const double *tab, int nx, const 
 }
 
 // doubles of staging behind the solver's region (even, so that the next wave's region stays 16-byte aligned)
-static inline size_t ro_stage_doubles(int nx, int nu, int nw, int m, int nv, int ny)
+static inline size_t ro_stage_doubles(int nx, int nu, int nw, int m, int nv, int ny, int n_kpi = 0)
 {
-    return ((size_t)2 * nx + nw + nu + m + nv + ny + 1) & ~(size_t)1;
+    return ((size_t)2 * nx + nw + nu + m + nv + ny + (size_t)6 * n_kpi + 1) & ~(size_t)1;
+}
+
+// The KPI accumulators of a trajectory in its staging, KPI q at [q] of each run (lane-contiguous, no bank shared): four runs of doubles, then two of int pairs
+struct RoKpiAcc { sm_f64 *sum, *min, *max, *prev; sm_i32 *steps, *counts; };
+SM_FN RoKpiAcc ro_kpi_acc(sm_f64 *as, int Q)
+{
+    RoKpiAcc a;
+    a.sum = as; a.min = as + Q; a.max = as + 2 * Q; a.prev = as + 3 * Q; a.steps = (sm_i32 *)(as + 4 * Q); a.counts = (sm_i32 *)(as + 5 * Q);
+    return a;
+}
+
+// the trajectory's KPI outputs: its accumulators, or NaN / -1 for one that did not end 0 (as == nullptr); lane q writes entry q
+SM_FN void ro_kpi_write(const RoKpi &Q, sm_f64 *as, int lane, int n_vio)
+{
+    const double qnan = __builtin_nan("");
+    if (as) {
+        const RoKpiAcc a = ro_kpi_acc(as, Q.n_kpi);
+        for (int q = lane; q < Q.n_kpi; q += SM_W) {
+            Q.sum[q] = a.sum[q]; Q.min[q] = a.min[q]; Q.max[q] = a.max[q];
+            Q.min_step[q] = a.steps[2 * q]; Q.max_step[q] = a.steps[2 * q + 1]; Q.n_above[q] = a.counts[2 * q]; Q.n_changes[q] = a.counts[2 * q + 1];
+        }
+    } else
+        for (int q = lane; q < Q.n_kpi; q += SM_W) {
+            Q.sum[q] = Q.min[q] = Q.max[q] = qnan;
+            Q.min_step[q] = Q.max_step[q] = Q.n_above[q] = Q.n_changes[q] = -1;
+        }
+    if (lane == 0) *Q.n_vio = as ? n_vio : -1;
 }
 
 // everything after step `from` of a trajectory that stopped there: NaN / -1
@@ -78,8 +124,11 @@ SM_FN void ro_blank(const RoModel &M, const RoTraj &T, int lane, int from, bool 
 
 // One trajectory, start to finish.  mem: the solver's region (S.wave_doubles doubles), stg: the staging (ro_stage_doubles); A: the resolver's model
 // (G, q, lb, ub, cs, is_int, bins), its h / v_out / fixed are set here.  POLICY: the ruled channels of u_k come from M.pol, x_k and u_{k-1} (T.u_prev before
-// step 0); T.u supplies the passed-through channels only, and R.switches counts the (step, ruled channel) pairs whose input changed.
-template <bool POLICY = false> SM_FN void ro_run(const SmShape &S, const RoModel &M, sm_f64 *mem, sm_f64 *stg, SmArgs A, const RoTraj &T, int lane, RoResult &R)
+// step 0); T.u supplies the passed-through channels only, and R.switches counts the (step, ruled channel) pairs whose input changed.  KPI: Q's statistics of
+// the trajectory's records are accumulated in the staging behind x_{k+1} and written by the end (every output of Q is written; stg holds ro_stage_doubles
+// with Q->n_kpi).
+template <bool POLICY = false, bool KPI = false>
+SM_FN void ro_run(const SmShape &S, const RoModel &M, sm_f64 *mem, sm_f64 *stg, SmArgs A, const RoTraj &T, int lane, RoResult &R, const RoKpi *Q = nullptr)
 {
     const int nx = M.nx, nu = M.nu, nw = M.nw, nv = M.nv, ny = M.ny, nc = M.nc, m = M.m, nw2 = M.nw + M.nu, nf = M.nv - M.nmu;
     sm_f64 *xs = stg, *ws = xs + nx, *hs = ws + nw2, *vs = hs + m, *ys = vs + nv, *xn = ys + ny;
@@ -90,7 +139,15 @@ template <bool POLICY = false> SM_FN void ro_run(const SmShape &S, const RoModel
     if constexpr (POLICY) for (int j = lane; j < nu; j += SM_W) vs[j] = T.u_prev[j];      /* u_{-1}: a lane reads and writes its own channels only */
     double cost = 0.0, mu_total = 0.0, worst = -S_INF;
     int wstep = -1, wrow = -1, end = RO_COMPLETE, k = 0;
-    [[maybe_unused]] int sw = 0;
+    [[maybe_unused]] int sw = 0, n_vio = 0;
+    if constexpr (KPI) {      /* a lane initialises the accumulators it alone reads and writes */
+        const RoKpiAcc a = ro_kpi_acc(xn + nx, Q->n_kpi);
+        for (int q = lane; q < Q->n_kpi; q += SM_W) {
+            LsAcc c; ls_acc_init(c);
+            a.sum[q] = c.sum; a.min[q] = c.min; a.max[q] = c.max; a.prev[q] = c.prev;
+            a.steps[2 * q] = c.min_step; a.steps[2 * q + 1] = c.max_step; a.counts[2 * q] = c.n_above; a.counts[2 * q + 1] = c.n_changes;
+        }
+    }
     for (; k < T.K; ++k) {
         // ---- 1. the step's inputs
         const double *uk = T.u + (size_t)k * T.u_step, *wk = T.om + (size_t)k * nw;
@@ -149,6 +206,30 @@ template <bool POLICY = false> SM_FN void ro_run(const SmShape &S, const RoModel
             const bool v_nan = best != best, w_nan = worst != worst;
             if (wstep < 0 || (!w_nan && (v_nan || best > worst))) { worst = best; wstep = k; wrow = brow; }      /* the earliest step of equals stays */
         }
+        if constexpr (KPI) {      /* the record of step k is the staging: xs, vs, ys, ws[0 .. nw), xn (published by the barrier behind step 4) */
+            const int nq = Q->n_kpi;
+            const RoKpiAcc a = ro_kpi_acc(xn + nx, nq);
+            const sm_f64 *const field[5] = {xs, vs, ys, ws, xn};
+            const int width[5] = {nx, nv, ny, nw, nx};
+            for (int q = lane; q < nq; q += SM_W) {
+                double f = 0.0;
+                int row = 0; bool first = true;
+                for (int t = 0; t < 5; ++t) {
+                    if (!(Q->given >> t & 1u)) continue;
+                    f = ls_add_term(f, ls_dot(Q->W + (size_t)row * nq + q, (size_t)nq, field[t], width[t]), first);
+                    first = false; row += width[t];
+                }
+                const int pc = Q->price_chan[q];
+                if (pc >= 0) f = ls_priced(Q->price[(size_t)k * Q->n_chan + pc], f);
+                LsAcc c;
+                c.sum = a.sum[q]; c.min = a.min[q]; c.max = a.max[q]; c.prev = a.prev[q];
+                c.min_step = a.steps[2 * q]; c.max_step = a.steps[2 * q + 1]; c.n_above = a.counts[2 * q]; c.n_changes = a.counts[2 * q + 1]; c.have_prev = k > 0;
+                ls_accumulate(c, f, Q->thresh[q], k);
+                a.sum[q] = c.sum; a.min[q] = c.min; a.max[q] = c.max; a.prev[q] = c.prev;
+                a.steps[2 * q] = c.min_step; a.steps[2 * q + 1] = c.max_step; a.counts[2 * q] = c.n_above; a.counts[2 * q + 1] = c.n_changes;
+            }
+            n_vio += best > Q->vio_tol;      /* best is the wave's after the butterfly: every lane counts the same */
+        }
         // ---- 6. what was asked for
         if (T.v) for (int j = lane; j < nv; j += SM_W) T.v[(size_t)k * nv + j] = vs[j];
         if (lane == 0) { if (T.vio) T.vio[k] = best; if (T.row) T.row[k] = brow; }
@@ -163,6 +244,7 @@ template <bool POLICY = false> SM_FN void ro_run(const SmShape &S, const RoModel
         for (int off = SM_W / 2; off; off >>= 1) sw += sm_xor_i32(sw, off);
         R.switches = end == RO_COMPLETE ? sm_uniform(sw) : -1;
     }
+    if constexpr (KPI) ro_kpi_write(*Q, end == RO_COMPLETE ? xn + nx : nullptr, lane, n_vio);
 }
 
 #ifndef SM_HOST
@@ -187,10 +269,21 @@ struct RoPolicyDev {      /* what k_rollout_policy takes on top: an argument of 
     int *switches;                                  /* per trajectory, or nullptr */
 };
 
+struct RoKpiDev {         /* what the KPI kernels take on top, likewise an argument of its own */
+    int n_kpi, rows, n_chan, step;
+    unsigned given;
+    const double *W, *thresh; const int *price_chan;      /* (n_models, rows, n_kpi) KPI-minor, (n_models, n_kpi), (n_kpi) */
+    const double *lib; const long long *price_start;      /* the resident price library and (batch) starts into it, or nullptr: no KPI is priced */
+    double vio_tol;
+    double *sum, *min, *max; int *min_step, *max_step, *n_above, *n_changes;      /* (batch S, n_kpi) */
+    int *n_vio;                                           /* (batch S) */
+};
+
 // The kernel body, written once and expanded into both kernels.  (A function template called by the two kernels was tried first: inlined, it left k_rollout
 // with 208 bytes of scratch per lane instead of 156 -- the kernel arguments reach the register allocator by another route.  Expanded in place, the open-loop
-// kernel's listing is the one it had: profiles/policy_rollout_resource_usage.txt.)  POLICY: a literal; `pol`: the kernel's RoPolicyDev (k_rollout: an empty one).
-#define RO_KERNEL_BODY(POLICY)                                                                                                                                     \
+// kernel's listing is the one it had: profiles/policy_rollout_resource_usage.txt.)  POLICY, KPI: literals; `pol`, `kd`: the kernel's RoPolicyDev and RoKpiDev (empty
+// ones where the kernel takes none).  Flat KPI indices are 64-bit: t n_kpi over batch S trajectories.
+#define RO_KERNEL_BODY(POLICY, KPI)                                                                                                                                \
     extern __shared__ double ro_lds[];                                                                                                                             \
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;                                                                                                    \
     sm_f64 *mem = (sm_f64 *)ro_lds + (size_t)wave * ((size_t)S.wave_doubles + a.stage_doubles), *stg = mem + S.wave_doubles;                                       \
@@ -218,14 +311,24 @@ struct RoPolicyDev {      /* what k_rollout_policy takes on top: an argument of 
         T.x = a.x ? a.x + (size_t)t * (a.K + 1) * a.nx : nullptr; T.v = a.v ? a.v + (size_t)t * a.K * a.nv : nullptr;                                              \
         T.y = a.y ? a.y + (size_t)t * a.K * a.ny : nullptr; T.vio = a.vio ? a.vio + (size_t)t * a.K : nullptr; T.row = a.row ? a.row + (size_t)t * a.K : nullptr;  \
         if constexpr (POLICY) { M.pol = pol.tab + (size_t)mdl * pol.tab_len; T.u_prev = pol.u_prev + (size_t)b * a.nu; }                                           \
+        [[maybe_unused]] RoKpi Q;                                                                                                                                  \
+        if constexpr (KPI) {                                                                                                                                       \
+            const size_t o = (size_t)t * (size_t)kd.n_kpi;                                                                                                         \
+            Q.n_kpi = kd.n_kpi; Q.n_chan = kd.n_chan; Q.given = kd.given; Q.vio_tol = kd.vio_tol;                                                                  \
+            Q.W = kd.W + (size_t)mdl * kd.rows * kd.n_kpi; Q.thresh = kd.thresh + (size_t)mdl * kd.n_kpi; Q.price_chan = kd.price_chan;                            \
+            Q.price = kd.lib ? kd.lib + kd.price_start[b] + (long long)kd.step * kd.n_chan : nullptr;                                                              \
+            Q.sum = kd.sum + o; Q.min = kd.min + o; Q.max = kd.max + o; Q.min_step = kd.min_step + o; Q.max_step = kd.max_step + o;                                \
+            Q.n_above = kd.n_above + o; Q.n_changes = kd.n_changes + o; Q.n_vio = kd.n_vio + t;                                                                    \
+        }                                                                                                                                                          \
         RoResult R;                                                                                                                                                \
         if (a.status && !plan_usable(a.status, a.obj, (int)b)) {      /* uniform over the wave: no plan whose inputs could be applied */                           \
             const double qnan = __builtin_nan("");                                                                                                                 \
             ro_blank(M, T, lane, 0, true);                                                                                                                         \
             R.cost = R.mu_total = R.worst_vio = qnan; R.worst_step = R.worst_row = -1; R.steps_done = 0; R.end_status = RO_NOT_ATTEMPTED;                          \
             if constexpr (POLICY) R.switches = -1;                                                                                                                 \
+            if constexpr (KPI) ro_kpi_write(Q, nullptr, lane, 0);                                                                                                  \
         } else                                                                                                                                                     \
-            ro_run<POLICY>(S, M, mem, stg, A, T, lane, R);                                                                                                         \
+            ro_run<POLICY, KPI>(S, M, mem, stg, A, T, lane, R, KPI ? &Q : nullptr);                                                                                \
         if (lane == 0) {                                                                                                                                           \
             if (a.cost) a.cost[t] = R.cost;                                                                                                                        \
             if (a.mu_total) a.mu_total[t] = R.mu_total;                                                                                                            \
@@ -243,13 +346,27 @@ struct RoPolicyDev {      /* what k_rollout_policy takes on top: an argument of 
 __global__ void __launch_bounds__(SM_NT, 3) k_rollout(SmShape S, ProblemDev P, RoDev a)
 {
     const RoPolicyDev pol{};
-    RO_KERNEL_BODY(false)
+    const RoKpiDev kd{};
+    RO_KERNEL_BODY(false, false)
 }
 
 // The policy instantiation: the same body, step 1's inputs by the rule.
 __global__ void __launch_bounds__(SM_NT, 3) k_rollout_policy(SmShape S, ProblemDev P, RoDev a, RoPolicyDev pol)
 {
-    RO_KERNEL_BODY(true)
+    const RoKpiDev kd{};
+    RO_KERNEL_BODY(true, false)
+}
+
+// The KPI instantiations (mld_rollout_kpi): the same body twice more, the trajectory's column statistics reduced in step 5.
+__global__ void __launch_bounds__(SM_NT, 3) k_rollout_kpi(SmShape S, ProblemDev P, RoDev a, RoKpiDev kd)
+{
+    const RoPolicyDev pol{};
+    RO_KERNEL_BODY(false, true)
+}
+
+__global__ void __launch_bounds__(SM_NT, 3) k_rollout_policy_kpi(SmShape S, ProblemDev P, RoDev a, RoPolicyDev pol, RoKpiDev kd)
+{
+    RO_KERNEL_BODY(true, true)
 }
 #undef RO_KERNEL_BODY
 

@@ -508,6 +508,7 @@ class GpuProblem(object):
             raise ValueError("n_chan = %r, expected at least one price channel" % (n_chan,))
         check(_lib.load().mld_upload_prices(self._h, lib.size, _lib.dptr(lib) if lib.size else None, int(n_chan)))
         self._pr_chan = int(n_chan) if lib.size else 0
+        self._pr_lib = lib if lib.size else None      # (rollout(kpis=...) prices the trajectories it finishes on the host from it)
 
     def _price_tables(self, **tables):
         """per-model tables (n_models, n_chan, width) of the price entry points; (n_chan, width) and (width,) broadcast over models and channels; None stays
@@ -814,7 +815,8 @@ class GpuProblem(object):
             raise ValueError("u_prev has shape %s, expected (%d, %d) or (%d,)" % (u_prev.shape, B, nu, nu))
         return np.ascontiguousarray(u_prev)
 
-    def rollout(self, resolve, K=None, u_seq=None, omega_seq=None, start=None, step=0, cost_w=None, trajectories=False, policy=False, u_prev=None):
+    def rollout(self, resolve, K=None, u_seq=None, omega_seq=None, start=None, step=0, cost_w=None, trajectories=False, policy=False, u_prev=None,
+                kpis=None, price_start=None, vio_tol=1e-6):
         """open-loop rollout of the resident batch under S realised disturbances, on device (mld_rollout_batch, kernel k_rollout): the reference's
         MldModel.lsim / lsim_k in a loop with _compute_aux at every step (models/mld_model.py:543-642, 647-699, 701-766), batch x S trajectories in one launch.
         resolve: an aux_resolve.BatchAuxResolver(..., small_lds=True) over the same models.  u_seq (batch, K, nu) / (K, nu), or None = the inputs of the
@@ -830,7 +832,14 @@ class GpuProblem(object):
         the ruled channels of u_k come from the trajectory's own x_k and u_{k-1}, u_seq / the plan supply the passed-through channels only (no plan is
         needed when every channel is ruled); u_prev (batch, nu) / (nu,) is the input before step 0, None = the resident policy state, which the call
         leaves as it is.  The result carries switches (batch, S): the (step, ruled channel) pairs whose input changed, -1 unless the trajectory ended 0.
-        The host completion applies the rule too."""
+        The host completion applies the rule too.
+        kpis: a simlog.KpiTable over this problem's models -- the campaign's column statistics of every trajectory, reduced inside the same kernel
+        (mld_rollout_kpi, kernels k_rollout_kpi / k_rollout_policy_kpi).  The record of step k is x_k, v_k, y_k, omega_k, x_{k+1}; a priced KPI multiplies
+        by lib[price_start[b] + (step + k) n_chan + ch] of the resident price library (upload_prices), price_start (batch,) or a scalar: one tariff for the
+        S realisations of an instance, the price sim_step(step=step + k) records.  The result gains kpi = dict(names, sum, min, max (batch, S, n_kpi),
+        min_step, max_step, n_above, n_changes (batch, S, n_kpi) int32, n_vio (batch, S) int32: steps with cons_vio > vio_tol); a trajectory that does not
+        end 0 has NaN / -1.  The figures are those of the logged stepwise campaign's sim_log_summary and of simlog.rollout_kpis_np, bit for bit;
+        trajectories finished on the host get theirs from rollout_kpis_np.  Without kpis the call is what it was."""
         from . import simlog
         d, B, nv = self.model.dims, self.batch, self.model.nv
         nx, nu, nw, ny = d["nx"], d["nu"], d["nomega"], d["ny"]
@@ -865,6 +874,24 @@ class GpuProblem(object):
         aux = resolve.problem._h if resolve is not None and resolve.problem is not None else None
         ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None
         lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64)) if a is not None else None
+        karr = ktabs = kthr = pst = None
+        if kpis is None:
+            if price_start is not None:
+                raise ValueError("price_start given without kpis (it prices the KPIs of the rollout)")
+        else:
+            if kpis.n_models != self.model.n_models:
+                raise ValueError("the KPI table has %d models, the problem %d" % (kpis.n_models, self.model.n_models))
+            want = dict(w_x=nx, w_v=nv, w_y=ny, w_omega=nw, w_xk1=nx)
+            if kpis.widths != want:
+                raise ValueError("the KPI table was built for other dimensions (%s, this problem %s)" % (kpis.widths, want))
+            karr = kpis.arrays()
+            ktabs = [None if karr[k] is None else np.ascontiguousarray(karr[k]) for k in simlog.KPI_TABLES]
+            kthr = None if karr["thresh"] is None else np.ascontiguousarray(karr["thresh"])
+            if price_start is not None:
+                pst = self._price_start(price_start)
+            elif np.any(karr["price_chan"] >= 0):
+                raise ValueError("KPI %r is priced, but price_start is None (the starts of the realised prices, one per instance)"
+                                 % (kpis.names[int(np.flatnonzero(karr["price_chan"] >= 0)[0])],))
 
         def call(full):
             o = dict(cost=np.zeros((B, S)), mu_total=np.zeros((B, S)), worst_vio=np.zeros((B, S)), worst_step=np.zeros((B, S), np.int32),
@@ -873,6 +900,22 @@ class GpuProblem(object):
                 o.update(x=np.zeros((B, S, K + 1, nx)), v=np.zeros((B, S, K, nv)), y=np.zeros((B, S, K, ny)), cons_vio=np.zeros((B, S, K)),
                          cons_row=np.zeros((B, S, K), np.int32))
             stats = np.zeros(4, np.int64)
+            if kpis is not None:
+                Q = len(kpis)
+                kp = dict(names=list(kpis.names), sum=np.zeros((B, S, Q)), min=np.zeros((B, S, Q)), max=np.zeros((B, S, Q)), min_step=np.zeros((B, S, Q), np.int32),
+                          max_step=np.zeros((B, S, Q), np.int32), n_above=np.zeros((B, S, Q), np.int32), n_changes=np.zeros((B, S, Q), np.int32),
+                          n_vio=np.zeros((B, S), np.int32))
+                if policy:
+                    o["switches"] = np.zeros((B, S), np.int32)
+                check(_lib.load().mld_rollout_kpi(
+                    self._h, aux, 1 if policy else 0, K, S, _lib.dptr(u_seq), _lib.dptr(u_prev), _lib.dptr(omega_seq) if nw else None, lp(st), int(step),
+                    _lib.dptr(cost_w), rows, Q, *([_lib.dptr(t) for t in ktabs] + [ip(karr["price_chan"]), _lib.dptr(kthr), float(vio_tol), lp(pst)]),
+                    _lib.dptr(o.get("x")), _lib.dptr(o.get("v")), _lib.dptr(o.get("y")), _lib.dptr(o.get("cons_vio")), ip(o.get("cons_row")),
+                    _lib.dptr(o["cost"]), _lib.dptr(o["mu_total"]), _lib.dptr(o["worst_vio"]), ip(o["worst_step"]), ip(o["steps_done"]), ip(o["end_status"]),
+                    ip(o.get("switches")), lp(stats), _lib.dptr(kp["sum"]), _lib.dptr(kp["min"]), _lib.dptr(kp["max"]), ip(kp["min_step"]), ip(kp["max_step"]),
+                    ip(kp["n_above"]), ip(kp["n_changes"]), ip(kp["n_vio"])))
+                o["kpi"] = kp
+                return o, stats
             if policy:
                 o["switches"] = np.zeros((B, S), np.int32)
                 check(_lib.load().mld_rollout_policy(
@@ -915,6 +958,7 @@ class GpuProblem(object):
             else:
                 om_all = omega_seq if nw else np.zeros((B, S, K, 0))
             T = B * S
+            kpi_dev = out.pop("kpi", None)
             flat = {k: out[k].reshape((T,) + out[k].shape[2:]) for k in out}
             todo = np.where(flat["end_status"] == 2)[0]
             n_host = int(todo.size)
@@ -924,6 +968,18 @@ class GpuProblem(object):
             simlog.rollout_continue(resolve.mats, d, np.repeat(midx, S), np.repeat(u_all, S, axis=0), om_all.reshape(T, K, nw), flat, todo, resolve.resolve, cw_t,
                                     policy=P, u_prev=up_t)
             out = {k: flat[k].reshape(out[k].shape) for k in out}
+            if kpi_dev is not None:      # the trajectories finished here take the numpy rule's figures of the finished trajectory: one convention for the caller
+                price = None
+                if pst is not None and np.any(karr["price_chan"] >= 0):
+                    from . import prices
+                    if getattr(self, "_pr_lib", None) is None:
+                        raise MldGpuError("rollout: the price library is not known on the host (upload_prices() keeps it)")
+                    price = prices.windows(self._pr_lib, pst, int(step), K, self._pr_chan).reshape(B, K, self._pr_chan)
+                host = simlog.rollout_kpis_np(out, kpis, price=price, vio_tol=vio_tol, omega_seq=om_all if nw else None, model_idx=midx)
+                sel = todo // S, todo % S
+                for key in simlog.KPI_ROLLOUT_KEYS:
+                    kpi_dev[key][sel] = host[key][sel]
+                out["kpi"] = kpi_dev
         es = out["end_status"]
         out["stats"] = dict(trajectories=int(stats[0]), complete=int((es == 0).sum()) if n_host else int(stats[1]), infeasible=int((es == 1).sum()) if n_host else int(stats[2]),
                             declined=int(stats[3]), not_attempted=int(stats[0] - stats[1] - stats[2] - stats[3]), finished_on_host=n_host)

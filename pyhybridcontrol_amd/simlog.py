@@ -381,6 +381,46 @@ def rollout_np(mats_list, dims, model_idx, x0, u_seq, omega_seq, resolve_fn, cos
     return {k: a.reshape((B, S) + a.shape[1:]) for k, a in out.items()}
 
 
+KPI_ROLLOUT_KEYS = ("sum", "min", "max", "min_step", "max_step", "n_above", "n_changes", "n_vio")      # what a rollout's "kpi" holds beside names
+
+
+def rollout_kpis_np(traj, kpis, price=None, vio_tol=1e-6, omega_seq=None, model_idx=None):
+    """GpuProblem.rollout(kpis=...)'s "kpi" stated in numpy (mld_rollout_kpi, kernels k_rollout_kpi / k_rollout_policy_kpi): traj the output of
+    rollout(trajectories=True) or rollout_np -- x (B, S, K + 1, nx), v (B, S, K, nv), y, cons_vio (B, S, K), end_status (B, S) --, kpis a KpiTable,
+    price (B, K, n_chan) the instances' price windows, prices.windows(lib, price_start, step, K, n_chan).reshape(B, K, n_chan) (needed by a priced KPI; the S
+    realisations of an instance share it), omega_seq (B, S, K, nomega) the realised disturbance (needed by a KPI with w_omega), model_idx (B,) or None.
+
+    The record of trajectory (b, c) at step k is x = x[b, c, k], v, y, omega = omega_seq[b, c, k], x_k1 = x[b, c, k + 1], and the statistics are summary_np's
+    of the log these records make, begun at 0: the arithmetic is summary_np's own, not restated.  A trajectory that did not end 0 gets NaN / -1.
+    Returns dict(names, sum, min, max (B, S, n_kpi), min_step, max_step, n_above, n_changes (B, S, n_kpi) int32, n_vio (B, S) int32)."""
+    x = np.asarray(traj["x"], dtype=np.float64)
+    v = np.asarray(traj["v"], dtype=np.float64)
+    B, S, K = v.shape[0], v.shape[1], v.shape[2]
+    T = B * S
+    arr = kpis.arrays()
+    if arr["w_omega"] is not None and omega_seq is None:
+        raise ValueError("a KPI reads omega (w_omega): rollout_kpis_np needs omega_seq (B, S, K, nomega)")
+    if np.any(arr["price_chan"] >= 0) and price is None:
+        raise ValueError("a KPI is priced (price_chan >= 0): rollout_kpis_np needs price (B, K, n_chan)")
+    steps = lambda a: np.ascontiguousarray(np.moveaxis(np.asarray(a).reshape((T, K) + np.shape(a)[3:]), 1, 0))      # (B, S, K, ...) -> (K, T, ...)
+    log = dict(x=steps(x[:, :, :K]), v=steps(v), y=steps(np.asarray(traj["y"], dtype=np.float64)), x_k1=steps(x[:, :, 1:]),
+               cons_vio=steps(np.asarray(traj["cons_vio"], dtype=np.float64)), nodes=np.zeros((K, T), np.int32))
+    if omega_seq is not None:
+        log["omega"] = steps(np.asarray(omega_seq, dtype=np.float64).reshape(B, S, K, -1))
+    midx = None if model_idx is None else np.repeat(np.asarray(model_idx, dtype=np.int64).reshape(B), S)
+    pr = None
+    if price is not None:
+        pr = np.ascontiguousarray(np.moveaxis(np.repeat(np.asarray(price, dtype=np.float64).reshape(B, K, -1), S, axis=0), 1, 0))      # (K, T, n_chan)
+    full = summary_np(log, kpis, midx, price=pr, vio_tol=vio_tol)
+    dead = np.asarray(traj["end_status"]).reshape(T) != 0
+    out = dict(names=list(kpis.names))
+    for key in KPI_ROLLOUT_KEYS:
+        a = np.array(full[key])
+        a[dead] = np.nan if a.dtype.kind == "f" else -1
+        out[key] = a.reshape((B, S) + a.shape[1:])
+    return out
+
+
 def start_from_rollout_np(v, end_status, bins, old=None):
     """GpuProblem.warm_start_from_rollout's byte rule stated in numpy (kernel k_warm_from_rollout): v (B, N_tilde, nv) or (B, 1, N_tilde, nv) of a rollout with
     S = 1, end_status (B,) or (B, 1), bins (n_bin,) the binaries' indices step * nv + pos (np.flatnonzero(GpuProblem.is_bin)), old (B, n_bin) the resident
