@@ -875,6 +875,49 @@ int mld_rollout_kpi(mld_problem_t *p, mld_problem_t *aux, int policy, int K, int
                     int32_t *switches_out, int64_t stats[4],
                     double *sum, double *min, double *max, int32_t *min_step, int32_t *max_step, int32_t *n_above, int32_t *n_changes, int32_t *n_vio);
 
+/* ---- rollout risk: statistics across a rollout's realisations ------------------------------------------------------------------------------------------------
+ * The reference's headline figures are a column statistic over time followed by a reduction over the Monte-Carlo runs, .mean(level=[..., 'controller'])
+ * (plot_multi_sim_campaign.py:69-131).  mld_rollout_risk is mld_rollout_kpi (n_kpi >= 1) or mld_rollout_batch / mld_rollout_policy (n_kpi == 0: no KPI table,
+ * the KPI arguments are ignored) with that second reduction made on the device, by k_rollout_risk queued behind the rollout kernel on the problem's stream:
+ * per instance a few doubles per column instead of every trajectory's.  Every argument, ending and output of the others means what it means there; ANY
+ * output may be NULL, the per-trajectory ones included, so a caller that wants only the risk downloads only the risk.
+ *
+ * A call names G columns (1 <= G <= MLD_RISK_COLS_MAX); column j is (col_src[j], col_q[j]) over the per-trajectory results of the same call:
+ *     0 cost   1 mu_total   2 worst_vio   3 switches (policy != 0 only)   4 n_vio   5 / 6 / 7 KPI sum / min / max of KPI col_q[j]
+ *     8 / 9 KPI n_above / n_changes of KPI col_q[j]                 (integers become doubles exactly; 4 .. 9 need n_kpi >= 1; col_q is read for 5 .. 9 only)
+ * For instance b and column j let g[c] be realisation c's value.  c is COMPLETE iff end_status[b, c] == 0; n is the number of complete realisations.
+ *   counts (batch, 4)   over all c: n_complete, n_infeasible (ending 1), n_declined (2), n_not_attempted (-1)
+ *   order               the complete c ascending by the pair (g, c): a before a' iff g < g', or g == g' and c < c' -- so -0.0 and +0.0 tie and c decides; a
+ *                       NaN sorts after every number, by c: a stable sort by value.  sorted[r], r = 0 .. n - 1.
+ *   T(leaf[0 .. 63])    the balanced binary tree over 64 leaves in index order: (0,1), (2,3), ..., then those results pairwise, six levels, every addition
+ *                       rounded on its own; a leaf that is not selected is +0.0
+ * Per (b, j) -- each output (batch, G):
+ *   mean = T(leaf c = g[c] if complete) / n;  min, min_c / max, max_c by strict < / >: the smallest attaining c wins, a NaN never wins;
+ *   n_exceed: the complete c with g[c] > level[j] (level (G), or NULL = +inf)
+ * Per (b, j, l) for the L levels alpha[l] in (0, 1] (0 <= L <= MLD_RISK_LEVELS_MAX) -- each output (batch, G, L):
+ *   i = the smallest i >= 0 with (double)(i + 1) >= alpha[l] * (double)n, the index ceil(alpha n) - 1 (tabulated by the host once per call);
+ *   quantile = sorted[i], quantile_c its c;  cvar_hi = T(leaf r = sorted[r], i <= r < n) / (n - i);  cvar_lo = T(leaf r = sorted[r], r <= i) / (i + 1)
+ * An instance with n == 0: mean, quantile, cvar_* NaN; min +inf, max -inf; every _c -1; n_exceed 0 (mld_sim_log_summary's conventions).
+ * The figures are bit-identical to simlog.py: rollout_risk_np on the per-trajectory outputs of the same call.  The call is host-synchronous and writes nothing
+ * on the handle.
+ * MLD_ERR_INVALID before anything is queued, the argument named: everything mld_rollout_kpi refuses (n_kpi == 0 aside); S > MLD_RISK_S_MAX; G or L out of
+ * range; an unknown source; source 3 with policy == 0; a source >= 4 with n_kpi == 0; col_q[j] outside [0, n_kpi); alpha[l] outside (0, 1] or NaN; a NaN
+ * level. */
+#define MLD_RISK_COLS_MAX 64
+#define MLD_RISK_LEVELS_MAX 8
+#define MLD_RISK_S_MAX 64      /* the lanes of a wave: one lane owns one realisation */
+int mld_rollout_risk(mld_problem_t *p, mld_problem_t *aux, int policy, int K, int S, const double *u_seq, const double *u_prev, const double *omega_seq,
+                     const int64_t *start, int step, const double *cost_w, int cost_rows, int n_kpi,
+                     const double *w_x, const double *w_v, const double *w_y, const double *w_omega, const double *w_xk1,
+                     const int32_t *price_chan, const double *thresh, double vio_tol, const int64_t *price_start,
+                     double *x_out, double *v_out, double *y_out, double *cons_vio_out, int32_t *cons_row_out,
+                     double *cost_out, double *mu_total_out, double *worst_vio_out, int32_t *worst_step_out, int32_t *steps_done_out, int32_t *end_status_out,
+                     int32_t *switches_out, int64_t stats[4],
+                     double *sum, double *min, double *max, int32_t *min_step, int32_t *max_step, int32_t *n_above, int32_t *n_changes, int32_t *n_vio,
+                     int G, const int32_t *col_src, const int32_t *col_q, const double *level, int L, const double *alpha,
+                     double *r_mean, double *r_min, double *r_max, int32_t *r_min_c, int32_t *r_max_c, int32_t *r_n_exceed,
+                     double *r_quantile, int32_t *r_quantile_c, double *r_cvar_hi, double *r_cvar_lo, int32_t *counts);
+
 /* Per-instance telemetry of the last solve: time spent inside the solve kernel (device wall clock, ns) and
  * the number of dictionary rows the rank-1 updates touched (x *row_bytes x 2 = bytes streamed by pivots). */
 int mld_download_telemetry(mld_problem_t *, int64_t *latency_ns, int64_t *rows_updated, int64_t *row_bytes);

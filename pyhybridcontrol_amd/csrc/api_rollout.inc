@@ -8,10 +8,13 @@
  * (the flag moves GEMMs to fp32, never the inputs), so the start comes from the buffers the rollout reads anyway and nothing is converted.
  * kc (mld_rollout_kpi): the KPI instantiations k_rollout_kpi / k_rollout_policy_kpi -- the column statistics of every trajectory, reduced inside the
  * kernel.  Its tables are tested as mld_sim_log_summary tests them, its price starts by the price library's window rule with len = K, the weights are laid
- * out KPI-minor as k_log_summary reads them, and everything it uploads and the kernel writes lives in temporaries of the call. */
+ * out KPI-minor as k_log_summary reads them, and everything it uploads and the kernel writes lives in temporaries of the call.
+ * rk (mld_rollout_risk): the statistics ACROSS the realisations of every instance (rollout_risk.inc: THE RULE) -- the per-trajectory results the columns read
+ * get their device temporaries whether or not the caller asked for them (as sc forces d_v and d_es), k_rollout_risk is queued behind the rollout kernel on
+ * the same stream and its results are downloaded inside the same queue_and_wait.  The rank table idx[l][n] is built here, once per call. */
 static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p, mld_problem_t *aux, int K, int S, const double *u_seq, const double *omega_seq,
                         const int64_t *start, int step, const double *cost_w, int cost_rows, const RolloutOut &out, const StartCall *sc = nullptr,
-                        const KpiCall *kc = nullptr)
+                        const KpiCall *kc = nullptr, const RiskCall *rk = nullptr)
 {
     double *const x_out = out.x, *const v_out = out.v, *const y_out = out.y, *const cons_vio_out = out.cons_vio, *const cost_out = out.cost,
            *const mu_total_out = out.mu_total, *const worst_vio_out = out.worst_vio;
@@ -67,6 +70,28 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
         }
         if (priced) { std::vector<long long> pmax; if (int rc = check_starts(price_lib(p), who, PF_PRICE, kc->price_start, batch, 1, step, K, pmax)) return rc; }
     }
+    /* the risk columns */
+    unsigned r_src = 0, r_need = 0;      /* bit s: some column has source s; bit t: some column reads KPI array t of sum, min, max, n_above, n_changes */
+    if (rk) {
+        if (S > MLD_RISK_S_MAX) { mld_set_error("%s: S = %d realisations (at most MLD_RISK_S_MAX = %d: a lane of the wave per realisation)", who, S, MLD_RISK_S_MAX); return MLD_ERR_INVALID; }
+        if (rk->G < 1 || rk->G > MLD_RISK_COLS_MAX) { mld_set_error("%s: G = %d columns (1 .. MLD_RISK_COLS_MAX = %d)", who, rk->G, MLD_RISK_COLS_MAX); return MLD_ERR_INVALID; }
+        if (rk->L < 0 || rk->L > MLD_RISK_LEVELS_MAX) { mld_set_error("%s: L = %d levels (0 .. MLD_RISK_LEVELS_MAX = %d)", who, rk->L, MLD_RISK_LEVELS_MAX); return MLD_ERR_INVALID; }
+        if (!rk->col_src) { mld_set_error("%s: col_src is NULL (the source of each of the G columns)", who); return MLD_ERR_INVALID; }
+        if (rk->L > 0 && !rk->alpha) { mld_set_error("%s: alpha is NULL with L = %d levels", who, rk->L); return MLD_ERR_INVALID; }
+        for (int j = 0; j < rk->G; ++j) {
+            const int s = rk->col_src[j], q = rk->col_q ? rk->col_q[j] : 0;
+            if (s < 0 || s >= RISK_N_SRC) { mld_set_error("%s: col_src[%d] = %d (a source 0 .. %d)", who, j, s, RISK_N_SRC - 1); return MLD_ERR_INVALID; }
+            if (s == RISK_SWITCHES && !pc) { mld_set_error("%s: col_src[%d] = %d (switches), but the rollout has no policy (policy == 0)", who, j, s); return MLD_ERR_INVALID; }
+            if (s >= RISK_N_VIO && n_kpi == 0) { mld_set_error("%s: col_src[%d] = %d reads the KPIs, but n_kpi = 0 (no KPI table in this call)", who, j, s); return MLD_ERR_INVALID; }
+            if (s >= RISK_KPI_SUM && (q < 0 || q >= n_kpi)) { mld_set_error("%s: col_q[%d] = %d (a KPI 0 .. n_kpi - 1 = %d)", who, j, q, n_kpi - 1); return MLD_ERR_INVALID; }
+            if (rk->level && std::isnan(rk->level[j])) { mld_set_error("%s: level[%d] is NaN", who, j); return MLD_ERR_INVALID; }
+            r_src |= 1u << s;
+            if (s >= RISK_KPI_SUM) r_need |= 1u << (s - RISK_KPI_SUM);
+        }
+        for (int l = 0; l < rk->L; ++l) if (!(rk->alpha[l] > 0.0 && rk->alpha[l] <= 1.0)) {
+            mld_set_error("%s: alpha[%d] = %g (a level in (0, 1])", who, l, rk->alpha[l]); return MLD_ERR_INVALID;
+        }
+    }
     const size_t stage_d = ro_stage_doubles(nx, nu, nw, aux ? aux->m0 : 0, nv, ny, n_kpi);
     if (sizeof(double) * stage_d > SM_WAVE_BUDGET) {
         mld_set_error("%s: the staging of a trajectory (%zu bytes: x, omega', h, v, y, x_k1) does not fit a wave's share of LDS (%d bytes); step with mld_sim_step_resolve", who, sizeof(double) * stage_d, SM_WAVE_BUDGET);
@@ -120,6 +145,8 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
     DevBuf<double> d_u, d_om, d_cw, d_x, d_v, d_y, d_vio, d_cost, d_mu, d_wv, d_uprev; DevBuf<int> d_row, d_ws, d_sd, d_es, d_sw; DevBuf<long long> d_start; DevBuf<unsigned long long> d_cnt;
     DevBuf<double> d_kW, d_kthr, d_ksum, d_kmin, d_kmax; DevBuf<int> d_kpc, d_kmins, d_kmaxs, d_kabove, d_kchg, d_knvio; DevBuf<long long> d_kps;      /* kc */
     std::vector<double> hW, hthr; std::vector<int> hpc;
+    DevBuf<double> d_rlev, d_rmean, d_rmin, d_rmax, d_rq, d_rhi, d_rlo; DevBuf<int> d_rsrc, d_rcq, d_ridx, d_rminc, d_rmaxc, d_rex, d_rqc, d_rcnt;      /* rk */
+    std::vector<int> hrq, hidx;
     DevBuf<unsigned char> d_old; DevBuf<int> d_src;      /* sc: the resident start as it was (where rows are kept), the source per instance */
     if (pc && !pc->u_prev) { if (int rc = policy_state_ready(p, who)) return rc; }      /* (an upload's reset state, laid out on first use: nothing a caller can see changes) */
     if (pc && pc->u_prev) HIP_TRY(d_uprev.alloc(std::max<size_t>(1, (size_t)batch * nu)));
@@ -134,6 +161,21 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
     HIP_TRY(take(d_cost, cost_out, T)); HIP_TRY(take(d_mu, mu_total_out, T)); HIP_TRY(take(d_wv, worst_vio_out, T));
     HIP_TRY(take(d_ws, worst_step_out, T)); HIP_TRY(take(d_sd, steps_done_out, T)); HIP_TRY(take(d_es, end_status_out, T));
     if (pc) HIP_TRY(take(d_sw, pc->switches_out, T));
+    const size_t rg = rk ? (size_t)batch * rk->G : 0, rgl = rk ? rg * rk->L : 0;
+    if (rk) {      /* the temporaries of the sources the columns read, asked for or not; the rank table; the results' buffers */
+        auto force = [](auto &buf, bool read, size_t count) -> hipError_t { return read && !buf ? buf.alloc(count) : hipSuccess; };
+        HIP_TRY(force(d_es, true, T)); HIP_TRY(force(d_cost, r_src >> RISK_COST & 1u, T)); HIP_TRY(force(d_mu, r_src >> RISK_MU_TOTAL & 1u, T));
+        HIP_TRY(force(d_wv, r_src >> RISK_WORST_VIO & 1u, T)); HIP_TRY(force(d_sw, r_src >> RISK_SWITCHES & 1u, T));
+        hrq.assign(rk->G, 0);
+        if (rk->col_q) std::copy(rk->col_q, rk->col_q + rk->G, hrq.begin());
+        hidx.resize(std::max<size_t>(1, (size_t)rk->L * S));
+        for (int l = 0; l < rk->L; ++l) for (int n = 1; n <= S; ++n) hidx[(size_t)l * S + n - 1] = risk_rank(rk->alpha[l], n);
+        HIP_TRY(d_rsrc.alloc(rk->G)); HIP_TRY(d_rcq.alloc(rk->G)); HIP_TRY(d_ridx.alloc(hidx.size()));
+        if (rk->level) HIP_TRY(d_rlev.alloc(rk->G));
+        HIP_TRY(take(d_rmean, rk->mean, rg)); HIP_TRY(take(d_rmin, rk->min, rg)); HIP_TRY(take(d_rmax, rk->max, rg)); HIP_TRY(take(d_rminc, rk->min_c, rg));
+        HIP_TRY(take(d_rmaxc, rk->max_c, rg)); HIP_TRY(take(d_rex, rk->n_exceed, rg)); HIP_TRY(take(d_rq, rk->quantile, rgl)); HIP_TRY(take(d_rqc, rk->quantile_c, rgl));
+        HIP_TRY(take(d_rhi, rk->cvar_hi, rgl)); HIP_TRY(take(d_rlo, rk->cvar_lo, rgl)); HIP_TRY(take(d_rcnt, rk->counts, (size_t)batch * 4));
+    }
     const size_t warm_len = sc ? (size_t)batch * p->nb : 0;
     const bool keep_rows = sc && sc->keep && p->has_warm;
     std::vector<int32_t> src_host;
@@ -195,6 +237,26 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
     (void)hipGetDevice(&dev); HIP_TRY(hipGetDeviceProperties(&prop, dev));
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, SM_NT, lds_bytes) != hipSuccess || per_cu < 1) per_cu = 1;
     const int grid = (int)std::min<size_t>((T + SM_WAVES - 1) / SM_WAVES, (size_t)per_cu * prop.multiProcessorCount);
+    RiskArgs ra{};
+    size_t risk_lds = 0; int risk_grid = 1;
+    if (rk) {
+        ra.batch = batch; ra.S = S; ra.G = rk->G; ra.L = rk->L; ra.n_kpi = n_kpi; ra.need = r_need;
+        const size_t stg = risk_stage_doubles(S, n_kpi, r_need, ra.off);
+        ra.staged = r_need && sizeof(double) * RISK_WAVES * (RISK_SORT_DOUBLES + stg) <= RISK_LDS_MAX;      /* blocks that do not fit are read in place: the same bits */
+        ra.ld = ra.staged ? (n_kpi | 1) : n_kpi;
+        ra.wave_doubles = (int)(RISK_SORT_DOUBLES + (ra.staged ? stg : 0));
+        ra.col_src = d_rsrc; ra.col_q = d_rcq; ra.level = rk->level ? d_rlev.get() : nullptr; ra.idx = d_ridx;
+        ra.es = d_es; ra.cost = d_cost; ra.mu = d_mu; ra.wv = d_wv; ra.sw = d_sw; ra.nvio = d_knvio;
+        ra.ksum = d_ksum; ra.kmin = d_kmin; ra.kmax = d_kmax; ra.kabove = d_kabove; ra.kchg = d_kchg;
+        ra.mean = d_rmean; ra.min = d_rmin; ra.max = d_rmax; ra.min_c = d_rminc; ra.max_c = d_rmaxc; ra.n_exceed = d_rex;
+        ra.quantile = d_rq; ra.quantile_c = d_rqc; ra.cvar_hi = d_rhi; ra.cvar_lo = d_rlo; ra.counts = d_rcnt;
+        risk_lds = sizeof(double) * RISK_WAVES * (size_t)ra.wave_doubles;
+        if (risk_lds > 48 * 1024)
+            HIP_TRY(hipFuncSetAttribute((const void *)k_rollout_risk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)risk_lds));
+        int rper = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&rper, (const void *)k_rollout_risk, 64 * RISK_WAVES, risk_lds) != hipSuccess || rper < 1) rper = 1;
+        risk_grid = (int)std::min<long long>(((long long)batch + RISK_WAVES - 1) / RISK_WAVES, (long long)rper * prop.multiProcessorCount);
+    }
     unsigned long long cnt[4] = {};
     /* everything queued on the stream and waited for on every path (queue_and_wait): the caller's arrays and the temporaries may go when this returns */
     auto queue = [&]() -> int {
@@ -215,6 +277,12 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
             HIP_TRY(hipMemcpyAsync(d_kpc, hpc.data(), sizeof(int) * n_kpi, hipMemcpyHostToDevice, sq));
             if (priced) HIP_TRY(hipMemcpyAsync(d_kps, kc->price_start, sizeof(long long) * (size_t)batch, hipMemcpyHostToDevice, sq));
         }
+        if (rk) {
+            HIP_TRY(hipMemcpyAsync(d_rsrc, rk->col_src, sizeof(int) * (size_t)rk->G, hipMemcpyHostToDevice, sq));
+            HIP_TRY(hipMemcpyAsync(d_rcq, hrq.data(), sizeof(int) * (size_t)rk->G, hipMemcpyHostToDevice, sq));
+            HIP_TRY(hipMemcpyAsync(d_ridx, hidx.data(), sizeof(int) * hidx.size(), hipMemcpyHostToDevice, sq));
+            if (rk->level) HIP_TRY(hipMemcpyAsync(d_rlev, rk->level, sizeof(double) * (size_t)rk->G, hipMemcpyHostToDevice, sq));
+        }
         if (kc && pc) hipLaunchKernelGGL(k_rollout_policy_kpi, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a, pd, kd);
         else if (kc) hipLaunchKernelGGL(k_rollout_kpi, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a, kd);
         else if (pc) hipLaunchKernelGGL(k_rollout_policy, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a, pd);
@@ -223,6 +291,13 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
         auto get = [&](auto *out, const auto &buf, size_t count) -> hipError_t {
             return out && buf ? hipMemcpyAsync(out, buf, sizeof(*out) * count, hipMemcpyDeviceToHost, sq) : hipSuccess;
         };
+        if (rk) {      /* behind the rollout kernel on the same stream: its per-trajectory results are this kernel's input */
+            hipLaunchKernelGGL(k_rollout_risk, dim3(risk_grid), dim3(64 * RISK_WAVES), risk_lds, sq, ra);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(get(rk->mean, d_rmean, rg)); HIP_TRY(get(rk->min, d_rmin, rg)); HIP_TRY(get(rk->max, d_rmax, rg)); HIP_TRY(get(rk->min_c, d_rminc, rg));
+            HIP_TRY(get(rk->max_c, d_rmaxc, rg)); HIP_TRY(get(rk->n_exceed, d_rex, rg)); HIP_TRY(get(rk->quantile, d_rq, rgl)); HIP_TRY(get(rk->quantile_c, d_rqc, rgl));
+            HIP_TRY(get(rk->cvar_hi, d_rhi, rgl)); HIP_TRY(get(rk->cvar_lo, d_rlo, rgl)); HIP_TRY(get(rk->counts, d_rcnt, (size_t)batch * 4));
+        }
         HIP_TRY(get(x_out, d_x, cx)); HIP_TRY(get(v_out, d_v, cv)); HIP_TRY(get(y_out, d_y, cy)); HIP_TRY(get(cons_vio_out, d_vio, ck)); HIP_TRY(get(cons_row_out, d_row, ck));
         HIP_TRY(get(cost_out, d_cost, T)); HIP_TRY(get(mu_total_out, d_mu, T)); HIP_TRY(get(worst_vio_out, d_wv, T));
         HIP_TRY(get(worst_step_out, d_ws, T)); HIP_TRY(get(steps_done_out, d_sd, T)); HIP_TRY(get(end_status_out, d_es, T));
@@ -288,6 +363,29 @@ int mld_rollout_kpi(mld_problem_t *p, mld_problem_t *aux, int policy, int K, int
     const RolloutOut out{x_out, v_out, y_out, cons_vio_out, cons_row_out, cost_out, mu_total_out, worst_vio_out, worst_step_out, steps_done_out, end_status_out, stats};
     const KpiCall kc{n_kpi, {w_x, w_v, w_y, w_omega, w_xk1}, price_chan, thresh, vio_tol, price_start, sum, min, max, min_step, max_step, n_above, n_changes, n_vio};
     return rollout_impl(who, policy ? &pc : nullptr, p, aux, K, S, u_seq, omega_seq, start, step, cost_w, cost_rows, out, nullptr, &kc);
+}
+
+/* mld_rollout_kpi (n_kpi >= 1) or the plain rollouts (n_kpi == 0: no table, the KPI arguments are ignored) with the statistics across the realisations of every
+ * instance reduced on the device behind the rollout (k_rollout_risk): rollout_impl with a RiskCall, so every refusal of the others is made by the same code. */
+int mld_rollout_risk(mld_problem_t *p, mld_problem_t *aux, int policy, int K, int S, const double *u_seq, const double *u_prev, const double *omega_seq,
+                     const int64_t *start, int step, const double *cost_w, int cost_rows, int n_kpi,
+                     const double *w_x, const double *w_v, const double *w_y, const double *w_omega, const double *w_xk1,
+                     const int32_t *price_chan, const double *thresh, double vio_tol, const int64_t *price_start,
+                     double *x_out, double *v_out, double *y_out, double *cons_vio_out, int32_t *cons_row_out,
+                     double *cost_out, double *mu_total_out, double *worst_vio_out, int32_t *worst_step_out, int32_t *steps_done_out, int32_t *end_status_out,
+                     int32_t *switches_out, int64_t stats[4],
+                     double *sum, double *min, double *max, int32_t *min_step, int32_t *max_step, int32_t *n_above, int32_t *n_changes, int32_t *n_vio,
+                     int G, const int32_t *col_src, const int32_t *col_q, const double *level, int L, const double *alpha,
+                     double *r_mean, double *r_min, double *r_max, int32_t *r_min_c, int32_t *r_max_c, int32_t *r_n_exceed,
+                     double *r_quantile, int32_t *r_quantile_c, double *r_cvar_hi, double *r_cvar_lo, int32_t *counts)
+{
+    static const char who[] = "mld_rollout_risk";
+    if (int rc = entry_guard(p, who, true, "no batch resident (mld_upload_batch)")) return rc;
+    const PolicyCall pc{u_prev, switches_out};
+    const RolloutOut out{x_out, v_out, y_out, cons_vio_out, cons_row_out, cost_out, mu_total_out, worst_vio_out, worst_step_out, steps_done_out, end_status_out, stats};
+    const KpiCall kc{n_kpi, {w_x, w_v, w_y, w_omega, w_xk1}, price_chan, thresh, vio_tol, price_start, sum, min, max, min_step, max_step, n_above, n_changes, n_vio};
+    const RiskCall rk{G, col_src, col_q, level, L, alpha, r_mean, r_min, r_max, r_min_c, r_max_c, r_n_exceed, r_quantile, r_quantile_c, r_cvar_hi, r_cvar_lo, counts};
+    return rollout_impl(who, policy ? &pc : nullptr, p, aux, K, S, u_seq, omega_seq, start, step, cost_w, cost_rows, out, nullptr, n_kpi ? &kc : nullptr, &rk);
 }
 
 } // extern "C"

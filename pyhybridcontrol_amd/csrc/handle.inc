@@ -384,6 +384,17 @@ struct RolloutOut {
     int64_t *stats;
 };
 
+/* What mld_rollout_risk adds to the same body: the columns (G) as (src, q) with their exceedance levels (G, or NULL = +inf), the levels alpha (L), and where
+ * the statistics across the realisations go: mean, min, max, min_c, max_c, n_exceed (batch, G), quantile, quantile_c, cvar_hi, cvar_lo (batch, G, L),
+ * counts (batch, 4); any NULL */
+struct RiskCall {
+    int G; const int32_t *col_src, *col_q; const double *level;
+    int L; const double *alpha;
+    double *mean, *min, *max; int32_t *min_c, *max_c, *n_exceed;
+    double *quantile; int32_t *quantile_c; double *cvar_hi, *cvar_lo;
+    int32_t *counts;
+};
+
 /* What mld_warm_start_from_rollout adds to the same body: the rows that have a start keep it (MLD_START_KEEP), and where the source per instance (batch, or
  * NULL) and the counts [trajectories, written, kept, none] (or NULL) go */
 struct StartCall { bool keep; int32_t *source_out; int64_t *stats; };

@@ -816,7 +816,7 @@ class GpuProblem(object):
         return np.ascontiguousarray(u_prev)
 
     def rollout(self, resolve, K=None, u_seq=None, omega_seq=None, start=None, step=0, cost_w=None, trajectories=False, policy=False, u_prev=None,
-                kpis=None, price_start=None, vio_tol=1e-6):
+                kpis=None, price_start=None, vio_tol=1e-6, risk=None, per_trajectory=True):
         """open-loop rollout of the resident batch under S realised disturbances, on device (mld_rollout_batch, kernel k_rollout): the reference's
         MldModel.lsim / lsim_k in a loop with _compute_aux at every step (models/mld_model.py:543-642, 647-699, 701-766), batch x S trajectories in one launch.
         resolve: an aux_resolve.BatchAuxResolver(..., small_lds=True) over the same models.  u_seq (batch, K, nu) / (K, nu), or None = the inputs of the
@@ -839,7 +839,15 @@ class GpuProblem(object):
         S realisations of an instance, the price sim_step(step=step + k) records.  The result gains kpi = dict(names, sum, min, max (batch, S, n_kpi),
         min_step, max_step, n_above, n_changes (batch, S, n_kpi) int32, n_vio (batch, S) int32: steps with cons_vio > vio_tol); a trajectory that does not
         end 0 has NaN / -1.  The figures are those of the logged stepwise campaign's sim_log_summary and of simlog.rollout_kpis_np, bit for bit;
-        trajectories finished on the host get theirs from rollout_kpis_np.  Without kpis the call is what it was."""
+        trajectories finished on the host get theirs from rollout_kpis_np.  Without kpis the call is what it was.
+        risk: a simlog.RiskTable -- the statistics ACROSS the S realisations of every instance, reduced on the device behind the rollout (mld_rollout_risk,
+        kernel k_rollout_risk): per column (cost, mu_total, worst_vio, switches, n_vio or a KPI's statistic; a table that names KPIs is built over `kpis`)
+        over the realisations that ended 0, sorted by (value, c).  The result gains risk = dict(names, levels, mean, min, max (batch, G), min_c, max_c,
+        n_exceed (batch, G) int32, quantile, cvar_hi, cvar_lo (batch, G, L), quantile_c (batch, G, L) int32, n_complete, n_infeasible, n_declined,
+        n_not_attempted (batch,) int32); an instance without a complete realisation has NaN / +inf / -inf / -1 / 0.  S <= 64.  The figures are those of
+        simlog.rollout_risk_np on the same result, bit for bit; the instances with a trajectory finished on the host take theirs from rollout_risk_np of
+        the finished arrays.  per_trajectory=False (with risk only) asks for nothing per trajectory: every (batch, S, ...) entry, kpi included, is neither
+        downloaded nor returned.  With risk=None the call and its result are what they were."""
         from . import simlog
         d, B, nv = self.model.dims, self.batch, self.model.nv
         nx, nu, nw, ny = d["nx"], d["nu"], d["nomega"], d["ny"]
@@ -893,7 +901,68 @@ class GpuProblem(object):
                 raise ValueError("KPI %r is priced, but price_start is None (the starts of the realised prices, one per instance)"
                                  % (kpis.names[int(np.flatnonzero(karr["price_chan"] >= 0)[0])],))
 
-        def call(full):
+        rarr = None
+        if risk is None:
+            if not per_trajectory:
+                raise ValueError("per_trajectory=False without risk (nothing would be returned)")
+        else:
+            if trajectories and not per_trajectory:
+                raise ValueError("trajectories=True with per_trajectory=False")
+            if S > simlog.RISK_S_MAX:
+                raise ValueError("risk: S = %d realisations (at most %d)" % (S, simlog.RISK_S_MAX))
+            rarr = risk.arrays()
+            if np.any(rarr["col_src"] == 3) and not policy:
+                raise ValueError("risk column %r reads switches, but the rollout has no policy (policy=True)" % (risk.names[int(np.flatnonzero(rarr["col_src"] == 3)[0])],))
+            if np.any(rarr["col_src"] >= 4):
+                if kpis is None:
+                    raise ValueError("risk column %r reads the KPIs, but kpis is None" % (risk.names[int(np.flatnonzero(rarr["col_src"] >= 4)[0])],))
+                if risk.kpis is not kpis and list(risk.kpis.names) != list(kpis.names):
+                    raise ValueError("the risk table was built over another KPI table (%s, this call's %s)" % (risk.kpis.names, kpis.names))
+
+        def call_risk(full, per):
+            """mld_rollout_risk: the per-trajectory arrays only with per, the trajectories only with full"""
+            G, L = len(risk), len(risk.levels)
+            o = {}
+            if per:
+                o.update(cost=np.zeros((B, S)), mu_total=np.zeros((B, S)), worst_vio=np.zeros((B, S)), worst_step=np.zeros((B, S), np.int32),
+                         steps_done=np.zeros((B, S), np.int32), end_status=np.zeros((B, S), np.int32))
+                if policy:
+                    o["switches"] = np.zeros((B, S), np.int32)
+            if full:
+                o.update(x=np.zeros((B, S, K + 1, nx)), v=np.zeros((B, S, K, nv)), y=np.zeros((B, S, K, ny)), cons_vio=np.zeros((B, S, K)),
+                         cons_row=np.zeros((B, S, K), np.int32))
+            stats = np.zeros(4, np.int64)
+            Q, kp, tabs, chan = 0, {}, [None] * 5, None
+            if kpis is not None:
+                Q, tabs, chan = len(kpis), ktabs, karr["price_chan"]
+                if per:
+                    kp = dict(names=list(kpis.names), sum=np.zeros((B, S, Q)), min=np.zeros((B, S, Q)), max=np.zeros((B, S, Q)), min_step=np.zeros((B, S, Q), np.int32),
+                              max_step=np.zeros((B, S, Q), np.int32), n_above=np.zeros((B, S, Q), np.int32), n_changes=np.zeros((B, S, Q), np.int32),
+                              n_vio=np.zeros((B, S), np.int32))
+            rk = dict(names=list(risk.names), levels=list(risk.levels), mean=np.zeros((B, G)), min=np.zeros((B, G)), min_c=np.zeros((B, G), np.int32),
+                      max=np.zeros((B, G)), max_c=np.zeros((B, G), np.int32), n_exceed=np.zeros((B, G), np.int32), quantile=np.zeros((B, G, L)),
+                      quantile_c=np.zeros((B, G, L), np.int32), cvar_hi=np.zeros((B, G, L)), cvar_lo=np.zeros((B, G, L)))
+            counts = np.zeros((B, 4), np.int32)
+            check(_lib.load().mld_rollout_risk(
+                self._h, aux, 1 if policy else 0, K, S, _lib.dptr(u_seq), _lib.dptr(u_prev), _lib.dptr(omega_seq) if nw else None, lp(st), int(step),
+                _lib.dptr(cost_w), rows, Q, *([_lib.dptr(t) for t in tabs] + [ip(chan), _lib.dptr(kthr), float(vio_tol), lp(pst)]),
+                _lib.dptr(o.get("x")), _lib.dptr(o.get("v")), _lib.dptr(o.get("y")), _lib.dptr(o.get("cons_vio")), ip(o.get("cons_row")),
+                _lib.dptr(o.get("cost")), _lib.dptr(o.get("mu_total")), _lib.dptr(o.get("worst_vio")), ip(o.get("worst_step")), ip(o.get("steps_done")),
+                ip(o.get("end_status")), ip(o.get("switches")), lp(stats), _lib.dptr(kp.get("sum")), _lib.dptr(kp.get("min")), _lib.dptr(kp.get("max")),
+                ip(kp.get("min_step")), ip(kp.get("max_step")), ip(kp.get("n_above")), ip(kp.get("n_changes")), ip(kp.get("n_vio")),
+                G, ip(rarr["col_src"]), ip(rarr["col_q"]), _lib.dptr(rarr["level"]), L, _lib.dptr(rarr["alpha"]),
+                _lib.dptr(rk["mean"]), _lib.dptr(rk["min"]), _lib.dptr(rk["max"]), ip(rk["min_c"]), ip(rk["max_c"]), ip(rk["n_exceed"]),
+                _lib.dptr(rk["quantile"]), ip(rk["quantile_c"]), _lib.dptr(rk["cvar_hi"]), _lib.dptr(rk["cvar_lo"]), ip(counts)))
+            for i, key in enumerate(simlog.RISK_COUNTS):
+                rk[key] = np.ascontiguousarray(counts[:, i])
+            if kp:
+                o["kpi"] = kp
+            o["risk"] = rk
+            return o, stats
+
+        def call(full, per=True):
+            if risk is not None:
+                return call_risk(full, per)
             o = dict(cost=np.zeros((B, S)), mu_total=np.zeros((B, S)), worst_vio=np.zeros((B, S)), worst_step=np.zeros((B, S), np.int32),
                      steps_done=np.zeros((B, S), np.int32), end_status=np.zeros((B, S), np.int32))
             if full:
@@ -931,10 +1000,10 @@ class GpuProblem(object):
                 lp(stats)))
             return o, stats
 
-        out, stats = call(trajectories)
+        out, stats = call(trajectories, per_trajectory)
         n_host = int(stats[3])
         if n_host:
-            if not trajectories:
+            if not trajectories or not per_trajectory:
                 out, stats = call(True)      # (the completion continues from the states and slices the device left: it needs the trajectories)
             midx = getattr(self, "_model_idx", None)
             midx = np.zeros(B, np.int64) if midx is None else np.asarray(midx, np.int64)
@@ -958,7 +1027,7 @@ class GpuProblem(object):
             else:
                 om_all = omega_seq if nw else np.zeros((B, S, K, 0))
             T = B * S
-            kpi_dev = out.pop("kpi", None)
+            kpi_dev, risk_dev = out.pop("kpi", None), out.pop("risk", None)
             flat = {k: out[k].reshape((T,) + out[k].shape[2:]) for k in out}
             todo = np.where(flat["end_status"] == 2)[0]
             n_host = int(todo.size)
@@ -980,12 +1049,20 @@ class GpuProblem(object):
                 for key in simlog.KPI_ROLLOUT_KEYS:
                     kpi_dev[key][sel] = host[key][sel]
                 out["kpi"] = kpi_dev
-        es = out["end_status"]
+            if risk_dev is not None:      # the instances with a trajectory finished here take the numpy rule's figures of the finished arrays
+                host = simlog.rollout_risk_np(out, risk, policy=bool(policy))
+                sel = np.unique(todo // S)
+                for key in simlog.RISK_COL_KEYS + simlog.RISK_LEVEL_KEYS + simlog.RISK_COUNTS:
+                    risk_dev[key][sel] = host[key][sel]
+                out["risk"] = risk_dev
+        es = out.get("end_status")
         out["stats"] = dict(trajectories=int(stats[0]), complete=int((es == 0).sum()) if n_host else int(stats[1]), infeasible=int((es == 1).sum()) if n_host else int(stats[2]),
                             declined=int(stats[3]), not_attempted=int(stats[0] - stats[1] - stats[2] - stats[3]), finished_on_host=n_host)
         if n_host and not trajectories:
             for k in ("x", "v", "y", "cons_vio", "cons_row"):
                 del out[k]
+        if not per_trajectory:
+            out = dict(risk=out["risk"], stats=out["stats"])
         return out
 
     def sim_log(self, first=0, count=None):

@@ -421,6 +421,156 @@ def rollout_kpis_np(traj, kpis, price=None, vio_tol=1e-6, omega_seq=None, model_
     return out
 
 
+# ---- rollout risk: statistics across the realisations of a rollout (GpuProblem.rollout(risk=...), mld_rollout_risk, kernel k_rollout_risk) ----------------
+RISK_COLS_MAX, RISK_LEVELS_MAX, RISK_S_MAX = 64, 8, 64      # MLD_RISK_COLS_MAX, MLD_RISK_LEVELS_MAX, MLD_RISK_S_MAX
+RISK_SOURCES = ("cost", "mu_total", "worst_vio", "switches", "n_vio", "kpi_sum", "kpi_min", "kpi_max", "kpi_n_above", "kpi_n_changes")      # src = the index
+RISK_COUNTS = ("n_complete", "n_infeasible", "n_declined", "n_not_attempted")      # the endings 0, 1, 2, -1
+RISK_COL_KEYS = ("mean", "min", "min_c", "max", "max_c", "n_exceed")               # (batch, G)
+RISK_LEVEL_KEYS = ("quantile", "quantile_c", "cvar_hi", "cvar_lo")                 # (batch, G, L)
+_RISK_KPI_KEYS = {5: "sum", 6: "min", 7: "max", 8: "n_above", 9: "n_changes"}
+
+
+class RiskTable(object):
+    """The columns of one risk reduction: each a per-trajectory result of the rollout -- cost, mu_total, worst_vio, switches (policy only), n_vio, or a KPI's
+    sum / min / max / n_above / n_changes -- reduced over the complete realisations of every instance.  kpis: the simlog.KpiTable of the same rollout (needed by
+    n_vio and the kpi_* sources), levels: the alpha in (0, 1] of the quantiles and tail means, at most 8."""
+
+    def __init__(self, kpis=None, levels=()):
+        self.kpis = kpis
+        self.levels = [float(a) for a in levels]
+        if len(self.levels) > RISK_LEVELS_MAX:
+            raise ValueError("a risk table holds at most %d levels" % RISK_LEVELS_MAX)
+        for a in self.levels:
+            if not (0.0 < a <= 1.0):
+                raise ValueError("level %r, expected alpha in (0, 1]" % (a,))
+        self.names, self._src, self._q, self._level = [], [], [], []
+
+    def __len__(self):
+        return len(self.names)
+
+    def add(self, name, source, kpi=None, level=None):
+        """one column: source one of RISK_SOURCES, kpi the KPI's name for the kpi_* sources, level the threshold of n_exceed (None = +inf).  ValueError on a
+        duplicate name, a 65th column, an unknown source or KPI, a kpi_* source or n_vio without a KPI table, kpi given for another source, a NaN level."""
+        if name in self.names:
+            raise ValueError("a column named %r has been added already" % (name,))
+        if len(self.names) >= RISK_COLS_MAX:
+            raise ValueError("a risk table holds at most %d columns" % RISK_COLS_MAX)
+        if source not in RISK_SOURCES:
+            raise ValueError("column %r: source %r, expected one of %s" % (name, source, ", ".join(RISK_SOURCES)))
+        src, q = RISK_SOURCES.index(source), 0
+        if src >= 4 and (self.kpis is None or len(self.kpis) < 1):
+            raise ValueError("column %r: source %r needs the rollout's KPI table (RiskTable(kpis=...))" % (name, source))
+        if src >= 5:
+            if kpi not in self.kpis.names:
+                raise ValueError("column %r: kpi %r is not a KPI of the table (%s)" % (name, kpi, ", ".join(map(str, self.kpis.names))))
+            q = self.kpis.names.index(kpi)
+        elif kpi is not None:
+            raise ValueError("column %r: kpi given, but source %r is not a KPI's" % (name, source))
+        if level is not None and np.isnan(float(level)):
+            raise ValueError("column %r: level is NaN" % (name,))
+        self.names.append(name)
+        self._src.append(src)
+        self._q.append(q)
+        self._level.append(np.inf if level is None else float(level))
+        return self
+
+    def arrays(self):
+        """the arguments of mld_rollout_risk: dict(col_src, col_q (G,) int32, level (G,) or None where no column gave one, alpha (L,))"""
+        if not self.names:
+            raise ValueError("the table holds no column")
+        level = np.asarray(self._level, dtype=np.float64)
+        return dict(col_src=np.asarray(self._src, dtype=np.int32), col_q=np.asarray(self._q, dtype=np.int32),
+                    level=None if np.all(np.isposinf(level)) else level, alpha=np.asarray(self.levels, dtype=np.float64))
+
+
+def risk_rank_table(alpha, S):
+    """the rank table the host uploads: idx (L, S) int32 with idx[l, n - 1] = the smallest i >= 0 with float(i + 1) >= alpha[l] * float(n), the index
+    ceil(alpha n) - 1, for n = 1 .. S"""
+    alpha = np.asarray(alpha, dtype=np.float64).reshape(-1)
+    idx = np.zeros((alpha.size, int(S)), np.int32)
+    for l, a in enumerate(alpha):
+        for n in range(1, int(S) + 1):
+            an = np.float64(a) * np.float64(n)
+            i = 0
+            while i + 1 < n and not (np.float64(i + 1) >= an):
+                i += 1
+            idx[l, n - 1] = i
+    return idx
+
+
+def _tree64(leaves):
+    """T over the last axis (64 leaves): neighbours added pairwise, six times; every addition is one rounded numpy addition"""
+    t = np.asarray(leaves, dtype=np.float64)
+    while t.shape[-1] > 1:
+        t = t.reshape(t.shape[:-1] + (t.shape[-1] // 2, 2))
+        t = t[..., 0] + t[..., 1]
+    return t[..., 0]
+
+
+def rollout_risk_np(out, risk, policy=False):
+    """GpuProblem.rollout(risk=...)'s "risk" stated in numpy (mld_rollout_risk, kernel k_rollout_risk; the rule: include/mldgpu.h): out the dict rollout()
+    returns -- cost, mu_total, worst_vio, end_status (B, S), switches with policy=True, kpi where a column reads one --, risk a RiskTable.  Over the COMPLETE
+    realisations of an instance (end_status == 0), sorted ascending by (value, c) with NaN last: mean, min / min_c, max / max_c, n_exceed (B, G); per level
+    quantile, quantile_c, cvar_hi, cvar_lo (B, G, L); the counts of the four endings (B,).  The sums are the balanced tree over 64 leaves.
+    Returns dict(names, levels, <those arrays>)."""
+    arr = risk.arrays()
+    es = np.asarray(out["end_status"])
+    B, S = es.shape
+    if S > RISK_S_MAX:
+        raise ValueError("S = %d realisations (at most %d)" % (S, RISK_S_MAX))
+    G, L = len(risk), len(risk.levels)
+    g = np.zeros((B, G, S))
+    for j, (src, q) in enumerate(zip(arr["col_src"], arr["col_q"])):
+        if src == 3 and (not policy or "switches" not in out):
+            raise ValueError("column %r reads switches: the rollout has to be a policy's (policy=True)" % (risk.names[j],))
+        if src >= 4 and "kpi" not in out:
+            raise ValueError("column %r reads the KPIs: out has no 'kpi'" % (risk.names[j],))
+        if src < 4:
+            col = out[RISK_SOURCES[src]]
+        elif src == 4:
+            col = out["kpi"]["n_vio"]
+        else:
+            col = np.asarray(out["kpi"][_RISK_KPI_KEYS[int(src)]])[:, :, q]
+        g[:, j, :] = np.asarray(col, dtype=np.float64)
+    complete = np.broadcast_to((es == 0)[:, None, :], (B, G, S))
+    level = np.full(G, np.inf) if arr["level"] is None else arr["level"]
+    n = (es == 0).sum(axis=1).astype(np.int32)
+    res = dict(names=list(risk.names), levels=list(risk.levels))
+    for key, e in zip(RISK_COUNTS, (0, 1, 2, -1)):
+        res[key] = (es == e).sum(axis=1).astype(np.int32)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        nan = np.isnan(g) & complete
+        c = np.broadcast_to(np.arange(S), (B, G, S))
+        order = np.lexsort((c, np.where(nan | ~complete, 0.0, g), nan, ~complete), axis=-1)      # (absent, isnan, g, c): the last key is the first
+        pad = lambda a: np.concatenate([a, np.zeros((B, G, 64 - S))], axis=-1)
+        srt, r = pad(np.take_along_axis(np.where(complete, g, 0.0), order, axis=-1)), np.arange(64)
+        nn = n[:, None].astype(np.float64)
+        res["mean"] = np.where(n[:, None] > 0, _tree64(pad(np.where(complete, g, 0.0))) / nn, np.nan)
+        m = (complete & ~nan).sum(axis=-1)      # the numbers: sorted[0 .. m)
+        some = m > 0
+        top = np.take_along_axis(srt, np.maximum(m - 1, 0)[..., None], axis=-1)[..., 0]
+        first_top = ((srt == top[..., None]) & (r < m[..., None])).argmax(axis=-1)
+        res["min"] = np.where(some, srt[..., 0], np.inf)
+        res["min_c"] = np.where(some, order[..., 0], -1).astype(np.int32)
+        res["max"] = np.where(some, np.take_along_axis(srt, first_top[..., None], axis=-1)[..., 0], -np.inf)      # (the value at that c: zeros tie, signs may differ)
+        res["max_c"] = np.where(some, np.take_along_axis(order, np.minimum(first_top, S - 1)[..., None], axis=-1)[..., 0], -1).astype(np.int32)
+        res["n_exceed"] = (complete & (g > level[None, :, None])).sum(axis=-1).astype(np.int32)
+        idx = risk_rank_table(arr["alpha"], S)
+        res["quantile"], res["cvar_hi"], res["cvar_lo"] = np.full((B, G, L), np.nan), np.full((B, G, L), np.nan), np.full((B, G, L), np.nan)
+        res["quantile_c"] = np.full((B, G, L), -1, np.int32)
+        live = n > 0
+        for l in range(L):
+            i = idx[l][np.maximum(n, 1) - 1].astype(np.int64)      # (B,)
+            ii = np.broadcast_to(i[:, None, None], (B, G, 1))
+            hi = _tree64(np.where((r >= ii) & (r < n[:, None, None]), srt, 0.0)) / (n - i)[:, None].astype(np.float64)
+            lo = _tree64(np.where(r <= ii, srt, 0.0)) / (i + 1)[:, None].astype(np.float64)
+            at = np.minimum(ii, S - 1)
+            res["quantile"][live, :, l] = np.take_along_axis(srt, ii, axis=-1)[..., 0][live]
+            res["quantile_c"][live, :, l] = np.take_along_axis(order, at, axis=-1)[..., 0][live]
+            res["cvar_hi"][live, :, l], res["cvar_lo"][live, :, l] = hi[live], lo[live]
+    return res
+
+
 def start_from_rollout_np(v, end_status, bins, old=None):
     """GpuProblem.warm_start_from_rollout's byte rule stated in numpy (kernel k_warm_from_rollout): v (B, N_tilde, nv) or (B, 1, N_tilde, nv) of a rollout with
     S = 1, end_status (B,) or (B, 1), bins (n_bin,) the binaries' indices step * nv + pos (np.flatnonzero(GpuProblem.is_bin)), old (B, n_bin) the resident
