@@ -918,6 +918,47 @@ int mld_rollout_risk(mld_problem_t *p, mld_problem_t *aux, int policy, int K, in
                      double *r_mean, double *r_min, double *r_max, int32_t *r_min_c, int32_t *r_max_c, int32_t *r_n_exceed,
                      double *r_quantile, int32_t *r_quantile_c, double *r_cvar_hi, double *r_cvar_lo, int32_t *counts);
 
+/* ---- plan selection: choose among candidate plans by their rollout risk ----------------------------------------------------------------------------------------
+ * A scenario-based controller rolls out several plans -- the one just solved, the shifted previous one, a baseline's nominal sequence, another handle's
+ * scenario plan -- under the SAME S realisations and applies the one whose risk is acceptable and whose cost is lowest; the same step is the safety filter
+ * in front of mld_sim_step_resolve.  mld_rollout_select is the open loop of mld_rollout_risk over P candidate input sequences per instance in ONE launch
+ * (kernels k_rollout_cand / k_rollout_cand_kpi): trajectory (b, p, c) applies candidate p of instance b under realisation c, the disturbance named once
+ * for all candidates -- omega_seq (batch, S, K, nomega) or start (batch, S, n_groups) --, x0, the model, the cost_w row, the price start per instance.
+ * Candidate 0 is the resident plan's inputs where plan_first != 0 (the plan-state tests of mld_rollout_batch with u_seq == NULL apply; an instance without a
+ * usable plan ends -1 for that candidate only); the others are u_cand (batch, P - plan_first, K, nu).  P == 1 with plan_first certifies the plan.
+ * Every per-trajectory output is (batch, P, S[, n_kpi]), the risk of candidate (b, p) is mld_rollout_risk's of "instance" b P + p (k_rollout_risk, unchanged):
+ * every r_* output is (batch, P, G[, L]), counts (batch, P, 4), stats as before over batch P S trajectories.
+ *
+ * THE RULE (csrc/plan_select.inc, kernel k_plan_select queued behind k_rollout_risk).  A statistic is (column, kind, level index): kind 0 mean, 1 min,
+ * 2 max, 3 n_exceed (as a double), 4 quantile[l], 5 cvar_hi[l], 6 cvar_lo[l] of risk column `column`; the level index is read for 4 .. 6 only.  Candidate
+ * (b, p) is ADMISSIBLE iff its count of complete realisations >= min_complete (1 .. S), every one of the n_cons (0 .. MLD_SELECT_CONS_MAX) constraints
+ * value(cons_col[k], cons_kind[k], cons_level[k]) <= cons_bound[k] holds (a NaN value fails), and its objective statistic (obj_col, obj_kind, obj_level) is
+ * not NaN.  choice[b] is the admissible p whose objective comes first in the order (value, p), strict < on the value: a tie, or -0.0 against +0.0, goes to the
+ * smaller p; score[b] its value, n_admissible[b] the count, admissible (batch, P) bytes.  No admissible candidate: choice -1, score NaN.  u_choice
+ * (batch, K, nu) is the chosen sequence and u0_choice (batch, nu) its step 0 -- what mld_sim_step_resolve takes as u0 --, NaN where choice is -1.  Every
+ * output may be NULL.  The figures are bit-identical to simlog.py: select_plan_np on the per-candidate risk of the same call.  The call is host-synchronous,
+ * reads the handle and changes nothing on it.
+ * MLD_ERR_INVALID before anything is queued, the argument named: everything mld_rollout_risk refuses for an open-loop call; P outside 1 .. MLD_SELECT_P_MAX;
+ * batch x P x S > INT_MAX (tested before S <= MLD_RISK_S_MAX, so a huge S names the trajectories); u_cand NULL where P - plan_first > 0, or not finite; a
+ * column, kind or level index out of range (a per-level kind with L == 0 included); a NaN bound; min_complete outside 1 .. S; n_cons outside
+ * 0 .. MLD_SELECT_CONS_MAX; cons_col, cons_kind or cons_bound NULL with n_cons > 0.  cons_level may be NULL: level index 0 for every constraint (and so
+ * refused where a constraint's kind is per level and L == 0). */
+#define MLD_SELECT_P_MAX 64        /* the lanes of a wave: one lane owns one candidate */
+#define MLD_SELECT_CONS_MAX 8
+int mld_rollout_select(mld_problem_t *p, mld_problem_t *aux, int K, int S, int P, int plan_first, const double *u_cand, const double *omega_seq,
+                       const int64_t *start, int step, const double *cost_w, int cost_rows, int n_kpi,
+                       const double *w_x, const double *w_v, const double *w_y, const double *w_omega, const double *w_xk1,
+                       const int32_t *price_chan, const double *thresh, double vio_tol, const int64_t *price_start,
+                       int G, const int32_t *col_src, const int32_t *col_q, const double *level, int L, const double *alpha,
+                       int obj_col, int obj_kind, int obj_level, int n_cons, const int32_t *cons_col, const int32_t *cons_kind, const int32_t *cons_level,
+                       const double *cons_bound, int min_complete,
+                       int32_t *choice, double *score, int32_t *n_admissible, uint8_t *admissible, double *u_choice, double *u0_choice,
+                       double *r_mean, double *r_min, double *r_max, int32_t *r_min_c, int32_t *r_max_c, int32_t *r_n_exceed,
+                       double *r_quantile, int32_t *r_quantile_c, double *r_cvar_hi, double *r_cvar_lo, int32_t *counts,
+                       double *cost_out, double *mu_total_out, double *worst_vio_out, int32_t *worst_step_out, int32_t *steps_done_out, int32_t *end_status_out,
+                       int64_t stats[4],
+                       double *sum, double *min, double *max, int32_t *min_step, int32_t *max_step, int32_t *n_above, int32_t *n_changes, int32_t *n_vio);
+
 /* Per-instance telemetry of the last solve: time spent inside the solve kernel (device wall clock, ns) and
  * the number of dictionary rows the rank-1 updates touched (x *row_bytes x 2 = bytes streamed by pivots). */
 int mld_download_telemetry(mld_problem_t *, int64_t *latency_ns, int64_t *rows_updated, int64_t *row_bytes);

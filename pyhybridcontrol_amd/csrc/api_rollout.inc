@@ -11,10 +11,15 @@
  * out KPI-minor as k_log_summary reads them, and everything it uploads and the kernel writes lives in temporaries of the call.
  * rk (mld_rollout_risk): the statistics ACROSS the realisations of every instance (rollout_risk.inc: THE RULE) -- the per-trajectory results the columns read
  * get their device temporaries whether or not the caller asked for them (as sc forces d_v and d_es), k_rollout_risk is queued behind the rollout kernel on
- * the same stream and its results are downloaded inside the same queue_and_wait.  The rank table idx[l][n] is built here, once per call. */
+ * the same stream and its results are downloaded inside the same queue_and_wait.  The rank table idx[l][n] is built here, once per call.
+ * sl (mld_rollout_select, always with rk, never with pc or sc): P candidate input sequences per instance under the same S realisations -- the kernels
+ * k_rollout_cand / k_rollout_cand_kpi over batch P S trajectories, t = (b P + p) S + c, while the disturbance buffer stays (batch S, K nw), filled once as
+ * for any other call; k_rollout_risk launched unchanged over batch P "instances"; k_plan_select (plan_select.inc: THE RULE) queued behind it.  The risk
+ * arrays the rule reads get their device temporaries whether or not the caller asked for them; the candidates, the choice and the chosen inputs live in
+ * temporaries of the call. */
 static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p, mld_problem_t *aux, int K, int S, const double *u_seq, const double *omega_seq,
                         const int64_t *start, int step, const double *cost_w, int cost_rows, const RolloutOut &out, const StartCall *sc = nullptr,
-                        const KpiCall *kc = nullptr, const RiskCall *rk = nullptr)
+                        const KpiCall *kc = nullptr, const RiskCall *rk = nullptr, const SelectCall *sl = nullptr)
 {
     double *const x_out = out.x, *const v_out = out.v, *const y_out = out.y, *const cons_vio_out = out.cons_vio, *const cost_out = out.cost,
            *const mu_total_out = out.mu_total, *const worst_vio_out = out.worst_vio;
@@ -28,6 +33,11 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
     if (pc && !p->pol_on) { mld_set_error("%s: no policy uploaded (mld_upload_policy)", who); return MLD_ERR_INVALID; }
     if (K < 1 || S < 1) { mld_set_error("%s: K = %d, S = %d (at least one step and one realisation)", who, K, S); return MLD_ERR_INVALID; }
     if ((long long)batch * S > INT_MAX) { mld_set_error("%s: batch x S = %lld trajectories (at most %d)", who, (long long)batch * S, INT_MAX); return MLD_ERR_INVALID; }
+    if (sl) {
+        if (pc || sc || !rk || u_seq) { mld_set_error("%s: internal: a selection is an open-loop risk call over u_cand", who); return MLD_ERR_INVALID; }
+        if (sl->P < 1 || sl->P > MLD_SELECT_P_MAX) { mld_set_error("%s: P = %d candidates (1 .. MLD_SELECT_P_MAX = %d: a lane of the wave per candidate)", who, sl->P, MLD_SELECT_P_MAX); return MLD_ERR_INVALID; }
+        if ((long long)batch * S * sl->P > INT_MAX) { mld_set_error("%s: batch x P x S = %lld trajectories (at most %d)", who, (long long)batch * S * sl->P, INT_MAX); return MLD_ERR_INVALID; }
+    }
     if (step < 0 || step > INT_MAX - K) { mld_set_error("%s: step = %d (must be >= 0)", who, step); return MLD_ERR_INVALID; }
     if (int rc = aux_fold_check(who, "rolled-out", p, aux)) return rc;
     if (aux) {
@@ -92,12 +102,35 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
             mld_set_error("%s: alpha[%d] = %g (a level in (0, 1])", who, l, rk->alpha[l]); return MLD_ERR_INVALID;
         }
     }
+    /* the selection rule */
+    const int n_own = sl ? sl->P - (sl->plan_first ? 1 : 0) : 0;      /* candidates of u_cand */
+    unsigned s_kinds = 0;                                            /* bit k: some statistic of the rule has kind k */
+    if (sl) {
+        auto stat_ok = [&](const char *col_name, const char *kind_name, const char *lvl_name, int k, int col, int kind, int lvl) -> bool {
+            char at[16] = "";
+            if (k >= 0) snprintf(at, sizeof at, "[%d]", k);
+            if (col < 0 || col >= rk->G) { mld_set_error("%s: %s%s = %d (a column 0 .. G - 1 = %d)", who, col_name, at, col, rk->G - 1); return false; }
+            if (kind < 0 || kind >= SEL_N_KIND) { mld_set_error("%s: %s%s = %d (a kind 0 .. %d: mean, min, max, n_exceed, quantile, cvar_hi, cvar_lo)", who, kind_name, at, kind, SEL_N_KIND - 1); return false; }
+            if (kind >= SEL_QUANTILE && (lvl < 0 || lvl >= rk->L)) { mld_set_error("%s: %s%s = %d (a level index 0 .. L - 1 = %d; kind %d is per level)", who, lvl_name, at, lvl, rk->L - 1, kind); return false; }
+            s_kinds |= 1u << kind;
+            return true;
+        };
+        if (n_own > 0 && !sl->u_cand) { mld_set_error("%s: u_cand is NULL (the %d candidate sequences per instance%s)", who, n_own, sl->plan_first ? " beside the resident plan" : ""); return MLD_ERR_INVALID; }
+        if (!stat_ok("obj_col", "obj_kind", "obj_level", -1, sl->obj_col, sl->obj_kind, sl->obj_level)) return MLD_ERR_INVALID;
+        if (sl->n_cons < 0 || sl->n_cons > MLD_SELECT_CONS_MAX) { mld_set_error("%s: n_cons = %d constraints (0 .. MLD_SELECT_CONS_MAX = %d)", who, sl->n_cons, MLD_SELECT_CONS_MAX); return MLD_ERR_INVALID; }
+        if (sl->n_cons > 0 && !(sl->cons_col && sl->cons_kind && sl->cons_bound)) { mld_set_error("%s: cons_col, cons_kind or cons_bound is NULL with n_cons = %d", who, sl->n_cons); return MLD_ERR_INVALID; }
+        for (int k = 0; k < sl->n_cons; ++k) {
+            if (!stat_ok("cons_col", "cons_kind", "cons_level", k, sl->cons_col[k], sl->cons_kind[k], sl->cons_level ? sl->cons_level[k] : 0)) return MLD_ERR_INVALID;
+            if (std::isnan(sl->cons_bound[k])) { mld_set_error("%s: cons_bound[%d] is NaN", who, k); return MLD_ERR_INVALID; }
+        }
+        if (sl->min_complete < 1 || sl->min_complete > S) { mld_set_error("%s: min_complete = %d (1 .. S = %d)", who, sl->min_complete, S); return MLD_ERR_INVALID; }
+    }
     const size_t stage_d = ro_stage_doubles(nx, nu, nw, aux ? aux->m0 : 0, nv, ny, n_kpi);
     if (sizeof(double) * stage_d > SM_WAVE_BUDGET) {
         mld_set_error("%s: the staging of a trajectory (%zu bytes: x, omega', h, v, y, x_k1) does not fit a wave's share of LDS (%d bytes); step with mld_sim_step_resolve", who, sizeof(double) * stage_d, SM_WAVE_BUDGET);
         return MLD_ERR_INVALID;
     }
-    const bool by_plan = !u_seq && !(pc && p->pol_all_ruled);      /* some channel takes the resident plan's input */
+    const bool by_plan = sl ? sl->plan_first != 0 : (!u_seq && !(pc && p->pol_all_ruled));      /* some channel takes the resident plan's input */
     if (by_plan) {      /* the plan-state tests of sim_step_check */
         if (K > p->N) { mld_set_error("%s: K = %d steps with the resident plan's inputs, but the plan has N_tilde = %d (pass u_seq for a longer rollout)", who, K, p->N); return MLD_ERR_INVALID; }
         if (!p->solved) { mld_set_error("%s: the resident batch has not been solved since its upload / selection (there is no plan to apply; pass u_seq)", who); return MLD_ERR_INVALID; }
@@ -114,11 +147,15 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
         if (!p->pf_len) { mld_set_error("%s: start given, but no profile library is resident (mld_upload_profiles)", who); return MLD_ERR_INVALID; }
         if (int rc = profile_check_starts(p, who, PF_WINDOW, start, batch, S, step, K, gmax)) return rc;
     }
-    const size_t T = (size_t)batch * S;
+    const size_t TW = (size_t)batch * S, T = TW * (size_t)(sl ? sl->P : 1);      /* the rows of the disturbance buffer, and the trajectories */
+    if (sl) for (size_t k = 0; k < (size_t)batch * n_own * K * nu; ++k) if (!std::isfinite(sl->u_cand[k])) {
+        mld_set_error("%s: u_cand of instance %zu, candidate %zu, step %zu, input %zu is not finite (%g)", who, k / ((size_t)n_own * K * nu), k / ((size_t)K * nu) % n_own, k / nu % K, k % nu, sl->u_cand[k]);
+        return MLD_ERR_INVALID;
+    }
     if (u_seq) for (size_t k = 0; k < (size_t)batch * K * nu; ++k) if (!std::isfinite(u_seq[k])) {
         mld_set_error("%s: u_seq of instance %zu, step %zu, input %zu is not finite (%g)", who, k / ((size_t)K * nu), k / nu % K, k % nu, u_seq[k]); return MLD_ERR_INVALID;
     }
-    if (omega_seq && nw) for (size_t k = 0; k < T * K * nw; ++k) if (!std::isfinite(omega_seq[k])) {
+    if (omega_seq && nw) for (size_t k = 0; k < TW * K * nw; ++k) if (!std::isfinite(omega_seq[k])) {
         mld_set_error("%s: omega_seq of trajectory %zu, step %zu, channel %zu is not finite (%g)", who, k / ((size_t)K * nw), k / nw % K, k % nw, omega_seq[k]); return MLD_ERR_INVALID;
     }
     if (pc && pc->u_prev) for (size_t k = 0; k < (size_t)batch * nu; ++k) if (!std::isfinite(pc->u_prev[k])) {
@@ -147,12 +184,13 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
     std::vector<double> hW, hthr; std::vector<int> hpc;
     DevBuf<double> d_rlev, d_rmean, d_rmin, d_rmax, d_rq, d_rhi, d_rlo; DevBuf<int> d_rsrc, d_rcq, d_ridx, d_rminc, d_rmaxc, d_rex, d_rqc, d_rcnt;      /* rk */
     std::vector<int> hrq, hidx;
+    DevBuf<double> d_ucand, d_sscore, d_such, d_su0; DevBuf<int> d_schoice, d_snadm; DevBuf<unsigned char> d_sadm;      /* sl */
     DevBuf<unsigned char> d_old; DevBuf<int> d_src;      /* sc: the resident start as it was (where rows are kept), the source per instance */
     if (pc && !pc->u_prev) { if (int rc = policy_state_ready(p, who)) return rc; }      /* (an upload's reset state, laid out on first use: nothing a caller can see changes) */
     if (pc && pc->u_prev) HIP_TRY(d_uprev.alloc(std::max<size_t>(1, (size_t)batch * nu)));
     if (u_seq) HIP_TRY(d_u.alloc(std::max<size_t>(1, (size_t)batch * Kz * nu)));
-    if (!sc) HIP_TRY(d_om.alloc(std::max<size_t>(1, T * Kz * nw)));
-    if (start) HIP_TRY(d_start.alloc(T * p->pf_groups));
+    if (!sc) HIP_TRY(d_om.alloc(std::max<size_t>(1, TW * Kz * nw)));
+    if (start) HIP_TRY(d_start.alloc(TW * p->pf_groups));
     if (cost_w) HIP_TRY(d_cw.alloc(std::max<size_t>(1, (size_t)cost_rows * Kz * nv)));
     /* an output that was asked for and is not empty gets a device buffer (take), and is copied back after the kernel (get) */
     const size_t cx = T * (Kz + 1) * nx, cv = T * Kz * nv, cy = T * Kz * ny, ck = T * Kz;
@@ -161,7 +199,8 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
     HIP_TRY(take(d_cost, cost_out, T)); HIP_TRY(take(d_mu, mu_total_out, T)); HIP_TRY(take(d_wv, worst_vio_out, T));
     HIP_TRY(take(d_ws, worst_step_out, T)); HIP_TRY(take(d_sd, steps_done_out, T)); HIP_TRY(take(d_es, end_status_out, T));
     if (pc) HIP_TRY(take(d_sw, pc->switches_out, T));
-    const size_t rg = rk ? (size_t)batch * rk->G : 0, rgl = rk ? rg * rk->L : 0;
+    const size_t r_inst = (size_t)batch * (size_t)(sl ? sl->P : 1);      /* what k_rollout_risk takes for its instances: i = b P + p */
+    const size_t rg = rk ? r_inst * rk->G : 0, rgl = rk ? rg * rk->L : 0;
     if (rk) {      /* the temporaries of the sources the columns read, asked for or not; the rank table; the results' buffers */
         auto force = [](auto &buf, bool read, size_t count) -> hipError_t { return read && !buf ? buf.alloc(count) : hipSuccess; };
         HIP_TRY(force(d_es, true, T)); HIP_TRY(force(d_cost, r_src >> RISK_COST & 1u, T)); HIP_TRY(force(d_mu, r_src >> RISK_MU_TOTAL & 1u, T));
@@ -174,7 +213,17 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
         if (rk->level) HIP_TRY(d_rlev.alloc(rk->G));
         HIP_TRY(take(d_rmean, rk->mean, rg)); HIP_TRY(take(d_rmin, rk->min, rg)); HIP_TRY(take(d_rmax, rk->max, rg)); HIP_TRY(take(d_rminc, rk->min_c, rg));
         HIP_TRY(take(d_rmaxc, rk->max_c, rg)); HIP_TRY(take(d_rex, rk->n_exceed, rg)); HIP_TRY(take(d_rq, rk->quantile, rgl)); HIP_TRY(take(d_rqc, rk->quantile_c, rgl));
-        HIP_TRY(take(d_rhi, rk->cvar_hi, rgl)); HIP_TRY(take(d_rlo, rk->cvar_lo, rgl)); HIP_TRY(take(d_rcnt, rk->counts, (size_t)batch * 4));
+        HIP_TRY(take(d_rhi, rk->cvar_hi, rgl)); HIP_TRY(take(d_rlo, rk->cvar_lo, rgl)); HIP_TRY(take(d_rcnt, rk->counts, r_inst * 4));
+    }
+    const size_t s_own = (size_t)batch * n_own * Kz * nu, s_seq = (size_t)batch * Kz * nu;
+    if (sl) {      /* the risk arrays the rule reads, asked for or not; the candidates; the choice */
+        auto force = [](auto &buf, bool read, size_t count) -> hipError_t { return read && !buf ? buf.alloc(std::max<size_t>(1, count)) : hipSuccess; };
+        HIP_TRY(force(d_rmean, s_kinds >> SEL_MEAN & 1u, rg)); HIP_TRY(force(d_rmin, s_kinds >> SEL_MIN & 1u, rg)); HIP_TRY(force(d_rmax, s_kinds >> SEL_MAX & 1u, rg));
+        HIP_TRY(force(d_rex, s_kinds >> SEL_N_EXCEED & 1u, rg)); HIP_TRY(force(d_rq, s_kinds >> SEL_QUANTILE & 1u, rgl));
+        HIP_TRY(force(d_rhi, s_kinds >> SEL_CVAR_HI & 1u, rgl)); HIP_TRY(force(d_rlo, s_kinds >> SEL_CVAR_LO & 1u, rgl)); HIP_TRY(force(d_rcnt, true, r_inst * 4));
+        HIP_TRY(d_ucand.alloc(std::max<size_t>(1, s_own)));
+        HIP_TRY(take(d_schoice, sl->choice, (size_t)batch)); HIP_TRY(take(d_sscore, sl->score, (size_t)batch)); HIP_TRY(take(d_snadm, sl->n_admissible, (size_t)batch));
+        HIP_TRY(take(d_sadm, sl->admissible, r_inst)); HIP_TRY(take(d_such, sl->u_choice, s_seq)); HIP_TRY(take(d_su0, sl->u0_choice, (size_t)batch * nu));
     }
     const size_t warm_len = sc ? (size_t)batch * p->nb : 0;
     const bool keep_rows = sc && sc->keep && p->has_warm;
@@ -212,6 +261,7 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
     a.model_idx = p->has_midx ? p->bat.model_idx.get() : nullptr;
     a.x0 = p->bat.x0;
     if (u_seq) { a.u = d_u; a.u_stride = Kz * nu; a.u_step = (size_t)nu; }
+    else if (sl && !by_plan) { a.u = d_ucand; a.u_stride = 0; a.u_step = 0; }      /* every candidate reads u_cand (RoCandDev) */
     else if (by_plan) { a.u = p->bat.v; a.u_stride = (size_t)p->n; a.u_step = (size_t)nv; a.status = p->bat.status; a.obj = p->bat.obj; }      /* rows < batch are the instances' (after the hand-off's device merge) */
     else { a.u = p->bat.x0; a.u_stride = 0; a.u_step = 0; }      /* every channel ruled: u is never read (a valid address all the same) */
     a.om = sc ? p->bat.omega.get() : d_om.get();
@@ -230,7 +280,9 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
         if (priced) { kd.lib = p->pr_lib; kd.price_start = d_kps; }
         kd.sum = d_ksum; kd.min = d_kmin; kd.max = d_kmax; kd.min_step = d_kmins; kd.max_step = d_kmaxs; kd.n_above = d_kabove; kd.n_changes = d_kchg; kd.n_vio = d_knvio;
     }
-    const void *kernel = kc ? (pc ? (const void *)k_rollout_policy_kpi : (const void *)k_rollout_kpi) : (pc ? (const void *)k_rollout_policy : (const void *)k_rollout);
+    RoCandDev cd{};
+    if (sl) { cd.P = sl->P; cd.plan_first = sl->plan_first ? 1 : 0; cd.u_cand = d_ucand; }
+    const void *kernel = sl ? (kc ? (const void *)k_rollout_cand_kpi : (const void *)k_rollout_cand) : kc ? (pc ? (const void *)k_rollout_policy_kpi : (const void *)k_rollout_kpi) : (pc ? (const void *)k_rollout_policy : (const void *)k_rollout);
     if (lds_bytes > 48 * 1024)
         HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     int dev = 0, per_cu = 0; hipDeviceProp_t prop;
@@ -240,7 +292,7 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
     RiskArgs ra{};
     size_t risk_lds = 0; int risk_grid = 1;
     if (rk) {
-        ra.batch = batch; ra.S = S; ra.G = rk->G; ra.L = rk->L; ra.n_kpi = n_kpi; ra.need = r_need;
+        ra.batch = (int)r_inst; ra.S = S; ra.G = rk->G; ra.L = rk->L; ra.n_kpi = n_kpi; ra.need = r_need;
         const size_t stg = risk_stage_doubles(S, n_kpi, r_need, ra.off);
         ra.staged = r_need && sizeof(double) * RISK_WAVES * (RISK_SORT_DOUBLES + stg) <= RISK_LDS_MAX;      /* blocks that do not fit are read in place: the same bits */
         ra.ld = ra.staged ? (n_kpi | 1) : n_kpi;
@@ -255,7 +307,24 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
             HIP_TRY(hipFuncSetAttribute((const void *)k_rollout_risk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)risk_lds));
         int rper = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&rper, (const void *)k_rollout_risk, 64 * RISK_WAVES, risk_lds) != hipSuccess || rper < 1) rper = 1;
-        risk_grid = (int)std::min<long long>(((long long)batch + RISK_WAVES - 1) / RISK_WAVES, (long long)rper * prop.multiProcessorCount);
+        risk_grid = (int)std::min<long long>(((long long)r_inst + RISK_WAVES - 1) / RISK_WAVES, (long long)rper * prop.multiProcessorCount);
+    }
+    SelArgs sa{};
+    int sel_grid = 1;
+    if (sl) {
+        sa.batch = batch; sa.P = sl->P; sa.G = rk->G; sa.L = rk->L; sa.K = K; sa.nu = nu; sa.plan_first = sl->plan_first ? 1 : 0;
+        sa.rule.obj = SelStat{sl->obj_col, sl->obj_kind, sl->obj_kind >= SEL_QUANTILE ? sl->obj_level : 0};
+        sa.rule.n_cons = sl->n_cons; sa.rule.min_complete = sl->min_complete;
+        for (int k = 0; k < sl->n_cons; ++k) {
+            sa.rule.cons[k] = SelStat{sl->cons_col[k], sl->cons_kind[k], sl->cons_kind[k] >= SEL_QUANTILE && sl->cons_level ? sl->cons_level[k] : 0};
+            sa.rule.bound[k] = sl->cons_bound[k];
+        }
+        sa.mean = d_rmean; sa.min = d_rmin; sa.max = d_rmax; sa.n_exceed = d_rex; sa.quantile = d_rq; sa.cvar_hi = d_rhi; sa.cvar_lo = d_rlo; sa.counts = d_rcnt;
+        sa.plan = p->bat.v; sa.plan_stride = (size_t)p->n; sa.plan_step = (size_t)nv; sa.u_cand = d_ucand;
+        sa.choice = d_schoice; sa.score = d_sscore; sa.n_adm = d_snadm; sa.adm = d_sadm; sa.u_choice = d_such; sa.u0_choice = d_su0;
+        int sper = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&sper, (const void *)k_plan_select, 64 * SEL_WAVES, 0) != hipSuccess || sper < 1) sper = 1;
+        sel_grid = (int)std::min<long long>(((long long)batch + SEL_WAVES - 1) / SEL_WAVES, (long long)sper * prop.multiProcessorCount);
     }
     unsigned long long cnt[4] = {};
     /* everything queued on the stream and waited for on every path (queue_and_wait): the caller's arrays and the temporaries may go when this returns */
@@ -264,10 +333,11 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
         if (u_seq && nu) HIP_TRY(hipMemcpyAsync(d_u, u_seq, sizeof(double) * (size_t)batch * Kz * nu, hipMemcpyHostToDevice, sq));
         if (pc && pc->u_prev && nu) HIP_TRY(hipMemcpyAsync(d_uprev, pc->u_prev, sizeof(double) * (size_t)batch * nu, hipMemcpyHostToDevice, sq));
         if (cost_w && nv) HIP_TRY(hipMemcpyAsync(d_cw, cost_w, sizeof(double) * (size_t)cost_rows * Kz * nv, hipMemcpyHostToDevice, sq));
-        if (omega_seq && nw) HIP_TRY(hipMemcpyAsync(d_om, omega_seq, sizeof(double) * T * Kz * nw, hipMemcpyHostToDevice, sq));
+        if (sl && s_own) HIP_TRY(hipMemcpyAsync(d_ucand, sl->u_cand, sizeof(double) * s_own, hipMemcpyHostToDevice, sq));
+        if (omega_seq && nw) HIP_TRY(hipMemcpyAsync(d_om, omega_seq, sizeof(double) * TW * Kz * nw, hipMemcpyHostToDevice, sq));
         if (start) {      /* the windows of K steps gathered into the buffer omega_seq would be uploaded to: one input layout for the kernel */
-            HIP_TRY(hipMemcpyAsync(d_start, start, sizeof(long long) * T * p->pf_groups, hipMemcpyHostToDevice, sq));
-            hipLaunchKernelGGL(k_profile_windows, dim3(profile_grid((long long)T * K * nw)), dim3(256), 0, sq, (int)T, K * nw, nw, S, S, 0, p->pf_groups, d_start.get(),
+            HIP_TRY(hipMemcpyAsync(d_start, start, sizeof(long long) * TW * p->pf_groups, hipMemcpyHostToDevice, sq));
+            hipLaunchKernelGGL(k_profile_windows, dim3(profile_grid((long long)TW * K * nw)), dim3(256), 0, sq, (int)TW, K * nw, nw, S, S, 0, p->pf_groups, d_start.get(),
                                p->pf_chan.get(), step, p->pf_lib.get(), d_om.get());
             HIP_TRY(hipGetLastError());
         }
@@ -283,7 +353,9 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
             HIP_TRY(hipMemcpyAsync(d_ridx, hidx.data(), sizeof(int) * hidx.size(), hipMemcpyHostToDevice, sq));
             if (rk->level) HIP_TRY(hipMemcpyAsync(d_rlev, rk->level, sizeof(double) * (size_t)rk->G, hipMemcpyHostToDevice, sq));
         }
-        if (kc && pc) hipLaunchKernelGGL(k_rollout_policy_kpi, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a, pd, kd);
+        if (sl && kc) hipLaunchKernelGGL(k_rollout_cand_kpi, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a, cd, kd);
+        else if (sl) hipLaunchKernelGGL(k_rollout_cand, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a, cd);
+        else if (kc && pc) hipLaunchKernelGGL(k_rollout_policy_kpi, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a, pd, kd);
         else if (kc) hipLaunchKernelGGL(k_rollout_kpi, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a, kd);
         else if (pc) hipLaunchKernelGGL(k_rollout_policy, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a, pd);
         else hipLaunchKernelGGL(k_rollout, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a);
@@ -296,7 +368,13 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
             HIP_TRY(hipGetLastError());
             HIP_TRY(get(rk->mean, d_rmean, rg)); HIP_TRY(get(rk->min, d_rmin, rg)); HIP_TRY(get(rk->max, d_rmax, rg)); HIP_TRY(get(rk->min_c, d_rminc, rg));
             HIP_TRY(get(rk->max_c, d_rmaxc, rg)); HIP_TRY(get(rk->n_exceed, d_rex, rg)); HIP_TRY(get(rk->quantile, d_rq, rgl)); HIP_TRY(get(rk->quantile_c, d_rqc, rgl));
-            HIP_TRY(get(rk->cvar_hi, d_rhi, rgl)); HIP_TRY(get(rk->cvar_lo, d_rlo, rgl)); HIP_TRY(get(rk->counts, d_rcnt, (size_t)batch * 4));
+            HIP_TRY(get(rk->cvar_hi, d_rhi, rgl)); HIP_TRY(get(rk->cvar_lo, d_rlo, rgl)); HIP_TRY(get(rk->counts, d_rcnt, r_inst * 4));
+        }
+        if (sl) {      /* behind k_rollout_risk on the same stream: the candidates' risk is this kernel's input */
+            hipLaunchKernelGGL(k_plan_select, dim3(sel_grid), dim3(64 * SEL_WAVES), 0, sq, sa);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(get(sl->choice, d_schoice, (size_t)batch)); HIP_TRY(get(sl->score, d_sscore, (size_t)batch)); HIP_TRY(get(sl->n_admissible, d_snadm, (size_t)batch));
+            HIP_TRY(get(sl->admissible, d_sadm, r_inst)); HIP_TRY(get(sl->u_choice, d_such, s_seq)); HIP_TRY(get(sl->u0_choice, d_su0, (size_t)batch * nu));
         }
         HIP_TRY(get(x_out, d_x, cx)); HIP_TRY(get(v_out, d_v, cv)); HIP_TRY(get(y_out, d_y, cy)); HIP_TRY(get(cons_vio_out, d_vio, ck)); HIP_TRY(get(cons_row_out, d_row, ck));
         HIP_TRY(get(cost_out, d_cost, T)); HIP_TRY(get(mu_total_out, d_mu, T)); HIP_TRY(get(worst_vio_out, d_wv, T));
@@ -386,6 +464,33 @@ int mld_rollout_risk(mld_problem_t *p, mld_problem_t *aux, int policy, int K, in
     const KpiCall kc{n_kpi, {w_x, w_v, w_y, w_omega, w_xk1}, price_chan, thresh, vio_tol, price_start, sum, min, max, min_step, max_step, n_above, n_changes, n_vio};
     const RiskCall rk{G, col_src, col_q, level, L, alpha, r_mean, r_min, r_max, r_min_c, r_max_c, r_n_exceed, r_quantile, r_quantile_c, r_cvar_hi, r_cvar_lo, counts};
     return rollout_impl(who, policy ? &pc : nullptr, p, aux, K, S, u_seq, omega_seq, start, step, cost_w, cost_rows, out, nullptr, n_kpi ? &kc : nullptr, &rk);
+}
+
+/* mld_rollout_risk's open loop over P candidate input sequences per instance under the same S realisations (k_rollout_cand / k_rollout_cand_kpi), each
+ * candidate's risk reduced by k_rollout_risk, and per instance the admissible candidate of least objective statistic chosen by k_plan_select behind it
+ * (plan_select.inc: THE RULE): rollout_impl with a SelectCall, so every refusal of the others is made by the same code. */
+int mld_rollout_select(mld_problem_t *p, mld_problem_t *aux, int K, int S, int P, int plan_first, const double *u_cand, const double *omega_seq,
+                       const int64_t *start, int step, const double *cost_w, int cost_rows, int n_kpi,
+                       const double *w_x, const double *w_v, const double *w_y, const double *w_omega, const double *w_xk1,
+                       const int32_t *price_chan, const double *thresh, double vio_tol, const int64_t *price_start,
+                       int G, const int32_t *col_src, const int32_t *col_q, const double *level, int L, const double *alpha,
+                       int obj_col, int obj_kind, int obj_level, int n_cons, const int32_t *cons_col, const int32_t *cons_kind, const int32_t *cons_level,
+                       const double *cons_bound, int min_complete,
+                       int32_t *choice, double *score, int32_t *n_admissible, uint8_t *admissible, double *u_choice, double *u0_choice,
+                       double *r_mean, double *r_min, double *r_max, int32_t *r_min_c, int32_t *r_max_c, int32_t *r_n_exceed,
+                       double *r_quantile, int32_t *r_quantile_c, double *r_cvar_hi, double *r_cvar_lo, int32_t *counts,
+                       double *cost_out, double *mu_total_out, double *worst_vio_out, int32_t *worst_step_out, int32_t *steps_done_out, int32_t *end_status_out,
+                       int64_t stats[4],
+                       double *sum, double *min, double *max, int32_t *min_step, int32_t *max_step, int32_t *n_above, int32_t *n_changes, int32_t *n_vio)
+{
+    static const char who[] = "mld_rollout_select";
+    if (int rc = entry_guard(p, who, true, "no batch resident (mld_upload_batch)")) return rc;
+    const RolloutOut out{nullptr, nullptr, nullptr, nullptr, nullptr, cost_out, mu_total_out, worst_vio_out, worst_step_out, steps_done_out, end_status_out, stats};
+    const KpiCall kc{n_kpi, {w_x, w_v, w_y, w_omega, w_xk1}, price_chan, thresh, vio_tol, price_start, sum, min, max, min_step, max_step, n_above, n_changes, n_vio};
+    const RiskCall rk{G, col_src, col_q, level, L, alpha, r_mean, r_min, r_max, r_min_c, r_max_c, r_n_exceed, r_quantile, r_quantile_c, r_cvar_hi, r_cvar_lo, counts};
+    const SelectCall sl{P, plan_first, u_cand, obj_col, obj_kind, obj_level, n_cons, cons_col, cons_kind, cons_level, cons_bound, min_complete,
+                        choice, score, n_admissible, admissible, u_choice, u0_choice};
+    return rollout_impl(who, nullptr, p, aux, K, S, nullptr, omega_seq, start, step, cost_w, cost_rows, out, nullptr, n_kpi ? &kc : nullptr, &rk, &sl);
 }
 
 } // extern "C"

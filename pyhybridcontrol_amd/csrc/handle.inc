@@ -395,6 +395,18 @@ struct RiskCall {
     int32_t *counts;
 };
 
+/* What mld_rollout_select adds to the same body (always beside a RiskCall, never a PolicyCall): P candidates per instance -- candidate 0 the resident plan
+ * where plan_first is set, the others u_cand (batch, P - plan_first, K, nu) --, the rule (plan_select.inc: objective, constraints, min_complete) and where the
+ * choice goes: choice, score, n_admissible (batch), admissible (batch, P), u_choice (batch, K, nu), u0_choice (batch, nu); any NULL.  Every per-trajectory
+ * output of the call is (batch, P, S, ...), every risk output (batch, P, G[, L]), counts (batch, P, 4). */
+struct SelectCall {
+    int P, plan_first; const double *u_cand;
+    int obj_col, obj_kind, obj_level;
+    int n_cons; const int32_t *cons_col, *cons_kind, *cons_level; const double *cons_bound;
+    int min_complete;
+    int32_t *choice; double *score; int32_t *n_admissible; uint8_t *admissible; double *u_choice, *u0_choice;
+};
+
 /* What mld_warm_start_from_rollout adds to the same body: the rows that have a start keep it (MLD_START_KEEP), and where the source per instance (batch, or
  * NULL) and the counts [trajectories, written, kept, none] (or NULL) go */
 struct StartCall { bool keep; int32_t *source_out; int64_t *stats; };

@@ -178,6 +178,7 @@ __global__ void __launch_bounds__(256) k_warm_from_rollout(long long batch, int 
 #include "aux_step.inc"        // k_aux_inputs / k_aux_merge (mld_sim_step_resolve): between a handle and its auxiliary resolver, the same masking
 #include "rollout.inc"         // k_rollout (mld_rollout_batch): K resolved steps per trajectory in one wave, the same masking
 #include "rollout_risk.inc"    // k_rollout_risk (mld_rollout_risk): statistics across a rollout's realisations, a wave per instance
+#include "plan_select.inc"     // k_plan_select (mld_rollout_select): the admissible candidate plan of least objective statistic, a wave per instance
 #include "fallback.inc"        // k_fallback_inputs / k_fallback_commit (mld_sim_step_fallback): the source of u for an instance without a usable plan
 
 // out[k] = a[k] * b[k]

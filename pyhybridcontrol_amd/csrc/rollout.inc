@@ -279,21 +279,38 @@ struct RoKpiDev {         /* what the KPI kernels take on top, likewise an argum
     int *n_vio;                                           /* (batch S) */
 };
 
+struct RoCandDev {        /* what the candidate kernels take on top (mld_rollout_select), likewise an argument of its own */
+    int P, plan_first;                              /* candidates per instance; candidate 0 is the resident plan (RoDev's u, u_stride, u_step, status, obj) */
+    const double *u_cand;                           /* (batch, P - plan_first, K, nu): the other candidates */
+};
+
 // The kernel body, written once and expanded into both kernels.  (A function template called by the two kernels was tried first: inlined, it left k_rollout
 // with 208 bytes of scratch per lane instead of 156 -- the kernel arguments reach the register allocator by another route.  Expanded in place, the open-loop
 // kernel's listing is the one it had: profiles/policy_rollout_resource_usage.txt.)  POLICY, KPI: literals; `pol`, `kd`: the kernel's RoPolicyDev and RoKpiDev (empty
 // ones where the kernel takes none).  Flat KPI indices are 64-bit: t n_kpi over batch S trajectories.
-#define RO_KERNEL_BODY(POLICY, KPI)                                                                                                                                \
+// CAND (k_rollout_cand / k_rollout_cand_kpi, open loop only): P candidate input sequences per instance under the same S realisations -- trajectory
+// t = (b P + p) S + c over a queue of batch P S; everything per instance is read at b, omega at b S + c (the buffer is laid out once for all candidates), every
+// output at t.  Candidate 0 reads RoDev's u (the resident plan's rows, masked by plan_usable) where `plan_first` is set, the others read cd.u_cand; p, c and
+// the two base addresses are computed once per trajectory, nothing else differs.  The four kernels without it expand RO_KERNEL_BODY as they always did.
+#define RO_KERNEL_BODY3(POLICY, KPI, CAND)                                                                                                                                \
     extern __shared__ double ro_lds[];                                                                                                                             \
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;                                                                                                    \
     sm_f64 *mem = (sm_f64 *)ro_lds + (size_t)wave * ((size_t)S.wave_doubles + a.stage_doubles), *stg = mem + S.wave_doubles;                                       \
-    const unsigned long long total = (unsigned long long)a.batch * a.S;                                                                                            \
+    const unsigned long long total = CAND ? (unsigned long long)a.batch * cd.P * a.S : (unsigned long long)a.batch * a.S;                                          \
     RoModel M;                                                                                                                                                     \
     M.nx = a.nx; M.nu = a.nu; M.nw = a.nw; M.nv = a.nv; M.nmu = a.nmu; M.ny = a.ny; M.nc = a.nc; M.m = a.m; M.n = a.n;                                             \
     for (;;) {                                                                                                                                                     \
         const unsigned long long t = sm_claim(a.counter, lane);                                                                                                    \
         if (t >= total) break;                                                                                                                                     \
-        const long long b = (long long)(t / (unsigned)a.S);                                                                                                        \
+        const long long b = CAND ? (long long)(t / ((unsigned long long)cd.P * (unsigned)a.S)) : (long long)(t / (unsigned)a.S);                                   \
+        [[maybe_unused]] int cp = 0;                                  /* CAND: the candidate, and the row of omega, b S + c */                                     \
+        [[maybe_unused]] unsigned long long tw = t;                                                                                                                \
+        if constexpr (CAND) {                                                                                                                                      \
+            const unsigned long long r = t - (unsigned long long)b * cd.P * a.S;                                                                                   \
+            cp = (int)(r / (unsigned)a.S);                                                                                                                         \
+            tw = (unsigned long long)b * a.S + (r - (unsigned long long)cp * a.S);                                                                                 \
+        }                                                                                                                                                          \
+        [[maybe_unused]] const bool cand_plan = CAND && cd.plan_first && cp == 0;                                                                                  \
         const int mdl = a.model_idx ? a.model_idx[b] : 0;                                                                                                          \
         M.P = plant_mats(a.pack + (size_t)mdl * a.pack_len, a.off);                                                                                                \
         SmArgs A{};                                                                                                                                                \
@@ -306,7 +323,8 @@ struct RoKpiDev {         /* what the KPI kernels take on top, likewise an argum
         }                                                                                                                                                          \
         RoTraj T;                                                                                                                                                  \
         T.K = a.K; T.x0 = a.x0 + (size_t)b * a.nx; T.u = a.u + (size_t)b * a.u_stride; T.u_step = a.u_step;                                                        \
-        T.om = a.om + (size_t)t * a.K * a.nw;                                                                                                                      \
+        if constexpr (CAND) if (!cand_plan) { T.u = cd.u_cand + ((size_t)b * (cd.P - cd.plan_first) + (cp - cd.plan_first)) * a.K * a.nu; T.u_step = (size_t)a.nu; }\
+        T.om = a.om + (size_t)(CAND ? tw : t) * a.K * a.nw;                                                                                                        \
         T.cw = a.cw ? a.cw + (size_t)(a.cw_by_inst ? b : mdl) * a.K * a.nv : nullptr;                                                                              \
         T.x = a.x ? a.x + (size_t)t * (a.K + 1) * a.nx : nullptr; T.v = a.v ? a.v + (size_t)t * a.K * a.nv : nullptr;                                              \
         T.y = a.y ? a.y + (size_t)t * a.K * a.ny : nullptr; T.vio = a.vio ? a.vio + (size_t)t * a.K : nullptr; T.row = a.row ? a.row + (size_t)t * a.K : nullptr;  \
@@ -321,7 +339,7 @@ struct RoKpiDev {         /* what the KPI kernels take on top, likewise an argum
             Q.n_above = kd.n_above + o; Q.n_changes = kd.n_changes + o; Q.n_vio = kd.n_vio + t;                                                                    \
         }                                                                                                                                                          \
         RoResult R;                                                                                                                                                \
-        if (a.status && !plan_usable(a.status, a.obj, (int)b)) {      /* uniform over the wave: no plan whose inputs could be applied */                           \
+        if ((!CAND || cand_plan) && a.status && !plan_usable(a.status, a.obj, (int)b)) {      /* uniform over the wave: no plan whose inputs could be applied */   \
             const double qnan = __builtin_nan("");                                                                                                                 \
             ro_blank(M, T, lane, 0, true);                                                                                                                         \
             R.cost = R.mu_total = R.worst_vio = qnan; R.worst_step = R.worst_row = -1; R.steps_done = 0; R.end_status = RO_NOT_ATTEMPTED;                          \
@@ -343,6 +361,7 @@ struct RoKpiDev {         /* what the KPI kernels take on top, likewise an argum
 
 // Three waves per SIMD asked for: unconstrained the kernel holds 219 VGPRs (two waves) and takes 1.44 x the time; at 168 it spills 42 registers to
 // scratch, outside the pivot loop's hot values (DESIGN section 6).
+#define RO_KERNEL_BODY(POLICY, KPI) const RoCandDev cd{}; RO_KERNEL_BODY3(POLICY, KPI, false)
 __global__ void __launch_bounds__(SM_NT, 3) k_rollout(SmShape S, ProblemDev P, RoDev a)
 {
     const RoPolicyDev pol{};
@@ -368,7 +387,22 @@ __global__ void __launch_bounds__(SM_NT, 3) k_rollout_policy_kpi(SmShape S, Prob
 {
     RO_KERNEL_BODY(true, true)
 }
+
+// The candidate instantiations (mld_rollout_select): the open-loop body twice more, P candidates per instance under the same realisations.
+__global__ void __launch_bounds__(SM_NT, 3) k_rollout_cand(SmShape S, ProblemDev P, RoDev a, RoCandDev cd)
+{
+    const RoPolicyDev pol{};
+    const RoKpiDev kd{};
+    RO_KERNEL_BODY3(false, false, true)
+}
+
+__global__ void __launch_bounds__(SM_NT, 3) k_rollout_cand_kpi(SmShape S, ProblemDev P, RoDev a, RoCandDev cd, RoKpiDev kd)
+{
+    const RoPolicyDev pol{};
+    RO_KERNEL_BODY3(false, true, true)
+}
 #undef RO_KERNEL_BODY
+#undef RO_KERNEL_BODY3
 
 // k_policy_inputs (mld_sim_step_policy): u[b, j] of ONE step for every instance, written into the buffer the resolving step reads its u0 from.  A ruled
 // channel takes the rule's value from the handle's current x0[b] and the resident u_prev[b]; a passed-through one keeps the caller's value (src ==

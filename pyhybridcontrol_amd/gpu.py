@@ -815,6 +815,56 @@ class GpuProblem(object):
             raise ValueError("u_prev has shape %s, expected (%d, %d) or (%d,)" % (u_prev.shape, B, nu, nu))
         return np.ascontiguousarray(u_prev)
 
+    def _rollout_inputs(self, K, omega_seq, start, cost_w, kpis, price_start):
+        """what rollout() and select_plan() share: the disturbance -- exactly one of omega_seq (batch, S, K, nomega) and start --, cost_w and the KPI table with its
+        price starts, tested and made contiguous.  Returns (omega_seq, start array or None, S, cost_w, cost rows, KPI arrays, KPI tables, thresholds, price starts);
+        the last four are None without a table."""
+        from . import simlog
+        d, B, nv = self.model.dims, self.batch, self.model.nv
+        nx, nw, ny = d["nx"], d["nomega"], d["ny"]
+        if (omega_seq is None) == (start is None) and nw:
+            raise ValueError("exactly one of omega_seq and start must be given (%s)" % ("both are" if start is not None else "neither is"))
+        st = None
+        if omega_seq is not None:
+            omega_seq = np.asarray(omega_seq, dtype=np.float64)
+            if omega_seq.ndim != 4 or omega_seq.shape[0] != B or omega_seq.shape[1] < 1 or omega_seq.shape[2:] != (K, nw):
+                raise ValueError("omega_seq has shape %s, expected (%d, S, %d, %d)" % (omega_seq.shape, B, K, nw))
+            omega_seq = np.ascontiguousarray(omega_seq)
+            S = omega_seq.shape[1]
+        elif start is not None:
+            st = self._start_array(start, 1)
+            S = st.shape[1]
+        else:
+            S = 1
+        rows = 0
+        if cost_w is not None:
+            cost_w = np.asarray(cost_w, dtype=np.float64)
+            if cost_w.ndim == 2:
+                cost_w = np.broadcast_to(cost_w, (self.model.n_models,) + cost_w.shape)
+            if cost_w.ndim != 3 or cost_w.shape[0] not in (self.model.n_models, B) or cost_w.shape[1:] != (K, nv):
+                raise ValueError("cost_w has shape %s, expected (%d, %d, %d), (%d, %d, %d) or (%d, %d)" % (cost_w.shape, self.model.n_models, K, nv, B, K, nv, K, nv))
+            cost_w = np.ascontiguousarray(cost_w)
+            rows = cost_w.shape[0]
+        karr = ktabs = kthr = pst = None
+        if kpis is None:
+            if price_start is not None:
+                raise ValueError("price_start given without kpis (it prices the KPIs of the rollout)")
+        else:
+            if kpis.n_models != self.model.n_models:
+                raise ValueError("the KPI table has %d models, the problem %d" % (kpis.n_models, self.model.n_models))
+            want = dict(w_x=nx, w_v=nv, w_y=ny, w_omega=nw, w_xk1=nx)
+            if kpis.widths != want:
+                raise ValueError("the KPI table was built for other dimensions (%s, this problem %s)" % (kpis.widths, want))
+            karr = kpis.arrays()
+            ktabs = [None if karr[k] is None else np.ascontiguousarray(karr[k]) for k in simlog.KPI_TABLES]
+            kthr = None if karr["thresh"] is None else np.ascontiguousarray(karr["thresh"])
+            if price_start is not None:
+                pst = self._price_start(price_start)
+            elif np.any(karr["price_chan"] >= 0):
+                raise ValueError("KPI %r is priced, but price_start is None (the starts of the realised prices, one per instance)"
+                                 % (kpis.names[int(np.flatnonzero(karr["price_chan"] >= 0)[0])],))
+        return omega_seq, st, S, cost_w, rows, karr, ktabs, kthr, pst
+
     def rollout(self, resolve, K=None, u_seq=None, omega_seq=None, start=None, step=0, cost_w=None, trajectories=False, policy=False, u_prev=None,
                 kpis=None, price_start=None, vio_tol=1e-6, risk=None, per_trajectory=True):
         """open-loop rollout of the resident batch under S realised disturbances, on device (mld_rollout_batch, kernel k_rollout): the reference's
@@ -856,50 +906,10 @@ class GpuProblem(object):
             K = u_seq.shape[1]
         K = self.N_tilde if K is None else int(K)
         u_prev = self._u_prev_array(u_prev, policy)
-        if (omega_seq is None) == (start is None) and nw:
-            raise ValueError("exactly one of omega_seq and start must be given (%s)" % ("both are" if start is not None else "neither is"))
-        st = None
-        if omega_seq is not None:
-            omega_seq = np.asarray(omega_seq, dtype=np.float64)
-            if omega_seq.ndim != 4 or omega_seq.shape[0] != B or omega_seq.shape[1] < 1 or omega_seq.shape[2:] != (K, nw):
-                raise ValueError("omega_seq has shape %s, expected (%d, S, %d, %d)" % (omega_seq.shape, B, K, nw))
-            omega_seq = np.ascontiguousarray(omega_seq)
-            S = omega_seq.shape[1]
-        elif start is not None:
-            st = self._start_array(start, 1)
-            S = st.shape[1]
-        else:
-            S = 1
-        rows = 0
-        if cost_w is not None:
-            cost_w = np.asarray(cost_w, dtype=np.float64)
-            if cost_w.ndim == 2:
-                cost_w = np.broadcast_to(cost_w, (self.model.n_models,) + cost_w.shape)
-            if cost_w.ndim != 3 or cost_w.shape[0] not in (self.model.n_models, B) or cost_w.shape[1:] != (K, nv):
-                raise ValueError("cost_w has shape %s, expected (%d, %d, %d), (%d, %d, %d) or (%d, %d)" % (cost_w.shape, self.model.n_models, K, nv, B, K, nv, K, nv))
-            cost_w = np.ascontiguousarray(cost_w)
-            rows = cost_w.shape[0]
+        omega_seq, st, S, cost_w, rows, karr, ktabs, kthr, pst = self._rollout_inputs(K, omega_seq, start, cost_w, kpis, price_start)
         aux = resolve.problem._h if resolve is not None and resolve.problem is not None else None
         ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None
         lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64)) if a is not None else None
-        karr = ktabs = kthr = pst = None
-        if kpis is None:
-            if price_start is not None:
-                raise ValueError("price_start given without kpis (it prices the KPIs of the rollout)")
-        else:
-            if kpis.n_models != self.model.n_models:
-                raise ValueError("the KPI table has %d models, the problem %d" % (kpis.n_models, self.model.n_models))
-            want = dict(w_x=nx, w_v=nv, w_y=ny, w_omega=nw, w_xk1=nx)
-            if kpis.widths != want:
-                raise ValueError("the KPI table was built for other dimensions (%s, this problem %s)" % (kpis.widths, want))
-            karr = kpis.arrays()
-            ktabs = [None if karr[k] is None else np.ascontiguousarray(karr[k]) for k in simlog.KPI_TABLES]
-            kthr = None if karr["thresh"] is None else np.ascontiguousarray(karr["thresh"])
-            if price_start is not None:
-                pst = self._price_start(price_start)
-            elif np.any(karr["price_chan"] >= 0):
-                raise ValueError("KPI %r is priced, but price_start is None (the starts of the realised prices, one per instance)"
-                                 % (kpis.names[int(np.flatnonzero(karr["price_chan"] >= 0)[0])],))
 
         rarr = None
         if risk is None:
@@ -1063,6 +1073,141 @@ class GpuProblem(object):
                 del out[k]
         if not per_trajectory:
             out = dict(risk=out["risk"], stats=out["stats"])
+        return out
+
+    def select_plan(self, resolve, selector, candidates=None, plan_first=False, K=None, omega_seq=None, start=None, step=0, cost_w=None, kpis=None,
+                    price_start=None, vio_tol=1e-6, min_complete=None, per_candidate=False, per_trajectory=False):
+        """choose, per instance, among P candidate input sequences by their rollout risk, on device (mld_rollout_select; kernels k_rollout_cand /
+        k_rollout_cand_kpi, k_rollout_risk, k_plan_select): every candidate is rolled out open loop under the SAME S realisations in one launch, each
+        candidate's risk is rollout(risk=...)'s, and the admissible candidate of least objective statistic wins (simlog.PlanSelector; the smaller p on a tie).
+        selector: a simlog.PlanSelector over the simlog.RiskTable of the call.  candidates (batch, P', K, nu) or (P', K, nu) for every instance;
+        plan_first=True puts the resident plan's inputs in front as candidate 0 (P = P' + 1; candidates=None certifies the plan alone; an instance
+        without a usable plan ends -1 for that candidate only).  resolve, K, omega_seq / start, step, cost_w, kpis, price_start, vio_tol: rollout()'s.
+        min_complete: the least number of complete realisations of an admissible candidate, 1 .. S, None = S.  The handle is not changed.
+        Returns dict(choice (batch,) int32, -1 = no admissible candidate; score (batch,), its objective, NaN without one; n_admissible (batch,) int32;
+        admissible (batch, P) bool; u (batch, K, nu) the chosen sequence and u0 (batch, nu) its step 0 -- what sim_step(resolve=R, u0=...) takes --, NaN
+        without a choice; stats as rollout()'s over batch P S trajectories).  per_candidate=True adds risk: rollout(risk=...)'s dict with a candidate axis,
+        (batch, P, G[, L]) and (batch, P) counts; per_trajectory=True adds cost, mu_total, worst_vio, worst_step, steps_done, end_status (batch, P, S) and,
+        with kpis, kpi (batch, P, S, n_kpi).  The figures are those of simlog.select_plan_np on that risk, bit for bit.  Trajectories the device's LDS solver
+        declined are finished on the host as rollout() finishes them: the instances they belong to take every candidate's risk from rollout() itself and
+        their choice from select_plan_np."""
+        from . import simlog
+        d, B, nv = self.model.dims, self.batch, self.model.nv
+        nx, nu, nw, ny = d["nx"], d["nu"], d["nomega"], d["ny"]
+        pf = 1 if plan_first else 0
+        cand = None
+        if candidates is not None:
+            cand = np.asarray(candidates, dtype=np.float64)
+            if cand.ndim == 3:
+                cand = np.broadcast_to(cand, (B,) + cand.shape)
+            if cand.ndim != 4 or cand.shape[0] != B or cand.shape[3] != nu or (K is not None and cand.shape[2] != int(K)):
+                raise ValueError("candidates has shape %s, expected (%d, P, K, %d) or (P, K, %d)%s" % (cand.shape, B, nu, nu, "" if K is None else " with K = %d" % int(K)))
+            cand = np.ascontiguousarray(cand)
+            K = cand.shape[2]
+        elif not plan_first:
+            raise ValueError("no candidate: candidates is None and plan_first is False")
+        K = self.N_tilde if K is None else int(K)
+        n_own = 0 if cand is None else cand.shape[1]
+        P = n_own + pf
+        if P < 1 or P > simlog.SELECT_P_MAX:
+            raise ValueError("P = %d candidates (1 .. %d)" % (P, simlog.SELECT_P_MAX))
+        if not isinstance(selector, simlog.PlanSelector):
+            raise ValueError("selector: a simlog.PlanSelector")
+        risk = selector.risk
+        sarr, rarr = selector.arrays(), risk.arrays()
+        omega_seq, st, S, cost_w, rows, karr, ktabs, kthr, pst = self._rollout_inputs(K, omega_seq, start, cost_w, kpis, price_start)
+        if S > simlog.RISK_S_MAX:
+            raise ValueError("risk: S = %d realisations (at most %d)" % (S, simlog.RISK_S_MAX))
+        min_complete = S if min_complete is None else int(min_complete)
+        if not 1 <= min_complete <= S:
+            raise ValueError("min_complete = %d (1 .. S = %d)" % (min_complete, S))
+        if np.any(rarr["col_src"] == 3):
+            raise ValueError("risk column %r reads switches, but a selection rolls out open loop" % (risk.names[int(np.flatnonzero(rarr["col_src"] == 3)[0])],))
+        Q, chan = 0, None
+        if kpis is None:
+            ktabs = [None] * 5
+            if np.any(rarr["col_src"] >= 4):
+                raise ValueError("risk column %r reads the KPIs, but kpis is None" % (risk.names[int(np.flatnonzero(rarr["col_src"] >= 4)[0])],))
+        else:
+            if np.any(rarr["col_src"] >= 4) and risk.kpis is not kpis and list(risk.kpis.names) != list(kpis.names):
+                raise ValueError("the risk table was built over another KPI table (%s, this call's %s)" % (risk.kpis.names, kpis.names))
+            Q, chan = len(kpis), karr["price_chan"]
+        aux = resolve.problem._h if resolve is not None and resolve.problem is not None else None
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None
+        lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64)) if a is not None else None
+        G, L = len(risk), len(risk.levels)
+        out = dict(choice=np.zeros(B, np.int32), score=np.zeros(B), n_admissible=np.zeros(B, np.int32), admissible=np.zeros((B, P), np.uint8),
+                   u=np.zeros((B, K, nu)), u0=np.zeros((B, nu)))
+        rk = dict(names=list(risk.names), levels=list(risk.levels))
+        if per_candidate:
+            rk.update(mean=np.zeros((B, P, G)), min=np.zeros((B, P, G)), min_c=np.zeros((B, P, G), np.int32), max=np.zeros((B, P, G)), max_c=np.zeros((B, P, G), np.int32),
+                      n_exceed=np.zeros((B, P, G), np.int32), quantile=np.zeros((B, P, G, L)), quantile_c=np.zeros((B, P, G, L), np.int32),
+                      cvar_hi=np.zeros((B, P, G, L)), cvar_lo=np.zeros((B, P, G, L)))
+        counts = np.zeros((B, P, 4), np.int32)
+        per, kp = {}, {}
+        if per_trajectory:
+            per = dict(cost=np.zeros((B, P, S)), mu_total=np.zeros((B, P, S)), worst_vio=np.zeros((B, P, S)), worst_step=np.zeros((B, P, S), np.int32),
+                       steps_done=np.zeros((B, P, S), np.int32), end_status=np.zeros((B, P, S), np.int32))
+            if kpis is not None:
+                kp = dict(names=list(kpis.names), sum=np.zeros((B, P, S, Q)), min=np.zeros((B, P, S, Q)), max=np.zeros((B, P, S, Q)), min_step=np.zeros((B, P, S, Q), np.int32),
+                          max_step=np.zeros((B, P, S, Q), np.int32), n_above=np.zeros((B, P, S, Q), np.int32), n_changes=np.zeros((B, P, S, Q), np.int32),
+                          n_vio=np.zeros((B, P, S), np.int32))
+        stats = np.zeros(4, np.int64)
+        oc, ok, ol = sarr["obj"]
+        nc = sarr["n_cons"]
+        check(_lib.load().mld_rollout_select(
+            self._h, aux, K, S, P, pf, _lib.dptr(cand), _lib.dptr(omega_seq) if nw else None, lp(st), int(step), _lib.dptr(cost_w), rows, Q,
+            *([_lib.dptr(t) for t in ktabs] + [ip(chan), _lib.dptr(kthr), float(vio_tol), lp(pst)]),
+            G, ip(rarr["col_src"]), ip(rarr["col_q"]), _lib.dptr(rarr["level"]), L, _lib.dptr(rarr["alpha"]),
+            int(oc), int(ok), int(ol), nc, ip(sarr["cons_col"]) if nc else None, ip(sarr["cons_kind"]) if nc else None, ip(sarr["cons_level"]) if nc else None,
+            _lib.dptr(sarr["cons_bound"]) if nc else None, min_complete,
+            ip(out["choice"]), _lib.dptr(out["score"]), ip(out["n_admissible"]), out["admissible"].ctypes.data_as(C.POINTER(C.c_uint8)), _lib.dptr(out["u"]), _lib.dptr(out["u0"]),
+            _lib.dptr(rk.get("mean")), _lib.dptr(rk.get("min")), _lib.dptr(rk.get("max")), ip(rk.get("min_c")), ip(rk.get("max_c")), ip(rk.get("n_exceed")),
+            _lib.dptr(rk.get("quantile")), ip(rk.get("quantile_c")), _lib.dptr(rk.get("cvar_hi")), _lib.dptr(rk.get("cvar_lo")), ip(counts),
+            _lib.dptr(per.get("cost")), _lib.dptr(per.get("mu_total")), _lib.dptr(per.get("worst_vio")), ip(per.get("worst_step")), ip(per.get("steps_done")),
+            ip(per.get("end_status")), lp(stats), _lib.dptr(kp.get("sum")), _lib.dptr(kp.get("min")), _lib.dptr(kp.get("max")),
+            ip(kp.get("min_step")), ip(kp.get("max_step")), ip(kp.get("n_above")), ip(kp.get("n_changes")), ip(kp.get("n_vio"))))
+        out["admissible"] = out["admissible"].astype(bool)
+        n_host = int(stats[3])
+        n_done = [int(stats[1]), int(stats[2])]
+        if n_host:      # finished on the host, by rollout() itself: one call per candidate, the route this entry point replaces
+            sel = np.flatnonzero((counts[:, :, 2] > 0).any(axis=1))
+            host = []
+            for p in range(P):
+                kw = dict(K=K) if (pf and p == 0) else dict(u_seq=cand[:, p - pf])
+                host.append(self.rollout(resolve, omega_seq=omega_seq, start=start, step=step, cost_w=cost_w, kpis=kpis, price_start=price_start, vio_tol=vio_tol,
+                                         risk=risk, **kw))
+            keys = simlog.RISK_COL_KEYS + simlog.RISK_LEVEL_KEYS
+            full = {k: np.stack([h["risk"][k][sel] for h in host], axis=1) for k in keys + simlog.RISK_COUNTS}
+            for i, key in enumerate(simlog.RISK_COUNTS):
+                counts[sel, :, i] = full[key]
+            if per_candidate:
+                for k in keys:
+                    rk[k][sel] = full[k]
+            for k in per:
+                per[k][sel] = np.stack([h[k][sel] for h in host], axis=1)
+            for k in kp:
+                if k != "names":
+                    kp[k][sel] = np.stack([h["kpi"][k][sel] for h in host], axis=1)
+            allc = cand
+            if pf:
+                plan_u = self.download()["v"].reshape(B, self.N_tilde, nv)[:, None, :K, :nu]
+                allc = plan_u if cand is None else np.concatenate([plan_u, cand], axis=1)
+            pick = simlog.select_plan_np(full, selector, min_complete, candidates=allc[sel])
+            for k in ("choice", "score", "n_admissible", "admissible", "u", "u0"):
+                out[k][sel] = pick[k]
+            es = np.stack([h["end_status"] for h in host], axis=1)
+            n_done = [int((es == 0).sum()), int((es == 1).sum())]
+        out["stats"] = dict(trajectories=int(stats[0]), complete=n_done[0], infeasible=n_done[1], declined=int(stats[3]),
+                            not_attempted=int(stats[0] - stats[1] - stats[2] - stats[3]), finished_on_host=n_host)
+        if per_candidate:
+            for i, key in enumerate(simlog.RISK_COUNTS):
+                rk[key] = np.ascontiguousarray(counts[:, :, i])
+            out["risk"] = rk
+        if per_trajectory:
+            out.update(per)
+            if kp:
+                out["kpi"] = kp
         return out
 
     def sim_log(self, first=0, count=None):

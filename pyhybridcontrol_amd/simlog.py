@@ -571,6 +571,113 @@ def rollout_risk_np(out, risk, policy=False):
     return res
 
 
+# ---- plan selection: the admissible candidate of least objective statistic (GpuProblem.select_plan, mld_rollout_select, kernel k_plan_select) -------------
+SELECT_P_MAX, SELECT_CONS_MAX = 64, 8      # MLD_SELECT_P_MAX, MLD_SELECT_CONS_MAX
+SELECT_KINDS = ("mean", "min", "max", "n_exceed", "quantile", "cvar_hi", "cvar_lo")      # kind = the index; the last three are per level
+SELECT_KEYS = ("choice", "score", "n_admissible", "admissible")
+
+
+class PlanSelector(object):
+    """The rule one selection applies to the risk of every candidate: PlanSelector(risk).minimise(column, kind, level=None).subject_to(column, kind, bound,
+    level=None)...  risk: the simlog.RiskTable of the call; column: the name of one of its columns (or its index); kind: one of SELECT_KINDS; level: for
+    quantile, cvar_hi and cvar_lo the alpha of one of the table's levels (a float) or its index (an int), None for the other kinds.  A candidate is
+    admissible iff it has at least min_complete complete realisations, every constraint's value <= bound holds (a NaN fails) and its objective is not NaN;
+    the choice is the admissible candidate of least objective, the smaller p on a tie (include/mldgpu.h: THE RULE)."""
+
+    def __init__(self, risk):
+        if not isinstance(risk, RiskTable) or len(risk) < 1:
+            raise ValueError("PlanSelector(risk): a simlog.RiskTable with at least one column")
+        self.risk = risk
+        self.objective = None
+        self.constraints = []      # (col, kind, lvl, bound)
+
+    def _stat(self, column, kind, level):
+        if isinstance(column, (int, np.integer)) and not isinstance(column, bool):
+            col = int(column)
+            if not 0 <= col < len(self.risk):
+                raise ValueError("column %d, but the risk table has %d columns" % (col, len(self.risk)))
+        elif column in self.risk.names:
+            col = self.risk.names.index(column)
+        else:
+            raise ValueError("column %r is not a column of the risk table (%s)" % (column, ", ".join(map(str, self.risk.names))))
+        if kind not in SELECT_KINDS:
+            raise ValueError("kind %r, expected one of %s" % (kind, ", ".join(SELECT_KINDS)))
+        k = SELECT_KINDS.index(kind)
+        if k < 4:
+            if level is not None:
+                raise ValueError("level given, but kind %r is not per level" % (kind,))
+            return col, k, 0
+        L = len(self.risk.levels)
+        if level is None:
+            raise ValueError("kind %r is per level: level= one of the risk table's levels %s" % (kind, self.risk.levels))
+        if isinstance(level, (int, np.integer)) and not isinstance(level, bool):
+            lvl = int(level)
+            if not 0 <= lvl < L:
+                raise ValueError("level index %d, but the risk table has %d levels" % (lvl, L))
+        elif float(level) in self.risk.levels:
+            lvl = self.risk.levels.index(float(level))
+        else:
+            raise ValueError("level %r is not a level of the risk table (%s)" % (level, self.risk.levels))
+        return col, k, lvl
+
+    def minimise(self, column, kind, level=None):
+        """the objective statistic (once)"""
+        if self.objective is not None:
+            raise ValueError("the objective has been set already")
+        self.objective = self._stat(column, kind, level)
+        return self
+
+    def subject_to(self, column, kind, bound, level=None):
+        """one constraint value <= bound, at most SELECT_CONS_MAX; a NaN bound is a ValueError"""
+        if len(self.constraints) >= SELECT_CONS_MAX:
+            raise ValueError("a selector holds at most %d constraints" % SELECT_CONS_MAX)
+        bound = float(bound)
+        if np.isnan(bound):
+            raise ValueError("the bound is NaN")
+        self.constraints.append(self._stat(column, kind, level) + (bound,))
+        return self
+
+    def arrays(self):
+        """the arguments of mld_rollout_select: dict(obj (col, kind, level index), n_cons, cons_col, cons_kind, cons_level (n_cons,) int32, cons_bound)"""
+        if self.objective is None:
+            raise ValueError("the selector has no objective (minimise(...))")
+        c = self.constraints
+        return dict(obj=self.objective, n_cons=len(c), cons_col=np.asarray([a[0] for a in c], dtype=np.int32), cons_kind=np.asarray([a[1] for a in c], dtype=np.int32),
+                    cons_level=np.asarray([a[2] for a in c], dtype=np.int32), cons_bound=np.asarray([a[3] for a in c], dtype=np.float64))
+
+
+def _select_value(risk, col, kind, lvl):
+    """the statistic (col, kind, lvl) of every candidate: (B, P) float64"""
+    a = np.asarray(risk[SELECT_KINDS[kind]])
+    return np.asarray(a[:, :, col, lvl] if kind >= 4 else a[:, :, col], dtype=np.float64)
+
+
+def select_plan_np(risk_per_candidate, selector, min_complete, candidates=None):
+    """GpuProblem.select_plan's choice stated in numpy (mld_rollout_select, kernel k_plan_select; the rule: include/mldgpu.h): risk_per_candidate the
+    per-candidate risk -- mean, min, max, n_exceed (B, P, G), quantile, cvar_hi, cvar_lo (B, P, G, L), n_complete (B, P) --, selector a PlanSelector,
+    min_complete the least number of complete realisations.  Returns dict(choice (B,) int32, -1 = none; score (B,), NaN without a choice; n_admissible (B,)
+    int32; admissible (B, P) bool); with candidates (B, P, K, nu) also u (B, K, nu) and u0 (B, nu), the chosen sequence and its step 0, NaN without a choice."""
+    arr = selector.arrays()
+    val = _select_value(risk_per_candidate, *arr["obj"])
+    B, P = val.shape
+    with np.errstate(invalid="ignore"):
+        adm = (np.asarray(risk_per_candidate["n_complete"]).reshape(B, P) >= int(min_complete)) & ~np.isnan(val)
+        for k in range(arr["n_cons"]):
+            adm &= _select_value(risk_per_candidate, int(arr["cons_col"][k]), int(arr["cons_kind"][k]), int(arr["cons_level"][k])) <= arr["cons_bound"][k]
+    rows = np.arange(B)
+    first = np.where(adm, val, np.inf).argmin(axis=1)      # argmin: the first of equals, -0.0 == +0.0
+    first = np.where(adm[rows, first], first, adm.argmax(axis=1))      # (every admissible value is +inf: an inadmissible +inf came first -- the first admissible)
+    choice = np.where(adm.any(axis=1), first, -1).astype(np.int32)
+    some = choice >= 0
+    score = np.where(some, val[rows, np.maximum(choice, 0)], np.nan)
+    out = dict(choice=choice, score=score, n_admissible=adm.sum(axis=1).astype(np.int32), admissible=adm)
+    if candidates is not None:
+        cand = np.asarray(candidates, dtype=np.float64)
+        u = np.where(some[:, None, None], cand[rows, np.maximum(choice, 0)], np.nan)
+        out.update(u=u, u0=np.ascontiguousarray(u[:, 0, :]))
+    return out
+
+
 def start_from_rollout_np(v, end_status, bins, old=None):
     """GpuProblem.warm_start_from_rollout's byte rule stated in numpy (kernel k_warm_from_rollout): v (B, N_tilde, nv) or (B, 1, N_tilde, nv) of a rollout with
     S = 1, end_status (B,) or (B, 1), bins (n_bin,) the binaries' indices step * nv + pos (np.flatnonzero(GpuProblem.is_bin)), old (B, n_bin) the resident
