@@ -959,6 +959,45 @@ int mld_rollout_select(mld_problem_t *p, mld_problem_t *aux, int K, int S, int P
                        int64_t stats[4],
                        double *sum, double *min, double *max, int32_t *min_step, int32_t *max_step, int32_t *n_above, int32_t *n_changes, int32_t *n_vio);
 
+/* ---- plan selection with closed-loop rule policies among the candidates --------------------------------------------------------------------------------------
+ * The reference quotes every MPC variant against its thermostat, DewhTheromstatController, a FEEDBACK rule u_k = f(x_k, u_{k-1}) stepped in closed loop, and
+ * the safety filter's fall-back is that same rule.  A nominal input sequence is not that baseline: under realisation c the rule reacts to the tank that
+ * realisation produced.  mld_rollout_select_policy takes mld_rollout_select's arguments and, behind them, T policies in mld_upload_policy's arrays with a
+ * leading table axis: pol_sel (T, n_models, nu, nx), pol_on_at, pol_off_at, pol_u_on, pol_u_off, pol_mode (T, n_models, nu).  The candidates of one call, in
+ * this order: the resident plan (plan_first: 0 or 1), n_own = P - plan_first - T open-loop sequences u_cand (batch, n_own, K, nu), T policies; P counts all
+ * of them, 1 .. MLD_SELECT_P_MAX; trajectory t = (b P + p) S + c, all candidates under the same S realisations.  Kernels k_rollout_cand_policy /
+ * k_rollout_cand_policy_kpi: ro_run<true> -- the body of k_rollout_policy -- with a TABLE per candidate: table p - (P - T) for a policy candidate, and for
+ * the plan and the sequences one whose every channel is passed through, with which the body copies u_k and counts no switch.  u_prev (batch, nu) is the input
+ * before step 0, NULL = the resident policy state as mld_rollout_policy reads it.  switches_out (batch, P, S): the (step, channel) pairs whose input changed,
+ * 0 for a complete plan or sequence trajectory, -1 where the trajectory did not end 0; a risk column of source `switches` is accepted in this entry.
+ * The choice is k_plan_select's.  The chosen inputs are k_select_inputs' (queued behind it): a plan or sequence pick is copied as before; a policy pick has
+ * u0_choice[b, j] = the rule on (x0[b], u_prev[b, j]) -- step 0 of the closed loop, the same bits, what mld_sim_step_resolve takes as u0 --, that row as
+ * u_choice[b, 0, :] and NaN in rows 1 .. K - 1, which differ from realisation to realisation; no choice: all NaN.  A policy candidate equals
+ * mld_upload_policy followed by mld_rollout_risk(policy = 1) bit for bit, a sequence candidate mld_rollout_risk(u_seq) with switches 0.
+ * T == 0 is mld_rollout_select's call: the same kernels, the same bits.  The tables, candidates and choice live in temporaries of the call; the handle is read
+ * and never changed -- the resident policy and its state, plan, MIP start, log and starts stay.  Nothing is finished on the host on this entry (as
+ * mld_warm_start_from_rollout): a trajectory the LDS solver declines ends 2, is counted in counts[.., 2] and stats[3], and with min_complete == S makes its
+ * candidate inadmissible.
+ * MLD_ERR_INVALID before anything is queued, the argument named: everything mld_rollout_select refuses; T < 0 or T > P - plan_first; any table entry
+ * mld_upload_policy would refuse (the message names table, model and channel); a policy candidate with a passed-through channel (pol_mode == 0) -- a candidate
+ * that rules some channels and takes the plan for the others is not built --; a pol_* array NULL with T > 0; u_prev NULL with no resident policy; a
+ * non-finite u_prev. */
+int mld_rollout_select_policy(mld_problem_t *p, mld_problem_t *aux, int K, int S, int P, int plan_first, const double *u_cand, const double *omega_seq,
+                              const int64_t *start, int step, const double *cost_w, int cost_rows, int n_kpi,
+                              const double *w_x, const double *w_v, const double *w_y, const double *w_omega, const double *w_xk1,
+                              const int32_t *price_chan, const double *thresh, double vio_tol, const int64_t *price_start,
+                              int G, const int32_t *col_src, const int32_t *col_q, const double *level, int L, const double *alpha,
+                              int obj_col, int obj_kind, int obj_level, int n_cons, const int32_t *cons_col, const int32_t *cons_kind, const int32_t *cons_level,
+                              const double *cons_bound, int min_complete,
+                              int32_t *choice, double *score, int32_t *n_admissible, uint8_t *admissible, double *u_choice, double *u0_choice,
+                              double *r_mean, double *r_min, double *r_max, int32_t *r_min_c, int32_t *r_max_c, int32_t *r_n_exceed,
+                              double *r_quantile, int32_t *r_quantile_c, double *r_cvar_hi, double *r_cvar_lo, int32_t *counts,
+                              double *cost_out, double *mu_total_out, double *worst_vio_out, int32_t *worst_step_out, int32_t *steps_done_out, int32_t *end_status_out,
+                              int64_t stats[4],
+                              double *sum, double *min, double *max, int32_t *min_step, int32_t *max_step, int32_t *n_above, int32_t *n_changes, int32_t *n_vio,
+                              int T, const double *pol_sel, const double *pol_on_at, const double *pol_off_at, const double *pol_u_on, const double *pol_u_off,
+                              const int32_t *pol_mode, const double *u_prev, int32_t *switches_out);
+
 /* Per-instance telemetry of the last solve: time spent inside the solve kernel (device wall clock, ns) and
  * the number of dictionary rows the rank-1 updates touched (x *row_bytes x 2 = bytes streamed by pivots). */
 int mld_download_telemetry(mld_problem_t *, int64_t *latency_ns, int64_t *rows_updated, int64_t *row_bytes);

@@ -67,7 +67,7 @@ EXPORTS = ("mld_device_count", "mld_set_device", "mld_last_error", "mld_version"
            "mld_upload_policy", "mld_set_policy_state", "mld_download_policy_state", "mld_rollout_policy", "mld_sim_step_policy",
            "mld_plan_memory", "mld_set_plan_memory", "mld_download_plan_memory", "mld_sim_step_fallback", "mld_download_sim_log_source",
            "mld_upload_prices", "mld_set_price_cost", "mld_instance_cost_from_prices", "mld_set_stage_cost", "mld_sim_log_cost_begin", "mld_download_sim_log_cost",
-           "mld_download_cost_total", "mld_sim_log_summary", "mld_rollout_kpi", "mld_rollout_risk", "mld_rollout_select",
+           "mld_download_cost_total", "mld_sim_log_summary", "mld_rollout_kpi", "mld_rollout_risk", "mld_rollout_select", "mld_rollout_select_policy",
            "mld_warm_start_from_rollout",
            "mld_comm_unique_id", "mld_comm_init", "mld_gather", "mld_comm_destroy")
 
@@ -129,6 +129,7 @@ def load():
                                        C.c_int, ip, ip, dp, C.c_int, dp, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip, dp, C.c_int,
                                        ip, dp, ip, bp, dp, dp, dp, dp, dp, ip, ip, ip, dp, ip, dp, dp, ip,
                                        dp, dp, dp, ip, ip, ip, lp, dp, dp, dp, ip, ip, ip, ip, ip]
+    lib.mld_rollout_select_policy.argtypes = list(lib.mld_rollout_select.argtypes) + [C.c_int, dp, dp, dp, dp, dp, ip, dp, ip]
     lib.mld_warm_start_from_rollout.argtypes = [C.c_void_p, C.c_void_p, C.c_int, dp, dp, C.c_int, ip, lp]
     if int(lib.mld_opts_size()) != C.sizeof(Opts):
         raise MldGpuError("libmldgpu.so was built with another layout of mld_opts (%d bytes, this binding %d): rebuild it (python -m pyhybridcontrol_amd.build)"

@@ -18,25 +18,7 @@ int mld_upload_policy(mld_problem_t *p, const double *sel, const double *on_at, 
     if (!on_at || !off_at || !u_on || !u_off || !mode) { mld_set_error("%s: sel given, but on_at, off_at, u_on, u_off or mode is NULL", who); return MLD_ERR_INVALID; }
     std::vector<double> tab((size_t)M * nu * row);
     bool all = true;
-    for (int m = 0; m < M; ++m)
-        for (int j = 0; j < nu; ++j) {
-            const size_t c = (size_t)m * nu + j;
-            double *t = tab.data() + c * row;
-            for (int i = 0; i < nx; ++i) {
-                t[i] = sel[c * nx + i];
-                if (!std::isfinite(t[i])) { mld_set_error("%s: sel of model %d, channel %d, state %d is not finite (%g)", who, m, j, i, t[i]); return MLD_ERR_INVALID; }
-            }
-            const double vals[4] = {on_at[c], off_at[c], u_on[c], u_off[c]};
-            static const char *const names[4] = {"on_at", "off_at", "u_on", "u_off"};
-            for (int k = 0; k < 4; ++k) {
-                if (!std::isfinite(vals[k])) { mld_set_error("%s: %s of model %d, channel %d is not finite (%g)", who, names[k], m, j, vals[k]); return MLD_ERR_INVALID; }
-                t[nx + k] = vals[k];
-            }
-            if (on_at[c] > off_at[c]) { mld_set_error("%s: on_at > off_at for model %d, channel %d (%g > %g): the band between the thresholds would be empty", who, m, j, on_at[c], off_at[c]); return MLD_ERR_INVALID; }
-            if (mode[c] != 0 && mode[c] != 1) { mld_set_error("%s: mode of model %d, channel %d is %d (0 = passed through, 1 = ruled)", who, m, j, (int)mode[c]); return MLD_ERR_INVALID; }
-            t[nx + POL_MODE] = (double)mode[c];
-            all = all && mode[c] == 1;
-        }
+    if (int rc = policy_table_fill(who, -1, M, nx, nu, sel, on_at, off_at, u_on, u_off, mode, tab.data(), &all)) return rc;
     DevBuf<double> d;
     HIP_TRY(d.alloc(tab.size()));
     HIP_TRY(hipMemcpy(d, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));

@@ -16,7 +16,11 @@
  * k_rollout_cand / k_rollout_cand_kpi over batch P S trajectories, t = (b P + p) S + c, while the disturbance buffer stays (batch S, K nw), filled once as
  * for any other call; k_rollout_risk launched unchanged over batch P "instances"; k_plan_select (plan_select.inc: THE RULE) queued behind it.  The risk
  * arrays the rule reads get their device temporaries whether or not the caller asked for them; the candidates, the choice and the chosen inputs live in
- * temporaries of the call. */
+ * temporaries of the call.
+ * sl with sl->T > 0 (mld_rollout_select_policy): the last T candidates are rule policies in closed loop -- the kernels k_rollout_cand_policy /
+ * k_rollout_cand_policy_kpi, ro_run<true> with a table per candidate (the caller's T tables and one whose every channel is passed through, for the plan and
+ * the sequences), u_prev the caller's or the resident policy state; the switches source is allowed; k_plan_select writes no inputs and k_select_inputs,
+ * queued behind it, writes the chosen ones.  The tables are tested by policy_table_fill, mld_upload_policy's own test, and live in a temporary. */
 static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p, mld_problem_t *aux, int K, int S, const double *u_seq, const double *omega_seq,
                         const int64_t *start, int step, const double *cost_w, int cost_rows, const RolloutOut &out, const StartCall *sc = nullptr,
                         const KpiCall *kc = nullptr, const RiskCall *rk = nullptr, const SelectCall *sl = nullptr)
@@ -37,6 +41,27 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
         if (pc || sc || !rk || u_seq) { mld_set_error("%s: internal: a selection is an open-loop risk call over u_cand", who); return MLD_ERR_INVALID; }
         if (sl->P < 1 || sl->P > MLD_SELECT_P_MAX) { mld_set_error("%s: P = %d candidates (1 .. MLD_SELECT_P_MAX = %d: a lane of the wave per candidate)", who, sl->P, MLD_SELECT_P_MAX); return MLD_ERR_INVALID; }
         if ((long long)batch * S * sl->P > INT_MAX) { mld_set_error("%s: batch x P x S = %lld trajectories (at most %d)", who, (long long)batch * S * sl->P, INT_MAX); return MLD_ERR_INVALID; }
+        if (sl->T < 0) { mld_set_error("%s: T = %d policy candidates (at least 0)", who, sl->T); return MLD_ERR_INVALID; }
+        if (sl->T > sl->P - (sl->plan_first ? 1 : 0)) {
+            mld_set_error("%s: T = %d policy candidates, but P = %d candidates in all%s (P counts the policies)", who, sl->T, sl->P, sl->plan_first ? ", the resident plan among them" : "");
+            return MLD_ERR_INVALID;
+        }
+    }
+    const int n_pol = sl ? sl->T : 0;      /* the closed-loop candidates of a selection: the last n_pol of its P */
+    if (n_pol) {
+        if (!(sl->pol_sel && sl->pol_on_at && sl->pol_off_at && sl->pol_u_on && sl->pol_u_off && sl->pol_mode)) {
+            mld_set_error("%s: pol_sel, pol_on_at, pol_off_at, pol_u_on, pol_u_off or pol_mode is NULL with T = %d", who, n_pol); return MLD_ERR_INVALID;
+        }
+        if (nu < 1) { mld_set_error("%s: the model has no input (nu = 0): there is nothing a policy could rule", who); return MLD_ERR_INVALID; }
+        if (!sl->u_prev && !p->pol_on) { mld_set_error("%s: u_prev is NULL, but no policy is resident (mld_upload_policy): there is no resident policy state to read", who); return MLD_ERR_INVALID; }
+    }
+    /* the tables of the policy candidates in the kernels' rows, and behind them one whose every channel is passed through (all zero: mode 0) */
+    const size_t ptab_len = (size_t)nu * (nx + POL_TAIL), ptab_all = n_pol ? (size_t)(n_pol + 1) * p->n_models * ptab_len : 0;
+    std::vector<double> hptab(ptab_all, 0.0);
+    for (int t = 0; t < n_pol; ++t) {
+        const size_t c = (size_t)t * p->n_models * nu;
+        if (int rc = policy_table_fill(who, t, p->n_models, nx, nu, sl->pol_sel + c * nx, sl->pol_on_at + c, sl->pol_off_at + c, sl->pol_u_on + c, sl->pol_u_off + c,
+                                       sl->pol_mode + c, hptab.data() + (size_t)t * p->n_models * ptab_len, nullptr)) return rc;
     }
     if (step < 0 || step > INT_MAX - K) { mld_set_error("%s: step = %d (must be >= 0)", who, step); return MLD_ERR_INVALID; }
     if (int rc = aux_fold_check(who, "rolled-out", p, aux)) return rc;
@@ -91,7 +116,7 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
         for (int j = 0; j < rk->G; ++j) {
             const int s = rk->col_src[j], q = rk->col_q ? rk->col_q[j] : 0;
             if (s < 0 || s >= RISK_N_SRC) { mld_set_error("%s: col_src[%d] = %d (a source 0 .. %d)", who, j, s, RISK_N_SRC - 1); return MLD_ERR_INVALID; }
-            if (s == RISK_SWITCHES && !pc) { mld_set_error("%s: col_src[%d] = %d (switches), but the rollout has no policy (policy == 0)", who, j, s); return MLD_ERR_INVALID; }
+            if (s == RISK_SWITCHES && !pc && !n_pol) { mld_set_error("%s: col_src[%d] = %d (switches), but the rollout has no policy (policy == 0)", who, j, s); return MLD_ERR_INVALID; }
             if (s >= RISK_N_VIO && n_kpi == 0) { mld_set_error("%s: col_src[%d] = %d reads the KPIs, but n_kpi = 0 (no KPI table in this call)", who, j, s); return MLD_ERR_INVALID; }
             if (s >= RISK_KPI_SUM && (q < 0 || q >= n_kpi)) { mld_set_error("%s: col_q[%d] = %d (a KPI 0 .. n_kpi - 1 = %d)", who, j, q, n_kpi - 1); return MLD_ERR_INVALID; }
             if (rk->level && std::isnan(rk->level[j])) { mld_set_error("%s: level[%d] is NaN", who, j); return MLD_ERR_INVALID; }
@@ -103,7 +128,7 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
         }
     }
     /* the selection rule */
-    const int n_own = sl ? sl->P - (sl->plan_first ? 1 : 0) : 0;      /* candidates of u_cand */
+    const int n_own = sl ? sl->P - (sl->plan_first ? 1 : 0) - n_pol : 0;      /* candidates of u_cand */
     unsigned s_kinds = 0;                                            /* bit k: some statistic of the rule has kind k */
     if (sl) {
         auto stat_ok = [&](const char *col_name, const char *kind_name, const char *lvl_name, int k, int col, int kind, int lvl) -> bool {
@@ -158,8 +183,9 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
     if (omega_seq && nw) for (size_t k = 0; k < TW * K * nw; ++k) if (!std::isfinite(omega_seq[k])) {
         mld_set_error("%s: omega_seq of trajectory %zu, step %zu, channel %zu is not finite (%g)", who, k / ((size_t)K * nw), k / nw % K, k % nw, omega_seq[k]); return MLD_ERR_INVALID;
     }
-    if (pc && pc->u_prev) for (size_t k = 0; k < (size_t)batch * nu; ++k) if (!std::isfinite(pc->u_prev[k])) {
-        mld_set_error("%s: u_prev of instance %zu, input %zu is not finite (%g)", who, k / nu, k % nu, pc->u_prev[k]); return MLD_ERR_INVALID;
+    const double *const u_prev_in = pc ? pc->u_prev : (n_pol ? sl->u_prev : nullptr);      /* the caller's inputs before step 0; nullptr: the resident policy state, or no policy */
+    if (u_prev_in) for (size_t k = 0; k < (size_t)batch * nu; ++k) if (!std::isfinite(u_prev_in[k])) {
+        mld_set_error("%s: u_prev of instance %zu, input %zu is not finite (%g)", who, k / nu, k % nu, u_prev_in[k]); return MLD_ERR_INVALID;
     }
     const bool cw_inst = cost_w && cost_rows != p->n_models;      /* (batch == n_models: a row per model) */
     if (cost_w) for (size_t k = 0; k < (size_t)cost_rows * K * nv; ++k) if (!std::isfinite(cost_w[k])) {
@@ -186,8 +212,10 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
     std::vector<int> hrq, hidx;
     DevBuf<double> d_ucand, d_sscore, d_such, d_su0; DevBuf<int> d_schoice, d_snadm; DevBuf<unsigned char> d_sadm;      /* sl */
     DevBuf<unsigned char> d_old; DevBuf<int> d_src;      /* sc: the resident start as it was (where rows are kept), the source per instance */
-    if (pc && !pc->u_prev) { if (int rc = policy_state_ready(p, who)) return rc; }      /* (an upload's reset state, laid out on first use: nothing a caller can see changes) */
-    if (pc && pc->u_prev) HIP_TRY(d_uprev.alloc(std::max<size_t>(1, (size_t)batch * nu)));
+    DevBuf<double> d_ptab;      /* sl with policies: the tables */
+    if ((pc || n_pol) && !u_prev_in) { if (int rc = policy_state_ready(p, who)) return rc; }      /* (an upload's reset state, laid out on first use: nothing a caller can see changes) */
+    if (u_prev_in) HIP_TRY(d_uprev.alloc(std::max<size_t>(1, (size_t)batch * nu)));
+    if (n_pol) HIP_TRY(d_ptab.alloc(ptab_all));
     if (u_seq) HIP_TRY(d_u.alloc(std::max<size_t>(1, (size_t)batch * Kz * nu)));
     if (!sc) HIP_TRY(d_om.alloc(std::max<size_t>(1, TW * Kz * nw)));
     if (start) HIP_TRY(d_start.alloc(TW * p->pf_groups));
@@ -199,6 +227,7 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
     HIP_TRY(take(d_cost, cost_out, T)); HIP_TRY(take(d_mu, mu_total_out, T)); HIP_TRY(take(d_wv, worst_vio_out, T));
     HIP_TRY(take(d_ws, worst_step_out, T)); HIP_TRY(take(d_sd, steps_done_out, T)); HIP_TRY(take(d_es, end_status_out, T));
     if (pc) HIP_TRY(take(d_sw, pc->switches_out, T));
+    if (n_pol) HIP_TRY(take(d_sw, sl->switches_out, T));
     const size_t r_inst = (size_t)batch * (size_t)(sl ? sl->P : 1);      /* what k_rollout_risk takes for its instances: i = b P + p */
     const size_t rg = rk ? r_inst * rk->G : 0, rgl = rk ? rg * rk->L : 0;
     if (rk) {      /* the temporaries of the sources the columns read, asked for or not; the rank table; the results' buffers */
@@ -224,6 +253,7 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
         HIP_TRY(d_ucand.alloc(std::max<size_t>(1, s_own)));
         HIP_TRY(take(d_schoice, sl->choice, (size_t)batch)); HIP_TRY(take(d_sscore, sl->score, (size_t)batch)); HIP_TRY(take(d_snadm, sl->n_admissible, (size_t)batch));
         HIP_TRY(take(d_sadm, sl->admissible, r_inst)); HIP_TRY(take(d_such, sl->u_choice, s_seq)); HIP_TRY(take(d_su0, sl->u0_choice, (size_t)batch * nu));
+        HIP_TRY(force(d_schoice, n_pol && (d_such || d_su0), (size_t)batch));      /* k_select_inputs reads the choice */
     }
     const size_t warm_len = sc ? (size_t)batch * p->nb : 0;
     const bool keep_rows = sc && sc->keep && p->has_warm;
@@ -282,7 +312,12 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
     }
     RoCandDev cd{};
     if (sl) { cd.P = sl->P; cd.plan_first = sl->plan_first ? 1 : 0; cd.u_cand = d_ucand; }
-    const void *kernel = sl ? (kc ? (const void *)k_rollout_cand_kpi : (const void *)k_rollout_cand) : kc ? (pc ? (const void *)k_rollout_policy_kpi : (const void *)k_rollout_kpi) : (pc ? (const void *)k_rollout_policy : (const void *)k_rollout);
+    RoCandPolDev cq{};
+    if (n_pol) {      /* of pd the candidate-policy kernels read u_prev and switches; the tables are cq's */
+        pd.u_prev = u_prev_in ? d_uprev.get() : p->pol_uprev.get(); pd.switches = d_sw;
+        cq.tab = d_ptab; cq.tab_len = ptab_len; cq.n_models = p->n_models; cq.n_seq = sl->P - n_pol;
+    }
+    const void *kernel = n_pol ? (kc ? (const void *)k_rollout_cand_policy_kpi : (const void *)k_rollout_cand_policy) : sl ? (kc ? (const void *)k_rollout_cand_kpi : (const void *)k_rollout_cand) : kc ? (pc ? (const void *)k_rollout_policy_kpi : (const void *)k_rollout_kpi) : (pc ? (const void *)k_rollout_policy : (const void *)k_rollout);
     if (lds_bytes > 48 * 1024)
         HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     int dev = 0, per_cu = 0; hipDeviceProp_t prop;
@@ -310,6 +345,7 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
         risk_grid = (int)std::min<long long>(((long long)r_inst + RISK_WAVES - 1) / RISK_WAVES, (long long)rper * prop.multiProcessorCount);
     }
     SelArgs sa{};
+    SelInputsArgs si{};
     int sel_grid = 1;
     if (sl) {
         sa.batch = batch; sa.P = sl->P; sa.G = rk->G; sa.L = rk->L; sa.K = K; sa.nu = nu; sa.plan_first = sl->plan_first ? 1 : 0;
@@ -322,6 +358,13 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
         sa.mean = d_rmean; sa.min = d_rmin; sa.max = d_rmax; sa.n_exceed = d_rex; sa.quantile = d_rq; sa.cvar_hi = d_rhi; sa.cvar_lo = d_rlo; sa.counts = d_rcnt;
         sa.plan = p->bat.v; sa.plan_stride = (size_t)p->n; sa.plan_step = (size_t)nv; sa.u_cand = d_ucand;
         sa.choice = d_schoice; sa.score = d_sscore; sa.n_adm = d_snadm; sa.adm = d_sadm; sa.u_choice = d_such; sa.u0_choice = d_su0;
+        if (n_pol) {      /* k_plan_select would index u_cand out of range for a policy pick: the chosen inputs are k_select_inputs', behind it */
+            sa.u_choice = sa.u0_choice = nullptr;
+            si.batch = batch; si.P = sl->P; si.K = K; si.nu = nu; si.nx = nx; si.plan_first = sa.plan_first; si.n_seq = sl->P - n_pol; si.n_models = p->n_models;
+            si.choice = d_schoice; si.plan = sa.plan; si.plan_stride = sa.plan_stride; si.plan_step = sa.plan_step; si.u_cand = d_ucand;
+            si.tab = d_ptab; si.tab_len = ptab_len; si.model_idx = a.model_idx; si.x0 = p->bat.x0; si.u_prev = pd.u_prev;
+            si.u_choice = d_such; si.u0_choice = d_su0;
+        }
         int sper = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&sper, (const void *)k_plan_select, 64 * SEL_WAVES, 0) != hipSuccess || sper < 1) sper = 1;
         sel_grid = (int)std::min<long long>(((long long)batch + SEL_WAVES - 1) / SEL_WAVES, (long long)sper * prop.multiProcessorCount);
@@ -331,7 +374,8 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
     auto queue = [&]() -> int {
         HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(cnt), sq));
         if (u_seq && nu) HIP_TRY(hipMemcpyAsync(d_u, u_seq, sizeof(double) * (size_t)batch * Kz * nu, hipMemcpyHostToDevice, sq));
-        if (pc && pc->u_prev && nu) HIP_TRY(hipMemcpyAsync(d_uprev, pc->u_prev, sizeof(double) * (size_t)batch * nu, hipMemcpyHostToDevice, sq));
+        if (u_prev_in && nu) HIP_TRY(hipMemcpyAsync(d_uprev, u_prev_in, sizeof(double) * (size_t)batch * nu, hipMemcpyHostToDevice, sq));
+        if (n_pol) HIP_TRY(hipMemcpyAsync(d_ptab, hptab.data(), sizeof(double) * ptab_all, hipMemcpyHostToDevice, sq));
         if (cost_w && nv) HIP_TRY(hipMemcpyAsync(d_cw, cost_w, sizeof(double) * (size_t)cost_rows * Kz * nv, hipMemcpyHostToDevice, sq));
         if (sl && s_own) HIP_TRY(hipMemcpyAsync(d_ucand, sl->u_cand, sizeof(double) * s_own, hipMemcpyHostToDevice, sq));
         if (omega_seq && nw) HIP_TRY(hipMemcpyAsync(d_om, omega_seq, sizeof(double) * TW * Kz * nw, hipMemcpyHostToDevice, sq));
@@ -353,7 +397,9 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
             HIP_TRY(hipMemcpyAsync(d_ridx, hidx.data(), sizeof(int) * hidx.size(), hipMemcpyHostToDevice, sq));
             if (rk->level) HIP_TRY(hipMemcpyAsync(d_rlev, rk->level, sizeof(double) * (size_t)rk->G, hipMemcpyHostToDevice, sq));
         }
-        if (sl && kc) hipLaunchKernelGGL(k_rollout_cand_kpi, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a, cd, kd);
+        if (n_pol && kc) hipLaunchKernelGGL(k_rollout_cand_policy_kpi, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a, cd, pd, cq, kd);
+        else if (n_pol) hipLaunchKernelGGL(k_rollout_cand_policy, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a, cd, pd, cq);
+        else if (sl && kc) hipLaunchKernelGGL(k_rollout_cand_kpi, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a, cd, kd);
         else if (sl) hipLaunchKernelGGL(k_rollout_cand, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a, cd);
         else if (kc && pc) hipLaunchKernelGGL(k_rollout_policy_kpi, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a, pd, kd);
         else if (kc) hipLaunchKernelGGL(k_rollout_kpi, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a, kd);
@@ -373,6 +419,10 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
         if (sl) {      /* behind k_rollout_risk on the same stream: the candidates' risk is this kernel's input */
             hipLaunchKernelGGL(k_plan_select, dim3(sel_grid), dim3(64 * SEL_WAVES), 0, sq, sa);
             HIP_TRY(hipGetLastError());
+            if (n_pol && (si.u_choice || si.u0_choice)) {
+                hipLaunchKernelGGL(k_select_inputs, dim3(sel_grid), dim3(64 * SEL_WAVES), 0, sq, si);
+                HIP_TRY(hipGetLastError());
+            }
             HIP_TRY(get(sl->choice, d_schoice, (size_t)batch)); HIP_TRY(get(sl->score, d_sscore, (size_t)batch)); HIP_TRY(get(sl->n_admissible, d_snadm, (size_t)batch));
             HIP_TRY(get(sl->admissible, d_sadm, r_inst)); HIP_TRY(get(sl->u_choice, d_such, s_seq)); HIP_TRY(get(sl->u0_choice, d_su0, (size_t)batch * nu));
         }
@@ -380,6 +430,7 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
         HIP_TRY(get(cost_out, d_cost, T)); HIP_TRY(get(mu_total_out, d_mu, T)); HIP_TRY(get(worst_vio_out, d_wv, T));
         HIP_TRY(get(worst_step_out, d_ws, T)); HIP_TRY(get(steps_done_out, d_sd, T)); HIP_TRY(get(end_status_out, d_es, T));
         if (pc) HIP_TRY(get(pc->switches_out, d_sw, T));
+        if (n_pol) HIP_TRY(get(sl->switches_out, d_sw, T));
         if (kc) {
             HIP_TRY(get(kc->sum, d_ksum, tq)); HIP_TRY(get(kc->min, d_kmin, tq)); HIP_TRY(get(kc->max, d_kmax, tq)); HIP_TRY(get(kc->min_step, d_kmins, tq));
             HIP_TRY(get(kc->max_step, d_kmaxs, tq)); HIP_TRY(get(kc->n_above, d_kabove, tq)); HIP_TRY(get(kc->n_changes, d_kchg, tq)); HIP_TRY(get(kc->n_vio, d_knvio, T));
@@ -490,6 +541,36 @@ int mld_rollout_select(mld_problem_t *p, mld_problem_t *aux, int K, int S, int P
     const RiskCall rk{G, col_src, col_q, level, L, alpha, r_mean, r_min, r_max, r_min_c, r_max_c, r_n_exceed, r_quantile, r_quantile_c, r_cvar_hi, r_cvar_lo, counts};
     const SelectCall sl{P, plan_first, u_cand, obj_col, obj_kind, obj_level, n_cons, cons_col, cons_kind, cons_level, cons_bound, min_complete,
                         choice, score, n_admissible, admissible, u_choice, u0_choice};
+    return rollout_impl(who, nullptr, p, aux, K, S, nullptr, omega_seq, start, step, cost_w, cost_rows, out, nullptr, n_kpi ? &kc : nullptr, &rk, &sl);
+}
+
+/* mld_rollout_select with closed-loop rule policies among the candidates: the last T of the P candidates are ThresholdPolicy tables stepped in closed loop
+ * (k_rollout_cand_policy / k_rollout_cand_policy_kpi: ro_run<true> with a table per candidate), the chosen inputs by k_select_inputs behind k_plan_select.
+ * rollout_impl with the SelectCall extended, so every refusal of the others is made by the same code; T == 0 is mld_rollout_select's call.  The handle is
+ * read and never changed, and nothing is finished on the host: a trajectory the LDS solver declines ends 2 and is counted. */
+int mld_rollout_select_policy(mld_problem_t *p, mld_problem_t *aux, int K, int S, int P, int plan_first, const double *u_cand, const double *omega_seq,
+                              const int64_t *start, int step, const double *cost_w, int cost_rows, int n_kpi,
+                              const double *w_x, const double *w_v, const double *w_y, const double *w_omega, const double *w_xk1,
+                              const int32_t *price_chan, const double *thresh, double vio_tol, const int64_t *price_start,
+                              int G, const int32_t *col_src, const int32_t *col_q, const double *level, int L, const double *alpha,
+                              int obj_col, int obj_kind, int obj_level, int n_cons, const int32_t *cons_col, const int32_t *cons_kind, const int32_t *cons_level,
+                              const double *cons_bound, int min_complete,
+                              int32_t *choice, double *score, int32_t *n_admissible, uint8_t *admissible, double *u_choice, double *u0_choice,
+                              double *r_mean, double *r_min, double *r_max, int32_t *r_min_c, int32_t *r_max_c, int32_t *r_n_exceed,
+                              double *r_quantile, int32_t *r_quantile_c, double *r_cvar_hi, double *r_cvar_lo, int32_t *counts,
+                              double *cost_out, double *mu_total_out, double *worst_vio_out, int32_t *worst_step_out, int32_t *steps_done_out, int32_t *end_status_out,
+                              int64_t stats[4],
+                              double *sum, double *min, double *max, int32_t *min_step, int32_t *max_step, int32_t *n_above, int32_t *n_changes, int32_t *n_vio,
+                              int T, const double *pol_sel, const double *pol_on_at, const double *pol_off_at, const double *pol_u_on, const double *pol_u_off,
+                              const int32_t *pol_mode, const double *u_prev, int32_t *switches_out)
+{
+    static const char who[] = "mld_rollout_select_policy";
+    if (int rc = entry_guard(p, who, true, "no batch resident (mld_upload_batch)")) return rc;
+    const RolloutOut out{nullptr, nullptr, nullptr, nullptr, nullptr, cost_out, mu_total_out, worst_vio_out, worst_step_out, steps_done_out, end_status_out, stats};
+    const KpiCall kc{n_kpi, {w_x, w_v, w_y, w_omega, w_xk1}, price_chan, thresh, vio_tol, price_start, sum, min, max, min_step, max_step, n_above, n_changes, n_vio};
+    const RiskCall rk{G, col_src, col_q, level, L, alpha, r_mean, r_min, r_max, r_min_c, r_max_c, r_n_exceed, r_quantile, r_quantile_c, r_cvar_hi, r_cvar_lo, counts};
+    const SelectCall sl{P, plan_first, u_cand, obj_col, obj_kind, obj_level, n_cons, cons_col, cons_kind, cons_level, cons_bound, min_complete,
+                        choice, score, n_admissible, admissible, u_choice, u0_choice, T, pol_sel, pol_on_at, pol_off_at, pol_u_on, pol_u_off, pol_mode, u_prev, switches_out};
     return rollout_impl(who, nullptr, p, aux, K, S, nullptr, omega_seq, start, step, cost_w, cost_rows, out, nullptr, n_kpi ? &kc : nullptr, &rk, &sl);
 }
 

@@ -367,6 +367,46 @@ template <typename Queue> static int queue_and_wait(hipStream_t sq, Queue &&queu
  * state) and where the switch counts go */
 struct PolicyCall { const double *u_prev; int32_t *switches_out; };
 
+/* One policy's tables tested and laid out in the kernels' rows -- per model and channel [sel (nx) | on_at | off_at | u_on | u_off | mode] -- into tab
+ * (M nu (nx + 5) doubles): the one copy of what mld_upload_policy and mld_rollout_select_policy refuse.  table < 0: mld_upload_policy's own arguments and
+ * messages; table >= 0: table `table` of the pol_* arrays of a selection, named in every message, where a passed-through channel is refused too (a policy
+ * candidate rules every channel).  all_ruled (or NULL): whether every channel is ruled. */
+static int policy_table_fill(const char *who, int table, int M, int nx, int nu, const double *sel, const double *on_at, const double *off_at, const double *u_on,
+                             const double *u_off, const int32_t *mode, double *tab, bool *all_ruled)
+{
+    const int row = nx + POL_TAIL;
+    const char *pre = table < 0 ? "" : "pol_";
+    char at[32] = "";
+    if (table >= 0) snprintf(at, sizeof at, "table %d, ", table);
+    bool all = true;
+    for (int m = 0; m < M; ++m)
+        for (int j = 0; j < nu; ++j) {
+            const size_t c = (size_t)m * nu + j;
+            double *t = tab + c * row;
+            for (int i = 0; i < nx; ++i) {
+                t[i] = sel[c * nx + i];
+                if (!std::isfinite(t[i])) { mld_set_error("%s: %ssel of %smodel %d, channel %d, state %d is not finite (%g)", who, pre, at, m, j, i, t[i]); return MLD_ERR_INVALID; }
+            }
+            const double vals[4] = {on_at[c], off_at[c], u_on[c], u_off[c]};
+            static const char *const names[4] = {"on_at", "off_at", "u_on", "u_off"};
+            for (int k = 0; k < 4; ++k) {
+                if (!std::isfinite(vals[k])) { mld_set_error("%s: %s%s of %smodel %d, channel %d is not finite (%g)", who, pre, names[k], at, m, j, vals[k]); return MLD_ERR_INVALID; }
+                t[nx + k] = vals[k];
+            }
+            if (on_at[c] > off_at[c]) { mld_set_error("%s: %son_at > %soff_at for %smodel %d, channel %d (%g > %g): the band between the thresholds would be empty", who, pre, pre, at, m, j, on_at[c], off_at[c]); return MLD_ERR_INVALID; }
+            if (mode[c] != 0 && mode[c] != 1) { mld_set_error("%s: %smode of %smodel %d, channel %d is %d (0 = passed through, 1 = ruled)", who, pre, at, m, j, (int)mode[c]); return MLD_ERR_INVALID; }
+            if (table >= 0 && mode[c] == 0) {
+                mld_set_error("%s: pol_mode of table %d, model %d, channel %d is 0 (passed through): a policy candidate rules every channel -- a candidate that rules some channels and takes the plan for the others is not built",
+                              who, table, m, j);
+                return MLD_ERR_INVALID;
+            }
+            t[nx + POL_MODE] = (double)mode[c];
+            all = all && mode[c] == 1;
+        }
+    if (all_ruled) *all_ruled = all;
+    return MLD_OK;
+}
+
 /* What mld_rollout_kpi adds to the same body: the KPI tables of mld_sim_log_summary (each (n_models, n_kpi, width) or NULL), the starts into the price
  * library (batch, or NULL) and where the statistics go: sum, min, max, min_step, max_step, n_above, n_changes (batch, S, n_kpi), n_vio (batch, S); any NULL */
 struct KpiCall {
@@ -405,6 +445,10 @@ struct SelectCall {
     int n_cons; const int32_t *cons_col, *cons_kind, *cons_level; const double *cons_bound;
     int min_complete;
     int32_t *choice; double *score; int32_t *n_admissible; uint8_t *admissible; double *u_choice, *u0_choice;
+    /* mld_rollout_select_policy: the last T of the P candidates are rule policies in closed loop (T == 0: mld_rollout_select's call) -- their tables
+     * pol_sel (T, n_models, nu, nx), pol_on_at, pol_off_at, pol_u_on, pol_u_off, pol_mode (T, n_models, nu), the inputs before step 0 (batch, nu; NULL: the
+     * resident policy state) and where the switch counts go (batch, P, S; NULL); u_cand is (batch, P - plan_first - T, K, nu) */
+    int T; const double *pol_sel, *pol_on_at, *pol_off_at, *pol_u_on, *pol_u_off; const int32_t *pol_mode; const double *u_prev; int32_t *switches_out;
 };
 
 /* What mld_warm_start_from_rollout adds to the same body: the rows that have a start keep it (MLD_START_KEEP), and where the source per instance (batch, or

@@ -97,7 +97,23 @@ LS_FN int sel_scan(const double *v, const unsigned char *ok, int P, double &scor
     return best;
 }
 
+// Where the chosen inputs of a call with policy candidates come from (k_select_inputs): the candidates are [plan (plan_first) | n_seq - plan_first rows of
+// u_cand | the policies]; row = the pick's row among an instance's rows of u_cand (SEL_FROM_SEQ only).  Element e of the K nu chosen inputs of a policy
+// pick: the rule's step 0 for e < nu, NaN behind it (sel_policy_row0).
+enum { SEL_FROM_NONE = 0, SEL_FROM_PLAN, SEL_FROM_SEQ, SEL_FROM_POLICY };
+LS_FN int sel_source(int pick, int plan_first, int n_seq, int &row)
+{
+    row = 0;
+    if (pick < 0) return SEL_FROM_NONE;
+    if (pick >= n_seq) return SEL_FROM_POLICY;
+    if (plan_first && pick == 0) return SEL_FROM_PLAN;
+    row = pick - (plan_first ? 1 : 0);
+    return SEL_FROM_SEQ;
+}
+LS_FN bool sel_policy_row0(size_t e, size_t nu) { return e < nu; }
+
 #if defined(__HIPCC__) && !defined(SM_HOST)
+#include "rollout.inc"      /* policy_rule, ro_cand_table: k_select_inputs applies step 0 of ro_run<true> */
 #define SEL_WAVES 4
 
 struct SelArgs {
@@ -111,6 +127,21 @@ struct SelArgs {
     int *choice; double *score; int *n_adm; unsigned char *adm;                 /* (batch) x 3, (batch, P); any nullptr */
     double *u_choice, *u0_choice;                                               /* (batch, K, nu), (batch, nu); any nullptr */
 };
+
+// The chosen sequence of instance b copied by its wave (k_plan_select, k_select_inputs): step k, input j at src[k step + j] -- the resident plan's strided rows
+// or a row of the candidate array -- into u_choice[b] (K nu doubles) and step 0 into u0_choice[b]; src == nullptr (no choice): NaN.  Lane-contiguous stores.
+__device__ __forceinline__ void sel_copy_inputs(const double *src, size_t step, int K, int nu_, long long b, int lane, double *u_choice, double *u0_choice)
+{
+    const size_t nu = (size_t)nu_, Knu = (size_t)K * nu;
+    const double qnan = __builtin_nan("");
+    if (u_choice)
+        for (size_t e = lane; e < Knu; e += 64) {
+            const size_t k = e / nu, j = e - k * nu;
+            u_choice[(size_t)b * Knu + e] = src ? src[k * step + j] : qnan;
+        }
+    if (u0_choice)
+        for (size_t j = lane; j < nu; j += 64) u0_choice[(size_t)b * nu + j] = src ? src[j] : qnan;
+}
 
 __global__ void __launch_bounds__(64 * SEL_WAVES) k_plan_select(const SelArgs a)
 {
@@ -152,13 +183,51 @@ __global__ void __launch_bounds__(64 * SEL_WAVES) k_plan_select(const SelArgs a)
             if (a.plan_first && pick == 0) { src = a.plan + (size_t)b * a.plan_stride; step = a.plan_step; }
             else src = a.u_cand + ((size_t)b * (size_t)(a.P - a.plan_first) + (size_t)(pick - a.plan_first)) * Knu;
         }
-        if (a.u_choice)
-            for (size_t e = lane; e < Knu; e += 64) {
-                const size_t k = e / (size_t)a.nu, j = e - k * (size_t)a.nu;
-                a.u_choice[(size_t)b * Knu + e] = src ? src[k * step + j] : qnan;
+        sel_copy_inputs(src, step, a.K, a.nu, b, lane, a.u_choice, a.u0_choice);
+    }
+}
+
+// k_select_inputs (mld_rollout_select_policy), queued behind k_plan_select: the chosen inputs where a candidate may be a closed-loop policy.  It reads
+// choice[b].  A plan or sequence pick is copied by sel_copy_inputs, as k_plan_select copies it (the rows of u_cand number n_seq - plan_first per instance
+// here).  A policy pick has no sequence -- its inputs differ from realisation to realisation -- but its step 0 does not: u0[b, j] = policy_rule(table of the
+// pick, x0[b], u_prev[b, j]), the function and the operands of step 0 of ro_run<true>, so the same bits, and what the resolving plant step takes as u0; the
+// row is also u[b, 0, :], and rows 1 .. K - 1 are NaN.  No choice: all NaN.  The mapping is k_plan_select's: one wave per instance, lane-contiguous stores,
+// 64-bit flat indices, no LDS, no atomics.
+struct SelInputsArgs {
+    int batch, P, K, nu, nx, plan_first, n_seq, n_models;
+    const int *choice;                                                          /* (batch): k_plan_select's */
+    const double *plan; size_t plan_stride, plan_step;                          /* the resident plan's rows (candidate 0 with plan_first): n, nv */
+    const double *u_cand;                                                       /* (batch, n_seq - plan_first, K, nu) */
+    const double *tab; size_t tab_len;                                          /* RoCandPolDev's tables: (P - n_seq + 1, n_models, nu, nx + 5) */
+    const int *model_idx; const double *x0, *u_prev;                            /* (batch) or nullptr, (batch, nx), (batch, nu) */
+    double *u_choice, *u0_choice;                                               /* (batch, K, nu), (batch, nu); any nullptr */
+};
+
+__global__ void __launch_bounds__(64 * SEL_WAVES) k_select_inputs(const SelInputsArgs a)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long batch = a.batch;
+    const size_t nu = (size_t)a.nu, Knu = (size_t)a.K * nu;
+    const double qnan = __builtin_nan("");
+    for (long long b = (long long)blockIdx.x * SEL_WAVES + wave; b < batch; b += (long long)gridDim.x * SEL_WAVES) {      /* uniform over the wave */
+        const int pick = a.choice[b];
+        int row;
+        const int from = sel_source(pick, a.plan_first, a.n_seq, row);
+        if (from == SEL_FROM_POLICY) {      /* the rule's step 0, lanes on channels; NaN behind it */
+            const int mdl = a.model_idx ? a.model_idx[b] : 0;
+            for (size_t e = lane; e < (a.u_choice ? Knu : nu); e += 64) {
+                double t = qnan;
+                if (sel_policy_row0(e, nu))
+                    t = ro_cand_input(a.tab, a.tab_len, a.n_models, pick, a.n_seq, a.P, mdl, (int)e, a.nx, a.x0 + (size_t)b * (size_t)a.nx, a.u_prev[(size_t)b * nu + e]);
+                if (a.u0_choice && e < nu) a.u0_choice[(size_t)b * nu + e] = t;
+                if (a.u_choice) a.u_choice[(size_t)b * Knu + e] = t;
             }
-        if (a.u0_choice)
-            for (size_t j = lane; j < (size_t)a.nu; j += 64) a.u0_choice[(size_t)b * (size_t)a.nu + j] = src ? src[j] : qnan;
+            continue;
+        }
+        const double *src = nullptr; size_t step = nu;
+        if (from == SEL_FROM_PLAN) { src = a.plan + (size_t)b * a.plan_stride; step = a.plan_step; }
+        else if (from == SEL_FROM_SEQ) src = a.u_cand + ((size_t)b * (size_t)(a.n_seq - a.plan_first) + (size_t)row) * Knu;
+        sel_copy_inputs(src, step, a.K, a.nu, b, lane, a.u_choice, a.u0_choice);
     }
 }
 #endif

@@ -77,6 +77,21 @@ template <typename X> SM_FN double policy_rule(const double *tab, int nx, const 
     return prev == t[POL_U_ON] ? t[POL_U_ON] : t[POL_U_OFF];
 }
 
+// The table a candidate of mld_rollout_select_policy reads, among the P - n_seq + 1 tables of the call: policy candidate cp >= n_seq its own, cp - n_seq; a
+// plan or sequence candidate the last one, whose every channel is passed through (mode 0) -- ro_run<true> with it copies u_k as ro_run<false> does and
+// counts no switch.  One index computation: no branch around ro_run.
+SM_FN size_t ro_cand_table(int cp, int n_seq, int P) { return (size_t)(cp >= n_seq ? cp - n_seq : P - n_seq); }
+// the rows of candidate cp for an instance of model mdl inside the tables (P - n_seq + 1, n_models, tab_len)
+SM_FN const double *ro_cand_rows(const double *tabs, size_t tab_len, int n_models, int cp, int n_seq, int P, int mdl)
+{
+    return tabs + (ro_cand_table(cp, n_seq, P) * (size_t)n_models + (size_t)mdl) * tab_len;
+}
+// Step 0 of policy candidate `pick` on channel j (k_select_inputs): policy_rule on the instance's x0 and u_prev[j], the call step 0 of ro_run<true> makes
+template <typename X> SM_FN double ro_cand_input(const double *tabs, size_t tab_len, int n_models, int pick, int n_seq, int P, int mdl, int j, int nx, const X *x0, double u_prev_j)
+{
+    return policy_rule(ro_cand_rows(tabs, tab_len, n_models, pick, n_seq, P, mdl) + (size_t)j * (size_t)(nx + POL_TAIL), nx, x0, u_prev_j);
+}
+
 // doubles of staging behind the solver's region (even, so that the next wave's region stays 16-byte aligned)
 static inline size_t ro_stage_doubles(int nx, int nu, int nw, int m, int nv, int ny, int n_kpi = 0)
 {
@@ -284,6 +299,11 @@ struct RoCandDev {        /* what the candidate kernels take on top (mld_rollout
     const double *u_cand;                           /* (batch, P - plan_first, K, nu): the other candidates */
 };
 
+struct RoCandPolDev {     /* what the candidate-policy kernels take on top (mld_rollout_select_policy), likewise an argument of its own */
+    const double *tab; size_t tab_len;              /* (P - n_seq + 1, n_models, nu, nx + 5) in mld_upload_policy's row layout, tab_len = nu (nx + 5); the last table all mode 0 */
+    int n_models, n_seq;                            /* candidates 0 .. n_seq - 1 are the plan and the sequences of u_cand (batch, n_seq - plan_first, K, nu) */
+};
+
 // The kernel body, written once and expanded into both kernels.  (A function template called by the two kernels was tried first: inlined, it left k_rollout
 // with 208 bytes of scratch per lane instead of 156 -- the kernel arguments reach the register allocator by another route.  Expanded in place, the open-loop
 // kernel's listing is the one it had: profiles/policy_rollout_resource_usage.txt.)  POLICY, KPI: literals; `pol`, `kd`: the kernel's RoPolicyDev and RoKpiDev (empty
@@ -292,6 +312,10 @@ struct RoCandDev {        /* what the candidate kernels take on top (mld_rollout
 // t = (b P + p) S + c over a queue of batch P S; everything per instance is read at b, omega at b S + c (the buffer is laid out once for all candidates), every
 // output at t.  Candidate 0 reads RoDev's u (the resident plan's rows, masked by plan_usable) where `plan_first` is set, the others read cd.u_cand; p, c and
 // the two base addresses are computed once per trajectory, nothing else differs.  The four kernels without it expand RO_KERNEL_BODY as they always did.
+// CAND and POLICY (k_rollout_cand_policy / k_rollout_cand_policy_kpi, mld_rollout_select_policy): the flag per trajectory is a TABLE per candidate -- M.pol is
+// table ro_cand_table(cp) of `cq`, ruled for a policy candidate, all passed through for the plan and the sequences, whose rows of u_cand number n_seq -
+// plan_first per instance; T.u of a policy candidate is u_cand's base, never read (every channel of it is ruled); u_prev is the instance's.  ro_run<true>
+// is the one k_rollout_policy calls.
 #define RO_KERNEL_BODY3(POLICY, KPI, CAND)                                                                                                                                \
     extern __shared__ double ro_lds[];                                                                                                                             \
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;                                                                                                    \
@@ -323,12 +347,18 @@ struct RoCandDev {        /* what the candidate kernels take on top (mld_rollout
         }                                                                                                                                                          \
         RoTraj T;                                                                                                                                                  \
         T.K = a.K; T.x0 = a.x0 + (size_t)b * a.nx; T.u = a.u + (size_t)b * a.u_stride; T.u_step = a.u_step;                                                        \
-        if constexpr (CAND) if (!cand_plan) { T.u = cd.u_cand + ((size_t)b * (cd.P - cd.plan_first) + (cp - cd.plan_first)) * a.K * a.nu; T.u_step = (size_t)a.nu; }\
+        if constexpr (CAND && !POLICY) if (!cand_plan) { T.u = cd.u_cand + ((size_t)b * (cd.P - cd.plan_first) + (cp - cd.plan_first)) * a.K * a.nu; T.u_step = (size_t)a.nu; }\
+        if constexpr (CAND && POLICY) if (!cand_plan) {                                                                                                            \
+            const bool seq = cp < cq.n_seq;                                                                                                                        \
+            T.u = seq ? cd.u_cand + ((size_t)b * (cq.n_seq - cd.plan_first) + (cp - cd.plan_first)) * a.K * a.nu : cd.u_cand;                                      \
+            T.u_step = seq ? (size_t)a.nu : 0;                                                                                                                     \
+        }                                                                                                                                                          \
         T.om = a.om + (size_t)(CAND ? tw : t) * a.K * a.nw;                                                                                                        \
         T.cw = a.cw ? a.cw + (size_t)(a.cw_by_inst ? b : mdl) * a.K * a.nv : nullptr;                                                                              \
         T.x = a.x ? a.x + (size_t)t * (a.K + 1) * a.nx : nullptr; T.v = a.v ? a.v + (size_t)t * a.K * a.nv : nullptr;                                              \
         T.y = a.y ? a.y + (size_t)t * a.K * a.ny : nullptr; T.vio = a.vio ? a.vio + (size_t)t * a.K : nullptr; T.row = a.row ? a.row + (size_t)t * a.K : nullptr;  \
         if constexpr (POLICY) { M.pol = pol.tab + (size_t)mdl * pol.tab_len; T.u_prev = pol.u_prev + (size_t)b * a.nu; }                                           \
+        if constexpr (POLICY && CAND) M.pol = ro_cand_rows(cq.tab, cq.tab_len, cq.n_models, cp, cq.n_seq, cd.P, mdl);                                              \
         [[maybe_unused]] RoKpi Q;                                                                                                                                  \
         if constexpr (KPI) {                                                                                                                                       \
             const size_t o = (size_t)t * (size_t)kd.n_kpi;                                                                                                         \
@@ -361,7 +391,7 @@ struct RoCandDev {        /* what the candidate kernels take on top (mld_rollout
 
 // Three waves per SIMD asked for: unconstrained the kernel holds 219 VGPRs (two waves) and takes 1.44 x the time; at 168 it spills 42 registers to
 // scratch, outside the pivot loop's hot values (DESIGN section 6).
-#define RO_KERNEL_BODY(POLICY, KPI) const RoCandDev cd{}; RO_KERNEL_BODY3(POLICY, KPI, false)
+#define RO_KERNEL_BODY(POLICY, KPI) const RoCandDev cd{}; const RoCandPolDev cq{}; RO_KERNEL_BODY3(POLICY, KPI, false)
 __global__ void __launch_bounds__(SM_NT, 3) k_rollout(SmShape S, ProblemDev P, RoDev a)
 {
     const RoPolicyDev pol{};
@@ -393,13 +423,28 @@ __global__ void __launch_bounds__(SM_NT, 3) k_rollout_cand(SmShape S, ProblemDev
 {
     const RoPolicyDev pol{};
     const RoKpiDev kd{};
+    const RoCandPolDev cq{};
     RO_KERNEL_BODY3(false, false, true)
 }
 
 __global__ void __launch_bounds__(SM_NT, 3) k_rollout_cand_kpi(SmShape S, ProblemDev P, RoDev a, RoCandDev cd, RoKpiDev kd)
 {
     const RoPolicyDev pol{};
+    const RoCandPolDev cq{};
     RO_KERNEL_BODY3(false, true, true)
+}
+
+// The candidate-policy instantiations (mld_rollout_select_policy): the policy body twice more, a table per candidate.  Of `pol` they read u_prev and
+// switches; the tables are cq's.
+__global__ void __launch_bounds__(SM_NT, 3) k_rollout_cand_policy(SmShape S, ProblemDev P, RoDev a, RoCandDev cd, RoPolicyDev pol, RoCandPolDev cq)
+{
+    const RoKpiDev kd{};
+    RO_KERNEL_BODY3(true, false, true)
+}
+
+__global__ void __launch_bounds__(SM_NT, 3) k_rollout_cand_policy_kpi(SmShape S, ProblemDev P, RoDev a, RoCandDev cd, RoPolicyDev pol, RoCandPolDev cq, RoKpiDev kd)
+{
+    RO_KERNEL_BODY3(true, true, true)
 }
 #undef RO_KERNEL_BODY
 #undef RO_KERNEL_BODY3

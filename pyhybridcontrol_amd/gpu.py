@@ -1210,6 +1210,126 @@ class GpuProblem(object):
                 out["kpi"] = kp
         return out
 
+    def select_plan_policies(self, resolve, selector, policies=None, u_prev=None, candidates=None, plan_first=False, K=None, omega_seq=None, start=None, step=0,
+                             cost_w=None, kpis=None, price_start=None, vio_tol=1e-6, min_complete=None, per_candidate=False, per_trajectory=False):
+        """select_plan() with closed-loop rule policies among the candidates (mld_rollout_select_policy; kernels k_rollout_cand_policy /
+        k_rollout_cand_policy_kpi, k_rollout_risk, k_plan_select, k_select_inputs).  Every argument of select_plan() means what it means there.
+        policies: a list of policy.ThresholdPolicy, every channel ruled -- T more candidates BEHIND the plan and the sequences, each stepped in CLOSED loop
+        under the same realisations: the reference's thermostat as the yardstick of the comparison and as the fall-back of the safety filter, or a family of
+        bands to tune.  u_prev (batch, nu) / (nu,): the input before step 0, None = the resident policy state (upload_policy), which the call leaves as it
+        is, like everything else on the handle.  Returns what select_plan() returns and policy (batch,) int32, the index into `policies` of the choice or
+        -1; for an instance whose choice is a policy u0 is the rule's step 0 on (x0, u_prev) -- what sim_step(resolve=R, u0=...) takes --, u[:, 0] that row
+        and u[:, 1:] NaN (the later inputs differ from realisation to realisation); per_trajectory=True adds switches (batch, P, S): 0 for a complete plan or
+        sequence trajectory, -1 where it did not end 0.  A risk column of source switches is accepted.  Nothing is finished on the host on this route: a
+        trajectory the LDS solver declines stays 2, counts as n_declined and, with min_complete = S, makes its candidate inadmissible;
+        stats["finished_on_host"] is 0.  policies None or empty: select_plan() itself, its code path and its result."""
+        if policies is None or not len(policies):
+            if u_prev is not None:
+                raise ValueError("u_prev given without policies (an open-loop candidate has no previous input)")
+            return self.select_plan(resolve, selector, candidates=candidates, plan_first=plan_first, K=K, omega_seq=omega_seq, start=start, step=step, cost_w=cost_w,
+                                    kpis=kpis, price_start=price_start, vio_tol=vio_tol, min_complete=min_complete, per_candidate=per_candidate,
+                                    per_trajectory=per_trajectory)
+        policies = list(policies)
+        from . import simlog, policy as _policy
+        d, B, nv = self.model.dims, self.batch, self.model.nv
+        nx, nu, nw = d["nx"], d["nu"], d["nomega"]
+        pf = 1 if plan_first else 0
+        cand = None
+        if candidates is not None:
+            cand = np.asarray(candidates, dtype=np.float64)
+            if cand.ndim == 3:
+                cand = np.broadcast_to(cand, (B,) + cand.shape)
+            if cand.ndim != 4 or cand.shape[0] != B or cand.shape[3] != nu or (K is not None and cand.shape[2] != int(K)):
+                raise ValueError("candidates has shape %s, expected (%d, P, K, %d) or (P, K, %d)%s" % (cand.shape, B, nu, nu, "" if K is None else " with K = %d" % int(K)))
+            cand = np.ascontiguousarray(cand)
+            K = cand.shape[2]
+        K = self.N_tilde if K is None else int(K)
+        n_own, T = 0 if cand is None else cand.shape[1], len(policies)
+        P = pf + n_own + T
+        if P > simlog.SELECT_P_MAX:
+            raise ValueError("P = %d candidates, the %d policies among them (1 .. %d)" % (P, T, simlog.SELECT_P_MAX))
+        for t, pol in enumerate(policies):
+            if not isinstance(pol, _policy.ThresholdPolicy):
+                raise ValueError("policies[%d]: a policy.ThresholdPolicy" % t)
+            if (pol.n_models, pol.nu, pol.nx) != (self.model.n_models, nu, nx):
+                raise ValueError("policies[%d] is shaped (n_models %d, nu %d, nx %d), the problem (%d, %d, %d)" % (t, pol.n_models, pol.nu, pol.nx, self.model.n_models, nu, nx))
+            if not pol.all_ruled:
+                m, j = np.argwhere(pol.mode == 0)[0]
+                raise ValueError("policies[%d] passes channel %d of model %d through: a policy candidate rules every channel (a candidate that rules some channels and "
+                                 "takes the plan for the others is not built)" % (t, j, m))
+        u_prev = self._u_prev_array(u_prev, True)
+        if not isinstance(selector, simlog.PlanSelector):
+            raise ValueError("selector: a simlog.PlanSelector")
+        risk = selector.risk
+        sarr, rarr = selector.arrays(), risk.arrays()
+        omega_seq, st, S, cost_w, rows, karr, ktabs, kthr, pst = self._rollout_inputs(K, omega_seq, start, cost_w, kpis, price_start)
+        if S > simlog.RISK_S_MAX:
+            raise ValueError("risk: S = %d realisations (at most %d)" % (S, simlog.RISK_S_MAX))
+        min_complete = S if min_complete is None else int(min_complete)
+        if not 1 <= min_complete <= S:
+            raise ValueError("min_complete = %d (1 .. S = %d)" % (min_complete, S))
+        Q, chan = 0, None
+        if kpis is None:
+            ktabs = [None] * 5
+            if np.any(rarr["col_src"] >= 4):
+                raise ValueError("risk column %r reads the KPIs, but kpis is None" % (risk.names[int(np.flatnonzero(rarr["col_src"] >= 4)[0])],))
+        else:
+            if np.any(rarr["col_src"] >= 4) and risk.kpis is not kpis and list(risk.kpis.names) != list(kpis.names):
+                raise ValueError("the risk table was built over another KPI table (%s, this call's %s)" % (risk.kpis.names, kpis.names))
+            Q, chan = len(kpis), karr["price_chan"]
+        tabs = {k: np.ascontiguousarray(np.stack([getattr(pol, k) for pol in policies])) for k in ("sel", "on_at", "off_at", "u_on", "u_off")}
+        modes = np.ascontiguousarray(np.stack([pol.mode for pol in policies]), dtype=np.int32)
+        aux = resolve.problem._h if resolve is not None and resolve.problem is not None else None
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None
+        lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64)) if a is not None else None
+        G, L = len(risk), len(risk.levels)
+        out = dict(choice=np.zeros(B, np.int32), score=np.zeros(B), n_admissible=np.zeros(B, np.int32), admissible=np.zeros((B, P), np.uint8),
+                   u=np.zeros((B, K, nu)), u0=np.zeros((B, nu)))
+        rk = dict(names=list(risk.names), levels=list(risk.levels))
+        if per_candidate:
+            rk.update(mean=np.zeros((B, P, G)), min=np.zeros((B, P, G)), min_c=np.zeros((B, P, G), np.int32), max=np.zeros((B, P, G)), max_c=np.zeros((B, P, G), np.int32),
+                      n_exceed=np.zeros((B, P, G), np.int32), quantile=np.zeros((B, P, G, L)), quantile_c=np.zeros((B, P, G, L), np.int32),
+                      cvar_hi=np.zeros((B, P, G, L)), cvar_lo=np.zeros((B, P, G, L)))
+        counts = np.zeros((B, P, 4), np.int32)
+        per, kp = {}, {}
+        if per_trajectory:
+            per = dict(cost=np.zeros((B, P, S)), mu_total=np.zeros((B, P, S)), worst_vio=np.zeros((B, P, S)), worst_step=np.zeros((B, P, S), np.int32),
+                       steps_done=np.zeros((B, P, S), np.int32), end_status=np.zeros((B, P, S), np.int32), switches=np.zeros((B, P, S), np.int32))
+            if kpis is not None:
+                kp = dict(names=list(kpis.names), sum=np.zeros((B, P, S, Q)), min=np.zeros((B, P, S, Q)), max=np.zeros((B, P, S, Q)), min_step=np.zeros((B, P, S, Q), np.int32),
+                          max_step=np.zeros((B, P, S, Q), np.int32), n_above=np.zeros((B, P, S, Q), np.int32), n_changes=np.zeros((B, P, S, Q), np.int32),
+                          n_vio=np.zeros((B, P, S), np.int32))
+        stats = np.zeros(4, np.int64)
+        oc, ok, ol = sarr["obj"]
+        nc = sarr["n_cons"]
+        check(_lib.load().mld_rollout_select_policy(
+            self._h, aux, K, S, P, pf, _lib.dptr(cand), _lib.dptr(omega_seq) if nw else None, lp(st), int(step), _lib.dptr(cost_w), rows, Q,
+            *([_lib.dptr(t) for t in ktabs] + [ip(chan), _lib.dptr(kthr), float(vio_tol), lp(pst)]),
+            G, ip(rarr["col_src"]), ip(rarr["col_q"]), _lib.dptr(rarr["level"]), L, _lib.dptr(rarr["alpha"]),
+            int(oc), int(ok), int(ol), nc, ip(sarr["cons_col"]) if nc else None, ip(sarr["cons_kind"]) if nc else None, ip(sarr["cons_level"]) if nc else None,
+            _lib.dptr(sarr["cons_bound"]) if nc else None, min_complete,
+            ip(out["choice"]), _lib.dptr(out["score"]), ip(out["n_admissible"]), out["admissible"].ctypes.data_as(C.POINTER(C.c_uint8)), _lib.dptr(out["u"]), _lib.dptr(out["u0"]),
+            _lib.dptr(rk.get("mean")), _lib.dptr(rk.get("min")), _lib.dptr(rk.get("max")), ip(rk.get("min_c")), ip(rk.get("max_c")), ip(rk.get("n_exceed")),
+            _lib.dptr(rk.get("quantile")), ip(rk.get("quantile_c")), _lib.dptr(rk.get("cvar_hi")), _lib.dptr(rk.get("cvar_lo")), ip(counts),
+            _lib.dptr(per.get("cost")), _lib.dptr(per.get("mu_total")), _lib.dptr(per.get("worst_vio")), ip(per.get("worst_step")), ip(per.get("steps_done")),
+            ip(per.get("end_status")), lp(stats), _lib.dptr(kp.get("sum")), _lib.dptr(kp.get("min")), _lib.dptr(kp.get("max")),
+            ip(kp.get("min_step")), ip(kp.get("max_step")), ip(kp.get("n_above")), ip(kp.get("n_changes")), ip(kp.get("n_vio")),
+            T, _lib.dptr(tabs["sel"]), _lib.dptr(tabs["on_at"]), _lib.dptr(tabs["off_at"]), _lib.dptr(tabs["u_on"]), _lib.dptr(tabs["u_off"]), ip(modes),
+            _lib.dptr(u_prev), ip(per.get("switches"))))
+        out["admissible"] = out["admissible"].astype(bool)
+        out["policy"] = np.where(out["choice"] >= P - T, out["choice"] - (P - T), -1).astype(np.int32)
+        out["stats"] = dict(trajectories=int(stats[0]), complete=int(stats[1]), infeasible=int(stats[2]), declined=int(stats[3]),
+                            not_attempted=int(stats[0] - stats[1] - stats[2] - stats[3]), finished_on_host=0)
+        if per_candidate:
+            for i, key in enumerate(simlog.RISK_COUNTS):
+                rk[key] = np.ascontiguousarray(counts[:, :, i])
+            out["risk"] = rk
+        if per_trajectory:
+            out.update(per)
+            if kp:
+                out["kpi"] = kp
+        return out
+
     def sim_log(self, first=0, count=None):
         """records [first, first + count) of the resident log (mld_download_sim_log; count=None: all from first): dict of arrays (count, batch, width) --
         x, v, y, omega, x_k1, cons (bool), cons_vio, cons_row, obj, lower_bound, status, nodes.  simlog.to_mld_sim_log turns one instance into the

@@ -652,11 +652,14 @@ def _select_value(risk, col, kind, lvl):
     return np.asarray(a[:, :, col, lvl] if kind >= 4 else a[:, :, col], dtype=np.float64)
 
 
-def select_plan_np(risk_per_candidate, selector, min_complete, candidates=None):
+def select_plan_np(risk_per_candidate, selector, min_complete, candidates=None, policy_u0=None):
     """GpuProblem.select_plan's choice stated in numpy (mld_rollout_select, kernel k_plan_select; the rule: include/mldgpu.h): risk_per_candidate the
     per-candidate risk -- mean, min, max, n_exceed (B, P, G), quantile, cvar_hi, cvar_lo (B, P, G, L), n_complete (B, P) --, selector a PlanSelector,
     min_complete the least number of complete realisations.  Returns dict(choice (B,) int32, -1 = none; score (B,), NaN without a choice; n_admissible (B,)
-    int32; admissible (B, P) bool); with candidates (B, P, K, nu) also u (B, K, nu) and u0 (B, nu), the chosen sequence and its step 0, NaN without a choice."""
+    int32; admissible (B, P) bool); with candidates (B, P, K, nu) also u (B, K, nu) and u0 (B, nu), the chosen sequence and its step 0, NaN without a choice.
+    policy_u0 (B, T, nu) (select_plan_policies(policies=...), mld_rollout_select_policy): the last T of the P candidates are closed-loop policies and policy_u0 their
+    step-0 inputs, policy.apply_np(P_t, model_idx, x0, u_prev); candidates is then (B, P - T, K, nu), the plan and the sequences ((B, 0, K, nu) where P == T: the empty array carries K; None there means K = 1).  The result
+    gains policy (B,) int32, the index of the chosen policy or -1; where the choice is a policy u0 is its policy_u0 row, u[:, 0] that row and u[:, 1:] NaN."""
     arr = selector.arrays()
     val = _select_value(risk_per_candidate, *arr["obj"])
     B, P = val.shape
@@ -671,7 +674,23 @@ def select_plan_np(risk_per_candidate, selector, min_complete, candidates=None):
     some = choice >= 0
     score = np.where(some, val[rows, np.maximum(choice, 0)], np.nan)
     out = dict(choice=choice, score=score, n_admissible=adm.sum(axis=1).astype(np.int32), admissible=adm)
-    if candidates is not None:
+    if policy_u0 is not None:
+        pu0 = np.asarray(policy_u0, dtype=np.float64)
+        T, nu = pu0.shape[1:]
+        n_seq = P - T
+        if pu0.shape[0] != B or T > P or (n_seq > 0 and candidates is None):
+            raise ValueError("policy_u0 has shape %s for %d instances and %d candidates, %d of them sequences%s" % (pu0.shape, B, P, n_seq, "" if candidates is not None else " (candidates is None)"))
+        cand = np.zeros((B, 0, 1, nu)) if candidates is None else np.asarray(candidates, dtype=np.float64)
+        if cand.shape[0] != B or cand.shape[1] != n_seq or cand.shape[3] != nu:
+            raise ValueError("candidates has shape %s, expected (%d, %d, K, %d): the plan and the sequences in front of the %d policies" % (cand.shape, B, n_seq, nu, T))
+        K = cand.shape[2]
+        pol = np.where(choice >= n_seq, choice - n_seq, -1).astype(np.int32)
+        u = np.full((B, K, nu), np.nan)
+        seq = some & (pol < 0)
+        u[seq] = cand[rows[seq], choice[seq]]
+        u[pol >= 0, 0] = pu0[rows[pol >= 0], pol[pol >= 0]]
+        out.update(u=u, u0=np.ascontiguousarray(u[:, 0, :]), policy=pol)
+    elif candidates is not None:
         cand = np.asarray(candidates, dtype=np.float64)
         u = np.where(some[:, None, None], cand[rows, np.maximum(choice, 0)], np.nan)
         out.update(u=u, u0=np.ascontiguousarray(u[:, 0, :]))
