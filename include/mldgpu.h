@@ -149,11 +149,15 @@ typedef enum {
     MLD_DBG_SELECT_R6 = 1 << 27,        /* k_solve's choice of (row, column) as it was before its block reductions left the LDS crossbar:
                                            __shfl_down reductions with a serial combine of the waves' partials, the eligibility test of the
                                            ratio test as nested branches (A/B on the same binary: results are bit-identical, only speed changes) */
-    MLD_DBG_UPDATE_R7 = 1 << 28         /* k_solve's row updates of a pivot and of a fused pair as they were before a unit was cut down to its
+    MLD_DBG_UPDATE_R7 = 1 << 28,        /* k_solve's row updates of a pivot and of a fused pair as they were before a unit was cut down to its
                                            payload: every lane and row predicated, the entering column selected in every unit, rows handed to the
                                            waves in blocks.  Bits 26, 27 and 28 each take the dual simplex into its legacy instantiation, which
                                            holds all three earlier variants; with none of them set the loop carries only the code it runs
                                            (A/B on the same binary: results and rows_updated are bit-identical, only speed changes) */
+    MLD_DBG_DEAD_WORK_R8 = 1 << 29      /* k_solve's bound changes as they were before the pass over work nobody reads: the x_B update of a bound
+                                           change (one variable or a list) walks every row, the rows that are not maintained included.  The bit
+                                           is read outside the pivot loop only and does not select the legacy instantiation (A/B on the same
+                                           binary: results are bit-identical, only speed changes) */
 } mld_reserved_bit;
 
 /* Linear cost in tiled horizon form (the Python layer parses the reference's string-keyed atoms,

@@ -23,6 +23,7 @@ MLD_DBG_SMALL_PIVOT_CAP = 1 << 25      # mld_opts.reserved: k_small_milp with a 
 MLD_DBG_PIVOT_SYNC_R5 = 1 << 26        # mld_opts.reserved: k_solve's pivot with its earlier barrier sequence (A/B on the same binary, bit-identical results)
 MLD_DBG_SELECT_R6 = 1 << 27            # mld_opts.reserved: k_solve's choice of (row, column) with its earlier block reductions (A/B, bit-identical results)
 MLD_DBG_UPDATE_R7 = 1 << 28            # mld_opts.reserved: k_solve's row updates as they were before a unit was cut down to its payload (A/B, bit-identical results)
+MLD_DBG_DEAD_WORK_R8 = 1 << 29         # mld_opts.reserved: k_solve's bound changes update x_B of every row, unmaintained ones included, as before (A/B, bit-identical results)
 MLD_SIM_ADVANCE, MLD_SIM_ACTUAL, MLD_SIM_LOG = 1, 2, 4      # flags of mld_sim_step_batch / mld_sim_step_resolve
 MLD_START_KEEP = 1                                          # flags of mld_warm_start_from_rollout: instances that already have a start keep it
 MLD_FB_MEMORY, MLD_FB_POLICY = 1, 2                         # fb of mld_sim_step_fallback: the sources an instance without a usable plan may take its u from

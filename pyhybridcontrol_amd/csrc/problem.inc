@@ -1031,6 +1031,28 @@ __device__ double s_objective(const Ws &w, Shared &sh)
     return block_sum(sh, s) + d[w.n];
 }
 
+// A row that is not maintained (bit 1 of skip[]: it can never bind, s_mark_dead, or it is a cut row that s_purge_slack_cuts retired): the pivots leave its
+// dictionary entries stale, its basic variable is its slack for good, and nobody reads its x_B -- pricing passes it over, s_refresh and the residual check
+// do not compute it for an original row, s_gather_x reads x_B of basic structurals only.  A bound change therefore has nothing to update there
+// (s_set_bounds, s_set_bounds_list; s_loop_flips skips these rows too).  skip[] through its LDS view where the shape placed it there.
+__device__ __forceinline__ bool s_row_dead(const Ws &w, int r) { return ((w.all_lds ? ((const lds_u8 *)w.skip)[r] : w.skip[r]) & 2) != 0; }
+
+// x_B -= D[:, c] * dl over the maintained rows, a thread per row: the gathers of two rows per thread are issued before the first use
+__device__ __forceinline__ void s_bound_step(const Ws &w, const Shared &sh, int c, double dl)
+{
+    const glb_f64 *Dg = (const glb_f64 *)w.D;
+    const int m = sh.m, ld = w.ld;
+    for (int r0 = threadIdx.x; r0 < m; r0 += 2 * SOL_NT) {
+        const int r1 = r0 + SOL_NT;
+        const bool k0 = !s_row_dead(w, r0), k1 = r1 < m && !s_row_dead(w, r1);
+        double v0 = 0.0, v1 = 0.0;
+        if (k0) v0 = Dg[(size_t)r0 * ld + c];
+        if (k1) v1 = Dg[(size_t)r1 * ld + c];
+        if (k0) w.xB[r0] -= v0 * dl;
+        if (k1) w.xB[r1] -= v1 * dl;
+    }
+}
+
 // change the bounds of variable j keeping dual feasibility (all threads call)
 __device__ void s_set_bounds(const Ws &w, Shared &sh, int j, double lo, double hi)
 {
@@ -1052,8 +1074,10 @@ __device__ void s_set_bounds(const Ws &w, Shared &sh, int j, double lo, double h
         if (threadIdx.x == 0) { w.xN[c] = nw; w.at_upper[c] = up; }
     }
     if (threadIdx.x == 0) { w.lo[j] = lo; w.hi[j] = hi; }
-    if (c >= 0 && dl != 0.0)
-        for (int r = threadIdx.x; r < sh.m; r += SOL_NT) w.xB[r] -= w.D[(size_t)r * w.ld + c] * dl;
+    if (c >= 0 && dl != 0.0) {
+        if (w.dbg & MLD_DBG_DEAD_WORK_R8) { for (int r = threadIdx.x; r < sh.m; r += SOL_NT) w.xB[r] -= w.D[(size_t)r * w.ld + c] * dl; }      // (every row, as before: A/B)
+        else s_bound_step(w, sh, c, dl);
+    }
     __syncthreads();
     if (threadIdx.x == 0) sh.prof[4] += wall_clock64() - tb0;
 }
@@ -1119,8 +1143,49 @@ __device__ void s_set_bounds_list(const Ws &w, Shared &sh, const int *js, const 
             nmove += tot;
         }
         __syncthreads();
-        if (nmove > 0 && !(w.dbg & MLD_DBG_WALKS_SERIAL)) {
-            // a wave takes four rows at a time (r, r + SOL_NW, ...): the gathers of all four are issued together, their shuffle sums run interleaved, then
+        if (nmove > 0 && !(w.dbg & (MLD_DBG_WALKS_SERIAL | MLD_DBG_DEAD_WORK_R8))) {
+            // The maintained rows only (s_row_dead): the grouping below over the list of maintained rows (live_row) instead of over every row, so a
+            // third fewer groups on the bench shape.  The list holds every cut row: one that was retired keeps its slot in a group -- its gathers are
+            // still issued (a stale row, read and not used), only its x_B is neither loaded nor stored, like a row past the end; such rows are few, and
+            // compacting them out would cost an exchange per call.  The four row indices of the NEXT group are read while this one's gathers are in
+            // flight.  Per row the same sum over the same lanes in the same order.
+            const glb_f64 *Dg = (const glb_f64 *)w.D;
+            const int nl = live_count(w, sh), nlive = sh.nlive;
+            int ri[4], rn[4]; bool rk[4], kn[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int t = wave + q * SOL_NW, r = __builtin_amdgcn_readfirstlane(live_row(w, sh, t < nl ? t : 0));      // (the same in every lane of the wave)
+                ri[q] = r; rk[q] = t < nl && !(t >= nlive && s_row_dead(w, r));
+            }
+            for (int t0 = wave; t0 < nl; t0 += 4 * SOL_NW) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int t = t0 + (4 + q) * SOL_NW, r = __builtin_amdgcn_readfirstlane(live_row(w, sh, t < nl ? t : 0));
+                    rn[q] = r; kn[q] = t < nl && !(t >= nlive && s_row_dead(w, r));
+                }
+                double sa[4] = {0.0, 0.0, 0.0, 0.0}, xb[4];
+                for (int tb = 0; tb < nmove; tb += 64) {
+                    const int t = tb + lane; const bool ok = t < nmove;
+                    const int c = ok ? (int)clist[t] : 0; const double dl = ok ? dlist[t] : 0.0;
+                    double v[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) v[q] = Dg[(size_t)ri[q] * ld + c];      // (no branch: a lane past the list reads column 0, a slot without a row reads a maintained row; neither is used)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) if (ok) sa[q] += v[q] * dl;
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) xb[q] = (lane == 0 && rk[q]) ? w.xB[ri[q]] : 0.0;
+                for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) sa[q] += __shfl_down(sa[q], o, 64);
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) if (lane == 0 && rk[q]) w.xB[ri[q]] = xb[q] - sa[q];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) { ri[q] = rn[q]; rk[q] = kn[q]; }
+            }
+        } else if (nmove > 0 && !(w.dbg & MLD_DBG_WALKS_SERIAL)) {
+            // (every row, as before: A/B) a wave takes four rows at a time (r, r + SOL_NW, ...): the gathers of all four are issued together, their shuffle sums run interleaved, then
             // the four stores; per row the same sum over the same lanes as the loop below (a row past the end of a tail group adds zeros and stores nothing)
             const glb_f64 *Dg = (const glb_f64 *)w.D;
             const int m = sh.m;
@@ -1146,6 +1211,7 @@ __device__ void s_set_bounds_list(const Ws &w, Shared &sh, const int *js, const 
             }
         } else if (nmove > 0)
             for (int r = wave; r < sh.m; r += SOL_NW) {
+                if (!(w.dbg & MLD_DBG_DEAD_WORK_R8) && s_row_dead(w, r)) continue;
                 const double *row = w.D + (size_t)r * ld;
                 double sacc = 0.0;
                 for (int t = lane; t < nmove; t += 64) sacc += row[clist[t]] * dlist[t];
