@@ -1002,6 +1002,34 @@ int mld_rollout_select_policy(mld_problem_t *p, mld_problem_t *aux, int K, int S
                               int T, const double *pol_sel, const double *pol_on_at, const double *pol_off_at, const double *pol_u_on, const double *pol_u_off,
                               const int32_t *pol_mode, const double *u_prev, int32_t *switches_out);
 
+/* ---- device completion of declined rollout trajectories -----------------------------------------------------------------------------------------------
+ * Every entry of the rollout family -- mld_rollout_batch, _policy, _kpi, _risk, _select, _select_policy, mld_warm_start_from_rollout -- solves the auxiliary
+ * problem of a step in LDS, and a trajectory whose step the LDS solver declines ends 2.  mld_set_rollout_completion(p, MLD_ROLLOUT_COMPLETE_DEVICE) makes
+ * every later call on the stepped handle p finish those trajectories WITHOUT LEAVING THE DEVICE, after the rollout kernel and before k_rollout_risk,
+ * k_plan_select, k_select_inputs or k_warm_from_rollout read anything.  THE RULE is mld_sim_step_resolve's, applied inside a trajectory:
+ *   - each declined trajectory t is re-run FROM STEP 0 by the same body, every sum in its order (kernels k_rollout_redo / k_rollout_redo_kpi over the list
+ *     k_ro_collect makes of the trajectories with end_status 2);
+ *   - at a step the dense solver has already answered, delta, z, mu come from the trajectory's table instead of the LDS solver;
+ *   - at the first step k the LDS solver declines without an answer, the wave writes x_k and [omega_k; u_k] -- under a policy the rule's u_k; the bytes
+ *     mld_sim_step_resolve(u0 = u_k) would give the resolver at that state -- into a slot of the resolver's input buffers, records k and ends 2 again;
+ *   - the listed slots are solved on the resolver's handle by the DENSE kernel, the small path bypassed; k_ro_fix_merge makes the answer table entry (t, k):
+ *     usable -- status 0 or 2 with a finite objective and finite values -- or "no feasible point", with which the trajectory ends 1 at step k, NaN / -1 from
+ *     there on;
+ *   - rounds repeat while a trajectory is still 2.  Each moves every listed trajectory's declining step forward: at most K rounds.
+ * The steps before k are re-solved by the same deterministic solver to the same bits, so nothing is kept per trajectory on the common path and the rollout
+ * kernels are what they were.  mode 0 (the default): every call queues the launches and returns the results it always did.
+ * MLD_ROLLOUT_COMPLETE_DBG_FIRST_ONLY (tests only, with MLD_ROLLOUT_COMPLETE_DEVICE): MLD_DBG_SMALL_PIVOT_CAP on the resolver then caps the rollout kernel and
+ * the first re-run, which finds its declines again, and no later one -- a trajectory with one dense step followed by LDS steps.
+ * stats[4] of the entries keeps its meaning: [1], [2] count the FINAL endings, [3] what the rollout kernel declined.  The stepped handle is left as found.
+ * On the resolver, the inputs and results of the slots used are put back; a resolver whose resident batch is not the one mld_sim_step_resolve laid out for p's
+ * batch is laid out as that call lays it out, by the same test; its work-queue order is forgotten.  A list longer than the slots of its models is solved in chunks.
+ * mld_rollout_completion_stats: out = [rounds, finished_on_device, dense_solves, left_declined] of the last call of the family on p (all 0 where nothing
+ * was completed).  MLD_ERR_INVALID: p NULL, unknown bits in mode (the mode stays), out NULL. */
+#define MLD_ROLLOUT_COMPLETE_DEVICE 1
+#define MLD_ROLLOUT_COMPLETE_DBG_FIRST_ONLY 2
+int mld_set_rollout_completion(mld_problem_t *p, int mode);
+int mld_rollout_completion_stats(mld_problem_t *p, int64_t out[4]);
+
 /* Per-instance telemetry of the last solve: time spent inside the solve kernel (device wall clock, ns) and
  * the number of dictionary rows the rank-1 updates touched (x *row_bytes x 2 = bytes streamed by pivots). */
 int mld_download_telemetry(mld_problem_t *, int64_t *latency_ns, int64_t *rows_updated, int64_t *row_bytes);

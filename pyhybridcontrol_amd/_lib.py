@@ -26,6 +26,7 @@ MLD_DBG_UPDATE_R7 = 1 << 28            # mld_opts.reserved: k_solve's row update
 MLD_DBG_DEAD_WORK_R8 = 1 << 29         # mld_opts.reserved: k_solve's bound changes update x_B of every row, unmaintained ones included, as before (A/B, bit-identical results)
 MLD_SIM_ADVANCE, MLD_SIM_ACTUAL, MLD_SIM_LOG = 1, 2, 4      # flags of mld_sim_step_batch / mld_sim_step_resolve
 MLD_START_KEEP = 1                                          # flags of mld_warm_start_from_rollout: instances that already have a start keep it
+MLD_ROLLOUT_COMPLETE_DEVICE, MLD_ROLLOUT_COMPLETE_DBG_FIRST_ONLY = 1, 2      # mode of mld_set_rollout_completion (the second: tests only)
 MLD_FB_MEMORY, MLD_FB_POLICY = 1, 2                         # fb of mld_sim_step_fallback: the sources an instance without a usable plan may take its u from
 
 
@@ -69,7 +70,7 @@ EXPORTS = ("mld_device_count", "mld_set_device", "mld_last_error", "mld_version"
            "mld_plan_memory", "mld_set_plan_memory", "mld_download_plan_memory", "mld_sim_step_fallback", "mld_download_sim_log_source",
            "mld_upload_prices", "mld_set_price_cost", "mld_instance_cost_from_prices", "mld_set_stage_cost", "mld_sim_log_cost_begin", "mld_download_sim_log_cost",
            "mld_download_cost_total", "mld_sim_log_summary", "mld_rollout_kpi", "mld_rollout_risk", "mld_rollout_select", "mld_rollout_select_policy",
-           "mld_warm_start_from_rollout",
+           "mld_warm_start_from_rollout", "mld_set_rollout_completion", "mld_rollout_completion_stats",
            "mld_comm_unique_id", "mld_comm_init", "mld_gather", "mld_comm_destroy")
 
 
@@ -132,6 +133,8 @@ def load():
                                        dp, dp, dp, ip, ip, ip, lp, dp, dp, dp, ip, ip, ip, ip, ip]
     lib.mld_rollout_select_policy.argtypes = list(lib.mld_rollout_select.argtypes) + [C.c_int, dp, dp, dp, dp, dp, ip, dp, ip]
     lib.mld_warm_start_from_rollout.argtypes = [C.c_void_p, C.c_void_p, C.c_int, dp, dp, C.c_int, ip, lp]
+    lib.mld_set_rollout_completion.argtypes = [C.c_void_p, C.c_int]
+    lib.mld_rollout_completion_stats.argtypes = [C.c_void_p, lp]
     if int(lib.mld_opts_size()) != C.sizeof(Opts):
         raise MldGpuError("libmldgpu.so was built with another layout of mld_opts (%d bytes, this binding %d): rebuild it (python -m pyhybridcontrol_amd.build)"
                           % (lib.mld_opts_size(), C.sizeof(Opts)))

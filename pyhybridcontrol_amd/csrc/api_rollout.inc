@@ -1,4 +1,34 @@
 // Open-loop rollout of the resident batch's plans under realised disturbances (mld_rollout_batch, kernel k_rollout in rollout.inc).
+enum { RO_MODE_ALL = MLD_ROLLOUT_COMPLETE_DEVICE | MLD_ROLLOUT_COMPLETE_DBG_FIRST_ONLY };
+
+/* The device completion's dense solve (rollout.inc: DEVICE COMPLETION): the listed slots of the resolver's resident batch, whose inputs the re-run kernel has
+ * written, solved by k_solve with the small path bypassed -- what launch() does for the instances k_small_milp declined: the dense path's right-hand sides
+ * and cost, the list as the work queue's order.  A MIP start, cutoffs or open-node recording of the resolver have no part in it, as after the new inputs of
+ * mld_sim_step_resolve.  Host-synchronous on the resolver's stream. */
+static int rollout_solve_slots(mld_problem *q, const std::vector<int> &slots)
+{
+    const hipStream_t sq = q->stream;
+    const bool warm = q->has_warm, cut = q->has_cutoff, open = q->want_open;
+    q->has_warm = q->has_cutoff = q->want_open = false;
+    auto queue = [&]() -> int {
+        HIP_TRY(hipMemsetAsync(q->d_counter, 0, sizeof(int), sq));
+        if (int rc = launch_rhs_cost(q)) return rc;
+        q->S.qp = 0;
+        const ProblemDev P = problem_dev(q);
+        BatchDev B = batch_dev(q, false);
+        HIP_TRY(hipMemcpyAsync(q->bat.order, slots.data(), sizeof(int) * slots.size(), hipMemcpyHostToDevice, sq));
+        q->order_batch = 0;
+        B.order = q->bat.order; B.batch = (int)slots.size();
+        if (q->lds_bytes > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)k_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q->lds_bytes));
+        hipLaunchKernelGGL(k_solve, dim3(std::min(B.batch, q->n_slots)), dim3(SOL_NT), q->lds_bytes, sq, q->S, P, B, q->d_ws.get());
+        HIP_TRY(hipGetLastError());
+        return MLD_OK;
+    };
+    const int rc = queue_and_wait(sq, queue);
+    q->has_warm = warm; q->has_cutoff = cut; q->want_open = open;
+    return rc;
+}
+
 /* The body mld_rollout_batch and mld_rollout_policy share.  pc == nullptr: the open-loop rollout, kernel k_rollout, as it always was.  pc: the policy
  * instantiation k_rollout_policy -- the ruled channels of u_k by p's resident policy from the trajectory's own x_k and u_{k-1}, u_seq / the plan for the
  * passed-through ones only (no plan is needed when every channel is ruled), pc->u_prev (batch, nu) or the resident policy state before step 0.
@@ -228,6 +258,8 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
     HIP_TRY(take(d_ws, worst_step_out, T)); HIP_TRY(take(d_sd, steps_done_out, T)); HIP_TRY(take(d_es, end_status_out, T));
     if (pc) HIP_TRY(take(d_sw, pc->switches_out, T));
     if (n_pol) HIP_TRY(take(d_sw, sl->switches_out, T));
+    const bool dev_complete = (p->ro_mode & MLD_ROLLOUT_COMPLETE_DEVICE) && aux;      /* declined trajectories are finished on the device: k_ro_collect reads the endings */
+    if (dev_complete && !d_es) HIP_TRY(d_es.alloc(T));
     const size_t r_inst = (size_t)batch * (size_t)(sl ? sl->P : 1);      /* what k_rollout_risk takes for its instances: i = b P + p */
     const size_t rg = rk ? r_inst * rk->G : 0, rgl = rk ? rg * rk->L : 0;
     if (rk) {      /* the temporaries of the sources the columns read, asked for or not; the rank table; the results' buffers */
@@ -371,7 +403,7 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
     }
     unsigned long long cnt[4] = {};
     /* everything queued on the stream and waited for on every path (queue_and_wait): the caller's arrays and the temporaries may go when this returns */
-    auto queue = [&]() -> int {
+    auto queue_rollout = [&]() -> int {
         HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(cnt), sq));
         if (u_seq && nu) HIP_TRY(hipMemcpyAsync(d_u, u_seq, sizeof(double) * (size_t)batch * Kz * nu, hipMemcpyHostToDevice, sq));
         if (u_prev_in && nu) HIP_TRY(hipMemcpyAsync(d_uprev, u_prev_in, sizeof(double) * (size_t)batch * nu, hipMemcpyHostToDevice, sq));
@@ -406,6 +438,10 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
         else if (pc) hipLaunchKernelGGL(k_rollout_policy, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a, pd);
         else hipLaunchKernelGGL(k_rollout, dim3(grid), dim3(SM_NT), lds_bytes, sq, SS, P, a);
         HIP_TRY(hipGetLastError());
+        return MLD_OK;
+    };
+    /* what reads the trajectories' results: queued behind the rollout kernel, or behind the device completion where that is on */
+    auto queue_readers = [&]() -> int {
         auto get = [&](auto *out, const auto &buf, size_t count) -> hipError_t {
             return out && buf ? hipMemcpyAsync(out, buf, sizeof(*out) * count, hipMemcpyDeviceToHost, sq) : hipSuccess;
         };
@@ -445,7 +481,167 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
         }
         return MLD_OK;
     };
-    if (int rc = queue_and_wait(sq, queue)) return rc;
+    /* ---- the device completion (rollout.inc: DEVICE COMPLETION): the trajectories the first kernel declined (cnt[3] of them) finished in HBM, before anything
+     * reads a trajectory's result.  The list, table, marks and steps are temporaries sized by the number declined.  The resolver's resident batch supplies the
+     * slots: a listed trajectory takes a slot of ITS model, a list longer than the slots of a model is solved in chunks; the inputs and results the slots
+     * held are put back at the end.  A resolver whose resident batch is not the one laid out for this handle's is laid out as mld_sim_step_resolve lays it out
+     * (the stepped handle's size and model_idx, by the same test): every model the list needs then has a slot. */
+    auto complete = [&]() -> int {
+        const size_t L = (size_t)cnt[3], nA = (size_t)aux->n, PS = (size_t)(sl ? sl->P : 1) * (size_t)S;
+        const hipStream_t aq = aux->stream;
+        DevBuf<long long> d_list; DevBuf<unsigned long long> d_ln; DevBuf<double> d_ans, d_ztab; DevBuf<int> d_mark, d_step, d_ent, d_slot;
+        HIP_TRY(d_list.alloc(L)); HIP_TRY(d_ln.alloc(1)); HIP_TRY(d_ans.alloc(std::max<size_t>(1, L * Kz * nA))); HIP_TRY(d_mark.alloc(L * Kz));
+        HIP_TRY(d_step.alloc(L)); HIP_TRY(d_ent.alloc(L)); HIP_TRY(d_slot.alloc(L));
+        unsigned long long ln = 0;
+        std::vector<long long> list(L);
+        auto collect = [&]() -> int {
+            HIP_TRY(hipMemsetAsync(d_ln, 0, sizeof(ln), sq));
+            HIP_TRY(hipMemsetAsync(d_mark, 0, sizeof(int) * L * Kz, sq));
+            hipLaunchKernelGGL(k_ro_collect, dim3(profile_grid((long long)T)), dim3(256), 0, sq, (long long)T, (const int *)d_es.get(), (long long)L, d_list.get(), d_ln.get());
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(&ln, d_ln, sizeof(ln), hipMemcpyDeviceToHost, sq));
+            HIP_TRY(hipMemcpyAsync(list.data(), d_list, sizeof(long long) * L, hipMemcpyDeviceToHost, sq));
+            return MLD_OK;
+        };
+        if (int rc = queue_and_wait(sq, collect)) return rc;
+        if (ln != L) { mld_set_error("%s: internal: %llu trajectories ended declined, the rollout kernel counted %zu", who, ln, L); return MLD_ERR_INVALID; }
+        std::sort(list.begin(), list.end());      /* (the kernel's order is the atomics': sorted, the slots are the same from call to call) */
+        std::vector<int> pm, emodel(L, 0);
+        if (p->has_midx) {
+            pm.resize((size_t)batch);
+            HIP_TRY(hipMemcpy(pm.data(), p->bat.model_idx, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost));
+            for (size_t e = 0; e < L; ++e) emodel[e] = pm[(size_t)list[e] / PS];
+        }
+        /* the resolver's slots by model */
+        std::vector<std::vector<int>> by((size_t)p->n_models);
+        auto read_layout = [&]() -> int {
+            std::vector<int> am((size_t)aux->batch, 0);
+            if (aux->has_midx) HIP_TRY(hipMemcpy(am.data(), aux->bat.model_idx, sizeof(int) * am.size(), hipMemcpyDeviceToHost));
+            for (auto &l : by) l.clear();
+            for (int i = 0; i < aux->batch; ++i) by[(size_t)am[(size_t)i]].push_back(i);
+            return MLD_OK;
+        };
+        const bool fresh = aux->batch != batch || aux->aux_src_gen != p->batch_gen || aux->aux_own_gen != aux->batch_gen;      /* mld_sim_step_resolve's test */
+        if (!fresh) { if (int rc = read_layout()) return rc; }
+        const size_t anx = (size_t)aux->nx, anw = (size_t)aux->nW;
+        if (fresh) {
+            if (int rc = lay_out_batch(aux, batch, pm.empty() ? nullptr : pm.data(), nullptr)) return rc;
+            aux->aux_src_gen = p->batch_gen; aux->aux_own_gen = aux->batch_gen;
+            HIP_TRY(hipMemset(aux->bat.x0, 0, sizeof(double) * (size_t)batch * anx));
+            HIP_TRY(hipMemset(aux->bat.omega, 0, sizeof(double) * (size_t)batch * anw));
+            if (int rc = read_layout()) return rc;
+        }
+        /* what the slots hold: put back when the rounds are over */
+        const size_t ab = (size_t)aux->batch;
+        DevBuf<double> s_x0, s_om, s_v, s_obj, s_lb; DevBuf<int> s_st, s_nd, s_pv;
+        auto copy_state = [&](bool save) -> int {
+            auto cp = [&](auto &keep, auto &live, size_t count) -> hipError_t {
+                if (!count) return hipSuccess;
+                return save ? hipMemcpyAsync(keep.get(), live.get(), sizeof(*keep.get()) * count, hipMemcpyDeviceToDevice, aq)
+                            : hipMemcpyAsync(live.get(), keep.get(), sizeof(*keep.get()) * count, hipMemcpyDeviceToDevice, aq);
+            };
+            HIP_TRY(cp(s_x0, aux->bat.x0, ab * anx)); HIP_TRY(cp(s_om, aux->bat.omega, ab * anw)); HIP_TRY(cp(s_v, aux->bat.v, ab * nA));
+            HIP_TRY(cp(s_obj, aux->bat.obj, ab)); HIP_TRY(cp(s_lb, aux->bat.lbnd, ab)); HIP_TRY(cp(s_st, aux->bat.status, ab));
+            HIP_TRY(cp(s_nd, aux->bat.nodes, ab)); HIP_TRY(cp(s_pv, aux->bat.pivots, ab));
+            return MLD_OK;
+        };
+        if (!fresh) {
+            HIP_TRY(s_x0.alloc(std::max<size_t>(1, ab * anx))); HIP_TRY(s_om.alloc(std::max<size_t>(1, ab * anw))); HIP_TRY(s_v.alloc(std::max<size_t>(1, ab * nA)));
+            HIP_TRY(s_obj.alloc(ab)); HIP_TRY(s_lb.alloc(ab)); HIP_TRY(s_st.alloc(ab)); HIP_TRY(s_nd.alloc(ab)); HIP_TRY(s_pv.alloc(ab));
+            if (int rc = queue_and_wait(aq, [&]() -> int { return copy_state(true); })) return rc;
+        }
+        /* the re-run kernel's view of the call: the superset body's arguments (rollout.inc) */
+        RoCandDev rcd = cd; RoCandPolDev rcq = cq;
+        if (!n_pol) {
+            rcq.tab_len = ptab_len; rcq.n_models = p->n_models;
+            if (pc) { rcq.tab = p->pol_tab; rcq.n_seq = 0; }
+            else {      /* open loop: the table whose every channel is passed through (all zero: mode 0) */
+                const size_t zl = std::max<size_t>(1, (size_t)p->n_models * ptab_len);
+                HIP_TRY(d_ztab.alloc(zl)); HIP_TRY(hipMemset(d_ztab, 0, sizeof(double) * zl));
+                rcq.tab = d_ztab; rcq.n_seq = sl ? sl->P : 1;
+            }
+            if (!sl) { rcd.P = 1; rcd.plan_first = 0; rcd.u_cand = nullptr; }
+        }
+        RoFixDev fx{};
+        fx.ent = d_ent; fx.slot = d_slot; fx.list = d_list; fx.ans = d_ans; fx.mark = d_mark; fx.ax0 = aux->bat.x0; fx.aom = aux->bat.omega; fx.step = d_step;
+        fx.sel = sl ? 1 : 0;
+        const void *redo_kernel = kc ? (const void *)k_rollout_redo_kpi : (const void *)k_rollout_redo;
+        if (lds_bytes > 48 * 1024) HIP_TRY(hipFuncSetAttribute(redo_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        HIP_TRY(hipMemcpy(d_list, list.data(), sizeof(long long) * L, hipMemcpyHostToDevice));
+        std::vector<int> hstep(L, 0), ent, slot, rest, later, todo;
+        std::vector<char> open(L, 1);
+        long long rounds = 0, dense = 0;
+        auto run = [&]() -> int {
+            for (int r = 0; r <= K; ++r) {      /* pass r leaves a trajectory declined at a step >= r: K rounds at the most, and the pass that ends them all */
+                rest.clear();
+                for (size_t e = 0; e < L; ++e) if (open[e]) rest.push_back((int)e);
+                if (rest.empty()) break;
+                SmShape Sr = SS;
+                if ((p->ro_mode & MLD_ROLLOUT_COMPLETE_DBG_FIRST_ONLY) && r > 0) Sr.max_pivots = aux->opts.max_pivots;      /* the cap: the first kernel's, and the pass that finds its declines again */
+                bool solved = false;
+                while (!rest.empty()) {      /* a chunk: as many of the rest as the resolver has slots of their models */
+                    std::vector<size_t> used((size_t)p->n_models, 0);
+                    ent.clear(); slot.clear(); later.clear(); todo.clear();
+                    for (int e : rest) {
+                        const size_t mdl = (size_t)emodel[(size_t)e];
+                        if (used[mdl] < by[mdl].size()) { ent.push_back(e); slot.push_back(by[mdl][used[mdl]++]); } else later.push_back(e);
+                    }
+                    fx.n_items = (long long)ent.size();
+                    auto redo = [&]() -> int {
+                        HIP_TRY(hipMemcpyAsync(d_ent, ent.data(), sizeof(int) * ent.size(), hipMemcpyHostToDevice, sq));
+                        HIP_TRY(hipMemcpyAsync(d_slot, slot.data(), sizeof(int) * slot.size(), hipMemcpyHostToDevice, sq));
+                        const dim3 rg((unsigned)((ent.size() + SM_WAVES - 1) / SM_WAVES));
+                        if (kc) hipLaunchKernelGGL(k_rollout_redo_kpi, rg, dim3(SM_NT), lds_bytes, sq, Sr, P, a, rcd, pd, rcq, kd, fx);
+                        else hipLaunchKernelGGL(k_rollout_redo, rg, dim3(SM_NT), lds_bytes, sq, Sr, P, a, rcd, pd, rcq, fx);
+                        HIP_TRY(hipGetLastError());
+                        HIP_TRY(hipMemcpyAsync(hstep.data(), d_step, sizeof(int) * L, hipMemcpyDeviceToHost, sq));      /* (the number still declined, read between the rounds) */
+                        return MLD_OK;
+                    };
+                    if (int rc = queue_and_wait(sq, redo)) return rc;
+                    for (size_t i = 0; i < ent.size(); ++i) {
+                        if (hstep[(size_t)ent[i]] >= 0) todo.push_back(slot[i]); else open[(size_t)ent[i]] = 0;
+                    }
+                    if (!todo.empty()) {
+                        if (r == K) { mld_set_error("%s: internal: a trajectory is still declined after K = %d completion rounds (every round moves its declining step forward)", who, K); return MLD_ERR_INVALID; }
+                        if (int rc = rollout_solve_slots(aux, todo)) return rc;
+                        auto merge = [&]() -> int {
+                            hipLaunchKernelGGL(k_ro_fix_merge, dim3((unsigned)std::min<size_t>(ent.size(), 65535)), dim3(64), 0, sq, (long long)ent.size(), (const int *)d_ent.get(),
+                                               (const int *)d_slot.get(), (const int *)d_step.get(), K, (int)nA, (const double *)aux->bat.v.get(), nA, (const int *)aux->bat.status.get(),
+                                               (const double *)aux->bat.obj.get(), d_ans.get(), d_mark.get());
+                            HIP_TRY(hipGetLastError());
+                            return MLD_OK;
+                        };
+                        if (int rc = queue_and_wait(sq, merge)) return rc;
+                        dense += (long long)todo.size(); solved = true;
+                    }
+                    rest.swap(later);
+                }
+                rounds += solved ? 1 : 0;
+            }
+            return MLD_OK;
+        };
+        const int rc = run();
+        int rc2 = MLD_OK;
+        if (!fresh) { rc2 = queue_and_wait(aq, [&]() -> int { return copy_state(false); }); }
+        long long left = 0;
+        for (size_t e = 0; e < L; ++e) left += open[e] ? 1 : 0;
+        p->ro_stats[0] = rounds; p->ro_stats[1] = (long long)L - left; p->ro_stats[2] = dense; p->ro_stats[3] = left;
+        return rc ? rc : rc2;
+    };
+    auto queue = [&]() -> int { if (int rc = queue_rollout()) return rc; return queue_readers(); };
+    std::fill(p->ro_stats, p->ro_stats + 4, 0LL);
+    if (!dev_complete) {
+        if (int rc = queue_and_wait(sq, queue)) return rc;
+    } else {
+        auto first = [&]() -> int {
+            if (int rc = queue_rollout()) return rc;
+            HIP_TRY(hipMemcpyAsync(cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, sq));      /* (read between the rounds, as launch_small reads its counter) */
+            return MLD_OK;
+        };
+        if (int rc = queue_and_wait(sq, first)) return rc;
+        if (cnt[3]) { if (int rc = complete()) return rc; }
+        if (int rc = queue_and_wait(sq, queue_readers)) return rc;
+    }
     if (sc) {      /* the start is set; written / kept / none counted from the sources */
         p->has_warm = true;
         int64_t n[3] = {0, 0, 0};
@@ -458,6 +654,27 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
 }
 
 extern "C" {
+
+/* The sticky completion mode of a stepped handle: what every later call of the rollout family on it does with the trajectories its LDS solver declines
+ * (rollout.inc: DEVICE COMPLETION).  0: as ever -- they end 2.  Nothing is queued; an unknown bit is refused and the mode stays. */
+int mld_set_rollout_completion(mld_problem_t *p, int mode)
+{
+    static const char who[] = "mld_set_rollout_completion";
+    if (!p) { mld_set_error("%s: p is NULL", who); return MLD_ERR_INVALID; }
+    if (mode & ~RO_MODE_ALL) { mld_set_error("%s: mode = %d has unknown bits (MLD_ROLLOUT_COMPLETE_DEVICE = 1, MLD_ROLLOUT_COMPLETE_DBG_FIRST_ONLY = 2)", who, mode); return MLD_ERR_INVALID; }
+    p->ro_mode = mode;
+    return MLD_OK;
+}
+
+/* What the last call of the rollout family on p did: out = [rounds, finished_on_device, dense_solves, left_declined]; all 0 after a call that completed nothing */
+int mld_rollout_completion_stats(mld_problem_t *p, int64_t out[4])
+{
+    static const char who[] = "mld_rollout_completion_stats";
+    if (!p) { mld_set_error("%s: p is NULL", who); return MLD_ERR_INVALID; }
+    if (!out) { mld_set_error("%s: out is NULL (rounds, finished_on_device, dense_solves, left_declined)", who); return MLD_ERR_INVALID; }
+    for (int k = 0; k < 4; ++k) out[k] = (int64_t)p->ro_stats[k];
+    return MLD_OK;
+}
 
 /* The a-posteriori step of a scenario-based controller: what the hybrid plant does over the next K steps if the plan's (or the caller's) inputs are applied
  * and the disturbance turns out to be realisation c -- the reference's MldModel.lsim / lsim_k in a loop (models/mld_model.py:543-642, 647-699) with

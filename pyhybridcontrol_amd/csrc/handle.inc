@@ -119,6 +119,9 @@ struct mld_problem {
      * inputs_advanced_by_plan); the fallback step adopts the count after its own advance (mem_chain).  Where either number has moved on, the first call that
      * needs the memory empties it (plan_memory_ready) */
     DevBuf<double> mem_u; DevBuf<int> mem_age; bool mem_on = false; unsigned long long mem_batch_gen = 0, mem_chain = 0, chain_gen = 0;
+    /* device completion of declined rollout trajectories (mld_set_rollout_completion): the sticky mode of this (stepped) handle, and what the last call of the
+     * rollout family did -- rounds, trajectories finished on the device, dense solves, trajectories left declined (mld_rollout_completion_stats) */
+    int ro_mode = 0; long long ro_stats[4] = {};
     long long ho_stats[4] = {};  /* last solve: items published, trees split, trees left unfinished, entries the queue had no room for (always 0: such trees stay unfinished) */
 };
 

@@ -30,6 +30,20 @@
 // sim_step(step = step + k) records.  The accumulators live in the wave's LDS behind x_{k+1}, 6 n_kpi doubles [sum | min | max | prev | min_step, max_step |
 // n_above, n_changes] (ro_stage_doubles): across sm_solve they cost no register -- k_rollout already spills at its bound -- and with SM_HOST one lane walks all
 // n_kpi of them.  A trajectory that does not end 0 gets NaN / -1.
+//
+// DEVICE COMPLETION of declined trajectories (mld_set_rollout_completion; k_ro_collect, k_rollout_redo[_kpi], k_ro_fix_merge) -- THE RULE, that of
+// mld_sim_step_resolve applied inside a trajectory.  A trajectory t that ended 2 is re-run FROM STEP 0 by the same ro_run body (its third flag, FIX), every sum
+// in its order.  Entry e of the call's list of declined trajectories owns a table of K answers (delta, z, mu: n doubles each) and K marks.  At a step whose mark
+// is RO_FIX_ANSWER ro_run takes delta, z, mu from the table instead of calling sm_solve; at one marked RO_FIX_NO_POINT it ends 1 there, NaN / -1 from there on.
+// At the first step k where sm_solve declines and the table has no answer the wave writes the resolver inputs of that step -- x_k and [omega_k; u_k], under a
+// policy the rule's u_k: the bytes k_aux_inputs writes for mld_sim_step_resolve(u0 = u_k) at that state -- into its slot of the resolver's input buffers,
+// records k and ends 2 again.  The host then solves the listed slots on the resolver's handle with the DENSE kernel, the small path bypassed (a slot's bits do
+// not depend on its neighbours), and k_ro_fix_merge makes the answer entry (e, k): usable -- status 0 or 2 with a finite objective and finite values, the rule
+// of BatchAuxResolver.resolve and simlog.rollout_continue -- or "no feasible point".  Rounds repeat while a trajectory is still 2; each moves every listed
+// trajectory's declining step strictly forward, so there are at most K of them and one more re-run (the loop is bounded by K in code).  The steps before k
+// are re-solved by the same deterministic LDS solver to the same bits: no resume record, nothing on the common path, nothing added to the eight kernels above.
+// The re-run kernel is the superset body -- candidates, a policy table per candidate, FIX -- in two instantiations, without and with the KPIs: an open-loop
+// trajectory reads the table whose every channel is passed through, which reproduces ro_run<false> bit for bit.
 #pragma once
 
 #include "plant_step.inc"
@@ -62,6 +76,13 @@ struct RoKpi {        // ro_run<., true>: one trajectory's KPIs (log_summary.inc
     double vio_tol;
     double *sum, *min, *max; int *min_step, *max_step, *n_above, *n_changes, *n_vio;      // the trajectory's n_kpi entries each, n_vio one
 };
+struct RoFix {        // ro_run<., ., true>: one listed trajectory's table and its slot of the resolver's inputs (DEVICE COMPLETION above)
+    const double *ans;                                                     // K x n: delta, z, mu of the steps the dense solver has answered
+    const int *mark;                                                       // K: RO_FIX_OPEN, RO_FIX_ANSWER or RO_FIX_NO_POINT
+    double *ax0, *aom;                                                     // the slot's rows of the resolver's inputs: nx, nw + nu
+    int *step;                                                             // out: the step whose inputs were written, -1 for a trajectory that ended 0 or 1
+};
+enum { RO_FIX_OPEN = 0, RO_FIX_ANSWER = 1, RO_FIX_NO_POINT = 2 };
 enum { RO_COMPLETE = 0, RO_INFEASIBLE = 1, RO_DECLINED = 2, RO_NOT_ATTEMPTED = -1 };
 enum { POL_ON_AT = 0, POL_OFF_AT = 1, POL_U_ON = 2, POL_U_OFF = 3, POL_MODE = 4, POL_TAIL = 5 };      // a channel's table row behind its nx selector entries
 
@@ -141,9 +162,11 @@ SM_FN void ro_blank(const RoModel &M, const RoTraj &T, int lane, int from, bool 
 // (G, q, lb, ub, cs, is_int, bins), its h / v_out / fixed are set here.  POLICY: the ruled channels of u_k come from M.pol, x_k and u_{k-1} (T.u_prev before
 // step 0); T.u supplies the passed-through channels only, and R.switches counts the (step, ruled channel) pairs whose input changed.  KPI: Q's statistics of
 // the trajectory's records are accumulated in the staging behind x_{k+1} and written by the end (every output of Q is written; stg holds ro_stage_doubles
-// with Q->n_kpi).
-template <bool POLICY = false, bool KPI = false>
-SM_FN void ro_run(const SmShape &S, const RoModel &M, sm_f64 *mem, sm_f64 *stg, SmArgs A, const RoTraj &T, int lane, RoResult &R, const RoKpi *Q = nullptr)
+// with Q->n_kpi).  FIX: step 3 reads F's table where it has an entry and solves where it has none; a decline there writes the step's resolver inputs (THE RULE
+// of the device completion, in the header).
+template <bool POLICY = false, bool KPI = false, bool FIX = false>
+SM_FN void ro_run(const SmShape &S, const RoModel &M, sm_f64 *mem, sm_f64 *stg, SmArgs A, const RoTraj &T, int lane, RoResult &R, const RoKpi *Q = nullptr,
+                  [[maybe_unused]] const RoFix *F = nullptr)
 {
     const int nx = M.nx, nu = M.nu, nw = M.nw, nv = M.nv, ny = M.ny, nc = M.nc, m = M.m, nw2 = M.nw + M.nu, nf = M.nv - M.nmu;
     sm_f64 *xs = stg, *ws = xs + nx, *hs = ws + nw2, *vs = hs + m, *ys = vs + nv, *xn = ys + ny;
@@ -190,10 +213,25 @@ SM_FN void ro_run(const SmShape &S, const RoModel &M, sm_f64 *mem, sm_f64 *stg, 
             }
             sm_sync();
             // ---- 3. delta, z, mu of least total slack
-            SmResult res;
-            sm_solve(S, mem, A, lane, res);
-            sm_sync();
-            if (res.status != MLD_STATUS_OPTIMAL) { end = res.status == MLD_STATUS_INFEASIBLE ? RO_INFEASIBLE : RO_DECLINED; break; }
+            [[maybe_unused]] int mk = RO_FIX_OPEN;
+            if constexpr (FIX) mk = F->mark[k];      /* the same for every lane */
+            if (FIX && mk == RO_FIX_NO_POINT) { end = RO_INFEASIBLE; break; }
+            if (FIX && mk == RO_FIX_ANSWER) {
+                for (int j = lane; j < M.n; j += SM_W) vs[nu + j] = F->ans[(size_t)k * M.n + j];
+                sm_sync();
+            } else {
+                SmResult res;
+                sm_solve(S, mem, A, lane, res);
+                sm_sync();
+                if (res.status != MLD_STATUS_OPTIMAL) {
+                    end = res.status == MLD_STATUS_INFEASIBLE ? RO_INFEASIBLE : RO_DECLINED;
+                    if constexpr (FIX) if (end == RO_DECLINED) {      /* the resolver's inputs of this step: x_k and omega' = [omega_k; u_k] */
+                        for (int j = lane; j < nx; j += SM_W) F->ax0[j] = xs[j];
+                        for (int j = lane; j < nw2; j += SM_W) F->aom[j] = ws[j];
+                    }
+                    break;
+                }
+            }
         }
         // ---- 4. x_{k+1}, y_k and the residuals: k_sim_step's, by the same functions (plant_step.inc)
         for (int i = lane; i < nx; i += SM_W) xn[i] = plant_row(i, P.b5, P.A, P.Bv, P.B4, nx, nv, nw, xs, vs, ws);
@@ -260,6 +298,7 @@ SM_FN void ro_run(const SmShape &S, const RoModel &M, sm_f64 *mem, sm_f64 *stg, 
         R.switches = end == RO_COMPLETE ? sm_uniform(sw) : -1;
     }
     if constexpr (KPI) ro_kpi_write(*Q, end == RO_COMPLETE ? xn + nx : nullptr, lane, n_vio);
+    if constexpr (FIX) if (lane == 0) *F->step = end == RO_DECLINED ? k : -1;
 }
 
 #ifndef SM_HOST
@@ -448,6 +487,127 @@ __global__ void __launch_bounds__(SM_NT, 3) k_rollout_cand_policy_kpi(SmShape S,
 }
 #undef RO_KERNEL_BODY
 #undef RO_KERNEL_BODY3
+
+// ---- the device completion's kernels (THE RULE: the header) ---------------------------------------------------------------------------------------------------
+struct RoFixDev {
+    long long n_items;                              /* listed trajectories this launch re-runs */
+    const int *ent, *slot;                          /* (n_items): the entry e of the call's list, and its slot of the resolver's input buffers */
+    const long long *list;                          /* (entries): the trajectory t of entry e */
+    const double *ans; const int *mark;             /* (entries, K, n), (entries, K) */
+    double *ax0, *aom;                              /* the resolver's inputs (slots, nx), (slots, nw + nu) */
+    int *step;                                      /* (entries) */
+    int sel;                                        /* the call is a selection: candidates other than the plan read u_cand */
+};
+
+// The list of the trajectories that ended 2, in any order: n[0] counts them (64-bit), entries past `cap` are counted and not written.
+__global__ void __launch_bounds__(256) k_ro_collect(long long total, const int *end_status, long long cap, long long *list, unsigned long long *n)
+{
+    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256)
+        if (end_status[t] == RO_DECLINED) {
+            const unsigned long long at = atomicAdd(n, 1ull);
+            if (at < (unsigned long long)cap) list[at] = t;
+        }
+}
+
+// The superset body over a LIST: a wave per item, t -> (b, p, c) as RO_KERNEL_BODY3 maps it (a call without candidates has P = 1), every output at t into
+// the arrays of the first kernel.  A trajectory that now ends 0 or 1 is counted there (counter[1], counter[2]); counter[3] keeps what the first kernel declined.
+template <bool KPI>
+__device__ __forceinline__ void ro_redo_body(const SmShape &S, const ProblemDev &P, const RoDev &a, const RoCandDev &cd, const RoPolicyDev &pol, const RoCandPolDev &cq,
+                                             const RoKpiDev &kd, const RoFixDev &fx)
+{
+    extern __shared__ double ro_lds[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    sm_f64 *mem = (sm_f64 *)ro_lds + (size_t)wave * ((size_t)S.wave_doubles + a.stage_doubles), *stg = mem + S.wave_doubles;
+    RoModel M;
+    M.nx = a.nx; M.nu = a.nu; M.nw = a.nw; M.nv = a.nv; M.nmu = a.nmu; M.ny = a.ny; M.nc = a.nc; M.m = a.m; M.n = a.n;
+    for (long long it = (long long)blockIdx.x * SM_WAVES + wave; it < fx.n_items; it += (long long)gridDim.x * SM_WAVES) {
+        const size_t e = (size_t)fx.ent[it], sl = (size_t)fx.slot[it];
+        const unsigned long long t = (unsigned long long)fx.list[e];
+        const long long b = (long long)(t / ((unsigned long long)cd.P * (unsigned)a.S));
+        const unsigned long long r = t - (unsigned long long)b * cd.P * a.S;
+        const int cp = (int)(r / (unsigned)a.S);
+        const unsigned long long tw = (unsigned long long)b * a.S + (r - (unsigned long long)cp * a.S);
+        const bool cand_plan = fx.sel && cd.plan_first && cp == 0;
+        const int mdl = a.model_idx ? a.model_idx[b] : 0;
+        M.P = plant_mats(a.pack + (size_t)mdl * a.pack_len, a.off);
+        SmArgs A{};
+        if (a.n) {
+            const size_t m = a.m, n = a.n;
+            M.Hx = P.Hx + (size_t)mdl * m * a.nx; M.Hw = P.Hw + (size_t)mdl * m * (a.nw + a.nu); M.H5 = P.H5 + (size_t)mdl * m; M.rs = P.rs + (size_t)mdl * m;
+            A.G = P.Gs + (size_t)mdl * m * n; A.q = P.qs + (size_t)mdl * n;
+            A.lb = P.lb + (size_t)mdl * n; A.ub = P.ub + (size_t)mdl * n; A.cs = P.cs + (size_t)mdl * n;
+            A.is_int = P.is_int; A.bins = P.bins;
+        }
+        RoTraj T;
+        T.K = a.K; T.x0 = a.x0 + (size_t)b * a.nx; T.u = a.u + (size_t)b * a.u_stride; T.u_step = a.u_step;
+        if (fx.sel && !cand_plan) {
+            const bool seq = cp < cq.n_seq;
+            T.u = seq ? cd.u_cand + ((size_t)b * (cq.n_seq - cd.plan_first) + (cp - cd.plan_first)) * a.K * a.nu : cd.u_cand;
+            T.u_step = seq ? (size_t)a.nu : 0;
+        }
+        T.om = a.om + (size_t)tw * a.K * a.nw;
+        T.cw = a.cw ? a.cw + (size_t)(a.cw_by_inst ? b : mdl) * a.K * a.nv : nullptr;
+        T.x = a.x ? a.x + (size_t)t * (a.K + 1) * a.nx : nullptr; T.v = a.v ? a.v + (size_t)t * a.K * a.nv : nullptr;
+        T.y = a.y ? a.y + (size_t)t * a.K * a.ny : nullptr; T.vio = a.vio ? a.vio + (size_t)t * a.K : nullptr; T.row = a.row ? a.row + (size_t)t * a.K : nullptr;
+        M.pol = ro_cand_rows(cq.tab, cq.tab_len, cq.n_models, cp, cq.n_seq, cd.P, mdl);
+        T.u_prev = pol.u_prev ? pol.u_prev + (size_t)b * a.nu : M.pol;      /* open loop: never used (every channel passed through), a valid address of nu doubles */
+        [[maybe_unused]] RoKpi Q;
+        if constexpr (KPI) {
+            const size_t o = (size_t)t * (size_t)kd.n_kpi;
+            Q.n_kpi = kd.n_kpi; Q.n_chan = kd.n_chan; Q.given = kd.given; Q.vio_tol = kd.vio_tol;
+            Q.W = kd.W + (size_t)mdl * kd.rows * kd.n_kpi; Q.thresh = kd.thresh + (size_t)mdl * kd.n_kpi; Q.price_chan = kd.price_chan;
+            Q.price = kd.lib ? kd.lib + kd.price_start[b] + (long long)kd.step * kd.n_chan : nullptr;
+            Q.sum = kd.sum + o; Q.min = kd.min + o; Q.max = kd.max + o; Q.min_step = kd.min_step + o; Q.max_step = kd.max_step + o;
+            Q.n_above = kd.n_above + o; Q.n_changes = kd.n_changes + o; Q.n_vio = kd.n_vio + t;
+        }
+        RoFix F;
+        F.ans = fx.ans + e * (size_t)a.K * (size_t)a.n; F.mark = fx.mark + e * (size_t)a.K;
+        F.ax0 = fx.ax0 + sl * (size_t)a.nx; F.aom = fx.aom + sl * (size_t)(a.nw + a.nu); F.step = fx.step + e;
+        RoResult R;
+        ro_run<true, KPI, true>(S, M, mem, stg, A, T, lane, R, KPI ? &Q : nullptr, &F);
+        if (lane == 0) {
+            if (a.cost) a.cost[t] = R.cost;
+            if (a.mu_total) a.mu_total[t] = R.mu_total;
+            if (a.worst_vio) a.worst_vio[t] = R.worst_vio;
+            if (a.worst_step) a.worst_step[t] = R.worst_step;
+            if (a.steps_done) a.steps_done[t] = R.steps_done;
+            if (a.end_status) a.end_status[t] = R.end_status;
+            if (pol.switches) pol.switches[t] = R.switches;
+            if (R.end_status != RO_DECLINED) atomicAdd(a.counter + 1 + R.end_status, 1ull);
+        }
+    }
+}
+__global__ void __launch_bounds__(SM_NT) k_rollout_redo(SmShape S, ProblemDev P, RoDev a, RoCandDev cd, RoPolicyDev pol, RoCandPolDev cq, RoFixDev fx)
+{
+    const RoKpiDev kd{};
+    ro_redo_body<false>(S, P, a, cd, pol, cq, kd, fx);
+}
+__global__ void __launch_bounds__(SM_NT) k_rollout_redo_kpi(SmShape S, ProblemDev P, RoDev a, RoCandDev cd, RoPolicyDev pol, RoCandPolDev cq, RoKpiDev kd, RoFixDev fx)
+{
+    ro_redo_body<true>(S, P, a, cd, pol, cq, kd, fx);
+}
+
+// The dense answer of slot[it] becomes entry (e, step[e]) of the table: usable -- status 0 or 2 with a finite objective (plan_usable) and finite values -- or
+// "no feasible point".  A wave per item, lanes on the n values; an item whose trajectory ended in this round (step -1) has nothing to merge.
+__global__ void __launch_bounds__(64) k_ro_fix_merge(long long n_items, const int *ent, const int *slot, const int *step, int K, int n, const double *aux_v, size_t aux_stride,
+                                                     const int *aux_status, const double *aux_obj, double *ans, int *mark)
+{
+    const int lane = threadIdx.x;
+    for (long long it = blockIdx.x; it < n_items; it += gridDim.x) {
+        const size_t e = (size_t)ent[it];
+        const int k = step[e], sl = slot[it];
+        if (k < 0 || k >= K) continue;
+        bool ok = plan_usable(aux_status, aux_obj, sl);
+        double *dst = ans + (e * (size_t)K + (size_t)k) * (size_t)n;
+        for (int j0 = 0; j0 < n; j0 += 64) {
+            const int j = j0 + lane;
+            const double t = j < n ? aux_v[(size_t)sl * aux_stride + j] : 0.0;
+            if (j < n) dst[j] = t;
+            ok = __all(fabs(t) < __builtin_huge_val()) && ok;      /* (a NaN fails the comparison too) */
+        }
+        if (lane == 0) mark[e * (size_t)K + (size_t)k] = ok ? RO_FIX_ANSWER : RO_FIX_NO_POINT;
+    }
+}
 
 // k_policy_inputs (mld_sim_step_policy): u[b, j] of ONE step for every instance, written into the buffer the resolving step reads its u0 from.  A ruled
 // channel takes the rule's value from the handle's current x0[b] and the resident u_prev[b]; a passed-through one keeps the caller's value (src ==

@@ -1,5 +1,6 @@
 """Thin object wrappers over the C ABI handles of libmldgpu (mld_model_t / mld_problem_t)."""
 import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -178,6 +179,35 @@ def make_opts(**kw):
             raise TypeError("unknown solver option %r" % k)
         setattr(o, k, type(getattr(o, k))(v))
     return o
+
+
+def _completes(host):
+    """adds complete=None | "host" | "device" to an entry of the rollout family (host: the entry has a host completion, its default).  "device" sets
+    MLD_ROLLOUT_COMPLETE_DEVICE on the handle for the call -- beside whatever set_rollout_completion() left there -- and puts the handle's mode back in a
+    finally; the wrapped method, whose signature stays what it was, reads self._ro_dev and never enters its host completion."""
+    def deco(fn):
+        @functools.wraps(fn)
+        def wrapper(self, *a, complete=None, **kw):
+            if complete not in (None, "host", "device"):
+                raise ValueError("complete = %r (None, 'host' or 'device')" % (complete,))
+            if complete == "host" and not host:
+                raise ValueError("complete = 'host': %s() has no host completion (None leaves declined trajectories as they end, 'device' finishes them on the device)" % fn.__name__)
+            if complete != "device":
+                return fn(self, *a, **kw)
+            mode, was = getattr(self, "_ro_mode", 0), getattr(self, "_ro_dev", False)
+            check(_lib.load().mld_set_rollout_completion(self._h, mode | _lib.MLD_ROLLOUT_COMPLETE_DEVICE))
+            self._ro_dev = True
+            try:
+                out = fn(self, *a, **kw)
+                resolve = a[0] if a else kw.get("resolve")
+                if resolve is not None and resolve.problem is not None and self.rollout_completion_stats()["dense_solves"]:
+                    resolve.problem.batch = self.batch      # (a completion leaves the resolver laid out as sim_step(resolve=) does)
+                return out
+            finally:
+                self._ro_dev = was
+                check(_lib.load().mld_set_rollout_completion(self._h, mode))
+        return wrapper
+    return deco
 
 
 class GpuProblem(object):
@@ -791,6 +821,26 @@ class GpuProblem(object):
         out["n_skipped"] = int(skipped.value)
         return out
 
+    def set_rollout_completion(self, mode):
+        """the sticky completion mode of this handle (mld_set_rollout_completion): 0 as ever, _lib.MLD_ROLLOUT_COMPLETE_DEVICE finishes the trajectories the
+        LDS solver declines on the device in every later call of the rollout family -- what complete="device" sets for one call --,
+        _lib.MLD_ROLLOUT_COMPLETE_DBG_FIRST_ONLY (tests) lets MLD_DBG_SMALL_PIVOT_CAP cap the rollout kernel and the first re-run only."""
+        check(_lib.load().mld_set_rollout_completion(self._h, int(mode)))
+        self._ro_mode = int(mode)
+
+    def rollout_completion_stats(self):
+        """what the last call of the rollout family did on the device (mld_rollout_completion_stats): dict(rounds, finished_on_device, dense_solves, left_declined)"""
+        out = np.zeros(4, np.int64)
+        check(_lib.load().mld_rollout_completion_stats(self._h, out.ctypes.data_as(C.POINTER(C.c_int64))))
+        return dict(rounds=int(out[0]), finished_on_device=int(out[1]), dense_solves=int(out[2]), left_declined=int(out[3]))
+
+    def _device_stats(self, stats):
+        """stats of an entry after a call with complete="device": [1] and [2] count the final endings, [3] what the rollout kernel declined"""
+        cs = self.rollout_completion_stats()
+        return dict(trajectories=int(stats[0]), complete=int(stats[1]), infeasible=int(stats[2]), declined=int(stats[3]),
+                    not_attempted=int(stats[0] - stats[1] - stats[2]) - cs["left_declined"], finished_on_host=0,
+                    finished_on_device=cs["finished_on_device"], completion_rounds=cs["rounds"])
+
     def _u_seq_array(self, u_seq, K):
         """u_seq of rollout() / warm_start_from_rollout(): (batch, K, nu), or (K, nu) for every instance; K=None takes the array's"""
         B, nu = self.batch, self.model.dims["nu"]
@@ -865,6 +915,7 @@ class GpuProblem(object):
                                  % (kpis.names[int(np.flatnonzero(karr["price_chan"] >= 0)[0])],))
         return omega_seq, st, S, cost_w, rows, karr, ktabs, kthr, pst
 
+    @_completes(True)
     def rollout(self, resolve, K=None, u_seq=None, omega_seq=None, start=None, step=0, cost_w=None, trajectories=False, policy=False, u_prev=None,
                 kpis=None, price_start=None, vio_tol=1e-6, risk=None, per_trajectory=True):
         """open-loop rollout of the resident batch under S realised disturbances, on device (mld_rollout_batch, kernel k_rollout): the reference's
@@ -897,7 +948,11 @@ class GpuProblem(object):
         n_not_attempted (batch,) int32); an instance without a complete realisation has NaN / +inf / -inf / -1 / 0.  S <= 64.  The figures are those of
         simlog.rollout_risk_np on the same result, bit for bit; the instances with a trajectory finished on the host take theirs from rollout_risk_np of
         the finished arrays.  per_trajectory=False (with risk only) asks for nothing per trajectory: every (batch, S, ...) entry, kpi included, is neither
-        downloaded nor returned.  With risk=None the call and its result are what they were."""
+        downloaded nor returned.  With risk=None the call and its result are what they were.
+        complete: None or "host" -- the host completion above; "device" -- the declined trajectories are finished on the device instead (mld.h: device
+        completion; re-run from step 0, the declined steps by the dense kernel on the resolver's handle), before the KPIs' and the risk's consumers read
+        them: nothing more is downloaded, per_trajectory=False downloads nothing per trajectory whatever declined, stats gains finished_on_device and
+        completion_rounds, finished_on_host is 0 and declined counts what the rollout kernel declined."""
         from . import simlog
         d, B, nv = self.model.dims, self.batch, self.model.nv
         nx, nu, nw, ny = d["nx"], d["nu"], d["nomega"], d["ny"]
@@ -1011,7 +1066,7 @@ class GpuProblem(object):
             return o, stats
 
         out, stats = call(trajectories, per_trajectory)
-        n_host = int(stats[3])
+        n_host = 0 if getattr(self, "_ro_dev", False) else int(stats[3])
         if n_host:
             if not trajectories or not per_trajectory:
                 out, stats = call(True)      # (the completion continues from the states and slices the device left: it needs the trajectories)
@@ -1068,6 +1123,8 @@ class GpuProblem(object):
         es = out.get("end_status")
         out["stats"] = dict(trajectories=int(stats[0]), complete=int((es == 0).sum()) if n_host else int(stats[1]), infeasible=int((es == 1).sum()) if n_host else int(stats[2]),
                             declined=int(stats[3]), not_attempted=int(stats[0] - stats[1] - stats[2] - stats[3]), finished_on_host=n_host)
+        if getattr(self, "_ro_dev", False):
+            out["stats"] = self._device_stats(stats)
         if n_host and not trajectories:
             for k in ("x", "v", "y", "cons_vio", "cons_row"):
                 del out[k]
@@ -1075,6 +1132,7 @@ class GpuProblem(object):
             out = dict(risk=out["risk"], stats=out["stats"])
         return out
 
+    @_completes(True)
     def select_plan(self, resolve, selector, candidates=None, plan_first=False, K=None, omega_seq=None, start=None, step=0, cost_w=None, kpis=None,
                     price_start=None, vio_tol=1e-6, min_complete=None, per_candidate=False, per_trajectory=False):
         """choose, per instance, among P candidate input sequences by their rollout risk, on device (mld_rollout_select; kernels k_rollout_cand /
@@ -1090,7 +1148,8 @@ class GpuProblem(object):
         (batch, P, G[, L]) and (batch, P) counts; per_trajectory=True adds cost, mu_total, worst_vio, worst_step, steps_done, end_status (batch, P, S) and,
         with kpis, kpi (batch, P, S, n_kpi).  The figures are those of simlog.select_plan_np on that risk, bit for bit.  Trajectories the device's LDS solver
         declined are finished on the host as rollout() finishes them: the instances they belong to take every candidate's risk from rollout() itself and
-        their choice from select_plan_np."""
+        their choice from select_plan_np.  complete="device" (rollout()'s): they are finished on the device before k_rollout_risk and k_plan_select read
+        them, and the host route is never entered."""
         from . import simlog
         d, B, nv = self.model.dims, self.batch, self.model.nv
         nx, nu, nw, ny = d["nx"], d["nu"], d["nomega"], d["ny"]
@@ -1168,7 +1227,7 @@ class GpuProblem(object):
             ip(per.get("end_status")), lp(stats), _lib.dptr(kp.get("sum")), _lib.dptr(kp.get("min")), _lib.dptr(kp.get("max")),
             ip(kp.get("min_step")), ip(kp.get("max_step")), ip(kp.get("n_above")), ip(kp.get("n_changes")), ip(kp.get("n_vio"))))
         out["admissible"] = out["admissible"].astype(bool)
-        n_host = int(stats[3])
+        n_host = 0 if getattr(self, "_ro_dev", False) else int(stats[3])
         n_done = [int(stats[1]), int(stats[2])]
         if n_host:      # finished on the host, by rollout() itself: one call per candidate, the route this entry point replaces
             sel = np.flatnonzero((counts[:, :, 2] > 0).any(axis=1))
@@ -1200,6 +1259,8 @@ class GpuProblem(object):
             n_done = [int((es == 0).sum()), int((es == 1).sum())]
         out["stats"] = dict(trajectories=int(stats[0]), complete=n_done[0], infeasible=n_done[1], declined=int(stats[3]),
                             not_attempted=int(stats[0] - stats[1] - stats[2] - stats[3]), finished_on_host=n_host)
+        if getattr(self, "_ro_dev", False):
+            out["stats"] = self._device_stats(stats)
         if per_candidate:
             for i, key in enumerate(simlog.RISK_COUNTS):
                 rk[key] = np.ascontiguousarray(counts[:, :, i])
@@ -1210,6 +1271,7 @@ class GpuProblem(object):
                 out["kpi"] = kp
         return out
 
+    @_completes(False)
     def select_plan_policies(self, resolve, selector, policies=None, u_prev=None, candidates=None, plan_first=False, K=None, omega_seq=None, start=None, step=0,
                              cost_w=None, kpis=None, price_start=None, vio_tol=1e-6, min_complete=None, per_candidate=False, per_trajectory=False):
         """select_plan() with closed-loop rule policies among the candidates (mld_rollout_select_policy; kernels k_rollout_cand_policy /
@@ -1222,13 +1284,14 @@ class GpuProblem(object):
         and u[:, 1:] NaN (the later inputs differ from realisation to realisation); per_trajectory=True adds switches (batch, P, S): 0 for a complete plan or
         sequence trajectory, -1 where it did not end 0.  A risk column of source switches is accepted.  Nothing is finished on the host on this route: a
         trajectory the LDS solver declines stays 2, counts as n_declined and, with min_complete = S, makes its candidate inadmissible;
-        stats["finished_on_host"] is 0.  policies None or empty: select_plan() itself, its code path and its result."""
+        stats["finished_on_host"] is 0.  complete="device" (rollout()'s): such a trajectory is finished on the device before the risk is reduced, so no
+        candidate is lost to a decline; complete="host" is refused.  policies None or empty: select_plan() itself, its code path and its result."""
         if policies is None or not len(policies):
             if u_prev is not None:
                 raise ValueError("u_prev given without policies (an open-loop candidate has no previous input)")
             return self.select_plan(resolve, selector, candidates=candidates, plan_first=plan_first, K=K, omega_seq=omega_seq, start=start, step=step, cost_w=cost_w,
                                     kpis=kpis, price_start=price_start, vio_tol=vio_tol, min_complete=min_complete, per_candidate=per_candidate,
-                                    per_trajectory=per_trajectory)
+                                    per_trajectory=per_trajectory, **(dict(complete="device") if getattr(self, "_ro_dev", False) else {}))
         policies = list(policies)
         from . import simlog, policy as _policy
         d, B, nv = self.model.dims, self.batch, self.model.nv
@@ -1320,6 +1383,8 @@ class GpuProblem(object):
         out["policy"] = np.where(out["choice"] >= P - T, out["choice"] - (P - T), -1).astype(np.int32)
         out["stats"] = dict(trajectories=int(stats[0]), complete=int(stats[1]), infeasible=int(stats[2]), declined=int(stats[3]),
                             not_attempted=int(stats[0] - stats[1] - stats[2] - stats[3]), finished_on_host=0)
+        if getattr(self, "_ro_dev", False):
+            out["stats"] = self._device_stats(stats)
         if per_candidate:
             for i, key in enumerate(simlog.RISK_COUNTS):
                 rk[key] = np.ascontiguousarray(counts[:, :, i])
@@ -1429,6 +1494,7 @@ class GpuProblem(object):
         the reference's backend), shift k = moved k steps on with the last step repeated (after advance())"""
         check(_lib.load().mld_warm_start_from_previous(self._h, int(shift)))
 
+    @_completes(False)
     def warm_start_from_rollout(self, resolve, policy=False, u_seq=None, u_prev=None, keep=False):
         """MIP start from a rollout of the current x0 under the resident forecast, on device (mld_warm_start_from_rollout, kernels k_rollout[_policy] and
         k_warm_from_rollout): the start for the instances warm_start_from_previous leaves without one, and for the first solve after an upload.
@@ -1437,7 +1503,8 @@ class GpuProblem(object):
         its auxiliaries re-derived for this handle's forecast.  resolve: as rollout().  keep=True: an instance whose resident start is not 255 keeps it.
         Returns dict(source (batch,) int32: 1 written, 0 kept, -1 infeasible auxiliaries, -2 the LDS solver declined, -3 not attempted (the last three: row
         255 = no start); stats: dict(trajectories, written, kept, none)).  Nothing else on the handle changes; a problem without binaries gets no start and
-        an empty stats."""
+        an empty stats.  complete="device" (rollout()'s): an instance whose trajectory the LDS solver declined is finished on the device and gets its start
+        (source 1, or -1) instead of -2; stats gains finished_on_device and completion_rounds.  complete="host" is refused."""
         B = self.batch
         if u_seq is not None:
             u_seq = self._u_seq_array(u_seq, self.N_tilde)
@@ -1448,7 +1515,11 @@ class GpuProblem(object):
                                                       source.ctypes.data_as(C.POINTER(C.c_int32)), stats.ctypes.data_as(C.POINTER(C.c_int64))))
         if not self.n_bin:
             return dict(source=None, stats={})
-        return dict(source=source, stats=dict(trajectories=int(stats[0]), written=int(stats[1]), kept=int(stats[2]), none=int(stats[3])))
+        st = dict(trajectories=int(stats[0]), written=int(stats[1]), kept=int(stats[2]), none=int(stats[3]))
+        if getattr(self, "_ro_dev", False):
+            cs = self.rollout_completion_stats()
+            st.update(finished_on_device=cs["finished_on_device"], completion_rounds=cs["rounds"])
+        return dict(source=source, stats=st)
 
     def stage(self, x0_sets, omega_sets):
         """input sets of the uploaded batch's size resident in HBM (mld_stage_inputs): x0_sets (n_sets, batch, nx), omega_sets

@@ -20,6 +20,7 @@ The scenario is scripts/gpu_rollout_risk_probe.py's: one realised series per ins
 independent random binary sequences of duty cycle 0.4, the inputs of scripts/gpu_rollout_probe.py.  A few trajectories in a million are declined by the LDS
 solver, and select_plan() as rollout() would finish them on the host, downloading every trajectory: the candidates that have one are REPLACED before anything
 is timed (redraw_declined), so the inputs are changed and the host-completion route is never measured here; the count is recorded as `instances_redrawn`.
+--unreplaced keeps the shard as drawn and passes complete="device" to every call of both routes instead; the default is what it was.
 """
 import csv
 import ctypes as C
@@ -200,10 +201,13 @@ def main():
     p.upload(x0, om, midx)
     p.upload_profiles(lib, (nx, 1))
     p.upload_prices(plib, 1)
-    res["instances_redrawn"] = redraw_declined(p, R, cand, start, pstart, kpis, risk, rng)
+    unreplaced = "--unreplaced" in sys.argv      # the shard as drawn: declined trajectories are finished on the device (complete="device"), by both routes
+    how = dict(complete="device") if unreplaced else {}
+    if not unreplaced:
+        res["instances_redrawn"] = redraw_declined(p, R, cand, start, pstart, kpis, risk, rng)
     per_cand = [np.ascontiguousarray(cand[:, q]) for q in range(P)]
-    on_device = lambda **kw: p.select_plan(R, sel, candidates=cand, start=start, kpis=kpis, price_start=pstart, **kw)
-    one = lambda q: p.rollout(R, u_seq=per_cand[q], start=start, kpis=kpis, price_start=pstart, risk=risk, per_trajectory=False)
+    on_device = lambda **kw: p.select_plan(R, sel, candidates=cand, start=start, kpis=kpis, price_start=pstart, **dict(how, **kw))
+    one = lambda q: p.rollout(R, u_seq=per_cand[q], start=start, kpis=kpis, price_start=pstart, risk=risk, per_trajectory=False, **how)
     if kernel_only:
         for _ in range(3):
             res["stats"] = on_device()["stats"]
@@ -228,7 +232,7 @@ def main():
         t = time.perf_counter(); dev = on_device(); ms_d = (time.perf_counter() - t) * 1e3
         t = time.perf_counter(); ref = on_host(); ms_h = (time.perf_counter() - t) * 1e3
         print("round %d: select_plan %.1f ms, %d x rollout(risk, per_trajectory=False) + select_plan_np %.1f ms" % (r, ms_d, P, ms_h), flush=True)
-        if dev["stats"]["finished_on_host"] or dev["stats"]["declined"]:
+        if dev["stats"]["finished_on_host"] or (dev["stats"]["declined"] and not unreplaced):
             sys.exit("trajectories were declined and finished on the host (%s): not the route this probe measures" % (dev["stats"],))
         if r >= 1:
             wall["select_plan_on_device"].append(ms_d); wall["rollouts_per_candidate_plus_select_plan_np"].append(ms_h)

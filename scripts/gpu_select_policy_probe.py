@@ -20,7 +20,8 @@ under S = 20 realisations, 3 candidate input sequences and 1 thermostat, the mic
 
 The new entry finishes nothing on the host; the parent's route does, downloading every trajectory.  An instance with a trajectory the LDS solver declines
 (a few in a million) is REPLACED before anything is timed by a neighbour of the same model that has none, so the inputs are changed and the host-completion
-route is never measured here; the count is recorded as `instances_replaced`.
+route is never measured here; the count is recorded as `instances_replaced`.  --unreplaced keeps the shard as drawn and passes complete="device" to every
+call of both routes instead (the trajectories are finished on the device); the default is what it was.
 """
 import json
 import os
@@ -94,6 +95,8 @@ def main():
     from pyhybridcontrol_amd import gpu, host, policy, simlog, _lib
     from pyhybridcontrol_amd.aux_resolve import BatchAuxResolver
     kernel_only = "--kernel-only" in sys.argv
+    unreplaced = "--unreplaced" in sys.argv      # the shard as drawn: declined trajectories are finished on the device (complete="device"), by both routes
+    how = dict(complete="device") if unreplaced else {}
     out_path = base.arg("--out", "")
     pairs = base.arg("--pairs", 7)
     agents, N_p, N_t, x0, om, midx = bench.make_shard(BATCH_MODELS, BATCH_SCEN, 0)
@@ -145,13 +148,13 @@ def main():
     p.upload_profiles(lib, (nx, 1))
     p.upload_prices(plib, 1)
     replaced = []
-    for _ in range(5):      # an instance with a declined trajectory takes the inputs of the nearest instance of its model that has none
+    for _ in range(1 if unreplaced else 5):      # an instance with a declined trajectory takes the inputs of the nearest instance of its model that has none
         cd, upv, start, pstart = inputs()
         p.upload(np.ascontiguousarray(x0[src]), np.ascontiguousarray(om[src]), midx)
         n_dec = p.select_plan_policies(R, sel, candidates=cd, policies=[thermo], u_prev=upv, start=start, kpis=kpis, price_start=pstart, per_candidate=True)["risk"]["n_declined"]
         bad = np.flatnonzero(n_dec.any(axis=1))
         replaced.append(int(bad.size))
-        if not bad.size:
+        if not bad.size or unreplaced:
             break
         clean = ~n_dec.any(axis=1)
         for b in bad:
@@ -159,14 +162,17 @@ def main():
             src[b] = src[same[np.argmin(np.abs(same - b))]]
     else:
         sys.exit("trajectories are still declined after 5 rounds: %s" % (replaced,))
-    res["instances_replaced"] = replaced
-    on_device = lambda **kw: p.select_plan_policies(R, sel, candidates=cd, policies=[thermo], u_prev=upv, start=start, kpis=kpis, price_start=pstart, **kw)
-    sequences = lambda **kw: p.select_plan(R, sel, candidates=cd, start=start, kpis=kpis, price_start=pstart, **kw)
+    if unreplaced:      # (c) of the device completion's measurement: the candidates that were inadmissible only because of a decline
+        res["unreplaced"] = dict(instances_with_a_declined_trajectory=replaced[0], candidates_with_a_declined_trajectory=int((n_dec > 0).sum()))
+    else:
+        res["instances_replaced"] = replaced
+    on_device = lambda **kw: p.select_plan_policies(R, sel, candidates=cd, policies=[thermo], u_prev=upv, start=start, kpis=kpis, price_start=pstart, **dict(how, **kw))
+    sequences = lambda **kw: p.select_plan(R, sel, candidates=cd, start=start, kpis=kpis, price_start=pstart, **dict(how, **kw))
 
     def closed_loop():
         p.upload_policy(thermo)
         try:
-            return p.rollout(R, K=K, policy=True, u_prev=upv, start=start, kpis=kpis, price_start=pstart, risk=risk, per_trajectory=False)
+            return p.rollout(R, K=K, policy=True, u_prev=upv, start=start, kpis=kpis, price_start=pstart, risk=risk, per_trajectory=False, **how)
         finally:
             p.upload_policy(None)
 
@@ -196,7 +202,7 @@ def main():
         t = time.perf_counter(); dev = on_device(); ms_d = (time.perf_counter() - t) * 1e3
         t = time.perf_counter(); ref = parents_route(); ms_h = (time.perf_counter() - t) * 1e3
         print("round %d: select_plan_policies(policies) %.1f ms, select_plan + upload_policy + rollout(policy) + merge + select_plan_np %.1f ms" % (r, ms_d, ms_h), flush=True)
-        if dev["stats"]["declined"]:
+        if dev["stats"]["declined"] and not unreplaced:
             sys.exit("trajectories were declined (%s): the parent's route would finish them on the host, which this probe does not measure" % (dev["stats"],))
         if r >= 1:
             wall["select_plan_with_policies"].append(ms_d); wall["parents_route"].append(ms_h)

@@ -1,7 +1,7 @@
 """The MIP start from a baseline rollout on the device (GpuProblem.warm_start_from_rollout, kernels k_rollout_policy and k_warm_from_rollout) at the bench
 shard (64 models x 512 scenarios = 32 768 instances, N_tilde = 25), thermostat on every channel.
 
-    python scripts/gpu_start_rollout_probe.py [--out profiles/start_rollout_probe.json]
+    python scripts/gpu_start_rollout_probe.py [--out profiles/start_rollout_probe.json] [--unreplaced]      # --unreplaced: complete="device" in every call
 
 Medians of seven runs behind one warm-up, the routes ALTERNATING in one session:
 * entry_vs_kernel_work: the entry against rollout(policy=True, K=N_tilde, omega_seq=forecast) with summaries only -- the same kernel work plus an upload of
@@ -59,17 +59,20 @@ def main():
     p.upload_policy(P)
     forecast = np.ascontiguousarray(p.inputs()[1].reshape(B, 1, N_t, nw))
 
+    unreplaced = "--unreplaced" in sys.argv      # declined trajectories are finished on the device (complete="device") by the entry and by both yardsticks
+    how = dict(complete="device") if unreplaced else {}
+
     def host_route():
-        ro = p.rollout(R, omega_seq=forecast, policy=True, trajectories=True)
+        ro = p.rollout(R, omega_seq=forecast, policy=True, trajectories=True, **how)
         start, source = simlog.start_from_rollout_np(ro["v"], ro["end_status"], bins)
         p.set_warm_start(start)
         return start, source, ro
 
     wall = dict(entry=[], rollout_summaries=[], host_route=[])
     for r in range(8):                                           # one warm-up round, seven timed rounds, alternating
-        got, ms_e = timed(lambda: p.warm_start_from_rollout(R, policy=True))
+        got, ms_e = timed(lambda: p.warm_start_from_rollout(R, policy=True, **how))
         dev_start = p.debug_warm_start()
-        lean, ms_r = timed(lambda: p.rollout(R, omega_seq=forecast, policy=True))
+        lean, ms_r = timed(lambda: p.rollout(R, omega_seq=forecast, policy=True, **how))
         (start, source, ro), ms_h = timed(host_route)
         if r >= 1:
             wall["entry"].append(ms_e); wall["rollout_summaries"].append(ms_r); wall["host_route"].append(ms_h)
