@@ -713,6 +713,54 @@ int mld_sim_step_fallback(mld_problem_t *, mld_problem_t *aux, int fb, const int
                           double *v0_out, int32_t *aux_status_out, int32_t *u_source_out, int32_t *n_skipped_out);
 int mld_download_sim_log_source(mld_problem_t *, int first, int count, int32_t *u_source);
 
+/* ---- applying a selection on the device ------------------------------------------------------------------------------------------------------------------
+ * mld_rollout_select and mld_rollout_select_policy (below) answer "which candidate should be applied now"; applying the answer through
+ * mld_sim_step_resolve(u0 = the downloaded u0_choice) sends u0 down and up again on every step, empties the plan memory (the advance is another entry
+ * point's), leaves the resident policy's u_prev where it was, logs u_source -2, and attempts an instance without an admissible candidate with a NaN row.
+ * mld_sim_step_selected is the resolving step with the selection as the FIRST source of u, in place of the plan, and the memory, the policy state and the
+ * log consistent with what was applied.
+ *
+ * Kept selection  owned by the resident batch: choice (batch) int32, -1 = none; policy (batch) int32, the policy index of the pick, -1 for a plan or sequence
+ *             pick or no pick; u (batch, K, nu) fp64, exactly what the select call returns as u_choice -- a policy pick has the rule's step 0 in row 0 and
+ *             NaN behind it, no choice is all NaN --; and K.  mld_keep_selection(p, enable) is sticky, like mld_set_rollout_completion: while it is on, every
+ *             successful mld_rollout_select / mld_rollout_select_policy on p leaves its selection there, copied device to device from the call's temporaries
+ *             behind k_plan_select / k_select_inputs on the same stream, and swapped in only when the call has succeeded (a call that fails leaves the
+ *             previous one).  Off (the default): nothing is allocated, no copy is queued.  enable = 0 frees the buffers.
+ *             mld_set_selection puts a caller's own selection there (a filter of the caller's, or the instances a host completion corrected), staged and
+ *             swapped in as mld_set_plan_memory does; policy == NULL: every pick is a sequence.  mld_download_selection reads it: K, the arrays (any NULL)
+ *             and valid (1 / 0).
+ * Validity    the selection is stamped with the batch and the inputs it was made for and is valid while both are unchanged -- the plan memory's rule:
+ *             mld_forecast_from_profiles, a solve, mld_problem_set_cost and mld_upload_instance_cost keep it; mld_upload_batch, mld_select_inputs,
+ *             mld_advance_batch[2] and an advancing step of any entry point (this one included: the selection is consumed) end it.
+ * Source of u  at a selected step, the first that applies, per instance b:
+ *                3  SELECTED  choice[b] >= 0                                         u[b, 0, :] of the kept selection
+ *                1  MEMORY    MLD_FB_MEMORY in fb and 1 <= age[b] <= N_tilde - 1     mem_u[b, age[b], :]                    (mld_sim_step_fallback's rule)
+ *                2  POLICY    MLD_FB_POLICY in fb                                    the resident policy's rule             (mld_sim_step_fallback's rule)
+ *               -1  NONE      none of the above                                      not attempted
+ *             The resident plan is deliberately NOT a source: either the filter judged it (plan_first) or the caller left it out, so an instance without an
+ *             admissible candidate goes to the memory or the policy.  From there on the step is mld_sim_step_resolve's own phases, unchanged.  No channel of
+ *             u is the plan's, so no solved plan is needed, the record's obj / lower_bound / status / nodes are those of mld_sim_step_resolve(u0), and after
+ *             an advancing step the handle is as after mld_sim_step_resolve(u0): new inputs, not solved.
+ * Commit      only with MLD_SIM_ADVANCE, after the step has been queued without an error.  An enabled memory (whether or not fb names it): an instance of
+ *             source 3 with a plan or sequence pick (policy[b] < 0) and K == N_tilde is remembered -- mem_u[b] = u[b], age[b] = 1, read from the source, not
+ *             from the advanced mask, as mld_sim_step_fallback reads it --; every other instance ages as a non-plan source does.  The memory's rows are the
+ *             time slots of a full horizon, so with K != N_tilde nothing is remembered.  The memory follows the advance: it survives the step.  A resident
+ *             policy: u_prev of every ADVANCED instance becomes the u applied.  Without MLD_SIM_ADVANCE nothing is written and the selection stays valid.
+ * Outputs     as mld_sim_step_fallback (u_source 3 / 1 / 2 / -1), plus pick_out (batch): choice[b] where the source is 3, -1 elsewhere.
+ * MLD_SIM_LOG  the record of mld_sim_step_resolve(u0), u_source in the array of mld_download_sim_log_source (3 is new there; mld_sim_log_summary's n_source
+ *             keeps its three columns, a record of source 3 counts in none), and pick in an int array (capacity, batch) beside it, -2 for the records of
+ *             other entry points: mld_download_sim_log_pick copies records [first, first + count).
+ * MLD_ERR_INVALID before anything is queued, nothing changed on either handle: no kept selection; a stale one (the message says what ended it); unknown fb
+ * bits and everything mld_sim_step_fallback refuses for its bits; everything mld_sim_step_resolve(u0) refuses.  mld_set_selection names the instance: K < 1;
+ * choice < -1; policy < -1, or >= 0 without a choice; where choice[b] >= 0, u[b, 0, :] not finite, and for a plan or sequence pick (policy[b] < 0) any row. */
+int mld_keep_selection(mld_problem_t *p, int enable);
+int mld_set_selection(mld_problem_t *p, int K, const int32_t *choice, const int32_t *policy, const double *u);
+int mld_download_selection(mld_problem_t *p, int32_t *K_out, int32_t *choice, int32_t *policy, double *u, int32_t *valid_out);
+int mld_sim_step_selected(mld_problem_t *, mld_problem_t *aux, int fb, const int64_t *act_start, int step, int flags,
+                          double *x_k1_out, double *y_out, uint8_t *cons_out, double *cons_vio_out, int32_t *cons_row_out,
+                          double *v0_out, int32_t *aux_status_out, int32_t *u_source_out, int32_t *n_skipped_out, int32_t *pick_out);
+int mld_download_sim_log_pick(mld_problem_t *, int first, int count, int32_t *pick);
+
 /* ---- MIP start from a baseline rollout ------------------------------------------------------------------------------------------------------------------
  * mld_warm_start_from_previous gives an instance without a usable plan no start (255), and so does the first solve after an upload: exactly the hard
  * instances enter the search cold.  The reference hands its backend whatever values the variables hold (warm_start=True, controllers/controller_base.py:493,

@@ -71,6 +71,7 @@ EXPORTS = ("mld_device_count", "mld_set_device", "mld_last_error", "mld_version"
            "mld_upload_prices", "mld_set_price_cost", "mld_instance_cost_from_prices", "mld_set_stage_cost", "mld_sim_log_cost_begin", "mld_download_sim_log_cost",
            "mld_download_cost_total", "mld_sim_log_summary", "mld_rollout_kpi", "mld_rollout_risk", "mld_rollout_select", "mld_rollout_select_policy",
            "mld_warm_start_from_rollout", "mld_set_rollout_completion", "mld_rollout_completion_stats",
+           "mld_keep_selection", "mld_set_selection", "mld_download_selection", "mld_sim_step_selected", "mld_download_sim_log_pick",
            "mld_comm_unique_id", "mld_comm_init", "mld_gather", "mld_comm_destroy")
 
 
@@ -135,6 +136,11 @@ def load():
     lib.mld_warm_start_from_rollout.argtypes = [C.c_void_p, C.c_void_p, C.c_int, dp, dp, C.c_int, ip, lp]
     lib.mld_set_rollout_completion.argtypes = [C.c_void_p, C.c_int]
     lib.mld_rollout_completion_stats.argtypes = [C.c_void_p, lp]
+    lib.mld_keep_selection.argtypes = [C.c_void_p, C.c_int]
+    lib.mld_set_selection.argtypes = [C.c_void_p, C.c_int, ip, ip, dp]
+    lib.mld_download_selection.argtypes = [C.c_void_p, ip, ip, ip, dp, ip]
+    lib.mld_sim_step_selected.argtypes = list(lib.mld_sim_step_fallback.argtypes) + [ip]
+    lib.mld_download_sim_log_pick.argtypes = [C.c_void_p, C.c_int, C.c_int, ip]
     if int(lib.mld_opts_size()) != C.sizeof(Opts):
         raise MldGpuError("libmldgpu.so was built with another layout of mld_opts (%d bytes, this binding %d): rebuild it (python -m pyhybridcontrol_amd.build)"
                           % (lib.mld_opts_size(), C.sizeof(Opts)))

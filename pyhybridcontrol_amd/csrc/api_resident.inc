@@ -654,8 +654,12 @@ static int aux_fold_check(const char *who, const char *what, const mld_problem_t
  *
  * fc (mld_sim_step_fallback, api_fallback.inc): the plan's step with one kernel in front -- k_fallback_inputs writes every instance's u from the first source
  * that applies (plan, plan memory, policy), its u_source and its attempt byte, which replaces the plan_usable test of the phases (AuxStepArgs::attempt).
- * After an advancing step k_policy_commit (a policy resident) and k_fallback_commit (a memory enabled) move the resident state on. */
-struct FallbackCall { int fb; int32_t *u_source_out; };
+ * After an advancing step k_policy_commit (a policy resident) and k_fallback_commit (a memory enabled) move the resident state on.
+ *
+ * fc->selected (mld_sim_step_selected, api_selected.inc): the same with the kept selection as the first source IN PLACE of the plan -- k_selected_inputs
+ * and k_selected_commit (selected.inc) where the fallback step launches k_fallback_inputs and k_fallback_commit.  No channel of u is the resident plan's, so
+ * the step needs no plan and leaves the handle as mld_sim_step_resolve(u0) does; the memory follows the advance as it follows the fallback step's. */
+struct FallbackCall { int fb; int32_t *u_source_out; bool selected = false; int32_t *pick_out = nullptr; };
 
 /* the (cap, batch) int array beside the log that one kind of step fills (SimLog::aux, SimLog::src): allocated by the first such step that logs, -2 elsewhere */
 static int sim_log_side_array(mld_problem_t *p, DevBuf<int> &arr)
@@ -676,7 +680,8 @@ static int sim_step_resolve_impl(const char *who, bool policy, mld_problem_t *p,
                                  double *v0_out, int32_t *aux_status_out, int32_t *n_skipped_out, const FallbackCall *fc = nullptr)
 {
     if (policy && !p->pol_on) { mld_set_error("%s: no policy uploaded (mld_upload_policy)", who); return MLD_ERR_INVALID; }
-    const bool by_plan = !u0 && !(policy && p->pol_all_ruled);      /* some channel of u is the resident plan's */
+    const bool selected = fc && fc->selected;
+    const bool by_plan = !u0 && !(policy && p->pol_all_ruled) && !selected;      /* some channel of u is the resident plan's */
     std::vector<long long> gmax;
     if (int rc = sim_step_check(p, who, !by_plan, "u0", act_start, step, flags, gmax)) return rc;
     const mld_dims &d = p->model->dims;
@@ -686,19 +691,21 @@ static int sim_step_resolve_impl(const char *who, bool policy, mld_problem_t *p,
     if (u0) for (size_t k = 0; k < (size_t)batch * nu; ++k) if (!std::isfinite(u0[k])) {
         mld_set_error("%s: u0 of instance %zu, input %zu is not finite (%g)", who, k / nu, k % nu, u0[k]); return MLD_ERR_INVALID;
     }
-    if (!(flags & (MLD_SIM_ADVANCE | MLD_SIM_LOG)) && !x_k1_out && !y_out && !cons_out && !cons_vio_out && !cons_row_out && !v0_out && !aux_status_out && !n_skipped_out && !act_start && !(fc && fc->u_source_out)) return MLD_OK;      /* nothing asked for */
+    if (!(flags & (MLD_SIM_ADVANCE | MLD_SIM_LOG)) && !x_k1_out && !y_out && !cons_out && !cons_vio_out && !cons_row_out && !v0_out && !aux_status_out && !n_skipped_out && !act_start && !(fc && (fc->u_source_out || fc->pick_out))) return MLD_OK;      /* nothing asked for */
 
     const hipStream_t sq = p->stream;
     mld_problem::SimLog &L = p->slog;
     if (log) { if (int rc = sim_log_side_array(p, L.aux)) return rc; }      /* every record so far was written by mld_sim_step_batch: "not resolved" */
     if (log && fc) { if (int rc = sim_log_side_array(p, L.src)) return rc; }
+    if (log && selected) { if (int rc = sim_log_side_array(p, L.pick)) return rc; }
     const size_t log_slot = log ? (size_t)L.count * batch : 0;
-    DevBuf<double> d_u, d_v0; DevBuf<unsigned char> d_mask, d_att; DevBuf<int> d_auxst, d_src; DevBuf<long long> d_start;
+    DevBuf<double> d_u, d_v0; DevBuf<unsigned char> d_mask, d_att; DevBuf<int> d_auxst, d_src, d_pick; DevBuf<long long> d_start;
     const bool commit_pol = policy || (fc && p->pol_on), commit_mem = fc && p->mem_on;      /* the resident state an advancing step moves on */
     if (commit_pol) { if (int rc = policy_state_ready(p, who)) return rc; }
     if (commit_mem) { if (int rc = plan_memory_ready(p, who)) return rc; }
     if (u0 || policy || fc) HIP_TRY(d_u.alloc((size_t)batch * std::max(1, nu)));
     if (fc) { HIP_TRY(d_att.alloc(batch)); HIP_TRY(d_src.alloc(batch)); }
+    if (selected) HIP_TRY(d_pick.alloc(batch));
     if (act_start) HIP_TRY(d_start.alloc((size_t)batch * p->pf_groups));
     HIP_TRY(d_v0.alloc((size_t)batch * std::max(1, nv))); HIP_TRY(d_mask.alloc(batch)); HIP_TRY(d_auxst.alloc(batch));
     if (aux && (aux->batch != batch || aux->aux_src_gen != p->batch_gen || aux->aux_own_gen != aux->batch_gen)) {
@@ -715,7 +722,15 @@ static int sim_step_resolve_impl(const char *who, bool policy, mld_problem_t *p,
     else { g.u = p->bat.v; g.u_stride = (size_t)p->n; }
     if (by_plan) { g.status = p->bat.status; g.obj = p->bat.obj; }
     FallbackArgs fa{};
-    if (fc) {
+    SelectedArgs sa{};
+    if (selected) {
+        g.attempt = d_att;
+        sa.batch = batch; sa.nx = nx; sa.nu = nu; sa.N = p->N; sa.fb = fc->fb; sa.K = p->sel.K;
+        sa.choice = p->sel.choice; sa.policy = p->sel.policy; sa.sel_u = p->sel.u;
+        if (p->mem_on) { sa.mem_u = p->mem_u; sa.mem_age = p->mem_age; }
+        if (p->pol_on) { sa.model_idx = p->has_midx ? p->bat.model_idx.get() : nullptr; sa.tab = p->pol_tab; sa.tab_len = (size_t)nu * (nx + POL_TAIL); sa.u_prev = p->pol_uprev; }
+        sa.x0 = p->bat.x0; sa.u = d_u; sa.source = d_src; sa.pick = d_pick; sa.attempt = d_att;
+    } else if (fc) {
         g.attempt = d_att;
         fa.batch = batch; fa.nx = nx; fa.nu = nu; fa.nv = nv; fa.N = p->N; fa.fb = fc->fb;
         fa.status = p->bat.status; fa.obj = p->bat.obj; fa.v = p->bat.v; fa.v_stride = (size_t)p->n;
@@ -737,7 +752,10 @@ static int sim_step_resolve_impl(const char *who, bool policy, mld_problem_t *p,
             hipLaunchKernelGGL(k_policy_inputs, dim3(profile_grid((long long)batch * nu)), dim3(256), 0, sq, pa);
             HIP_TRY(hipGetLastError());
         }
-        if (fc) {
+        if (selected) {
+            hipLaunchKernelGGL(k_selected_inputs, dim3(profile_grid((long long)batch * nu)), dim3(256), 0, sq, sa);
+            HIP_TRY(hipGetLastError());
+        } else if (fc) {
             hipLaunchKernelGGL(k_fallback_inputs, dim3(profile_grid((long long)batch * nu)), dim3(256), 0, sq, fa);
             HIP_TRY(hipGetLastError());
         }
@@ -770,12 +788,15 @@ static int sim_step_resolve_impl(const char *who, bool policy, mld_problem_t *p,
         auto commit = [&]() -> int {
             if (fc && log) HIP_TRY(hipMemcpyAsync(L.src.get() + log_slot, d_src, sizeof(int) * batch, hipMemcpyDeviceToDevice, sq));
             if (fc && fc->u_source_out) HIP_TRY(hipMemcpyAsync(fc->u_source_out, d_src, sizeof(int) * batch, hipMemcpyDeviceToHost, sq));
+            if (selected && log) HIP_TRY(hipMemcpyAsync(L.pick.get() + log_slot, d_pick, sizeof(int) * batch, hipMemcpyDeviceToDevice, sq));
+            if (selected && fc->pick_out) HIP_TRY(hipMemcpyAsync(fc->pick_out, d_pick, sizeof(int) * batch, hipMemcpyDeviceToHost, sq));
             if (commit_pol && advance && nu) {
                 hipLaunchKernelGGL(k_policy_commit, dim3(profile_grid((long long)batch * nu)), dim3(256), 0, sq, (long long)batch, nu, d_mask.get(), d_u.get(), p->pol_uprev.get());
                 HIP_TRY(hipGetLastError());
             }
             if (commit_mem && advance) {
-                hipLaunchKernelGGL(k_fallback_commit, dim3(profile_grid((long long)batch * p->N * nu)), dim3(256), 0, sq, fa);
+                if (selected) hipLaunchKernelGGL(k_selected_commit, dim3(profile_grid((long long)batch * p->N * nu)), dim3(256), 0, sq, sa);
+                else hipLaunchKernelGGL(k_fallback_commit, dim3(profile_grid((long long)batch * p->N * nu)), dim3(256), 0, sq, fa);
                 HIP_TRY(hipGetLastError());
             }
             return MLD_OK;

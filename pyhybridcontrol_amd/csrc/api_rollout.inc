@@ -287,6 +287,15 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
         HIP_TRY(take(d_sadm, sl->admissible, r_inst)); HIP_TRY(take(d_such, sl->u_choice, s_seq)); HIP_TRY(take(d_su0, sl->u0_choice, (size_t)batch * nu));
         HIP_TRY(force(d_schoice, n_pol && (d_such || d_su0), (size_t)batch));      /* k_select_inputs reads the choice */
     }
+    /* keep_selection (mld_keep_selection): the choice and the chosen inputs also stay on the device, in buffers built beside the kept ones and swapped in when
+     * the call has succeeded.  Off: nothing is allocated and no copy is queued */
+    const bool keep_sel = sl && p->sel_keep;
+    mld_problem::Selection kept;
+    if (keep_sel) {
+        auto force = [](auto &buf, size_t count) -> hipError_t { return !buf ? buf.alloc(std::max<size_t>(1, count)) : hipSuccess; };
+        HIP_TRY(force(d_schoice, (size_t)batch)); HIP_TRY(force(d_such, s_seq));
+        HIP_TRY(kept.choice.alloc((size_t)batch)); HIP_TRY(kept.policy.alloc((size_t)batch)); HIP_TRY(kept.u.alloc(std::max<size_t>(1, s_seq)));
+    }
     const size_t warm_len = sc ? (size_t)batch * p->nb : 0;
     const bool keep_rows = sc && sc->keep && p->has_warm;
     std::vector<int32_t> src_host;
@@ -457,6 +466,12 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
             HIP_TRY(hipGetLastError());
             if (n_pol && (si.u_choice || si.u0_choice)) {
                 hipLaunchKernelGGL(k_select_inputs, dim3(sel_grid), dim3(64 * SEL_WAVES), 0, sq, si);
+                HIP_TRY(hipGetLastError());
+            }
+            if (keep_sel) {      /* device to device from the call's temporaries, behind the kernels that wrote them */
+                HIP_TRY(hipMemcpyAsync(kept.choice, d_schoice, sizeof(int) * (size_t)batch, hipMemcpyDeviceToDevice, sq));
+                if (s_seq) HIP_TRY(hipMemcpyAsync(kept.u, d_such, sizeof(double) * s_seq, hipMemcpyDeviceToDevice, sq));
+                hipLaunchKernelGGL(k_selection_policy, dim3(profile_grid((long long)batch)), dim3(256), 0, sq, (long long)batch, sl->P - n_pol, (const int *)d_schoice.get(), kept.policy.get());
                 HIP_TRY(hipGetLastError());
             }
             HIP_TRY(get(sl->choice, d_schoice, (size_t)batch)); HIP_TRY(get(sl->score, d_sscore, (size_t)batch)); HIP_TRY(get(sl->n_admissible, d_snadm, (size_t)batch));
@@ -650,6 +665,10 @@ static int rollout_impl(const char *who, const PolicyCall *pc, mld_problem_t *p,
         if (sc->stats) { sc->stats[0] = (int64_t)T; sc->stats[1] = n[0]; sc->stats[2] = n[1]; sc->stats[3] = n[2]; }
     }
     if (stats) { stats[0] = (int64_t)T; stats[1] = (int64_t)cnt[1]; stats[2] = (int64_t)cnt[2]; stats[3] = (int64_t)cnt[3]; }
+    if (keep_sel) {      /* the call has succeeded: its selection is the kept one, stamped with the inputs it was made for */
+        kept.K = K; kept.batch = batch; kept.has = true; kept.batch_gen = p->batch_gen; kept.chain = p->chain_gen;
+        p->sel = std::move(kept);
+    }
     return MLD_OK;
 }
 

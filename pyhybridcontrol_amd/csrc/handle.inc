@@ -100,6 +100,7 @@ struct mld_problem {
         DevBuf<double> x, v, y, om, x_k1, vio, obj, lb; DevBuf<unsigned char> cons; DevBuf<int> row, status, nodes;
         DevBuf<int> aux;        /* (cap, batch) resolver statuses of the records mld_sim_step_resolve wrote, -2 elsewhere: allocated by the first such step that logs */
         DevBuf<int> src;        /* (cap, batch) u_source of the records mld_sim_step_fallback wrote, -2 elsewhere: allocated by the first such step that logs */
+        DevBuf<int> pick;       /* (cap, batch) the candidate the records of mld_sim_step_selected applied (-1: another source), -2 elsewhere: allocated likewise */
         /* stage cost (mld_sim_log_cost_begin), armed while `cost` is allocated: cost (cap, batch) and price (cap, batch, pr_chan) beside the records, the
          * running total and the count of stepped records per instance, the starts into the price library and the largest of them */
         DevBuf<double> cost, price, total; DevBuf<int> steps; DevBuf<long long> cstart; long long cstart_max = 0;
@@ -122,6 +123,13 @@ struct mld_problem {
     /* device completion of declined rollout trajectories (mld_set_rollout_completion): the sticky mode of this (stepped) handle, and what the last call of the
      * rollout family did -- rounds, trajectories finished on the device, dense solves, trajectories left declined (mld_rollout_completion_stats) */
     int ro_mode = 0; long long ro_stats[4] = {};
+    /* kept selection (mld_keep_selection, mld_set_selection, mld_sim_step_selected): what the last successful mld_rollout_select[_policy] chose -- choice and
+     * policy (batch), u (batch, K, nu) -- or what the caller set.  Stamped with batch_gen and chain_gen: valid while both are unchanged, the plan memory's rule,
+     * so a new forecast, a solve and a new cost keep it and an upload, new inputs and every advance end it.  sel_keep: the sticky switch of the select calls */
+    struct Selection {
+        DevBuf<int> choice, policy; DevBuf<double> u; int K = 0, batch = 0; bool has = false; unsigned long long batch_gen = 0, chain = 0;
+    } sel;
+    bool sel_keep = false;
     long long ho_stats[4] = {};  /* last solve: items published, trees split, trees left unfinished, entries the queue had no room for (always 0: such trees stay unfinished) */
 };
 

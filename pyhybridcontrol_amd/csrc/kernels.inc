@@ -180,6 +180,7 @@ __global__ void __launch_bounds__(256) k_warm_from_rollout(long long batch, int 
 #include "rollout_risk.inc"    // k_rollout_risk (mld_rollout_risk): statistics across a rollout's realisations, a wave per instance
 #include "plan_select.inc"     // k_plan_select (mld_rollout_select): the admissible candidate plan of least objective statistic, a wave per instance
 #include "fallback.inc"        // k_fallback_inputs / k_fallback_commit (mld_sim_step_fallback): the source of u for an instance without a usable plan
+#include "selected.inc"        // k_selected_inputs / k_selected_commit (mld_sim_step_selected): a kept selection as the first source of u
 
 // out[k] = a[k] * b[k]
 __global__ void __launch_bounds__(256) k_scale_vec(size_t count, const double *a, const double *b, double *out)

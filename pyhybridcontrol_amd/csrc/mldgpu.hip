@@ -28,7 +28,7 @@ void mld_set_error(const char *fmt, ...)
 extern "C" {
 
 const char *mld_last_error(void) { return g_err; }
-const char *mld_version(void) { return "mldgpu 0.6 (gfx950, fp64 dense-dictionary cut-and-branch, in-kernel sub-tree hand-off, per-instance linear cost, predicted trajectories, solution quality, resident disturbance profiles, plant step and simulation log, auxiliaries re-derived on device, open-loop rollout, rule-based feedback policies, fallback inputs for instances without a usable plan, resident price profiles, MIP start from a baseline rollout; sizeof(mld_opts) = 64)"; }
+const char *mld_version(void) { return "mldgpu 0.6 (gfx950, fp64 dense-dictionary cut-and-branch, in-kernel sub-tree hand-off, per-instance linear cost, predicted trajectories, solution quality, resident disturbance profiles, plant step and simulation log, auxiliaries re-derived on device, open-loop rollout, rule-based feedback policies, fallback inputs for instances without a usable plan, resident price profiles, MIP start from a baseline rollout, kept selection applied on device; sizeof(mld_opts) = 64)"; }
 
 int mld_device_count(void)
 {
@@ -226,6 +226,7 @@ int mld_condense_f32(mld_model_t *m, int N_tilde, int flags, float *Phi_x, float
 #include "api_policy.inc"       // rule-based feedback policies: tables, resident u_prev, policy rollout (k_rollout_policy) and policy step (k_policy_inputs)
 #include "api_start.inc"        // MIP start from a rollout of the resident forecast (rollout_impl with a StartCall; k_warm_from_rollout)
 #include "api_fallback.inc"     // fallback inputs for instances without a usable plan: plan memory, the fallback step (k_fallback_inputs, k_fallback_commit), its log
+#include "api_selected.inc"     // applying a selection on the device: the kept selection, the selected step (k_selected_inputs, k_selected_commit), its log
 #include "api_prices.inc"       // resident price profiles: the price library, the cost of a batch from price windows, the stage cost in the simulation log
 #include "api_summary.inc"      // campaign KPIs: column statistics of the resident log, reduced on the device
 #include "api_gather.inc"       // RCCL gather

@@ -80,3 +80,58 @@ def commit_np(source, plan_u_all, mem_u, age, N):
     age[older] = np.minimum(age[older] + 1, N)
     age[plan] = 1
     return mem_u, age
+
+
+# ---- applying a kept selection (mld_sim_step_selected, GpuProblem.sim_step(resolve=R, selected=True)) ----------------------------------------------------
+# The selection is the FIRST source, in place of the plan:
+#     3  SELECTED   choice >= 0                                     sel_u[b, 0]: step 0 of the chosen sequence, or the chosen rule's step 0
+#     1  MEMORY, 2  POLICY, -1  NONE                                as above
+# The plan is deliberately not a source: the filter judged it or the caller left it out.  After an advancing step a plan or sequence pick (policy < 0) of
+# K == N_tilde steps becomes the memory (age 1); every other instance ages as a non-plan source does, and with K != N_tilde nothing is remembered (the
+# memory's rows are the time slots of a full horizon).
+SELECTED = 3
+
+
+def choose_selected_np(choice, sel_u, mem_u, age, fb, P=None, midx=None, x=None, u_prev=None):
+    """the source, the input and the pick of one selected step: choice (B,) ints, -1 = none; sel_u (B, K, nu) the kept selection's inputs (row 0 read
+    where choice >= 0); mem_u, age, fb, P, midx, x, u_prev as choose_np's.  Returns (u (B, nu), source (B,) int32, pick (B,) int32: the choice where the
+    source is SELECTED, -1 elsewhere)."""
+    choice = np.asarray(choice)
+    if choice.ndim != 1 or not np.issubdtype(choice.dtype, np.integer):
+        raise ValueError("choice has shape %s and dtype %s, expected (B,) integers" % (choice.shape, choice.dtype))
+    B = choice.shape[0]
+    sel_u = np.asarray(sel_u, dtype=np.float64)
+    if sel_u.ndim != 3 or sel_u.shape[0] != B or sel_u.shape[1] < 1:
+        raise ValueError("sel_u has shape %s, expected (%d, K >= 1, nu)" % (sel_u.shape, B))
+    if np.any(choice < -1):
+        raise ValueError("choice of instance %d is %d (-1 = none, or a candidate >= 0)" % (int(np.flatnonzero(choice < -1)[0]), int(choice[choice < -1][0])))
+    picked = choice >= 0
+    if not np.all(np.isfinite(sel_u[picked, 0])):
+        raise ValueError("sel_u of instance %d, step 0 is not finite" % int(np.flatnonzero(picked & ~np.isfinite(sel_u[:, 0]).all(axis=1))[0]))
+    u, source = choose_np(np.zeros(B, bool), np.zeros((B, sel_u.shape[2])), mem_u, age, fb, P=P, midx=midx, x=x, u_prev=u_prev)
+    source[picked] = SELECTED
+    u = np.where(picked[:, None], sel_u[:, 0], u)
+    pick = np.where(picked, choice, -1).astype(np.int32)
+    return np.ascontiguousarray(u), source, pick
+
+
+def commit_selected_np(source, sel_policy, sel_u, mem_u, age, N):
+    """the plan memory after an advancing selected step: source (B,) of choose_selected_np, sel_policy (B,) the kept selection's policy (-1: a plan or
+    sequence pick), sel_u (B, K, nu), mem_u (B, N, nu), age (B,).  Returns new (mem_u, age (int32)); the arguments are left as they are."""
+    source = np.asarray(source)
+    B = source.shape[0]
+    sel_policy = np.asarray(sel_policy)
+    if sel_policy.shape != (B,):
+        raise ValueError("sel_policy has shape %s, expected (%d,)" % (sel_policy.shape, B))
+    sel_u = np.asarray(sel_u, dtype=np.float64)
+    if sel_u.ndim != 3 or sel_u.shape[0] != B:
+        raise ValueError("sel_u has shape %s, expected (%d, K, nu)" % (sel_u.shape, B))
+    mem_u = np.array(mem_u, dtype=np.float64).reshape(B, N, -1)
+    age = np.array(age, dtype=np.int32)
+    kept = (source == SELECTED) & (sel_policy < 0) & (sel_u.shape[1] == N)
+    if kept.any():
+        mem_u[kept] = sel_u.reshape(mem_u.shape)[kept]
+    older = ~kept & (age >= 1)
+    age[older] = np.minimum(age[older] + 1, N)
+    age[kept] = 1
+    return mem_u, age

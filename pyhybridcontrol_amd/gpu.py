@@ -210,6 +210,27 @@ def _completes(host):
     return deco
 
 
+def _keeps(fn):
+    """adds keep=False to a select entry: True switches mld_keep_selection on for the call, so that its choice stays on the device as the kept selection, and
+    corrects the kept arrays where the method finished instances on the host; False switches it off (and frees what an earlier keep=True left).  The wrapped
+    method's signature stays what it was.  A select entry that hands over to another one (select_plan_policies() without policies) is one call: the outer keep
+    holds."""
+    @functools.wraps(fn)
+    def wrapper(self, *a, keep=False, **kw):
+        if getattr(self, "_sel_in_call", False):
+            return fn(self, *a, **kw)
+        self._keep_selection(keep)
+        self._sel_in_call = True
+        try:
+            out = fn(self, *a, **kw)
+        finally:
+            self._sel_in_call = False
+        if keep and out["stats"].get("finished_on_host", 0) > 0:      # the device holds what the method returns
+            self.set_selection(out["choice"], out["u"], out.get("policy"))
+        return out
+    return wrapper
+
+
 class GpuProblem(object):
     """mld_problem_t: condensed constraint maps of a GpuModel + cost + solver workspace, on device."""
 
@@ -724,7 +745,7 @@ class GpuProblem(object):
         check(_lib.load().mld_sim_log_count(self._h, C.byref(n), C.byref(cap)))
         return int(n.value), int(cap.value)
 
-    def sim_step(self, v0=None, act_start=None, step=0, actual=None, advance=True, log=None, outputs=False, resolve=None, u0=None, policy=False, fallback=None):
+    def sim_step(self, v0=None, act_start=None, step=0, actual=None, advance=True, log=None, outputs=False, resolve=None, u0=None, policy=False, fallback=None, selected=False):
         """one plant step of the resident batch on device (mld_sim_step_batch): the reference's lsim_k(x_k, v_k=, omega_k) with the whole step-0 slice --
         of the last solve's plans (v0=None; instances without a usable plan are skipped and counted) or the caller's v0 (batch, nv) / (nv,) -- under the
         forecast's step 0 or, with actual, the element `step` of the realised series at act_start (batch, n_groups) / (n_groups,) of the resident profile
@@ -743,9 +764,21 @@ class GpuProblem(object):
         row for the current time (plan_memory()), then the resident policy's rule (upload_policy, every channel ruled); with neither it is skipped as
         before.  fallback=() allows no source: the step of sim_step(resolve=R).  outputs=True additionally returns u_source (batch) int32: 0 plan,
         1 memory, 2 policy, -1 none.  An advancing step remembers the usable plans in an enabled memory, ages the others, and moves a resident policy's
-        u_prev of every advanced instance to the u applied."""
+        u_prev of every advanced instance to the u applied.
+        selected=True (with resolve, without u0 / policy): the kept selection as the FIRST source, in place of the plan (mld_sim_step_selected, kernels
+        k_selected_inputs / k_selected_commit) -- what select_plan(..., keep=True) / select_plan_policies(..., keep=True) chose, or set_selection().  An
+        instance with a choice takes its u[b, 0]; one without (choice -1) goes to the sources `fallback` names (none without the argument), never to the
+        plan.  u_source: 3 selected, 1 memory, 2 policy, -1 none; outputs=True additionally returns pick (batch) int32, the candidate applied or -1.  An
+        advancing step remembers a chosen plan or sequence of K == N_tilde steps in an enabled memory (age 1) and ages the others, keeps the memory valid,
+        moves a resident policy's u_prev to the u applied, and consumes the selection; the log says 3 in sim_log_source() and the candidate in
+        sim_log_pick().  No plan is needed; the handle ends as after sim_step(resolve=R, u0=...)."""
         d, B = self.model.dims, self.batch
         nv = self.model.nv
+        if selected:
+            if resolve is None or u0 is not None or policy or v0 is not None:
+                raise ValueError("selected=True goes with resolve alone (no v0, no u0, no policy=True): the kept selection supplies u")
+            if fallback is None:
+                fallback = ()
         if policy and resolve is None:
             raise ValueError("policy=True goes with resolve (a BatchAuxResolver re-derives the auxiliaries of the rule's u)")
         fb = None
@@ -791,12 +824,14 @@ class GpuProblem(object):
             if fb is not None:
                 if outputs:
                     out["u_source"] = np.zeros(B, np.int32)
-                check(_lib.load().mld_sim_step_fallback(
+                    if selected:
+                        out["pick"] = np.zeros(B, np.int32)
+                check((_lib.load().mld_sim_step_selected if selected else _lib.load().mld_sim_step_fallback)(
                     self._h, aux, fb, st.ctypes.data_as(C.POINTER(C.c_int64)) if st is not None else None, int(step), flags,
                     _lib.dptr(out["x_k1"]) if out else None, _lib.dptr(out["y"]) if out else None,
                     out["cons"].ctypes.data_as(C.POINTER(C.c_uint8)) if out else None, _lib.dptr(out["cons_vio"]) if out else None,
                     ip(out["cons_row"]) if out else None, _lib.dptr(out["v0"]) if out else None, ip(out["aux_status"]) if out else None,
-                    ip(out["u_source"]) if out else None, C.byref(skipped)))
+                    ip(out["u_source"]) if out else None, C.byref(skipped), *([ip(out["pick"]) if out else None] if selected else [])))
             else:
                 check((_lib.load().mld_sim_step_policy if policy else _lib.load().mld_sim_step_resolve)(
                     self._h, aux, _lib.dptr(u0), st.ctypes.data_as(C.POINTER(C.c_int64)) if st is not None else None, int(step), flags,
@@ -1133,6 +1168,7 @@ class GpuProblem(object):
         return out
 
     @_completes(True)
+    @_keeps
     def select_plan(self, resolve, selector, candidates=None, plan_first=False, K=None, omega_seq=None, start=None, step=0, cost_w=None, kpis=None,
                     price_start=None, vio_tol=1e-6, min_complete=None, per_candidate=False, per_trajectory=False):
         """choose, per instance, among P candidate input sequences by their rollout risk, on device (mld_rollout_select; kernels k_rollout_cand /
@@ -1149,7 +1185,11 @@ class GpuProblem(object):
         with kpis, kpi (batch, P, S, n_kpi).  The figures are those of simlog.select_plan_np on that risk, bit for bit.  Trajectories the device's LDS solver
         declined are finished on the host as rollout() finishes them: the instances they belong to take every candidate's risk from rollout() itself and
         their choice from select_plan_np.  complete="device" (rollout()'s): they are finished on the device before k_rollout_risk and k_plan_select read
-        them, and the host route is never entered."""
+        them, and the host route is never entered.
+        keep=True (a keyword of the wrapper, like complete=): the choice and the chosen inputs also stay on the device as the kept selection
+        (mld_keep_selection; selection() reads it), which sim_step(resolve=R, selected=True) applies; instances finished on the host are corrected there
+        (set_selection), so the device holds what this method returns.  keep=False (the default) allocates nothing, queues no extra copy and drops a
+        selection an earlier keep=True left."""
         from . import simlog
         d, B, nv = self.model.dims, self.batch, self.model.nv
         nx, nu, nw, ny = d["nx"], d["nu"], d["nomega"], d["ny"]
@@ -1272,6 +1312,7 @@ class GpuProblem(object):
         return out
 
     @_completes(False)
+    @_keeps
     def select_plan_policies(self, resolve, selector, policies=None, u_prev=None, candidates=None, plan_first=False, K=None, omega_seq=None, start=None, step=0,
                              cost_w=None, kpis=None, price_start=None, vio_tol=1e-6, min_complete=None, per_candidate=False, per_trajectory=False):
         """select_plan() with closed-loop rule policies among the candidates (mld_rollout_select_policy; kernels k_rollout_cand_policy /
@@ -1285,7 +1326,8 @@ class GpuProblem(object):
         sequence trajectory, -1 where it did not end 0.  A risk column of source switches is accepted.  Nothing is finished on the host on this route: a
         trajectory the LDS solver declines stays 2, counts as n_declined and, with min_complete = S, makes its candidate inadmissible;
         stats["finished_on_host"] is 0.  complete="device" (rollout()'s): such a trajectory is finished on the device before the risk is reduced, so no
-        candidate is lost to a decline; complete="host" is refused.  policies None or empty: select_plan() itself, its code path and its result."""
+        candidate is lost to a decline; complete="host" is refused.  policies None or empty: select_plan() itself, its code path and its result.  keep: select_plan()'s; the kept policy (batch)
+        is the returned one."""
         if policies is None or not len(policies):
             if u_prev is not None:
                 raise ValueError("u_prev given without policies (an open-loop candidate has no previous input)")
@@ -1395,6 +1437,49 @@ class GpuProblem(object):
                 out["kpi"] = kp
         return out
 
+    # -- the kept selection ---------------------------------------------------------------------------------
+    def _keep_selection(self, keep):
+        """the sticky switch of the select calls as this call wants it; switching it off frees what it kept (a set_selection() of the caller's stays)"""
+        if bool(keep) != getattr(self, "_sel_keep", False):
+            check(_lib.load().mld_keep_selection(self._h, 1 if keep else 0))
+            self._sel_keep = bool(keep)
+
+    def selection(self):
+        """the kept selection (mld_download_selection): dict(K, choice (batch,) int32, policy (batch,) int32, u (batch, K, nu), valid) -- what the last
+        select_plan(..., keep=True) / select_plan_policies(..., keep=True) chose, or set_selection() set; valid: it was made for the current inputs, so
+        sim_step(resolve=R, selected=True) takes it.  The arrays are None where the batch it belonged to is gone."""
+        B, nu = self.batch, self.model.dims["nu"]
+        K, valid = C.c_int32(0), C.c_int32(0)
+        check(_lib.load().mld_download_selection(self._h, C.byref(K), None, None, None, C.byref(valid)))
+        out = dict(K=int(K.value), choice=None, policy=None, u=None, valid=bool(valid.value))
+        arr = dict(choice=np.zeros(B, np.int32), policy=np.zeros(B, np.int32), u=np.zeros((B, out["K"], nu)))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        if _lib.load().mld_download_selection(self._h, None, ip(arr["choice"]), ip(arr["policy"]), _lib.dptr(arr["u"]), None) == 0:
+            out.update(arr)
+        elif out["valid"]:
+            check(-1)
+        return out
+
+    def set_selection(self, choice, u, policy=None):
+        """a selection of the caller's as the kept one (mld_set_selection): choice (batch,) ints, -1 = none; u (batch, K, nu) the chosen inputs, row 0
+        finite where there is a choice and every row for a plan or sequence pick; policy (batch,) ints or None (every pick a sequence).  It is made for
+        the current inputs, and sim_step(resolve=R, selected=True) applies it like a kept one."""
+        B, nu = self.batch, self.model.dims["nu"]
+        choice = np.asarray(choice)
+        if choice.shape != (B,) or not np.issubdtype(choice.dtype, np.integer):
+            raise ValueError("choice has shape %s and dtype %s, expected (%d,) integers" % (choice.shape, choice.dtype, B))
+        u = np.asarray(u, dtype=np.float64)
+        if u.ndim != 3 or u.shape[0] != B or u.shape[2] != nu:
+            raise ValueError("u has shape %s, expected (%d, K, %d)" % (u.shape, B, nu))
+        if policy is not None:
+            policy = np.asarray(policy)
+            if policy.shape != (B,) or not np.issubdtype(policy.dtype, np.integer):
+                raise ValueError("policy has shape %s and dtype %s, expected (%d,) integers" % (policy.shape, policy.dtype, B))
+            policy = np.ascontiguousarray(policy, dtype=np.int32)
+        choice, u = np.ascontiguousarray(choice, dtype=np.int32), np.ascontiguousarray(u)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None
+        check(_lib.load().mld_set_selection(self._h, u.shape[1], ip(choice), ip(policy), _lib.dptr(u)))
+
     def sim_log(self, first=0, count=None):
         """records [first, first + count) of the resident log (mld_download_sim_log; count=None: all from first): dict of arrays (count, batch, width) --
         x, v, y, omega, x_k1, cons (bool), cons_vio, cons_row, obj, lower_bound, status, nodes.  simlog.to_mld_sim_log turns one instance into the
@@ -1441,6 +1526,19 @@ class GpuProblem(object):
             raise ValueError("sim_log_source: first = %d lies beyond the %d logged steps" % (first, K + first))
         out = np.zeros((K, self.batch), np.int32)
         check(_lib.load().mld_download_sim_log_source(self._h, first, K, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
+    def sim_log_pick(self, first=0, count=None):
+        """the candidate applied per record and instance (mld_download_sim_log_pick), (count, batch) int32: what sim_step(resolve=R, selected=True)
+        returned as pick (the choice where the source is 3, -1 elsewhere), -2 for the records any other step wrote"""
+        first = int(first)
+        if count is None:
+            count = self.sim_log_count()[0] - first
+        K = int(count)
+        if K < 0:
+            raise ValueError("sim_log_pick: first = %d lies beyond the %d logged steps" % (first, K + first))
+        out = np.zeros((K, self.batch), np.int32)
+        check(_lib.load().mld_download_sim_log_pick(self._h, first, K, out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out
 
     def sim_log_summary(self, kpis, first=0, count=None, vio_tol=1e-6):
